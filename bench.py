@@ -7,7 +7,12 @@ Workload (BASELINE.json configs[1], reading 2a of SURVEY.md section 8d):
 One step = one pass of the hot path over operands already resident in HBM.
 Metric: GNZ/s = nonzeros of A streamed per second (whole job, all ranks).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--config 2|4]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--config 2|4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline, roofline of the timed steps).
+`--full` adds everything that takes runs of its own: the extras (other operations, sizes and entry points), the CPU
+baseline against the oracle, and at N > 1 the `multi_gpu` diagnostics.  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (float64; at most 64 MB in all, see dump_outputs()).
 
 N > 1 runs one rank per GPU under torch.distributed.run (RCCL): either the caller starts it that way (RANK / WORLD_SIZE
 in the environment), or `python bench.py --gpus N` starts its own ranks -- the parent spawns
@@ -92,7 +97,17 @@ def parse():
     p.add_argument("--no-extras", action="store_true")
     p.add_argument("--no-sparse-crossprod", action="store_true",
                    help="skip extras.sparse_crossprod (unary / SVT x SVT crossprod at the reference's published shapes and at config-2 scale)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure what the headline does not need: the extras, the CPU baseline "
+                        "and (N > 1) the multi_gpu diagnostics; --no-extras / --no-cpu-baseline / --no-sparse-crossprod "
+                        "leave parts of it out")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the result(s) of the last timed step as DIR/<name>.npy (float64, rank 0, at most 64 MB in all)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    if a.warmup < 0:
+        p.error("--warmup must not be negative")
     c = CONFIGS[a.config]
     for k in ("nrow", "ncol", "density", "K"):
         if getattr(a, k) is None:
@@ -339,6 +354,28 @@ def sparse_crossprod_extras(dev, A_big, timed):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as <outdir>/<name>.npy in float64.  When they hold more than DUMP_BUDGET_BYTES (less
+    1 MB for the headers) together, each keeps its share as a fixed, seeded sample of its rows (sorted), and the indices of
+    those rows go beside it as <name>_rows.npy (float64, exact)."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    budget = DUMP_BUDGET_BYTES - (1 << 20)                  # (room for the .npy headers)
+    for name, v in arrays.items():
+        if total > budget and v.ndim >= 1 and v.shape[0] > 1:
+            allowance = v.nbytes * budget // total
+            row_bytes = v.nbytes // v.shape[0]
+            n = max(1, min(v.shape[0], allowance // (row_bytes + 8)))
+            rows = np.sort(np.random.default_rng(12345).choice(v.shape[0], n, replace=False))
+            np.save(os.path.join(outdir, name + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(outdir, name + ".npy"), v)
+
+
 def launch_ranks(a) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as a FRESH child process
     (`python -m torch.distributed.run`; never an exec, and nothing in this process has touched the GPU yet), pass
@@ -554,8 +591,15 @@ def main():
     kern_ms = float(np.mean([e0.elapsed_time(e1) for i, (e0, e1) in enumerate(evs) if i % ev_every == ev_every - 1]))
     res_t = result()
     checksum = [float(res_t.sum().item()), float(res_t.abs().sum().item())]
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: crossprod(A, Y) as R returns it (ncol x K; the
+        # device holds it as K x ncol, i.e. column-major ncol x K), and colSums(A) at config 4
+        outs = {"crossprod": res_t.t().cpu().numpy()}
+        if with_colsums and csum[0] is not None:
+            outs["colSums"] = csum[0].cpu().numpy()
+        dump_outputs(a.dump_outputs, outs)
     diag = None
-    if coll and a.path == "pbc":
+    if a.full and coll and a.path == "pbc":
         # (a failure here must not leave the other ranks inside a collective: let it end the process with a
         # non-zero status -- torch.distributed.run then ends the job -- rather than be caught on one rank)
         diag = multi_gpu_diagnostics(a, dist, par, dev, sc, A, Y, step, finish, kern_ms, elapsed / a.steps * 1e3,
@@ -637,7 +681,7 @@ def main():
             res["config"]["spare_cus"] = a.spare_cus
         if spare_tuned is not None:
             res["config"]["spare_cus_chosen_in_warmup_from_ms_per_step"] = {str(k): v for k, v in spare_tuned.items()}
-    if world == 1 and not coll and not a.no_extras and a.config == 2:
+    if a.full and world == 1 and not coll and not a.no_extras and a.config == 2:
         def timed(fn, reps=5):
             fn(); torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -857,7 +901,7 @@ def main():
             ex["sparse_crossprod"]["crossprod(A)_config2_scale"]["host_result_bit_symmetric"] = bool(np.array_equal(hsq, hsq.T))
             del hsq
         del hcp, hri, hv, hy, hout, hview
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         ns = max(1, min(ncol, int(1e8 / max(nnz / ncol, 1))))   # <= 1e8 nz x K: 10-30 core-seconds
         cb, ref_out, ns = cpu_baseline(col_ptr, row_idx, val, Y, lrow, K, ns)
         # the timed GPU result must agree with the CPU oracle on the sample

@@ -5,32 +5,88 @@ into a shared library together with
   * tests/r_api_standin/r_standin.c -- a functional test-only stand-in for the part of R's C API it uses
     (fake SEXPs, attributes, a COUNTED protection stack, guarded R_alloc() blocks, error() as a longjmp,
     warning() into a log),
-  * the reference helper files the glue calls that compile as they are, straight from the read-only mount
-    (src/argcheck_utils.c, src/Rvector_utils.c, src/Rvector_summarization.c -- hidden visibility +
-    --gc-sections: only what the glue reaches is kept),
+  * the reference helper files the glue calls that compile as they are (src/argcheck_utils.c,
+    src/Rvector_utils.c, src/Rvector_summarization.c -- hidden visibility + --gc-sections: only what the glue
+    reaches is kept),
   * tests/r_api_standin/glue_env.c -- the helpers that are `static` in the reference (its maintainer makes
     them extern for the glue), the leaf constructor, and recording stubs for the `_cpu` bodies,
 and binds the svt_* symbols the glue dlsym()s to the CPU oracle's ABI (tests/r_api_standin/svt_over_oracle.c).
 `GlueDispatcher` then offers the `.Call`-level interface of sparsearray_amd/_dispatch.py THROUGH the
 registered C_* names, so that `Session(GlueDispatcher(...))` pushes the golden cases through the glue.
-Nothing here travels to the GPU box as a product path; /root/reference must be present.
+Nothing here travels to the GPU box as a product path.  What needs the reference's sources or headers (the glue,
+glue_env.c, the helper files) is compiled into oracle/_ref/ (oracle/Makefile, `ref`; oracle/ref.py finds the tree)
+by build(), and again here when oracle/_ref/ is missing or out of date; the harness links it from there.
 """
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import os
+import shutil
 import subprocess
 import warnings
 
 import numpy as np
 
+from oracle.ref import REF_BUILD, build_ref
 from sparsearray_amd.api import OPCODES, SparseArrayError
 from sparsearray_amd.svt import SVT_SparseArray
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SRC = "/root/reference/src"
 STANDIN = os.path.join(ROOT, "tests", "r_api_standin")
 REF_HELPERS = ("argcheck_utils", "Rvector_utils", "Rvector_summarization")
+
+
+def _ref_current() -> bool:
+    """oracle/_ref/ was compiled from a reference tree and from the files of this repository as they are now."""
+    inputs = os.path.join(REF_BUILD, "INPUTS")
+    if not (os.path.exists(os.path.join(REF_BUILD, "SOURCE")) and os.path.exists(inputs)):
+        return False
+    for line in open(inputs):
+        digest, rel = line.split()
+        src = os.path.normpath(os.path.join(ROOT, "oracle", rel))
+        if not os.path.exists(src) or hashlib.sha256(open(src, "rb").read()).hexdigest() != digest:
+            return False
+    return True
+
+
+_UNAVAILABLE = []
+
+
+def ref_build_unavailable():
+    """Why the glue cannot be built here (None: it can): no gcc, or no oracle/_ref/ from a reference tree.  A missing
+    or out-of-date oracle/_ref/ is compiled again first (oracle/ref.py), where a tree of the reference can be read."""
+    if not _UNAVAILABLE:
+        why = None
+        if shutil.which("gcc") is None:
+            why = "needs gcc"
+        else:
+            if not _ref_current():
+                build_ref()
+            if not os.path.exists(os.path.join(REF_BUILD, "SOURCE")):
+                why = ("oracle/_ref/ holds no build of the reference's glue pieces and no SparseArray source tree was "
+                       "found to compile it from (SPARSEARRAY_SRC)")
+        _UNAVAILABLE.append(why)
+    return _UNAVAILABLE[0]
+
+
+def ref_file(name: str) -> str:
+    """oracle/_ref/<name>, checked against the repository files it was compiled from (oracle/_ref/INPUTS)."""
+    path = os.path.join(REF_BUILD, name)
+    if not os.path.exists(path):
+        log = path + ".log"
+        raise RuntimeError(f"{path} is missing (build() compiles it)" +
+                           (f":\n{open(log).read()}" if os.path.exists(log) else ""))
+    inputs = os.path.join(REF_BUILD, "INPUTS")
+    if not os.path.exists(inputs):
+        raise RuntimeError(f"{inputs} is missing: build() did not finish oracle/_ref/")
+    for line in open(inputs):
+        digest, rel = line.split()
+        src = os.path.normpath(os.path.join(ROOT, "oracle", rel))
+        if hashlib.sha256(open(src, "rb").read()).hexdigest() != digest:
+            raise RuntimeError(f"oracle/_ref/ was compiled from another {os.path.relpath(src, ROOT)}: run build() again")
+    return path
+
 
 LGLSXP, INTSXP, REALSXP, STRSXP, VECSXP = 10, 13, 14, 16, 19
 _NP = {LGLSXP: np.int32, INTSXP: np.int32, REALSXP: np.float64}
@@ -40,8 +96,9 @@ def build(outdir: str) -> tuple[str, str]:
     """Returns (harness .so, shim .so).  Raises CalledProcessError with the compiler's text on failure."""
     oracle_dir = os.path.join(ROOT, "oracle")
     subprocess.check_call(["make", "-s", "-C", oracle_dir])
-    inc = ["-I", STANDIN, "-I", REF_SRC, "-I", os.path.join(ROOT, "include"), "-I", oracle_dir]
-    objs = []
+    inc = ["-I", STANDIN, "-I", os.path.join(ROOT, "include"), "-I", oracle_dir]
+    # compiled by build() with the reference's headers: the glue, its environment, the reference helper files
+    objs = [ref_file(n + ".o") for n in ("svt_hip_glue", "glue_env") + REF_HELPERS]
 
     def cc(src, extra=()):
         obj = os.path.join(outdir, os.path.basename(src)[:-2] + ".o")
@@ -50,11 +107,7 @@ def build(outdir: str) -> tuple[str, str]:
         if res.returncode != 0:
             raise RuntimeError(f"{' '.join(cmd)}\n{res.stderr}")
         objs.append(obj)
-    cc(os.path.join(ROOT, "integration", "svt_hip_glue.c"), ["-Wall", "-Werror=implicit-function-declaration"])
     cc(os.path.join(STANDIN, "r_standin.c"), ["-Wall"])
-    cc(os.path.join(STANDIN, "glue_env.c"), ["-Wall"])
-    for h in REF_HELPERS:       # the reference's files, read where they lie; nothing of them is kept in the repository
-        cc(os.path.join(REF_SRC, h + ".c"), ["-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-w"])
     harness = os.path.join(outdir, "libglue_harness.so")
     shim = os.path.join(outdir, "libsvt_shim.so")
     link = ["gcc", "-shared", "-o", harness, *objs, "-Wl,--gc-sections", "-Wl,-z,defs", "-L", oracle_dir, "-lsvt_oracle",

@@ -1,8 +1,8 @@
 """integration/svt_hip_glue.c EXECUTED (build container, CPU).
 
 The glue -- the 20 registered `.Call` entry points an R maintainer adds to the reference's src/ -- is compiled
-with the reference helper files it calls (read straight from /root/reference/src; the test skips where that
-mount is absent, i.e. on the GPU box) against a FUNCTIONAL test-only stand-in for R's C API
+with the reference helper files it calls (compiled into oracle/_ref/ where a tree of the reference is at hand;
+the test skips where there is neither that nor a tree) against a FUNCTIONAL test-only stand-in for R's C API
 (tests/r_api_standin/r_standin.c: fake SEXPs, counted PROTECT stack, guarded R_alloc(), error() / warning()
 capture), its svt_* lookups bound to the CPU oracle's ABI (same svt_view layout), and driven through the
 registered C_* names with every golden case of tests/golden/ (inputs of the reference's own testthat files):
@@ -13,16 +13,15 @@ What this is NOT: a build of the reference's compute path, or an oracle -- expec
 tests/golden/golden.json.
 """
 import os
-import shutil
 
 import numpy as np
 import pytest
 
+import glue_harness
 from helpers import check_case, golden_cases
 
-REF_SRC = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SRC) or shutil.which("gcc") is None,
-                                reason="needs the reference's headers / helper files and gcc (build container only)")
+pytestmark = pytest.mark.skipif(glue_harness.ref_build_unavailable() is not None,
+                                reason=str(glue_harness.ref_build_unavailable()))
 
 CASES = golden_cases()
 

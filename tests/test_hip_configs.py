@@ -310,7 +310,8 @@ def test_bench_strong_scaling_rehearsal_same_problem(hip):
     product as --gpus 1: the global matrix is defined by row blocks that do not depend on the number of
     ranks, the all-reduced result has the same checksum, and the line names the workload and the scaling."""
     torch.cuda.empty_cache()
-    common = ["--nrow", "262144", "--ncol", "4000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+    common = ["--nrow", "262144", "--ncol", "4000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--no-extras"]
     one = _bench_line(common, 1, 0)
     two = _bench_line(common + ["--spare-cus", "32", "--compare-reducers"], 2, 29700 + os.getpid() % 200)
     assert two["config"]["spare_cus"] == 32                   # CUs left to the collective
@@ -351,7 +352,8 @@ def test_bench_starts_its_own_ranks(hip):
     torch.cuda.empty_cache()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    common = ["--nrow", "262144", "--ncol", "4000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+    common = ["--nrow", "262144", "--ncol", "4000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--no-extras"]
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device"] + common
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]

@@ -40,7 +40,8 @@ def test_bench_collective_path_over_rccl_one_rank(hip):
     all-reduce alone / product alone / spare-CU variant) with backend nccl and one rank; same product as the plain
     one-GPU line."""
     torch.cuda.empty_cache()
-    common = ["--nrow", "262144", "--ncol", "4000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+    common = ["--nrow", "262144", "--ncol", "4000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--no-extras"]
 
     def line(extra, port):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra, env=_env(port),
