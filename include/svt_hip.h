@@ -23,9 +23,9 @@
  *         error(), like the reference's own error() calls
  *         (e.g. src/SparseMatrix_mult.c:943-966).
  *   > 0   (SVT_UNSUPPORTED = 1) not supported HERE: the device kernels do not take
- *         this operand or operation -- 2^31 nonzeros or more in a transposition /
- *         aperm / colMedians / the second operand of the row-panel product (an SVT's
- *         total count is unbounded, R/SVT_SparseArray-class.R:13-23), too many strata
+ *         this operand or operation -- 2^31 nonzeros or more in an aperm that moves
+ *         the rows (perm[1] != 1) or in the second operand of the row-panel product
+ *         (an SVT's total count is unbounded, R/SVT_SparseArray-class.R:13-23), too many strata
  *         for the row-statistics counters, an opcode the R API never sends
  *         (RANGE, SUM_X_X2, VAR2, SD2 for col / row statistics).  The reason is in
  *         svt_last_error(); nothing the caller relies on has been written.  The R glue
@@ -426,10 +426,23 @@ int svt_set_max_threads(int nthread);
    R/SparseMatrix-mult.R:165-206).  The caller provides the output arrays
    (out_col_ptr int64[nrow+1], out_row_idx int32[nnz], out_val like A's) and
    svt_dev_transpose_ws_bytes() bytes of workspace; entries of every output leaf
-   come out in ascending offset order. */
+   come out in ascending offset order.
+   Operands of 2^31 nonzeros or more take the boxed driver: runs of consecutive columns of at
+   most 2^30 nonzeros (or one column) are transposed one after the other by the routes below the
+   limit and copied to their place -- bit for bit the result of the unboxed routes.  The cuts
+   between boxes are found by a search over the offsets and read back: such a call synchronises
+   the stream once.  Its workspace grows with nrow and the box size, not with nnz. */
 size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz);
 int svt_dev_transpose(const svt_dev_csc *A, int64_t *out_col_ptr, int32_t *out_row_idx,
 		      void *out_val, void *ws, size_t ws_bytes, void *stream);
+/* Box limit of the transposition, process-wide (tests, timing): n > 0 sends every operand of more
+   than n nonzeros through the boxed driver with boxes of at most n nonzeros (or one column);
+   n <= 0 restores the default (boxes only from 2^31 nonzeros on, of at most 2^30).  Every call
+   reads it once; a workspace sized under another setting may be too small (the call says so). */
+void svt_dev_set_box_nnz(int64_t n);
+/* Calls of this process that took the boxed driver (t(), and through it rowMedians, tcrossprod,
+   %*% ...); reset != 0 zeroes the count and returns the count before. */
+int64_t svt_dev_boxed_calls(int reset);
 
 /* x %*% y for two sparse operands, y much sparser than a dense matrix (the `svt %*% svt2` of BASELINE config 3):
    out[r + k * ldo] = sum over the nonzeros (j, b) of column k of B of b * A[r, j] -- for finite operands the sum
@@ -499,7 +512,8 @@ void svt_sparse_crossprod_set_cost(double factor);
    (caller-allocated); 1 <= ndim <= 8.  Asynchronous on `stream`, except for permutations whose new
    leading axis is an old outer axis and whose second axis is the old rows (aperm(x, c(3, 1, 2))): the
    choice between the per-slab kernel and the key sort reads one counter back and synchronises the
-   stream once. */
+   stream once.  Operands of 2^31 nonzeros or more: leaf-preserving permutations (perm[1] == 1)
+   only; the others answer > 0. */
 size_t svt_dev_aperm_ws_bytes(int64_t nnz, int ndim, const int64_t *dim);
 int svt_dev_aperm(const svt_dev_csc *A, int ndim, const int64_t *dim, const int *perm,
 		  int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val,

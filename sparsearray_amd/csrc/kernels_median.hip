@@ -342,8 +342,10 @@ int launch_colmedians(const int64_t *col_ptr, const void *val, int Rtype, int64_
 {
 	if (ncol <= 0)
 		return 0;
-	if (nnz > 0x7FFFFFFFLL || ncol > 0x7FFFFFFFLL)
-		return svt_set_unsupported("colMedians: more than 2^31-1 nonzeros or columns");
+	// (positions and counts are 64-bit throughout; ranks inside a column are < nrow < 2^31, so msel_select's 32-bit
+	// ranks and LDS counters hold any column -- the operand's total count is not limited)
+	if (ncol > 0x7FFFFFFFLL)
+		return svt_set_unsupported("colMedians: more than 2^31-1 columns");
 	int64_t *cnt_neg = (int64_t *) (((uintptr_t) ws + 255) & ~(uintptr_t) 255);
 	int64_t *cnt_pos = cnt_neg + ncol, *cnt_nan = cnt_pos + ncol;
 	int *todo = (int *) (cnt_nan + ncol);

@@ -15,6 +15,11 @@
 
 #include <string.h>
 
+#include <algorithm>
+#include <atomic>
+#include <utility>
+#include <vector>
+
 #include "svt_scan.h"
 
 #include "svt_sort.h"
@@ -891,6 +896,265 @@ int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void 
 }
 
 // ---------------------------------------------------------------------------
+// t(A) past 2^31 nonzeros: the boxed driver.  The routes above count positions in 32 bits; an SVT's nonzero count is
+// unbounded (src/SVT_SparseArray_class.c:200-218).  The operand is cut into BOXES -- runs of consecutive columns, each
+// holding at most `box` nonzeros, or a single column (<= nrow < 2^31 entries) -- and every box is transposed by the
+// unchanged routes above as an operand of its own, into a box-sized temporary, from which a placement pass copies it to
+// its final place:
+//   count   one pass over row_idx: the length of every output leaf (a row histogram, privatised in LDS when nrow
+//           allows), scanned in place into out_ptr (launch_exclusive_scan_i64); fill[L] = 0 (placed so far).
+//   cuts    one search per multiple p of `box` over col_ptr: the column holding position p; boxes end on both sides
+//           of it, so every other box lies strictly between two such columns and holds fewer than `box` nonzeros.
+//           Columns W = 2^20 apart are cut the same way (a run of empty columns cannot make the box's rebased
+//           col_ptr larger than the workspace; t(A) has ncol < 2^31 rows, so at most 2048 such cuts).  The cuts and col_ptr there are read back: one stream sync per call.
+//   per box rebase its slice of col_ptr (-col_ptr[c0]); the route (bucketed or key sort) on (nrow x width, nnz_b);
+//           placement: one wavefront per output leaf L copies the box's run of L to out_ptr[L] + fill[L], adding c0
+//           to every row index (the box-local column), and advances fill[L].
+// Why the result is exact: the entries of output leaf L are ordered by their old column.  Boxes are consecutive column
+// ranges, processed in order, so every box contributes ONE contiguous run to every output leaf, and the runs come in
+// box order = column order; inside a run the route orders them.  Only copies happen: the result is bit for bit the
+// unboxed route's (and out_ptr is the same scan of the same counts).
+// Workspace: the route's at max(box, nrow) nonzeros, the box temporary (nrow + 1 pointers, max(box, nrow) entries), the
+// rebased col_ptr (W + 1), fill and scan scratch (O(nrow)), the cut table (O(nnz / box + 2048)) -- not O(nnz).
+// ---------------------------------------------------------------------------
+static std::atomic<int64_t> g_box_nnz{0};
+static std::atomic<int64_t> g_boxed_calls{0};
+
+void box_nnz_set(int64_t n) { g_box_nnz.store(n > 0 ? n : 0); }
+int64_t box_nnz_get(void) { return g_box_nnz.load(); }
+int64_t boxed_calls(int reset) { return reset ? g_boxed_calls.exchange(0) : g_boxed_calls.load(); }
+
+#define BOX_DEFAULT ((int64_t) 1 << 30)
+#define BOX_W ((int64_t) 1 << 20)
+#define BOX_HIST_NT 1024
+#define BOX_HIST_LDS 32768            // rows counted in LDS (128 KB of 32-bit counters); more: memory atomics
+
+static bool box_taken(int64_t nnz, int64_t box_limit)
+{
+	return box_limit > 0 ? nnz > box_limit : nnz >= ((int64_t) 1 << 31);
+}
+
+static int64_t box_size(int64_t box_limit)
+{
+	return box_limit > 0 ? (box_limit < 0x7FFFFFFFLL ? box_limit : 0x7FFFFFFFLL) : BOX_DEFAULT;
+}
+
+struct BoxLayout {
+	int64_t bsz, bmax, W, npts_max;
+	size_t pts, fill, scan, bcp, bptr, bidx, bval, route, total;
+};
+
+static BoxLayout box_layout(int64_t nrow, int64_t nnz, int64_t box_limit)
+{
+	BoxLayout L;
+	L.bsz = box_size(box_limit);
+	L.bmax = L.bsz > nrow ? L.bsz : nrow;                   // a box: <= bsz nonzeros, or one column
+	if (L.bmax > nnz) L.bmax = nnz > 0 ? nnz : 1;
+	L.W = BOX_W;
+	// (ncol = nrow of t(A) < 2^31: at most 2^31 / W cuts by width)
+	L.npts_max = (nnz + L.bsz - 1) / L.bsz + (((int64_t) 1 << 31) + L.W - 1) / L.W + 1;
+	size_t o = 0;
+	L.pts = o;   o += t2_a((size_t) L.npts_max * 3, 8);
+	L.fill = o;  o += t2_a((size_t) nrow + 1, 8);
+	L.scan = o;  o += t2_a(exclusive_scan_ws_bytes(nrow + 1), 1);
+	L.bcp = o;   o += t2_a((size_t) L.W + 1, 8);
+	L.bptr = o;  o += t2_a((size_t) nrow + 1, 8);
+	L.bidx = o;  o += t2_a((size_t) L.bmax, 4);
+	L.bval = o;  o += t2_a((size_t) L.bmax, 8);
+	L.route = o; o += transpose_ws_bytes(nrow, L.bmax);
+	L.total = o + 256;
+	return L;
+}
+
+// out[r] += entries of row r (out zeroed by the caller); grid-stride over all positions
+__global__ void __launch_bounds__(BOX_HIST_NT)
+box_row_hist_kernel(const int32_t *__restrict__ row_idx, int64_t nnz, int64_t nrow, int use_lds,
+		    unsigned long long *__restrict__ cnt)
+{
+	extern __shared__ uint32_t h[];
+	const bool lds = use_lds != 0;                  // (nrow <= BOX_HIST_LDS counters of dynamic LDS)
+	if (lds) {
+		for (int64_t r = threadIdx.x; r < nrow; r += BOX_HIST_NT) h[r] = 0;
+		__syncthreads();
+	}
+	const int64_t stride = (int64_t) gridDim.x * BOX_HIST_NT * 4;
+	for (int64_t k0 = (int64_t) blockIdx.x * BOX_HIST_NT * 4 + threadIdx.x; k0 < nnz; k0 += stride) {
+		int32_t r[4];
+#pragma unroll
+		for (int u = 0; u < 4; u++) r[u] = k0 + u * BOX_HIST_NT < nnz ? row_idx[k0 + u * BOX_HIST_NT] : -1;
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			if (r[u] < 0) continue;
+			if (lds) atomicAdd(&h[r[u]], 1u);
+			else atomicAdd(&cnt[r[u]], 1ull);
+		}
+	}
+	if (lds) {
+		__syncthreads();
+		for (int64_t r = threadIdx.x; r < nrow; r += BOX_HIST_NT)
+			if (h[r]) atomicAdd(&cnt[r], (unsigned long long) h[r]);
+	}
+}
+
+// Cut point i: i < nk -- the column holding position (i + 1) * box (last c with col_ptr[c] <= p); else the column
+// (i - nk + 1) * W.  pts[3 i ..] = (c, col_ptr[c], col_ptr[c + 1]).
+__global__ void box_cut_kernel(const int64_t *__restrict__ col_ptr, int64_t ncol, int64_t nk, int64_t box,
+			       int64_t W, int64_t npts, int64_t *__restrict__ pts)
+{
+	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= npts) return;
+	int64_t c;
+	if (i < nk) {
+		const int64_t p = (i + 1) * box;
+		int64_t lo = 0, hi = ncol - 1;
+		while (lo < hi) {
+			const int64_t mid = (lo + hi + 1) >> 1;
+			if (col_ptr[mid] <= p) lo = mid; else hi = mid - 1;
+		}
+		c = lo;
+	} else {
+		c = (i - nk + 1) * W;
+	}
+	pts[3 * i] = c;
+	pts[3 * i + 1] = col_ptr[c];
+	pts[3 * i + 2] = col_ptr[c + 1];
+}
+
+__global__ void box_rebase_kernel(const int64_t *__restrict__ col_ptr, int64_t c0, int64_t w, int64_t base,
+				  int64_t *__restrict__ bcp)
+{
+	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i <= w) bcp[i] = col_ptr[c0 + i] - base;
+}
+
+// One wavefront per output leaf: the box's run of leaf L goes to out_ptr[L] + fill[L], its row indices (box-local
+// columns) shifted by the box's first column.  Coalesced: consecutive lanes on consecutive entries of one run.
+template <typename T>
+__global__ void __launch_bounds__(256)
+box_place_kernel(const int64_t *__restrict__ bptr, const int32_t *__restrict__ bidx, const T *__restrict__ bval,
+		 int64_t nleaf, int32_t add, const int64_t *__restrict__ out_ptr, int64_t *__restrict__ fill,
+		 int32_t *__restrict__ out_idx, T *__restrict__ out_val)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t L = (int64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (L >= nleaf) return;
+	const int64_t b = bptr[L], n = bptr[L + 1] - b;
+	if (n == 0) return;
+	const int64_t dst = out_ptr[L] + fill[L];
+	for (int64_t k0 = 0; k0 < n; k0 += 256) {
+		int32_t r[4];
+		T v[4];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int64_t k = k0 + u * 64 + lane;
+			if (k < n) { r[u] = bidx[b + k]; v[u] = bval[b + k]; }
+		}
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int64_t k = k0 + u * 64 + lane;
+			if (k < n) { out_idx[dst + k] = r[u] + add; out_val[dst + k] = v[u]; }
+		}
+	}
+	if (lane == 0) fill[L] += n;
+}
+
+size_t transpose_ws_bytes_box(int64_t nrow, int64_t nnz, int64_t box_limit)
+{
+	if (!box_taken(nnz, box_limit))
+		return transpose_ws_bytes(nrow, nnz);
+	return box_layout(nrow, nnz, box_limit).total;
+}
+
+static int launch_transpose_boxed(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
+				  int64_t nrow, int64_t ncol, int64_t nnz, int64_t *out_ptr, int32_t *out_idx,
+				  void *out_val, void *ws, int64_t box_limit, hipStream_t s)
+{
+	if (ncol > 0x7FFFFFFFLL)
+		return svt_set_error("svt_dev_transpose: more than 2^31-1 columns");
+	const BoxLayout Ly = box_layout(nrow, nnz, box_limit);
+	char *w = (char *) ws;
+	int64_t *pts = (int64_t *) (w + Ly.pts), *fill = (int64_t *) (w + Ly.fill);
+	int64_t *bcp = (int64_t *) (w + Ly.bcp), *bptr = (int64_t *) (w + Ly.bptr);
+	int32_t *bidx = (int32_t *) (w + Ly.bidx);
+	void *bval = w + Ly.bval, *rws = w + Ly.route;
+	const size_t esz = Rtype == SVT_REALSXP ? 8 : 4;
+	// lengths of the output leaves -> out_ptr
+	HIP_TRY(hipMemsetAsync(out_ptr, 0, (size_t) (nrow + 1) * 8, s));
+	HIP_TRY(hipMemsetAsync(fill, 0, (size_t) nrow * 8, s));
+	// (rows counted in LDS where the 128 KB of counters can be had, else memory atomics; the kernel decides by nrow)
+	bool lds = nrow <= BOX_HIST_LDS;
+	if (lds && hipFuncSetAttribute((const void *) box_row_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+				       BOX_HIST_LDS * 4) != hipSuccess) {
+		(void) hipGetLastError();
+		lds = false;
+	}
+	int64_t nbh = (nnz + BOX_HIST_NT * 4 - 1) / (BOX_HIST_NT * 4);
+	if (nbh > 1024) nbh = 1024;                         // (a workgroup counts < 2^32 entries per row up to 4e12 nonzeros)
+	hipLaunchKernelGGL(box_row_hist_kernel, dim3((unsigned) nbh), dim3(BOX_HIST_NT), lds ? (size_t) nrow * 4 : 0, s,
+			   row_idx, nnz, nrow, lds ? 1 : 0, (unsigned long long *) out_ptr);
+	HIP_TRY(hipGetLastError());
+	if (launch_exclusive_scan_i64(out_ptr, nrow + 1, w + Ly.scan, s))
+		return -1;
+	// the cuts, read back once
+	const int64_t nk = (nnz - 1) / Ly.bsz, nw = (ncol - 1) / Ly.W, npts = nk + nw;
+	if (npts > Ly.npts_max)
+		return svt_set_error("svt_dev_transpose: internal error (box cuts)");
+	std::vector<int64_t> hp((size_t) npts * 3 + 1);
+	if (npts > 0) {
+		hipLaunchKernelGGL(box_cut_kernel, dim3((unsigned) ((npts + 255) / 256)), dim3(256), 0, s, col_ptr, ncol, nk,
+				   Ly.bsz, Ly.W, npts, pts);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(hp.data(), pts, (size_t) npts * 24, hipMemcpyDeviceToHost, s));
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	std::vector<std::pair<int64_t, int64_t>> bd;        // (column, col_ptr there): box boundaries
+	bd.reserve((size_t) npts * 2 + 2);
+	bd.push_back({0, 0});
+	bd.push_back({ncol, nnz});
+	for (int64_t i = 0; i < npts; i++) {
+		bd.push_back({hp[3 * i], hp[3 * i + 1]});
+		bd.push_back({hp[3 * i] + 1, hp[3 * i + 2]});
+	}
+	std::sort(bd.begin(), bd.end());
+	bd.erase(std::unique(bd.begin(), bd.end()), bd.end());
+	const unsigned nbp = (unsigned) ((nrow + 3) / 4);
+	for (size_t b = 0; b + 1 < bd.size(); b++) {
+		const int64_t c0 = bd[b].first, c1 = bd[b + 1].first, p0 = bd[b].second, nb = bd[b + 1].second - p0;
+		if (nb == 0)
+			continue;
+		if (nb > Ly.bmax || c1 - c0 > Ly.W)
+			return svt_set_error("svt_dev_transpose: internal error (box of %lld nonzeros, %lld columns)",
+					     (long long) nb, (long long) (c1 - c0));
+		hipLaunchKernelGGL(box_rebase_kernel, dim3((unsigned) ((c1 - c0 + 1 + 255) / 256)), dim3(256), 0, s,
+				   col_ptr, c0, c1 - c0, p0, bcp);
+		if (launch_transpose(bcp, row_idx + p0, (const char *) val + (size_t) p0 * esz, Rtype, nrow, c1 - c0, nb,
+				     bptr, bidx, bval, rws, s))
+			return -1;
+		if (Rtype == SVT_REALSXP)
+			hipLaunchKernelGGL(box_place_kernel<double>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const double *) bval,
+					   nrow, (int32_t) c0, out_ptr, fill, out_idx, (double *) out_val);
+		else
+			hipLaunchKernelGGL(box_place_kernel<int32_t>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const int32_t *) bval,
+					   nrow, (int32_t) c0, out_ptr, fill, out_idx, (int32_t *) out_val);
+		HIP_TRY(hipGetLastError());
+	}
+	g_boxed_calls++;
+	return 0;
+}
+
+// t(A) with the box limit of the call (read once by the caller: box_nnz_get()): the boxed driver past it, else the
+// routes above exactly as they are.
+int launch_transpose_box(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
+			 int64_t nrow, int64_t ncol, int64_t nnz, int64_t *out_ptr, int32_t *out_idx,
+			 void *out_val, void *ws, int64_t box_limit, hipStream_t s)
+{
+	if (!box_taken(nnz, box_limit))
+		return launch_transpose(col_ptr, row_idx, val, Rtype, nrow, ncol, nnz, out_ptr, out_idx, out_val, ws, s);
+	return launch_transpose_boxed(col_ptr, row_idx, val, Rtype, nrow, ncol, nnz, out_ptr, out_idx, out_val, ws,
+				      box_limit, s);
+}
+
+// ---------------------------------------------------------------------------
 // N-d aperm (C_aperm_SVT, src/SparseArray_aperm.c:148-930).  The device layout
 // knows leaves only, so the caller passes the array's dims.  Every nonzero gets
 // the 64-bit key  new_leaf * new_dim0 + new_row  (its linear index in the
@@ -1354,6 +1618,12 @@ static size_t aperm_general_bytes(int64_t nnz, const int64_t *dim, int ndim, siz
 
 size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim)
 {
+	if (nnz >= ((int64_t) 1 << 31)) {
+		// only the leaf-preserving form takes such an operand: the scratch of a scan over the leaf counts
+		double nl = 1.0;
+		for (int a = 1; a < ndim; a++) nl *= (double) (dim[a] > 0 ? dim[a] : 1);
+		return (nl < 2147483646.0 ? exclusive_scan_ws_bytes((int64_t) nl + 1) : 0) + 256;
+	}
 	size_t need = aperm_ws_core(nnz, dim, ndim);
 	{
 		// (a step of the general form may itself fall back to the forms that aperm_ws_core() sizes: the intermediates
@@ -1413,8 +1683,6 @@ static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const 
 {
 	if (ndim < 1 || ndim > 8)
 		return svt_set_error("aperm: between 1 and 8 dimensions are supported");
-	if (nnz >= ((int64_t) 1 << 31))
-		return svt_set_unsupported("aperm: more than 2^31-1 nonzeros");
 	ApermDims d;
 	d.ndim = ndim;
 	bool seen[8] = {false, false, false, false, false, false, false, false};
@@ -1464,6 +1732,9 @@ static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const 
 		HIP_TRY(hipGetLastError());
 		return 0;
 	}
+	// (the leaf-preserving form above counts positions in 64 bits; the others do not)
+	if (nnz >= ((int64_t) 1 << 31))
+		return svt_set_unsupported("aperm: more than 2^31-1 nonzeros");
 	// 3-d: c(2,3,1) and c(3,2,1) as c(2,1,3) followed by c(1,3,2) / c(3,1,2) (see aperm_via_bytes)
 	if (!nested && ndim == 3 && ((perm[0] == 1 && perm[1] == 2 && perm[2] == 0) ||
 			  (perm[0] == 2 && perm[1] == 1 && perm[2] == 0 && dim[2] <= 1024))) {

@@ -196,6 +196,14 @@ int launch_gram_mirror(double *out, int64_t n, int64_t ld, hipStream_t s);
 int launch_gram_pairs(const int64_t *a_ptr, int64_t nrow, double *out, hipStream_t s);
 
 size_t transpose_ws_bytes(int64_t nrow, int64_t nnz);
+// the same with the boxed driver past the box limit (box_nnz_get(), read once per call and passed down)
+size_t transpose_ws_bytes_box(int64_t nrow, int64_t nnz, int64_t box_limit);
+int launch_transpose_box(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
+			 int64_t nrow, int64_t ncol, int64_t nnz, int64_t *out_ptr, int32_t *out_idx,
+			 void *out_val, void *ws, int64_t box_limit, hipStream_t s);
+void box_nnz_set(int64_t n);
+int64_t box_nnz_get(void);
+int64_t boxed_calls(int reset);
 int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
 		     int64_t nrow, int64_t ncol, int64_t nnz, int64_t *out_ptr, int32_t *out_idx,
 		     void *out_val, void *ws, hipStream_t s);

@@ -812,16 +812,27 @@ extern "C" int svt_dev_rowsums_prepared(const svt_dev_csc *A, int na_rm, int64_t
 
 extern "C" size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz)
 {
-	return transpose_ws_bytes(nrow, nnz);
+	return transpose_ws_bytes_box(nrow, nnz, box_nnz_get());
 }
 
 static int dev_transpose_impl(const svt_dev_csc *A, int64_t *out_col_ptr, int32_t *out_row_idx,
 				 void *out_val, void *ws, size_t ws_bytes, void *stream)
 {
-	if (ws_bytes < transpose_ws_bytes(A->nrow, A->nnz))
+	const int64_t box = box_nnz_get();                  // (once: the size check and the launch agree)
+	if (ws_bytes < transpose_ws_bytes_box(A->nrow, A->nnz, box))
 		return svt_set_error("svt_dev_transpose: workspace too small");
-	return launch_transpose(A->col_ptr, A->row_idx, A->val, A->Rtype, A->nrow, A->ncol, A->nnz,
-				out_col_ptr, out_row_idx, out_val, ws, (hipStream_t) stream);
+	return launch_transpose_box(A->col_ptr, A->row_idx, A->val, A->Rtype, A->nrow, A->ncol, A->nnz,
+				    out_col_ptr, out_row_idx, out_val, ws, box, (hipStream_t) stream);
+}
+
+extern "C" void svt_dev_set_box_nnz(int64_t n)
+{
+	box_nnz_set(n);
+}
+
+extern "C" int64_t svt_dev_boxed_calls(int reset)
+{
+	return boxed_calls(reset);
 }
 extern "C" int svt_dev_transpose(const svt_dev_csc *A, int64_t *out_col_ptr, int32_t *out_row_idx,
 				 void *out_val, void *ws, size_t ws_bytes, void *stream)
@@ -1502,6 +1513,12 @@ static int dev_crossprod_sparse_on(const svt_dev_csc *T, const svt_dev_csc *Y, b
 
 static int dev_crossprod_sparse(const CscGuard &X, const svt_dev_csc *Y, bool sym, double *O, int64_t ldo, double dense_ops)
 {
+	// An operand of 2^31 nonzeros or more keeps the dense-buffer route, which needs no t(x): the transposition takes
+	// such operands through its boxed driver, but a t(x) of that size (plus its workspace) for the sparse-aware kernel
+	// is a separate, unmeasured choice.  (The fixed bound, not the box limit of svt_dev_set_box_nnz: forcing boxes in a
+	// test changes no route.)
+	if (X.h->nnz >= ((int64_t) 1 << 31))
+		return 1;
 	int own_T = 1;
 	svt_dev_csc *T = transposed_for(X, &own_T);
 	OwnedCsc TX = { T, own_T };
@@ -1599,17 +1616,18 @@ static svt_dev_csc *dev_transposed(const svt_dev_csc *A)
 	T->Rtype = A->Rtype; T->owned = 1; T->na_background = A->na_background;
 	T->nrow = A->ncol; T->ncol = A->nrow; T->nnz = A->nnz;
 	const size_t n = A->nnz > 0 ? (size_t) A->nnz : 1;
+	const int64_t box = box_nnz_get();
 	DevBuf ws;
 	if (hipMalloc((void **) &T->col_ptr, ((size_t) T->ncol + 1) * 8) != hipSuccess ||
 	    hipMalloc((void **) &T->row_idx, n * 4) != hipSuccess ||
 	    hipMalloc(&T->val, n * elt_size(A->Rtype)) != hipSuccess ||
-	    ws.alloc(transpose_ws_bytes(A->nrow, A->nnz))) {
+	    ws.alloc(transpose_ws_bytes_box(A->nrow, A->nnz, box))) {
 		svt_set_error("device allocation failed (transposed operand)");
 		svt_release(T);
 		return NULL;
 	}
-	if (launch_transpose(A->col_ptr, A->row_idx, A->val, A->Rtype, A->nrow, A->ncol, A->nnz,
-			     T->col_ptr, T->row_idx, T->val, ws.p, 0) ||
+	if (launch_transpose_box(A->col_ptr, A->row_idx, A->val, A->Rtype, A->nrow, A->ncol, A->nnz,
+				 T->col_ptr, T->row_idx, T->val, ws.p, box, 0) ||
 	    hipDeviceSynchronize() != hipSuccess) {
 		if (svt_last_error()[0] == '\0') svt_set_error("device transposition failed");
 		svt_release(T);

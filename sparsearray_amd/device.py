@@ -86,6 +86,10 @@ def _lib():
         lib.svt_dev_transpose_ws_bytes.restype = c_size_t
         lib.svt_dev_transpose_ws_bytes.argtypes = [c_int64, c_int64]
         lib.svt_dev_transpose.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.svt_dev_set_box_nnz.argtypes = [c_int64]
+        lib.svt_dev_set_box_nnz.restype = None
+        lib.svt_dev_boxed_calls.argtypes = [c_int]
+        lib.svt_dev_boxed_calls.restype = c_int64
         lib.svt_dev_aperm_ws_bytes.restype = c_size_t
         lib.svt_dev_aperm_ws_bytes.argtypes = [c_int64, c_int, c_void_p]
         lib.svt_dev_aperm.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -242,6 +246,17 @@ def aperm_route_counts(reset=False) -> dict:
     _lib().svt_dev_aperm_route_counts.restype = None
     _lib().svt_dev_aperm_route_counts(buf, int(bool(reset)))
     return dict(zip(names, (int(x) for x in buf)))
+
+
+def set_box_nnz(n: int = 0) -> None:
+    """Box limit of the device transposition (svt_dev_set_box_nnz): n > 0 sends every operand of more than n
+    nonzeros through the boxed driver with boxes of at most n; n <= 0 restores the default (2^31 / 2^30)."""
+    _lib().svt_dev_set_box_nnz(int(n))
+
+
+def boxed_calls(reset=False) -> int:
+    """Transpositions of this process that took the boxed driver (svt_dev_boxed_calls)."""
+    return int(_lib().svt_dev_boxed_calls(int(bool(reset))))
 
 
 def trim_layout_pool() -> None:
