@@ -295,9 +295,13 @@ int svt_dev_crossprod_csc_dense(const svt_dev_csc *A, const void *Y,
  * sparse operand -- the device analogue of the reference's per-call leaf
  * "preprocessing" (src/SparseMatrix_mult.c:632-724) -- and a kernel that keeps
  * row panels of Y in LDS and per-column partial sums in registers.
- *   CBW   columns per wavefront (<= 64), WPB wavefronts per workgroup, logR = log2(rows per
- *         panel).  (0, 0, 0) = chosen by the operand's density: (40, 16, 7), the LDS-DMA kernel,
- *         or, below ~0.25 % density, (40, 4, 9), the gather kernels (rows of Y straight from L2).
+ *   CBW   columns per wavefront, WPB wavefronts per workgroup, logR = log2(rows per panel).
+ *         Two families, both with 1 <= CBW <= 40: (CBW, 16, 7), the LDS-DMA kernel, and
+ *         (CBW, 4, 9 .. 15), the gather kernels (rows of Y straight from L2).  (0, 0, 0) = chosen
+ *         by the operand's density: (40, 16, 7), or, below ~0.25 % density, (40, 4, 9 .. 11).
+ *         Any other layout is refused (NULL, svt_last_error()).  An LDS-DMA layout of an operand
+ *         with fewer than 256 (or 2^28 and more) rows is built without records: its products run
+ *         the general kernels of svt_dev_crossprod_csc_dense(), with their results.
  * svt_dev_pbc_build() allocates and synchronises (not for the launch path).
  * svt_dev_crossprod_pbc() has the semantics and the out-indexing of
  * svt_dev_crossprod_csc_dense() (A is needed for the general path that

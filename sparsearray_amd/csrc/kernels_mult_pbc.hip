@@ -16,7 +16,8 @@
 //                in registers (CBW/16 register-indexable vectors, contiguous)
 //   tile(g, p) = the nonzeros of group g in row panel p, in CSC order
 //                (column-major, rows ascending), stored contiguously and
-//                zero-padded to a multiple of PBC_BATCH records of 16 bytes:
+//                zero-padded to whole batches of records (gather layouts: PBC_BATCH
+//                records of 16 bytes; LDS-DMA layouts: 8 records of 12 bytes, pbc1_store):
 //                { u32 8*(row - p*R)   byte offset of the row in an LDS column,
 //                  u32 2*(local column) VGPR index of the partial sum,
 //                  f64 value }
@@ -26,10 +27,9 @@
 //   tile order = (group, panel): everything one wavefront reads is one
 //                sequential stream
 //   tile_ptr[g*npanels + p] = first record of tile (g, p)
-// A workgroup = WPB wavefronts; grid = (row split, 64-wide tile of dense
-// columns, column block).  Row splits give >= 256
-// workgroups; their partial results are summed in a fixed order by
-// pbc_reduce_kernel (deterministic, no atomics).
+// A workgroup = WPB wavefronts, one per column group; its work is a (row split,
+// tile of dense columns, column block).  Row splits fill the chip; their partial
+// results are summed in a fixed order by pbc_reduce_kernel (deterministic, no atomics).
 //
 // Special values: the kernel is the reference's *finite* path
 // (_dotprod_doubleSV_finite_doubles, src/SparseVec_dotprod.c:28-43).  While
@@ -49,17 +49,15 @@
 
 #include "svt_scan.h"
 
-#include <vector>
-
 typedef double d16 __attribute__((ext_vector_type(16)));
 typedef double d8 __attribute__((ext_vector_type(8)));
 
 struct svt_dev_pbc {
 	int64_t nrow, ncol, nnz, nrec;
 	int CBW, WPB, logR;
-	int fmt;               // record format: 0 = 16-byte records, batches of 4 (register-staged
-	                       // kernel); 1 = 12-byte records, batches of 8 (LDS-DMA kernel)
-	int gather;            // format 0 with tall panels, read by crossprod_pbc_gather_kernel (very sparse operands)
+	int kind;              // pbc_kind(): PBC_KIND_DMA = 12-byte records, batches of 8 (LDS-DMA kernel);
+	                       // PBC_KIND_GATHER = 16-byte records, batches of 4, tall panels (gather kernels,
+	                       // very sparse operands); PBC_KIND_NONE = no records (general kernels)
 	int64_t ngroups, nblocks, npanels;
 	uint4 *rec;            // [nrec] 16-byte records
 	int64_t *tile_ptr;     // [ngroups*npanels + 1]
@@ -111,7 +109,6 @@ static int g_pbc_nsplit = 0;
 static int g_pbc_stagger = 7;
 static int g_pbc_ahead10 = 20;
 #else
-static constexpr int g_pbc_debug = 0;
 static constexpr int g_pbc_nsplit = 0;
 static constexpr int g_pbc_stagger = 7;   // DMA issue: wavefronts 4g..4g+3 after batch g of their tile (patterns 12 and 15 time the same in the bench, tools/debug/r2_rot.sh)
 static constexpr int g_pbc_ahead10 = 20;  // record touch: look-ahead in tenths of a tile
@@ -131,7 +128,6 @@ __device__ inline int64_t lower_bound_row(const int32_t *__restrict__ row, int64
 }
 
 #define PBC_BATCH 4        // records per scalar-load batch; tiles are padded to it
-#define PBC_AHEAD 2        // panels of look-ahead of the record prefetch into L2
 #define PBC_SLACK 320       // zeroed records past the end: look-ahead loads and L2 touches land here
 #define PBC_TP_PAD 8        // tile_ptr entries past the end (= nrec): the kernels read up to [p + 3]
 
@@ -617,7 +613,7 @@ extern "C" void svt_dev_pbc_release(svt_dev_pbc *h)
 extern "C" size_t svt_dev_pbc_bytes(const svt_dev_pbc *h)
 {
 	if (h == NULL) return 0;
-	return (size_t) h->nrec * (h->fmt == 1 ? 12 : 16) + PBC_SLACK * 16 +
+	return (size_t) h->nrec * (h->kind == PBC_KIND_DMA ? 12 : 16) + PBC_SLACK * 16 +
 	       (size_t) (h->ngroups * h->npanels + 1 + PBC_TP_PAD) * 8 + (size_t) h->ncol * 4;
 }
 
@@ -638,6 +634,18 @@ void pbc_auto_layout(int64_t nrow, int64_t ncol, int64_t nnz, int *CBW, int *WPB
 	} else { *WPB = 16; *logR = 7; }
 }
 
+// Which product kernel reads the layout (CBW, WPB, logR) of an operand of nrow rows.  Both keep at most
+// 40 columns per wavefront (16 + 16 + 8).  The LDS-DMA kernel stages the last, partial panel as rows
+// nrow-128 .. nrow-1 and a row split through 32-bit byte offsets (8 bytes per row per dense column).
+int pbc_kind(int64_t nrow, int CBW, int WPB, int logR)
+{
+	if (CBW < 1 || CBW > 40)
+		return PBC_KIND_BAD;
+	if (WPB == 16 && logR == 7)                     // below 256 rows and from 2^28 on: the general kernels
+		return nrow >= 256 && nrow < ((int64_t) 1 << 28) ? PBC_KIND_DMA : PBC_KIND_NONE;
+	return WPB == 4 && logR >= 9 && logR <= 15 ? PBC_KIND_GATHER : PBC_KIND_BAD;
+}
+
 // Not on the launch path: allocates, synchronises.
 extern "C" svt_dev_pbc *svt_dev_pbc_build(const svt_dev_csc *A, int CBW, int WPB, int logR)
 {
@@ -647,16 +655,18 @@ extern "C" svt_dev_pbc *svt_dev_pbc_build(const svt_dev_csc *A, int CBW, int WPB
 	}
 	if (CBW == 0 && WPB == 0 && logR == 0)
 		pbc_auto_layout(A->nrow, A->ncol, A->nnz, &CBW, &WPB, &logR);
-	if (CBW <= 0 || CBW > 64 || WPB <= 0 || WPB > 16 || logR < 4 || logR > 15) {
-		svt_set_error("svt_dev_pbc_build: bad parameters");
+	const int kind = pbc_kind(A->nrow, CBW, WPB, logR);
+	if (kind == PBC_KIND_BAD) {
+		svt_set_error("svt_dev_pbc_build: no product kernel reads the layout (CBW %d, WPB %d, logR %d): "
+			      "(CBW <= 40, 16, 7) for the LDS-DMA kernel or (CBW <= 40, 4, 9 .. 15) for the gather kernels",
+			      CBW, WPB, logR);
 		return NULL;
 	}
 	svt_dev_pbc *h = (svt_dev_pbc *) calloc(1, sizeof(*h));
 	h->nrow = A->nrow; h->ncol = A->ncol; h->nnz = A->nnz;
 	h->CBW = CBW; h->WPB = WPB; h->logR = logR;
-	// the LDS-DMA kernel wants 16 wavefronts, 128-row panels, <= 40 columns each
-	h->fmt = (WPB == 16 && logR == 7 && CBW <= 40 && A->nrow >= 256 && g_pbc_debug != 9) ? 1 : 0;
-	h->gather = (h->fmt == 0 && WPB == 4 && logR >= 9) ? 1 : 0;
+	h->kind = kind;
+	const bool dma = kind == PBC_KIND_DMA;
 	const int64_t CB = (int64_t) CBW * WPB;
 	h->nblocks = (A->ncol + CB - 1) / CB;
 	h->ngroups = h->nblocks * WPB;                // one group per wavefront
@@ -676,7 +686,7 @@ extern "C" svt_dev_pbc *svt_dev_pbc_build(const svt_dev_csc *A, int CBW, int WPB
 		  pbc_alloc((void **) &h->col_has_na, (size_t) (A->ncol > 0 ? A->ncol : 1) * 4) == hipSuccess;
 	if (ok) ok = hipMemsetAsync(h->tile_ptr, 0, (size_t) (ntiles + 1 + PBC_TP_PAD) * 8, 0) == hipSuccess &&
 		     hipMemsetAsync(h->col_has_na, 0, (size_t) (A->ncol > 0 ? A->ncol : 1) * 4, 0) == hipSuccess;
-	// format 1: the scatter workgroups take `subp` panels at a time -- the fewest (>= 16) that give a column ~8
+	// LDS-DMA layouts: the scatter workgroups take `subp` panels at a time -- the fewest (>= 16) that give a column ~8
 	// nonzeros per stretch on average (very sparse operands: fewer, larger stretches; the table of stretch bounds
 	// then stays smaller than the operand)
 	int subp = 16;
@@ -685,15 +695,15 @@ extern "C" svt_dev_pbc *svt_dev_pbc_build(const svt_dev_csc *A, int CBW, int WPB
 	const int64_t nchunks = (h->npanels + subp - 1) / subp;
 	const int64_t nb_entries = A->ncol * (nchunks + 1);
 	bool bounds_done = false;
-	if (ok && A->ncol > 0 && A->nnz > 0) {
-		const int BATCH = h->fmt == 1 ? 8 : PBC_BATCH;
-		const size_t rbytes = h->fmt == 1 ? 12 : 16;
-		// Every tile is padded to whole batches (format 1: at least one): at most BATCH - 1 (BATCH)
-		// records of padding per tile.  Allocating for that bound spares the build a round trip to
-		// the host between its count and scatter passes; the exact count is read back at the end.
-		const int64_t nrec_max = A->nnz + ntiles * (int64_t) (h->fmt == 1 || h->gather ? BATCH : BATCH - 1);
+	if (ok && kind != PBC_KIND_NONE && A->ncol > 0 && A->nnz > 0) {
+		const int BATCH = dma ? 8 : PBC_BATCH;
+		const size_t rbytes = dma ? 12 : 16;
+		// Every tile is padded to whole batches, at least one: at most BATCH records of padding per
+		// tile.  Allocating for that bound spares the build a round trip to the host between its
+		// count and scatter passes; the exact count is read back at the end.
+		const int64_t nrec_max = A->nnz + ntiles * (int64_t) BATCH;
 		dim3 grid((unsigned) h->ngroups, (unsigned) ((h->npanels + PCH - 1) / PCH));
-		if (h->fmt == 1 && h->npanels <= PBC_COUNT_MAXPANELS) {
+		if (dma && h->npanels <= PBC_COUNT_MAXPANELS) {
 			// one stream over the offsets: tile counts and the table of stretch bounds together
 			ok = pbc_alloc((void **) &bounds, (size_t) nb_entries * 4) == hipSuccess;
 			if (ok) {
@@ -707,21 +717,21 @@ extern "C" svt_dev_pbc *svt_dev_pbc_build(const svt_dev_csc *A, int CBW, int WPB
 						   bounds, nchunks, logR + sl);
 				bounds_done = true;
 			}
-		} else if (h->fmt == 1)
+		} else if (dma)
 			hipLaunchKernelGGL((pbc_pass_kernel<0, 1>), grid, dim3(64), 0, 0, A->col_ptr, A->row_idx,
 					   (const double *) A->val, A->ncol, CBW, logR, h->npanels,
 					   h->tile_ptr, (uint4 *) NULL, h->col_has_na, g_pbc_stagger, 0);
-		else
+		else                                    // (gather layouts: tile-start flags, the last argument)
 			hipLaunchKernelGGL((pbc_pass_kernel<0, 0>), grid, dim3(64), 0, 0, A->col_ptr, A->row_idx,
 					   (const double *) A->val, A->ncol, CBW, logR, h->npanels,
-					   h->tile_ptr, (uint4 *) NULL, h->col_has_na, g_pbc_stagger, h->gather);
+					   h->tile_ptr, (uint4 *) NULL, h->col_has_na, g_pbc_stagger, 1);
 		// exclusive scan in place over ntiles+1 entries (last entry = total)
 		tmp_bytes = exclusive_scan_ws_bytes(ntiles + 1);
 		ok = pbc_alloc(&tmp, tmp_bytes) == hipSuccess &&
 		     launch_exclusive_scan_i64(h->tile_ptr, ntiles + 1, tmp, 0) == 0;
 		if (ok) ok = pbc_alloc((void **) &h->rec, (size_t) nrec_max * rbytes + PBC_SLACK * 16) == hipSuccess;
 		if (ok) {
-			if (h->fmt == 1) {
+			if (dma) {
 				if (!bounds_done) ok = pbc_alloc((void **) &bounds, (size_t) nb_entries * 4) == hipSuccess;
 				if (ok) {
 					if (!bounds_done)
@@ -739,7 +749,7 @@ extern "C" svt_dev_pbc *svt_dev_pbc_build(const svt_dev_csc *A, int CBW, int WPB
 			} else {
 				hipLaunchKernelGGL((pbc_pass_kernel<1, 0>), grid, dim3(64), 0, 0, A->col_ptr,
 						   A->row_idx, (const double *) A->val, A->ncol, CBW, logR,
-						   h->npanels, h->tile_ptr, h->rec, h->col_has_na, g_pbc_stagger, h->gather);
+						   h->npanels, h->tile_ptr, h->rec, h->col_has_na, g_pbc_stagger, 1);
 			}
 		}
 		// One read-back for the whole build: records, longest leaf, "a column group too large for the
@@ -794,8 +804,7 @@ extern "C" void svt_dev_pbc_set_spare_cus(int n)
 extern "C" int svt_dev_pbc_spare_cus(void) { return g_pbc_spare_cus; }
 // ---------------------------------------------------------------------------
 #ifdef SVT_TUNING
-// 0 = normal; 2 = timing-only build without the record loop (results wrong by construction);
-// 3 = normal results + per-section cycle counts of workgroup 0 (svt_dev_pbc_read_prof);
+// 0 = normal; 3 = normal results + per-section cycle counts of the LDS-DMA kernel (svt_dev_pbc_read_prof);
 // 100 + n = force n row splits; 200 + m = DMA issue stagger mode; 300 + t = record-touch look-ahead
 extern "C" void svt_dev_pbc_set_debug(int mode)
 {
@@ -810,10 +819,8 @@ struct PbcFlags {
 	int *y_nonfinite;    // [1] any NaN/Inf/NA in the dense operand
 };
 
-// DBG == 3 (tuning only): cycles per section, per wavefront of workgroup (0,0,0):
-// [w][0] fetch issue, [1] record loop, [2] barrier after the loop, [3] commit,
-// [4] barrier after commit, [5] panels
-// (kept in the flag block at the head of the workspace, its last 1024 bytes)
+// Debug mode 3 (tuning only): the LDS-DMA kernel's cycles per section, 8 words per wavefront of
+// workgroup 0 (crossprod_pbc_dma_kernel, PROF 1), kept in the workspace's flag block at byte 7168
 #define PBC_SUBFLAG0 16           // flags[16 .. 63]: "a non-finite entry in block (row split, dense tile) of Y", index modulo 48
 #define PBC_NSUBFLAG 48
 #define PBC_FLAG_BYTES 16384     // [0, 256) flags; [256, 8192) per-column counters of the dirty-column fix-up when they fit;
@@ -828,324 +835,27 @@ extern "C" int svt_dev_pbc_read_prof(const void *ws, unsigned long long *out)
 }
 #endif
 
-// A batch of PBC_BATCH (= 4) records = 16 dwords, held in a block of 16 SGPRs
-// that is pinned to fixed physical registers (s[32:47] / s[48:63]) so that the
-// hand-written step below can name the fields directly: no decoding, no copies.
-typedef uint32_t batch_t __attribute__((ext_vector_type(16)));
-
-// Staging of one Y panel through registers: NPF 16-byte pieces per thread,
-// fetched while the previous panel is being consumed, written to LDS between
-// two barriers.  LDS layout ylds[k][r], row stride RS = R + 1 doubles (odd, so
-// that the lane = k reads of the product loop are bank-conflict free).
-// Piece e (0 .. 32R-1) of a panel: column-major Y -> rows 2*(e % (R/2)), +1 of
-// dense column e / (R/2); row-contiguous Y (TRY) -> dense columns 2*(e % 32),
-// +1 of row e / 32.  Thread (w, lane) owns pieces (w*NPF + q)*64 + lane.
-// Panels that stick out of Y (last rows, K not a multiple of 64) or that are
-// not 16-byte aligned take the element-wise path in commit().
-template <int NPF, int WPB, int LOGR, bool TRY>
-struct Stager {
-	double2 pf[NPF];
-	bool fast = false;
-
-	__device__ static inline void piece(int e, int &kk, int &rr)
-	{
-		constexpr int R = 1 << LOGR;
-		if (!TRY) { kk = e / (R / 2); rr = (e % (R / 2)) * 2; }
-		else { kk = (e % 32) * 2; rr = e / 32; }
-	}
-
-	__device__ inline void fetch(const double *__restrict__ Y, int64_t ldY, int64_t nrow,
-				     int K, int k0, int64_t p, int w, int lane)
-	{
-		constexpr int R = 1 << LOGR;
-		const int64_t r0 = p << LOGR;
-		fast = (r0 + R <= nrow) && (k0 + 64 <= K) && ((ldY & 1) == 0) &&
-		       ((((uintptr_t) Y) & 15) == 0);          // wave-uniform
-		if (!fast)
-			return;
-#pragma unroll
-		for (int q = 0; q < NPF; q++) {
-			int kk, rr;
-			piece((w * NPF + q) * 64 + lane, kk, rr);
-			const double *src = TRY ? Y + (k0 + kk) + (r0 + rr) * ldY
-						: Y + (r0 + rr) + (int64_t) (k0 + kk) * ldY;
-			pf[q] = *(const double2 *) src;
-		}
-	}
-
-	__device__ inline void commit(double *__restrict__ ylds, const double *__restrict__ Y,
-				      int64_t ldY, int64_t nrow, int K, int k0, int64_t p,
-				      int w, int lane, int &bad)
-	{
-		constexpr int R = 1 << LOGR, RS = R + 1;
-		if (fast) {
-#pragma unroll
-			for (int q = 0; q < NPF; q++) {
-				int kk, rr;
-				piece((w * NPF + q) * 64 + lane, kk, rr);
-				if (!svt_is_finite(pf[q].x) || !svt_is_finite(pf[q].y)) bad = 1;
-				ylds[kk * RS + rr] = pf[q].x;
-				if (!TRY) ylds[kk * RS + rr + 1] = pf[q].y;
-				else ylds[(kk + 1) * RS + rr] = pf[q].y;
-			}
-			return;
-		}
-		const int64_t r0 = p << LOGR;
-		for (int idx = w * 64 + lane; idx < 64 * R; idx += WPB * 64) {
-			const int kk = TRY ? (idx & 63) : (idx >> LOGR);
-			const int rr = TRY ? (idx >> 6) : (idx & (R - 1));
-			const int64_t r = r0 + rr;
-			double y = 0.0;
-			if (r < nrow && k0 + kk < K)
-				y = TRY ? Y[(k0 + kk) + r * ldY] : Y[r + (int64_t) (k0 + kk) * ldY];
-			if (!svt_is_finite(y)) bad = 1;
-			ylds[kk * RS + rr] = y;
-		}
-	}
-};
-
-// The record loop of one tile (the records of one wavefront in one panel),
-// written by hand: the scalar unit is shared by the 4 SIMDs of a CU, so every
-// SALU instruction per record counts, and the compiler's lowering of a
-// register-indexed accumulator costs 2 mode switches + 4 v_mov per record
-// (tools/micro/idx_bench.hip).
-//
-// Software pipeline over batches of 4 records, 3 stages:
-//   L(k+2)  one 64-byte scalar load                       -> SGPR block
-//   D(k+1)  4 x (LDS address = lane base + row offset), 4 x ds_read_b64
-//           (lane = dense column: bank-conflict free)      -> y set
-//   F(k)    4 x acc[c_q] += a_q * y_q in VGPR-index mode: all partial sums of
-//           the wavefront are pinned to v[64 ...]; each v_fma_f64 addresses
-//           source-2 and destination relative to M0 = 2*c_q
-//           (1 SALU + 1 VALU per record)
-// and ONE `s_waitcnt lgkmcnt(0)` per step, after the FMAs: the scalar load and
-// the LDS reads of the step complete under them.  Three SGPR blocks (s[36:51],
-// s[52:67], s[68:83]) and two y sets rotate, hence 6 phases per loop trip.
-// The stream of a wavefront is contiguous (and has 3 batches of slack at the
-// end of the array), so the look-ahead stages never need to know where the
-// tile ends; row offsets of look-ahead records are valid LDS addresses.
-// Record = {s+0: LDS byte offset of the row, s+1: 2*column, s[+2:+3]: value}.
-#define PBC_D4(B0, B1, B2, B3, YS)                                                    \
-	"v_add_u32 %[t0], s" #B0 ", %[lb]\n\t"                                          \
-	"v_add_u32 %[t1], s" #B1 ", %[lb]\n\t"                                          \
-	"v_add_u32 %[t2], s" #B2 ", %[lb]\n\t"                                          \
-	"v_add_u32 %[t3], s" #B3 ", %[lb]\n\t"                                          \
-	"ds_read_b64 %[" #YS "0], %[t0]\n\t"                                           \
-	"ds_read_b64 %[" #YS "1], %[t1]\n\t"                                           \
-	"ds_read_b64 %[" #YS "2], %[t2]\n\t"                                           \
-	"ds_read_b64 %[" #YS "3], %[t3]\n\t"
-#define PBC_F4(I0, A0L, A0H, I1, A1L, A1H, I2, A2L, A2H, I3, A3L, A3H, YS)              \
-	"s_set_gpr_idx_on s" #I0 ", gpr_idx(SRC2,DST)\n\t"                              \
-	"v_fma_f64 v[64:65], s[" #A0L ":" #A0H "], %[" #YS "0], v[64:65]\n\t"            \
-	"s_set_gpr_idx_idx s" #I1 "\n\t"                                                \
-	"v_fma_f64 v[64:65], s[" #A1L ":" #A1H "], %[" #YS "1], v[64:65]\n\t"            \
-	"s_set_gpr_idx_idx s" #I2 "\n\t"                                                \
-	"v_fma_f64 v[64:65], s[" #A2L ":" #A2H "], %[" #YS "2], v[64:65]\n\t"            \
-	"s_set_gpr_idx_idx s" #I3 "\n\t"                                                \
-	"v_fma_f64 v[64:65], s[" #A3L ":" #A3H "], %[" #YS "3], v[64:65]\n\t"            \
-	"s_set_gpr_idx_off\n\t"
-// block A = s[36:51], B = s[52:67], C = s[68:83]  (s32-s35 are the stack/frame
-// pointer registers of the calling convention and are left alone)
-#define PBC_LOAD_A "s_load_dwordx16 s[36:51], %[base], %[lo]\n\t"
-#define PBC_LOAD_B "s_load_dwordx16 s[52:67], %[base], %[lo]\n\t"
-#define PBC_LOAD_C "s_load_dwordx16 s[68:83], %[base], %[lo]\n\t"
-#define PBC_D_A(YS) PBC_D4(36, 40, 44, 48, YS)
-#define PBC_D_B(YS) PBC_D4(52, 56, 60, 64, YS)
-#define PBC_D_C(YS) PBC_D4(68, 72, 76, 80, YS)
-#define PBC_F_A(YS) PBC_F4(37, 38, 39, 41, 42, 43, 45, 46, 47, 49, 50, 51, YS)
-#define PBC_F_B(YS) PBC_F4(53, 54, 55, 57, 58, 59, 61, 62, 63, 65, 66, 67, YS)
-#define PBC_F_C(YS) PBC_F4(69, 70, 71, 73, 74, 75, 77, 78, 79, 81, 82, 83, YS)
-// one phase: load into LB, LDS reads for DB into set YD, FMAs of FB with set YF
-#define PBC_PHASE(LOADTXT, DTXT, FTXT)                                                 \
-	"s_add_u32 %[lo], %[lo], 64\n\t"                                               \
-	LOADTXT DTXT FTXT                                                              \
-	"s_waitcnt lgkmcnt(0)\n\t"                                                     \
-	"s_sub_u32 %[nb], %[nb], 1\n\t"                                                \
-	"s_cmp_eq_u32 %[nb], 0\n\t"                                                    \
-	"s_cbranch_scc1 9f\n\t"
-#define PBC_PANEL_TXT                                                                  \
-	"s_mov_b32 s85, m0\n\t"             /* VGPR-index mode rewrites M0 */           \
-	"s_cmp_eq_u32 %[nb], 0\n\t"                                                    \
-	"s_cbranch_scc1 9f\n\t"                                                        \
-	/* prologue: batch 0 -> A, then its LDS reads + batch 1 -> B */                \
-	PBC_LOAD_A                                                                     \
-	"s_waitcnt lgkmcnt(0)\n\t"                                                     \
-	"s_add_u32 %[lo], %[lo], 64\n\t"                                               \
-	PBC_LOAD_B PBC_D_A(ya)                                                         \
-	"s_waitcnt lgkmcnt(0)\n"                                                       \
-	"1:\n\t"                                                                       \
-	PBC_PHASE(PBC_LOAD_C, PBC_D_B(yb), PBC_F_A(ya))                                \
-	PBC_PHASE(PBC_LOAD_A, PBC_D_C(ya), PBC_F_B(yb))                                \
-	PBC_PHASE(PBC_LOAD_B, PBC_D_A(yb), PBC_F_C(ya))                                \
-	PBC_PHASE(PBC_LOAD_C, PBC_D_B(ya), PBC_F_A(yb))                                \
-	PBC_PHASE(PBC_LOAD_A, PBC_D_C(yb), PBC_F_B(ya))                                \
-	PBC_PHASE(PBC_LOAD_B, PBC_D_A(ya), PBC_F_C(yb))                                \
-	"s_branch 1b\n"                                                                \
-	"9:\n\t"                                                                       \
-	"s_mov_b32 m0, s85\n\t"
-#define PBC_PANEL_OPS                                                                  \
-	[lo] "+s"(lo_), [nb] "+s"(nb_),                                                \
-	[t0] "=&v"(t0_), [t1] "=&v"(t1_), [t2] "=&v"(t2_), [t3] "=&v"(t3_),              \
-	[ya0] "=&v"(ya0_), [ya1] "=&v"(ya1_), [ya2] "=&v"(ya2_), [ya3] "=&v"(ya3_),      \
-	[yb0] "=&v"(yb0_), [yb1] "=&v"(yb1_), [yb2] "=&v"(yb2_), [yb3] "=&v"(yb3_)
-#define PBC_PANEL_CLOBBERS "scc", "memory", "s85", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84"
-
-// DBG: 0 = product build; 1 = skip staging of Y (timing only); 2 = skip the
-// record loop (timing only).  Selected with svt_dev_pbc_set_debug().
-template <int NV, int WPB, int LOGR, bool TRY, int DBG>
-__global__ void __launch_bounds__(WPB * 64)
-crossprod_pbc_kernel(const uint4 *__restrict__ rec,
-		     const int64_t *__restrict__ tile_ptr, int64_t npanels,
-		     const double *__restrict__ Y, int64_t ldY, int64_t nrow, int K,
-		     int64_t ncol, int64_t panels_per_split, double *__restrict__ part,
-		     int64_t Kp, PbcFlags fl, int CBW)
-{
-	// The only LDS object of this kernel: its byte offset is 0, which
-	// lds_read_batch() relies on.
-	extern __shared__ double ylds[];            // [64][R + 1]
-	constexpr int R = 1 << LOGR;
-	constexpr int RS = R + 1;
-	constexpr int NPF = R / (2 * WPB);          // 16-byte pieces per thread per panel
-	static_assert(NPF >= 1 && NPF * 2 * WPB == R, "panel must split evenly over the workgroup");
-	const int tid = threadIdx.x, lane = tid & 63;
-	// the wavefront id is wave-uniform; tell the compiler so that everything
-	// derived from it (tile bounds, records) lives in SGPRs / scalar loads
-	const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const int split = blockIdx.x, kt = blockIdx.y;
-	const int64_t b = blockIdx.z;
-	const int64_t wv = b * WPB + w;             // global wavefront-group index
-	const int64_t pa = (int64_t) split * panels_per_split;
-	const int64_t pb = pa + panels_per_split < npanels ? pa + panels_per_split : npanels;
-	const int k0 = kt * 64;
-	if (pa >= pb)
-		return;                                 // whole workgroup: no barrier crossed yet
-
-	d16 acc[NV];
-#pragma unroll
-	for (int i = 0; i < NV; i++) acc[i] = 0.0;
-	int bad = 0;
-	uint32_t touch = 0, tv = 0;
-	const uint32_t lane_base = (uint32_t) lane * (RS * 8);
-	Stager<NPF, WPB, LOGR, TRY> st;
-
-	// prologue: panel pa straight into LDS
-	if (DBG != 1) {
-		st.fetch(Y, ldY, nrow, K, k0, pa, w, lane);
-		st.commit(ylds, Y, ldY, nrow, K, k0, pa, w, lane, bad);
-	}
-	__syncthreads();
-	const int64_t *__restrict__ tb = tile_ptr + (wv * npanels + pa);
-	// byte offset of the wavefront's current batch, relative to its own first record
-	// (32-bit: svt_dev_pbc_build refuses layouts in which one group's stream reaches 4 GiB)
-	const uint4 *__restrict__ rec_w = rec + tb[0];
-	uint32_t off = 0;
-
-	unsigned long long pr[6] = {0, 0, 0, 0, 0, 0}, tq = 0;
-#define PBC_PROF(i) if (DBG == 3) { const unsigned long long t_ = __builtin_readcyclecounter(); pr[i] += t_ - tq; tq = t_; }
-	if (DBG == 3) tq = __builtin_readcyclecounter();
-	for (int64_t p = pa; p < pb; p++, tb += 1) {
-		const int64_t tbeg = tb[0], tend = tb[1];
-		// next panel of Y starts its trip from L2/HBM now, lands in registers
-		if (DBG != 1 && p + 1 < pb) st.fetch(Y, ldY, nrow, K, k0, p + 1, w, lane);
-		// Pull this wavefront's records of panel p + PBC_AHEAD towards L2: one
-		// dword per 128-byte line.  The loaded word is only consumed one panel
-		// later, so nothing waits for it here.
-		touch ^= tv;
-		tv = 0;
-		if (DBG != 2 && p + PBC_AHEAD < npanels) {
-			const int64_t ta = tb[PBC_AHEAD], te = tb[PBC_AHEAD + 1];
-			const uint32_t toff = lane * 128u;
-			const uint32_t len = (uint32_t) (te - ta) * 16u;
-			if (toff < len)
-				tv = *(const uint32_t *) ((const char *) (rec + ta) + toff);
-		}
-
-		PBC_PROF(0)
-		// ---- this wavefront's records of the panel --------------------------
-		if (DBG == 2) {
-			acc[0][0] += (double) tbeg;
-		} else {
-			uint32_t nb_ = (uint32_t) ((tend - tbeg) / PBC_BATCH);
-			uint32_t lo_ = off;                 // byte offset of the stream cursor
-			off += nb_ * (PBC_BATCH * 16u);
-			uint32_t t0_, t1_, t2_, t3_;
-			double ya0_, ya1_, ya2_, ya3_, yb0_, yb1_, yb2_, yb3_;
-			if constexpr (NV == 1) {
-				asm volatile(PBC_PANEL_TXT
-					     : "+{v[64:95]}"(acc[0]), PBC_PANEL_OPS
-					     : [base] "s"(rec_w), [lb] "v"(lane_base)
-					     : PBC_PANEL_CLOBBERS);
-			} else if constexpr (NV == 2) {
-				asm volatile(PBC_PANEL_TXT
-					     : "+{v[64:95]}"(acc[0]), "+{v[96:127]}"(acc[NV > 1 ? 1 : 0]),
-					       PBC_PANEL_OPS
-					     : [base] "s"(rec_w), [lb] "v"(lane_base)
-					     : PBC_PANEL_CLOBBERS);
-			} else if constexpr (NV == 3) {
-				asm volatile(PBC_PANEL_TXT
-					     : "+{v[64:95]}"(acc[0]), "+{v[96:127]}"(acc[NV > 1 ? 1 : 0]),
-					       "+{v[128:159]}"(acc[NV > 2 ? 2 : 0]), PBC_PANEL_OPS
-					     : [base] "s"(rec_w), [lb] "v"(lane_base)
-					     : PBC_PANEL_CLOBBERS);
-			} else {
-				asm volatile(PBC_PANEL_TXT
-					     : "+{v[64:95]}"(acc[0]), "+{v[96:127]}"(acc[NV > 1 ? 1 : 0]),
-					       "+{v[128:159]}"(acc[NV > 2 ? 2 : 0]),
-					       "+{v[160:191]}"(acc[NV > 3 ? 3 : 0]), PBC_PANEL_OPS
-					     : [base] "s"(rec_w), [lb] "v"(lane_base)
-					     : PBC_PANEL_CLOBBERS);
-			}
-		}
-		PBC_PROF(1)
-		if (p + 1 < pb) {
-			__syncthreads();                    // panel p fully consumed
-			PBC_PROF(2)
-			if (DBG != 1) st.commit(ylds, Y, ldY, nrow, K, k0, p + 1, w, lane, bad);
-			PBC_PROF(3)
-			__syncthreads();
-			PBC_PROF(4)
-		}
-		if (DBG == 3) pr[5]++;
-	}
-	if (DBG == 3 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0)
-		for (int i = 0; i < 6; i++) ((unsigned long long *) (fl.y_nonfinite + 1792))[w * 8 + i] = pr[i];
-	if (b == 0 && __any(bad) && lane == 0)
-		*fl.y_nonfinite = 1;
-	touch ^= tv;
-	if (touch == 0x9E3779B9u && K < 0)      // never true: keeps the prefetch loads alive
-		fl.y_nonfinite[1] = 1;
-	// ---- partial results: part[(split*Kp + k) * ncol + c] -----------------
-	const int64_t c0 = wv * CBW;
-	double *__restrict__ dst = part + ((int64_t) split * Kp + k0 + lane) * ncol + c0;
-	if (CBW == 16 * NV && c0 + 16 * NV <= ncol) {   // wave-uniform: whole slabs inside
-#pragma unroll
-		for (int ii = 0; ii < NV; ii++)
-#pragma unroll
-			for (int jj = 0; jj < 16; jj++)
-				dst[ii * 16 + jj] = acc[ii][jj];
-	} else {
-#pragma unroll
-		for (int ii = 0; ii < NV; ii++)
-#pragma unroll
-			for (int jj = 0; jj < 16; jj++)
-				if (ii * 16 + jj < CBW && c0 + ii * 16 + jj < ncol) dst[ii * 16 + jj] = acc[ii][jj];
-	}
-}
-
 // ---------------------------------------------------------------------------
 // Gather kernel: very sparse operands (BASELINE config 4: 0.1 %, 5 nonzeros per (40-column group,
 // 128-row panel) tile).  Staging whole panels of Y for every block of columns moves 64 KB into LDS
 // per ~80 nonzeros there; here every nonzero fetches the 512 bytes it needs -- row r of the
 // row-major, K-padded copy Yt that prep_dense_kernel makes (kernels_mult.hip), 64 dense columns,
 // lane = dense column -- straight from L2 into registers.  No LDS, no barrier: a wavefront streams
-// the records of its column group (format 0, panels of 2^logR >= 512 rows, padded to batches of 4)
-// through the same 3-stage pipeline as crossprod_pbc_kernel, with the LDS reads replaced by
-// global loads (two batches = 8 loads in flight per wavefront, counted by vmcnt, which the scalar
-// record loads do not share).  All wavefronts of a row split walk the rows in the same order, so
-// a row of Yt is fetched from HBM once per XCD and hit in L2 by the other column groups.
+// the records of its column group (16-byte records, panels of 2^logR >= 512 rows, padded to batches
+// of 4) through a 3-stage pipeline over batches: L(k+2) one 64-byte scalar load into an SGPR block
+// (A = s[36:51], B = s[52:67], C = s[68:83]: three rotate); D(k+1) 4 loads of rows of Yt (two batches
+// = 8 loads in flight per wavefront, counted by vmcnt, which the scalar record loads do not share);
+// F(k) 4 x acc[c] += a * y in VGPR-index mode, M0 = 2*c (the compiler's lowering of a register-indexed
+// accumulator costs 2 mode switches + 4 v_mov per record, tools/micro/idx_bench.hip).  All wavefronts
+// of a row split walk the rows in the same order, so a row of Yt is fetched from HBM once per XCD and
+// hit in L2 by the other column groups.
 // Traffic: 512 B per (nonzero, 64 dense columns) L2 -> CU, i.e. nnz * K * 8 bytes: the floor of an
 // out-stationary product when a column block holds less than one nonzero per row.
 // ---------------------------------------------------------------------------
+#define PBC_LOAD_A "s_load_dwordx16 s[36:51], %[base], %[lo]\n\t"
+#define PBC_LOAD_B "s_load_dwordx16 s[52:67], %[base], %[lo]\n\t"
+#define PBC_LOAD_C "s_load_dwordx16 s[68:83], %[base], %[lo]\n\t"
+#define PBC_PANEL_CLOBBERS "scc", "memory", "s85", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84"
 #define PBG_D4(B0, B1, B2, B3, YS)                                                    \
 	"v_mad_u32_u24 %[t0], s" #B0 ", %[kp], %[l8]\n\t"                               \
 	"v_mad_u32_u24 %[t1], s" #B1 ", %[kp], %[l8]\n\t"                               \
@@ -1501,11 +1211,11 @@ crossprod_pbc_gatherx_kernel(const uint4 *__restrict__ rec, const int64_t *__res
 }
 
 // ---------------------------------------------------------------------------
-// DMA kernel: the same product on the same layout, restructured around the three
-// things the register-staged kernel above spends its time on (measured with
-// s_memtime per section, tools/tune_pbc.py --prof: per 128-row panel ~3000
-// cycles in the record loop and ~4000 in fetch issue, two barriers and the
-// LDS write pass):
+// DMA kernel: 128-row panels of Y in LDS, built around the three things its
+// register-staged predecessor of round 1 (Y through VGPRs, then written to LDS)
+// spent its time on (measured with s_memtime per section: per 128-row panel
+// ~3000 cycles in the record loop and ~4000 in fetch issue, two barriers and
+// the LDS write pass):
 //   * the Y panel goes global -> LDS by LDS-DMA (global_load_lds_dwordx4, one
 //     1 KiB piece = 128 rows of one dense column), double-buffered: the pieces of
 //     panel p+1 fly while panel p is consumed, ONE barrier per panel, no VGPRs
@@ -1534,8 +1244,9 @@ crossprod_pbc_gatherx_kernel(const uint4 *__restrict__ rec, const int64_t *__res
 // all column blocks of one (row split, dense tile) on one XCD, next to each
 // other in launch order, so that they pull the same Y panels through one L2 at
 // about the same time.
-// Preconditions (checked by the launcher, else the kernel above runs):
-// column-major Y, WPB = 16, logR = 7, nrow >= 256.
+// Preconditions (the layout's kind, pbc_kind: PBC_KIND_DMA): column-major Y (the
+// launcher transposes a Y given by rows first), WPB = 16, logR = 7, CBW <= 40,
+// 256 <= nrow < 2^28.
 // ---------------------------------------------------------------------------
 #include "pbc_dma_asm.inc"
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
@@ -2171,20 +1882,12 @@ pbc_dirty_leaf_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__rest
 // ---------------------------------------------------------------------------
 // launch
 // ---------------------------------------------------------------------------
-// Row splits: enough workgroups to fill the chip, every split non-empty.
-static bool pbc_dma_ok(const svt_dev_pbc *P, int tr_y)
-{
-	// the layout was built for it; the kernel stages a row split through 32-bit byte offsets
-	// (8 bytes per row per dense column), and a split is never longer than the matrix
-	return !tr_y && P->fmt == 1 && P->nrow < ((int64_t) 1 << 28);
-}
-
 // rows of the staged dense operand the gather kernel may touch: its look-ahead loads run on into the
 // records of the next tile, whose row offsets are relative to a panel that may be the last, partial one
 static int64_t pbc_padded_rows(const svt_dev_pbc *P)
 {
 	// (one panel more: the XCD-paced kernel's look-ahead batch past its last tile may carry a tile-start flag)
-	return P->gather ? ((P->npanels + 1) << P->logR) : P->nrow;
+	return P->kind == PBC_KIND_GATHER ? ((P->npanels + 1) << P->logR) : P->nrow;
 }
 
 // Pacing of crossprod_pbc_gatherx_kernel: a wavefront runs at most `dsync` tiles ahead of the slowest started
@@ -2220,8 +1923,18 @@ static int pbc_cus(void)
 static bool pbgx_ok(const svt_dev_pbc *P, int K)
 {
 	const int64_t Kp = ((int64_t) K + 63) / 64 * 64;
-	return P->gather && g_pbgx_dsync >= 0 && Kp % 128 == 0 && P->npanels >= 64 && P->WPB == 4 &&
+	return P->kind == PBC_KIND_GATHER && g_pbgx_dsync >= 0 && Kp % 128 == 0 && P->npanels >= 64 && P->WPB == 4 &&
 	       ((int64_t) 8 << P->logR) * Kp < ((int64_t) 1 << 31);
+}
+
+// s row splits, at most one per panel, every split non-empty
+static int pbc_splits(const svt_dev_pbc *P, int64_t s, int64_t *pps_out)
+{
+	if (s > P->npanels) s = P->npanels;
+	if (s < 1) s = 1;
+	const int64_t pps = (P->npanels + s - 1) / s;
+	if (pps_out) *pps_out = pps;
+	return (int) ((P->npanels + pps - 1) / pps);
 }
 
 // gather kernel: no staging to share, so splits only have to fill the chip (~8192 wavefronts)
@@ -2241,13 +1954,7 @@ static int pick_nsplit_gather(const svt_dev_pbc *P, int K, int64_t *pps_out, boo
 #ifdef SVT_TUNING
 	if (getenv("SVT_PBG_WAVES")) target = atoll(getenv("SVT_PBG_WAVES"));
 #endif
-	int64_t s = waves >= target ? 1 : (target + waves - 1) / waves;
-	if (s > P->npanels) s = P->npanels;
-	if (s < 1) s = 1;
-	const int64_t pps = (P->npanels + s - 1) / s;
-	s = (P->npanels + pps - 1) / pps;
-	if (pps_out) *pps_out = pps;
-	return (int) s;
+	return pbc_splits(P, waves >= target ? 1 : (target + waves - 1) / waves, pps_out);
 }
 
 // CUs are kept free (svt_dev_pbc_set_spare_cus) when one round of workgroups fits the rest
@@ -2257,17 +1964,25 @@ static bool pbc_sparing(const svt_dev_pbc *P, int K)
 	return g_pbc_spare_cus > 0 && units <= 256 - g_pbc_spare_cus && P->npanels >= 8 * 16;
 }
 
-static int pick_nsplit(const svt_dev_pbc *P, int K, bool dma, int64_t *pps_out, bool may_spare = true)
+// splits that give >= 512 workgroups of `units` (column block, dense tile) pairs, in whole XCD rounds
+static int64_t pbc_fill_splits(int64_t units)
+{
+	if (units >= 512)
+		return 1;                               // enough column blocks: no row split, no partials
+	const int64_t s = (512 + units - 1) / units;
+	return (s + 7) / 8 * 8;
+}
+
+// Row splits of the LDS-DMA kernel: enough workgroups to fill the chip.
+static int pick_nsplit(const svt_dev_pbc *P, int K, int64_t *pps_out, bool may_spare = true)
 {
 	const int64_t kt = ((int64_t) K + 63) / 64;
 	const int64_t units = P->nblocks * kt;
 	int64_t s;
-	if (dma && may_spare && pbc_sparing(P, K)) {
+	if (may_spare && pbc_sparing(P, K)) {
 		s = (256 - g_pbc_spare_cus) / units;    // one round on the CUs that may be used
 		if (P->npanels / s < 16) s = P->npanels / 16;
-	} else if (units >= 512) {
-		s = 1;                                  // enough column blocks: no row split, no partials
-	} else if (dma && P->npanels >= 8 * 16) {
+	} else if (units < 512 && P->npanels >= 8 * 16) {
 		// One workgroup per CU (LDS, VGPRs), 32 CUs per XCD, the column blocks of a (split, dense
 		// tile) pair share an XCD.  Candidates: sx splits per XCD (8 sx in all), plus, where CUs are
 		// left over in the last round, further splits whose workgroups are dealt over all XCDs (28
@@ -2292,64 +2007,32 @@ static int pick_nsplit(const svt_dev_pbc *P, int K, bool dma, int64_t *pps_out, 
 			}
 		}
 	} else {
-		s = (512 + units - 1) / units;          // aim for >= 512 workgroups
-		s = (s + 7) / 8 * 8;                    // whole XCD rounds
+		s = pbc_fill_splits(units);
 	}
 	if (g_pbc_nsplit > 0 && units < 512) s = g_pbc_nsplit;   // tuning override
-	if (s > P->npanels) s = P->npanels;
-	if (s < 1) s = 1;
-	const int64_t pps = (P->npanels + s - 1) / s;
-	s = (P->npanels + pps - 1) / pps;              // drop empty splits
-	if (pps_out) *pps_out = pps;
-	return (int) s;
+	return pbc_splits(P, s, pps_out);
 }
 
 extern "C" size_t svt_dev_crossprod_pbc_ws_bytes(const svt_dev_pbc *P, int K)
 {
 	const int64_t Kp = ((int64_t) K + 63) / 64 * 64;
-	int ns = pick_nsplit(P, K, false, NULL);
-	{                                               // (the knob may change between the query and the launch)
-		const int n0 = pick_nsplit(P, K, true, NULL, false);
-		if (pbc_dma_ok(P, 0) && n0 > ns) ns = n0;
-	}
-	if (pbc_dma_ok(P, 0)) {
-		const int nd = pick_nsplit(P, K, true, NULL);
+	// partials: room for the splits of >= 512 workgroups, and for whatever split count the kind's launch
+	// picks with either setting of the knobs (they may change between the query and the launch)
+	int ns = pbc_splits(P, pbc_fill_splits(P->nblocks * (Kp / 64)), NULL);
+	if (P->kind == PBC_KIND_DMA) {
+		const int nd = pick_nsplit(P, K, NULL), n0 = pick_nsplit(P, K, NULL, false);
 		if (nd > ns) ns = nd;
+		if (n0 > ns) ns = n0;
 	}
-	if (P->gather) {
+	if (P->kind == PBC_KIND_GATHER) {
 		const int ng = pick_nsplit_gather(P, K, NULL, true);
 		if (ng > ns) ns = ng;
-		if (ns < 8) ns = 8;                         // (the pacing knob may change between the query and the launch)
+		if (ns < 8) ns = 8;                         // (the paced kernel: one split per XCD)
 	}
 	// [flags][partials][general-path workspace; a row-major Y is transposed into it first]
 	// [dirty-column scratch]
 	return PBC_FLAG_BYTES + (size_t) ns * Kp * (P->ncol > 0 ? P->ncol : 1) * 8 +
 	       crossprod_ws_bytes(pbc_padded_rows(P), P->ncol, K) + dirty_ws_bytes(P->ncol, Kp);
-}
-
-template <int NV, int WPB, int LOGR>
-static void launch_main(const svt_dev_pbc *P, const double *Y, int64_t ldY, int tr_y, int K,
-			int nsplit, int64_t pps, double *part, int64_t Kp, PbcFlags fl,
-			hipStream_t s)
-{
-	const int R = 1 << LOGR;
-	const size_t lds = (size_t) 64 * (R + 1) * 8;
-	dim3 grid((unsigned) nsplit, (unsigned) (Kp / 64), (unsigned) P->nblocks);
-	void (*kern)(const uint4 *, const int64_t *, int64_t, const double *,
-		     int64_t, int64_t, int, int64_t, int64_t, double *, int64_t, PbcFlags, int);
-	if (tr_y)
-		kern = crossprod_pbc_kernel<NV, WPB, LOGR, true, 0>;
-	else
-#ifdef SVT_TUNING
-		kern = g_pbc_debug == 2 ? crossprod_pbc_kernel<NV, WPB, LOGR, false, 2> :
-		       g_pbc_debug == 3 ? crossprod_pbc_kernel<NV, WPB, LOGR, false, 3> :
-					  crossprod_pbc_kernel<NV, WPB, LOGR, false, 0>;
-#else
-		kern = crossprod_pbc_kernel<NV, WPB, LOGR, false, 0>;
-#endif
-	(void) hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-	hipLaunchKernelGGL(kern, grid, dim3(WPB * 64), lds, s, P->rec, P->tile_ptr, P->npanels,
-			   Y, ldY, P->nrow, K, P->ncol, pps, part, Kp, fl, P->CBW);
 }
 
 template <int NV>
@@ -2428,11 +2111,11 @@ pbc_clear_kernel(uint32_t *__restrict__ a, int na, uint32_t *__restrict__ b, int
 }
 
 int launch_crossprod_general_if(const CrossprodArgs &a, const int *flag, bool counters_cleared, hipStream_t s);
-int *crossprod_general_counters(void *ws, int64_t nrow, int K, int *n);
 int launch_dense_prepare_flag(const CrossprodArgs &a, int *any, hipStream_t s);
 
-// phase 1: the LDS-panel product kernel (partials into ws); phase 2: sum the
-// partials into `out`, then the general kernels if Y was not finite.
+// phase 1: the product kernel of the layout's kind (partials into ws); phase 2: sum the
+// partials into `out` and fix up the cells of dense columns that are not finite.  Without a
+// product kernel (PBC_KIND_NONE, or no records) phase 2 runs the general kernels instead.
 // first_col > 0: only the leaves of the workgroup column block that holds first_col and of the
 // later ones are computed (their cells of `out` written); the cells of earlier leaves are left
 // alone.  Unary crossprod(x) needs only the leaves c >= k of dense column k (the reference's
@@ -2466,10 +2149,11 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 		return svt_set_error("svt_dev_crossprod_pbc: workspace too small");
 	const int64_t Kp = ((int64_t) K + 63) / 64 * 64;
 	int64_t pps = 1;
+	// a layout without records (no nonzero at all) has no product kernel to run either
+	const int kind = P->rec != NULL ? P->kind : PBC_KIND_NONE;
+	const bool dma = kind == PBC_KIND_DMA, gath = kind == PBC_KIND_GATHER;
 	// a dense operand given by rows is transposed on the device first (phase 1) and the product
 	// runs on the column-major copy: same kernel, same speed + one 2 x |Y| pass
-	const bool dma = pbc_dma_ok(P, 0);
-	const bool gath = P->gather != 0;
 	const bool via_copy = tr_y && dma;
 	int block0 = 0;
 	if (dma && first_col > 0) {
@@ -2477,7 +2161,7 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 		if (block0 > P->nblocks - 1) block0 = (int) P->nblocks - 1;
 	}
 	const int64_t c_begin = (int64_t) block0 * 16 * P->CBW;
-	const int nsplit = gath ? pick_nsplit_gather(P, K, &pps) : pick_nsplit(P, K, dma, &pps);
+	const int nsplit = gath ? pick_nsplit_gather(P, K, &pps) : dma ? pick_nsplit(P, K, &pps) : 0;
 	PbcFlags fl;
 	fl.y_nonfinite = (int *) ws;
 	double *part = (double *) ((char *) ws + PBC_FLAG_BYTES);
@@ -2496,15 +2180,15 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 		// (profiles/r05_share_trace.txt: the runtime orders its blit kernels behind a barrier packet) -- 4 % of the
 		// step at an eighth of the rows of config 2a
 		{
-			const bool paced = gath && P->rec != NULL && pbgx_ok(P, K);
+			const bool paced = gath && pbgx_ok(P, K);
 			hipLaunchKernelGGL(pbc_clear_kernel, dim3(1), dim3(256), 0, s,
 					   (uint32_t *) ws, 64, (uint32_t *) dw.col_nf, (int) (Kp * 2),
 					   paced ? (uint32_t *) ((char *) ws + PBC_PROG_OFFSET) : (uint32_t *) NULL,
 					   8 * PBGX_PROG_ENTRIES);
 		}
-		if (P->rec == NULL) {
-			// no nonzero at all (no record stream was built): the general kernels
-			// produce the zeros -- or the NaNs, if Y is not finite
+		if (kind == PBC_KIND_NONE) {
+			// no record stream: raise the flags that send the whole product through the general
+			// kernels in phase 2 (they produce the zeros of an operand without nonzeros too)
 			HIP_TRY(hipMemsetAsync(ws, 1, 12, s));        // flags [0] and [2]
 			return 0;
 		}
@@ -2562,98 +2246,84 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 			HIP_TRY(hipGetLastError());
 			return 0;
 		}
-		if (dma) {
-			if (via_copy && P->nrow > 0) {
-				const int64_t ntile = (P->nrow + 63) / 64;
-				dim3 tg((unsigned) (ntile < 8192 ? ntile : 8192), (unsigned) (Kp / 64));
-				hipLaunchKernelGGL(pbc_transpose_dense_kernel, tg, dim3(256), 0, s, Y, ldY, P->nrow, K,
-						   (double *) gen_ws);
-			}
-			// Many column blocks, no row split (A %*% Y on the layout of t(A): 1563 blocks x 2 dense tiles of
-			// 79 panels each): one launch per round of workgroups (a workgroup per CU).  In ONE launch the
-			// workgroups of later rounds start whenever a CU frees up, spread over all panel positions, and
-			// the 5 MB dense tile they all stage no longer fits the XCD's 4 MiB L2 (4030 cycles per panel in
-			// the first round, 4650 later); launch by launch every round starts aligned.
-			const int kt_ = (int) (Kp / 64);
-			int per_launch = 0;
-			if (nsplit == 1 && !pbc_sparing(P, K) && g_pbc_rounds != 0 &&
-			    (int64_t) (P->nblocks - block0) * kt_ >= 2 * pbc_cus())
-				per_launch = pbc_cus() / kt_ > 0 ? pbc_cus() / kt_ : 1;
-			// The last round: `rem` column blocks (54 of 256 CUs busy at config 2b) are cut by rows so that they fill
-			// the chip -- ts row splits of a quarter of the panels each instead of one more full round; their partial
-			// sums go to the (unused: the product writes `out` directly) partials area of the workspace and are summed in
-			// split order behind them.  12.2 rounds then cost 12 + 1 / ts instead of 13.
-			int tail_blocks = 0, ts = 1;
-			int64_t tpps = pps;
-			if (per_launch > 0 && direct && g_pbc_rounds == 1) {
-				const int rem = (int) ((P->nblocks - block0) % per_launch);
-				if (rem > 0 && rem * kt_ * 2 <= pbc_cus()) {
-					ts = pbc_cus() / (rem * kt_);
-					if (ts > 8) ts = 8;
-					while (ts > 1 && P->npanels / ts < 8) ts--;
-					tpps = (P->npanels + ts - 1) / ts;
-					ts = (int) ((P->npanels + tpps - 1) / tpps);
-					const int64_t tcols = (int64_t) rem * 16 * P->CBW;
-					if (ts > 1 && (int64_t) ts * tcols <= P->ncol)      // (fits the partials area: Kp * ncol doubles)
-						tail_blocks = rem;
-				}
-			}
-			const int last_full = (int) P->nblocks - tail_blocks;
-			for (int b0 = block0; b0 < last_full; b0 += per_launch > 0 ? per_launch : (int) P->nblocks) {
-				const int nbl = per_launch > 0 ? (b0 + per_launch <= last_full ? per_launch : last_full - b0)
-							       : tail_blocks > 0 ? last_full - b0 : 0;
-				if (nv == 1) launch_dma<1>(P, Yc, ldc, K, nsplit, pps, part, Kp, fl, s, b0, nbl);
-				else if (nv == 2) launch_dma<2>(P, Yc, ldc, K, nsplit, pps, part, Kp, fl, s, b0, nbl);
-				else launch_dma<3>(P, Yc, ldc, K, nsplit, pps, part, Kp, fl, s, b0, nbl);
-			}
-			if (tail_blocks > 0) {
-				double *tail = (double *) ((char *) ws + PBC_FLAG_BYTES);
-				const int64_t c0 = (int64_t) last_full * 16 * P->CBW;
-				const int64_t tld = (int64_t) tail_blocks * 16 * P->CBW;
-				const int64_t tcols = P->ncol - c0;                  // (the last block may be short)
-				if (nv == 1) launch_dma<1>(P, Yc, ldc, K, ts, tpps, tail, Kp, fl, s, last_full, tail_blocks, tld, c0);
-				else if (nv == 2) launch_dma<2>(P, Yc, ldc, K, ts, tpps, tail, Kp, fl, s, last_full, tail_blocks, tld, c0);
-				else launch_dma<3>(P, Yc, ldc, K, ts, tpps, tail, Kp, fl, s, last_full, tail_blocks, tld, c0);
-				dim3 tg((unsigned) ((tcols + 511) / 512), (unsigned) K);
-				hipLaunchKernelGGL(pbc_tail_reduce_kernel, tg, dim3(256), 0, s, tail, ts, Kp, K, tld, tcols,
-						   out, P->ncol, c0);
-			}
-			HIP_TRY(hipGetLastError());
-			return 0;
+		if (via_copy && P->nrow > 0) {
+			const int64_t ntile = (P->nrow + 63) / 64;
+			dim3 tg((unsigned) (ntile < 8192 ? ntile : 8192), (unsigned) (Kp / 64));
+			hipLaunchKernelGGL(pbc_transpose_dense_kernel, tg, dim3(256), 0, s, Y, ldY, P->nrow, K,
+					   (double *) gen_ws);
 		}
-		// format-1 layouts have no register-staged kernel (row-major Y): general path
-		const int key = P->fmt == 1 ? -1 : nv * 10000 + P->WPB * 100 + P->logR;
-#define PBC_CASE(NV, WPB, LOGR) \
-		case (NV) * 10000 + (WPB) * 100 + (LOGR): \
-			launch_main<NV, WPB, LOGR>(P, Y, ldY, tr_y, K, nsplit, pps, part, Kp, fl, s); break;
-		switch (key) {
-		PBC_CASE(1, 16, 7) PBC_CASE(2, 16, 7)
-		PBC_CASE(1, 16, 8) PBC_CASE(2, 16, 8)
-		PBC_CASE(2, 8, 7) PBC_CASE(3, 8, 7) PBC_CASE(4, 8, 7)
-		PBC_CASE(2, 8, 6) PBC_CASE(4, 4, 5)
-		default:
-			// no panel kernel for this layout: raise the flags that send the whole
-			// product through the general kernels in phase 2
-			HIP_TRY(hipMemsetAsync(ws, 1, 12, s));
+		// Many column blocks, no row split (A %*% Y on the layout of t(A): 1563 blocks x 2 dense tiles of
+		// 79 panels each): one launch per round of workgroups (a workgroup per CU).  In ONE launch the
+		// workgroups of later rounds start whenever a CU frees up, spread over all panel positions, and
+		// the 5 MB dense tile they all stage no longer fits the XCD's 4 MiB L2 (4030 cycles per panel in
+		// the first round, 4650 later); launch by launch every round starts aligned.
+		const int kt_ = (int) (Kp / 64);
+		int per_launch = 0;
+		if (nsplit == 1 && !pbc_sparing(P, K) && g_pbc_rounds != 0 &&
+		    (int64_t) (P->nblocks - block0) * kt_ >= 2 * pbc_cus())
+			per_launch = pbc_cus() / kt_ > 0 ? pbc_cus() / kt_ : 1;
+		// The last round: `rem` column blocks (54 of 256 CUs busy at config 2b) are cut by rows so that they fill
+		// the chip -- ts row splits of a quarter of the panels each instead of one more full round; their partial
+		// sums go to the (unused: the product writes `out` directly) partials area of the workspace and are summed in
+		// split order behind them.  12.2 rounds then cost 12 + 1 / ts instead of 13.
+		int tail_blocks = 0, ts = 1;
+		int64_t tpps = pps;
+		if (per_launch > 0 && direct && g_pbc_rounds == 1) {
+			const int rem = (int) ((P->nblocks - block0) % per_launch);
+			if (rem > 0 && rem * kt_ * 2 <= pbc_cus()) {
+				ts = pbc_cus() / (rem * kt_);
+				if (ts > 8) ts = 8;
+				while (ts > 1 && P->npanels / ts < 8) ts--;
+				tpps = (P->npanels + ts - 1) / ts;
+				ts = (int) ((P->npanels + tpps - 1) / tpps);
+				const int64_t tcols = (int64_t) rem * 16 * P->CBW;
+				if (ts > 1 && (int64_t) ts * tcols <= P->ncol)      // (fits the partials area: Kp * ncol doubles)
+					tail_blocks = rem;
+			}
 		}
-#undef PBC_CASE
+		const int last_full = (int) P->nblocks - tail_blocks;
+		for (int b0 = block0; b0 < last_full; b0 += per_launch > 0 ? per_launch : (int) P->nblocks) {
+			const int nbl = per_launch > 0 ? (b0 + per_launch <= last_full ? per_launch : last_full - b0)
+						       : tail_blocks > 0 ? last_full - b0 : 0;
+			if (nv == 1) launch_dma<1>(P, Yc, ldc, K, nsplit, pps, part, Kp, fl, s, b0, nbl);
+			else if (nv == 2) launch_dma<2>(P, Yc, ldc, K, nsplit, pps, part, Kp, fl, s, b0, nbl);
+			else launch_dma<3>(P, Yc, ldc, K, nsplit, pps, part, Kp, fl, s, b0, nbl);
+		}
+		if (tail_blocks > 0) {
+			double *tail = (double *) ((char *) ws + PBC_FLAG_BYTES);
+			const int64_t c0 = (int64_t) last_full * 16 * P->CBW;
+			const int64_t tld = (int64_t) tail_blocks * 16 * P->CBW;
+			const int64_t tcols = P->ncol - c0;                  // (the last block may be short)
+			if (nv == 1) launch_dma<1>(P, Yc, ldc, K, ts, tpps, tail, Kp, fl, s, last_full, tail_blocks, tld, c0);
+			else if (nv == 2) launch_dma<2>(P, Yc, ldc, K, ts, tpps, tail, Kp, fl, s, last_full, tail_blocks, tld, c0);
+			else launch_dma<3>(P, Yc, ldc, K, ts, tpps, tail, Kp, fl, s, last_full, tail_blocks, tld, c0);
+			dim3 tg((unsigned) ((tcols + 511) / 512), (unsigned) K);
+			hipLaunchKernelGGL(pbc_tail_reduce_kernel, tg, dim3(256), 0, s, tail, ts, Kp, K, tld, tcols,
+					   out, P->ncol, c0);
+		}
 		HIP_TRY(hipGetLastError());
 		return 0;
 	}
+	if (kind == PBC_KIND_NONE) {
+		// general (slow-path) semantics for the whole product: phase 1 raised the flags
+		CrossprodArgs a;
+		memset(&a, 0, sizeof(a));
+		a.col_ptr = A->col_ptr; a.row_idx = A->row_idx; a.val = A->val; a.Rtype = SVT_REALSXP;
+		a.nrow = A->nrow; a.ncol = A->ncol; a.Y = Y; a.ldY = ldY; a.K = K; a.tr_y = tr_y;
+		a.out = out; a.out_stride_c = out_stride_c; a.out_stride_k = out_stride_k;
+		a.ws = gen_ws; a.ws_bytes = gen_bytes;
+		return launch_crossprod_general_if(a, fl.y_nonfinite, false, s);
+	}
 	// Dense columns with NaN / Inf / NA (step 1 rides on the launch below, step 2 is one launch that
-	// returns at once while the product kernel's flag is clear).  The register-staged kernels read the
-	// dense operand as it was given: their dirty columns always take the general kernels.
-	const bool fast = dma || gath;
+	// returns at once while the product kernel's flag is clear).
 	// where the fix-up reads the dense operand: element (r, k) at Yd[r * yrs + k * ycs]
 	const double *Yd = gath ? (const double *) gen_ws : Yc;
 	const int64_t yrs = gath ? Kp : 1, ycs = gath ? 1 : ldc;
 	DirtyScanArgs ds;
 	memset(&ds, 0, sizeof(ds));
 	ds.d = dw;
-	if (fast && P->rec != NULL) {
-		ds.Y = Yd; ds.rs = yrs; ds.cs = ycs; ds.nrow = P->nrow; ds.K = K;
-		ds.nsplit = nsplit; ds.kt = (int) (Kp / 64); ds.pps = dma ? pps : 0;
-	}
+	ds.Y = Yd; ds.rs = yrs; ds.cs = ycs; ds.nrow = P->nrow; ds.K = K;
+	ds.nsplit = nsplit; ds.kt = (int) (Kp / 64); ds.pps = dma ? pps : 0;
 	if (direct) {
 		hipLaunchKernelGGL(pbc_nafix_kernel, dim3((unsigned) ((P->ncol - c_begin + 255) / 256)), dim3(256), 0, s,
 				   P->col_has_na, K, P->ncol, out, out_stride_c, out_stride_k, c_begin, ds);
@@ -2666,29 +2336,16 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 				   P->col_has_na, out, out_stride_c, out_stride_k, c_begin, ds, pairs);
 	}
 	HIP_TRY(hipGetLastError());
-	if (fast && P->rec != NULL) {
-		int n_gen_counters = 0;
-		int *gen_counters = NULL;
-		// one wavefront per leaf, at most ~8 wavefronts per CU's worth of workgroups in flight at a time
-		int64_t nwg = (P->ncol + PBC_DIRTY_WPB - 1) / PBC_DIRTY_WPB;
-		if (nwg > 4096) nwg = 4096;
-		hipLaunchKernelGGL(pbc_dirty_leaf_kernel, dim3((unsigned) nwg), dim3(PBC_DIRTY_WPB * 64),
-				   (size_t) (K + PBC_DIRTY_WPB * PBC_DIRTY_COLS + PBC_DIRTY_WPB * K) * 4, s,
-				   A->col_ptr, A->row_idx, (const double *) A->val, P->col_has_na, Yd, yrs, ycs,
-				   P->ncol, K, dw, out, out_stride_c, out_stride_k, P->max_leaf_nnz,
-				   gen_counters, n_gen_counters);
-		HIP_TRY(hipGetLastError());
-	}
-	if (fast && P->rec != NULL)
-		return 0;                               // (round 5: the leaf kernel above handles every class of dirty column itself)
-	// General (slow-path) semantics for the layouts without the fix-up (register-staged kernels, no record stream).
-	CrossprodArgs a;
-	memset(&a, 0, sizeof(a));
-	a.col_ptr = A->col_ptr; a.row_idx = A->row_idx; a.val = A->val; a.Rtype = SVT_REALSXP;
-	a.nrow = A->nrow; a.ncol = A->ncol; a.Y = Y; a.ldY = ldY; a.K = K; a.tr_y = tr_y;
-	a.out = out; a.out_stride_c = out_stride_c; a.out_stride_k = out_stride_k;
-	a.ws = gen_ws; a.ws_bytes = gen_bytes;
-	return launch_crossprod_general_if(a, fl.y_nonfinite, false, s);
+	// one wavefront per leaf, at most ~8 wavefronts per CU's worth of workgroups in flight at a time
+	int64_t nwg = (P->ncol + PBC_DIRTY_WPB - 1) / PBC_DIRTY_WPB;
+	if (nwg > 4096) nwg = 4096;
+	hipLaunchKernelGGL(pbc_dirty_leaf_kernel, dim3((unsigned) nwg), dim3(PBC_DIRTY_WPB * 64),
+			   (size_t) (K + PBC_DIRTY_WPB * PBC_DIRTY_COLS + PBC_DIRTY_WPB * K) * 4, s,
+			   A->col_ptr, A->row_idx, (const double *) A->val, P->col_has_na, Yd, yrs, ycs,
+			   P->ncol, K, dw, out, out_stride_c, out_stride_k, P->max_leaf_nnz,
+			   (int *) NULL, 0);
+	HIP_TRY(hipGetLastError());
+	return 0;
 }
 
 extern "C" int svt_dev_crossprod_pbc_phase(const svt_dev_pbc *P, const svt_dev_csc *A,

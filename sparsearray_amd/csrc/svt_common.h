@@ -262,4 +262,9 @@ int launch_densify(const int64_t *col_ptr, const int32_t *row_idx,
 // out[j, i] = out[i, j] for i > j (n x n, column-major)
 int launch_mirror_lower(double *out, int64_t n, hipStream_t s);
 void pbc_auto_layout(int64_t nrow, int64_t ncol, int64_t nnz, int *CBW, int *WPB, int *logR);
+// Which product kernel reads the panel-blocked layout (CBW, WPB, logR) of an operand of nrow rows
+// (kernels_mult_pbc.hip): PBC_KIND_BAD = none is built; PBC_KIND_NONE = built without records, the
+// general kernels answer the product.
+enum { PBC_KIND_BAD = -1, PBC_KIND_NONE = 0, PBC_KIND_DMA = 1, PBC_KIND_GATHER = 2 };
+int pbc_kind(int64_t nrow, int CBW, int WPB, int logR);
 int launch_int_to_f64(const int *in, int64_t n, double *out, hipStream_t s);

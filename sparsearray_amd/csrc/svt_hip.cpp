@@ -1142,11 +1142,14 @@ static int chunk_K(int64_t nrow, int64_t K)
 // The panel-blocked layout stores every (column group, 128-row panel) tile as whole batches of
 // 8 records (96 bytes, at least one per tile) plus 8 bytes of tile table: a hypersparse operand
 // (1e6 x 1e6 with 3e7 nonzeros: 20 GB of records for 0.36 GB of CSC) would be streamed at a
-// fraction of the general kernels' speed, and the tile count must fit the 32-bit scan.
+// fraction of the general kernels' speed, and the tile count must fit the 32-bit scan.  And a
+// product kernel must read the layout (pbc_kind: not below 256 rows, for one).
 static bool pbc_shape_ok(int64_t nrow, int64_t ncol, int64_t nnz)
 {
 	int cbw, wpb, logr;
 	pbc_auto_layout(nrow, ncol, nnz, &cbw, &wpb, &logr);      // (very sparse operands: panels of 1024 rows)
+	if (pbc_kind(nrow, cbw, wpb, logr) <= PBC_KIND_NONE)
+		return false;
 	const int64_t cb = (int64_t) cbw * wpb;
 	const double ngroups = (double) ((ncol + cb - 1) / cb) * (double) wpb;
 	const double npanels = (double) ((nrow + ((int64_t) 1 << logr) - 1) >> logr);
@@ -1154,11 +1157,10 @@ static bool pbc_shape_ok(int64_t nrow, int64_t ncol, int64_t nnz)
 	return ntiles + 1.0 < 2147483647.0 && (double) nnz >= 4.0 * ntiles;
 }
 
-static bool pbc_applies(const svt_dev_csc *A, int64_t K, int tr_y)
+// (whatever the orientation of the dense operand: one given by rows is transposed on the device)
+static bool pbc_applies(const svt_dev_csc *A, int64_t K)
 {
-	(void) tr_y;       // a dense operand given by rows is transposed on the device (kernels_mult_pbc.hip)
-	return A->Rtype == SVT_REALSXP && A->nrow >= 256 && A->ncol > 0 &&
-	       (double) A->nnz * (double) K >= 268435456.0 && pbc_shape_ok(A->nrow, A->ncol, A->nnz);
+	return A->ncol > 0 && (double) A->nnz * (double) K >= 268435456.0 && pbc_shape_ok(A->nrow, A->ncol, A->nnz);
 }
 
 // The layout build is device work (a few ms at 1e8 nonzeros) and the upload of the dense
@@ -1168,9 +1170,9 @@ struct PbcAhead {
 	svt_dev_pbc *P = NULL;
 	int own = 1;
 	bool started = false, taken = false;
-	void start(const svt_dev_csc *A, int64_t K, int tr_y)
+	void start(const svt_dev_csc *A, int64_t K)
 	{
-		if (!pbc_applies(A, K, tr_y)) return;
+		if (A->Rtype != SVT_REALSXP || !pbc_applies(A, K)) return;
 		started = true;
 		th = std::thread([this, A] {
 			(void) hipSetDevice(g_device);
@@ -1202,8 +1204,7 @@ static int dev_crossprod_chunked(const svt_dev_csc *A, const void *Y_dev, int64_
 	// of the dense operand (count matrices are integer; see int_to_f64_kernel for why the
 	// results, NA rules included, are those of the integer path -- bit for bit while the sums
 	// stay below 2^53).
-	if (A->Rtype == SVT_INTSXP && !tr_y && ldY == A->nrow && A->nrow >= 256 &&
-	    (double) A->nnz * (double) K >= 268435456.0 && pbc_shape_ok(A->nrow, A->ncol, A->nnz)) {
+	if (A->Rtype == SVT_INTSXP && !tr_y && ldY == A->nrow && pbc_applies(A, K)) {
 		DevBuf V, Yf;
 		if (V.alloc((size_t) (A->nnz > 0 ? A->nnz : 1) * 8) || Yf.alloc((size_t) A->nrow * K * 8) ||
 		    launch_int_to_f64((const int *) A->val, A->nnz, V.as<double>(), 0) ||
@@ -1218,7 +1219,7 @@ static int dev_crossprod_chunked(const svt_dev_csc *A, const void *Y_dev, int64_
 	// pays for itself within the call.  Below the threshold the general kernels run,
 	// whose sums are bit-identical to the reference's sequential ones; above it the
 	// row-split partial sums differ from those in the last bits (parity bar: 1e-6).
-	if (pbc_applies(A, K, tr_y)) {
+	if (A->Rtype == SVT_REALSXP && pbc_applies(A, K)) {
 		int own_P = 1;
 		svt_dev_pbc *P = (ahead && ahead->started) ? ahead->get(&own_P) : pbc_for(A, &own_P);
 		if (P == NULL)                 // e.g. more records than 32-bit stream offsets reach:
@@ -1315,7 +1316,7 @@ static int crossprod2_SVT_mat_impl(const svt_view *x, const void *y, int y_nrow,
 	if (A.h == NULL) return -1;
 	DevBuf Y, O;
 	PbcAhead ahead;
-	ahead.start(A.h, out_ncol, tr_y);
+	ahead.start(A.h, out_ncol);
 	if (Y.upload(y, (size_t) y_nrow * y_ncol * elt_size(y_Rtype)) ||
 	    O.alloc(out_n * 8) || O.zero())
 		return -1;
@@ -1357,7 +1358,7 @@ static int crossprod2_mat_SVT_impl(const void *x, int x_nrow, int x_ncol,
 	if (A.h == NULL) return -1;
 	DevBuf X, O;
 	PbcAhead ahead;
-	ahead.start(A.h, out_nrow, tr_x);
+	ahead.start(A.h, out_nrow);
 	if (X.upload(x, (size_t) x_nrow * x_ncol * elt_size(x_Rtype)) ||
 	    O.alloc(out_n * 8) || O.zero())
 		return -1;
@@ -1388,8 +1389,7 @@ static int dev_crossprod_pp(const svt_dev_csc *other, const svt_dev_csc *pp,
 	const int64_t K = pp->ncol, nrow = pp->nrow;
 	if (K <= 0 || other->ncol <= 0)
 		return 0;
-	const bool big = nrow >= 256 && (double) other->nnz * (double) K >= 268435456.0 &&
-			 pbc_shape_ok(other->nrow, other->ncol, other->nnz);
+	const bool big = pbc_applies(other, K);
 	if (other->Rtype == SVT_INTSXP && big) {                         // as in dev_crossprod_chunked
 		DevBuf V1, V2;
 		if (V1.alloc((size_t) (other->nnz > 0 ? other->nnz : 1) * 8) ||
@@ -1724,7 +1724,7 @@ static int matmul_SVT_mat_impl(const svt_view *x, const void *y, int y_nrow,
 	A.drop();                           // a one-call operand: its untransposed copy can go now
 	DevBuf Y, O;
 	PbcAhead ahead;
-	ahead.start(T, y_ncol, 0);
+	ahead.start(T, y_ncol);
 	if (Y.upload(y, (size_t) y_nrow * y_ncol * elt_size(y_Rtype)) ||
 	    O.alloc(out_n * 8) || O.zero())
 		return -1;

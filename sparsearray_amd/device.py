@@ -201,10 +201,14 @@ class CrossprodPlan:
 
 class PbcPlan:
     """Fast path of crossprod(A, Y) for f64: panel-blocked copy of A (built
-    once, here) + workspace for K dense columns."""
+    once, here) + workspace for K dense columns.
+
+    Layouts (CBW, WPB, logR), 1 <= CBW <= 40: (CBW, 16, 7) for the LDS-DMA kernel,
+    (CBW, 4, 9..15) for the gather kernels, (0, 0, 0) to let the library pick one
+    by density.  Any other layout raises SparseArrayError.  Below 256 rows an
+    LDS-DMA layout holds no records and the general kernels answer the product."""
 
     def __init__(self, A: DeviceCSC, K: int, CBW: int = 40, WPB: int = 16, logR: int = 7):
-        # (0, 0, 0): the library picks the layout by density (LDS-DMA kernel or gather kernel)
         assert A.Rtype == REALSXP
         self.A, self.K = A, int(K)
         self._p = _lib().svt_dev_pbc_build(A.handle, CBW, WPB, logR)

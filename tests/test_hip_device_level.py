@@ -16,8 +16,7 @@ def _dev(cp, ri, v, nrow):
     return DeviceCSC.from_host(nrow, cp, ri, v)
 
 
-@pytest.mark.parametrize("cfg", [(32, 16, 7), (16, 16, 7), (40, 16, 7), (24, 16, 7), (5, 16, 7), (48, 8, 7),
-                                 (64, 8, 7), (32, 8, 6), (64, 4, 5), (32, 16, 8), (20, 16, 8)])
+@pytest.mark.parametrize("cfg", [(32, 16, 7), (16, 16, 7), (40, 16, 7), (24, 16, 7), (5, 16, 7)])
 @pytest.mark.parametrize("shape", [(5000, 300, 70), (70000, 1100, 128), (300, 17, 5), (4096, 700, 64),
                                    (1281, 90, 3), (1282, 90, 130)])
 def test_pbc_crossprod_matches_oracle(hip, oracle, cfg, shape):
@@ -41,6 +40,48 @@ def test_pbc_crossprod_matches_oracle(hip, oracle, cfg, shape):
     plan.run(Yr, K, out2, stride_c=K, stride_k=1, tr_y=True)
     torch.cuda.synchronize()
     assert_equal(out2.cpu().numpy(), want, tol=1e-9, atol=1e-11, what="pbc crossprod tr")
+
+
+@pytest.mark.parametrize("cfg", [(48, 8, 7), (32, 16, 8), (48, 4, 9), (64, 4, 10), (40, 4, 8)])
+def test_pbc_refuses_layouts_no_kernel_reads(hip, cfg):
+    """Only (CBW <= 40, 16, 7) and (CBW <= 40, 4, 9..15) have a product kernel (the gather kernels keep 40
+    columns per wavefront: a wider group would leave its columns past 40 uncomputed)."""
+    from sparsearray_amd.api import SparseArrayError
+    from sparsearray_amd.device import PbcPlan
+    nrow, ncol = 5000, 300
+    A = _dev(*random_csc(nrow, ncol, 0.01, seed=25), nrow)
+    with pytest.raises(SparseArrayError, match="no product kernel reads the layout"):
+        PbcPlan(A, 16, *cfg)
+
+
+def test_pbc_below_256_rows_runs_the_general_kernels(hip, oracle):
+    """Below 256 rows the LDS-DMA layout is built without records (pbc_kind: PBC_KIND_NONE) and the general
+    kernels, which add in the reference's order, answer every product, NaN or not."""
+    import ctypes
+    from sparsearray_amd.device import CrossprodPlan, PbcPlan, _lib
+    nrow, ncol, K = 200, 90, 24
+    cp, ri, v = random_csc(nrow, ncol, 0.2, seed=26)
+    x = SVT_SparseArray.from_csc((nrow, ncol), "double", cp, ri, v)
+    A = _dev(cp, ri, v, nrow)
+    plan = PbcPlan(A, K)
+    lib = _lib()
+    lib.svt_dev_pbc_bytes.restype = ctypes.c_size_t
+    lib.svt_dev_pbc_bytes.argtypes = [ctypes.c_void_p]
+    assert lib.svt_dev_pbc_bytes(plan._p) < 12 * len(ri)       # a record stream takes >= 12 bytes per nonzero
+    rng = np.random.default_rng(27)
+    for poison in (False, True):
+        y = rng.uniform(-1, 1, (nrow, K))
+        if poison:
+            y[nrow // 3, 5] = np.nan
+        Yd = torch.as_tensor(np.ascontiguousarray(y.T), device="cuda")
+        out = torch.full((K, ncol), 7.0, dtype=torch.float64, device="cuda")
+        plan.run(Yd, nrow, out)
+        gen = torch.full((K, ncol), 5.0, dtype=torch.float64, device="cuda")
+        CrossprodPlan(A, K).run(Yd, nrow, gen)
+        torch.cuda.synchronize()
+        assert_equal(out.cpu().numpy().T, oracle.crossprod(x, y), tol=1e-9, atol=1e-11, strict_na=True,
+                     what=f"poison={poison}")
+        assert np.array_equal(out.cpu().numpy(), gen.cpu().numpy(), equal_nan=True), f"poison={poison}"
 
 
 def test_pbc_special_values_take_general_path(hip, oracle):

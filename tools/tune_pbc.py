@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Tuning harness for the PBC crossprod kernel (run on the GPU box):
-times the kernel for several (CBW, WPB, logR) and, with --ablate, the
-timing-only builds (no staging / no record loop)."""
+"""Tuning harness for the PBC crossprod kernels (run on the GPU box):
+times the product for several layouts (CBW, WPB, logR), row-split counts,
+DMA issue staggers and record-touch look-aheads."""
 import argparse
 import os
 import sys
@@ -20,8 +20,7 @@ p.add_argument("--nrow", type=int, default=1_000_000)
 p.add_argument("--ncol", type=int, default=10_000)
 p.add_argument("--density", type=float, default=0.01)
 p.add_argument("--K", type=int, default=128)
-p.add_argument("--cfgs", default="32,16,8")
-p.add_argument("--ablate", action="store_true")
+p.add_argument("--cfgs", default="40,16,7")
 p.add_argument("--prof", action="store_true", help="per-section cycle counts of workgroup 0")
 p.add_argument("--reps", type=int, default=5)
 p.add_argument("--nsplits", default="0")
@@ -61,12 +60,9 @@ for cfg in a.cfgs.split(";"):
         lib.svt_dev_pbc_set_debug(200 + stg)
         del plan
         plan = PbcPlan(A, a.K, cbw, wpb, logr)      # workspace depends on the split count
-        for mode, name in ((0, "full"), (2, "no-compute")):
-            if mode and not a.ablate:
-                continue
-            lib.svt_dev_pbc_set_debug(mode)
-            ms = timed(lambda: plan.run(Y, 0 if a.ldy0 else a.nrow, out), a.reps)
-            row.append(f"[nsplit {ns} stagger {stg} ahead {ah}] {name} {ms:.3f} ms ({A.nnz / ms / 1e6:.1f} GNZ/s)")
+        lib.svt_dev_pbc_set_debug(0)
+        ms = timed(lambda: plan.run(Y, 0 if a.ldy0 else a.nrow, out), a.reps)
+        row.append(f"[nsplit {ns} stagger {stg} ahead {ah}] {ms:.3f} ms ({A.nnz / ms / 1e6:.1f} GNZ/s)")
         if a.prof:
             import ctypes
             lib.svt_dev_pbc_set_debug(3)
@@ -75,7 +71,7 @@ for cfg in a.cfgs.split(";"):
             lib.svt_dev_pbc_read_prof.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
             assert lib.svt_dev_pbc_read_prof(plan.ws.data_ptr(), buf) == 0
             row.append(f"\n  prof build {ms:.3f} ms; per wavefront cycles "
-                       "[fetch|records, records|dma-wait, barrier1|barrier, commit|issue, barrier2|prescan, panels] (register-staged|DMA kernel):")
+                       "[-, dma-wait, barrier, issue, prescan, dispatch, stub, phases] (LDS-DMA kernel):")
             for w in range(wpb):
                 row.append("\n    w%02d " % w + " ".join("%9d" % buf[w * 8 + i] for i in range(8)))
         lib.svt_dev_pbc_set_debug(0)
