@@ -106,11 +106,39 @@ typedef struct svt_view {
 
 /* Selects the HIP device for the calling process (one process per GPU).
    Returns 0, or -1 when no gfx950 device is usable.  Called implicitly with
-   device 0 by the first host-level call. */
+   device 0 by the first host-level call.  Sets the device list below to {device}. */
 int svt_init(int device);
 const char *svt_last_error(void);
 /* "gfx950" etc. of the selected device, or "" before svt_init(). */
 const char *svt_device_arch(void);
+
+/*
+ * Device list of the host-level entry points (one process, several GPUs).  With more than one entry, four entry
+ * points split an operand of at least svt_set_shard_min_nnz() nonzeros over the listed devices, one host thread,
+ * pinned staging buffer pair and set of device buffers per entry:
+ *   svt_crossprod2_SVT_mat  row blocks of x and y (boundaries at multiples of 128 rows); every shard forms a whole
+ *                           ncol(x) x K partial, then a reduce-scatter: shard s fetches slice s of every partial,
+ *                           adds them in list order ((p0 + p1) + p2) + ..., and copies the slice into `out`.  The
+ *                           sums depend on the list's length and the row blocks only: {0,1} gives the bits of {0,0}.
+ *   svt_matmul_SVT_mat      the same row blocks of x, y replicated; each shard writes its rows of `out`.
+ *   svt_colStats_SVT        ranges of output cells balanced by nonzeros; each shard writes its slice; warn ORed.
+ *   svt_rowsum_SVT          leaf ranges balanced by nonzeros; each shard writes its columns; ovflow ORed.
+ * Every other entry point, and these below the threshold, run on the first entry as with one device.  A shard that
+ * fails makes the call fail with its message; else a shard that answers > 0 makes the call answer > 0.  Sharded
+ * calls do not use the resident cache (svt_resident_set_limit): they upload their parts and free them.  With a
+ * one-entry list the entry points run exactly the one-device code.  The marshalling threads of svt_set_max_threads()
+ * are divided among the shards (at least one each); the 96 MB of pinned staging buffers of the sharded path are
+ * divided too (48 MB / N per buffer, two per shard), next to the 96 MB of the one-device path.
+ * Ordinals may repeat ({0,0,0,0}: four shards on device 0).  Peer access is enabled between distinct ordinals.
+ * No run on more than one physical device exists yet.
+ */
+/* 0, or -1 (svt_last_error()) when an ordinal is out of range or not gfx950, or n > 16: the previous list stays.
+   n == 0: back to {the device of the last svt_init()}.  The first entry becomes the calling thread's device. */
+int svt_set_devices(const int *ordinals, int n);
+/* Length of the list (0 before svt_init()); fills up to cap entries of ordinals. */
+int svt_get_devices(int *ordinals, int cap);
+/* Operands with fewer nonzeros stay on the first device (default 2^24, an unmeasured guess); 0 = always shard. */
+void svt_set_shard_min_nnz(int64_t nnz);
 
 /*
  * Resident operands (off by default).  R code calls the entry points below over and over

@@ -96,6 +96,37 @@ SEXP C_set_max_threads_cpu(SEXP);
 static void *hip_lib;           /* NULL: not tried yet; (void *) -1: unavailable */
 #define HIP_FN(name) ((__typeof__(&name)) dlsym(hip_lib, #name))
 
+/* SPARSEARRAY_HIP_DEVICES="0,1,2,3": the device list of the library (svt_set_devices, include/svt_hip.h), 1 to 16
+   ordinals >= 0 separated by commas.  Returns the count, or 0 for an absent or malformed value (the one-device
+   default stays). */
+static int hip_parse_devices(const char *s, int *ord)
+{
+	int n = 0;
+	if (s == NULL || s[0] == '\0')
+		return 0;
+	for (;;) {
+		long v = 0;
+		const char *p = s;
+		while (*p == ' ') p++;
+		if (*p < '0' || *p > '9')
+			return 0;
+		while (*p >= '0' && *p <= '9') {
+			v = v * 10 + (*p - '0');
+			if (v > 65535) return 0;
+			p++;
+		}
+		while (*p == ' ') p++;
+		if (n == 16)
+			return 0;
+		ord[n++] = (int) v;
+		if (*p == '\0')
+			return n;
+		if (*p != ',')
+			return 0;
+		s = p + 1;
+	}
+}
+
 static int hip_available(void)
 {
 	if (hip_lib == NULL) {
@@ -105,8 +136,17 @@ static int hip_available(void)
 			hip_lib = (void *) -1;
 		} else {
 			hip_lib = dlopen(path ? path : "libsvt_hip.so", RTLD_NOW | RTLD_LOCAL);
-			if (hip_lib == NULL || HIP_FN(svt_init)(0) != 0)
+			if (hip_lib == NULL || HIP_FN(svt_init)(0) != 0) {
 				hip_lib = (void *) -1;
+			} else {
+				/* several GPUs for one R process (an older library has no svt_set_devices: nothing happens;
+				   a list the library refuses leaves its one-device default) */
+				int ord[16];
+				const int n = hip_parse_devices(getenv("SPARSEARRAY_HIP_DEVICES"), ord);
+				__typeof__(&svt_set_devices) set_devices = HIP_FN(svt_set_devices);
+				if (n > 0 && set_devices != NULL)
+					(void) set_devices(ord, n);
+			}
 		}
 	}
 	return hip_lib != (void *) -1;

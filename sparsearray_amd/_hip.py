@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libsvt_hip_tuning.so" if os.environ.get("SVT_HIP
 
 # Every symbol include/svt_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
-    "svt_init", "svt_last_error", "svt_device_arch",
+    "svt_init", "svt_last_error", "svt_device_arch", "svt_set_devices", "svt_get_devices", "svt_set_shard_min_nnz",
     "svt_crossprod2_SVT_mat", "svt_crossprod2_mat_SVT",
     "svt_crossprod2_SVT_SVT", "svt_crossprod1_SVT",
     "svt_matmul_SVT_mat", "svt_matmul_SVT_SVT", "svt_tcrossprod1_SVT", "svt_tcrossprod2_SVT_SVT",
@@ -79,6 +79,34 @@ def init(device: int | None = None) -> ctypes.CDLL:
             raise HipBackendError(lib.svt_last_error().decode())
         _ready = True
     return lib
+
+
+def set_devices(ordinals) -> None:
+    """Device list of the host-level entry points (include/svt_hip.h, svt_set_devices): more than one entry
+    shards crossprod(x, y), x %*% y, the col statistics and rowsum() over them; repeated ordinals are separate
+    shards on one device; [] restores the device of init()."""
+    lib = init()
+    ords = [int(d) for d in ordinals]
+    arr = (ctypes.c_int * max(1, len(ords)))(*ords)
+    lib.svt_set_devices.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    if lib.svt_set_devices(arr, len(ords)) != 0:
+        raise HipBackendError(lib.svt_last_error().decode())
+
+
+def get_devices() -> list:
+    lib = init()
+    lib.svt_get_devices.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    arr = (ctypes.c_int * 16)()
+    n = lib.svt_get_devices(arr, 16)
+    return [arr[i] for i in range(min(n, 16))]
+
+
+def set_shard_min_nnz(n: int) -> None:
+    """Operands with fewer nonzeros stay on the first device of the list (0: always shard)."""
+    lib = init()
+    lib.svt_set_shard_min_nnz.argtypes = [ctypes.c_int64]
+    lib.svt_set_shard_min_nnz.restype = None
+    lib.svt_set_shard_min_nnz(int(n))
 
 
 def hip_dispatcher():

@@ -47,6 +47,8 @@
 
 #include <string.h>
 
+#include <mutex>
+
 #include "svt_scan.h"
 
 typedef double d16 __attribute__((ext_vector_type(16)));
@@ -528,10 +530,13 @@ __global__ void pbc_build_finish_kernel(int64_t *__restrict__ tile_ptr, int64_t 
 static hipMemPool_t g_pbc_pool[PBC_MAX_DEV];
 static bool g_pbc_pool_ok[PBC_MAX_DEV];
 
+static std::mutex g_pbc_pool_mu;          // (the shards of a sharded host call build layouts concurrently)
+
 static hipMemPool_t pbc_pool(int dev)
 {
 	if (dev < 0 || dev >= PBC_MAX_DEV)
 		return NULL;
+	std::lock_guard<std::mutex> lk(g_pbc_pool_mu);
 	if (!g_pbc_pool_ok[dev]) {
 		hipMemPoolProps props;
 		memset(&props, 0, sizeof(props));

@@ -268,3 +268,7 @@ void pbc_auto_layout(int64_t nrow, int64_t ncol, int64_t nnz, int *CBW, int *WPB
 enum { PBC_KIND_BAD = -1, PBC_KIND_NONE = 0, PBC_KIND_DMA = 1, PBC_KIND_GATHER = 2 };
 int pbc_kind(int64_t nrow, int CBW, int WPB, int logR);
 int launch_int_to_f64(const int *in, int64_t n, double *out, hipStream_t s);
+// kernels_shard.hip: the sharded host entry points (svt_set_devices).  out = ((p_0 + p_1) + ...) + p_{nparts-1}
+// elementwise, part t at parts + t * stride (stride even, >= n); and idx[k] -= base for k < n.
+int launch_shard_sum(const double *parts, int nparts, int64_t stride, int64_t n, double *out, hipStream_t s);
+int launch_rebase_rows(int32_t *idx, int64_t n, int32_t base, hipStream_t s);

@@ -14,6 +14,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <chrono>
 #include <vector>
 
 static thread_local char g_err[1024];
@@ -51,7 +53,7 @@ static inline int svt_status(int rc)
 extern "C" const char *svt_last_error(void) { return g_err; }
 extern "C" const char *svt_device_arch(void) { return g_arch; }
 
-extern "C" int svt_init(int device)
+static int select_device(int device)
 {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
@@ -70,6 +72,89 @@ extern "C" int svt_init(int device)
 	g_device = device;
 	return 0;
 }
+
+// ---- the device list of the host-level entry points (svt_set_devices) --------------------------------
+// One entry (what svt_init() sets): every entry point runs on that device, as it always did.  More entries:
+// the four sharded entry points split their operand over them, one host thread per entry (repeated ordinals
+// are separate shards on one device); the others run on the first entry.
+#define SVT_MAX_SHARDS 16
+static std::vector<int> g_devices;             // empty until svt_init()
+static int g_init_device = -1;                 // device of the last svt_init()
+// Operands with fewer nonzeros stay on the first device.  A guess, not a measurement: no run on more than one
+// physical device exists yet; below ~1.6e7 nonzeros the upload of one shard is a few ms over one PCIe link.
+static int64_t g_shard_min_nnz = (int64_t) 1 << 24;
+
+extern "C" int svt_init(int device)
+{
+	if (select_device(device))
+		return -1;
+	g_devices.assign(1, device);
+	g_init_device = device;
+	return 0;
+}
+
+extern "C" int svt_set_devices(const int *ordinals, int n)
+{
+	if (n == 0)
+		return svt_init(g_init_device >= 0 ? g_init_device : 0);
+	if (n < 0 || n > SVT_MAX_SHARDS || ordinals == NULL)
+		return svt_set_error("svt_set_devices: between 1 and %d devices", SVT_MAX_SHARDS);
+	int cnt = 0;
+	if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
+		return svt_set_error("libsvt_hip: no HIP device visible -- the SVT "
+				     "backend has no CPU fallback");
+	for (int i = 0; i < n; i++) {
+		const int d = ordinals[i];
+		if (d < 0 || d >= cnt)
+			return svt_set_error("svt_set_devices: device %d out of range (0..%d)", d, cnt - 1);
+		hipDeviceProp_t prop;
+		HIP_TRY(hipGetDeviceProperties(&prop, d));
+		if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+			return svt_set_error("svt_set_devices: device %d is %s; this library "
+					     "carries gfx950 (MI355X) code only", d, prop.gcnArchName);
+	}
+	// peer access between distinct ordinals (the reduce-scatter's copies); a pair without it still copies,
+	// through the runtime
+	std::vector<int> distinct;
+	for (int i = 0; i < n; i++)
+		if (std::find(distinct.begin(), distinct.end(), ordinals[i]) == distinct.end())
+			distinct.push_back(ordinals[i]);
+	for (int a : distinct)
+		for (int b : distinct) {
+			int ok = 0;
+			if (a == b || hipDeviceCanAccessPeer(&ok, a, b) != hipSuccess || !ok) continue;
+			if (hipSetDevice(a) == hipSuccess && hipDeviceEnablePeerAccess(b, 0) != hipSuccess)
+				(void) hipGetLastError();        // hipErrorPeerAccessAlreadyEnabled among them
+		}
+	if (select_device(ordinals[0])) {
+		if (g_device >= 0) (void) hipSetDevice(g_device);
+		return -1;
+	}
+	g_devices.assign(ordinals, ordinals + n);
+	return 0;
+}
+
+extern "C" int svt_get_devices(int *ordinals, int cap)
+{
+	const int n = (int) g_devices.size();
+	for (int i = 0; i < n && i < cap; i++)
+		if (ordinals) ordinals[i] = g_devices[(size_t) i];
+	return n;
+}
+
+extern "C" void svt_set_shard_min_nnz(int64_t nnz)
+{
+	g_shard_min_nnz = nnz > 0 ? nnz : 0;
+}
+
+// The shard a worker thread of a sharded call runs (NULL on every other thread): its slot, the number of
+// shards, its device.  Stager, marshalling team and helper threads follow it.
+struct ShardCtx {
+	int slot, nshard, device;
+};
+static thread_local const ShardCtx *t_shard = NULL;
+
+static int cur_device() { return t_shard ? t_shard->device : g_device; }
 
 // ---- thread control (src/thread_control.c:47-66) ---------------------------------
 static int g_max_threads = 0;
@@ -111,6 +196,8 @@ static int ensure_init()
 
 struct Stager {
 	static const size_t CHUNK = (size_t) 48 << 20;      // bytes per pinned buffer
+	size_t chunk = CHUNK;                                // (a shard's stager: CHUNK / number of shards)
+	int dev = -1;                                        // device of `stream` (shard stagers)
 	char *buf[2] = {NULL, NULL};
 	hipEvent_t done[2];
 	hipStream_t stream = NULL;
@@ -122,7 +209,7 @@ struct Stager {
 	{
 		if (ok) return 0;
 		for (int i = 0; i < 2; i++) {
-			HIP_TRY(hipHostMalloc((void **) &buf[i], CHUNK, hipHostMallocDefault));
+			HIP_TRY(hipHostMalloc((void **) &buf[i], chunk, hipHostMallocDefault));
 			HIP_TRY(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
 		}
 		HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -157,8 +244,31 @@ struct Stager {
 		busy[0] = busy[1] = false;
 		return 0;
 	}
+	// a shard stager: buffers of `bytes` on device `d` -- kept from call to call, rebuilt when either changes
+	void use(size_t bytes, int d)
+	{
+		if (ok && (bytes != chunk || d != dev)) {
+			(void) hipStreamSynchronize(stream);
+			(void) hipStreamDestroy(stream);
+			for (int i = 0; i < 2; i++) {
+				(void) hipEventDestroy(done[i]);
+				(void) hipHostFree(buf[i]);
+				buf[i] = NULL;
+			}
+			ok = false;
+			next = 0;
+			busy[0] = busy[1] = false;
+		}
+		chunk = bytes;
+		dev = d;
+	}
 };
+// The one-device path stages through g_stager (2 x 48 MB pinned).  Shard s of a sharded call stages through
+// g_shard_stager[s], whose two buffers hold 48 MB / N each: 96 MB pinned for all shards together whatever N
+// (2 x 6 MB per shard at N = 8), next to the 96 MB of g_stager.
 static Stager g_stager;
+static Stager g_shard_stager[SVT_MAX_SHARDS];
+static Stager &cur_stager() { return t_shard ? g_shard_stager[t_shard->slot] : g_stager; }
 
 // Bytes of a pinned buffer used per trip.  SVT_STAGING_CHUNK (bytes, read once) lowers it so
 // that a test can drive the multi-chunk paths -- a leaf longer than a chunk among them --
@@ -174,7 +284,7 @@ static size_t g_stager_chunk()
 			if (t >= 4096 && (size_t) t < Stager::CHUNK) v = (size_t) t / 4096 * 4096;
 		}
 	}
-	return v;
+	return v < cur_stager().chunk ? v : cur_stager().chunk;
 }
 
 // run fn(t, nt) on a small team (the calling thread is one of them)
@@ -189,6 +299,7 @@ static void team_run(int nt, const std::function<void(int, int)> &fn)
 static int team_size(size_t bytes)
 {
 	int nt = svt_get_max_threads();
+	if (t_shard) nt /= t_shard->nshard;                 // the shards' teams share the caller's thread count
 	if (nt > 8) nt = 8;
 	if (bytes < ((size_t) 4 << 20) || nt < 1) nt = 1;
 	return nt;
@@ -201,18 +312,46 @@ static int staged_copy(void *dst, const void *src, size_t n)
 		if (n) HIP_TRY(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
 		return 0;
 	}
-	for (size_t off = 0; off < n; off += Stager::CHUNK) {
-		const size_t len = n - off < Stager::CHUNK ? n - off : Stager::CHUNK;
+	Stager &st = cur_stager();
+	for (size_t off = 0; off < n; off += st.chunk) {
+		const size_t len = n - off < st.chunk ? n - off : st.chunk;
 		char *b; int slot;
-		if (g_stager.acquire(&b, &slot)) return -1;
+		if (st.acquire(&b, &slot)) return -1;
 		const char *s0 = (const char *) src + off;
 		team_run(team_size(len), [&](int t, int nt) {
 			const size_t a = len * t / nt, e = len * (t + 1) / nt;
 			memcpy(b + a, s0 + a, e - a);
 		});
-		if (g_stager.send(slot, (char *) dst + off, 0, len) || g_stager.commit(slot)) return -1;
+		if (st.send(slot, (char *) dst + off, 0, len) || st.commit(slot)) return -1;
 	}
-	return g_stager.drain();
+	return st.drain();
+}
+
+// ncols runs of `run` bytes, `ld` bytes apart on the host (rows [r0, r1) of a column-major matrix), -> one
+// contiguous device array, through the pinned buffers
+static int staged_copy_2d(void *dst, const void *src, size_t run, size_t ncols, size_t ld)
+{
+	if (run == ld || ncols <= 1)
+		return staged_copy(dst, src, run * ncols);
+	const size_t n = run * ncols;
+	Stager &st = cur_stager();
+	for (size_t off = 0; off < n; off += st.chunk) {
+		const size_t len = n - off < st.chunk ? n - off : st.chunk;
+		char *b; int slot;
+		if (st.acquire(&b, &slot)) return -1;
+		team_run(team_size(len), [&](int t, int nt) {
+			size_t a = off + len * t / nt;
+			const size_t e = off + len * (t + 1) / nt;
+			while (a < e) {                     // piece of column a / run
+				const size_t c = a / run, in = a - c * run;
+				const size_t m = std::min(run - in, e - a);
+				memcpy(b + (a - off), (const char *) src + c * ld + in, m);
+				a += m;
+			}
+		});
+		if (st.send(slot, (char *) dst + off, 0, len) || st.commit(slot)) return -1;
+	}
+	return st.drain();
 }
 
 // device -> contiguous host array: D2H into one pinned buffer while the thread team
@@ -224,21 +363,22 @@ static int staged_download(void *dst, const void *src, size_t n)
 		if (n) HIP_TRY(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
 		return 0;
 	}
-	if (g_stager.init() || g_stager.drain()) return -1;
+	Stager &st = cur_stager();
+	if (st.init() || st.drain()) return -1;
 	HIP_TRY(hipDeviceSynchronize());            // the producer kernels ran on other streams
-	const size_t C = Stager::CHUNK;
+	const size_t C = st.chunk;
 	const size_t nchunk = (n + C - 1) / C;
 	for (size_t c = 0; c <= nchunk; c++) {
 		if (c < nchunk) {                   // start chunk c into buffer c & 1
 			const size_t off = c * C, len = n - off < C ? n - off : C;
-			HIP_TRY(hipMemcpyAsync(g_stager.buf[c & 1], (const char *) src + off, len,
-					       hipMemcpyDeviceToHost, g_stager.stream));
-			HIP_TRY(hipEventRecord(g_stager.done[c & 1], g_stager.stream));
+			HIP_TRY(hipMemcpyAsync(st.buf[c & 1], (const char *) src + off, len,
+					       hipMemcpyDeviceToHost, st.stream));
+			HIP_TRY(hipEventRecord(st.done[c & 1], st.stream));
 		}
 		if (c > 0) {                        // chunk c - 1 has landed: copy it out
 			const size_t off = (c - 1) * C, len = n - off < C ? n - off : C;
-			HIP_TRY(hipEventSynchronize(g_stager.done[(c - 1) & 1]));
-			const char *b = g_stager.buf[(c - 1) & 1];
+			HIP_TRY(hipEventSynchronize(st.done[(c - 1) & 1]));
+			const char *b = st.buf[(c - 1) & 1];
 			char *d0 = (char *) dst + off;
 			team_run(team_size(len), [&](int t, int nt) {
 				const size_t a = len * t / nt, e = len * (t + 1) / nt;
@@ -353,10 +493,11 @@ extern "C" svt_dev_csc *svt_upload(const svt_view *x)
 	// exceed CHUNK / 12), and the team splits a chunk evenly whatever the leaf lengths are.
 	const int64_t cap = (int64_t) (g_stager_chunk() / (4 + esz));
 	const int64_t nnz = d->nnz;
+	Stager &st = cur_stager();
 	for (int64_t k0 = 0; ok && k0 < nnz; k0 += cap) {
 		const int64_t cnt = nnz - k0 < cap ? nnz - k0 : cap;
 		char *b; int slot;
-		if (g_stager.acquire(&b, &slot)) { ok = false; break; }
+		if (st.acquire(&b, &slot)) { ok = false; break; }
 		int32_t *so = (int32_t *) b;
 		char *sv = b + (size_t) cnt * 4;
 		team_run(team_size((size_t) cnt * (4 + esz)), [&](int t, int nt) {
@@ -383,12 +524,12 @@ extern "C" svt_dev_csc *svt_upload(const svt_view *x)
 				}
 			}
 		});
-		ok = g_stager.send(slot, d->row_idx + k0, 0, (size_t) cnt * 4) == 0 &&
-		     g_stager.send(slot, (char *) d->val + (size_t) k0 * esz, (size_t) cnt * 4,
+		ok = st.send(slot, d->row_idx + k0, 0, (size_t) cnt * 4) == 0 &&
+		     st.send(slot, (char *) d->val + (size_t) k0 * esz, (size_t) cnt * 4,
 				   (size_t) cnt * esz) == 0 &&
-		     g_stager.commit(slot) == 0;
+		     st.commit(slot) == 0;
 	}
-	if (ok) ok = g_stager.drain() == 0;
+	if (ok) ok = st.drain() == 0;
 	if (!ok) {
 		if (svt_last_error()[0] == '\0') svt_set_error("H2D copy failed");
 		svt_release(d);
@@ -1111,6 +1252,182 @@ extern "C" int svt_dev_rowsum_prepared(const svt_dev_csc *A, const void *gid, in
 }
 
 // ==================================================================================
+// Sharded host entry points (svt_set_devices)
+// ==================================================================================
+// With more than one device in the list and an operand of at least svt_set_shard_min_nnz() nonzeros,
+// crossprod2_SVT_mat and matmul_SVT_mat split the operand into row blocks, colStats and rowsum into leaf ranges.
+// Shard s runs on a host thread of its own, on device g_devices[s], with its own stager and 1/N of the marshalling
+// threads.  It uploads its part of the operand and frees it again: sharded calls do not use the resident cache.
+static int64_t view_nzcount(const svt_view *x);
+
+static bool shard_applies(const svt_view *x)
+{
+	return t_shard == NULL && g_devices.size() > 1 && view_nzcount(x) >= g_shard_min_nnz;
+}
+
+// Runs fn(s) for every shard and joins every thread.  Status: a shard < 0 makes the call < 0 with that shard's
+// message (the first in shard order); else a shard refused (> 0 at the ABI) makes the call refused.
+// SVT_SHARD_REFUSE=<slot> (read at every call; tests) makes that shard refuse.
+template <class F> static int run_shards(const std::vector<int> &devs, F fn)
+{
+	const int N = (int) devs.size();
+	struct Res {
+		int rc, unsupported;
+		char err[sizeof(g_err)];
+	};
+	std::vector<Res> res((size_t) N);
+	const size_t chunk = Stager::CHUNK / (size_t) N / 4096 * 4096;
+	const char *refuse = getenv("SVT_SHARD_REFUSE");
+	const int refuse_slot = refuse != NULL && refuse[0] != '\0' ? atoi(refuse) : -1;
+	auto body = [&](int s) {
+		const ShardCtx ctx = { s, N, devs[(size_t) s] };
+		t_shard = &ctx;
+		g_err[0] = '\0';
+		g_unsupported = 0;
+		int rc;
+		if (s == refuse_slot) {
+			rc = svt_set_unsupported("shard %d refused the call (SVT_SHARD_REFUSE)", s);
+		} else if (hipSetDevice(ctx.device) != hipSuccess) {
+			rc = svt_set_error("shard %d: hipSetDevice(%d) failed", s, ctx.device);
+		} else {
+			g_shard_stager[s].use(chunk, ctx.device);
+			rc = fn(s);
+		}
+		Res &r = res[(size_t) s];
+		r.rc = rc;
+		r.unsupported = rc < 0 && g_unsupported;
+		memcpy(r.err, g_err, sizeof(g_err));
+		t_shard = NULL;
+	};
+	std::vector<std::thread> th;
+	for (int s = 0; s < N; s++) th.emplace_back(body, s);
+	for (auto &t : th) t.join();
+	int failed = -1, refused = -1;
+	for (int s = 0; s < N; s++) {
+		const Res &r = res[(size_t) s];
+		if (r.rc < 0 && !r.unsupported && failed < 0) failed = s;
+		if (r.rc < 0 && r.unsupported && refused < 0) refused = s;
+	}
+	const int pick = failed >= 0 ? failed : refused;
+	if (pick < 0) return 0;
+	memcpy(g_err, res[(size_t) pick].err, sizeof(g_err));
+	g_unsupported = failed < 0;
+	return -1;
+}
+
+// Part of a view: rows [r0, r1) of every leaf of a 2-d operand (offsets as they are: shard_upload() rebases them
+// on the device), or leaves [c0, c1).  Pointers into the caller's leaves; nothing is copied.
+struct SubView {
+	svt_view v;
+	int32_t dim[2];
+	std::vector<int32_t> cnt;
+	std::vector<const int32_t *> offs;
+	std::vector<const void *> vals;
+};
+
+static void row_block_view(const svt_view *x, int r0, int r1, SubView &sv)
+{
+	sv.v = *x;
+	sv.dim[0] = r1 - r0;
+	sv.dim[1] = x->dim[1];
+	sv.v.dim = sv.dim;
+	if (x->svt_is_null) return;
+	const size_t n = (size_t) x->nleaves, esz = elt_size(x->Rtype);
+	sv.cnt.assign(n, 0);
+	sv.offs.assign(n, NULL);
+	sv.vals.assign(n, NULL);
+	for (size_t j = 0; j < n; j++) {
+		const int c = x->nzcount[j];
+		if (c <= 0) continue;
+		// offsets ascend inside a leaf (src/leaf_utils.h:12-15)
+		const int32_t *o = x->nzoffs[j];
+		const int32_t *lo = std::lower_bound(o, o + c, r0), *hi = std::lower_bound(lo, o + c, r1);
+		sv.cnt[j] = (int32_t) (hi - lo);
+		sv.offs[j] = lo;
+		if (x->nzvals[j] != NULL) sv.vals[j] = (const char *) x->nzvals[j] + (size_t) (lo - o) * esz;
+	}
+	sv.v.nzcount = sv.cnt.data();
+	sv.v.nzoffs = sv.offs.data();
+	sv.v.nzvals = sv.vals.data();
+}
+
+static void col_block_view(const svt_view *x, int64_t c0, int64_t c1, SubView &sv)
+{
+	sv.v = *x;
+	sv.v.ndim = 2;
+	sv.dim[0] = x->dim[0];
+	sv.dim[1] = (int32_t) (c1 - c0);
+	sv.v.dim = sv.dim;
+	sv.v.nleaves = c1 - c0;
+	if (x->svt_is_null) return;
+	sv.v.nzcount = x->nzcount + c0;
+	sv.v.nzoffs = x->nzoffs + c0;
+	sv.v.nzvals = x->nzvals + c0;
+}
+
+// Upload of a row block [r0, ...): offsets rebased to 0 on the device.
+static svt_dev_csc *shard_upload(const svt_view *v, int r0)
+{
+	svt_dev_csc *d = svt_upload(v);
+	if (d == NULL || r0 == 0) return d;
+	if (launch_rebase_rows(d->row_idx, d->nnz, r0, 0) || hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("device error while rebasing a row block");
+		svt_release(d);
+		return NULL;
+	}
+	return d;
+}
+
+// Row block of shard s: the blocks of parallel.row_block(nrow, s, N, 128) -- every boundary but the last a
+// multiple of 128 rows (the row panels of the product kernels); empty blocks when N exceeds the panels.
+static void shard_rows(int64_t nrow, int s, int N, int64_t *r0, int64_t *r1)
+{
+	const int64_t units = (nrow + 127) / 128, base = units / N, rem = units % N;
+	const int64_t u0 = s * base + (s < rem ? s : rem), u1 = u0 + base + (s < rem ? 1 : 0);
+	*r0 = u0 * 128 < nrow ? u0 * 128 : nrow;
+	*r1 = u1 * 128 < nrow ? u1 * 128 : nrow;
+}
+
+// Leaf ranges cut on unit boundaries (units of `unit` consecutive leaves: the output cells of colStats), balanced by
+// weight = nonzeros + 1 per unit.  cut[s] .. cut[s + 1] are the units of shard s (possibly none).
+static std::vector<int64_t> shard_cuts(const svt_view *x, int64_t unit, int64_t nunits, int N)
+{
+	std::vector<int64_t> pre((size_t) nunits + 1, 0);
+	for (int64_t u = 0; u < nunits; u++) {
+		int64_t w = 1;
+		if (!x->svt_is_null)
+			for (int64_t j = u * unit; j < (u + 1) * unit; j++) w += x->nzcount[j];
+		pre[(size_t) u + 1] = pre[(size_t) u] + w;
+	}
+	const int64_t total = pre[(size_t) nunits];
+	std::vector<int64_t> cut((size_t) N + 1, nunits);
+	cut[0] = 0;
+	for (int s = 1; s < N; s++) {
+		const int64_t target = total / N * s + total % N * s / N;
+		cut[(size_t) s] = std::lower_bound(pre.begin(), pre.end(), target) - pre.begin();
+		if (cut[(size_t) s] > nunits) cut[(size_t) s] = nunits;
+		if (cut[(size_t) s] < cut[(size_t) s - 1]) cut[(size_t) s] = cut[(size_t) s - 1];
+	}
+	return cut;
+}
+
+// Device buffers of the shards that outlive one run_shards() (the partial results of the reduce-scatter), freed
+// on their devices.
+struct ShardBufs {
+	std::vector<void *> p;
+	std::vector<int> dev;
+	explicit ShardBufs(const std::vector<int> &devs) : p(devs.size(), nullptr), dev(devs) {}
+	~ShardBufs()
+	{
+		for (size_t s = 0; s < p.size(); s++)
+			if (p[s] && hipSetDevice(dev[s]) == hipSuccess) (void) hipFree(p[s]);
+		if (g_device >= 0) (void) hipSetDevice(g_device);
+	}
+	ShardBufs(const ShardBufs &) = delete;
+	ShardBufs &operator=(const ShardBufs &) = delete;
+};
+
+// ==================================================================================
 // Host level: crossprod
 // ==================================================================================
 static int check_mult_view(const svt_view *x, const char *what)
@@ -1174,8 +1491,9 @@ struct PbcAhead {
 	{
 		if (A->Rtype != SVT_REALSXP || !pbc_applies(A, K)) return;
 		started = true;
-		th = std::thread([this, A] {
-			(void) hipSetDevice(g_device);
+		const int dev = cur_device();                     // (a shard's device on a shard's thread)
+		th = std::thread([this, A, dev] {
+			(void) hipSetDevice(dev);
 			P = pbc_for(A, &own);
 		});
 	}
@@ -1293,6 +1611,98 @@ static bool mult_types_ok(int a, int b)
 	return (a == SVT_REALSXP || a == SVT_INTSXP) && (b == SVT_REALSXP || b == SVT_INTSXP);
 }
 
+// crossprod(x, y) over the device list: shard s multiplies the rows [r0, r1) of x and y into a whole ncol x K
+// partial (on its device), then owns slice s of the result's cells: it fetches that slice of every partial
+// (hipMemcpyPeerAsync; a device-to-device copy between shards on one device), adds them in shard order
+// (kernels_shard.hip) and copies the sum into `out`.  The sums depend on N and the row blocks only.
+static int crossprod2_SVT_mat_sharded(const svt_view *x, const void *y, int y_nrow, int y_ncol, int y_Rtype,
+				      int tr_y, double *out)
+{
+	if (check_leaves(x))                                // (the row blocks read the offsets)
+		return -1;
+	const std::vector<int> devs = g_devices;
+	const int N = (int) devs.size();
+	const int64_t nrow = x->dim[0], ncol = x->dim[1], K = tr_y ? y_nrow : y_ncol;
+	const size_t out_n = (size_t) ncol * (size_t) K, ysz = elt_size(y_Rtype);
+	ShardBufs part(devs);
+	// SVT_SHARD_TIMING=1 (tools/debug/multi_device_time.py): per-shard upload / product / reduce-scatter ms on stderr
+	const bool timing = getenv("SVT_SHARD_TIMING") != NULL;
+	std::vector<double> t_up((size_t) N, 0.0), t_mul((size_t) N, 0.0), t_red((size_t) N, 0.0);
+	auto ms_since = [](std::chrono::steady_clock::time_point t0) {
+		return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	};
+	int rc = run_shards(devs, [&](int s) -> int {
+		const auto t0 = std::chrono::steady_clock::now();
+		int64_t r0, r1;
+		shard_rows(nrow, s, N, &r0, &r1);
+		const int64_t rs = r1 - r0;
+		DevBuf O;
+		if (O.alloc(out_n * 8) || O.zero())
+			return -1;
+		if (rs > 0) {
+			SubView sv;
+			row_block_view(x, (int) r0, (int) r1, sv);
+			CscGuard A(shard_upload(&sv.v, (int) r0));
+			if (A.h == NULL) return -1;
+			DevBuf Y;
+			PbcAhead ahead;
+			ahead.start(A.h, K);
+			if (tr_y) {                                 // y is K x nrow: its columns r0 .. r1 are contiguous
+				if (Y.upload((const char *) y + (size_t) r0 * y_nrow * ysz, (size_t) rs * y_nrow * ysz))
+					return -1;
+			} else if (Y.alloc((size_t) rs * K * ysz) ||
+				   staged_copy_2d(Y.p, (const char *) y + (size_t) r0 * ysz, (size_t) rs * ysz, (size_t) K,
+						  (size_t) y_nrow * ysz)) {
+				return -1;
+			}
+			t_up[(size_t) s] = ms_since(t0);
+			Promoted pr;
+			if (pr.promote(A.h, Y.p, y_Rtype, (size_t) rs * K))
+				return -1;
+			if (dev_crossprod_chunked(pr.A, pr.Y, tr_y ? y_nrow : rs, K, tr_y, O.as<double>(), 1, ncol,
+						  pr.A == A.h ? &ahead : NULL))
+				return -1;
+		}
+		HIP_TRY(hipDeviceSynchronize());                 // (the other shards read the partial next)
+		t_mul[(size_t) s] = ms_since(t0) - t_up[(size_t) s];
+		part.p[(size_t) s] = O.p;
+		O.p = nullptr;
+		return 0;
+	});
+	if (rc) return -1;
+	// reduce-scatter: slice s = cells [q[s], q[s + 1]), even boundaries (16-byte accesses in the sum)
+	std::vector<size_t> q((size_t) N + 1, out_n);
+	for (int s = 0; s < N; s++) q[(size_t) s] = (out_n / N * s + out_n % N * s / N) & ~(size_t) 1;
+	rc = run_shards(devs, [&](int s) -> int {
+		const auto t0 = std::chrono::steady_clock::now();
+		const size_t c0 = q[(size_t) s], len = q[(size_t) s + 1] - c0;
+		if (len == 0) return 0;
+		const size_t stride = (len + 1) & ~(size_t) 1;
+		DevBuf F, R;
+		if (F.alloc(stride * N * 8) || R.alloc(len * 8))
+			return -1;
+		for (int t = 0; t < N; t++) {
+			double *dst = F.as<double>() + (size_t) t * stride;
+			const double *src = (const double *) part.p[(size_t) t] + c0;
+			if (devs[(size_t) t] == devs[(size_t) s])
+				HIP_TRY(hipMemcpyAsync(dst, src, len * 8, hipMemcpyDeviceToDevice, 0));
+			else
+				HIP_TRY(hipMemcpyPeerAsync(dst, devs[(size_t) s], src, devs[(size_t) t], len * 8, 0));
+		}
+		if (launch_shard_sum(F.as<double>(), N, (int64_t) stride, (int64_t) len, R.as<double>(), 0))
+			return -1;
+		HIP_TRY(hipStreamSynchronize(0));
+		const int rd = staged_download(out + c0, R.p, len * 8);
+		t_red[(size_t) s] = ms_since(t0);
+		return rd;
+	});
+	if (timing)
+		for (int s = 0; s < N; s++)
+			fprintf(stderr, "svt shard %d/%d device %d: upload %.3f ms, product %.3f ms, reduce-scatter %.3f ms\n",
+				s, N, devs[(size_t) s], t_up[(size_t) s], t_mul[(size_t) s], t_red[(size_t) s]);
+	return rc;
+}
+
 // C_crossprod2_SVT_mat, src/SparseMatrix_mult.c:931-982
 static int crossprod2_SVT_mat_impl(const svt_view *x, const void *y, int y_nrow,
 				      int y_ncol, int y_Rtype, int tr_y, double *out)
@@ -1312,6 +1722,8 @@ static int crossprod2_SVT_mat_impl(const svt_view *x, const void *y, int y_nrow,
 	memset(out, 0, out_n * sizeof(double));
 	if (x->svt_is_null || out_n == 0)     // :389-390
 		return 0;
+	if (shard_applies(x))
+		return crossprod2_SVT_mat_sharded(x, y, y_nrow, y_ncol, y_Rtype, tr_y, out);
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
 	DevBuf Y, O;
@@ -1694,6 +2106,46 @@ extern "C" int svt_transpose_2D_SVT(const svt_view *x, int64_t *out_col_ptr,
 	return svt_status(transpose_2D_SVT_impl(x, out_col_ptr, out_row_idx, out_val));
 }
 
+// x %*% y over the device list: shard s takes the rows [r0, r1) of x, transposes them and multiplies them with the
+// whole of y (replicated); its rows of the result go straight into `out` (a 2-d copy, ld = nrow).  No collective.
+static int matmul_SVT_mat_sharded(const svt_view *x, const void *y, int y_nrow, int y_ncol, int y_Rtype, double *out)
+{
+	if (check_leaves(x))
+		return -1;
+	const std::vector<int> devs = g_devices;
+	const int N = (int) devs.size();
+	const int64_t nrow = x->dim[0], K = y_ncol;
+	const size_t y_bytes = (size_t) y_nrow * y_ncol * elt_size(y_Rtype);
+	return run_shards(devs, [&](int s) -> int {
+		int64_t r0, r1;
+		shard_rows(nrow, s, N, &r0, &r1);
+		const int64_t rs = r1 - r0;
+		if (rs == 0) return 0;
+		SubView sv;
+		row_block_view(x, (int) r0, (int) r1, sv);
+		CscGuard A(shard_upload(&sv.v, (int) r0));
+		if (A.h == NULL) return -1;
+		int own_T = 1;
+		svt_dev_csc *T = transposed_for(A, &own_T);
+		OwnedCsc TA = { T, own_T };
+		if (T == NULL) return -1;
+		A.drop();
+		DevBuf Y, O;
+		PbcAhead ahead;
+		ahead.start(T, K);
+		if (Y.upload(y, y_bytes) || O.alloc((size_t) rs * K * 8) || O.zero())
+			return -1;
+		Promoted pr;
+		if (pr.promote(T, Y.p, y_Rtype, (size_t) y_nrow * y_ncol))
+			return -1;
+		if (dev_crossprod_chunked(pr.A, pr.Y, y_nrow, K, 0, O.as<double>(), 1, rs, pr.A == T ? &ahead : NULL))
+			return -1;
+		HIP_TRY(hipMemcpy2D(out + r0, (size_t) nrow * 8, O.p, (size_t) rs * 8, (size_t) rs * 8, (size_t) K,
+				    hipMemcpyDeviceToHost));
+		return 0;
+	});
+}
+
 // x %*% y, y an ordinary matrix: the R method (R/SparseMatrix-mult.R:195-215) is
 // .crossprod2_SparseMatrix_matrix(t(x), y), i.e. C_transpose_2D_SVT on the host
 // followed by C_crossprod2_SVT_mat.  Here the transposition happens on the device,
@@ -1715,6 +2167,8 @@ static int matmul_SVT_mat_impl(const svt_view *x, const void *y, int y_nrow,
 	memset(out, 0, out_n * sizeof(double));
 	if (x->svt_is_null || out_n == 0)
 		return 0;
+	if (shard_applies(x))
+		return matmul_SVT_mat_sharded(x, y, y_nrow, y_ncol, y_Rtype, out);
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
 	int own_T = 1;
@@ -1969,6 +2423,31 @@ static int run_colstats(const svt_dev_csc *A, int opcode, int na_rm, double cent
 	return 0;
 }
 
+// colStats over the device list: shard s takes the output cells [g0, g1) -- leaves [g0 * inner, g1 * inner),
+// ranges balanced by nonzeros -- and writes its slice of `out`; the warn flags are ORed.
+static int colStats_SVT_sharded(const svt_view *x, int opcode, int na_rm, double center, int64_t inner, int64_t nout,
+				int out_Rtype, void *out, int *warn)
+{
+	const std::vector<int> devs = g_devices;
+	const int N = (int) devs.size();
+	const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
+	const std::vector<int64_t> cut = shard_cuts(x, inner, nout, N);
+	std::vector<int> w((size_t) N, 0);
+	const int rc = run_shards(devs, [&](int s) -> int {
+		const int64_t g0 = cut[(size_t) s], g1 = cut[(size_t) s + 1];
+		if (g1 <= g0) return 0;
+		SubView sv;
+		col_block_view(x, g0 * inner, g1 * inner, sv);
+		CscGuard A(svt_upload(&sv.v));
+		if (A.h == NULL) return -1;
+		return run_colstats(A.h, opcode, na_rm, center, inner, (char *) out + (size_t) g0 * osz, out_Rtype,
+				    &w[(size_t) s]);
+	});
+	for (int s = 0; s < N; s++)
+		if (w[(size_t) s]) *warn = 1;
+	return rc;
+}
+
 // C_colStats_SVT, src/SparseArray_matrixStats.c:234-284
 static int colStats_SVT_impl(const svt_view *x, int opcode, int na_rm, double center,
 				int dims, void *out, int *warn)
@@ -1986,6 +2465,8 @@ static int colStats_SVT_impl(const svt_view *x, int opcode, int na_rm, double ce
 	if (nout == 0)
 		return 0;
 	const int out_Rtype = svt_colStats_out_Rtype(opcode, x->Rtype);
+	if (inner > 0 && shard_applies(x))
+		return colStats_SVT_sharded(x, opcode, na_rm, center, inner, nout, out_Rtype, out, warn);
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
 	if (inner == 0) {
@@ -2246,6 +2727,33 @@ static int groupsum_host(const svt_dev_csc *A, const int32_t *col_ptr32,
 	return 0;
 }
 
+// rowsum over the device list: shard s takes the leaves [c0, c1) (ranges balanced by nonzeros); its ngroup x (c1 - c0)
+// block of the column-major result is contiguous in `out`.  The overflow flags are ORed.
+static int rowsum_SVT_sharded(const svt_view *x, const int *group, int ngroup, int na_rm, void *out, int *ovflow)
+{
+	const std::vector<int> devs = g_devices;
+	const int N = (int) devs.size();
+	const int64_t ncol = x->dim[1];
+	if ((int64_t) ngroup * ncol > 0x7FFFFFFFLL)   // safe_int_mult() guard, src/rowsum_methods.c:296-301
+		return svt_set_error("too many groups (matrix of sums will be too big)");
+	const size_t osz = elt_size(x->Rtype);
+	const std::vector<int64_t> cut = shard_cuts(x, 1, ncol, N);
+	std::vector<int> ov((size_t) N, 0);
+	const int rc = run_shards(devs, [&](int s) -> int {
+		const int64_t c0 = cut[(size_t) s], c1 = cut[(size_t) s + 1];
+		if (c1 <= c0) return 0;
+		SubView sv;
+		col_block_view(x, c0, c1, sv);
+		CscGuard A(svt_upload(&sv.v));
+		if (A.h == NULL) return -1;
+		return groupsum_host(A.h, NULL, group, ngroup, na_rm, false, (char *) out + (size_t) ngroup * c0 * osz,
+				     &ov[(size_t) s]);
+	});
+	for (int s = 0; s < N; s++)
+		if (ov[(size_t) s]) *ovflow = 1;
+	return rc;
+}
+
 static int xsum_SVT(const svt_view *x, const int *group, int ngroup, int na_rm,
 		    bool colsum, void *out, int *ovflow)
 {
@@ -2261,6 +2769,8 @@ static int xsum_SVT(const svt_view *x, const int *group, int ngroup, int na_rm,
 				     "SVT_SparseMatrix objects of this type at the moment");
 	if (check_group(group, colsum ? x->dim[1] : x->dim[0], ngroup))
 		return -1;
+	if (!colsum && shard_applies(x))
+		return rowsum_SVT_sharded(x, group, ngroup, na_rm, out, ovflow);
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
 	return groupsum_host(A.h, NULL, group, ngroup, na_rm, colsum, out, ovflow);
