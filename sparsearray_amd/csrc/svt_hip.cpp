@@ -16,6 +16,9 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
+#include <mutex>
+#include <thread>
 #include <vector>
 
 static thread_local char g_err[1024];
@@ -48,6 +51,12 @@ void svt_clear_unsupported(void) { g_unsupported = 0; }
 static inline int svt_status(int rc)
 {
 	return rc < 0 && g_unsupported ? 1 : rc;
+}
+// The status an entry point hands to its caller: f() run with the mark cleared, a refusal turned into 1.
+template <class F> static int abi_status(F f)
+{
+	g_unsupported = 0;
+	return svt_status(f());
 }
 
 extern "C" const char *svt_last_error(void) { return g_err; }
@@ -188,12 +197,6 @@ static int ensure_init()
 // the R heap) into one buffer while the previous one is in flight on a copy stream
 // (the reference's counterpart is the leaf walk of
 // src/SVT_SparseArray_class.c:598-633, which never leaves the host).
-#include <algorithm>
-#include <functional>
-#include <mutex>
-#include <vector>
-#include <thread>
-
 struct Stager {
 	static const size_t CHUNK = (size_t) 48 << 20;      // bytes per pinned buffer
 	size_t chunk = CHUNK;                                // (a shard's stager: CHUNK / number of shards)
@@ -881,8 +884,7 @@ extern "C" int svt_dev_colstats(const svt_dev_csc *A, int opcode, int na_rm,
 				double center, int64_t inner, void *out,
 				int *warn_flag, void *stream)
 {
-	g_unsupported = 0;
-	return svt_status(dev_colstats_ex(A, opcode, na_rm, center, inner, out, warn_flag, stream, 0));
+	return abi_status([&] { return dev_colstats_ex(A, opcode, na_rm, center, inner, out, warn_flag, stream, 0); });
 }
 
 extern "C" size_t svt_dev_colmedians_ws_bytes(int64_t nnz, int64_t ncol)
@@ -903,8 +905,7 @@ static int dev_colmedians_impl(const svt_dev_csc *A, int na_rm, double *out, voi
 extern "C" int svt_dev_colmedians(const svt_dev_csc *A, int na_rm, double *out, void *ws,
 				  size_t ws_bytes, void *stream)
 {
-	g_unsupported = 0;
-	return svt_status(dev_colmedians_impl(A, na_rm, out, ws, ws_bytes, stream));
+	return abi_status([&] { return dev_colmedians_impl(A, na_rm, out, ws, ws_bytes, stream); });
 }
 
 extern "C" size_t svt_dev_rowstats_ws_bytes(int64_t nrow, int64_t ncol)
@@ -978,8 +979,7 @@ extern "C" int64_t svt_dev_boxed_calls(int reset)
 extern "C" int svt_dev_transpose(const svt_dev_csc *A, int64_t *out_col_ptr, int32_t *out_row_idx,
 				 void *out_val, void *ws, size_t ws_bytes, void *stream)
 {
-	g_unsupported = 0;
-	return svt_status(dev_transpose_impl(A, out_col_ptr, out_row_idx, out_val, ws, ws_bytes, stream));
+	return abi_status([&] { return dev_transpose_impl(A, out_col_ptr, out_row_idx, out_val, ws, ws_bytes, stream); });
 }
 
 // A %*% B, both sparse (kernels_spmm.hip): out[r + k * ldo], r < A->nrow, k < B->ncol.
@@ -1032,8 +1032,7 @@ static int dev_matmul_csc_csc_prepared_impl(const svt_dev_csc *A, const svt_dev_
 extern "C" int svt_dev_matmul_csc_csc_prepared(const svt_dev_csc *A, const svt_dev_csc *B, double *out, int64_t ldo,
 					       void *ws, size_t ws_bytes, int *not_finite, void *stream)
 {
-	g_unsupported = 0;
-	return svt_status(dev_matmul_csc_csc_prepared_impl(A, B, out, ldo, ws, ws_bytes, not_finite, stream));
+	return abi_status([&] { return dev_matmul_csc_csc_prepared_impl(A, B, out, ldo, ws, ws_bytes, not_finite, stream); });
 }
 
 static int dev_matmul_csc_csc_impl(const svt_dev_csc *A, const svt_dev_csc *B, double *out, int64_t ldo,
@@ -1063,8 +1062,7 @@ static int dev_matmul_csc_csc_impl(const svt_dev_csc *A, const svt_dev_csc *B, d
 extern "C" int svt_dev_matmul_csc_csc(const svt_dev_csc *A, const svt_dev_csc *B, double *out, int64_t ldo,
 				      void *ws, size_t ws_bytes, int *not_finite, void *stream)
 {
-	g_unsupported = 0;
-	return svt_status(dev_matmul_csc_csc_impl(A, B, out, ldo, ws, ws_bytes, not_finite, stream));
+	return abi_status([&] { return dev_matmul_csc_csc_impl(A, B, out, ldo, ws, ws_bytes, not_finite, stream); });
 }
 
 // crossprod(X, Y) of two sparse operands on t(X) and Y (kernels_gram.hip)
@@ -1107,8 +1105,7 @@ static int dev_crossprod_csc_csc_impl(const svt_dev_csc *Xt, const svt_dev_csc *
 extern "C" int svt_dev_crossprod_csc_csc(const svt_dev_csc *Xt, const svt_dev_csc *Y, int sym, double *out,
 					 int64_t ldo, void *ws, size_t ws_bytes, int *not_finite, void *stream)
 {
-	g_unsupported = 0;
-	return svt_status(dev_crossprod_csc_csc_impl(Xt, Y, sym, out, ldo, ws, ws_bytes, not_finite, stream));
+	return abi_status([&] { return dev_crossprod_csc_csc_impl(Xt, Y, sym, out, ldo, ws, ws_bytes, not_finite, stream); });
 }
 
 extern "C" void svt_dev_aperm_route_counts(int64_t *counts, int reset)
@@ -1153,8 +1150,7 @@ extern "C" int svt_dev_aperm(const svt_dev_csc *A, int ndim, const int64_t *dim,
 			     int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val,
 			     void *ws, size_t ws_bytes, void *stream)
 {
-	g_unsupported = 0;
-	return svt_status(dev_aperm_impl(A, ndim, dim, perm, out_col_ptr, out_row_idx, out_val, ws, ws_bytes, stream));
+	return abi_status([&] { return dev_aperm_impl(A, ndim, dim, perm, out_col_ptr, out_row_idx, out_val, ws, ws_bytes, stream); });
 }
 
 // C_aperm_SVT, src/SparseArray_aperm.c:935-970
@@ -1191,8 +1187,15 @@ static int aperm_SVT_impl(const svt_view *x, const int *perm, int64_t *out_col_p
 extern "C" int svt_aperm_SVT(const svt_view *x, const int *perm, int64_t *out_col_ptr,
 			     int32_t *out_row_idx, void *out_val)
 {
-	g_unsupported = 0;
-	return svt_status(aperm_SVT_impl(x, perm, out_col_ptr, out_row_idx, out_val));
+	return abi_status([&] { return aperm_SVT_impl(x, perm, out_col_ptr, out_row_idx, out_val); });
+}
+
+// rowsum of doubles: the LDS kernel for few groups and leaves long enough to fill them, else the atomic one
+static int launch_rowsum_f64(const GroupSumArgs &a, int64_t nnz, hipStream_t stream)
+{
+	if (a.ngroup <= 8192 && a.ncol > 0 && nnz / a.ncol >= a.ngroup / 4)
+		return launch_rowsum_lds(a, stream);
+	return launch_rowsum(a, stream);
 }
 
 extern "C" int svt_dev_rowsum(const svt_dev_csc *A, const int *group, int ngroup,
@@ -1205,9 +1208,7 @@ extern "C" int svt_dev_rowsum(const svt_dev_csc *A, const int *group, int ngroup
 	a.col_ptr64 = A->col_ptr; a.row_idx = A->row_idx; a.val = A->val;
 	a.Rtype = A->Rtype; a.nrow = A->nrow; a.ncol = A->ncol;
 	a.group = group; a.ngroup = ngroup; a.na_rm = na_rm; a.out = out;
-	if (ngroup <= 8192 && A->ncol > 0 && A->nnz / A->ncol >= ngroup / 4)
-		return launch_rowsum_lds(a, (hipStream_t) stream);
-	return launch_rowsum(a, (hipStream_t) stream);
+	return launch_rowsum_f64(a, A->nnz, (hipStream_t) stream);
 }
 
 // rowsum(x, group) for a (x, group) pair that is used more than once: the group of every nonzero, as a 16-bit
@@ -1315,7 +1316,7 @@ template <class F> static int run_shards(const std::vector<int> &devs, F fn)
 	return -1;
 }
 
-// Part of a view: rows [r0, r1) of every leaf of a 2-d operand (offsets as they are: shard_upload() rebases them
+// Part of a view: rows [r0, r1) of every leaf of a 2-d operand (offsets as they are: row_block_upload() rebases them
 // on the device), or leaves [c0, c1).  Pointers into the caller's leaves; nothing is copied.
 struct SubView {
 	svt_view v;
@@ -1365,12 +1366,14 @@ static void col_block_view(const svt_view *x, int64_t c0, int64_t c1, SubView &s
 	sv.v.nzvals = x->nzvals + c0;
 }
 
-// Upload of a row block [r0, ...): offsets rebased to 0 on the device.
-static svt_dev_csc *shard_upload(const svt_view *v, int r0)
+// Upload of the rows [r0, r1) of x: offsets rebased to 0 on the device.
+static svt_dev_csc *row_block_upload(const svt_view *x, int64_t r0, int64_t r1)
 {
-	svt_dev_csc *d = svt_upload(v);
+	SubView sv;
+	row_block_view(x, (int) r0, (int) r1, sv);
+	svt_dev_csc *d = svt_upload(&sv.v);
 	if (d == NULL || r0 == 0) return d;
-	if (launch_rebase_rows(d->row_idx, d->nnz, r0, 0) || hipStreamSynchronize(0) != hipSuccess) {
+	if (launch_rebase_rows(d->row_idx, d->nnz, (int32_t) r0, 0) || hipStreamSynchronize(0) != hipSuccess) {
 		if (svt_last_error()[0] == '\0') svt_set_error("device error while rebasing a row block");
 		svt_release(d);
 		return NULL;
@@ -1511,6 +1514,28 @@ struct PbcAhead {
 	}
 };
 
+// n integers on the device -> a new f64 array `dst` (NA_integer_ -> NA_real_: int_to_f64_kernel)
+static int widen_int(DevBuf &dst, const void *src, int64_t n)
+{
+	if (dst.alloc((size_t) (n > 0 ? n : 1) * 8))
+		return -1;
+	return launch_int_to_f64((const int *) src, n, dst.as<double>(), 0);
+}
+
+// An integer operand with f64 values: `view` is A with `val` in place of its values (owns nothing).
+struct Widened {
+	svt_dev_csc view;
+	DevBuf val;
+	int widen(const svt_dev_csc *A)
+	{
+		if (widen_int(val, A->val, A->nnz))
+			return -1;
+		view = *A;
+		view.Rtype = SVT_REALSXP; view.val = val.p; view.owned = 0;
+		return 0;
+	}
+};
+
 // out (device) receives all K columns; the dense operand is already on the device.
 static int dev_crossprod_chunked(const svt_dev_csc *A, const void *Y_dev, int64_t ldY,
 				 int64_t K, int tr_y, double *out_dev,
@@ -1523,14 +1548,11 @@ static int dev_crossprod_chunked(const svt_dev_csc *A, const void *Y_dev, int64_
 	// results, NA rules included, are those of the integer path -- bit for bit while the sums
 	// stay below 2^53).
 	if (A->Rtype == SVT_INTSXP && !tr_y && ldY == A->nrow && pbc_applies(A, K)) {
-		DevBuf V, Yf;
-		if (V.alloc((size_t) (A->nnz > 0 ? A->nnz : 1) * 8) || Yf.alloc((size_t) A->nrow * K * 8) ||
-		    launch_int_to_f64((const int *) A->val, A->nnz, V.as<double>(), 0) ||
-		    launch_int_to_f64((const int *) Y_dev, A->nrow * K, Yf.as<double>(), 0))
+		Widened Af;
+		DevBuf Yf;
+		if (Af.widen(A) || widen_int(Yf, Y_dev, A->nrow * K))
 			return -1;
-		svt_dev_csc Af = *A;
-		Af.Rtype = SVT_REALSXP; Af.val = V.p; Af.owned = 0;
-		return dev_crossprod_chunked(&Af, Yf.p, ldY, K, 0, out_dev, sc, sk, NULL);
+		return dev_crossprod_chunked(&Af.view, Yf.p, ldY, K, 0, out_dev, sc, sk, NULL);
 	}
 	// Large double products with a column-major dense operand take the panel-blocked
 	// kernels: the one-off layout build (a few ms at 1e8 nonzeros)
@@ -1579,32 +1601,33 @@ general:
 // R/SparseMatrix-mult.R:75-120) -- a copy of the whole tree.  Here the integer side is uploaded
 // as it is (4 bytes per value over PCIe) and widened on the device; as.double(NA_integer_) is
 // NA_real_, which is what int_to_f64_kernel writes.
-struct Promoted {
-	svt_dev_csc view;
-	DevBuf val, dense;
-	const svt_dev_csc *A;
-	const void *Y;
-	int promote(const svt_dev_csc *A_in, const void *Y_dev, int y_Rtype, size_t y_elems)
-	{
-		A = A_in; Y = Y_dev;
-		if (A_in->Rtype == y_Rtype)
-			return 0;
-		if (A_in->Rtype == SVT_INTSXP) {                 // sparse int, dense double
-			if (val.alloc((size_t) (A_in->nnz > 0 ? A_in->nnz : 1) * 8) ||
-			    launch_int_to_f64((const int *) A_in->val, A_in->nnz, val.as<double>(), 0))
-				return -1;
-			view = *A_in;
-			view.Rtype = SVT_REALSXP; view.val = val.p; view.owned = 0;
-			A = &view;
-		} else {                                          // sparse double, dense int
-			if (dense.alloc((y_elems > 0 ? y_elems : 1) * 8) ||
-			    launch_int_to_f64((const int *) Y_dev, (int64_t) y_elems, dense.as<double>(), 0))
-				return -1;
-			Y = dense.p;
+// The product of the dense-operand entry points: A times a dense operand of y_elems elements of y_Rtype, which
+// put_y(dst) copies to the device (ldY, tr_y: its layout there), into O (device, zeroed; strides sc, sk).  The layout
+// build of A starts first, on a helper thread, so that it overlaps the copy of Y.  (An integer A paired with a double
+// Y is widened, and it has no layout to build: PbcAhead::start() does nothing for it.)
+template <class PutY>
+static int dense_product(const svt_dev_csc *A, int64_t K, int y_Rtype, size_t y_elems, PutY put_y, int64_t ldY,
+			 int tr_y, double *O, int64_t sc, int64_t sk)
+{
+	PbcAhead ahead;
+	ahead.start(A, K);
+	DevBuf Y;
+	if (Y.alloc(y_elems * elt_size(y_Rtype)) || put_y(Y.p))
+		return -1;
+	const void *Yp = Y.p;
+	Widened Aw;
+	DevBuf Yw;
+	if (A->Rtype != y_Rtype) {
+		if (A->Rtype == SVT_INTSXP) {             // sparse int, dense double
+			if (Aw.widen(A)) return -1;
+			A = &Aw.view;
+		} else {                                  // sparse double, dense int
+			if (widen_int(Yw, Y.p, (int64_t) y_elems)) return -1;
+			Yp = Yw.p;
 		}
-		return 0;
 	}
-};
+	return dev_crossprod_chunked(A, Yp, ldY, K, tr_y, O, sc, sk, &ahead);
+}
 
 static bool mult_types_ok(int a, int b)
 {
@@ -1640,27 +1663,19 @@ static int crossprod2_SVT_mat_sharded(const svt_view *x, const void *y, int y_nr
 		if (O.alloc(out_n * 8) || O.zero())
 			return -1;
 		if (rs > 0) {
-			SubView sv;
-			row_block_view(x, (int) r0, (int) r1, sv);
-			CscGuard A(shard_upload(&sv.v, (int) r0));
+			CscGuard A(row_block_upload(x, r0, r1));
 			if (A.h == NULL) return -1;
-			DevBuf Y;
-			PbcAhead ahead;
-			ahead.start(A.h, K);
-			if (tr_y) {                                 // y is K x nrow: its columns r0 .. r1 are contiguous
-				if (Y.upload((const char *) y + (size_t) r0 * y_nrow * ysz, (size_t) rs * y_nrow * ysz))
-					return -1;
-			} else if (Y.alloc((size_t) rs * K * ysz) ||
-				   staged_copy_2d(Y.p, (const char *) y + (size_t) r0 * ysz, (size_t) rs * ysz, (size_t) K,
-						  (size_t) y_nrow * ysz)) {
-				return -1;
-			}
-			t_up[(size_t) s] = ms_since(t0);
-			Promoted pr;
-			if (pr.promote(A.h, Y.p, y_Rtype, (size_t) rs * K))
-				return -1;
-			if (dev_crossprod_chunked(pr.A, pr.Y, tr_y ? y_nrow : rs, K, tr_y, O.as<double>(), 1, ncol,
-						  pr.A == A.h ? &ahead : NULL))
+			auto put_y = [&](void *d) -> int {
+				// y is K x nrow: its columns r0 .. r1 are contiguous; else its rows r0 .. r1 of every column
+				const int rc = tr_y ? staged_copy(d, (const char *) y + (size_t) r0 * y_nrow * ysz,
+								  (size_t) rs * y_nrow * ysz)
+						    : staged_copy_2d(d, (const char *) y + (size_t) r0 * ysz, (size_t) rs * ysz,
+								     (size_t) K, (size_t) y_nrow * ysz);
+				t_up[(size_t) s] = ms_since(t0);
+				return rc;
+			};
+			if (dense_product(A.h, K, y_Rtype, (size_t) rs * K, put_y, tr_y ? y_nrow : rs, tr_y, O.as<double>(), 1,
+					  ncol))
 				return -1;
 		}
 		HIP_TRY(hipDeviceSynchronize());                 // (the other shards read the partial next)
@@ -1726,26 +1741,18 @@ static int crossprod2_SVT_mat_impl(const svt_view *x, const void *y, int y_nrow,
 		return crossprod2_SVT_mat_sharded(x, y, y_nrow, y_ncol, y_Rtype, tr_y, out);
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	DevBuf Y, O;
-	PbcAhead ahead;
-	ahead.start(A.h, out_ncol);
-	if (Y.upload(y, (size_t) y_nrow * y_ncol * elt_size(y_Rtype)) ||
-	    O.alloc(out_n * 8) || O.zero())
+	const size_t y_elems = (size_t) y_nrow * y_ncol;
+	auto put_y = [&](void *d) { return staged_copy(d, y, y_elems * elt_size(y_Rtype)); };
+	DevBuf O;
+	if (O.alloc(out_n * 8) || O.zero() ||
+	    dense_product(A.h, out_ncol, y_Rtype, y_elems, put_y, y_nrow, tr_y, O.as<double>(), 1, out_nrow))
 		return -1;
-	Promoted pr;
-	if (pr.promote(A.h, Y.p, y_Rtype, (size_t) y_nrow * y_ncol))
-		return -1;
-	if (dev_crossprod_chunked(pr.A, pr.Y, y_nrow, out_ncol, tr_y, O.as<double>(),
-				  1, out_nrow, pr.A == A.h ? &ahead : NULL))
-		return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	return staged_download(out, O.p, out_n * 8);
 }
 extern "C" int svt_crossprod2_SVT_mat(const svt_view *x, const void *y, int y_nrow,
 				      int y_ncol, int y_Rtype, int tr_y, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(crossprod2_SVT_mat_impl(x, y, y_nrow, y_ncol, y_Rtype, tr_y, out));
+	return abi_status([&] { return crossprod2_SVT_mat_impl(x, y, y_nrow, y_ncol, y_Rtype, tr_y, out); });
 }
 
 // C_crossprod2_mat_SVT, src/SparseMatrix_mult.c:985-1034
@@ -1768,34 +1775,27 @@ static int crossprod2_mat_SVT_impl(const void *x, int x_nrow, int x_ncol,
 		return 0;
 	CscGuard A(y);
 	if (A.h == NULL) return -1;
-	DevBuf X, O;
-	PbcAhead ahead;
-	ahead.start(A.h, out_nrow);
-	if (X.upload(x, (size_t) x_nrow * x_ncol * elt_size(x_Rtype)) ||
-	    O.alloc(out_n * 8) || O.zero())
-		return -1;
+	const size_t x_elems = (size_t) x_nrow * x_ncol;
+	auto put_x = [&](void *d) { return staged_copy(d, x, x_elems * elt_size(x_Rtype)); };
 	// result cell (i = dense vector, j = leaf) lives at out[i + j*out_nrow]
-	Promoted pr;
-	if (pr.promote(A.h, X.p, x_Rtype, (size_t) x_nrow * x_ncol))
+	DevBuf O;
+	if (O.alloc(out_n * 8) || O.zero() ||
+	    dense_product(A.h, out_nrow, x_Rtype, x_elems, put_x, x_nrow, tr_x, O.as<double>(), out_nrow, 1))
 		return -1;
-	if (dev_crossprod_chunked(pr.A, pr.Y, x_nrow, out_nrow, tr_x, O.as<double>(),
-				  out_nrow, 1, pr.A == A.h ? &ahead : NULL))
-		return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	return staged_download(out, O.p, out_n * 8);
 }
 extern "C" int svt_crossprod2_mat_SVT(const void *x, int x_nrow, int x_ncol,
 				      int x_Rtype, const svt_view *y, int tr_x,
 				      double *out)
 {
-	g_unsupported = 0;
-	return svt_status(crossprod2_mat_SVT_impl(x, x_nrow, x_ncol, x_Rtype, y, tr_x, out));
+	return abi_status([&] { return crossprod2_mat_SVT_impl(x, x_nrow, x_ncol, x_Rtype, y, tr_x, out); });
 }
 
 // Densify columns of `pp` chunk by chunk and multiply every chunk with the
 // leaves of `other`: crossprod2_Lpp_* / crossprod2_Rpp_*,
-// src/SparseMatrix_mult.c:728-820.
-static int dev_crossprod_pp(const svt_dev_csc *other, const svt_dev_csc *pp,
+// src/SparseMatrix_mult.c:728-820.  sym (crossprod(x): pp is other) computes
+// only the cells that the caller's mirror does not fill.
+static int dev_crossprod_pp(const svt_dev_csc *other, const svt_dev_csc *pp, bool sym,
 			    double *out_dev, int64_t sc, int64_t sk)
 {
 	const int64_t K = pp->ncol, nrow = pp->nrow;
@@ -1803,16 +1803,10 @@ static int dev_crossprod_pp(const svt_dev_csc *other, const svt_dev_csc *pp,
 		return 0;
 	const bool big = pbc_applies(other, K);
 	if (other->Rtype == SVT_INTSXP && big) {                         // as in dev_crossprod_chunked
-		DevBuf V1, V2;
-		if (V1.alloc((size_t) (other->nnz > 0 ? other->nnz : 1) * 8) ||
-		    V2.alloc((size_t) (pp->nnz > 0 ? pp->nnz : 1) * 8) ||
-		    launch_int_to_f64((const int *) other->val, other->nnz, V1.as<double>(), 0) ||
-		    launch_int_to_f64((const int *) pp->val, pp->nnz, V2.as<double>(), 0))
+		Widened of, pf;
+		if (of.widen(other) || (!sym && pf.widen(pp)))
 			return -1;
-		svt_dev_csc of = *other, pf = *pp;
-		of.Rtype = pf.Rtype = SVT_REALSXP; of.owned = pf.owned = 0;
-		of.val = V1.p; pf.val = V2.p;
-		return dev_crossprod_pp(&of, other == pp ? &of : &pf, out_dev, sc, sk);
+		return dev_crossprod_pp(&of.view, sym ? &of.view : &pf.view, sym, out_dev, sc, sk);
 	}
 	int kc = chunk_K(nrow, K);
 	const size_t esz = elt_size(pp->Rtype);
@@ -1830,10 +1824,9 @@ static int dev_crossprod_pp(const svt_dev_csc *other, const svt_dev_csc *pp,
 	    ws.alloc(P ? svt_dev_crossprod_pbc_ws_bytes(P, kc)
 		       : crossprod_ws_bytes(nrow, other->ncol, kc)))
 		rc = -1;
-	// crossprod(x) (other == pp): of the dense chunk [k0, k0 + kn) only the leaves c >= k0 are
-	// needed -- the cells with c >= k, which the caller mirrors -- as in compute_sym_dotprods_*
+	// sym: of the dense chunk [k0, k0 + kn) only the leaves c >= k0 are needed -- the cells
+	// with c >= k, which the caller mirrors -- as in compute_sym_dotprods_*
 	// (src/SparseMatrix_mult.c:263-296: ncol^2 / 2 dot products).
-	const bool sym = other == pp;
 	for (int64_t k0 = 0; rc == 0 && k0 < K; k0 += kc) {
 		const int kn = (int) (K - k0 < kc ? K - k0 : kc);
 		if (launch_densify(pp->col_ptr, pp->row_idx, pp->val, pp->Rtype, nrow,
@@ -1861,13 +1854,16 @@ static int dev_crossprod_pp(const svt_dev_csc *other, const svt_dev_csc *pp,
 	return rc;
 }
 
-struct CscGuard;
-static svt_dev_csc *transposed_for(const CscGuard &A, int *owned);
-struct OwnedCsc {            // releases a handle only if this call built it
+struct OwnedCsc {            // a handle, released with this object only if this call built it
 	svt_dev_csc *t;
-	int own;
+	bool own;
+	OwnedCsc(svt_dev_csc *p, bool o) : t(p), own(o) {}
+	OwnedCsc(OwnedCsc &&o) : t(o.t), own(o.own) { o.own = false; }
+	OwnedCsc(const OwnedCsc &) = delete;
+	OwnedCsc &operator=(const OwnedCsc &) = delete;
 	~OwnedCsc() { if (own) svt_release(t); }
 };
+static OwnedCsc transposed_for(const CscGuard &A);
 
 // The sparse-aware route (kernels_gram.hip) multiplies only the pairs of nonzeros that meet in a row -- about
 // nnz(x) * nnz(y) / nrow of them (half that for the unary form), each an LDS atomic behind a gathered 12-byte read --
@@ -1931,35 +1927,54 @@ static int dev_crossprod_sparse(const CscGuard &X, const svt_dev_csc *Y, bool sy
 	// test changes no route.)
 	if (X.h->nnz >= ((int64_t) 1 << 31))
 		return 1;
-	int own_T = 1;
-	svt_dev_csc *T = transposed_for(X, &own_T);
-	OwnedCsc TX = { T, own_T };
-	if (T == NULL) {
+	const OwnedCsc T = transposed_for(X);
+	if (T.t == NULL) {
 		// an operand the transposition does not take (2^31 nonzeros or more): the dense-buffer route needs no t(x)
 		if (g_unsupported) { g_unsupported = 0; return 1; }
 		return -1;
 	}
-	return dev_crossprod_sparse_on(T, Y, sym, O, ldo, dense_ops);
+	return dev_crossprod_sparse_on(T.t, Y, sym, O, ldo, dense_ops);
 }
 
-// The dense-buffer route on resident operands (what the entry points below fall back to, and the yardstick of
-// tools/debug/sparse_crossprod_time.py): out = ncol(X) x ncol(Y), column-major, zeroed here.  Y == X (the same
-// handle): the unary form, half the dot products + mirror.  Allocates and synchronises.
+// The dense-buffer route of crossprod(X, Y) (what the sparse x sparse entry points fall back to): O = ncol(X) x ncol(Y)
+// on the device, column-major, zeroed here.  sym: the unary form crossprod(X) (Y is X), half the dot products + mirror.
+// Else the columns of the operand with fewer multiply-adds are expanded (Lpp_nops / Rpp_nops,
+// src/SparseMatrix_mult.c:1075-1097).
+static int dense_buffer_route(const svt_dev_csc *X, const svt_dev_csc *Y, bool sym, double *O)
+{
+	const int64_t nx = X->ncol, ny = Y->ncol;
+	HIP_TRY(hipMemset(O, 0, (size_t) nx * ny * 8));
+	if (sym)
+		return dev_crossprod_pp(X, X, true, O, 1, nx) || launch_mirror_lower(O, nx, 0) ? -1 : 0;
+	if (Y->nnz * nx < X->nnz * ny)     // expand the columns of X, walk the leaves of Y
+		return dev_crossprod_pp(Y, X, false, O, nx, 1);
+	return dev_crossprod_pp(X, Y, false, O, 1, nx);     // expand the columns of Y, walk the leaves of X
+}
+
+// The dense-buffer route on resident operands (the yardstick of tools/debug/sparse_crossprod_time.py).  Y == X (the
+// same handle): the unary form.  Allocates and synchronises.
 extern "C" int svt_dev_crossprod_csc_csc_dense_buffer(const svt_dev_csc *X, const svt_dev_csc *Y, double *out)
 {
 	if (X->nrow != Y->nrow)
 		return svt_set_error("svt_dev_crossprod_csc_csc_dense_buffer: non-conformable operands");
-	const int64_t nx = X->ncol, ny = Y->ncol;
-	if (nx == 0 || ny == 0) return 0;
-	HIP_TRY(hipMemset(out, 0, (size_t) nx * ny * 8));
-	if (X == Y) {
-		if (dev_crossprod_pp(X, X, out, 1, nx)) return -1;
-		if (launch_mirror_lower(out, nx, 0)) return -1;
-		HIP_TRY(hipDeviceSynchronize());
-		return 0;
-	}
-	const double Lpp = (double) Y->nnz * (double) nx, Rpp = (double) X->nnz * (double) ny;
-	return Lpp < Rpp ? dev_crossprod_pp(Y, X, out, nx, 1) : dev_crossprod_pp(X, Y, out, 1, nx);
+	if (X->ncol == 0 || Y->ncol == 0) return 0;
+	if (dense_buffer_route(X, Y, X == Y, out)) return -1;
+	HIP_TRY(hipDeviceSynchronize());
+	return 0;
+}
+
+// The sparse x sparse entry points' last step, into `out` (out_n doubles): sparse(O), the sparse-aware route into the
+// device buffer O (0: done; 1: declined, the route does not pay or a non-finite value took part; -1: error), then if
+// it declined dense(O), the dense-buffer route.
+template <class S, class D> static int sparse_then_dense(double *out, size_t out_n, S sparse, D dense)
+{
+	DevBuf O;
+	if (O.alloc(out_n * 8))
+		return -1;
+	const int st = sparse(O.as<double>());
+	if (st < 0 || (st > 0 && dense(O.as<double>())))
+		return -1;
+	return staged_download(out, O.p, out_n * 8);
 }
 
 static int64_t view_nzcount(const svt_view *x)   // _REC_nzcount_SVT, SVT_SparseArray_class.c:200-218
@@ -1989,35 +2004,21 @@ static int crossprod2_SVT_SVT_impl(const svt_view *x, const svt_view *y, double 
 		return 0;
 	const int64_t Lpp_nops = view_nzcount(y) * out_nrow;   // :1077-1078
 	const int64_t Rpp_nops = view_nzcount(x) * out_ncol;
+	const double dense_ops = (double) (Lpp_nops < Rpp_nops ? Lpp_nops : Rpp_nops);
 	CscGuard X(x), Y(y);
 	if (X.h == NULL || Y.h == NULL) return -1;
-	DevBuf O;
-	if (O.alloc(out_n * 8))
-		return -1;
 	// few pairs of nonzeros meet in a row: multiply only those (kernels_gram.hip); a non-finite value or an NA
-	// anywhere sends the product down the reference's route below
-	if (!x->svt_is_null && !y->svt_is_null &&
-	    sparse_route_pays(X.h->nnz, Y.h->nnz, in_nrow, (double) (Lpp_nops < Rpp_nops ? Lpp_nops : Rpp_nops), false)) {
-		const int st = dev_crossprod_sparse(X, Y.h, false, O.as<double>(), out_nrow, (double) (Lpp_nops < Rpp_nops ? Lpp_nops : Rpp_nops));
-		if (st < 0) return -1;
-		if (st == 0)
-			return staged_download(out, O.p, out_n * 8) ? -1 : 0;
-	}
-	if (O.zero())
-		return -1;
-	int rc;
-	if (Lpp_nops < Rpp_nops)   // expand the columns of x, walk the leaves of y
-		rc = dev_crossprod_pp(Y.h, X.h, O.as<double>(), out_nrow, 1);
-	else                       // expand the columns of y, walk the leaves of x
-		rc = dev_crossprod_pp(X.h, Y.h, O.as<double>(), 1, out_nrow);
-	if (rc) return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	// anywhere sends the product down the reference's route.  (Under the resident cache crossprod(x, x) gets one
+	// handle for both operands: still the two-operand form.)
+	const bool pays = !x->svt_is_null && !y->svt_is_null &&
+			  sparse_route_pays(X.h->nnz, Y.h->nnz, in_nrow, dense_ops, false);
+	return sparse_then_dense(out, out_n,
+		[&](double *O) { return pays ? dev_crossprod_sparse(X, Y.h, false, O, out_nrow, dense_ops) : 1; },
+		[&](double *O) { return dense_buffer_route(X.h, Y.h, false, O); });
 }
 extern "C" int svt_crossprod2_SVT_SVT(const svt_view *x, const svt_view *y, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(crossprod2_SVT_SVT_impl(x, y, out));
+	return abi_status([&] { return crossprod2_SVT_SVT_impl(x, y, out); });
 }
 
 // t(A) on the device, as a handle that owns its buffers (A may be released afterwards).
@@ -2048,17 +2049,16 @@ static svt_dev_csc *dev_transposed(const svt_dev_csc *A)
 	return T;
 }
 
-// t(A) of an operand: kept with a resident operand, else built for this call (*owned = 1).
-static svt_dev_csc *transposed_for(const CscGuard &A, int *owned)
+// t(A) of an operand: kept with a resident operand, else built for this call and owned by the result.
+static OwnedCsc transposed_for(const CscGuard &A)
 {
-	*owned = 1;
 	if (A.key != 0) {
 		std::lock_guard<std::mutex> lk(g_res_mu);
 		for (Resident &r : g_res)
-			if (r.key == A.key && r.tr != NULL) { *owned = 0; return r.tr; }
+			if (r.key == A.key && r.tr != NULL) return OwnedCsc(r.tr, false);
 	}
 	svt_dev_csc *T = dev_transposed(A.h);
-	if (T == NULL || A.key == 0) return T;
+	if (T == NULL || A.key == 0) return OwnedCsc(T, true);
 	std::lock_guard<std::mutex> lk(g_res_mu);
 	const size_t nb = csc_bytes(T);
 	resident_make_room(nb);                           // may erase entries: search afterwards
@@ -2066,10 +2066,9 @@ static svt_dev_csc *transposed_for(const CscGuard &A, int *owned)
 		for (Resident &r : g_res)
 			if (r.key == A.key) {
 				r.tr = T; r.bytes += nb; g_res_bytes += nb;
-				*owned = 0;
-				break;
+				return OwnedCsc(T, false);
 			}
-	return T;
+	return OwnedCsc(T, true);
 }
 
 // C_transpose_2D_SVT, src/SparseArray_aperm.c:395-423
@@ -2087,9 +2086,8 @@ static int transpose_2D_SVT_impl(const svt_view *x, int64_t *out_col_ptr,
 	}
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	int own_T = 1;
-	svt_dev_csc *T = transposed_for(A, &own_T);
-	OwnedCsc TA = { T, own_T };
+	const OwnedCsc TA = transposed_for(A);
+	const svt_dev_csc *T = TA.t;
 	if (T == NULL) return -1;
 	HIP_TRY(hipMemcpy(out_col_ptr, T->col_ptr, (size_t) (nrow + 1) * 8, hipMemcpyDeviceToHost));
 	if (T->nnz > 0) {
@@ -2102,8 +2100,7 @@ static int transpose_2D_SVT_impl(const svt_view *x, int64_t *out_col_ptr,
 extern "C" int svt_transpose_2D_SVT(const svt_view *x, int64_t *out_col_ptr,
 				    int32_t *out_row_idx, void *out_val)
 {
-	g_unsupported = 0;
-	return svt_status(transpose_2D_SVT_impl(x, out_col_ptr, out_row_idx, out_val));
+	return abi_status([&] { return transpose_2D_SVT_impl(x, out_col_ptr, out_row_idx, out_val); });
 }
 
 // x %*% y over the device list: shard s takes the rows [r0, r1) of x, transposes them and multiplies them with the
@@ -2115,30 +2112,21 @@ static int matmul_SVT_mat_sharded(const svt_view *x, const void *y, int y_nrow, 
 	const std::vector<int> devs = g_devices;
 	const int N = (int) devs.size();
 	const int64_t nrow = x->dim[0], K = y_ncol;
-	const size_t y_bytes = (size_t) y_nrow * y_ncol * elt_size(y_Rtype);
+	const size_t y_elems = (size_t) y_nrow * y_ncol;
 	return run_shards(devs, [&](int s) -> int {
 		int64_t r0, r1;
 		shard_rows(nrow, s, N, &r0, &r1);
 		const int64_t rs = r1 - r0;
 		if (rs == 0) return 0;
-		SubView sv;
-		row_block_view(x, (int) r0, (int) r1, sv);
-		CscGuard A(shard_upload(&sv.v, (int) r0));
+		CscGuard A(row_block_upload(x, r0, r1));
 		if (A.h == NULL) return -1;
-		int own_T = 1;
-		svt_dev_csc *T = transposed_for(A, &own_T);
-		OwnedCsc TA = { T, own_T };
-		if (T == NULL) return -1;
+		const OwnedCsc T = transposed_for(A);
+		if (T.t == NULL) return -1;
 		A.drop();
-		DevBuf Y, O;
-		PbcAhead ahead;
-		ahead.start(T, K);
-		if (Y.upload(y, y_bytes) || O.alloc((size_t) rs * K * 8) || O.zero())
-			return -1;
-		Promoted pr;
-		if (pr.promote(T, Y.p, y_Rtype, (size_t) y_nrow * y_ncol))
-			return -1;
-		if (dev_crossprod_chunked(pr.A, pr.Y, y_nrow, K, 0, O.as<double>(), 1, rs, pr.A == T ? &ahead : NULL))
+		auto put_y = [&](void *d) { return staged_copy(d, y, y_elems * elt_size(y_Rtype)); };
+		DevBuf O;
+		if (O.alloc((size_t) rs * K * 8) || O.zero() ||
+		    dense_product(T.t, K, y_Rtype, y_elems, put_y, y_nrow, 0, O.as<double>(), 1, rs))
 			return -1;
 		HIP_TRY(hipMemcpy2D(out + r0, (size_t) nrow * 8, O.p, (size_t) rs * 8, (size_t) rs * 8, (size_t) K,
 				    hipMemcpyDeviceToHost));
@@ -2171,31 +2159,21 @@ static int matmul_SVT_mat_impl(const svt_view *x, const void *y, int y_nrow,
 		return matmul_SVT_mat_sharded(x, y, y_nrow, y_ncol, y_Rtype, out);
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	int own_T = 1;
-	svt_dev_csc *T = transposed_for(A, &own_T);
-	OwnedCsc TA = { T, own_T };
-	if (T == NULL) return -1;
+	const OwnedCsc T = transposed_for(A);
+	if (T.t == NULL) return -1;
 	A.drop();                           // a one-call operand: its untransposed copy can go now
-	DevBuf Y, O;
-	PbcAhead ahead;
-	ahead.start(T, y_ncol);
-	if (Y.upload(y, (size_t) y_nrow * y_ncol * elt_size(y_Rtype)) ||
-	    O.alloc(out_n * 8) || O.zero())
+	const size_t y_elems = (size_t) y_nrow * y_ncol;
+	auto put_y = [&](void *d) { return staged_copy(d, y, y_elems * elt_size(y_Rtype)); };
+	DevBuf O;
+	if (O.alloc(out_n * 8) || O.zero() ||
+	    dense_product(T.t, y_ncol, y_Rtype, y_elems, put_y, y_nrow, 0, O.as<double>(), 1, out_nrow))
 		return -1;
-	Promoted pr;
-	if (pr.promote(T, Y.p, y_Rtype, (size_t) y_nrow * y_ncol))
-		return -1;
-	if (dev_crossprod_chunked(pr.A, pr.Y, y_nrow, y_ncol, 0, O.as<double>(), 1, out_nrow,
-				  pr.A == T ? &ahead : NULL))
-		return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	return staged_download(out, O.p, out_n * 8);
 }
 extern "C" int svt_matmul_SVT_mat(const svt_view *x, const void *y, int y_nrow,
 				  int y_ncol, int y_Rtype, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(matmul_SVT_mat_impl(x, y, y_nrow, y_ncol, y_Rtype, out));
+	return abi_status([&] { return matmul_SVT_mat_impl(x, y, y_nrow, y_ncol, y_Rtype, out); });
 }
 
 // x %*% y, both SVT_SparseMatrix: .crossprod2_SparseMatrix_SparseMatrix(t(x), y) with
@@ -2216,8 +2194,6 @@ static int matmul_SVT_SVT_impl(const svt_view *x, const svt_view *y, double *out
 	memset(out, 0, out_n * sizeof(double));
 	if (out_n == 0)
 		return 0;
-	const int64_t Lpp_nops = view_nzcount(y) * out_nrow;
-	const int64_t Rpp_nops = view_nzcount(x) * out_ncol;
 	CscGuard X(x);
 	if (X.h == NULL) return -1;
 	CscGuard Y(y);                                  // (one upload of y for both routes)
@@ -2242,27 +2218,15 @@ static int matmul_SVT_SVT_impl(const svt_view *x, const svt_view *y, double *out
 		} else
 			g_unsupported = 0;                // (a shape the row-panel kernel refuses: the route below)
 	}
-	int own_T = 1;
-	svt_dev_csc *T = transposed_for(X, &own_T);
-	OwnedCsc TX = { T, own_T };
-	if (T == NULL) return -1;
+	const OwnedCsc T = transposed_for(X);
+	if (T.t == NULL) return -1;
 	X.drop();
-	DevBuf O;
-	if (O.alloc(out_n * 8) || O.zero())
-		return -1;
-	int rc;
-	if (Lpp_nops < Rpp_nops)
-		rc = dev_crossprod_pp(Y.h, T, O.as<double>(), out_nrow, 1);
-	else
-		rc = dev_crossprod_pp(T, Y.h, O.as<double>(), 1, out_nrow);
-	if (rc) return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	return sparse_then_dense(out, out_n, [](double *) { return 1; },
+				 [&](double *O) { return dense_buffer_route(T.t, Y.h, false, O); });
 }
 extern "C" int svt_matmul_SVT_SVT(const svt_view *x, const svt_view *y, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(matmul_SVT_SVT_impl(x, y, out));
+	return abi_status([&] { return matmul_SVT_SVT_impl(x, y, out); });
 }
 
 // C_crossprod1_SVT, src/SparseMatrix_mult.c:1104-1140
@@ -2277,28 +2241,15 @@ static int crossprod1_SVT_impl(const svt_view *x, double *out)
 		return 0;
 	CscGuard X(x);
 	if (X.h == NULL) return -1;
-	DevBuf O;
-	if (O.alloc(out_n * 8))
-		return -1;
-	if (sparse_route_pays(X.h->nnz, X.h->nnz, x->dim[0], (double) X.h->nnz * (double) n, true)) {
-		const int st = dev_crossprod_sparse(X, X.h, true, O.as<double>(), n, (double) X.h->nnz * (double) n);
-		if (st < 0) return -1;
-		if (st == 0)
-			return staged_download(out, O.p, out_n * 8) ? -1 : 0;
-	}
-	if (O.zero())
-		return -1;
-	if (dev_crossprod_pp(X.h, X.h, O.as<double>(), 1, n))
-		return -1;
-	if (launch_mirror_lower(O.as<double>(), n, 0))
-		return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	const double dense_ops = (double) X.h->nnz * (double) n;
+	const bool pays = sparse_route_pays(X.h->nnz, X.h->nnz, x->dim[0], dense_ops, true);
+	return sparse_then_dense(out, out_n,
+		[&](double *O) { return pays ? dev_crossprod_sparse(X, X.h, true, O, n, dense_ops) : 1; },
+		[&](double *O) { return dense_buffer_route(X.h, X.h, true, O); });
 }
 extern "C" int svt_crossprod1_SVT(const svt_view *x, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(crossprod1_SVT_impl(x, out));
+	return abi_status([&] { return crossprod1_SVT_impl(x, out); });
 }
 
 // tcrossprod(x) = crossprod(t(x)) and tcrossprod(x, y) = crossprod(t(x), t(y)) of SVT_SparseMatrix objects in one call.
@@ -2319,33 +2270,18 @@ static int tcrossprod1_SVT_impl(const svt_view *x, double *out)
 		return 0;
 	CscGuard X(x);
 	if (X.h == NULL) return -1;
-	int own_T = 1;
-	svt_dev_csc *M = transposed_for(X, &own_T);             // M = t(x): ncol(x) rows, nrow(x) leaves
-	OwnedCsc TM = { M, own_T };
+	const OwnedCsc TM = transposed_for(X);                  // M = t(x): ncol(x) rows, nrow(x) leaves
+	const svt_dev_csc *M = TM.t;
 	if (M == NULL) return -1;
-	DevBuf O;
-	if (O.alloc(out_n * 8))
-		return -1;
 	const double dense_ops = (double) M->nnz * (double) n;
-	if (sparse_route_pays(M->nnz, M->nnz, M->nrow, dense_ops, true)) {
-		const int st = dev_crossprod_sparse_on(X.h, M, true, O.as<double>(), n, dense_ops);     // t(M) is x
-		if (st < 0) return -1;
-		if (st == 0)
-			return staged_download(out, O.p, out_n * 8) ? -1 : 0;
-	}
-	if (O.zero())
-		return -1;
-	if (dev_crossprod_pp(M, M, O.as<double>(), 1, n))
-		return -1;
-	if (launch_mirror_lower(O.as<double>(), n, 0))
-		return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	const bool pays = sparse_route_pays(M->nnz, M->nnz, M->nrow, dense_ops, true);
+	return sparse_then_dense(out, out_n,
+		[&](double *O) { return pays ? dev_crossprod_sparse_on(X.h, M, true, O, n, dense_ops) : 1; },   // t(M) is x
+		[&](double *O) { return dense_buffer_route(M, M, true, O); });
 }
 extern "C" int svt_tcrossprod1_SVT(const svt_view *x, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(tcrossprod1_SVT_impl(x, out));
+	return abi_status([&] { return tcrossprod1_SVT_impl(x, out); });
 }
 
 static int tcrossprod2_SVT_SVT_impl(const svt_view *x, const svt_view *y, double *out)
@@ -2365,42 +2301,23 @@ static int tcrossprod2_SVT_SVT_impl(const svt_view *x, const svt_view *y, double
 		return 0;
 	const int64_t Lpp_nops = view_nzcount(y) * out_nrow;
 	const int64_t Rpp_nops = view_nzcount(x) * out_ncol;
+	const double dense_ops = (double) (Lpp_nops < Rpp_nops ? Lpp_nops : Rpp_nops);
 	CscGuard X(x), Y(y);
 	if (X.h == NULL || Y.h == NULL) return -1;
-	int own_Ty = 1;
-	svt_dev_csc *Ty = transposed_for(Y, &own_Ty);
-	OwnedCsc TY = { Ty, own_Ty };
-	if (Ty == NULL) return -1;
-	DevBuf O;
-	if (O.alloc(out_n * 8))
-		return -1;
-	const double dense_ops = (double) (Lpp_nops < Rpp_nops ? Lpp_nops : Rpp_nops);
-	if (!x->svt_is_null && !y->svt_is_null && x->dim[1] > 0 &&
-	    sparse_route_pays(X.h->nnz, Y.h->nnz, x->dim[1], dense_ops, false)) {
-		const int st = dev_crossprod_sparse_on(X.h, Ty, false, O.as<double>(), out_nrow, dense_ops);   // t(t(x)) is x
-		if (st < 0) return -1;
-		if (st == 0)
-			return staged_download(out, O.p, out_n * 8) ? -1 : 0;
-	}
-	int own_Tx = 1;
-	svt_dev_csc *Tx = transposed_for(X, &own_Tx);
-	OwnedCsc TXg = { Tx, own_Tx };
-	if (Tx == NULL) return -1;
-	if (O.zero())
-		return -1;
-	int rc;
-	if (Lpp_nops < Rpp_nops)
-		rc = dev_crossprod_pp(Ty, Tx, O.as<double>(), out_nrow, 1);
-	else
-		rc = dev_crossprod_pp(Tx, Ty, O.as<double>(), 1, out_nrow);
-	if (rc) return -1;
-	if (staged_download(out, O.p, out_n * 8)) return -1;
-	return 0;
+	const OwnedCsc Ty = transposed_for(Y);
+	if (Ty.t == NULL) return -1;
+	const bool pays = !x->svt_is_null && !y->svt_is_null && x->dim[1] > 0 &&
+			  sparse_route_pays(X.h->nnz, Y.h->nnz, x->dim[1], dense_ops, false);
+	return sparse_then_dense(out, out_n,
+		[&](double *O) { return pays ? dev_crossprod_sparse_on(X.h, Ty.t, false, O, out_nrow, dense_ops) : 1; },   // t(t(x)) is x
+		[&](double *O) {
+			const OwnedCsc Tx = transposed_for(X);      // (only now: the sparse-aware route needs none)
+			return Tx.t == NULL ? -1 : dense_buffer_route(Tx.t, Ty.t, false, O);
+		});
 }
 extern "C" int svt_tcrossprod2_SVT_SVT(const svt_view *x, const svt_view *y, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(tcrossprod2_SVT_SVT_impl(x, y, out));
+	return abi_status([&] { return tcrossprod2_SVT_SVT_impl(x, y, out); });
 }
 
 // ==================================================================================
@@ -2423,28 +2340,26 @@ static int run_colstats(const svt_dev_csc *A, int opcode, int na_rm, double cent
 	return 0;
 }
 
-// colStats over the device list: shard s takes the output cells [g0, g1) -- leaves [g0 * inner, g1 * inner),
-// ranges balanced by nonzeros -- and writes its slice of `out`; the warn flags are ORed.
-static int colStats_SVT_sharded(const svt_view *x, int opcode, int na_rm, double center, int64_t inner, int64_t nout,
-				int out_Rtype, void *out, int *warn)
+// A leaf-range statistic over the device list: shard s takes the units [u0, u1) -- leaves [u0 * unit, u1 * unit),
+// ranges balanced by nonzeros (shard_cuts) -- and runs fn(A, u0, flag) on their upload; fn writes its slice of the
+// result.  *flag gets the OR of the shards' flags (warn, overflow).
+template <class F> static int run_leaf_shards(const svt_view *x, int64_t unit, int64_t nunits, int *flag, F fn)
 {
 	const std::vector<int> devs = g_devices;
 	const int N = (int) devs.size();
-	const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
-	const std::vector<int64_t> cut = shard_cuts(x, inner, nout, N);
-	std::vector<int> w((size_t) N, 0);
+	const std::vector<int64_t> cut = shard_cuts(x, unit, nunits, N);
+	std::vector<int> f((size_t) N, 0);
 	const int rc = run_shards(devs, [&](int s) -> int {
-		const int64_t g0 = cut[(size_t) s], g1 = cut[(size_t) s + 1];
-		if (g1 <= g0) return 0;
+		const int64_t u0 = cut[(size_t) s], u1 = cut[(size_t) s + 1];
+		if (u1 <= u0) return 0;
 		SubView sv;
-		col_block_view(x, g0 * inner, g1 * inner, sv);
+		col_block_view(x, u0 * unit, u1 * unit, sv);
 		CscGuard A(svt_upload(&sv.v));
 		if (A.h == NULL) return -1;
-		return run_colstats(A.h, opcode, na_rm, center, inner, (char *) out + (size_t) g0 * osz, out_Rtype,
-				    &w[(size_t) s]);
+		return fn(A.h, u0, &f[(size_t) s]);
 	});
 	for (int s = 0; s < N; s++)
-		if (w[(size_t) s]) *warn = 1;
+		if (f[(size_t) s]) *flag = 1;
 	return rc;
 }
 
@@ -2465,8 +2380,12 @@ static int colStats_SVT_impl(const svt_view *x, int opcode, int na_rm, double ce
 	if (nout == 0)
 		return 0;
 	const int out_Rtype = svt_colStats_out_Rtype(opcode, x->Rtype);
-	if (inner > 0 && shard_applies(x))
-		return colStats_SVT_sharded(x, opcode, na_rm, center, inner, nout, out_Rtype, out, warn);
+	if (inner > 0 && shard_applies(x)) {      // shard s: output cells [g0, ...)
+		const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
+		return run_leaf_shards(x, inner, nout, warn, [&](const svt_dev_csc *A, int64_t g0, int *w) {
+			return run_colstats(A, opcode, na_rm, center, inner, (char *) out + (size_t) g0 * osz, out_Rtype, w);
+		});
+	}
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
 	if (inner == 0) {
@@ -2484,8 +2403,7 @@ static int colStats_SVT_impl(const svt_view *x, int opcode, int na_rm, double ce
 extern "C" int svt_colStats_SVT(const svt_view *x, int opcode, int na_rm, double center,
 				int dims, void *out, int *warn)
 {
-	g_unsupported = 0;
-	return svt_status(colStats_SVT_impl(x, opcode, na_rm, center, dims, out, warn));
+	return abi_status([&] { return colStats_SVT_impl(x, opcode, na_rm, center, dims, out, warn); });
 }
 
 // colMedians(): .colMedians_SVT_SparseMatrix, R/SparseArray-matrixStats.R:761-784 (pure R in the
@@ -2507,15 +2425,10 @@ static int medians_SVT(const svt_view *x, int na_rm, int by_row, double *out)
 		return 0;
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	const svt_dev_csc *M = A.h;
-	int own_T = 0;
-	svt_dev_csc *T = NULL;
-	if (by_row) {           // rowMedians(x) = colMedians(t(x)), :802-815; t() on the device
-		T = transposed_for(A, &own_T);
-		if (T == NULL) return -1;
-		M = T;
-	}
-	OwnedCsc TG = { T, own_T };
+	// rowMedians(x) = colMedians(t(x)), :802-815; t() on the device
+	const OwnedCsc T = by_row ? transposed_for(A) : OwnedCsc(NULL, false);
+	if (by_row && T.t == NULL) return -1;
+	const svt_dev_csc *M = by_row ? T.t : A.h;
 	DevBuf O, W;
 	if (O.alloc((size_t) nout * 8) || W.alloc(colmedians_ws_bytes(M->nnz, nout)))
 		return -1;
@@ -2526,24 +2439,14 @@ static int medians_SVT(const svt_view *x, int na_rm, int by_row, double *out)
 	return staged_download(out, O.p, (size_t) nout * 8);
 }
 
-static int colMedians_SVT_impl(const svt_view *x, int na_rm, double *out)
-{
-	return medians_SVT(x, na_rm, 0, out);
-}
 extern "C" int svt_colMedians_SVT(const svt_view *x, int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(colMedians_SVT_impl(x, na_rm, out));
+	return abi_status([&] { return medians_SVT(x, na_rm, 0, out); });
 }
 
-static int rowMedians_SVT_impl(const svt_view *x, int na_rm, double *out)
-{
-	return medians_SVT(x, na_rm, 1, out);
-}
 extern "C" int svt_rowMedians_SVT(const svt_view *x, int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(rowMedians_SVT_impl(x, na_rm, out));
+	return abi_status([&] { return medians_SVT(x, na_rm, 1, out); });
 }
 
 // C_summarize_SVT, src/SparseArray_summarization.c:112-142
@@ -2587,8 +2490,7 @@ static int summarize_SVT_impl(const svt_view *x, int opcode, int na_rm, double c
 extern "C" int svt_summarize_SVT(const svt_view *x, int opcode, int na_rm, double center,
 				 double *out_d, int *out_i, int *out_Rtype, int *warn)
 {
-	g_unsupported = 0;
-	return svt_status(summarize_SVT_impl(x, opcode, na_rm, center, out_d, out_i, out_Rtype, warn));
+	return abi_status([&] { return summarize_SVT_impl(x, opcode, na_rm, center, out_d, out_i, out_Rtype, warn); });
 }
 
 // C_rowStats_SVT, src/SparseArray_matrixStats.c:1121-1205
@@ -2664,8 +2566,7 @@ static int rowStats_SVT_impl(const svt_view *x, int opcode, int na_rm,
 extern "C" int svt_rowStats_SVT(const svt_view *x, int opcode, int na_rm,
 				const double *center, int dims, void *out, int *warn)
 {
-	g_unsupported = 0;
-	return svt_status(rowStats_SVT_impl(x, opcode, na_rm, center, dims, out, warn));
+	return abi_status([&] { return rowStats_SVT_impl(x, opcode, na_rm, center, dims, out, warn); });
 }
 
 // ==================================================================================
@@ -2711,47 +2612,14 @@ static int groupsum_host(const svt_dev_csc *A, const int32_t *col_ptr32,
 	a.nrow = A->nrow; a.ncol = A->ncol;
 	a.group = G.as<int>(); a.ngroup = ngroup; a.na_rm = na_rm;
 	a.out = O.p; a.scratch = S.p; a.ovflow_flag = W.as<int>();
-	int rc;
-	if (colsum)
-		rc = launch_colsum(a, 0);
-	else if (A->Rtype == SVT_REALSXP && ngroup <= 8192 && A->ncol > 0 &&
-		 A->nnz / A->ncol >= ngroup / 4)
-		rc = launch_rowsum_lds(a, 0);
-	else
-		rc = launch_rowsum(a, 0);
+	const int rc = colsum ? launch_colsum(a, 0)
+			      : A->Rtype == SVT_REALSXP ? launch_rowsum_f64(a, A->nnz, 0) : launch_rowsum(a, 0);
 	if (rc) return -1;
 	int w = 0;
 	if (staged_download(out, O.p, (size_t) out_len * osz)) return -1;
 	HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
 	if (ovflow && w) *ovflow = 1;
 	return 0;
-}
-
-// rowsum over the device list: shard s takes the leaves [c0, c1) (ranges balanced by nonzeros); its ngroup x (c1 - c0)
-// block of the column-major result is contiguous in `out`.  The overflow flags are ORed.
-static int rowsum_SVT_sharded(const svt_view *x, const int *group, int ngroup, int na_rm, void *out, int *ovflow)
-{
-	const std::vector<int> devs = g_devices;
-	const int N = (int) devs.size();
-	const int64_t ncol = x->dim[1];
-	if ((int64_t) ngroup * ncol > 0x7FFFFFFFLL)   // safe_int_mult() guard, src/rowsum_methods.c:296-301
-		return svt_set_error("too many groups (matrix of sums will be too big)");
-	const size_t osz = elt_size(x->Rtype);
-	const std::vector<int64_t> cut = shard_cuts(x, 1, ncol, N);
-	std::vector<int> ov((size_t) N, 0);
-	const int rc = run_shards(devs, [&](int s) -> int {
-		const int64_t c0 = cut[(size_t) s], c1 = cut[(size_t) s + 1];
-		if (c1 <= c0) return 0;
-		SubView sv;
-		col_block_view(x, c0, c1, sv);
-		CscGuard A(svt_upload(&sv.v));
-		if (A.h == NULL) return -1;
-		return groupsum_host(A.h, NULL, group, ngroup, na_rm, false, (char *) out + (size_t) ngroup * c0 * osz,
-				     &ov[(size_t) s]);
-	});
-	for (int s = 0; s < N; s++)
-		if (ov[(size_t) s]) *ovflow = 1;
-	return rc;
 }
 
 static int xsum_SVT(const svt_view *x, const int *group, int ngroup, int na_rm,
@@ -2769,37 +2637,33 @@ static int xsum_SVT(const svt_view *x, const int *group, int ngroup, int na_rm,
 				     "SVT_SparseMatrix objects of this type at the moment");
 	if (check_group(group, colsum ? x->dim[1] : x->dim[0], ngroup))
 		return -1;
-	if (!colsum && shard_applies(x))
-		return rowsum_SVT_sharded(x, group, ngroup, na_rm, out, ovflow);
+	if (!colsum && shard_applies(x)) {
+		// shard s: the leaves [c0, c1); its ngroup x (c1 - c0) block of the column-major result is contiguous in `out`
+		const int64_t ncol = x->dim[1];
+		if ((int64_t) ngroup * ncol > 0x7FFFFFFFLL)   // safe_int_mult() guard, src/rowsum_methods.c:296-301
+			return svt_set_error("too many groups (matrix of sums will be too big)");
+		const size_t osz = elt_size(x->Rtype);
+		return run_leaf_shards(x, 1, ncol, ovflow, [&](const svt_dev_csc *A, int64_t c0, int *ov) {
+			return groupsum_host(A, NULL, group, ngroup, na_rm, false, (char *) out + (size_t) ngroup * c0 * osz, ov);
+		});
+	}
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
 	return groupsum_host(A.h, NULL, group, ngroup, na_rm, colsum, out, ovflow);
 }
 
 // C_rowsum_SVT, src/rowsum_methods.c:281-325
-static int rowsum_SVT_impl(const svt_view *x, const int *group, int ngroup,
-			      int na_rm, void *out, int *ovflow)
-{
-	return xsum_SVT(x, group, ngroup, na_rm, false, out, ovflow);
-}
 extern "C" int svt_rowsum_SVT(const svt_view *x, const int *group, int ngroup,
 			      int na_rm, void *out, int *ovflow)
 {
-	g_unsupported = 0;
-	return svt_status(rowsum_SVT_impl(x, group, ngroup, na_rm, out, ovflow));
+	return abi_status([&] { return xsum_SVT(x, group, ngroup, na_rm, false, out, ovflow); });
 }
 
 // C_colsum_SVT, src/rowsum_methods.c:363-401
-static int colsum_SVT_impl(const svt_view *x, const int *group, int ngroup,
-			      int na_rm, void *out, int *ovflow)
-{
-	return xsum_SVT(x, group, ngroup, na_rm, true, out, ovflow);
-}
 extern "C" int svt_colsum_SVT(const svt_view *x, const int *group, int ngroup,
 			      int na_rm, void *out, int *ovflow)
 {
-	g_unsupported = 0;
-	return svt_status(colsum_SVT_impl(x, group, ngroup, na_rm, out, ovflow));
+	return abi_status([&] { return xsum_SVT(x, group, ngroup, na_rm, true, out, ovflow); });
 }
 
 static int xsum_dgC(int nrow, int ncol, const double *xx, const int *xi, const int *xp,
@@ -2812,12 +2676,6 @@ static int xsum_dgC(int nrow, int ncol, const double *xx, const int *xi, const i
 	if (P.upload(xp, (size_t) (ncol + 1) * 4) || I.upload(xi, (size_t) nnz * 4) ||
 	    X.upload(xx, (size_t) nnz * 8))
 		return -1;
-	svt_dev_csc A;
-	memset(&A, 0, sizeof(A));
-	A.Rtype = SVT_REALSXP; A.nrow = nrow; A.ncol = ncol; A.nnz = nnz;
-	A.row_idx = I.as<int32_t>(); A.val = X.p;
-	int ov = 0;
-	// the LDS path reads col_ptr64; keep the int32 'p' slot on the atomic path
 	const int64_t out_len = colsum ? (int64_t) nrow * ngroup : (int64_t) ngroup * ncol;
 	if (out_len > 0x7FFFFFFFLL)
 		return svt_set_error("too many groups (matrix of sums will be too big)");
@@ -2829,43 +2687,28 @@ static int xsum_dgC(int nrow, int ncol, const double *xx, const int *xi, const i
 		return -1;
 	GroupSumArgs a;
 	memset(&a, 0, sizeof(a));
-	a.col_ptr32 = P.as<int32_t>();
-	a.row_idx = A.row_idx; a.val = A.val; a.Rtype = SVT_REALSXP;
+	a.col_ptr32 = P.as<int32_t>();      // (the LDS kernel reads col_ptr64: the int32 'p' slot takes the atomic one)
+	a.row_idx = I.as<int32_t>(); a.val = X.p; a.Rtype = SVT_REALSXP;
 	a.nrow = nrow; a.ncol = ncol; a.group = G.as<int>(); a.ngroup = ngroup;
 	a.na_rm = na_rm; a.out = O.p; a.scratch = S.p;
 	if (colsum ? launch_colsum(a, 0) : launch_rowsum(a, 0))
 		return -1;
-	(void) ov;
 	if (staged_download(out, O.p, (size_t) out_len * 8)) return -1;
 	return 0;
 }
 
 // C_rowsum_dgCMatrix / C_colsum_dgCMatrix, src/rowsum_methods.c:328-356, 404-439
-static int rowsum_dgCMatrix_impl(int nrow, int ncol, const double *xx, const int *xi,
-				    const int *xp, const int *group, int ngroup,
-				    int na_rm, double *out)
-{
-	return xsum_dgC(nrow, ncol, xx, xi, xp, group, ngroup, na_rm, false, out);
-}
 extern "C" int svt_rowsum_dgCMatrix(int nrow, int ncol, const double *xx, const int *xi,
 				    const int *xp, const int *group, int ngroup,
 				    int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(rowsum_dgCMatrix_impl(nrow, ncol, xx, xi, xp, group, ngroup, na_rm, out));
-}
-static int colsum_dgCMatrix_impl(int nrow, int ncol, const double *xx, const int *xi,
-				    const int *xp, const int *group, int ngroup,
-				    int na_rm, double *out)
-{
-	return xsum_dgC(nrow, ncol, xx, xi, xp, group, ngroup, na_rm, true, out);
+	return abi_status([&] { return xsum_dgC(nrow, ncol, xx, xi, xp, group, ngroup, na_rm, false, out); });
 }
 extern "C" int svt_colsum_dgCMatrix(int nrow, int ncol, const double *xx, const int *xi,
 				    const int *xp, const int *group, int ngroup,
 				    int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(colsum_dgCMatrix_impl(nrow, ncol, xx, xi, xp, group, ngroup, na_rm, out));
+	return abi_status([&] { return xsum_dgC(nrow, ncol, xx, xi, xp, group, ngroup, na_rm, true, out); });
 }
 
 // ==================================================================================
@@ -2921,49 +2764,25 @@ static int colstat_dgC(int nrow, int ncol, const double *xx, const int *xp, int 
 }
 
 // C_colMins_dgCMatrix / C_colMaxs_dgCMatrix, src/sparseMatrix_utils.c:128-138
-static int colMins_dgCMatrix_impl(int nrow, int ncol, const double *xx, const int *xp,
-				     int na_rm, double *out)
-{
-	return colstat_dgC(nrow, ncol, xx, xp, na_rm, 0, out);
-}
 extern "C" int svt_colMins_dgCMatrix(int nrow, int ncol, const double *xx, const int *xp,
 				     int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(colMins_dgCMatrix_impl(nrow, ncol, xx, xp, na_rm, out));
-}
-static int colMaxs_dgCMatrix_impl(int nrow, int ncol, const double *xx, const int *xp,
-				     int na_rm, double *out)
-{
-	return colstat_dgC(nrow, ncol, xx, xp, na_rm, 1, out);
+	return abi_status([&] { return colstat_dgC(nrow, ncol, xx, xp, na_rm, 0, out); });
 }
 extern "C" int svt_colMaxs_dgCMatrix(int nrow, int ncol, const double *xx, const int *xp,
 				     int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(colMaxs_dgCMatrix_impl(nrow, ncol, xx, xp, na_rm, out));
+	return abi_status([&] { return colstat_dgC(nrow, ncol, xx, xp, na_rm, 1, out); });
 }
 // C_colRanges_dgCMatrix, src/sparseMatrix_utils.c:143-166
-static int colRanges_dgCMatrix_impl(int nrow, int ncol, const double *xx, const int *xp,
-				       int na_rm, double *out)
-{
-	return colstat_dgC(nrow, ncol, xx, xp, na_rm, 2, out);
-}
 extern "C" int svt_colRanges_dgCMatrix(int nrow, int ncol, const double *xx, const int *xp,
 				       int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(colRanges_dgCMatrix_impl(nrow, ncol, xx, xp, na_rm, out));
+	return abi_status([&] { return colstat_dgC(nrow, ncol, xx, xp, na_rm, 2, out); });
 }
 // C_colVars_dgCMatrix, src/sparseMatrix_utils.c:205-223
-static int colVars_dgCMatrix_impl(int nrow, int ncol, const double *xx, const int *xp,
-				     int na_rm, double *out)
-{
-	return colstat_dgC(nrow, ncol, xx, xp, na_rm, 3, out);
-}
 extern "C" int svt_colVars_dgCMatrix(int nrow, int ncol, const double *xx, const int *xp,
 				     int na_rm, double *out)
 {
-	g_unsupported = 0;
-	return svt_status(colVars_dgCMatrix_impl(nrow, ncol, xx, xp, na_rm, out));
+	return abi_status([&] { return colstat_dgC(nrow, ncol, xx, xp, na_rm, 3, out); });
 }

@@ -431,6 +431,44 @@ def test_resident_operands(hip, oracle):
     assert_identical(hip.colSums(x), want[0])
 
 
+def test_resident_two_operand_crossprod_of_itself(hip, oracle):
+    """crossprod(x, x) and tcrossprod(x, x) under the resident cache: both operands resolve to one device handle,
+    and the dense-buffer route must still compute every cell (the two-operand form is not the unary one, which
+    computes half and mirrors).  Forced onto that route; 4.8e5 nonzeros x 1200 columns takes the panel-blocked
+    kernels with 512-column chunks, so a symmetric half would leave cells of later chunks at zero."""
+    from sparsearray_amd.device import set_sparse_crossprod_cost
+    def few_nonfinite(x, seed, n=8):
+        """x with n stored values (in n different leaves) replaced by NaN / Inf / -Inf."""
+        rng = np.random.default_rng(seed)
+        leaves = list(x.leaves)
+        for j in rng.choice([j for j, lf in enumerate(leaves) if lf is not None], n, replace=False):
+            offs, vals = leaves[j]
+            vals = vals.copy()
+            vals[rng.integers(0, len(vals))] = [np.nan, np.inf, -np.inf][rng.integers(0, 3)]
+            leaves[j] = (offs, vals)
+        return SVT_SparseArray(x.dim, x.type, leaves)
+
+    x = _svt(20000, 1200, 0.02, 41)
+    x2 = _svt(1200, 20000, 0.02, 42)
+    cases = [(x, x2), (few_nonfinite(x, 43), few_nonfinite(x2, 44))]
+    try:
+        set_sparse_crossprod_cost(-1.0)
+        for a, b in cases:
+            cold = [hip.crossprod(a, a), hip.tcrossprod(b, b)]
+            try:
+                hip.resident_set_limit(1 << 30)
+                warm = [hip.crossprod(a, a), hip.tcrossprod(b, b)]
+                assert hip.resident_stats()["hits"] > 0
+            finally:
+                hip.resident_set_limit(0)
+            for c, w in zip(cold, warm):
+                assert_identical(w, c)
+            assert_equal(warm[0], oracle.crossprod(a, a), tol=1e-9, atol=1e-11, strict_na=True)
+            assert_equal(warm[1], oracle.tcrossprod(b, b), tol=1e-9, atol=1e-11, strict_na=True)
+    finally:
+        set_sparse_crossprod_cost(1.0)
+
+
 @pytest.mark.parametrize("na_rm", [False, True])
 @pytest.mark.parametrize("type_", ["double", "integer", "NaArray"])
 def test_colstats_very_short_leaves(hip, oracle, type_, na_rm):
