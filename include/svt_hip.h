@@ -23,9 +23,13 @@
  *         error(), like the reference's own error() calls
  *         (e.g. src/SparseMatrix_mult.c:943-966).
  *   > 0   (SVT_UNSUPPORTED = 1) not supported HERE: the device kernels do not take
- *         this operand or operation -- 2^31 nonzeros or more in an aperm that moves
- *         the rows (perm[1] != 1) or in the second operand of the row-panel product
- *         (an SVT's total count is unbounded, R/SVT_SparseArray-class.R:13-23), too many strata
+ *         this operand or operation -- 2^31 nonzeros or more in the second operand of
+ *         the row-panel product (an SVT's total count is unbounded,
+ *         R/SVT_SparseArray-class.R:13-23; the host entry points fall back to the
+ *         transposition route inside the library), a permuted array of 2^31 - 1 leaves or
+ *         more in an aperm of 2^31 nonzeros or more (no aperm is refused for the operand's
+ *         nonzero count alone: t() and the permutations that move the rows take the boxed
+ *         drivers, the leaf-preserving ones count in 64 bits), too many strata
  *         for the row-statistics counters, an opcode the R API never sends
  *         (RANGE, SUM_X_X2, VAR2, SD2 for col / row statistics).  The reason is in
  *         svt_last_error(); nothing the caller relies on has been written.  The R glue
@@ -467,13 +471,15 @@ int svt_set_max_threads(int nthread);
 size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz);
 int svt_dev_transpose(const svt_dev_csc *A, int64_t *out_col_ptr, int32_t *out_row_idx,
 		      void *out_val, void *ws, size_t ws_bytes, void *stream);
-/* Box limit of the transposition, process-wide (tests, timing): n > 0 sends every operand of more
-   than n nonzeros through the boxed driver with boxes of at most n nonzeros (or one column);
-   n <= 0 restores the default (boxes only from 2^31 nonzeros on, of at most 2^30).  Every call
-   reads it once; a workspace sized under another setting may be too small (the call says so). */
+/* Box limit of the transposition and of the aperm that moves the rows, process-wide (tests, timing):
+   n > 0 sends every such operand of more than n nonzeros through the boxed driver with boxes of at
+   most n nonzeros (or one column / one index of the axis that becomes the rows); n <= 0 restores the
+   default (boxes only from 2^31 nonzeros on, of at most 2^30 for t(), 2^28 for aperm).
+   Leaf-preserving permutations are never boxed.  Every call reads it once; a workspace sized under
+   another setting may be too small (the call says so). */
 void svt_dev_set_box_nnz(int64_t n);
-/* Calls of this process that took the boxed driver (t(), and through it rowMedians, tcrossprod,
-   %*% ...); reset != 0 zeroes the count and returns the count before. */
+/* Calls of this process that took a boxed driver (t(), and through it rowMedians, tcrossprod,
+   %*% ...; aperm: once per call); reset != 0 zeroes the count and returns the count before. */
 int64_t svt_dev_boxed_calls(int reset);
 
 /* x %*% y for two sparse operands, y much sparser than a dense matrix (the `svt %*% svt2` of BASELINE config 3):
@@ -544,9 +550,21 @@ void svt_sparse_crossprod_set_cost(double factor);
    (caller-allocated); 1 <= ndim <= 8.  Asynchronous on `stream`, except for permutations whose new
    leading axis is an old outer axis and whose second axis is the old rows (aperm(x, c(3, 1, 2))): the
    choice between the per-slab kernel and the key sort reads one counter back and synchronises the
-   stream once.  Operands of 2^31 nonzeros or more: leaf-preserving permutations (perm[1] == 1)
-   only; the others answer > 0. */
+   stream once.
+   Every permutation is taken at every nonzero count.  Leaf-preserving permutations (perm[1] == 1) count
+   positions in 64 bits.  The others, on an operand of 2^31 nonzeros or more (or past svt_dev_set_box_nnz),
+   take the boxed driver: with q = perm[1] the old axis that becomes the rows, ranges of indices of axis q of
+   at most 2^28 nonzeros (or one index) are gathered, permuted one after the other by the routes below the
+   limit and copied to their place -- bit for bit the result of the unboxed routes (perm = c(2, 1): the boxed
+   t()).  Such a call synchronises the stream once for its cuts, and wherever a box's own route does (the
+   slab form).  It answers > 0 only when the permuted array has 2^31 - 1 leaves or more.
+   Workspace: svt_dev_aperm_perm_ws_bytes() is the need of one permutation (what svt_dev_aperm() checks);
+   svt_dev_aperm_ws_bytes() is at least the need of every permutation of `dim`, and the same value for both
+   whenever the boxed driver is not taken.  Past the limit the boxed need does not grow with nnz (route area at
+   the box size, two box-sized temporaries, O(leaves of the result + dim[q] + nnz / box)), and that of a
+   leaf-preserving permutation is the scratch of one scan over the leaf counts. */
 size_t svt_dev_aperm_ws_bytes(int64_t nnz, int ndim, const int64_t *dim);
+size_t svt_dev_aperm_perm_ws_bytes(int64_t nnz, int ndim, const int64_t *dim, const int *perm);
 int svt_dev_aperm(const svt_dev_csc *A, int ndim, const int64_t *dim, const int *perm,
 		  int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val,
 		  void *ws, size_t ws_bytes, void *stream);

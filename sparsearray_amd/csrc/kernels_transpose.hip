@@ -1665,7 +1665,9 @@ static size_t aperm_ws_core(int64_t nnz, const int64_t *dim, int ndim)
 // the workspace behind its caller's intermediates, which aperm_ws_bytes() sizes for the forms of aperm_ws_core() only:
 // it must not carve intermediates of its own (a slab form that refuses at run time -- one slab over
 // SLAB_CAP -- used to re-enter the general form inside `sub` and write past the workspace), so it goes from the
-// direct forms (leaf-preserving, first two axes swapped, slab) straight to the key sort.
+// direct forms (leaf-preserving, first two axes swapped, slab) straight to the key sort.  nested == 2: a box of the
+// boxed driver whose preferred route needs more than the driver's route area: the key sort alone, whose need
+// depends on the nonzero count only.
 static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
 			  int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
 			  int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, hipStream_t s, int nested);
@@ -1766,7 +1768,7 @@ static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const 
 	}
 	// the first two axes change places, the others stay: one batched bucketed transposition, no sort
 	{
-		bool swap01 = ndim >= 3 && perm[0] == 1 && perm[1] == 0;
+		bool swap01 = nested < 2 && ndim >= 3 && perm[0] == 1 && perm[1] == 0;
 		for (int a = 2; a < ndim && swap01; a++) swap01 = perm[a] == a;
 		T2Shape sh;
 		size_t reserve = 0;
@@ -1782,7 +1784,7 @@ static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const 
 	// slab form (see aperm_slab_kernel): new axis 0 = an old outer axis of <= 1024 entries, new axis 1 = the old
 	// rows, slabs of a few thousand nonzeros.  The largest slab is read back (one synchronisation of the
 	// stream): a slab over the cap sends the array through the key sort below.
-	if (ndim >= 3 && perm[1] == 0 && perm[0] >= 1 && dim[perm[0]] <= 1024 && dim[0] < ((int64_t) 1 << 30)) {
+	if (nested < 2 && ndim >= 3 && perm[1] == 0 && perm[0] >= 1 && dim[perm[0]] <= 1024 && dim[0] < ((int64_t) 1 << 30)) {
 		const int q = perm[0];
 		int64_t os[8], st = 1;
 		for (int a = 1; a < ndim; a++) { os[a] = st; st *= dim[a]; }
@@ -1931,4 +1933,355 @@ static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const 
 				   (const int32_t *) val, nnz, new_dim0, out_idx, (int32_t *) out_val);
 	HIP_TRY(hipGetLastError());
 	return 0;
+}
+
+// ---------------------------------------------------------------------------
+// aperm(x, perm) with perm[1] != 1 past 2^31 nonzeros: the boxed driver, the N-d counterpart of launch_transpose_boxed.
+// Let q = perm[0] be the old axis that becomes the rows of the result.  Inside every leaf of the result the entries are
+// ordered by their index i_q along q and no two share one.  A BOX is a range [q0, q1) of indices of axis q holding at
+// most `box` nonzeros, or a single index (at most one entry per result leaf: <= new_nleaves < 2^31 - 1 nonzeros).  The
+// sub-array x[..., q0:q1, ...] is an operand of its own below 2^31 nonzeros; permuted with the SAME perm by the
+// unchanged routes it has the leaves of the full result and rows 0 .. q1 - q0:
+//   axis    nonzeros per index of axis q from col_ptr alone (one thread per old leaf, 64-bit counters, privatised in
+//           LDS when dim[q] allows), scanned into qptr[dim[q] + 1]: the "col_ptr" of axis q.
+//   cuts    box_cut_kernel over qptr, as for t(): the index holding every multiple of `box` is a box of its own; indices
+//           Wq apart are cut too, so that a box's own leaves (Wq * leaves per index) stay within the workspace.  The
+//           cuts are read back: one stream synchronisation per call.
+//   count   the lengths of the result's leaves: one wavefront per old leaf, one 64-bit atomic per nonzero (the entries
+//           of one old leaf hit distinct counters), scanned in place into out_ptr; fill[] = 0.
+//   per box gather: the leaves with i_q in [q0, q1) -- a run of (q1 - q0) * stride_q leaves for every index of the axes
+//           outside q -- are copied with a rebased col_ptr into a box-sized temporary by the leaf-preserving form's own
+//           kernels (64-bit source positions, coalesced runs); when q is outermost the box is a slice of the operand
+//           and only its col_ptr is rebased.  Route: launch_aperm_n on (temporary, dims with q1 - q0 on axis q, perm)
+//           into a second temporary of new_nleaves + 1 pointers.  Placement: box_place_kernel, adding q0 to the rows.
+// Why the result is exact: boxes are taken in ascending q0, so every box contributes ONE contiguous run to every result
+// leaf and the runs come in box order = i_q order; only copies happen, and the permuted array has one representation.
+// Workspace: the route area R = the larger of the key sort's need and aperm_ws_bytes() at the largest box, two box
+// temporaries (12 B and 8-12 B per entry), new_nleaves + 1 pointers twice (box result, fill), qptr (dim[q] + 1), the
+// box's col_ptr, scan scratch, the cut table -- not O(nnz).  The routes' needs depend on the box's dims, which are not
+// known before the data is seen: a box whose preferred route needs more than R takes the key sort (nested = 2), whose
+// need depends on the box's nonzero count alone and is part of R.
+// ---------------------------------------------------------------------------
+#define ABOX_DEFAULT ((int64_t) 1 << 28)
+#define ABOX_LEAVES ((int64_t) 1 << 20)  // a box spans at most max(this, new_nleaves) old leaves (or one index of axis q)
+#define ABOX_CNT_NT 256
+#define ABOX_CNT_LDS 8192                // indices of axis q counted in LDS (64 KB of 64-bit counters); more: memory atomics
+
+static int64_t abox_size(int64_t box_limit)
+{
+	return box_limit > 0 ? (box_limit < 0x7FFFFFFFLL ? box_limit : 0x7FFFFFFFLL) : ABOX_DEFAULT;
+}
+
+static bool aperm_perm_ok(int ndim, const int *perm)
+{
+	if (ndim < 1 || ndim > 8)
+		return false;
+	bool seen[8] = {false, false, false, false, false, false, false, false};
+	for (int a = 0; a < ndim; a++) {
+		if (perm[a] < 0 || perm[a] >= ndim || seen[perm[a]])
+			return false;
+		seen[perm[a]] = true;
+	}
+	return true;
+}
+
+static size_t aperm_key_sort_bytes(int64_t nnz)
+{
+	const size_t a4 = ((size_t) (nnz > 0 ? nnz : 1) * 4 + 255) / 256 * 256;
+	return 7 * a4 + hint_bytes(nnz) + svt_sort_ws_bytes(nnz) + 256;
+}
+
+struct ABoxLayout {
+	bool ok;                 // the result has fewer than 2^31 - 1 leaves and no extent is 0
+	bool outer;              // q is the outermost axis with an extent over 1: a box is a slice of the operand
+	int64_t bsz, bmax, Wq, npts_max, new_nl, slice_nl, osq, nouter, box_leaves;
+	size_t pts, qptr, scan, fill, bcp, gidx, gval, bptr, bidx, bval, route, route_bytes, total;
+};
+
+static ABoxLayout abox_layout(int64_t nnz, const int64_t *dim, int ndim, int q, int64_t box_limit)
+{
+	ABoxLayout L;
+	memset(&L, 0, sizeof(L));
+	double nl = 1.0;
+	for (int a = 0; a < ndim; a++) {
+		if (dim[a] <= 0) return L;
+		if (a != q) nl *= (double) dim[a];
+	}
+	if (nl >= 2147483646.0) return L;
+	L.ok = true;
+	L.new_nl = (int64_t) nl;
+	L.slice_nl = L.new_nl / dim[0];                         // old leaves per index of axis q
+	L.osq = 1;
+	for (int a = 1; a < q; a++) L.osq *= dim[a];
+	L.nouter = L.slice_nl / L.osq;
+	L.outer = L.nouter == 1;
+	L.bsz = abox_size(box_limit);
+	L.bmax = L.bsz > L.new_nl ? L.bsz : L.new_nl;           // a box: <= bsz nonzeros, or one index of axis q
+	if (L.bmax > nnz) L.bmax = nnz > 0 ? nnz : 1;
+	const int64_t lcap = L.new_nl > ABOX_LEAVES ? L.new_nl : ABOX_LEAVES;
+	L.Wq = lcap / L.slice_nl > 1 ? lcap / L.slice_nl : 1;
+	if (L.Wq > dim[q]) L.Wq = dim[q];
+	L.box_leaves = L.Wq * L.slice_nl;
+	L.npts_max = (nnz + L.bsz - 1) / L.bsz + (dim[q] + L.Wq - 1) / L.Wq + 1;
+	size_t sc = exclusive_scan_ws_bytes(dim[q] + 1), t;
+	if ((t = exclusive_scan_ws_bytes(L.new_nl + 1)) > sc) sc = t;
+	if ((t = exclusive_scan_ws_bytes(L.box_leaves + 1)) > sc) sc = t;
+	L.route_bytes = aperm_ws_bytes(L.bmax, dim, ndim);
+	if ((t = aperm_key_sort_bytes(L.bmax)) > L.route_bytes) L.route_bytes = t;
+	size_t o = 0;
+	L.pts = o;   o += t2_a((size_t) L.npts_max * 3, 8);
+	L.qptr = o;  o += t2_a((size_t) dim[q] + 1, 8);
+	L.scan = o;  o += t2_a(sc, 1);
+	L.fill = o;  o += t2_a((size_t) L.new_nl + 1, 8);
+	L.bcp = o;   o += t2_a((size_t) L.box_leaves + 1, 8);
+	L.gidx = o;  o += L.outer ? 0 : t2_a((size_t) L.bmax, 4);
+	L.gval = o;  o += L.outer ? 0 : t2_a((size_t) L.bmax, 8);
+	L.bptr = o;  o += t2_a((size_t) L.new_nl + 1, 8);
+	L.bidx = o;  o += t2_a((size_t) L.bmax, 4);
+	L.bval = o;  o += t2_a((size_t) L.bmax, 8);
+	L.route = o; o += L.route_bytes;
+	L.total = o + 256;
+	return L;
+}
+
+// the need of one permutation (0-based perm, valid) under the box limit of the call
+size_t aperm_perm_ws_bytes_box(int64_t nnz, const int64_t *dim, int ndim, const int *perm, int64_t box_limit)
+{
+	if (!box_taken(nnz, box_limit) || !aperm_perm_ok(ndim, perm))
+		return aperm_ws_bytes(nnz, dim, ndim);
+	if (perm[0] == 0) {
+		// leaf-preserving, never boxed: the scratch of a scan over the leaf counts (with 2^31 - 1 leaves or more
+		// the call goes to the 64-bit key sort, or is refused)
+		double nl = 1.0;
+		for (int a = 1; a < ndim; a++) nl *= (double) (dim[a] > 0 ? dim[a] : 1);
+		if (nl < 2147483646.0)
+			return exclusive_scan_ws_bytes((int64_t) nl + 1) + 256;
+		return aperm_ws_bytes(nnz, dim, ndim);
+	}
+	if (ndim == 2)
+		return transpose_ws_bytes_box(dim[0], nnz, box_limit);
+	const ABoxLayout L = abox_layout(nnz, dim, ndim, perm[0], box_limit);
+	return L.ok ? L.total : 256;                            // (not ok: the call is refused before it touches the workspace)
+}
+
+// at least the need of every permutation; what aperm_ws_bytes() returns whenever the boxed driver is not taken
+size_t aperm_ws_bytes_box(int64_t nnz, const int64_t *dim, int ndim, int64_t box_limit)
+{
+	if (!box_taken(nnz, box_limit) || ndim < 1 || ndim > 8)
+		return aperm_ws_bytes(nnz, dim, ndim);
+	int perm[8];
+	for (int a = 0; a < ndim; a++) perm[a] = a;
+	size_t need = aperm_perm_ws_bytes_box(nnz, dim, ndim, perm, box_limit);
+	for (int q = 1; q < ndim; q++) {
+		perm[0] = q; perm[q] = 0;                           // (the need depends on perm through perm[0] alone)
+		const size_t t = aperm_perm_ws_bytes_box(nnz, dim, ndim, perm, box_limit);
+		if (t > need) need = t;
+		perm[0] = 0; perm[q] = q;
+	}
+	return need;
+}
+
+// cnt[i] += nonzeros of the old leaves whose index along axis q is i (cnt zeroed by the caller); grid-stride over leaves
+__global__ void __launch_bounds__(ABOX_CNT_NT)
+abox_axis_count_kernel(const int64_t *__restrict__ col_ptr, int64_t nleaves, int64_t osq, int64_t dq, int use_lds,
+		       unsigned long long *__restrict__ cnt)
+{
+	extern __shared__ unsigned long long hq[];
+	const bool lds = use_lds != 0;                  // (dq <= ABOX_CNT_LDS counters of dynamic LDS)
+	if (lds) {
+		for (int64_t i = threadIdx.x; i < dq; i += ABOX_CNT_NT) hq[i] = 0;
+		__syncthreads();
+	}
+	const int64_t stride = (int64_t) gridDim.x * ABOX_CNT_NT;
+	for (int64_t l = (int64_t) blockIdx.x * ABOX_CNT_NT + threadIdx.x; l < nleaves; l += stride) {
+		const int64_t n = col_ptr[l + 1] - col_ptr[l];
+		if (n == 0) continue;
+		const int64_t iq = (l / osq) % dq;
+		if (lds) atomicAdd(&hq[iq], (unsigned long long) n);
+		else atomicAdd(&cnt[iq], (unsigned long long) n);
+	}
+	if (lds) {
+		__syncthreads();
+		for (int64_t i = threadIdx.x; i < dq; i += ABOX_CNT_NT)
+			if (hq[i]) atomicAdd(&cnt[i], hq[i]);
+	}
+}
+
+struct ABoxMap {
+	int ndim;
+	int64_t dim[8];      // old extents
+	int64_t nmul[8];     // stride of old axis a in the NEW leaf index (0 for the axis that becomes the rows)
+};
+
+// len[new leaf] += 1 for every nonzero (len zeroed by the caller): one wavefront per old leaf, whose entries differ in
+// the old row and so hit distinct counters
+__global__ void __launch_bounds__(256)
+abox_leaf_len_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx, int64_t nleaves,
+		     ABoxMap m, unsigned long long *__restrict__ len)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t stride = (int64_t) gridDim.x * 4;
+	for (int64_t l = (int64_t) blockIdx.x * 4 + (threadIdx.x >> 6); l < nleaves; l += stride) {
+		const int64_t b = col_ptr[l], n = col_ptr[l + 1] - b;
+		if (n == 0) continue;
+		int64_t base = 0, rest = l;
+		for (int a = 1; a < m.ndim; a++) {
+			const int64_t ia = rest % m.dim[a];
+			rest /= m.dim[a];
+			base += ia * m.nmul[a];
+		}
+		for (int64_t k = lane; k < n; k += 64)
+			atomicAdd(&len[base + (int64_t) row_idx[b + k] * m.nmul[0]], 1ull);
+	}
+}
+
+static int launch_aperm_boxed(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
+			      int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
+			      int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, int64_t box_limit, hipStream_t s)
+{
+	const int q = perm[0];
+	const ABoxLayout Ly = abox_layout(nnz, dim, ndim, q, box_limit);
+	if (!Ly.ok) {
+		double nl = 1.0;
+		for (int a = 0; a < ndim; a++) if (a != q) nl *= (double) dim[a];
+		return svt_set_unsupported("aperm: the permuted array has %.0f leaves, 2^31-1 or more", nl);
+	}
+	char *w = (char *) ws;
+	int64_t *pts = (int64_t *) (w + Ly.pts), *qptr = (int64_t *) (w + Ly.qptr), *fill = (int64_t *) (w + Ly.fill);
+	int64_t *bcp = (int64_t *) (w + Ly.bcp), *bptr = (int64_t *) (w + Ly.bptr);
+	int32_t *gidx = (int32_t *) (w + Ly.gidx), *bidx = (int32_t *) (w + Ly.bidx);
+	void *gval = w + Ly.gval, *bval = w + Ly.bval, *rws = w + Ly.route, *scan_ws = w + Ly.scan;
+	const size_t esz = Rtype == SVT_REALSXP ? 8 : 4;
+	const int64_t dq = dim[q], new_nl = Ly.new_nl;
+	// nonzeros per index of axis q -> qptr
+	HIP_TRY(hipMemsetAsync(qptr, 0, (size_t) (dq + 1) * 8, s));
+	bool lds = dq <= ABOX_CNT_LDS;
+	if (lds && hipFuncSetAttribute((const void *) abox_axis_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+				       ABOX_CNT_LDS * 8) != hipSuccess) {
+		(void) hipGetLastError();
+		lds = false;
+	}
+	int64_t nbc = (ncol + ABOX_CNT_NT - 1) / ABOX_CNT_NT;
+	if (nbc > 1024) nbc = 1024;
+	hipLaunchKernelGGL(abox_axis_count_kernel, dim3((unsigned) nbc), dim3(ABOX_CNT_NT), lds ? (size_t) dq * 8 : 0, s,
+			   col_ptr, ncol, Ly.osq, dq, lds ? 1 : 0, (unsigned long long *) qptr);
+	HIP_TRY(hipGetLastError());
+	if (launch_exclusive_scan_i64(qptr, dq + 1, scan_ws, s))
+		return -1;
+	// the cuts, read back once
+	const int64_t nk = (nnz - 1) / Ly.bsz, nw = (dq - 1) / Ly.Wq, npts = nk + nw;
+	if (npts > Ly.npts_max)
+		return svt_set_error("aperm: internal error (box cuts)");
+	std::vector<int64_t> hp((size_t) npts * 3 + 1);
+	if (npts > 0) {
+		hipLaunchKernelGGL(box_cut_kernel, dim3((unsigned) ((npts + 255) / 256)), dim3(256), 0, s, qptr, dq, nk,
+				   Ly.bsz, Ly.Wq, npts, pts);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(hp.data(), pts, (size_t) npts * 24, hipMemcpyDeviceToHost, s));
+	}
+	// lengths of the result's leaves -> out_ptr (queued before the wait for the cuts)
+	ABoxMap mp;
+	memset(&mp, 0, sizeof(mp));
+	mp.ndim = ndim;
+	for (int a = 0; a < ndim; a++) mp.dim[a] = dim[a];
+	{
+		int64_t st = 1;
+		for (int a = 1; a < ndim; a++) { mp.nmul[perm[a]] = st; st *= dim[perm[a]]; }
+	}
+	HIP_TRY(hipMemsetAsync(out_ptr, 0, (size_t) (new_nl + 1) * 8, s));
+	HIP_TRY(hipMemsetAsync(fill, 0, (size_t) new_nl * 8, s));
+	int64_t nbl = (ncol + 3) / 4;
+	if (nbl > ((int64_t) 1 << 22)) nbl = (int64_t) 1 << 22;
+	hipLaunchKernelGGL(abox_leaf_len_kernel, dim3((unsigned) nbl), dim3(256), 0, s, col_ptr, row_idx, ncol, mp,
+			   (unsigned long long *) out_ptr);
+	HIP_TRY(hipGetLastError());
+	if (launch_exclusive_scan_i64(out_ptr, new_nl + 1, scan_ws, s))
+		return -1;
+	HIP_TRY(hipStreamSynchronize(s));
+	std::vector<std::pair<int64_t, int64_t>> bd;        // (index of axis q, qptr there): box boundaries
+	bd.reserve((size_t) npts * 2 + 2);
+	bd.push_back({0, 0});
+	bd.push_back({dq, nnz});
+	for (int64_t i = 0; i < npts; i++) {
+		bd.push_back({hp[3 * i], hp[3 * i + 1]});
+		bd.push_back({hp[3 * i] + 1, hp[3 * i + 2]});
+	}
+	std::sort(bd.begin(), bd.end());
+	bd.erase(std::unique(bd.begin(), bd.end()), bd.end());
+	const unsigned nbp = (unsigned) ((new_nl + 3) / 4);
+	int64_t bdim[8];
+	for (int a = 0; a < ndim; a++) bdim[a] = dim[a];
+	LeafMap lm;                                         // box leaf (inner, i_q - q0, outer) -> old leaf, from leaf q0 * osq on
+	memset(&lm, 0, sizeof(lm));
+	lm.ndim = 4;
+	lm.new_dim[1] = Ly.osq;    lm.old_stride[1] = 1;
+	lm.new_dim[3] = Ly.nouter; lm.old_stride[3] = Ly.osq * dq;
+	lm.old_stride[2] = Ly.osq;
+	for (size_t b = 0; b + 1 < bd.size(); b++) {
+		const int64_t q0 = bd[b].first, wq = bd[b + 1].first - q0, p0 = bd[b].second, nb = bd[b + 1].second - p0;
+		if (nb == 0)
+			continue;
+		if (nb > Ly.bmax || wq > Ly.Wq)
+			return svt_set_error("aperm: internal error (box of %lld nonzeros, %lld indices)", (long long) nb,
+					     (long long) wq);
+		const int64_t bl = wq * Ly.slice_nl;                // the box's leaves
+		const int64_t *lcp = col_ptr + q0 * Ly.osq;
+		const int32_t *bri = gidx;
+		const void *bv = gval;
+		if (Ly.outer) {
+			hipLaunchKernelGGL(box_rebase_kernel, dim3((unsigned) ((bl + 1 + 255) / 256)), dim3(256), 0, s,
+					   lcp, (int64_t) 0, bl, p0, bcp);
+			bri = row_idx + p0;
+			bv = (const char *) val + (size_t) p0 * esz;
+		} else {
+			lm.new_dim[2] = wq;
+			hipLaunchKernelGGL(aperm_leaf_count_kernel, dim3((unsigned) ((bl + 1 + 255) / 256)), dim3(256), 0, s,
+					   lcp, bl, lm, bcp);
+			if (launch_exclusive_scan_i64(bcp, bl + 1, scan_ws, s))
+				return -1;
+			const unsigned nbg = (unsigned) ((bl + 4 * APERM_LU - 1) / (4 * APERM_LU));
+			if (Rtype == SVT_REALSXP)
+				hipLaunchKernelGGL(aperm_leaf_copy_kernel<double>, dim3(nbg), dim3(256), 0, s, lcp, row_idx,
+						   (const double *) val, bl, lm, bcp, gidx, (double *) gval);
+			else
+				hipLaunchKernelGGL(aperm_leaf_copy_kernel<int32_t>, dim3(nbg), dim3(256), 0, s, lcp, row_idx,
+						   (const int32_t *) val, bl, lm, bcp, gidx, (int32_t *) gval);
+		}
+		HIP_TRY(hipGetLastError());
+		bdim[q] = wq;
+		// the box's preferred route where the route area holds it, else the key sort (whose need is part of the area)
+		const bool fits = aperm_ws_bytes(nb, bdim, ndim) <= Ly.route_bytes;
+		if (!fits && aperm_key_sort_bytes(nb) > Ly.route_bytes)
+			return svt_set_error("aperm: internal error (route area of a box)");
+		if (launch_aperm_n(bcp, bri, bv, Rtype, bl, nb, bdim, ndim, perm, bptr, bidx, bval, rws, s, fits ? 0 : 2))
+			return -1;
+		if (Rtype == SVT_REALSXP)
+			hipLaunchKernelGGL(box_place_kernel<double>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const double *) bval,
+					   new_nl, (int32_t) q0, out_ptr, fill, out_idx, (double *) out_val);
+		else
+			hipLaunchKernelGGL(box_place_kernel<int32_t>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const int32_t *) bval,
+					   new_nl, (int32_t) q0, out_ptr, fill, out_idx, (int32_t *) out_val);
+		HIP_TRY(hipGetLastError());
+	}
+	g_boxed_calls++;
+	return 0;
+}
+
+// aperm with the box limit of the call (read once by the caller): a permutation that moves the rows takes the boxed
+// driver past the limit (a 2-d one: the boxed t()); everything else the routes above exactly as they are.
+int launch_aperm_box(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
+		     int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
+		     int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, int64_t box_limit, hipStream_t s)
+{
+	if (!box_taken(nnz, box_limit) || ndim < 2 || !aperm_perm_ok(ndim, perm) || perm[0] == 0)
+		return launch_aperm(col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, perm, out_ptr, out_idx, out_val, ws, s);
+	if (ndim == 2)
+		return launch_transpose_box(col_ptr, row_idx, val, Rtype, dim[0], ncol, nnz, out_ptr, out_idx, out_val, ws,
+					    box_limit, s);
+	double total = 1.0;
+	for (int a = 0; a < ndim; a++) total *= (double) (dim[a] > 0 ? dim[a] : 1);
+	if (total >= 9.2e18)
+		return svt_set_error("aperm: array too large for 64-bit linear indices");
+	return launch_aperm_boxed(col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, perm, out_ptr, out_idx, out_val, ws,
+				  box_limit, s);
 }

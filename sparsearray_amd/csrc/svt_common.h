@@ -213,6 +213,14 @@ size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim);
 int launch_aperm(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
 		 int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
 		 int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, hipStream_t s);
+// the same with the boxed driver for the permutations that move the rows, past the box limit (read once per call and
+// passed down); perm is 0-based.  aperm_ws_bytes_box(): at least the need of every permutation, and aperm_ws_bytes()
+// itself whenever the driver is not taken; aperm_perm_ws_bytes_box(): the need of one permutation.
+size_t aperm_ws_bytes_box(int64_t nnz, const int64_t *dim, int ndim, int64_t box_limit);
+size_t aperm_perm_ws_bytes_box(int64_t nnz, const int64_t *dim, int ndim, const int *perm, int64_t box_limit);
+int launch_aperm_box(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
+		     int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
+		     int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, int64_t box_limit, hipStream_t s);
 
 struct GroupSumArgs {
 	const int64_t *col_ptr64;   // one of the two col_ptr flavours is set

@@ -1127,7 +1127,16 @@ static int aperm_args(int ndim, const int *perm, int *perm0)
 
 extern "C" size_t svt_dev_aperm_ws_bytes(int64_t nnz, int ndim, const int64_t *dim)
 {
-	return aperm_ws_bytes(nnz, dim, ndim);
+	return aperm_ws_bytes_box(nnz, dim, ndim, box_nnz_get());
+}
+
+extern "C" size_t svt_dev_aperm_perm_ws_bytes(int64_t nnz, int ndim, const int64_t *dim, const int *perm)
+{
+	int perm0[8];
+	if (ndim < 1 || ndim > 8)
+		return aperm_ws_bytes_box(nnz, dim, ndim, box_nnz_get());
+	for (int a = 0; a < ndim; a++) perm0[a] = perm[a] - 1;      // (not a permutation: the need of every permutation)
+	return aperm_perm_ws_bytes_box(nnz, dim, ndim, perm0, box_nnz_get());
 }
 
 static int dev_aperm_impl(const svt_dev_csc *A, int ndim, const int64_t *dim, const int *perm,
@@ -1141,10 +1150,11 @@ static int dev_aperm_impl(const svt_dev_csc *A, int ndim, const int64_t *dim, co
 	for (int a = 1; a < ndim; a++) nl *= dim[a];
 	if (dim[0] != A->nrow || nl != A->ncol)
 		return svt_set_error("aperm: 'dim' does not match the operand");
-	if (ws_bytes < aperm_ws_bytes(A->nnz, dim, ndim))
+	const int64_t box = box_nnz_get();                  // (once: the size check and the launch agree)
+	if (ws_bytes < aperm_perm_ws_bytes_box(A->nnz, dim, ndim, perm0, box))
 		return svt_set_error("svt_dev_aperm: workspace too small");
-	return launch_aperm(A->col_ptr, A->row_idx, A->val, A->Rtype, A->ncol, A->nnz, dim, ndim,
-			    perm0, out_col_ptr, out_row_idx, out_val, ws, (hipStream_t) stream);
+	return launch_aperm_box(A->col_ptr, A->row_idx, A->val, A->Rtype, A->ncol, A->nnz, dim, ndim,
+				perm0, out_col_ptr, out_row_idx, out_val, ws, box, (hipStream_t) stream);
 }
 extern "C" int svt_dev_aperm(const svt_dev_csc *A, int ndim, const int64_t *dim, const int *perm,
 			     int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val,
@@ -1169,12 +1179,13 @@ static int aperm_SVT_impl(const svt_view *x, const int *perm, int64_t *out_col_p
 	if (A.h == NULL) return -1;
 	const size_t esz = elt_size(x->Rtype);
 	const size_t nn = (size_t) (A.h->nnz > 0 ? A.h->nnz : 1);
+	const int64_t box = box_nnz_get();
 	DevBuf P, I, V, W;
 	if (P.alloc((size_t) (new_nl + 1) * 8) || I.alloc(nn * 4) || V.alloc(nn * esz) ||
-	    W.alloc(aperm_ws_bytes(A.h->nnz, dim, x->ndim)))
+	    W.alloc(aperm_perm_ws_bytes_box(A.h->nnz, dim, x->ndim, perm0, box)))
 		return -1;
-	if (launch_aperm(A.h->col_ptr, A.h->row_idx, A.h->val, A.h->Rtype, A.h->ncol, A.h->nnz, dim,
-			 x->ndim, perm0, P.as<int64_t>(), I.as<int32_t>(), V.p, W.p, 0))
+	if (launch_aperm_box(A.h->col_ptr, A.h->row_idx, A.h->val, A.h->Rtype, A.h->ncol, A.h->nnz, dim,
+			     x->ndim, perm0, P.as<int64_t>(), I.as<int32_t>(), V.p, W.p, box, 0))
 		return -1;
 	HIP_TRY(hipMemcpy(out_col_ptr, P.p, (size_t) (new_nl + 1) * 8, hipMemcpyDeviceToHost));
 	if (A.h->nnz) {

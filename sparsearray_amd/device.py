@@ -92,6 +92,8 @@ def _lib():
         lib.svt_dev_boxed_calls.restype = c_int64
         lib.svt_dev_aperm_ws_bytes.restype = c_size_t
         lib.svt_dev_aperm_ws_bytes.argtypes = [c_int64, c_int, c_void_p]
+        lib.svt_dev_aperm_perm_ws_bytes.restype = c_size_t
+        lib.svt_dev_aperm_perm_ws_bytes.argtypes = [c_int64, c_int, c_void_p, c_void_p]
         lib.svt_dev_aperm.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]
         _protos_done = True
@@ -149,7 +151,9 @@ class DeviceCSC:
     def aperm(self, dim, perm):
         """aperm(x, perm) on the device for the N-d array of extents ``dim`` stored in
         this layout (dim[0] == nrow, prod(dim[1:]) == ncol); ``perm`` is 1-based.
-        Returns (DeviceCSC of the permuted array, its dim)."""
+        Returns (DeviceCSC of the permuted array, its dim).  The workspace is the permutation's own need
+        (svt_dev_aperm_perm_ws_bytes): past the box limit a permutation that moves the rows takes the boxed
+        driver, a leaf-preserving one needs the scratch of one scan."""
         dim = np.asarray(dim, dtype=np.int64)
         perm = np.asarray(perm, dtype=np.int32)
         new_dim = tuple(int(dim[p - 1]) for p in perm)
@@ -158,7 +162,7 @@ class DeviceCSC:
         cp = torch.empty(new_nl + 1, dtype=torch.int64, device=dev)
         ri = torch.empty(self.nnz, dtype=torch.int32, device=dev)
         vv = torch.empty(self.nnz, dtype=self.val.dtype, device=dev)
-        nb = _lib().svt_dev_aperm_ws_bytes(self.nnz, len(dim), dim.ctypes.data)
+        nb = _lib().svt_dev_aperm_perm_ws_bytes(self.nnz, len(dim), dim.ctypes.data, perm.ctypes.data)
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         _check(_lib().svt_dev_aperm(self.handle, len(dim), dim.ctypes.data, perm.ctypes.data,
                                     cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
@@ -253,13 +257,16 @@ def aperm_route_counts(reset=False) -> dict:
 
 
 def set_box_nnz(n: int = 0) -> None:
-    """Box limit of the device transposition (svt_dev_set_box_nnz): n > 0 sends every operand of more than n
-    nonzeros through the boxed driver with boxes of at most n; n <= 0 restores the default (2^31 / 2^30)."""
+    """Box limit of the device transposition and of the aperm that moves the rows (svt_dev_set_box_nnz): n > 0
+    sends every such operand of more than n nonzeros through the boxed driver with boxes of at most n (or one
+    column / one index of the axis that becomes the rows); n <= 0 restores the default (from 2^31 nonzeros on,
+    boxes of 2^30 for t(), 2^28 for aperm).  Leaf-preserving permutations are never boxed."""
     _lib().svt_dev_set_box_nnz(int(n))
 
 
 def boxed_calls(reset=False) -> int:
-    """Transpositions of this process that took the boxed driver (svt_dev_boxed_calls)."""
+    """Transpositions and row-moving permutations of this process that took a boxed driver, one per call
+    (svt_dev_boxed_calls)."""
     return int(_lib().svt_dev_boxed_calls(int(bool(reset))))
 
 
