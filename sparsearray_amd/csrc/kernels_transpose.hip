@@ -130,14 +130,33 @@ int launch_exclusive_scan_i64(int64_t *data, int64_t n, void *ws, hipStream_t s)
 // launch_transpose_sorted() below.
 // ---------------------------------------------------------------------------
 // which route the transpositions / permutations of this process took (svt_dev_aperm_route_counts; the fuzzers print it:
-// evidence for what is hot and what is a fallback): 0 t() bucketed, 1 t() key sort, 2 aperm leaf-preserving,
-// 3 first two axes swapped (bucketed), 4 slab form, 5 3-d via an intermediate, 6 general (composed), 7 key sort, 32-bit
-// keys, 8 key sort, 64-bit keys, 9 slab form refused at run time
-static int64_t g_route[10];
+// evidence for what is hot and what is a fallback), in the order device.aperm_route_counts() names them.  Atomic: the
+// sharded host entry points transpose on one thread per device.
+enum {
+	R_T_BUCKETED, R_T_KEY_SORT, R_LEAF_PRESERVING, R_SWAP01 /* first two axes swapped (bucketed) */, R_SLAB,
+	R_VIA_3D, R_GENERAL /* composed */, R_SORT32, R_SORT64, R_SLAB_REFUSED /* at run time */, R_NROUTES
+};
+static std::atomic<int64_t> g_route[R_NROUTES];
 void aperm_route_counts(int64_t *out, int reset)
 {
-	for (int i = 0; i < 10; i++) { if (out != NULL) out[i] = g_route[i]; if (reset) g_route[i] = 0; }
+	for (int i = 0; i < R_NROUTES; i++) {
+		const int64_t v = reset ? g_route[i].exchange(0) : g_route[i].load();
+		if (out != NULL) out[i] = v;
+	}
 }
+
+// bytes of n elements of esz bytes as a part of a workspace: rounded up to 256
+static size_t t2_a(size_t n, size_t esz) { return (n * esz + 255) / 256 * 256; }
+
+// product of the extents dim[from .. to) as a double, without axis `skip`; an extent below 1 counts as 1 unless !clamp
+static double extent_prod(const int64_t *dim, int from, int to, int skip = -1, bool clamp = true)
+{
+	double p = 1.0;
+	for (int a = from; a < to; a++)
+		if (a != skip) p *= (double) (clamp && dim[a] < 1 ? 1 : dim[a]);
+	return p;
+}
+#define LEAVES_MAX 2147483646.0   // leaf counts the 32-bit forms take lie below this
 
 #define T2_NT 256                 // columns per group = threads per workgroup of pass 2
 #define T2_NFINE_MAX 32           // fine buckets per coarse bucket: 16 or 32 (T2Shape::cbits = 4 or 5)
@@ -231,16 +250,6 @@ transpose_count_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__res
 		}
 		__syncthreads();
 	}
-}
-
-// first position in [lo, hi) whose row is >= r
-__device__ inline int64_t t2_lower_bound(const int32_t *__restrict__ row_idx, int64_t lo, int64_t hi, int64_t r)
-{
-	while (lo < hi) {
-		const int64_t mid = (lo + hi) >> 1;
-		if ((int64_t) row_idx[mid] < r) lo = mid + 1; else hi = mid;
-	}
-	return lo;
 }
 
 // Passes 2 and 3 are the same operation: a workgroup holds a SEQUENCE of nonzeros made of pieces (pass 2:
@@ -669,7 +678,15 @@ static bool t2_shape(int64_t nrow, int64_t ncol, int64_t nnz_all, T2Shape *sh, i
 	return ntab < 1.0e8 && nwg < 2.0e9 && sh->ngroups <= 6000;      // (pass 3 keeps one int per group in LDS)
 }
 
-static size_t t2_a(size_t n, size_t esz) { return (n * esz + 255) / 256 * 256; }
+// Head of the bucketed form's workspace: [table ntab * 8][fine buckets' output positions (nslab * nfb + 1) * 8][scan scratch].
+// launch_transpose() tests it against t2_reserve(), aperm_swap01_bytes() sizes its reserve from it, launch_transpose_bucketed() carves it.
+struct T2Head { int64_t ntab; size_t table, fb_base, scan, total; };
+static T2Head t2_head(const T2Shape &sh)
+{
+	const int64_t ntab = ((sh.nslab * sh.ncoarse * sh.ngroups) << sh.cbits) + 1;
+	const size_t fb = t2_a((size_t) ntab, 8), scan = fb + t2_a((size_t) (sh.nslab * sh.nfb + 1), 8);
+	return T2Head{ntab, 0, fb, scan, scan + exclusive_scan_ws_bytes(ntab)};
+}
 
 // ---- fallback: stable LSD radix sort of (row -> position) pairs, then a gather (rounds 1-2; any shape) ----
 __global__ void iota_u32_kernel(uint32_t *__restrict__ p, int64_t n)
@@ -745,6 +762,9 @@ __global__ void transpose_gather_kernel(const int64_t *__restrict__ col_ptr, int
 	out_val[i] = val[k];
 }
 
+static unsigned blocks256(int64_t n) { return (unsigned) ((n + 255) / 256); }
+static unsigned blocks256_xcd(int64_t n) { return (unsigned) (((n + 255) / 256 + 7) / 8 * 8); }      // whole rounds over the 8 XCDs (xcd_chunk)
+
 static int key_bits(int64_t nrow)
 {
 	int b = 1;
@@ -758,57 +778,39 @@ static size_t hint_bytes(int64_t nnz)
 }
 
 // [sorted rows nnz*4][positions nnz*4][sorted positions nnz*4][second buffers of the sort's passes 2 * nnz*4][column hints]
-// [the sort's histograms]
-static size_t transpose_sorted_ws_bytes(int64_t nrow, int64_t nnz)
+// [the sort's histograms] + 256
+struct TSortedLayout { size_t srows, pos, perm, ktmp, ptmp, hint, sort, total; };
+static TSortedLayout t_sorted_layout(int64_t nnz)
 {
-	(void) nrow;
-	const size_t a = ((size_t) (nnz > 0 ? nnz : 1) * 4 + 255) / 256 * 256;
-	return 5 * a + hint_bytes(nnz) + svt_sort_ws_bytes(nnz) + 256;
+	const size_t a = t2_a((size_t) (nnz > 0 ? nnz : 1), 4), sort = 5 * a + hint_bytes(nnz);
+	return TSortedLayout{0, a, 2 * a, 3 * a, 4 * a, 5 * a, sort, sort + svt_sort_ws_bytes(nnz) + 256};
 }
+static size_t transpose_sorted_ws_bytes(int64_t nnz) { return t_sorted_layout(nnz).total; }
 
 static int launch_transpose_sorted(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
 		     int64_t nrow, int64_t ncol, int64_t nnz, int64_t *out_ptr, int32_t *out_idx,
 		     void *out_val, void *ws, hipStream_t s)
 {
-	if (nnz >= ((int64_t) 1 << 31))
-		return svt_set_unsupported("svt_dev_transpose: more than 2^31-1 nonzeros");
-	g_route[1]++;
-	const unsigned nbr = (unsigned) ((nrow + 1 + 255) / 256);
-	if (nnz == 0) {
-		HIP_TRY(hipMemsetAsync(out_ptr, 0, (size_t) (nrow + 1) * 8, s));
-		return 0;
-	}
-	const size_t a = ((size_t) nnz * 4 + 255) / 256 * 256;
-	int32_t *srows = (int32_t *) ws;
-	uint32_t *pos = (uint32_t *) ((char *) ws + a);
-	uint32_t *perm = (uint32_t *) ((char *) ws + 2 * a);
-	uint32_t *ktmp = (uint32_t *) ((char *) ws + 3 * a), *ptmp = (uint32_t *) ((char *) ws + 4 * a);
-	uint32_t *hint = (uint32_t *) ((char *) ws + 5 * a);
-	void *tmp = (char *) ws + 5 * a + hint_bytes(nnz);
-	const int bits = key_bits(nrow);
-	const unsigned nb = (unsigned) ((nnz + 255) / 256);
-	const unsigned nb8 = (unsigned) (((nnz + 255) / 256 + 7) / 8 * 8);      // whole rounds over the 8 XCDs (xcd_chunk)
-	hipLaunchKernelGGL(iota_u32_kernel, dim3(nb), dim3(256), 0, s, pos, nnz);
+	g_route[R_T_KEY_SORT]++;
+	const TSortedLayout L = t_sorted_layout(nnz);
+	char *w = (char *) ws;
+	uint32_t *srows = (uint32_t *) (w + L.srows), *pos = (uint32_t *) (w + L.pos), *perm = (uint32_t *) (w + L.perm);
+	uint32_t *ktmp = (uint32_t *) (w + L.ktmp), *ptmp = (uint32_t *) (w + L.ptmp), *hint = (uint32_t *) (w + L.hint);
+	hipLaunchKernelGGL(iota_u32_kernel, dim3(blocks256(nnz)), dim3(256), 0, s, pos, nnz);
 	const int64_t nblk = (nnz >> HINT_SHIFT) + 1;
-	hipLaunchKernelGGL(col_hint_kernel, dim3((unsigned) ((nblk + 1 + 255) / 256)), dim3(256), 0, s, col_ptr, ncol, nblk, hint);
+	hipLaunchKernelGGL(col_hint_kernel, dim3(blocks256(nblk + 1)), dim3(256), 0, s, col_ptr, ncol, nblk, hint);
 	// stable sort of (row, position) by row: positions ascend inside a row = (row, column) order
-	if (svt_sort_pairs<uint32_t>((const uint32_t *) row_idx, (uint32_t *) srows, ktmp, pos, perm, ptmp, nnz, bits, tmp, s))
+	if (svt_sort_pairs<uint32_t>((const uint32_t *) row_idx, srows, ktmp, pos, perm, ptmp, nnz, key_bits(nrow), w + L.sort, s))
 		return -1;
-	hipLaunchKernelGGL(row_bounds_kernel, dim3(nbr), dim3(256), 0, s, srows, nnz, nrow, out_ptr);
-	if (Rtype == SVT_REALSXP)
-		hipLaunchKernelGGL(transpose_gather_kernel<double>, dim3(nb8), dim3(256), 0, s, col_ptr, ncol,
-				   (const double *) val, perm, hint, nnz, out_idx, (double *) out_val);
-	else
-		hipLaunchKernelGGL(transpose_gather_kernel<int32_t>, dim3(nb8), dim3(256), 0, s, col_ptr, ncol,
-				   (const int32_t *) val, perm, hint, nnz, out_idx, (int32_t *) out_val);
+	hipLaunchKernelGGL(row_bounds_kernel, dim3(blocks256(nrow + 1)), dim3(256), 0, s, (const int32_t *) srows, nnz, nrow, out_ptr);
+	svt_by_rtype(Rtype, val, out_val, [&](auto *v, auto *o) {
+		hipLaunchKernelGGL(transpose_gather_kernel, dim3(blocks256_xcd(nnz)), dim3(256), 0, s, col_ptr, ncol, v, perm, hint, nnz, out_idx, o);
+	});
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
 
-
-// workspace of the bucketed form: [reserve: table (nfb * ngroups + 1) * 8, scan scratch][columns nnz*4][rows in
-// bucket nnz][values nnz*8]
-// Head of the workspace kept for the bucket table, the fine buckets' output positions and the scan scratch.
+// workspace of the bucketed form: [reserve, which starts with t2_head()][t2_body()].  What t() reserves:
 // The caller sizes the workspace from (nrow, nnz) alone; the shapes the bucketed form accepts (at least one
 // nonzero per column and coarse bucket) have at most ~nnz / 8 + 512 * nnz / nrow table entries and at most
 // nrow fine buckets, and never more than 96 MiB are set aside: an operand that needs more takes the key sort.
@@ -821,30 +823,37 @@ static size_t t2_reserve(int64_t nrow, int64_t nnz)
 	return b >= (double) cap ? cap : ((size_t) b + 255) / 256 * 256;
 }
 
+// behind the reserve: [columns nnz*4][rows in bucket nnz][values nnz*8][coarse-bucket starts per column ncstart*4] + 512
+struct T2Body { size_t col1, rlow1, val1, cstart, total; };
+static T2Body t2_body(size_t reserve, size_t nnz, size_t ncstart)
+{
+	const size_t rlow1 = reserve + t2_a(nnz, 4), val1 = rlow1 + t2_a(nnz, 1), cstart = val1 + t2_a(nnz, 8);
+	return T2Body{reserve, rlow1, val1, cstart, cstart + t2_a(ncstart, 4) + 512};
+}
+
 size_t transpose_ws_bytes(int64_t nrow, int64_t nnz)
 {
 	const size_t n = (size_t) (nnz > 0 ? nnz : 1);
-	const size_t sorted = transpose_sorted_ws_bytes(nrow, nnz);
-	// (+ the coarse-bucket starts per column: (ncoarse + 1) * ncol <= 2 * nnz entries for the shapes accepted)
-	const size_t b2 = t2_reserve(nrow, nnz) + t2_a(n, 4) + t2_a(n, 1) + t2_a(n, 8) + t2_a(2 * n + 64, 4) + 512;
+	const size_t sorted = transpose_sorted_ws_bytes(nnz);
+	// (the coarse-bucket starts per column: (ncoarse + 1) * ncol <= 2 * nnz entries for the shapes accepted)
+	const size_t b2 = t2_body(t2_reserve(nrow, nnz), n, 2 * n + 64).total;
 	return sorted > b2 ? sorted : b2;
 }
 
-template <typename T>
-static int launch_transpose_bucketed(const int64_t *col_ptr, const int32_t *row_idx, const T *val,
+// `reserve`: where the body starts (t2_reserve() for t(), the head's own size for the batched form)
+static int launch_transpose_bucketed(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
 				     int64_t nrow, int64_t ncol, int64_t nnz, const T2Shape &sh, int64_t *out_ptr,
-				     int32_t *out_idx, T *out_val, void *ws, size_t reserve, hipStream_t s)
+				     int32_t *out_idx, void *out_val, void *ws, size_t reserve, hipStream_t s)
 {
-	const int64_t ntab = ((sh.nslab * sh.ncoarse * sh.ngroups) << sh.cbits) + 1;
-	char *p = (char *) ws;
-	int64_t *table = (int64_t *) p;            p += t2_a((size_t) ntab, 8);
-	int64_t *fb_base = (int64_t *) p;          p += t2_a((size_t) (sh.nslab * sh.nfb + 1), 8);
-	void *scan_ws = p;
-	p = (char *) ws + reserve;
-	int32_t *col1 = (int32_t *) p;             p += t2_a((size_t) nnz, 4);
-	uint8_t *rlow1 = (uint8_t *) p;            p += t2_a((size_t) nnz, 1);
-	T *val1 = (T *) p;                         p += t2_a((size_t) nnz, 8);
-	uint32_t *cstart = (uint32_t *) p;         // [(ncoarse + 1) * ncol]
+	const T2Head H = t2_head(sh);
+	const T2Body B = t2_body(reserve, (size_t) nnz, 0);
+	const int64_t ntab = H.ntab;
+	char *w = (char *) ws;
+	int64_t *table = (int64_t *) (w + H.table), *fb_base = (int64_t *) (w + H.fb_base);
+	int32_t *col1 = (int32_t *) (w + B.col1);
+	uint8_t *rlow1 = (uint8_t *) (w + B.rlow1);
+	void *scan_ws = w + H.scan, *val1 = w + B.val1;
+	uint32_t *cstart = (uint32_t *) (w + B.cstart);         // [(ncoarse + 1) * ncol]
 	HIP_TRY(hipMemsetAsync(table, 0, (size_t) ntab * 8, s));
 	const size_t hist_b = (size_t) ((sh.nfb < T1_HIST ? sh.nfb : T1_HIST) + 1) / 2 * 4;
 	(void) hipFuncSetAttribute((const void *) transpose_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -855,14 +864,16 @@ static int launch_transpose_bucketed(const int64_t *col_ptr, const int32_t *row_
 		return -1;
 	hipLaunchKernelGGL(transpose_fb_base_kernel, dim3((unsigned) ((sh.nslab * sh.ncoarse + 3) / 4)), dim3(256), 0, s,
 			   table, sh, nnz, fb_base);
-	hipLaunchKernelGGL(transpose_scatter_kernel<T>, dim3((unsigned) (sh.nslab * sh.ngroups * ((sh.ncoarse + T2_CPW - 1) / T2_CPW))), dim3(T2_NT), 0, s,
-			   col_ptr, row_idx, val, nrow, ncol, sh, table, cstart, col1, rlow1, val1);
-	const size_t lds = ((sizeof(SplitLds<T3_NT, T3_ITEMS, 64>) + 15) & ~(size_t) 15) + (size_t) sh.ngroups * 8 +
-			   (size_t) ((sh.ngroups + 1 + 3) & ~(int64_t) 3) * 4 + (size_t) T3_STAGE * 4 + (size_t) T3_STAGE * sizeof(T);
-	(void) hipFuncSetAttribute((const void *) transpose_finish_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				   (int) lds);
-	hipLaunchKernelGGL(transpose_finish_kernel<T>, dim3((unsigned) (sh.nslab * sh.nfb)), dim3(T3_NT), lds, s, table, sh, nrow, nnz,
-			   col1, rlow1, val1, fb_base, out_ptr, out_idx, out_val);
+	svt_by_rtype(Rtype, val, out_val, [&](auto *v, auto *o) {
+		typedef std::remove_pointer_t<decltype(o)> T;
+		hipLaunchKernelGGL(transpose_scatter_kernel<T>, dim3((unsigned) (sh.nslab * sh.ngroups * ((sh.ncoarse + T2_CPW - 1) / T2_CPW))), dim3(T2_NT), 0, s,
+				   col_ptr, row_idx, v, nrow, ncol, sh, table, cstart, col1, rlow1, (T *) val1);
+		const size_t lds = ((sizeof(SplitLds<T3_NT, T3_ITEMS, 64>) + 15) & ~(size_t) 15) + (size_t) sh.ngroups * 8 +
+				   (size_t) ((sh.ngroups + 1 + 3) & ~(int64_t) 3) * 4 + (size_t) T3_STAGE * 4 + (size_t) T3_STAGE * sizeof(T);
+		(void) hipFuncSetAttribute((const void *) transpose_finish_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+		hipLaunchKernelGGL(transpose_finish_kernel<T>, dim3((unsigned) (sh.nslab * sh.nfb)), dim3(T3_NT), lds, s, table, sh, nrow, nnz,
+				   col1, rlow1, (const T *) val1, fb_base, out_ptr, out_idx, o);
+	});
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -879,20 +890,11 @@ int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void 
 	}
 	T2Shape sh;
 	const size_t reserve = t2_reserve(nrow, nnz);
-	bool bucketed = t2_shape(nrow, ncol, nnz, &sh);
-	if (bucketed) {
-		const int64_t ntab = ((sh.ncoarse * sh.ngroups) << sh.cbits) + 1;
-		bucketed = t2_a((size_t) ntab, 8) + t2_a((size_t) (sh.nfb + 1), 8) + exclusive_scan_ws_bytes(ntab) <= reserve;
-	}
-	// (one matrix: t2_shape() has left nslab = 1, srow = nrow, scol = ncol)
-	if (!bucketed)
+	// (one matrix: t2_shape() leaves nslab = 1, srow = nrow, scol = ncol)
+	if (!t2_shape(nrow, ncol, nnz, &sh) || t2_head(sh).total > reserve)
 		return launch_transpose_sorted(col_ptr, row_idx, val, Rtype, nrow, ncol, nnz, out_ptr, out_idx, out_val, ws, s);
-	g_route[0]++;
-	if (Rtype == SVT_REALSXP)
-		return launch_transpose_bucketed<double>(col_ptr, row_idx, (const double *) val, nrow, ncol, nnz, sh, out_ptr,
-							 out_idx, (double *) out_val, ws, reserve, s);
-	return launch_transpose_bucketed<int32_t>(col_ptr, row_idx, (const int32_t *) val, nrow, ncol, nnz, sh, out_ptr,
-						  out_idx, (int32_t *) out_val, ws, reserve, s);
+	g_route[R_T_BUCKETED]++;
+	return launch_transpose_bucketed(col_ptr, row_idx, val, Rtype, nrow, ncol, nnz, sh, out_ptr, out_idx, out_val, ws, reserve, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -914,8 +916,7 @@ int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void 
 // ranges, processed in order, so every box contributes ONE contiguous run to every output leaf, and the runs come in
 // box order = column order; inside a run the route orders them.  Only copies happen: the result is bit for bit the
 // unboxed route's (and out_ptr is the same scan of the same counts).
-// Workspace: the route's at max(box, nrow) nonzeros, the box temporary (nrow + 1 pointers, max(box, nrow) entries), the
-// rebased col_ptr (W + 1), fill and scan scratch (O(nrow)), the cut table (O(nnz / box + 2048)) -- not O(nnz).
+// Workspace: box_layout() -- the route's at max(box, nrow) nonzeros, a box-sized temporary, O(nrow) and O(nnz / box), not O(nnz).
 // ---------------------------------------------------------------------------
 static std::atomic<int64_t> g_box_nnz{0};
 static std::atomic<int64_t> g_boxed_calls{0};
@@ -934,9 +935,9 @@ static bool box_taken(int64_t nnz, int64_t box_limit)
 	return box_limit > 0 ? nnz > box_limit : nnz >= ((int64_t) 1 << 31);
 }
 
-static int64_t box_size(int64_t box_limit)
+static int64_t box_size(int64_t box_limit, int64_t dflt)
 {
-	return box_limit > 0 ? (box_limit < 0x7FFFFFFFLL ? box_limit : 0x7FFFFFFFLL) : BOX_DEFAULT;
+	return box_limit > 0 ? (box_limit < 0x7FFFFFFFLL ? box_limit : 0x7FFFFFFFLL) : dflt;
 }
 
 struct BoxLayout {
@@ -947,7 +948,7 @@ struct BoxLayout {
 static BoxLayout box_layout(int64_t nrow, int64_t nnz, int64_t box_limit)
 {
 	BoxLayout L;
-	L.bsz = box_size(box_limit);
+	L.bsz = box_size(box_limit, BOX_DEFAULT);
 	L.bmax = L.bsz > nrow ? L.bsz : nrow;                   // a box: <= bsz nonzeros, or one column
 	if (L.bmax > nnz) L.bmax = nnz > 0 ? nnz : 1;
 	L.W = BOX_W;
@@ -1058,6 +1059,48 @@ box_place_kernel(const int64_t *__restrict__ bptr, const int32_t *__restrict__ b
 	if (lane == 0) fill[L] += n;
 }
 
+static void launch_box_place(int Rtype, const int64_t *bptr, const int32_t *bidx, const void *bval, int64_t nleaf,
+			     int64_t first, const int64_t *out_ptr, int64_t *fill, int32_t *out_idx, void *out_val, hipStream_t s)
+{
+	svt_by_rtype(Rtype, bval, out_val, [&](auto *v, auto *o) {
+		hipLaunchKernelGGL(box_place_kernel, dim3((unsigned) ((nleaf + 3) / 4)), dim3(256), 0, s, bptr, bidx, v, nleaf,
+				   (int32_t) first, out_ptr, fill, out_idx, o);
+	});
+}
+
+// The cuts, shared by the two boxed drivers, over a pointer array ptr[0 .. n] with ptr[n] = nnz (col_ptr for t(); for
+// aperm() the nonzeros per index of the axis that becomes the rows): box_cut_kernel, its table copied to the host,
+// whatever else the driver queues with queue_more() (work that does not depend on the cuts), then the one stream
+// synchronisation of a boxed call; *bd = the boxes' boundaries (index, ptr there), ascending, each once.
+typedef std::vector<std::pair<int64_t, int64_t>> BoxBounds;
+template <class F>
+static int box_boundaries(const char *who, const int64_t *ptr, int64_t n, int64_t nnz, int64_t bsz, int64_t W,
+			  int64_t npts_max, int64_t *pts, hipStream_t s, BoxBounds *bd, F queue_more)
+{
+	const int64_t nk = (nnz - 1) / bsz, nw = (n - 1) / W, npts = nk + nw;
+	if (npts > npts_max)
+		return svt_set_error("%s: internal error (box cuts)", who);
+	std::vector<int64_t> hp((size_t) npts * 3 + 1);
+	if (npts > 0) {
+		hipLaunchKernelGGL(box_cut_kernel, dim3((unsigned) ((npts + 255) / 256)), dim3(256), 0, s, ptr, n, nk, bsz, W, npts, pts);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(hp.data(), pts, (size_t) npts * 24, hipMemcpyDeviceToHost, s));
+	}
+	if (queue_more())
+		return -1;
+	HIP_TRY(hipStreamSynchronize(s));
+	bd->reserve((size_t) npts * 2 + 2);
+	bd->push_back({0, 0});
+	bd->push_back({n, nnz});
+	for (int64_t i = 0; i < npts; i++) {
+		bd->push_back({hp[3 * i], hp[3 * i + 1]});
+		bd->push_back({hp[3 * i] + 1, hp[3 * i + 2]});
+	}
+	std::sort(bd->begin(), bd->end());
+	bd->erase(std::unique(bd->begin(), bd->end()), bd->end());
+	return 0;
+}
+
 size_t transpose_ws_bytes_box(int64_t nrow, int64_t nnz, int64_t box_limit)
 {
 	if (!box_taken(nnz, box_limit))
@@ -1096,28 +1139,9 @@ static int launch_transpose_boxed(const int64_t *col_ptr, const int32_t *row_idx
 	if (launch_exclusive_scan_i64(out_ptr, nrow + 1, w + Ly.scan, s))
 		return -1;
 	// the cuts, read back once
-	const int64_t nk = (nnz - 1) / Ly.bsz, nw = (ncol - 1) / Ly.W, npts = nk + nw;
-	if (npts > Ly.npts_max)
-		return svt_set_error("svt_dev_transpose: internal error (box cuts)");
-	std::vector<int64_t> hp((size_t) npts * 3 + 1);
-	if (npts > 0) {
-		hipLaunchKernelGGL(box_cut_kernel, dim3((unsigned) ((npts + 255) / 256)), dim3(256), 0, s, col_ptr, ncol, nk,
-				   Ly.bsz, Ly.W, npts, pts);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(hp.data(), pts, (size_t) npts * 24, hipMemcpyDeviceToHost, s));
-	}
-	HIP_TRY(hipStreamSynchronize(s));
-	std::vector<std::pair<int64_t, int64_t>> bd;        // (column, col_ptr there): box boundaries
-	bd.reserve((size_t) npts * 2 + 2);
-	bd.push_back({0, 0});
-	bd.push_back({ncol, nnz});
-	for (int64_t i = 0; i < npts; i++) {
-		bd.push_back({hp[3 * i], hp[3 * i + 1]});
-		bd.push_back({hp[3 * i] + 1, hp[3 * i + 2]});
-	}
-	std::sort(bd.begin(), bd.end());
-	bd.erase(std::unique(bd.begin(), bd.end()), bd.end());
-	const unsigned nbp = (unsigned) ((nrow + 3) / 4);
+	BoxBounds bd;                                       // (column, col_ptr there)
+	if (box_boundaries("svt_dev_transpose", col_ptr, ncol, nnz, Ly.bsz, Ly.W, Ly.npts_max, pts, s, &bd, [] { return 0; }))
+		return -1;
 	for (size_t b = 0; b + 1 < bd.size(); b++) {
 		const int64_t c0 = bd[b].first, c1 = bd[b + 1].first, p0 = bd[b].second, nb = bd[b + 1].second - p0;
 		if (nb == 0)
@@ -1130,12 +1154,7 @@ static int launch_transpose_boxed(const int64_t *col_ptr, const int32_t *row_idx
 		if (launch_transpose(bcp, row_idx + p0, (const char *) val + (size_t) p0 * esz, Rtype, nrow, c1 - c0, nb,
 				     bptr, bidx, bval, rws, s))
 			return -1;
-		if (Rtype == SVT_REALSXP)
-			hipLaunchKernelGGL(box_place_kernel<double>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const double *) bval,
-					   nrow, (int32_t) c0, out_ptr, fill, out_idx, (double *) out_val);
-		else
-			hipLaunchKernelGGL(box_place_kernel<int32_t>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const int32_t *) bval,
-					   nrow, (int32_t) c0, out_ptr, fill, out_idx, (int32_t *) out_val);
+		launch_box_place(Rtype, bptr, bidx, bval, nrow, c0, out_ptr, fill, out_idx, out_val, s);
 		HIP_TRY(hipGetLastError());
 	}
 	g_boxed_calls++;
@@ -1155,14 +1174,11 @@ int launch_transpose_box(const int64_t *col_ptr, const int32_t *row_idx, const v
 }
 
 // ---------------------------------------------------------------------------
-// N-d aperm (C_aperm_SVT, src/SparseArray_aperm.c:148-930).  The device layout
-// knows leaves only, so the caller passes the array's dims.  Every nonzero gets
-// the 64-bit key  new_leaf * new_dim0 + new_row  (its linear index in the
-// permuted array), one radix sort over ceil(log2(prod(dim))) bits orders them
-// the way the permuted SVT stores them, one pass gathers.  The reference
-// distinguishes leaf-preserving permutations (perm[1] == 1: pointer shuffle,
-// :949-957) from those that shatter leaves (counting sort, :892-929); the key
-// sort covers both.
+// N-d aperm (C_aperm_SVT, src/SparseArray_aperm.c:148-930).  The device layout knows leaves only, so the caller passes
+// the array's dims.  The reference distinguishes leaf-preserving permutations (perm[1] == 1: pointer shuffle, :949-957)
+// from those that shatter leaves (counting sort, :892-929).  Here: one function per route, each next to the function
+// that lays out its workspace, tried in the order of launch_aperm_n(); the last resort gives every nonzero the 64-bit
+// key  new_leaf * new_dim0 + new_row  (its linear index in the permuted array), sorts and gathers.
 // ---------------------------------------------------------------------------
 struct ApermDims {
 	int ndim;
@@ -1278,6 +1294,50 @@ aperm_leaf_copy_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__res
 	}
 }
 
+// count, scan, copy: whole leaves to their new places (scan_ws: exclusive_scan_ws_bytes(nleaves + 1))
+static int launch_leaf_move(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype, int64_t nleaves,
+			    const LeafMap &lm, int64_t *out_ptr, int32_t *out_idx, void *out_val, void *scan_ws, hipStream_t s)
+{
+	hipLaunchKernelGGL(aperm_leaf_count_kernel, dim3((unsigned) ((nleaves + 1 + 255) / 256)), dim3(256), 0, s, col_ptr, nleaves, lm, out_ptr);
+	if (launch_exclusive_scan_i64(out_ptr, nleaves + 1, scan_ws, s))
+		return -1;
+	const unsigned nbc = (unsigned) ((nleaves + 4 * APERM_LU - 1) / (4 * APERM_LU));
+	svt_by_rtype(Rtype, val, out_val, [&](auto *v, auto *o) {
+		hipLaunchKernelGGL(aperm_leaf_copy_kernel, dim3(nbc), dim3(256), 0, s, col_ptr, row_idx, v, nleaves, lm, out_ptr, out_idx, o);
+	});
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// One aperm() call as its routes see it.  A route returns 0 (done), -1 (error), or one of the two below, on which the
+// dispatcher (launch_aperm_n) goes on to the next route.
+struct ApermCall {
+	const int64_t *col_ptr; const int32_t *row_idx; const void *val; int Rtype;
+	int64_t ncol, nnz; const int64_t *dim; int ndim; const int *perm;
+	int64_t *out_ptr; int32_t *out_idx; void *out_val; void *ws; hipStream_t s;
+};
+enum { APERM_NA = 1, APERM_REFUSED = 2 };              // not this route's shape / its shape, refused on seeing the data
+static int launch_aperm_n(const ApermCall &c, int nested);
+
+// workspace of the leaf-preserving form: the scratch of a scan over the new leaves' counts (0: too many leaves for it)
+static size_t aperm_leaf_scan_bytes(const int64_t *dim, int ndim)
+{
+	const double nl = extent_prod(dim, 1, ndim);
+	return nl < LEAVES_MAX ? exclusive_scan_ws_bytes((int64_t) nl + 1) : 0;
+}
+
+static int aperm_leaf_preserving(const ApermCall &c, int64_t new_nleaves)
+{
+	LeafMap lm;
+	lm.ndim = c.ndim;
+	int64_t os[8], st = 1;
+	for (int a = 1; a < c.ndim; a++) { os[a] = st; st *= c.dim[a]; }      // leaf strides of the old axes
+	for (int a = 1; a < c.ndim; a++) { lm.new_dim[a] = c.dim[c.perm[a]]; lm.old_stride[a] = os[c.perm[a]]; }
+	g_route[R_LEAF_PRESERVING]++;
+	// counts into out_ptr, exclusive scan in place
+	return launch_leaf_move(c.col_ptr, c.row_idx, c.val, c.Rtype, new_nleaves, lm, c.out_ptr, c.out_idx, c.out_val, c.ws, c.s);
+}
+
 // ---- leaf-shattering permutations, 32-bit keys.  A stable sort by the NEW LEAF index alone is enough:
 // two nonzeros of one new leaf differ only in the coordinate that becomes the new row, and the input order
 // (old leaves in order, offsets ascending) already ascends in that coordinate for fixed other ones.  So the
@@ -1358,16 +1418,91 @@ __global__ void aperm_gather32_kernel(const uint32_t *__restrict__ spos, const i
 	out_val[i] = val[k];
 }
 
-static int aperm_bits(const int64_t *dim, int ndim)
+static ApermDims aperm_dims(const ApermCall &c)
 {
-	double tot = 1.0;
-	for (int a = 0; a < ndim; a++) tot *= (double) (dim[a] > 0 ? dim[a] : 1);
-	int b = 1;
-	while (b < 64 && ldexp(1.0, b) < tot) b++;
-	return b;
+	ApermDims d;
+	d.ndim = c.ndim;
+	int64_t m = 1;                                      // multiplier of old axis perm[a] = product of the new dims below new axis a
+	for (int a = 0; a < c.ndim; a++) {
+		d.dim[a] = c.dim[a];
+		d.perm[a] = c.perm[a];
+		d.mul[c.perm[a]] = m;
+		m *= c.dim[c.perm[a]];
+	}
+	return d;
 }
 
-// [keys nnz*8][sorted keys nnz*8][pos nnz*4][sorted pos nnz*4][sort temp]
+// [keys][sorted keys][pos][sorted pos][new row][second buffers of the sort's passes, twice], nnz*4 each, [leaf hints]
+// [the sort's scratch] + 256.  Depends on the nonzero count alone.
+struct Sort32Layout { size_t keys, skeys, pos, spos, newrow, ktmp, ptmp, hint, sort, total; };
+static Sort32Layout aperm_sort32_layout(int64_t nnz)
+{
+	const size_t a4 = t2_a((size_t) (nnz > 0 ? nnz : 1), 4), sort = 7 * a4 + hint_bytes(nnz);
+	return Sort32Layout{0, a4, 2 * a4, 3 * a4, 4 * a4, 5 * a4, 6 * a4, 7 * a4, sort, sort + svt_sort_ws_bytes(nnz) + 256};
+}
+static size_t aperm_key_sort_bytes(int64_t nnz) { return aperm_sort32_layout(nnz).total; }
+
+static int aperm_sort32(const ApermCall &c, int64_t new_nleaves)
+{
+	const Sort32Layout L = aperm_sort32_layout(c.nnz);
+	char *w = (char *) c.ws;
+	uint32_t *keys = (uint32_t *) (w + L.keys), *skeys = (uint32_t *) (w + L.skeys), *pos = (uint32_t *) (w + L.pos);
+	uint32_t *spos = (uint32_t *) (w + L.spos), *ktmp = (uint32_t *) (w + L.ktmp), *ptmp = (uint32_t *) (w + L.ptmp);
+	uint32_t *hint = (uint32_t *) (w + L.hint);
+	int32_t *newrow = (int32_t *) (w + L.newrow);
+	int bits = 1;
+	while (bits < 32 && ((int64_t) 1 << bits) < new_nleaves) bits++;
+	const int64_t nblk = (c.nnz >> HINT_SHIFT) + 1;
+	g_route[R_SORT32]++;
+	hipLaunchKernelGGL(col_hint_kernel, dim3(blocks256(nblk + 1)), dim3(256), 0, c.s, c.col_ptr, c.ncol, nblk, hint);
+	hipLaunchKernelGGL(aperm_key32_kernel, dim3(blocks256(c.nnz)), dim3(256), 0, c.s, c.col_ptr, c.row_idx, hint, c.ncol, c.nnz,
+			   aperm_dims(c), keys, pos, newrow);
+	if (svt_sort_pairs<uint32_t>(keys, skeys, ktmp, pos, spos, ptmp, c.nnz, bits, w + L.sort, c.s))
+		return -1;
+	hipLaunchKernelGGL(aperm_ptr_fill_kernel, dim3((unsigned) ((c.nnz + 1 + PTRFILL_NT - 1) / PTRFILL_NT)), dim3(PTRFILL_NT), 0, c.s,
+			   skeys, c.nnz, new_nleaves, 1ULL, c.out_ptr);
+	svt_by_rtype(c.Rtype, c.val, c.out_val, [&](auto *v, auto *o) {
+		hipLaunchKernelGGL(aperm_gather32_kernel, dim3(blocks256_xcd(c.nnz)), dim3(256), 0, c.s, spos, newrow, v, c.nnz, c.out_idx, o);
+	});
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// ---- 64-bit keys, the new linear index (aperm_key_kernel): results of 2^31 - 1 leaves or more.
+// [keys nnz*8][sorted keys nnz*8][pos nnz*4][sorted pos nnz*4][second buffers of the sort's passes nnz*8, nnz*4]
+// [the sort's scratch] + 256.  Depends on the nonzero count alone.
+struct Sort64Layout { size_t keys, skeys, pos, spos, ktmp, ptmp, sort, total; };
+static Sort64Layout aperm_sort64_layout(int64_t nnz)
+{
+	const size_t n = (size_t) (nnz > 0 ? nnz : 1), a8 = t2_a(n, 8), a4 = t2_a(n, 4), sort = 3 * a8 + 3 * a4;
+	return Sort64Layout{0, a8, 2 * a8, 2 * a8 + a4, 2 * a8 + 2 * a4, 3 * a8 + 2 * a4, sort, sort + svt_sort_ws_bytes(nnz) + 256};
+}
+
+static int aperm_sort64(const ApermCall &c, int64_t new_nleaves)
+{
+	typedef unsigned long long u64;
+	const Sort64Layout L = aperm_sort64_layout(c.nnz);
+	char *w = (char *) c.ws;
+	u64 *keys = (u64 *) (w + L.keys), *skeys = (u64 *) (w + L.skeys), *ktmp = (u64 *) (w + L.ktmp);
+	uint32_t *pos = (uint32_t *) (w + L.pos), *spos = (uint32_t *) (w + L.spos), *ptmp = (uint32_t *) (w + L.ptmp);
+	const int64_t new_dim0 = c.dim[c.perm[0]];
+	const double tot = extent_prod(c.dim, 0, c.ndim);
+	int bits = 1;                                       // of the new linear index
+	while (bits < 64 && ldexp(1.0, bits) < tot) bits++;
+	g_route[R_SORT64]++;
+	hipLaunchKernelGGL(aperm_key_kernel, dim3(blocks256(c.nnz)), dim3(256), 0, c.s, c.col_ptr, c.row_idx, c.ncol, c.nnz, aperm_dims(c),
+			   keys, pos);
+	if (svt_sort_pairs<u64>(keys, skeys, ktmp, pos, spos, ptmp, c.nnz, bits, w + L.sort, c.s))
+		return -1;
+	hipLaunchKernelGGL(aperm_ptr_fill_kernel, dim3((unsigned) ((c.nnz + 1 + PTRFILL_NT - 1) / PTRFILL_NT)), dim3(PTRFILL_NT), 0, c.s,
+			   skeys, c.nnz, new_nleaves, (u64) (new_dim0 > 0 ? new_dim0 : 1), c.out_ptr);
+	svt_by_rtype(c.Rtype, c.val, c.out_val, [&](auto *v, auto *o) {
+		hipLaunchKernelGGL(aperm_gather_kernel, dim3(blocks256_xcd(c.nnz)), dim3(256), 0, c.s, skeys, spos, v, c.nnz, new_dim0, c.out_idx, o);
+	});
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
 // ---- slab form: the new leading axis is an old outer axis q of small extent, the old rows become new
 // axis 1 (aperm(x, c(3, 1, 2)) of a 2e4 x 2e4 x 64 array).  For every index of the remaining axes (a slab)
 // the sub-array is a d0 x dq matrix held in dq whole old leaves, to be transposed into d0 new leaves of at
@@ -1489,27 +1624,122 @@ aperm_slab_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict
 	if (g == nslab - 1 && tid == 0) out_ptr[nslab * d0] = nnz;
 }
 
+// Head of the slab form's workspace: [nonzeros per slab (nslab + 2) * 8, scanned in place][the largest: 8 bytes of 256][scan scratch]
+struct SlabHead { size_t cnt, maxcnt, scan, total; };
+static SlabHead aperm_slab_head(int64_t nslab)
+{
+	const size_t maxcnt = t2_a((size_t) (nslab + 2), 8);
+	return SlabHead{0, maxcnt, maxcnt + 256, maxcnt + 256 + exclusive_scan_ws_bytes(nslab + 1)};
+}
+
+// new axis 0 = an old outer axis of <= 1024 entries, new axis 1 = the old rows, slabs of a few thousand nonzeros.  The
+// largest slab is read back (one synchronisation of the stream): with a slab over the cap the form refuses.
+static int aperm_slab(const ApermCall &c)
+{
+	const int ndim = c.ndim, *perm = c.perm;
+	const int64_t *dim = c.dim, nnz = c.nnz;
+	if (!(ndim >= 3 && perm[1] == 0 && perm[0] >= 1 && dim[perm[0]] <= 1024 && dim[0] < ((int64_t) 1 << 30)))
+		return APERM_NA;
+	const int q = perm[0];
+	int64_t os[8], st = 1;
+	for (int a = 1; a < ndim; a++) { os[a] = st; st *= dim[a]; }
+	SlabMap sm;
+	sm.nother = ndim - 2;
+	int64_t nslab = 1;
+	for (int t = 0; t < ndim - 2; t++) {
+		sm.new_ext[t] = dim[perm[2 + t]];
+		sm.old_stride[t] = os[perm[2 + t]];
+		nslab *= dim[perm[2 + t]];
+	}
+	if (!(nslab >= 1 && nslab < 2147483646LL && nnz / nslab <= SLAB_CAP * 9 / 10))
+		return APERM_NA;
+	// The form has no budget of its own: its head must fit in front of the second buffers of the 32-bit key sort
+	// (Sort32Layout::ktmp = five arrays of nnz * 4 bytes).  Safe for every caller: aperm_ws_core() gives a top-level call
+	// at least aperm_sort32_layout(nnz).total, a step of a composed route gets aperm_ws_core() behind its caller's
+	// intermediates (aperm_ws_bytes()), a box of the boxed driver aperm_key_sort_bytes() -- and the sort layouts depend
+	// on nnz alone, which no step changes.  The bound is part of the route decision: it stays at ktmp, not .total.
+	const SlabHead H = aperm_slab_head(nslab);
+	if (H.total > aperm_sort32_layout(nnz).ktmp)
+		return APERM_NA;
+	char *w = (char *) c.ws;
+	int64_t *base = (int64_t *) (w + H.cnt);
+	unsigned long long *maxcnt = (unsigned long long *) (w + H.maxcnt), mx = 0;
+	hipStream_t s = c.s;
+	HIP_TRY(hipMemsetAsync(maxcnt, 0, 8, s));
+	hipLaunchKernelGGL(aperm_slab_count_kernel, dim3((unsigned) ((nslab + 1 + 255) / 256)), dim3(256), 0, s,
+			   c.col_ptr, sm, nslab, dim[q], os[q], base, maxcnt);
+	HIP_TRY(hipMemcpyAsync(&mx, maxcnt, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if (mx > SLAB_CAP) {
+		g_route[R_SLAB_REFUSED]++;
+		return APERM_REFUSED;
+	}
+	g_route[R_SLAB]++;
+	if (launch_exclusive_scan_i64(base, nslab + 1, w + H.scan, s))
+		return -1;
+	const int bits = key_bits(dim[0]);
+	svt_by_rtype(c.Rtype, c.val, c.out_val, [&](auto *v, auto *o) {
+		hipLaunchKernelGGL(aperm_slab_kernel, dim3((unsigned) nslab), dim3(SLAB_NT), (size_t) SLAB_CAP * 4, s, c.col_ptr,
+				   c.row_idx, v, sm, nslab, dim[0], (int) dim[q], os[q], bits, nnz, base, c.out_ptr, c.out_idx, o);
+	});
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
 // aperm(x, c(2, 1, 3, ...)): the first two axes change places inside every slab of the remaining ones -- prod(dim[2..])
 // independent transpositions of dim[0] x dim[1] matrices that follow one another in the operand's leaves: the bucketed
-// transposition, batched (T2Shape).  Returns the workspace it needs (0: the shape does not suit it) and fills *sh, *reserve.
+// transposition, batched (T2Shape).  Returns the workspace it needs (0: the shape does not suit it) and fills *sh,
+// *reserve: [t2_head() + 256, rounded up][t2_body() with all (ncoarse + 1) * columns coarse-bucket starts].
 static size_t aperm_swap01_bytes(int64_t nnz, const int64_t *dim, int ndim, T2Shape *sh, size_t *reserve)
 {
 	if (ndim < 3 || nnz <= 0 || nnz >= ((int64_t) 1 << 31))
 		return 0;
-	double ns = 1.0;
-	for (int a = 2; a < ndim; a++) ns *= (double) dim[a];
+	const double ns = extent_prod(dim, 2, ndim, -1, false);
 	if (ns < 1.0 || ns > 1.0e9)
 		return 0;
 	if (!t2_shape(dim[0], dim[1], nnz, sh, (int64_t) ns))
 		return 0;
-	const int64_t ntab = ((sh->nslab * sh->ncoarse * sh->ngroups) << sh->cbits) + 1;
-	const size_t res = t2_a((size_t) ntab, 8) + t2_a((size_t) (sh->nslab * sh->nfb + 1), 8) + exclusive_scan_ws_bytes(ntab) + 256;
-	const size_t cst = t2_a((size_t) (sh->ncoarse + 1) * (size_t) (sh->nslab * sh->scol), 4);
-	if (reserve) *reserve = (res + 255) / 256 * 256;
-	return (res + 255) / 256 * 256 + t2_a((size_t) nnz, 4) + t2_a((size_t) nnz, 1) + t2_a((size_t) nnz, 8) + cst + 512;
+	const size_t res = t2_a(t2_head(*sh).total + 256, 1);
+	if (reserve) *reserve = res;
+	return t2_body(res, (size_t) nnz, (size_t) (sh->ncoarse + 1) * (size_t) (sh->nslab * sh->scol)).total;
 }
 
-static size_t aperm_ws_core(int64_t nnz, const int64_t *dim, int ndim);
+// the first two axes change places, the others stay: one batched bucketed transposition, no sort
+static int aperm_swap01(const ApermCall &c)
+{
+	bool swap01 = c.ndim >= 3 && c.perm[0] == 1 && c.perm[1] == 0;
+	for (int a = 2; a < c.ndim && swap01; a++) swap01 = c.perm[a] == a;
+	T2Shape sh;
+	size_t reserve = 0;
+	if (!swap01 || aperm_swap01_bytes(c.nnz, c.dim, c.ndim, &sh, &reserve) == 0)
+		return APERM_NA;
+	g_route[R_SWAP01]++;
+	return launch_transpose_bucketed(c.col_ptr, c.row_idx, c.val, c.Rtype, c.dim[0], c.ncol, c.nnz, sh, c.out_ptr, c.out_idx,
+					 c.out_val, c.ws, reserve, c.s);
+}
+
+// ---- composed routes: steps through intermediate arrays in the workspace.  One such array:
+// [leaf pointers (leaves + 1) * 8][row indices nnz*4][values nnz*8]
+static size_t aperm_inter_bytes(int64_t leaves, int64_t nnz)
+{
+	return t2_a((size_t) leaves + 1, 8) + t2_a((size_t) (nnz > 0 ? nnz : 1), 4) + t2_a((size_t) (nnz > 0 ? nnz : 1), 8);
+}
+
+// the array at *p, in the order of aperm_inter_bytes(); moves *p past it
+struct InterArray { int64_t *col_ptr; int32_t *row_idx; void *val; };
+static InterArray aperm_inter_carve(char **p, int64_t leaves, int64_t nnz)
+{
+	char *idx = *p + t2_a((size_t) leaves + 1, 8);
+	const InterArray x = {(int64_t *) *p, (int32_t *) idx, idx + t2_a((size_t) nnz, 4)};
+	*p += aperm_inter_bytes(leaves, nnz);
+	return x;
+}
+
+// a step reads `x` (leaves, dim)
+static void aperm_from(ApermCall *n, const InterArray &x, int64_t leaves, const int64_t *dim)
+{
+	n->col_ptr = x.col_ptr; n->row_idx = x.row_idx; n->val = x.val; n->ncol = leaves; n->dim = dim;
+}
 
 // 3-d arrays: the two permutations that neither keep axis 1 nor are one of the forms above are two of those in a row --
 // c(2,3,1) = c(2,1,3) then c(1,3,2); c(3,2,1) = c(2,1,3) then c(3,1,2) -- through an intermediate array in the workspace
@@ -1519,9 +1749,36 @@ static size_t aperm_via_bytes(int64_t nnz, const int64_t *dim, int ndim)
 	if (ndim != 3 || nnz <= 0)
 		return 0;
 	const double nly = (double) dim[0] * (double) dim[2];
-	if (nly >= 2147483646.0)
+	if (nly >= LEAVES_MAX)
 		return 0;
-	return t2_a((size_t) nly + 1, 8) + t2_a((size_t) nnz, 4) + t2_a((size_t) nnz, 8);
+	return aperm_inter_bytes((int64_t) nly, nnz);
+}
+
+static int aperm_via_3d(const ApermCall &c)
+{
+	const int *perm = c.perm;
+	const int64_t *dim = c.dim;
+	if (!(c.ndim == 3 && ((perm[0] == 1 && perm[1] == 2 && perm[2] == 0) || (perm[0] == 2 && perm[1] == 1 && perm[2] == 0 && dim[2] <= 1024))))
+		return APERM_NA;
+	T2Shape sh;
+	size_t reserve = 0;
+	if (aperm_via_bytes(c.nnz, dim, 3) == 0 || aperm_swap01_bytes(c.nnz, dim, 3, &sh, &reserve) == 0)
+		return APERM_NA;
+	g_route[R_VIA_3D]++;
+	const int64_t nly = dim[0] * dim[2];
+	char *p = (char *) c.ws;
+	const InterArray y = aperm_inter_carve(&p, nly, c.nnz);         // (p: what is left, for both steps)
+	const int rc = launch_transpose_bucketed(c.col_ptr, c.row_idx, c.val, c.Rtype, dim[0], c.ncol, c.nnz, sh, y.col_ptr,
+						 y.row_idx, y.val, p, reserve, c.s);
+	if (rc)
+		return rc;
+	const int64_t dimy[3] = {dim[1], dim[0], dim[2]};
+	const int p231[3] = {0, 2, 1}, p321[3] = {2, 0, 1};
+	ApermCall n = c;
+	aperm_from(&n, y, nly, dimy);
+	n.perm = perm[0] == 1 ? p231 : p321;
+	n.ws = p;
+	return launch_aperm_n(n, 1);
 }
 
 // General permutation of an array with three or more axes (round 5; rounds 1-4: a device-wide key sort):
@@ -1540,11 +1797,6 @@ struct ApermPlan3 {
 	int64_t leaves_a, leaves_b;
 };
 
-static size_t aperm_inter_bytes(int64_t leaves, int64_t nnz)
-{
-	return t2_a((size_t) leaves + 1, 8) + t2_a((size_t) (nnz > 0 ? nnz : 1), 4) + t2_a((size_t) (nnz > 0 ? nnz : 1), 8);
-}
-
 static bool aperm_general_plan(int64_t nnz, const int64_t *dim, int ndim, const int *perm, ApermPlan3 *pl)
 {
 	if (ndim < 3 || perm[0] == 0 || nnz <= 0)
@@ -1554,11 +1806,10 @@ static bool aperm_general_plan(int64_t nnz, const int64_t *dim, int ndim, const 
 	for (int a = 1, i = 2; a < ndim; a++)
 		if (a != q) pl->pa[i++] = a;
 	pl->a_id = q == 1;
-	double la = 1.0, lb = 1.0;
 	for (int i = 0; i < ndim; i++) pl->dim_a[i] = dim[pl->pa[i]];
 	for (int i = 0; i < ndim; i++) pl->dim_b[i] = i == 0 ? pl->dim_a[1] : i == 1 ? pl->dim_a[0] : pl->dim_a[i];
-	for (int i = 1; i < ndim; i++) { la *= (double) pl->dim_a[i]; lb *= (double) pl->dim_b[i]; }
-	if (la >= 2147483646.0 || lb >= 2147483646.0 || la < 1.0 || lb < 1.0)
+	const double la = extent_prod(pl->dim_a, 1, ndim, -1, false), lb = extent_prod(pl->dim_b, 1, ndim, -1, false);
+	if (la >= LEAVES_MAX || lb >= LEAVES_MAX || la < 1.0 || lb < 1.0)
 		return false;
 	pl->leaves_a = (int64_t) la; pl->leaves_b = (int64_t) lb;
 	// a leaf-preserving step reads and writes every leaf pointer a few times: with many more leaves than nonzeros (a short
@@ -1616,14 +1867,59 @@ static size_t aperm_general_bytes(int64_t nnz, const int64_t *dim, int ndim, siz
 	return need;
 }
 
+// the general form: leaf-preserving step, first two axes swapped (or both in one by the slab form), leaf-preserving step
+static int aperm_general(const ApermCall &c)
+{
+	ApermPlan3 pl;
+	if (!aperm_general_plan(c.nnz, c.dim, c.ndim, c.perm, &pl))
+		return APERM_NA;
+	g_route[R_GENERAL]++;
+	const InterArray out = {c.out_ptr, c.out_idx, c.out_val};
+	char *p = (char *) c.ws;
+	InterArray x = {NULL, NULL, NULL}, y = out;
+	if (!pl.a_id && !pl.slab_first) x = aperm_inter_carve(&p, pl.leaves_a, c.nnz);     // (the slab form goes from the operand to y in one step)
+	if (!pl.c_id) y = aperm_inter_carve(&p, pl.leaves_b, c.nnz);
+	ApermCall n = c;                                    // the steps: nested, in what is left of the workspace
+	n.ws = p;
+	auto step = [&n](const int *perm, const InterArray &into) {
+		n.perm = perm; n.out_ptr = into.col_ptr; n.out_idx = into.row_idx; n.out_val = into.val;
+		return launch_aperm_n(n, 1);
+	};
+	int rc, p1[8], pb[8];
+	if (pl.slab_first) {
+		// c(q, 1, others) in one go (slab form; if a slab turns out too long the step takes the key sort), then step C
+		p1[0] = c.perm[0]; p1[1] = 0;
+		for (int a = 2; a < c.ndim; a++) p1[a] = pl.pa[a];
+		if ((rc = step(p1, y)) != 0)
+			return rc;
+	} else {
+		if (!pl.a_id) {
+			if ((rc = step(pl.pa, x)) != 0)
+				return rc;
+			aperm_from(&n, x, pl.leaves_a, pl.dim_a);
+		}
+		for (int a = 0; a < c.ndim; a++) pb[a] = a == 0 ? 1 : a == 1 ? 0 : a;
+		n.dim = pl.dim_a;
+		if ((rc = step(pb, y)) != 0 || pl.c_id)
+			return rc;
+	}
+	aperm_from(&n, y, pl.leaves_b, pl.dim_b);
+	return step(pl.pc, out);
+}
+
+// the forms that need no intermediate: the largest of the key sorts and the batched transposition (+ 256 each) + the leaf-preserving form's
+static size_t aperm_ws_core(int64_t nnz, const int64_t *dim, int ndim)
+{
+	T2Shape sh;
+	size_t need = aperm_swap01_bytes(nnz, dim, ndim, &sh, NULL) + 256;
+	need = std::max(need, std::max(aperm_sort32_layout(nnz).total, aperm_sort64_layout(nnz).total));
+	return need + aperm_leaf_scan_bytes(dim, ndim);
+}
+
 size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim)
 {
-	if (nnz >= ((int64_t) 1 << 31)) {
-		// only the leaf-preserving form takes such an operand: the scratch of a scan over the leaf counts
-		double nl = 1.0;
-		for (int a = 1; a < ndim; a++) nl *= (double) (dim[a] > 0 ? dim[a] : 1);
-		return (nl < 2147483646.0 ? exclusive_scan_ws_bytes((int64_t) nl + 1) : 0) + 256;
-	}
+	if (nnz >= ((int64_t) 1 << 31))                         // only the leaf-preserving form takes such an operand
+		return aperm_leaf_scan_bytes(dim, ndim) + 256;
 	size_t need = aperm_ws_core(nnz, dim, ndim);
 	{
 		// (a step of the general form may itself fall back to the forms that aperm_ws_core() sizes: the intermediates
@@ -1641,298 +1937,57 @@ size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim)
 	return need;
 }
 
-static size_t aperm_ws_core(int64_t nnz, const int64_t *dim, int ndim)
-{
-	const size_t n = (size_t) (nnz > 0 ? nnz : 1);
-	const size_t a8 = (n * 8 + 255) / 256 * 256, a4 = (n * 4 + 255) / 256 * 256;
-	// (leaf-preserving permutations: only the scratch of a scan over the leaf counts)
-	double nl = 1.0;
-	for (int a = 1; a < ndim; a++) nl *= (double) (dim[a] > 0 ? dim[a] : 1);
-	size_t scan_b = 0;
-	if (nl < 2147483646.0)
-		scan_b = exclusive_scan_ws_bytes((int64_t) nl + 1);
-	const size_t t32 = svt_sort_ws_bytes(nnz);
-	const size_t need64 = 3 * a8 + 3 * a4 + t32;
-	const size_t need32 = 7 * a4 + hint_bytes(nnz) + t32;
-	T2Shape sh;
-	const size_t swap01 = aperm_swap01_bytes(nnz, dim, ndim, &sh, NULL);
-	size_t need = need64 > need32 ? need64 : need32;
-	if (swap01 > need) need = swap01;
-	return need + scan_b + 256;
-}
-
-// nested != 0: a step of a composed route (the 3-d "via" form, the general form).  Such a call gets what is left of
-// the workspace behind its caller's intermediates, which aperm_ws_bytes() sizes for the forms of aperm_ws_core() only:
-// it must not carve intermediates of its own (a slab form that refuses at run time -- one slab over
-// SLAB_CAP -- used to re-enter the general form inside `sub` and write past the workspace), so it goes from the
-// direct forms (leaf-preserving, first two axes swapped, slab) straight to the key sort.  nested == 2: a box of the
-// boxed driver whose preferred route needs more than the driver's route area: the key sort alone, whose need
-// depends on the nonzero count only.
-static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
-			  int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
-			  int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, hipStream_t s, int nested);
-
-int launch_aperm(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
-		 int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
-		 int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, hipStream_t s)
-{
-	return launch_aperm_n(col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, perm, out_ptr, out_idx, out_val, ws, s, 0);
-}
-
-static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
-			  int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
-			  int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, hipStream_t s, int nested)
+static bool aperm_perm_ok(int ndim, const int *perm)
 {
 	if (ndim < 1 || ndim > 8)
-		return svt_set_error("aperm: between 1 and 8 dimensions are supported");
-	ApermDims d;
-	d.ndim = ndim;
+		return false;
 	bool seen[8] = {false, false, false, false, false, false, false, false};
-	double total = 1.0;
 	for (int a = 0; a < ndim; a++) {
 		if (perm[a] < 0 || perm[a] >= ndim || seen[perm[a]])
-			return svt_set_error("'perm' must be a permutation of 1:%d", ndim);
+			return false;
 		seen[perm[a]] = true;
-		d.dim[a] = dim[a];
-		d.perm[a] = perm[a];
-		total *= (double) (dim[a] > 0 ? dim[a] : 1);
 	}
-	if (total >= 9.2e18)
+	return true;
+}
+
+// The dispatcher: the routes in the order they are tried.
+// nested != 0: a step of a composed route (aperm_via_3d, aperm_general).  Such a call gets what is left of the
+// workspace behind its caller's intermediates, which aperm_ws_bytes() sizes by aperm_ws_core() alone: it must not carve
+// intermediates of its own (a slab form that refused at run time used to re-enter the general form inside the rest and
+// write past the workspace).  So a nested call reaches aperm_leaf_preserving (aperm_leaf_scan_bytes), aperm_swap01
+// (aperm_swap01_bytes), aperm_slab (aperm_slab_head, within aperm_sort32_layout) and the two key sorts
+// (aperm_sort32_layout, aperm_sort64_layout) -- the terms of aperm_ws_core(), none of which calls back into here.
+// nested == 2: a box of the boxed driver whose preferred route needs more than the driver's route area: the
+// leaf-preserving form or the key sort alone, whose need depends on the nonzero count only.
+static int launch_aperm_n(const ApermCall &c, int nested)
+{
+	if (c.ndim < 1 || c.ndim > 8)
+		return svt_set_error("aperm: between 1 and 8 dimensions are supported");
+	if (!aperm_perm_ok(c.ndim, c.perm))
+		return svt_set_error("'perm' must be a permutation of 1:%d", c.ndim);
+	if (extent_prod(c.dim, 0, c.ndim) >= 9.2e18)
 		return svt_set_error("aperm: array too large for 64-bit linear indices");
-	// multiplier of old axis perm[a] = product of the new dims below new axis a
-	int64_t m = 1;
-	for (int a = 0; a < ndim; a++) {
-		d.mul[perm[a]] = m;
-		m *= dim[perm[a]];
-	}
-	const int64_t new_dim0 = dim[perm[0]];
 	int64_t new_nleaves = 1;
-	for (int a = 1; a < ndim; a++) new_nleaves *= dim[perm[a]];
-	const unsigned nbl = (unsigned) ((new_nleaves + 1 + 255) / 256);
-	if (nnz == 0) {
-		HIP_TRY(hipMemsetAsync(out_ptr, 0, (size_t) (new_nleaves + 1) * 8, s));
+	for (int a = 1; a < c.ndim; a++) new_nleaves *= c.dim[c.perm[a]];
+	if (c.nnz == 0) {
+		HIP_TRY(hipMemsetAsync(c.out_ptr, 0, (size_t) (new_nleaves + 1) * 8, c.s));
 		return 0;
 	}
-	if (perm[0] == 0 && new_nleaves < ((int64_t) 1 << 31) - 1) {
-		LeafMap lm;
-		lm.ndim = ndim;
-		int64_t os[8], st = 1;
-		for (int a = 1; a < ndim; a++) { os[a] = st; st *= dim[a]; }      // leaf strides of the old axes
-		for (int a = 1; a < ndim; a++) { lm.new_dim[a] = dim[perm[a]]; lm.old_stride[a] = os[perm[a]]; }
-		// counts into out_ptr, exclusive scan in place (the scan's scratch comes from the workspace)
-		g_route[2]++;
-		hipLaunchKernelGGL(aperm_leaf_count_kernel, dim3(nbl), dim3(256), 0, s, col_ptr, new_nleaves, lm, out_ptr);
-		if (launch_exclusive_scan_i64(out_ptr, new_nleaves + 1, ws, s))
-			return -1;
-		const unsigned nbc = (unsigned) ((new_nleaves + 4 * APERM_LU - 1) / (4 * APERM_LU));
-		if (Rtype == SVT_REALSXP)
-			hipLaunchKernelGGL(aperm_leaf_copy_kernel<double>, dim3(nbc), dim3(256), 0, s, col_ptr, row_idx,
-					   (const double *) val, new_nleaves, lm, out_ptr, out_idx, (double *) out_val);
-		else
-			hipLaunchKernelGGL(aperm_leaf_copy_kernel<int32_t>, dim3(nbc), dim3(256), 0, s, col_ptr, row_idx,
-					   (const int32_t *) val, new_nleaves, lm, out_ptr, out_idx, (int32_t *) out_val);
-		HIP_TRY(hipGetLastError());
-		return 0;
-	}
+	if (c.perm[0] == 0 && new_nleaves < ((int64_t) 1 << 31) - 1)
+		return aperm_leaf_preserving(c, new_nleaves);
 	// (the leaf-preserving form above counts positions in 64 bits; the others do not)
-	if (nnz >= ((int64_t) 1 << 31))
+	if (c.nnz >= ((int64_t) 1 << 31))
 		return svt_set_unsupported("aperm: more than 2^31-1 nonzeros");
-	// 3-d: c(2,3,1) and c(3,2,1) as c(2,1,3) followed by c(1,3,2) / c(3,1,2) (see aperm_via_bytes)
-	if (!nested && ndim == 3 && ((perm[0] == 1 && perm[1] == 2 && perm[2] == 0) ||
-			  (perm[0] == 2 && perm[1] == 1 && perm[2] == 0 && dim[2] <= 1024))) {
-		T2Shape sh;
-		size_t reserve = 0;
-		const size_t via = aperm_via_bytes(nnz, dim, 3);
-		if (via > 0 && aperm_swap01_bytes(nnz, dim, 3, &sh, &reserve) > 0) {
-			g_route[5]++;
-			const int64_t nly = dim[0] * dim[2];
-			char *p = (char *) ws;
-			int64_t *ycp = (int64_t *) p;         p += t2_a((size_t) nly + 1, 8);
-			int32_t *yri = (int32_t *) p;         p += t2_a((size_t) nnz, 4);
-			void *yv = p;
-			void *sub = (char *) ws + via;
-			int rc;
-			if (Rtype == SVT_REALSXP)
-				rc = launch_transpose_bucketed<double>(col_ptr, row_idx, (const double *) val, dim[0], ncol, nnz, sh,
-								       ycp, yri, (double *) yv, sub, reserve, s);
-			else
-				rc = launch_transpose_bucketed<int32_t>(col_ptr, row_idx, (const int32_t *) val, dim[0], ncol, nnz, sh,
-									ycp, yri, (int32_t *) yv, sub, reserve, s);
-			if (rc)
-				return rc;
-			const int64_t dimy[3] = {dim[1], dim[0], dim[2]};
-			const int p231[3] = {0, 2, 1}, p321[3] = {2, 0, 1};
-			return launch_aperm_n(ycp, yri, yv, Rtype, nly, nnz, dimy, 3, perm[0] == 1 ? p231 : p321,
-					      out_ptr, out_idx, out_val, sub, s, 1);
-		}
-	}
-	// the first two axes change places, the others stay: one batched bucketed transposition, no sort
-	{
-		bool swap01 = nested < 2 && ndim >= 3 && perm[0] == 1 && perm[1] == 0;
-		for (int a = 2; a < ndim && swap01; a++) swap01 = perm[a] == a;
-		T2Shape sh;
-		size_t reserve = 0;
-		if (swap01 && aperm_swap01_bytes(nnz, dim, ndim, &sh, &reserve) > 0) {
-			g_route[3]++;
-			if (Rtype == SVT_REALSXP)
-				return launch_transpose_bucketed<double>(col_ptr, row_idx, (const double *) val, dim[0], ncol, nnz, sh,
-									 out_ptr, out_idx, (double *) out_val, ws, reserve, s);
-			return launch_transpose_bucketed<int32_t>(col_ptr, row_idx, (const int32_t *) val, dim[0], ncol, nnz, sh,
-								  out_ptr, out_idx, (int32_t *) out_val, ws, reserve, s);
-		}
-	}
-	// slab form (see aperm_slab_kernel): new axis 0 = an old outer axis of <= 1024 entries, new axis 1 = the old
-	// rows, slabs of a few thousand nonzeros.  The largest slab is read back (one synchronisation of the
-	// stream): a slab over the cap sends the array through the key sort below.
-	if (nested < 2 && ndim >= 3 && perm[1] == 0 && perm[0] >= 1 && dim[perm[0]] <= 1024 && dim[0] < ((int64_t) 1 << 30)) {
-		const int q = perm[0];
-		int64_t os[8], st = 1;
-		for (int a = 1; a < ndim; a++) { os[a] = st; st *= dim[a]; }
-		SlabMap sm;
-		sm.nother = ndim - 2;
-		int64_t nslab = 1;
-		for (int t = 0; t < ndim - 2; t++) {
-			sm.new_ext[t] = dim[perm[2 + t]];
-			sm.old_stride[t] = os[perm[2 + t]];
-			nslab *= dim[perm[2 + t]];
-		}
-		size_t tb = 0;
-		if (nslab < 2147483646LL)
-			tb = exclusive_scan_ws_bytes(nslab + 1);
-		const size_t a4 = ((size_t) nnz * 4 + 255) / 256 * 256;
-		const size_t cnt_b = ((size_t) (nslab + 2) * 8 + 255) / 256 * 256;
-		if (nslab >= 1 && nslab < 2147483646LL && nnz / nslab <= SLAB_CAP * 9 / 10 && cnt_b + tb + 256 <= 5 * a4) {
-			int64_t *base = (int64_t *) ws;
-			unsigned long long *maxcnt = (unsigned long long *) ((char *) ws + cnt_b);
-			void *scan_tmp = (char *) ws + cnt_b + 256;
-			HIP_TRY(hipMemsetAsync(maxcnt, 0, 8, s));
-			hipLaunchKernelGGL(aperm_slab_count_kernel, dim3((unsigned) ((nslab + 1 + 255) / 256)), dim3(256), 0, s,
-					   col_ptr, sm, nslab, dim[q], os[q], base, maxcnt);
-			unsigned long long mx = 0;
-			HIP_TRY(hipMemcpyAsync(&mx, maxcnt, 8, hipMemcpyDeviceToHost, s));
-			HIP_TRY(hipStreamSynchronize(s));
-			if (mx > SLAB_CAP) g_route[9]++;
-			if (mx <= SLAB_CAP) {
-				g_route[4]++;
-				if (launch_exclusive_scan_i64(base, nslab + 1, scan_tmp, s))
-					return -1;
-				int bits = 1;
-				while (bits < 31 && ((int64_t) 1 << bits) < dim[0]) bits++;
-				const size_t lds = (size_t) SLAB_CAP * 4;
-				if (Rtype == SVT_REALSXP)
-					hipLaunchKernelGGL(aperm_slab_kernel<double>, dim3((unsigned) nslab), dim3(SLAB_NT), lds, s,
-							   col_ptr, row_idx, (const double *) val, sm, nslab, dim[0], (int) dim[q], os[q],
-							   bits, nnz, base, out_ptr, out_idx, (double *) out_val);
-				else
-					hipLaunchKernelGGL(aperm_slab_kernel<int32_t>, dim3((unsigned) nslab), dim3(SLAB_NT), lds, s,
-							   col_ptr, row_idx, (const int32_t *) val, sm, nslab, dim[0], (int) dim[q], os[q],
-							   bits, nnz, base, out_ptr, out_idx, (int32_t *) out_val);
-				HIP_TRY(hipGetLastError());
-				return 0;
-			}
-		}
-	}
-	// the general form: leaf-preserving step, first two axes swapped, leaf-preserving step (aperm_general_plan)
-	if (!nested) {
-		ApermPlan3 pl;
-		if (aperm_general_plan(nnz, dim, ndim, perm, &pl)) {
-			g_route[6]++;
-			char *p = (char *) ws;
-			const int64_t *cp_a = col_ptr; const int32_t *ri_a = row_idx; const void *v_a = val;
-			int64_t ncol_a = ncol;
-			int64_t *xcp = NULL; int32_t *xri = NULL; void *xv = NULL;
-			if (!pl.a_id && !pl.slab_first) {       // (the slab form goes from the operand to y in one step)
-				xcp = (int64_t *) p; p += t2_a((size_t) pl.leaves_a + 1, 8);
-				xri = (int32_t *) p; p += t2_a((size_t) nnz, 4);
-				xv = p;              p += t2_a((size_t) nnz, 8);
-			}
-			int64_t *ycp = out_ptr; int32_t *yri = out_idx; void *yv = out_val;
-			if (!pl.c_id) {
-				ycp = (int64_t *) p; p += t2_a((size_t) pl.leaves_b + 1, 8);
-				yri = (int32_t *) p; p += t2_a((size_t) nnz, 4);
-				yv = p;              p += t2_a((size_t) nnz, 8);
-			}
-			void *sub = p;
-			if (pl.slab_first) {
-				// c(q, 1, others) in one go (slab form; if a slab turns out too long the call takes the two steps, or the
-				// sort, itself), then the leaf-preserving step
-				int p1[8];
-				p1[0] = perm[0]; p1[1] = 0;
-				for (int a = 2; a < ndim; a++) p1[a] = pl.pa[a];
-				int rc = launch_aperm_n(col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, p1, ycp, yri, yv, sub, s, 1);
-				if (rc) return rc;
-				return launch_aperm_n(ycp, yri, yv, Rtype, pl.leaves_b, nnz, pl.dim_b, ndim, pl.pc, out_ptr, out_idx, out_val, sub, s, 1);
-			}
-			if (!pl.a_id) {
-				const int rc = launch_aperm_n(col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, pl.pa, xcp, xri, xv, sub, s, 1);
-				if (rc) return rc;
-				cp_a = xcp; ri_a = xri; v_a = xv; ncol_a = pl.leaves_a;
-			}
-			int pb[8];
-			for (int a = 0; a < ndim; a++) pb[a] = a == 0 ? 1 : a == 1 ? 0 : a;
-			int rc = launch_aperm_n(cp_a, ri_a, v_a, Rtype, ncol_a, nnz, pl.dim_a, ndim, pb, ycp, yri, yv, sub, s, 1);
-			if (rc) return rc;
-			if (!pl.c_id)
-				rc = launch_aperm_n(ycp, yri, yv, Rtype, pl.leaves_b, nnz, pl.dim_b, ndim, pl.pc, out_ptr, out_idx, out_val, sub, s, 1);
-			return rc;
-		}
-	}
-	if (new_nleaves < ((int64_t) 1 << 31) - 1) {
-		const size_t a4 = ((size_t) nnz * 4 + 255) / 256 * 256;
-		uint32_t *keys = (uint32_t *) ws, *skeys = (uint32_t *) ((char *) ws + a4);
-		uint32_t *pos = (uint32_t *) ((char *) ws + 2 * a4), *spos = (uint32_t *) ((char *) ws + 3 * a4);
-		int32_t *newrow = (int32_t *) ((char *) ws + 4 * a4);
-		uint32_t *ktmp = (uint32_t *) ((char *) ws + 5 * a4), *ptmp = (uint32_t *) ((char *) ws + 6 * a4);
-		uint32_t *hint = (uint32_t *) ((char *) ws + 7 * a4);
-		void *tmp = (char *) ws + 7 * a4 + hint_bytes(nnz);
-		int bits = 1;
-		while (bits < 32 && ((int64_t) 1 << bits) < new_nleaves) bits++;
-		const unsigned nb = (unsigned) ((nnz + 255) / 256);
-		const unsigned nb8 = (unsigned) (((nnz + 255) / 256 + 7) / 8 * 8);
-		const int64_t nblk = (nnz >> HINT_SHIFT) + 1;
-		g_route[7]++;
-		hipLaunchKernelGGL(col_hint_kernel, dim3((unsigned) ((nblk + 1 + 255) / 256)), dim3(256), 0, s, col_ptr, ncol, nblk, hint);
-		hipLaunchKernelGGL(aperm_key32_kernel, dim3(nb), dim3(256), 0, s, col_ptr, row_idx, hint, ncol, nnz, d,
-				   keys, pos, newrow);
-		if (svt_sort_pairs<uint32_t>(keys, skeys, ktmp, pos, spos, ptmp, nnz, bits, tmp, s))
-			return -1;
-		hipLaunchKernelGGL(aperm_ptr_fill_kernel<uint32_t>, dim3((unsigned) ((nnz + 1 + PTRFILL_NT - 1) / PTRFILL_NT)), dim3(PTRFILL_NT), 0, s,
-				   skeys, nnz, new_nleaves, 1ULL, out_ptr);
-		if (Rtype == SVT_REALSXP)
-			hipLaunchKernelGGL(aperm_gather32_kernel<double>, dim3(nb8), dim3(256), 0, s, spos, newrow,
-					   (const double *) val, nnz, out_idx, (double *) out_val);
-		else
-			hipLaunchKernelGGL(aperm_gather32_kernel<int32_t>, dim3(nb8), dim3(256), 0, s, spos, newrow,
-					   (const int32_t *) val, nnz, out_idx, (int32_t *) out_val);
-		HIP_TRY(hipGetLastError());
-		return 0;
-	}
-	const size_t n = (size_t) nnz;
-	const size_t a8 = (n * 8 + 255) / 256 * 256, a4 = (n * 4 + 255) / 256 * 256;
-	unsigned long long *keys = (unsigned long long *) ws;
-	unsigned long long *skeys = (unsigned long long *) ((char *) ws + a8);
-	uint32_t *pos = (uint32_t *) ((char *) ws + 2 * a8);
-	uint32_t *spos = (uint32_t *) ((char *) ws + 2 * a8 + a4);
-	unsigned long long *ktmp = (unsigned long long *) ((char *) ws + 2 * a8 + 2 * a4);
-	uint32_t *ptmp = (uint32_t *) ((char *) ws + 3 * a8 + 2 * a4);
-	void *tmp = (char *) ws + 3 * a8 + 3 * a4;
-	const int bits = aperm_bits(dim, ndim);
-	const unsigned nb = (unsigned) ((nnz + 255) / 256);
-	const unsigned nb8 = (unsigned) (((nnz + 255) / 256 + 7) / 8 * 8);
-	g_route[8]++;
-	hipLaunchKernelGGL(aperm_key_kernel, dim3(nb), dim3(256), 0, s, col_ptr, row_idx, ncol, nnz, d, keys, pos);
-	if (svt_sort_pairs<unsigned long long>(keys, skeys, ktmp, pos, spos, ptmp, nnz, bits, tmp, s))
-		return -1;
-	hipLaunchKernelGGL(aperm_ptr_fill_kernel<unsigned long long>, dim3((unsigned) ((nnz + 1 + PTRFILL_NT - 1) / PTRFILL_NT)), dim3(PTRFILL_NT), 0, s,
-			   skeys, nnz, new_nleaves, (unsigned long long) (new_dim0 > 0 ? new_dim0 : 1), out_ptr);
-	if (Rtype == SVT_REALSXP)
-		hipLaunchKernelGGL(aperm_gather_kernel<double>, dim3(nb8), dim3(256), 0, s, skeys, spos,
-				   (const double *) val, nnz, new_dim0, out_idx, (double *) out_val);
-	else
-		hipLaunchKernelGGL(aperm_gather_kernel<int32_t>, dim3(nb8), dim3(256), 0, s, skeys, spos,
-				   (const int32_t *) val, nnz, new_dim0, out_idx, (int32_t *) out_val);
-	HIP_TRY(hipGetLastError());
-	return 0;
+	int rc;
+	if (!nested && (rc = aperm_via_3d(c)) != APERM_NA)
+		return rc;
+	if (nested < 2 && (rc = aperm_swap01(c)) != APERM_NA)
+		return rc;
+	if (nested < 2 && (rc = aperm_slab(c)) <= 0)            // (APERM_NA or APERM_REFUSED: on to the forms below)
+		return rc;
+	if (!nested && (rc = aperm_general(c)) != APERM_NA)
+		return rc;
+	return new_nleaves < ((int64_t) 1 << 31) - 1 ? aperm_sort32(c, new_nleaves) : aperm_sort64(c, new_nleaves);
 }
 
 // ---------------------------------------------------------------------------
@@ -1956,40 +2011,14 @@ static int launch_aperm_n(const int64_t *col_ptr, const int32_t *row_idx, const 
 //           into a second temporary of new_nleaves + 1 pointers.  Placement: box_place_kernel, adding q0 to the rows.
 // Why the result is exact: boxes are taken in ascending q0, so every box contributes ONE contiguous run to every result
 // leaf and the runs come in box order = i_q order; only copies happen, and the permuted array has one representation.
-// Workspace: the route area R = the larger of the key sort's need and aperm_ws_bytes() at the largest box, two box
-// temporaries (12 B and 8-12 B per entry), new_nleaves + 1 pointers twice (box result, fill), qptr (dim[q] + 1), the
-// box's col_ptr, scan scratch, the cut table -- not O(nnz).  The routes' needs depend on the box's dims, which are not
-// known before the data is seen: a box whose preferred route needs more than R takes the key sort (nested = 2), whose
-// need depends on the box's nonzero count alone and is part of R.
+// Workspace: abox_layout() -- not O(nnz).  Its route area R is the larger of aperm_key_sort_bytes() and aperm_ws_bytes() at the
+// largest box.  The routes' needs depend on the box's dims, which are not known before the data is seen: a box whose preferred
+// route needs more than R takes the key sort (nested = 2), whose need depends on the box's nonzero count alone.
 // ---------------------------------------------------------------------------
 #define ABOX_DEFAULT ((int64_t) 1 << 28)
 #define ABOX_LEAVES ((int64_t) 1 << 20)  // a box spans at most max(this, new_nleaves) old leaves (or one index of axis q)
 #define ABOX_CNT_NT 256
 #define ABOX_CNT_LDS 8192                // indices of axis q counted in LDS (64 KB of 64-bit counters); more: memory atomics
-
-static int64_t abox_size(int64_t box_limit)
-{
-	return box_limit > 0 ? (box_limit < 0x7FFFFFFFLL ? box_limit : 0x7FFFFFFFLL) : ABOX_DEFAULT;
-}
-
-static bool aperm_perm_ok(int ndim, const int *perm)
-{
-	if (ndim < 1 || ndim > 8)
-		return false;
-	bool seen[8] = {false, false, false, false, false, false, false, false};
-	for (int a = 0; a < ndim; a++) {
-		if (perm[a] < 0 || perm[a] >= ndim || seen[perm[a]])
-			return false;
-		seen[perm[a]] = true;
-	}
-	return true;
-}
-
-static size_t aperm_key_sort_bytes(int64_t nnz)
-{
-	const size_t a4 = ((size_t) (nnz > 0 ? nnz : 1) * 4 + 255) / 256 * 256;
-	return 7 * a4 + hint_bytes(nnz) + svt_sort_ws_bytes(nnz) + 256;
-}
 
 struct ABoxLayout {
 	bool ok;                 // the result has fewer than 2^31 - 1 leaves and no extent is 0
@@ -2002,12 +2031,10 @@ static ABoxLayout abox_layout(int64_t nnz, const int64_t *dim, int ndim, int q, 
 {
 	ABoxLayout L;
 	memset(&L, 0, sizeof(L));
-	double nl = 1.0;
-	for (int a = 0; a < ndim; a++) {
+	for (int a = 0; a < ndim; a++)
 		if (dim[a] <= 0) return L;
-		if (a != q) nl *= (double) dim[a];
-	}
-	if (nl >= 2147483646.0) return L;
+	const double nl = extent_prod(dim, 0, ndim, q);
+	if (nl >= LEAVES_MAX) return L;
 	L.ok = true;
 	L.new_nl = (int64_t) nl;
 	L.slice_nl = L.new_nl / dim[0];                         // old leaves per index of axis q
@@ -2015,7 +2042,7 @@ static ABoxLayout abox_layout(int64_t nnz, const int64_t *dim, int ndim, int q, 
 	for (int a = 1; a < q; a++) L.osq *= dim[a];
 	L.nouter = L.slice_nl / L.osq;
 	L.outer = L.nouter == 1;
-	L.bsz = abox_size(box_limit);
+	L.bsz = box_size(box_limit, ABOX_DEFAULT);
 	L.bmax = L.bsz > L.new_nl ? L.bsz : L.new_nl;           // a box: <= bsz nonzeros, or one index of axis q
 	if (L.bmax > nnz) L.bmax = nnz > 0 ? nnz : 1;
 	const int64_t lcap = L.new_nl > ABOX_LEAVES ? L.new_nl : ABOX_LEAVES;
@@ -2052,11 +2079,8 @@ size_t aperm_perm_ws_bytes_box(int64_t nnz, const int64_t *dim, int ndim, const 
 	if (perm[0] == 0) {
 		// leaf-preserving, never boxed: the scratch of a scan over the leaf counts (with 2^31 - 1 leaves or more
 		// the call goes to the 64-bit key sort, or is refused)
-		double nl = 1.0;
-		for (int a = 1; a < ndim; a++) nl *= (double) (dim[a] > 0 ? dim[a] : 1);
-		if (nl < 2147483646.0)
-			return exclusive_scan_ws_bytes((int64_t) nl + 1) + 256;
-		return aperm_ws_bytes(nnz, dim, ndim);
+		const size_t scan_b = aperm_leaf_scan_bytes(dim, ndim);
+		return scan_b > 0 ? scan_b + 256 : aperm_ws_bytes(nnz, dim, ndim);
 	}
 	if (ndim == 2)
 		return transpose_ws_bytes_box(dim[0], nnz, box_limit);
@@ -2135,17 +2159,33 @@ abox_leaf_len_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restr
 	}
 }
 
+// count: the lengths of the result's leaves, scanned in place into out_ptr; fill[] = 0
+static int abox_leaf_lengths(const int64_t *col_ptr, const int32_t *row_idx, int64_t ncol, const int64_t *dim, int ndim,
+			     const int *perm, int64_t new_nl, int64_t *out_ptr, int64_t *fill, void *scan_ws, hipStream_t s)
+{
+	ABoxMap mp;
+	memset(&mp, 0, sizeof(mp));
+	mp.ndim = ndim;
+	for (int a = 0; a < ndim; a++) mp.dim[a] = dim[a];
+	int64_t st = 1;
+	for (int a = 1; a < ndim; a++) { mp.nmul[perm[a]] = st; st *= dim[perm[a]]; }
+	HIP_TRY(hipMemsetAsync(out_ptr, 0, (size_t) (new_nl + 1) * 8, s));
+	HIP_TRY(hipMemsetAsync(fill, 0, (size_t) new_nl * 8, s));
+	int64_t nbl = (ncol + 3) / 4;
+	if (nbl > ((int64_t) 1 << 22)) nbl = (int64_t) 1 << 22;
+	hipLaunchKernelGGL(abox_leaf_len_kernel, dim3((unsigned) nbl), dim3(256), 0, s, col_ptr, row_idx, ncol, mp, (unsigned long long *) out_ptr);
+	HIP_TRY(hipGetLastError());
+	return launch_exclusive_scan_i64(out_ptr, new_nl + 1, scan_ws, s);
+}
+
 static int launch_aperm_boxed(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
 			      int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
 			      int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, int64_t box_limit, hipStream_t s)
 {
 	const int q = perm[0];
 	const ABoxLayout Ly = abox_layout(nnz, dim, ndim, q, box_limit);
-	if (!Ly.ok) {
-		double nl = 1.0;
-		for (int a = 0; a < ndim; a++) if (a != q) nl *= (double) dim[a];
-		return svt_set_unsupported("aperm: the permuted array has %.0f leaves, 2^31-1 or more", nl);
-	}
+	if (!Ly.ok)
+		return svt_set_unsupported("aperm: the permuted array has %.0f leaves, 2^31-1 or more", extent_prod(dim, 0, ndim, q, false));
 	char *w = (char *) ws;
 	int64_t *pts = (int64_t *) (w + Ly.pts), *qptr = (int64_t *) (w + Ly.qptr), *fill = (int64_t *) (w + Ly.fill);
 	int64_t *bcp = (int64_t *) (w + Ly.bcp), *bptr = (int64_t *) (w + Ly.bptr);
@@ -2168,47 +2208,11 @@ static int launch_aperm_boxed(const int64_t *col_ptr, const int32_t *row_idx, co
 	HIP_TRY(hipGetLastError());
 	if (launch_exclusive_scan_i64(qptr, dq + 1, scan_ws, s))
 		return -1;
-	// the cuts, read back once
-	const int64_t nk = (nnz - 1) / Ly.bsz, nw = (dq - 1) / Ly.Wq, npts = nk + nw;
-	if (npts > Ly.npts_max)
-		return svt_set_error("aperm: internal error (box cuts)");
-	std::vector<int64_t> hp((size_t) npts * 3 + 1);
-	if (npts > 0) {
-		hipLaunchKernelGGL(box_cut_kernel, dim3((unsigned) ((npts + 255) / 256)), dim3(256), 0, s, qptr, dq, nk,
-				   Ly.bsz, Ly.Wq, npts, pts);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(hp.data(), pts, (size_t) npts * 24, hipMemcpyDeviceToHost, s));
-	}
-	// lengths of the result's leaves -> out_ptr (queued before the wait for the cuts)
-	ABoxMap mp;
-	memset(&mp, 0, sizeof(mp));
-	mp.ndim = ndim;
-	for (int a = 0; a < ndim; a++) mp.dim[a] = dim[a];
-	{
-		int64_t st = 1;
-		for (int a = 1; a < ndim; a++) { mp.nmul[perm[a]] = st; st *= dim[perm[a]]; }
-	}
-	HIP_TRY(hipMemsetAsync(out_ptr, 0, (size_t) (new_nl + 1) * 8, s));
-	HIP_TRY(hipMemsetAsync(fill, 0, (size_t) new_nl * 8, s));
-	int64_t nbl = (ncol + 3) / 4;
-	if (nbl > ((int64_t) 1 << 22)) nbl = (int64_t) 1 << 22;
-	hipLaunchKernelGGL(abox_leaf_len_kernel, dim3((unsigned) nbl), dim3(256), 0, s, col_ptr, row_idx, ncol, mp,
-			   (unsigned long long *) out_ptr);
-	HIP_TRY(hipGetLastError());
-	if (launch_exclusive_scan_i64(out_ptr, new_nl + 1, scan_ws, s))
+	// the cuts, read back once; the lengths of the result's leaves -> out_ptr are queued before the wait for them
+	BoxBounds bd;                                       // (index of axis q, qptr there)
+	if (box_boundaries("aperm", qptr, dq, nnz, Ly.bsz, Ly.Wq, Ly.npts_max, pts, s, &bd, [&] {
+		    return abox_leaf_lengths(col_ptr, row_idx, ncol, dim, ndim, perm, new_nl, out_ptr, fill, scan_ws, s); }))
 		return -1;
-	HIP_TRY(hipStreamSynchronize(s));
-	std::vector<std::pair<int64_t, int64_t>> bd;        // (index of axis q, qptr there): box boundaries
-	bd.reserve((size_t) npts * 2 + 2);
-	bd.push_back({0, 0});
-	bd.push_back({dq, nnz});
-	for (int64_t i = 0; i < npts; i++) {
-		bd.push_back({hp[3 * i], hp[3 * i + 1]});
-		bd.push_back({hp[3 * i] + 1, hp[3 * i + 2]});
-	}
-	std::sort(bd.begin(), bd.end());
-	bd.erase(std::unique(bd.begin(), bd.end()), bd.end());
-	const unsigned nbp = (unsigned) ((new_nl + 3) / 4);
 	int64_t bdim[8];
 	for (int a = 0; a < ndim; a++) bdim[a] = dim[a];
 	LeafMap lm;                                         // box leaf (inner, i_q - q0, outer) -> old leaf, from leaf q0 * osq on
@@ -2231,36 +2235,23 @@ static int launch_aperm_boxed(const int64_t *col_ptr, const int32_t *row_idx, co
 		if (Ly.outer) {
 			hipLaunchKernelGGL(box_rebase_kernel, dim3((unsigned) ((bl + 1 + 255) / 256)), dim3(256), 0, s,
 					   lcp, (int64_t) 0, bl, p0, bcp);
+			HIP_TRY(hipGetLastError());
 			bri = row_idx + p0;
 			bv = (const char *) val + (size_t) p0 * esz;
 		} else {
 			lm.new_dim[2] = wq;
-			hipLaunchKernelGGL(aperm_leaf_count_kernel, dim3((unsigned) ((bl + 1 + 255) / 256)), dim3(256), 0, s,
-					   lcp, bl, lm, bcp);
-			if (launch_exclusive_scan_i64(bcp, bl + 1, scan_ws, s))
+			if (launch_leaf_move(lcp, row_idx, val, Rtype, bl, lm, bcp, gidx, gval, scan_ws, s))
 				return -1;
-			const unsigned nbg = (unsigned) ((bl + 4 * APERM_LU - 1) / (4 * APERM_LU));
-			if (Rtype == SVT_REALSXP)
-				hipLaunchKernelGGL(aperm_leaf_copy_kernel<double>, dim3(nbg), dim3(256), 0, s, lcp, row_idx,
-						   (const double *) val, bl, lm, bcp, gidx, (double *) gval);
-			else
-				hipLaunchKernelGGL(aperm_leaf_copy_kernel<int32_t>, dim3(nbg), dim3(256), 0, s, lcp, row_idx,
-						   (const int32_t *) val, bl, lm, bcp, gidx, (int32_t *) gval);
 		}
-		HIP_TRY(hipGetLastError());
 		bdim[q] = wq;
 		// the box's preferred route where the route area holds it, else the key sort (whose need is part of the area)
 		const bool fits = aperm_ws_bytes(nb, bdim, ndim) <= Ly.route_bytes;
 		if (!fits && aperm_key_sort_bytes(nb) > Ly.route_bytes)
 			return svt_set_error("aperm: internal error (route area of a box)");
-		if (launch_aperm_n(bcp, bri, bv, Rtype, bl, nb, bdim, ndim, perm, bptr, bidx, bval, rws, s, fits ? 0 : 2))
+		const ApermCall box = {bcp, bri, bv, Rtype, bl, nb, bdim, ndim, perm, bptr, bidx, bval, rws, s};
+		if (launch_aperm_n(box, fits ? 0 : 2))
 			return -1;
-		if (Rtype == SVT_REALSXP)
-			hipLaunchKernelGGL(box_place_kernel<double>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const double *) bval,
-					   new_nl, (int32_t) q0, out_ptr, fill, out_idx, (double *) out_val);
-		else
-			hipLaunchKernelGGL(box_place_kernel<int32_t>, dim3(nbp), dim3(256), 0, s, bptr, bidx, (const int32_t *) bval,
-					   new_nl, (int32_t) q0, out_ptr, fill, out_idx, (int32_t *) out_val);
+		launch_box_place(Rtype, bptr, bidx, bval, new_nl, q0, out_ptr, fill, out_idx, out_val, s);
 		HIP_TRY(hipGetLastError());
 	}
 	g_boxed_calls++;
@@ -2273,14 +2264,14 @@ int launch_aperm_box(const int64_t *col_ptr, const int32_t *row_idx, const void 
 		     int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
 		     int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, int64_t box_limit, hipStream_t s)
 {
-	if (!box_taken(nnz, box_limit) || ndim < 2 || !aperm_perm_ok(ndim, perm) || perm[0] == 0)
-		return launch_aperm(col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, perm, out_ptr, out_idx, out_val, ws, s);
+	if (!box_taken(nnz, box_limit) || ndim < 2 || !aperm_perm_ok(ndim, perm) || perm[0] == 0) {
+		const ApermCall c = {col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, perm, out_ptr, out_idx, out_val, ws, s};
+		return launch_aperm_n(c, 0);
+	}
 	if (ndim == 2)
 		return launch_transpose_box(col_ptr, row_idx, val, Rtype, dim[0], ncol, nnz, out_ptr, out_idx, out_val, ws,
 					    box_limit, s);
-	double total = 1.0;
-	for (int a = 0; a < ndim; a++) total *= (double) (dim[a] > 0 ? dim[a] : 1);
-	if (total >= 9.2e18)
+	if (extent_prod(dim, 0, ndim) >= 9.2e18)
 		return svt_set_error("aperm: array too large for 64-bit linear indices");
 	return launch_aperm_boxed(col_ptr, row_idx, val, Rtype, ncol, nnz, dim, ndim, perm, out_ptr, out_idx, out_val, ws,
 				  box_limit, s);

@@ -114,6 +114,16 @@ void svt_clear_unsupported(void);
 					     __FILE__, __LINE__);             \
 	} while (0)
 
+// f(in, out) with two value arrays typed by the R type of the values, double or int32_t (host side; a templated
+// kernel deduces its type from them):
+//   svt_by_rtype(Rtype, val, out_val, [&](auto *v, auto *o) { hipLaunchKernelGGL(kernel, ..., v, ..., o); });
+template <class F>
+static inline void svt_by_rtype(int Rtype, const void *in, void *out, F &&f)
+{
+	if (Rtype == SVT_REALSXP) f((const double *) in, (double *) out);
+	else f((const int32_t *) in, (int32_t *) out);
+}
+
 // kernel launchers implemented in the .hip files ---------------------------------
 struct StatsArgs {
 	const int64_t *col_ptr;
@@ -210,10 +220,7 @@ int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void 
 
 void aperm_route_counts(int64_t *out, int reset);
 size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim);
-int launch_aperm(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
-		 int64_t ncol, int64_t nnz, const int64_t *dim, int ndim, const int *perm,
-		 int64_t *out_ptr, int32_t *out_idx, void *out_val, void *ws, hipStream_t s);
-// the same with the boxed driver for the permutations that move the rows, past the box limit (read once per call and
+// aperm, with the boxed driver for the permutations that move the rows past the box limit (read once per call and
 // passed down); perm is 0-based.  aperm_ws_bytes_box(): at least the need of every permutation, and aperm_ws_bytes()
 // itself whenever the driver is not taken; aperm_perm_ws_bytes_box(): the need of one permutation.
 size_t aperm_ws_bytes_box(int64_t nnz, const int64_t *dim, int ndim, int64_t box_limit);

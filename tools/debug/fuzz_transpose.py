@@ -1,11 +1,102 @@
 """Differential fuzzing of the device transposition (bucketed count / scan / scatter, and its key-sort
 fallback for the shapes it does not take) against a stable sort by row on the GPU: random shapes from one
 row to 3e5, from one column to 2e5, densities from 1e-4 to 1, skewed rows and columns, both value types.
-    python tools/debug/fuzz_transpose.py [ncases] [seed]"""
+    python tools/debug/fuzz_transpose.py [ncases] [seed]
+    python tools/debug/fuzz_transpose.py --routes      the route table (below) instead"""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from sparsearray_amd.device import DeviceCSC
+
+
+def routes_table():
+    """Which routes (device.aperm_route_counts()) fixed operands take: the shapes of the device-level aperm tests and of
+    the boxed t() / aperm() tests with their box limits, seeded.  One line per call; two builds of the library that
+    are meant to route alike give the same output."""
+    from sparsearray_amd import device
+    dev = torch.device("cuda", 0)
+
+    def operand(a):
+        flat = a.reshape(-1, order="F")
+        nz = np.flatnonzero(flat)
+        cp = np.zeros(a.size // a.shape[0] + 1, np.int64)
+        np.cumsum(np.bincount(nz // a.shape[0], minlength=len(cp) - 1), out=cp[1:])
+        return DeviceCSC(a.shape[0], torch.as_tensor(cp, device=dev), torch.as_tensor((nz % a.shape[0]).astype(np.int32), device=dev),
+                         torch.as_tensor(flat[nz], device=dev))
+
+    def dense(dim, nnz, dtype, seed):
+        rng = np.random.default_rng(seed)
+        a = np.zeros(dim, dtype=np.float64 if dtype == "double" else np.int32, order="F")
+        if nnz:
+            idx = rng.choice(a.size, size=nnz, replace=False)
+            a.reshape(-1, order="F")[idx] = rng.normal(size=nnz) if dtype == "double" else rng.integers(1, 1000, size=nnz)
+        return a
+
+    def run(name, A, dim, perm, limit=0):
+        device.aperm_route_counts(reset=True)
+        b0 = device.boxed_calls()
+        try:
+            device.set_box_nnz(limit)
+            A.t() if perm is None else A.aperm(dim, perm)
+            torch.cuda.synchronize()
+        finally:
+            device.set_box_nnz(0)
+        rc = device.aperm_route_counts()
+        print(f"{name} dim {'x'.join(map(str, dim))} perm {perm} box {limit}: " + " ".join(str(v) for v in rc.values())
+              + f" | boxed {device.boxed_calls() - b0}", flush=True)
+
+    d3 = [((700, 40, 23), 20000, p, "double") for p in ((3, 2, 1), (1, 3, 2), (2, 3, 1), (3, 1, 2), (2, 1, 3))]
+    swapped = [((3000, 2500, 5), 750_000, (2, 1, 3), "double"), ((3000, 2500, 5), 750_000, (2, 1, 3), "integer"),
+               ((1234, 777, 3, 2), 400_000, (2, 1, 3, 4), "double"), ((5000, 300, 7), 900_000, (2, 1, 3), "double"),
+               ((700, 40, 23), 20000, (2, 1, 3), "double"), ((3000, 2500, 5), 750_000, (2, 3, 1), "double"),
+               ((3000, 2500, 5), 750_000, (3, 2, 1), "double"), ((3000, 2500, 5), 750_000, (3, 2, 1), "integer"),
+               ((5000, 300, 7), 900_000, (2, 3, 1), "integer")]
+    slab = [((700, 40, 23), 20000, (3, 1, 2), "integer"), ((5000, 9, 64), 30000, (3, 1, 2), "double"),
+            ((300, 6, 5, 4), 9000, (3, 1, 2, 4), "double"), ((300, 6, 5, 4), 9000, (4, 1, 3, 2), "double"),
+            ((64, 50, 1), 1500, (3, 1, 2), "double"), ((20000, 3, 64), 800000, (3, 1, 2), "double"),
+            ((900, 30, 16), 0, (3, 1, 2), "double")]
+    general = [((1500, 900, 4, 3), 1_500_000, (2, 4, 1, 3), "double"), ((1500, 900, 4, 3), 1_500_000, (3, 1, 4, 2), "double"),
+               ((1500, 4, 900, 3), 1_500_000, (3, 2, 4, 1), "double"), ((1500, 4, 900, 3), 1_500_000, (3, 4, 2, 1), "integer"),
+               ((1200, 5, 3, 700, 2), 1_200_000, (4, 5, 1, 3, 2), "double"), ((1200, 5, 3, 700, 2), 1_200_000, (4, 1, 2, 3, 5), "double"),
+               ((300, 6, 5, 4), 9000, (2, 4, 3, 1), "double"), ((300, 6, 5, 4), 9000, (4, 3, 2, 1), "integer"),
+               ((40, 30, 20, 10, 3), 50_000, (5, 3, 1, 4, 2), "double")]
+    for group, cases, seed in (("aperm", d3, 44), ("swapped", swapped, 46), ("slab", slab, 45), ("general", general, 47)):
+        for dim, nnz, perm, dtype in cases:
+            run(f"{group} {dtype}", operand(dense(dim, nnz, dtype, seed)), dim, perm)
+    # one slab over the slab form's cap inside the general form, and inside the 3-d "via" route
+    dim, rng = (3000, 4, 6, 5), np.random.default_rng(49)
+    a = np.zeros(dim, order="F")
+    blk = np.zeros((dim[0], dim[2]))
+    blk.reshape(-1)[rng.choice(blk.size, size=12_000, replace=False)] = rng.normal(size=12_000)
+    a[:, 0, :, 0] = blk
+    mask = np.ones(dim, dtype=bool); mask[:, 0, :, 0] = False
+    a.reshape(-1, order="F")[rng.choice(np.flatnonzero(mask.reshape(-1, order="F")), size=80_000, replace=False)] = rng.normal(size=80_000)
+    run("slab_refused general", operand(a), dim, (3, 4, 1, 2))
+    a3 = np.asfortranarray(a.transpose(0, 2, 1, 3).reshape((3000, 6, 20), order="F"))
+    run("slab_refused via", operand(a3), (3000, 6, 20), (3, 2, 1))
+    # the boxed drivers
+    rm3 = [(2, 1, 3), (2, 3, 1), (3, 1, 2), (3, 2, 1)]
+    boxed = [((700, 40, 23), 20000, rm3), ((5000, 300, 7), 900_000, [(2, 1, 3)]), ((900, 30, 16), 40000, [(3, 1, 2)]),
+             ((1500, 900, 4, 3), 1_500_000, [(2, 4, 1, 3), (3, 1, 4, 2)]), ((1500, 4, 900, 3), 1_500_000, [(3, 2, 4, 1), (3, 4, 2, 1)]),
+             ((1200, 5, 3, 700, 2), 1_200_000, [(4, 5, 1, 3, 2), (4, 1, 2, 3, 5)]), ((300, 6, 5, 4), 9000, [(2, 4, 3, 1), (4, 3, 2, 1)]),
+             ((40, 30, 20, 10, 3), 50_000, [(5, 3, 1, 4, 2)]), ((300, 500), 20000, [(2, 1)]), ((64, 50, 1), 1500, [(3, 1, 2), (3, 2, 1)]),
+             ((50, 1, 40), 1200, [(2, 1, 3), (2, 3, 1)]), ((1, 60, 45), 1500, rm3), ((900, 30, 16), 0, [(3, 1, 2), (2, 1, 3)])]
+    for dim, nnz, perms in boxed:
+        for dtype in ("double", "integer"):
+            A = operand(dense(dim, nnz, dtype, 50))
+            for perm in perms:
+                for limit in (257, 4096, 100000):
+                    run(f"boxed aperm {dtype}", A, dim, perm, limit)
+    for nrow, ncol, nnz in ((700, 900, 54000), (500, 3000, 18000), (5000, 400, 8000), (1, 6000, 2400), (9000, 1, 6000),
+                            (300, 100_000, 2400), (3000, 2000, 600_000), (50000, 300, 3000)):
+        A = operand(dense((nrow, ncol), nnz, "double", 51))
+        for limit in (257, 4096, 100000):
+            run("boxed t", A, (nrow, ncol), None, limit)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--routes":
+    routes_table()
+    sys.exit(0)
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
