@@ -38,38 +38,144 @@ __host__ __device__ inline MinMaxScratch split_scratch(void *p, int64_t n)
 	return s;
 }
 
-size_t rowstats_scratch_bytes(int opcode, int out_Rtype, int64_t out_len)
+size_t rowstats_scratch_bytes(int opcode, int64_t out_len)
 {
-	(void) out_Rtype;
 	if (opcode != SVT_OP_MIN && opcode != SVT_OP_MAX)
 		return 16;
 	return (size_t) out_len * 16 + 16;
 }
 
+// The three rules below are the whole of the reference's row statistics; every route states them through these
+// functions.  A cell is entry `i` of four arrays -- `acc` (a double; an int flag for anyNA on a zero background; an
+// ordered 64-bit key for min / max), `cen` (centered_X2_sum), `flg` and `cov` (min / max, and the coverage under the
+// NaArray background) -- which live in `out` / the min-max scratch on the memory-atomic route and in LDS on the others.
+// NABG: the route can see a NaArray operand at all (`nabg`: this one is); cells covered fewer than nstrata times then
+// hold implicit NAs:
+//   countNAs / anyNA: count the stored non-NA values, result nstrata - count (!= 0)
+//   sum, na.rm=FALSE: NA_real_ wherever the coverage is short (:612-634)
+//   min / max: the NA background joins instead of the implicit zero (:914-961)
+
+// a cell before its first nonzero; `cell`: its place in `out` and `center`.  The centered sum starts from
+// c * c * nstrata (:1044-1066), once per cell: `first` is false for the strata ranges after the first.  `cen`: where
+// the LDS routes keep c for the update rule (NULL: the rule reads a.center itself).
+template <bool NABG, typename I>
+__device__ __forceinline__ void rowstats_init_cell(const RowStatsArgs &a, const bool nabg, const bool first,
+						   const int64_t cell, const I i, void *acc, double *cen, int *flg,
+						   unsigned int *cov)
+{
+	const int oc = a.opcode;
+	if (oc == SVT_OP_MIN || oc == SVT_OP_MAX) {
+		((unsigned long long *) acc)[i] = oc == SVT_OP_MIN ? ~0ULL : 0ULL;
+		flg[i] = 0;
+		cov[i] = 0;
+	} else if (oc == SVT_OP_CENTERED_X2_SUM) {
+		const double c = a.center ? a.center[cell] : 0.0;
+		if (cen) cen[i] = c;
+		((double *) acc)[i] = a.center && first ? c * c * (double) a.nstrata : 0.0;
+	} else if (oc == SVT_OP_ANYNA && !(NABG && nabg)) {
+		((int *) acc)[i] = 0;
+	} else {
+		((double *) acc)[i] = 0.0;
+		if (NABG && nabg) cov[i] = 0;
+	}
+}
+
+// one nonzero into its cell
+template <typename T, bool NABG, typename I>
+__device__ __forceinline__ void rowstats_update(const int oc, const bool narm, const bool nabg, const T v, const I i,
+						void *acc, const double *cen, int *flg, unsigned int *cov)
+{
+	const bool is_dbl = sizeof(T) == 8;
+	const bool bg = NABG && nabg;
+	const bool miss = is_dbl ? (v != v) : ((int) v == NA_INT);
+	double *accd = (double *) acc;
+	switch (oc) {
+	case SVT_OP_ANYNA:       // :498-514
+		if (bg) { if (!miss) atomicAdd(accd + i, 1.0); }
+		else if (miss) ((int *) acc)[i] = 1;
+		break;
+	case SVT_OP_COUNTNAS:    // :516-535
+		if (bg ? !miss : miss) atomicAdd(accd + i, 1.0);
+		break;
+	case SVT_OP_SUM:         // :599-634 with :412-433
+		if (bg && !narm) atomicAdd(cov + i, 1u);
+		if (miss && narm) break;
+		atomicAdd(accd + i, (!is_dbl && miss) ? svt_na_real() : (double) v);
+		break;
+	case SVT_OP_CENTERED_X2_SUM: {   // :636-696
+		const double c = cen ? cen[i] : 0.0;
+		if (miss && narm) { atomicAdd(accd + i, -(c * c)); break; }
+		const double x = (!is_dbl && miss) ? svt_na_real() : (double) v;
+		atomicAdd(accd + i, x * (x - 2 * c));
+		break;
+	}
+	default: {               // min / max, :537-597
+		atomicAdd(cov + i, 1u);
+		if (miss) {
+			const bool isna = is_dbl ? svt_is_na((double) v) : true;
+			atomicOr(flg + i, isna ? RF_NA : RF_NAN);
+			break;
+		}
+		atomicOr(flg + i, RF_HAVE);
+		const unsigned long long key = is_dbl ?
+			f64_to_ordered((double) v) :
+			(unsigned long long) ((long long) (int) v + 0x80000000LL);
+		if (oc == SVT_OP_MIN) atomicMin((unsigned long long *) acc + i, key);
+		else atomicMax((unsigned long long *) acc + i, key);
+	}
+	}
+}
+
+// a finished min / max cell into out[cell]: NA > NaN > extremum; the implicit zero (the NA background) joins when the
+// cell was covered fewer than nstrata times (:914-961); an int cell with nothing is NA and warns (:930-931)
+template <typename T, bool NABG>
+__device__ __forceinline__ void rowstats_minmax_finish(const RowStatsArgs &a, const bool nabg, const int64_t cell,
+						       const unsigned long long best, const int fl,
+						       const unsigned int cv)
+{
+	const bool is_dbl = sizeof(T) == 8;
+	const bool bg = NABG && nabg;
+	const bool is_min = a.opcode == SVT_OP_MIN;
+	const bool narm = a.na_rm != 0;
+	const bool partial = (int64_t) cv < a.nstrata;
+	bool have = (fl & RF_HAVE) != 0;
+	if (is_dbl) {
+		double m = have ? ordered_to_f64(best) : 0.0, res;
+		if (!narm && ((fl & RF_NA) || (bg && partial))) res = svt_na_real();
+		else if (!narm && (fl & RF_NAN)) res = NAN;
+		else {
+			if (partial && !bg) {
+				m = have ? (is_min ? (0.0 < m ? 0.0 : m) : (0.0 > m ? 0.0 : m)) : 0.0;
+				have = true;
+			}
+			res = have ? m : (is_min ? INFINITY : -INFINITY);   // :956-957
+		}
+		((double *) a.out)[cell] = res;
+	} else {
+		int m = have ? (int) ((long long) best - 0x80000000LL) : 0, res;
+		if (!narm && ((fl & RF_NA) || (bg && partial))) res = NA_INT;
+		else {
+			if (partial && !bg) {
+				m = have ? (is_min ? (0 < m ? 0 : m) : (0 > m ? 0 : m)) : 0;
+				have = true;
+			}
+			if (have) res = m;
+			else { res = NA_INT; if (a.warn_flag) *a.warn_flag = 1; }
+		}
+		((int *) a.out)[cell] = res;
+	}
+}
+
+// Memory-atomic route (more than 65535 output columns; never a NaArray operand: the entry point has refused it): the
+// cells are `out` itself, for min / max the scratch.
 __global__ void rowstats_init_kernel(RowStatsArgs a)
 {
 	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= a.out_len)
 		return;
-	switch (a.opcode) {
-	case SVT_OP_ANYNA:
-		((int *) a.out)[i] = 0;
-		break;
-	case SVT_OP_COUNTNAS: case SVT_OP_SUM:
-		((double *) a.out)[i] = 0.0;
-		break;
-	case SVT_OP_CENTERED_X2_SUM: {   // :1044-1066
-		const double c = a.center ? a.center[i] : 0.0;
-		((double *) a.out)[i] = a.center ? c * c * (double) a.nstrata : 0.0;
-		break;
-	}
-	default: {
-		MinMaxScratch s = split_scratch(a.scratch, a.out_len);
-		s.best[i] = a.opcode == SVT_OP_MIN ? ~0ULL : 0ULL;
-		s.flags[i] = 0;
-		s.cov[i] = 0;
-	}
-	}
+	const bool minmax = a.opcode == SVT_OP_MIN || a.opcode == SVT_OP_MAX;
+	MinMaxScratch ms = split_scratch(a.scratch, a.out_len);
+	rowstats_init_cell<false>(a, false, true, i, i, minmax ? (void *) ms.best : a.out, (double *) NULL, ms.flags, ms.cov);
 }
 
 template <typename T>
@@ -84,54 +190,12 @@ rowstats_scatter_kernel(RowStatsArgs a)
 	const int32_t *__restrict__ row = a.row_idx;
 	const int64_t beg = a.col_ptr[j], end = a.col_ptr[j + 1];
 	const int64_t base = (j % a.inner) * a.nrow;
-	const bool is_dbl = sizeof(T) == 8;
-	const bool narm = a.na_rm != 0;
-	const double NAr = svt_na_real();
+	const bool minmax = a.opcode == SVT_OP_MIN || a.opcode == SVT_OP_MAX;
 	MinMaxScratch ms = split_scratch(a.scratch, a.out_len);
+	void *acc = minmax ? (void *) ms.best : a.out;
 
-	for (int64_t k = beg + lane; k < end; k += SVT_WAVE) {
-		const T v = val[k];
-		const int64_t i = base + row[k];
-		const bool miss = is_dbl ? (v != v) : ((int) v == NA_INT);
-		const bool isna = is_dbl ? svt_is_na((double) v) : miss;
-		switch (a.opcode) {
-		case SVT_OP_ANYNA:       // :498-514
-			if (miss) ((int *) a.out)[i] = 1;
-			break;
-		case SVT_OP_COUNTNAS:    // :516-535
-			if (miss) atomicAdd((double *) a.out + i, 1.0);
-			break;
-		case SVT_OP_SUM: {       // :599-634 with :412-433
-			if (miss && narm) break;
-			const double x = (!is_dbl && miss) ? NAr : (double) v;
-			atomicAdd((double *) a.out + i, x);
-			break;
-		}
-		case SVT_OP_CENTERED_X2_SUM: {   // :636-696
-			const double c = a.center ? a.center[i] : 0.0;
-			if (miss && narm) {
-				atomicAdd((double *) a.out + i, -(c * c));
-				break;
-			}
-			const double x = (!is_dbl && miss) ? NAr : (double) v;
-			atomicAdd((double *) a.out + i, x * (x - 2 * c));
-			break;
-		}
-		default: {               // min / max, :537-597
-			atomicAdd(ms.cov + i, 1u);
-			if (miss) {
-				atomicOr(ms.flags + i, isna ? RF_NA : RF_NAN);
-				break;
-			}
-			atomicOr(ms.flags + i, RF_HAVE);
-			unsigned long long key = is_dbl ?
-				f64_to_ordered((double) v) :
-				(unsigned long long) ((long long) (int) v + 0x80000000LL);
-			if (a.opcode == SVT_OP_MIN) atomicMin(ms.best + i, key);
-			else atomicMax(ms.best + i, key);
-		}
-		}
-	}
+	for (int64_t k = beg + lane; k < end; k += SVT_WAVE)
+		rowstats_update<T, false>(a.opcode, a.na_rm != 0, false, val[k], base + row[k], acc, a.center, ms.flags, ms.cov);
 }
 
 template <typename T>
@@ -141,39 +205,7 @@ __global__ void rowstats_minmax_finish_kernel(RowStatsArgs a)
 	if (i >= a.out_len)
 		return;
 	MinMaxScratch ms = split_scratch(a.scratch, a.out_len);
-	const bool is_dbl = sizeof(T) == 8;
-	const bool is_min = a.opcode == SVT_OP_MIN;
-	const bool narm = a.na_rm != 0;
-	const int fl = ms.flags[i];
-	const bool partial = (int64_t) ms.cov[i] < a.nstrata;   // implicit zeros
-	bool have = (fl & RF_HAVE) != 0;
-	if (is_dbl) {
-		double m = have ? ordered_to_f64(ms.best[i]) : 0.0;
-		double r;
-		if (!narm && (fl & RF_NA)) r = svt_na_real();
-		else if (!narm && (fl & RF_NAN)) r = NAN;
-		else {
-			if (partial) {
-				m = have ? (is_min ? (0.0 < m ? 0.0 : m) : (0.0 > m ? 0.0 : m)) : 0.0;
-				have = true;
-			}
-			r = have ? m : (is_min ? INFINITY : -INFINITY);   // :956-957
-		}
-		((double *) a.out)[i] = r;
-	} else {
-		int m = have ? (int) ((long long) ms.best[i] - 0x80000000LL) : 0;
-		int r;
-		if (!narm && (fl & RF_NA)) r = NA_INT;
-		else {
-			if (partial) {
-				m = have ? (is_min ? (0 < m ? 0 : m) : (0 > m ? 0 : m)) : 0;
-				have = true;
-			}
-			if (have) r = m;
-			else { r = NA_INT; if (a.warn_flag) *a.warn_flag = 1; }   // :930-931
-		}
-		((int *) a.out)[i] = r;
-	}
+	rowstats_minmax_finish<T, false>(a, false, i, ms.best[i], ms.flags[i], ms.cov[i]);
 }
 
 // --------------------------------------------------------------------------
@@ -234,27 +266,33 @@ rowpanel_table_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__rest
 		pt[q * ncol + j] = (int32_t) (end - beg);
 }
 
-// Same table, 16 leaves per workgroup (a wavefront each): the entries are collected in LDS
-// and every table row gets one 64-byte run instead of 16 scattered 4-byte stores (the
-// scattered form spends 222 us of a 0.65 ms rowSums at BASELINE config 2 on write
-// amplification).  LDS: (npan + 1) * 64 bytes.
+// Same table through an LDS image: a workgroup of 1024 lanes takes SLOTS leaf slots of LANES lanes each, collects
+// the entries in LDS and stores every table row as one run.  Two shapes:
+//   64 lanes x 16 slots, 8 loads in flight: every table row gets one 64-byte run instead of 16 scattered 4-byte
+//     stores (the scattered form spends 222 us of a 0.65 ms rowSums at BASELINE config 2 on write amplification).
+//   16 lanes x 64 slots, 4 loads in flight, for SHORT leaves (mean < 256 offsets: the 1.28e6 leaves of ~100 offsets
+//     of BASELINE config 5): a wavefront per leaf leaves three quarters of its lanes idle and its table rows leave
+//     in 64-byte pieces (0.45 ms of a 1.12 ms rowSums(dims = 2) at config 5); here a row of the LDS image is 256 bytes.
+// LDS: (npan + 1) * (SLOTS / S) * 4 bytes.
 #define PT_LEAVES 16
 #define PT_U 8                  // loads of 64 offsets a wavefront keeps in flight (4: 157 us for the pass at config 3, 8: see DESIGN.md)
+#define PTS_LEAVES 64
+#define PTS_U 4
 // SCAN (the sparse x sparse product, kernels_spmm.hip): the pass also looks at the VALUES of the leaves it walks
 // -- all of them (skip == NULL) or those with skip[j] == 0 -- and raises *flag at a NaN / Inf / NA (doubles) or an
 // NA_integer_ (ints): one stream over the operand instead of two.  SCAN: 0 none, 1 doubles, 2 ints.
-// S wavefronts share a leaf (each a contiguous S-th of its offsets; a workgroup then holds 16 / S leaves): leaves
+// S slots share a leaf (each a contiguous S-th of its offsets; a workgroup then holds SLOTS / S leaves): leaves
 // are the unit the chip is filled with, and 1e4 long leaves on 8192 wavefront slots are two rounds of which the
 // second is a quarter full (BASELINE config 2/3: 101 us; in quarters 5 rounds of a quarter the length).
-template <int SCAN, int S>
-__global__ void __launch_bounds__(PT_LEAVES * 64)
-rowpanel_table16_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx,
-			int64_t ncol, int64_t npan, int ps, int32_t *__restrict__ pt,
-			const void *__restrict__ val, const uint8_t *__restrict__ skip, int *__restrict__ flag)
+template <int SCAN, int LANES, int SLOTS, int U, int S>
+__global__ void __launch_bounds__(LANES * SLOTS)
+rowpanel_table_lds_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx,
+			  int64_t ncol, int64_t npan, int ps, int32_t *__restrict__ pt,
+			  const void *__restrict__ val, const uint8_t *__restrict__ skip, int *__restrict__ flag)
 {
 	extern __shared__ int32_t tab[];            // [npan + 1][L]
-	constexpr int L = PT_LEAVES / S;
-	const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	constexpr int NT = LANES * SLOTS, L = SLOTS / S;
+	const int w = threadIdx.x / LANES, lane = threadIdx.x % LANES;
 	const int wl = w / S, sg = w % S;           // leaf of the workgroup, segment of the leaf
 	const int64_t j0 = (int64_t) blockIdx.x * L, j = j0 + wl;
 	// (with a map of the leaves the product will ask for -- svt %*% svt2, skip[j] != 0 -- the others need no run bounds:
@@ -263,20 +301,20 @@ rowpanel_table16_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__re
 		const int64_t beg = col_ptr[j], end = col_ptr[j + 1];
 		const int64_t sb = beg + (end - beg) * sg / S, se = beg + (end - beg) * (sg + 1) / S;
 		int carry = sb > beg ? row_idx[sb - 1] >> ps : -1;     // panel of the element before this trip
-		for (int64_t k0 = sb; k0 < se; k0 += PT_U * 64) {
-			int32_t r[PT_U];
+		for (int64_t k0 = sb; k0 < se; k0 += U * LANES) {
+			int32_t r[U];
 #pragma unroll
-			for (int u = 0; u < PT_U; u++) {    // PT_U coalesced loads in flight
-				const int64_t k = k0 + u * 64 + lane;
+			for (int u = 0; u < U; u++) {       // U coalesced loads in flight
+				const int64_t k = k0 + u * LANES + lane;
 				r[u] = k < se ? row_idx[k] : 0x7FFFFFFF;
 			}
 #pragma unroll
-			for (int u = 0; u < PT_U; u++) {
-				const int64_t k = k0 + u * 64 + lane;
+			for (int u = 0; u < U; u++) {
+				const int64_t k = k0 + u * LANES + lane;
 				const int p = r[u] >> ps;
-				int prev = __shfl_up(p, 1, 64);
+				int prev = __shfl_up(p, 1, LANES);
 				if (lane == 0) prev = carry;
-				carry = __shfl(p, 63, 64);
+				carry = __shfl(p, LANES - 1, LANES);
 				if (k < se)
 					for (int q = prev + 1; q <= p; q++)
 						tab[(int64_t) q * L + wl] = (int32_t) (k - beg);
@@ -284,7 +322,7 @@ rowpanel_table16_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__re
 		}
 		if (sg == S - 1) {
 			const int64_t pl = end > beg ? row_idx[end - 1] >> ps : -1;
-			for (int64_t q = pl + 1 + lane; q <= npan; q += 64)
+			for (int64_t q = pl + 1 + lane; q <= npan; q += LANES)
 				tab[q * L + wl] = (int32_t) (end - beg);
 		}
 	}
@@ -296,129 +334,46 @@ rowpanel_table16_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__re
 			if (skip != NULL && skip[j0 + l] != 0)
 				continue;
 			const int64_t b = col_ptr[j0 + l], e = col_ptr[j0 + l + 1];
-			for (int64_t k = b + threadIdx.x; k < e; k += 4 * PT_LEAVES * 64) {
+			for (int64_t k = b + threadIdx.x; k < e; k += 4 * NT) {
 				if (SCAN == 1) {
 					double x[4];
 #pragma unroll
 					for (int u = 0; u < 4; u++)
-						x[u] = k + u * PT_LEAVES * 64 < e ? ((const double *) val)[k + u * PT_LEAVES * 64] : 0.0;
+						x[u] = k + u * NT < e ? ((const double *) val)[k + u * NT] : 0.0;
 #pragma unroll
 					for (int u = 0; u < 4; u++) bad |= !(fabs(x[u]) <= 1.7976931348623157e308);
 				} else {
 #pragma unroll
 					for (int u = 0; u < 4; u++)
-						bad |= k + u * PT_LEAVES * 64 < e && ((const int *) val)[k + u * PT_LEAVES * 64] == NA_INT;
+						bad |= k + u * NT < e && ((const int *) val)[k + u * NT] == NA_INT;
 				}
 			}
 		}
-		if (__ballot(bad) != 0 && lane == 0) *flag = 1;
+		if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) *flag = 1;
 	}
 	__syncthreads();
 	const int64_t n = (npan + 1) * L;
-	for (int64_t t = threadIdx.x; t < n; t += PT_LEAVES * 64) {
+	for (int64_t t = threadIdx.x; t < n; t += NT) {
 		const int64_t q = t / L, l = t % L;
 		if (j0 + l < ncol && (skip == NULL || skip[j0 + l] != 0))
 			pt[q * ncol + j0 + l] = tab[t];
 	}
 }
 
-// G = lanes that share one leaf segment (power of two <= 64): the host picks
-// it from the mean segment length so that short segments still fill the wave.
-template <typename T>
-__global__ void __launch_bounds__(ROWPANEL_NT)
-rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t npan, int G, int ps)
+// The walk of the LDS routes: the workgroup's lanes form groups of G (a power of two <= 64: the host picks it from
+// the mean segment length so that short segments still fill the wave); a group takes the segments of strata
+// s_lo + its rank, + the number of groups, ... below s_hi.  seg(s, kb, ke): the nonzeros [kb, ke) of stratum s that
+// belong to the workgroup (a run of the table, or a whole leaf); apply(v, r): the nonzero v at row r0 + r.
+// RS_U leaf segments per lane group at a time, their loads in flight together (one segment
+// after the other leaves a wavefront with a single load pair outstanding: 2.1 TB/s at
+// BASELINE config 2); the next round's bounds are fetched a round ahead.
+#define RS_U 4
+template <typename T, typename Seg, typename Apply>
+__device__ __forceinline__ void rowstats_walk(const T *__restrict__ val, const int32_t *__restrict__ row,
+					      const int64_t r0, const int64_t s_lo, const int64_t s_hi, const int G,
+					      Seg seg, Apply apply)
 {
-	extern __shared__ unsigned long long lds64[];   // 1 << ps cells
-	const int64_t q = blockIdx.x, i = blockIdx.y;
-	const int tid = threadIdx.x, NT = blockDim.x;
-	const int prow = 1 << ps;
-	const int64_t r0 = q * prow;
-	const int np = (int) (a.nrow - r0 < prow ? a.nrow - r0 : prow);   // rows in this panel
-	// strata range of this workgroup (gridDim.z > 1: sum-like operations only, `out` zeroed)
-	const bool split = gridDim.z > 1;
-	const int64_t s_chunk = (a.nstrata + gridDim.z - 1) / gridDim.z;
-	const int64_t s_lo = (int64_t) blockIdx.z * s_chunk;
-	const int64_t s_hi = s_lo + s_chunk < a.nstrata ? s_lo + s_chunk : a.nstrata;
-	const int64_t cell0 = i * a.nrow + r0;
-	const bool is_dbl = sizeof(T) == 8;
-	const bool narm = a.na_rm != 0;
-	const int oc = a.opcode;
-	const bool is_minmax = oc == SVT_OP_MIN || oc == SVT_OP_MAX;
-	double *accd = (double *) lds64;
-	double *cen = accd + prow;                           // centered_X2_sum only
-	int *flg = (int *) (lds64 + prow);                   // min/max only
-	unsigned int *cov = (unsigned int *) (flg + prow);
-	const T *__restrict__ val = (const T *) a.val;
-	const int32_t *__restrict__ row = a.row_idx;
-	const double NAr = svt_na_real();
-	// NaArray (a.na_bg): cells covered fewer than nstrata times hold implicit NAs:
-	//   countNAs / anyNA: count the stored non-NA values, result nstrata - count (!= 0)
-	//   sum, na.rm=FALSE: NA_real_ wherever the coverage is short (:612-634)
-	//   min / max: the NA background joins instead of the implicit zero (:914-961)
-	const bool nabg = a.na_bg != 0;
-
-	for (int r = tid; r < np; r += NT) {
-		if (is_minmax) {
-			lds64[r] = oc == SVT_OP_MIN ? ~0ULL : 0ULL;
-			flg[r] = 0;
-			cov[r] = 0;
-		} else if (oc == SVT_OP_CENTERED_X2_SUM) {
-			const double c = a.center ? a.center[cell0 + r] : 0.0;
-			cen[r] = c;
-			accd[r] = a.center && blockIdx.z == 0 ? c * c * (double) a.nstrata : 0.0;
-		} else if (oc == SVT_OP_ANYNA && !nabg) {
-			((int *) lds64)[r] = 0;
-		} else {
-			accd[r] = 0.0;
-			if (nabg) cov[r] = 0;
-		}
-	}
-	__syncthreads();
-	const int sub = tid / G, sl = tid % G, nsub = NT / G;
-	const int32_t *__restrict__ pt0 = pt + q * a.ncol, *__restrict__ pt1 = pt0 + a.ncol;
-	// one nonzero into its cell
-	auto apply = [&](const T v, const int r) {
-		const bool miss = is_dbl ? (v != v) : ((int) v == NA_INT);
-		switch (oc) {
-		case SVT_OP_ANYNA:
-			if (nabg) { if (!miss) atomicAdd(accd + r, 1.0); }
-			else if (miss) ((int *) lds64)[r] = 1;
-			break;
-		case SVT_OP_COUNTNAS:
-			if (nabg ? !miss : miss) atomicAdd(accd + r, 1.0);
-			break;
-		case SVT_OP_SUM:
-			if (nabg && !narm) atomicAdd(cov + r, 1u);
-			if (miss && narm) break;
-			atomicAdd(accd + r, (!is_dbl && miss) ? NAr : (double) v);
-			break;
-		case SVT_OP_CENTERED_X2_SUM: {
-			const double c = cen[r];
-			if (miss && narm) { atomicAdd(accd + r, -(c * c)); break; }
-			const double x = (!is_dbl && miss) ? NAr : (double) v;
-			atomicAdd(accd + r, x * (x - 2 * c));
-			break;
-		}
-		default: {
-			atomicAdd(cov + r, 1u);
-			if (miss) {
-				const bool isna = is_dbl ? svt_is_na((double) v) : true;
-				atomicOr(flg + r, isna ? RF_NA : RF_NAN);
-				break;
-			}
-			atomicOr(flg + r, RF_HAVE);
-			const unsigned long long key = is_dbl ?
-				f64_to_ordered((double) v) :
-				(unsigned long long) ((long long) (int) v + 0x80000000LL);
-			if (oc == SVT_OP_MIN) atomicMin(lds64 + r, key);
-			else atomicMax(lds64 + r, key);
-		}
-		}
-	};
-	// RS_U leaf segments per lane group at a time, their loads in flight together (one segment
-	// after the other leaves a wavefront with a single load pair outstanding: 2.1 TB/s at
-	// BASELINE config 2); the next round's bounds are fetched a round ahead.
-	constexpr int RS_U = 4;
+	const int sub = threadIdx.x / G, sl = threadIdx.x % G, nsub = blockDim.x / G;
 	int64_t nb[RS_U], ne[RS_U];
 	auto bounds = [&](const int64_t s0) {
 #pragma unroll
@@ -426,9 +381,8 @@ rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t np
 			const int64_t s = s0 + (int64_t) u * nsub;
 			nb[u] = ne[u] = 0;
 			if (s < s_hi) {
-				const int64_t j = i + s * a.inner;
-				const int64_t base = a.col_ptr[j];
-				nb[u] = base + pt0[j] + sl; ne[u] = base + pt1[j];
+				seg(s, nb[u], ne[u]);
+				nb[u] += sl;
 			}
 		}
 	};
@@ -456,6 +410,44 @@ rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t np
 				}
 		}
 	}
+}
+
+template <typename T>
+__global__ void __launch_bounds__(ROWPANEL_NT)
+rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t npan, int G, int ps)
+{
+	extern __shared__ unsigned long long lds64[];   // 1 << ps cells
+	const int64_t q = blockIdx.x, i = blockIdx.y;
+	const int tid = threadIdx.x, NT = blockDim.x;
+	const int prow = 1 << ps;
+	const int64_t r0 = q * prow;
+	const int np = (int) (a.nrow - r0 < prow ? a.nrow - r0 : prow);   // rows in this panel
+	// strata range of this workgroup (gridDim.z > 1: sum-like operations only, `out` zeroed)
+	const bool split = gridDim.z > 1;
+	const int64_t s_chunk = (a.nstrata + gridDim.z - 1) / gridDim.z;
+	const int64_t s_lo = (int64_t) blockIdx.z * s_chunk;
+	const int64_t s_hi = s_lo + s_chunk < a.nstrata ? s_lo + s_chunk : a.nstrata;
+	const int64_t cell0 = i * a.nrow + r0;
+	const bool narm = a.na_rm != 0;
+	const int oc = a.opcode;
+	const bool is_minmax = oc == SVT_OP_MIN || oc == SVT_OP_MAX;
+	double *accd = (double *) lds64;
+	double *cen = accd + prow;                           // centered_X2_sum only
+	int *flg = (int *) (lds64 + prow);                   // min/max only
+	unsigned int *cov = (unsigned int *) (flg + prow);
+	const bool nabg = a.na_bg != 0;
+
+	for (int r = tid; r < np; r += NT)
+		rowstats_init_cell<true>(a, nabg, blockIdx.z == 0, cell0 + r, r, lds64, cen, flg, cov);
+	__syncthreads();
+	const int32_t *__restrict__ pt0 = pt + q * a.ncol, *__restrict__ pt1 = pt0 + a.ncol;
+	rowstats_walk((const T *) a.val, a.row_idx, r0, s_lo, s_hi, G,
+		[&](const int64_t s, int64_t &kb, int64_t &ke) {
+			const int64_t j = i + s * a.inner;
+			const int64_t base = a.col_ptr[j];
+			kb = base + pt0[j]; ke = base + pt1[j];
+		},
+		[&](const T v, const int r) { rowstats_update<T, true>(oc, narm, nabg, v, r, lds64, cen, flg, cov); });
 	__syncthreads();
 	if (split) {                                 // partial cells of this strata range
 		for (int r = tid; r < np; r += NT) {
@@ -469,50 +461,18 @@ rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t np
 	}
 	for (int r = tid; r < np; r += NT) {
 		const int64_t cell = cell0 + r;
-		if (!is_minmax) {
-			if (nabg && (oc == SVT_OP_ANYNA || oc == SVT_OP_COUNTNAS)) {
-				const double nas = (double) a.nstrata - accd[r];
-				if (oc == SVT_OP_ANYNA) ((int *) a.out)[cell] = nas != 0.0;
-				else ((double *) a.out)[cell] = nas;
-			} else if (oc == SVT_OP_ANYNA) {
-				((int *) a.out)[cell] = ((int *) lds64)[r];
-			} else if (nabg && oc == SVT_OP_SUM && !narm && (int64_t) cov[r] < a.nstrata) {
-				((double *) a.out)[cell] = NAr;
-			} else {
-				((double *) a.out)[cell] = accd[r];
-			}
-			continue;
-		}
-		// NA > NaN > extremum; the implicit zero joins when the cell was
-		// covered fewer than nstrata times (:914-961)
-		const bool is_min = oc == SVT_OP_MIN;
-		const int fl = flg[r];
-		const bool partial = (int64_t) cov[r] < a.nstrata;
-		bool have = (fl & RF_HAVE) != 0;
-		if (is_dbl) {
-			double m = have ? ordered_to_f64(lds64[r]) : 0.0, res;
-			if (!narm && ((fl & RF_NA) || (nabg && partial))) res = NAr;
-			else if (!narm && (fl & RF_NAN)) res = NAN;
-			else {
-				if (partial && !nabg) {
-					m = have ? (is_min ? (0.0 < m ? 0.0 : m) : (0.0 > m ? 0.0 : m)) : 0.0;
-					have = true;
-				}
-				res = have ? m : (is_min ? INFINITY : -INFINITY);
-			}
-			((double *) a.out)[cell] = res;
+		if (is_minmax) {
+			rowstats_minmax_finish<T, true>(a, nabg, cell, lds64[r], flg[r], cov[r]);
+		} else if (nabg && (oc == SVT_OP_ANYNA || oc == SVT_OP_COUNTNAS)) {
+			const double nas = (double) a.nstrata - accd[r];
+			if (oc == SVT_OP_ANYNA) ((int *) a.out)[cell] = nas != 0.0;
+			else ((double *) a.out)[cell] = nas;
+		} else if (oc == SVT_OP_ANYNA) {
+			((int *) a.out)[cell] = ((int *) lds64)[r];
+		} else if (nabg && oc == SVT_OP_SUM && !narm && (int64_t) cov[r] < a.nstrata) {
+			((double *) a.out)[cell] = svt_na_real();
 		} else {
-			int m = have ? (int) ((long long) lds64[r] - 0x80000000LL) : 0, res;
-			if (!narm && ((fl & RF_NA) || (nabg && partial))) res = NA_INT;
-			else {
-				if (partial && !nabg) {
-					m = have ? (is_min ? (0 < m ? 0 : m) : (0 > m ? 0 : m)) : 0;
-					have = true;
-				}
-				if (have) res = m;
-				else { res = NA_INT; if (a.warn_flag) *a.warn_flag = 1; }
-			}
-			((int *) a.out)[cell] = res;
+			((double *) a.out)[cell] = accd[r];
 		}
 	}
 }
@@ -530,79 +490,22 @@ rowstats_whole_kernel(RowStatsArgs a, int G)
 	const int64_t i = blockIdx.x;
 	const int tid = threadIdx.x, NT = blockDim.x;
 	const int np = (int) a.nrow;
-	const bool is_dbl = sizeof(T) == 8;
 	const bool narm = a.na_rm != 0;
 	const int oc = a.opcode;
 	double *accd = (double *) lds64;
 	double *cen = accd + np;                             // centered_X2_sum only
-	const T *__restrict__ val = (const T *) a.val;
-	const int32_t *__restrict__ row = a.row_idx;
-	const double NAr = svt_na_real();
 	const int64_t cell0 = i * a.nrow;
-	for (int r = tid; r < np; r += NT) {
-		if (oc == SVT_OP_CENTERED_X2_SUM) {
-			const double c = a.center ? a.center[cell0 + r] : 0.0;
-			cen[r] = c;
-			accd[r] = a.center ? c * c * (double) a.nstrata : 0.0;
-		} else if (oc == SVT_OP_ANYNA) {
-			((int *) lds64)[r] = 0;
-		} else {
-			accd[r] = 0.0;
-		}
-	}
+	for (int r = tid; r < np; r += NT)
+		rowstats_init_cell<false>(a, false, true, cell0 + r, r, lds64, cen, (int *) NULL, (unsigned int *) NULL);
 	__syncthreads();
-	auto apply = [&](const T v, const int r) {
-		const bool miss = is_dbl ? (v != v) : ((int) v == NA_INT);
-		switch (oc) {
-		case SVT_OP_ANYNA:
-			if (miss) ((int *) lds64)[r] = 1;
-			break;
-		case SVT_OP_COUNTNAS:
-			if (miss) atomicAdd(accd + r, 1.0);
-			break;
-		case SVT_OP_SUM:
-			if (miss && narm) break;
-			atomicAdd(accd + r, (!is_dbl && miss) ? NAr : (double) v);
-			break;
-		default: {                                   // centered_X2_sum
-			const double c = cen[r];
-			if (miss && narm) { atomicAdd(accd + r, -(c * c)); break; }
-			const double x = (!is_dbl && miss) ? NAr : (double) v;
-			atomicAdd(accd + r, x * (x - 2 * c));
-		}
-		}
-	};
-	// four leaves per lane group at a time (see rowstats_panel_kernel)
-	constexpr int RS_U = 4;
-	const int sub = tid / G, sl = tid % G, nsub = NT / G;
-	for (int64_t s0 = sub; s0 < a.nstrata; s0 += (int64_t) nsub * RS_U) {
-		int64_t kb[RS_U], ke[RS_U];
-#pragma unroll
-		for (int u = 0; u < RS_U; u++) {
-			const int64_t s = s0 + (int64_t) u * nsub;
-			kb[u] = ke[u] = 0;
-			if (s < a.nstrata) {
-				const int64_t j = i + s * a.inner;
-				kb[u] = a.col_ptr[j] + sl; ke[u] = a.col_ptr[j + 1];
-			}
-		}
-		bool more = true;
-		while (more) {
-			T v[RS_U];
-			int r[RS_U];
-#pragma unroll
-			for (int u = 0; u < RS_U; u++)
-				if (kb[u] < ke[u]) { v[u] = val[kb[u]]; r[u] = (int) row[kb[u]]; }
-			more = false;
-#pragma unroll
-			for (int u = 0; u < RS_U; u++)
-				if (kb[u] < ke[u]) {
-					apply(v[u], r[u]);
-					kb[u] += G;
-					more |= kb[u] < ke[u];
-				}
-		}
-	}
+	rowstats_walk((const T *) a.val, a.row_idx, 0, 0, a.nstrata, G,
+		[&](const int64_t s, int64_t &kb, int64_t &ke) {
+			const int64_t j = i + s * a.inner;
+			kb = a.col_ptr[j]; ke = a.col_ptr[j + 1];
+		},
+		[&](const T v, const int r) {
+			rowstats_update<T, false>(oc, narm, false, v, r, lds64, cen, (int *) NULL, (unsigned int *) NULL);
+		});
 	__syncthreads();
 	for (int r = tid; r < np; r += NT) {
 		if (oc == SVT_OP_ANYNA) ((int *) a.out)[cell0 + r] = ((int *) lds64)[r];
@@ -627,20 +530,14 @@ rowstats_whole_pipe_kernel(RowStatsArgs a, int64_t nchunks)
 	constexpr int U = 4, TT = 2;                    // leaves per wavefront, trips of 64 lanes fetched ahead
 	const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, w = tid >> 6, nw = NT >> 6;
 	const int np = (int) a.nrow;
-	const bool is_dbl = sizeof(T) == 8;
 	const bool narm = a.na_rm != 0;
-	const int oc = a.opcode;
 	double *accd = (double *) lds64;
 	const T *__restrict__ val = (const T *) a.val;
 	const int32_t *__restrict__ row = a.row_idx;
-	const double NAr = svt_na_real();
+	// (sums and NA counts only: the rule's other operations fold away)
+	const int oc = a.opcode == SVT_OP_COUNTNAS ? SVT_OP_COUNTNAS : SVT_OP_SUM;
 	auto apply = [&](const T v, const int r) {
-		const bool miss = is_dbl ? (v != v) : ((int) v == NA_INT);
-		if (oc == SVT_OP_COUNTNAS) {
-			if (miss) atomicAdd(accd + r, 1.0);
-		} else if (!(miss && narm)) {
-			atomicAdd(accd + r, (!is_dbl && miss) ? NAr : (double) v);
-		}
+		rowstats_update<T, false>(oc, narm, false, v, r, lds64, (const double *) NULL, (int *) NULL, (unsigned int *) NULL);
 	};
 	int64_t kb[U], ke[U];
 	T v[U][TT];
@@ -694,53 +591,7 @@ rowstats_whole_pipe_kernel(RowStatsArgs a, int64_t nchunks)
 	}
 }
 
-// The same table for SHORT leaves (mean < 256 offsets: the 1.28e6 leaves of ~100 offsets of BASELINE config 5): 16 lanes per
-// leaf, 64 leaves per workgroup -- a wavefront per leaf leaves three quarters of its lanes idle and its table rows leave in
-// 64-byte pieces (0.45 ms of a 1.12 ms rowSums(dims = 2) at config 5); here a row of the LDS image is 256 bytes.
-#define PTS_LEAVES 64
-__global__ void __launch_bounds__(1024)
-rowpanel_table_short_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx,
-			    int64_t ncol, int64_t npan, int ps, int32_t *__restrict__ pt)
-{
-	extern __shared__ int32_t tab[];            // [npan + 1][PTS_LEAVES]
-	const int g = threadIdx.x >> 4, sl = threadIdx.x & 15;
-	const int64_t j0 = (int64_t) blockIdx.x * PTS_LEAVES, j = j0 + g;
-	if (j < ncol) {
-		const int64_t beg = col_ptr[j], end = col_ptr[j + 1];
-		int carry = -1;                         // panel of the element before this trip
-		for (int64_t k0 = beg; k0 < end; k0 += 4 * 16) {
-			int32_t r[4];
-#pragma unroll
-			for (int u = 0; u < 4; u++) {
-				const int64_t k = k0 + u * 16 + sl;
-				r[u] = k < end ? row_idx[k] : 0x7FFFFFFF;
-			}
-#pragma unroll
-			for (int u = 0; u < 4; u++) {
-				const int64_t k = k0 + u * 16 + sl;
-				const int p = r[u] >> ps;
-				int prev = __shfl_up(p, 1, 16);
-				if (sl == 0) prev = carry;
-				carry = __shfl(p, 15, 16);
-				if (k < end)
-					for (int q = prev + 1; q <= p; q++)
-						tab[q * PTS_LEAVES + g] = (int32_t) (k - beg);
-			}
-		}
-		const int64_t pl = end > beg ? row_idx[end - 1] >> ps : -1;
-		for (int64_t q = pl + 1 + sl; q <= npan; q += 16)
-			tab[q * PTS_LEAVES + g] = (int32_t) (end - beg);
-	}
-	__syncthreads();
-	const int64_t n = (npan + 1) * PTS_LEAVES;
-	for (int64_t t = threadIdx.x; t < n; t += 1024) {
-		const int64_t q = t / PTS_LEAVES, l = t % PTS_LEAVES;
-		if (j0 + l < ncol)
-			pt[q * ncol + j0 + l] = tab[t];
-	}
-}
-
-// wavefronts per leaf of rowpanel_table16_kernel: the split (1, 2 or 4) with the fewest leaf-times of rounds on 8192
+// wavefronts per leaf of the 64-lane table form: the split (1, 2 or 4) with the fewest leaf-times of rounds on 8192
 // wavefront slots; short leaves are not split
 static int rowpanel_split(int64_t ncol, int64_t nnz_hint)
 {
@@ -762,17 +613,11 @@ static void launch_table16(const int64_t *col_ptr, const int32_t *row_idx, int64
 {
 	const int sp = rowpanel_split(ncol, nnz_hint);
 	const int L = PT_LEAVES / sp;
-	const dim3 grid((unsigned) ((ncol + L - 1) / L));
-	const size_t lds = (size_t) (npan + 1) * L * 4;
-	if (sp == 4)
-		hipLaunchKernelGGL((rowpanel_table16_kernel<SCAN, 4>), grid, dim3(PT_LEAVES * 64), lds, s, col_ptr, row_idx,
-				   ncol, npan, ps, pt, val, skip, flag);
-	else if (sp == 2)
-		hipLaunchKernelGGL((rowpanel_table16_kernel<SCAN, 2>), grid, dim3(PT_LEAVES * 64), lds, s, col_ptr, row_idx,
-				   ncol, npan, ps, pt, val, skip, flag);
-	else
-		hipLaunchKernelGGL((rowpanel_table16_kernel<SCAN, 1>), grid, dim3(PT_LEAVES * 64), lds, s, col_ptr, row_idx,
-				   ncol, npan, ps, pt, val, skip, flag);
+	auto kernel = sp == 4 ? rowpanel_table_lds_kernel<SCAN, 64, PT_LEAVES, PT_U, 4> :
+		      sp == 2 ? rowpanel_table_lds_kernel<SCAN, 64, PT_LEAVES, PT_U, 2> :
+				rowpanel_table_lds_kernel<SCAN, 64, PT_LEAVES, PT_U, 1>;
+	hipLaunchKernelGGL(kernel, dim3((unsigned) ((ncol + L - 1) / L)), dim3(PT_LEAVES * 64), (size_t) (npan + 1) * L * 4, s,
+			   col_ptr, row_idx, ncol, npan, ps, pt, val, skip, flag);
 }
 
 // pt[q * ncol + j] = number of offsets of leaf j below q << ps, q = 0 .. npan ((npan + 1) * ncol entries)
@@ -780,8 +625,10 @@ void launch_rowpanel_table(const int64_t *col_ptr, const int32_t *row_idx, int64
 			   int64_t npan, int ps, int32_t *pt, hipStream_t s)
 {
 	if (ncol > 0 && nnz_hint / ncol < 256 && (size_t) (npan + 1) * PTS_LEAVES * 4 <= 64 * 1024) {
-		hipLaunchKernelGGL(rowpanel_table_short_kernel, dim3((unsigned) ((ncol + PTS_LEAVES - 1) / PTS_LEAVES)), dim3(1024),
-				   (size_t) (npan + 1) * PTS_LEAVES * 4, s, col_ptr, row_idx, ncol, npan, ps, pt);
+		hipLaunchKernelGGL((rowpanel_table_lds_kernel<0, 16, PTS_LEAVES, PTS_U, 1>),
+				   dim3((unsigned) ((ncol + PTS_LEAVES - 1) / PTS_LEAVES)), dim3(16 * PTS_LEAVES),
+				   (size_t) (npan + 1) * PTS_LEAVES * 4, s, col_ptr, row_idx, ncol, npan, ps, pt,
+				   (const void *) NULL, (const uint8_t *) NULL, (int *) NULL);
 	} else if (ncol > 0 && (size_t) (npan + 1) * PT_LEAVES * 4 <= 64 * 1024) {
 		launch_table16<0>(col_ptr, row_idx, ncol, nnz_hint, npan, ps, pt, NULL, NULL, NULL, s);
 	} else if (ncol > 0) {                      // very tall arrays: the table rows do not fit LDS
@@ -810,128 +657,144 @@ bool launch_rowpanel_table_scan(const int64_t *col_ptr, const int32_t *row_idx, 
 	return false;
 }
 
+// The form of the LDS routes a shape takes, and what its launch needs.
+enum RowStatsForm {
+	RS_PIPE_UNITS,          // rowstats_whole_pipe_kernel<T, true>
+	RS_PIPE,                // rowstats_whole_pipe_kernel<T, false>
+	RS_WHOLE,               // rowstats_whole_kernel
+	RS_PANEL                // the table of run bounds + rowstats_panel_kernel
+};
+struct RowStatsRoute {
+	RowStatsForm form;
+	int ps;                 // RS_PANEL: panel shift, panels, strata ranges
+	int64_t npan, nsplit;
+	int G;                  // RS_WHOLE, RS_PANEL: lanes per leaf segment
+	int64_t nchunks;        // the pipe forms: chunks of 64 leaves per output column
+	size_t lds;
+};
+
+// lanes per leaf segment ~ mean segment length `seg`
+static int rowstats_lanes(double seg)
+{
+	int G = 64;
+	while (G > 8 && seg <= G / 2) G >>= 1;
+	// long segments: 32 lanes where they waste fewer load slots than 64 (81 nonzeros: three trips of
+	// 32 = 96 slots instead of two of 64 = 128; 0.45 -> 0.39 ms at BASELINE config 2)
+	if (G == 64 && ((int64_t) (seg + 31.0) / 32) * 32 < ((int64_t) (seg + 63.0) / 64) * 64) G = 32;
+	return G;
+}
+
+static RowStatsRoute rowstats_route(const RowStatsArgs &a)
+{
+	RowStatsRoute rt = {};
+	const int oc = a.opcode;
+	const bool sumlike = oc == SVT_OP_SUM || oc == SVT_OP_COUNTNAS || oc == SVT_OP_CENTERED_X2_SUM ||
+		oc == SVT_OP_ANYNA;
+	const bool centered = oc == SVT_OP_CENTERED_X2_SUM;
+	const bool pipe_op = oc == SVT_OP_SUM || oc == SVT_OP_COUNTNAS;
+	const double leaf_len = a.ncol > 0 ? (double) a.nnz_hint / (double) a.ncol : 0.0;
+	const int64_t spu = 4 * (ROWPANEL_NT / 64);           // leaves per unit of the pipe forms
+	rt.nsplit = 1;
+	rt.nchunks = 1;
+	// output columns of MANY short leaves, all rows in LDS (rowSums(x, dims = 1) of an N-d array, a 2-d operand of at most
+	// 20480 rows and short columns): the persistent whole-column kernel over (column, chunk of 64 leaves) units, cells added
+	// to a zeroed `out` when a workgroup's column changes
+	const int64_t nchunks = (a.nstrata + spu - 1) / spu;
+	if (pipe_op && !a.na_bg && a.nnz_hint > 0 && a.nstrata > spu &&
+	    a.nrow > (1 << ROWPANEL_BIG_SHIFT) && (size_t) a.nrow * 8 <= 160 * 1024 && leaf_len <= 112.0 && leaf_len >= 8.0 &&
+	    a.inner * nchunks >= 2048) {
+		rt.form = RS_PIPE_UNITS;
+		rt.nchunks = nchunks;
+		rt.lds = (size_t) a.nrow * 8;
+		return rt;
+	}
+	// many output columns of few short leaves, all rows in LDS: the whole-column kernel
+	const size_t lds_whole = (size_t) a.nrow * (centered ? 16 : 8);
+	if (sumlike && !a.na_bg && a.nnz_hint > 0 && a.inner >= 1024 && a.nrow > (1 << ROWPANEL_BIG_SHIFT) &&
+	    lds_whole <= 160 * 1024 && leaf_len <= 512.0 && a.nstrata * leaf_len <= 65536.0) {
+		const bool pipe = pipe_op && a.nstrata <= spu && leaf_len <= 112.0 && a.inner >= 1024;
+		rt.form = pipe ? RS_PIPE : RS_WHOLE;
+		rt.G = rowstats_lanes(leaf_len);
+		rt.lds = lds_whole;
+		return rt;
+	}
+	rt.form = RS_PANEL;
+	const bool big = sumlike && !a.na_bg && a.nrow >= (2LL << ROWPANEL_BIG_SHIFT);
+	rt.ps = big ? ROWPANEL_BIG_SHIFT : ROWPANEL_SHIFT;
+	const int64_t prow = 1LL << rt.ps;
+	rt.npan = (a.nrow + prow - 1) / prow;
+	// (nnz unknown here: the caller passes it in a.nnz_hint, 0 = assume long segments)
+	rt.G = a.nnz_hint > 0 && a.ncol > 0 ? rowstats_lanes((double) a.nnz_hint / ((double) a.ncol * (double) rt.npan)) : 64;
+	// strata ranges: aim at two workgroups per CU when the panels alone are fewer
+	if (big) {
+		rt.nsplit = (2 * 256 + rt.npan * a.inner / 2) / (rt.npan * a.inner);
+		const int64_t cap = a.nstrata / (4 * (ROWPANEL_NT / rt.G));      // >= 4 segments per lane group
+		if (rt.nsplit > cap) rt.nsplit = cap;
+		if (rt.nsplit > 1024) rt.nsplit = 1024;
+		if (rt.nsplit < 1) rt.nsplit = 1;
+	}
+	rt.lds = sumlike && !a.na_bg ? (size_t) prow * (centered ? 16 : 8) : (size_t) prow * 16;
+	return rt;
+}
+
+// the double or the int instantiation of a row-statistics kernel, ROWPANEL_NT lanes, `lds` bytes of dynamic LDS
+template <typename... P, typename... A>
+static void launch_rowstats_typed(int Rtype, void (*for_double)(P...), void (*for_int)(P...), dim3 grid, size_t lds,
+				  hipStream_t s, A... args)
+{
+	void (*kernel)(P...) = Rtype == SVT_REALSXP ? for_double : for_int;
+	if (lds > 64 * 1024)
+		(void) hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+	hipLaunchKernelGGL(kernel, grid, dim3(ROWPANEL_NT), lds, s, args...);
+}
+
 // `ws`: rowstats_panel_ws_bytes() bytes.
 int launch_rowstats_panel(const RowStatsArgs &a, void *ws, hipStream_t s)
 {
 	if (a.out_len <= 0)
 		return 0;
-	const int oc = a.opcode;
-	const bool sumlike = oc == SVT_OP_SUM || oc == SVT_OP_COUNTNAS || oc == SVT_OP_CENTERED_X2_SUM ||
-		oc == SVT_OP_ANYNA;
-	// output columns of MANY short leaves, all rows in LDS (rowSums(x, dims = 1) of an N-d array, a 2-d operand of at most
-	// 20480 rows and short columns): the persistent whole-column kernel over (column, chunk of 64 leaves) units, cells added
-	// to a zeroed `out` when a workgroup's column changes
-	{
-		const size_t lds_w = (size_t) a.nrow * 8;
-		const double leaf_len = a.ncol > 0 ? (double) a.nnz_hint / (double) a.ncol : 0.0;
-		const int64_t spu = 4 * (ROWPANEL_NT / 64), nchunks = (a.nstrata + spu - 1) / spu;
-		if ((oc == SVT_OP_SUM || oc == SVT_OP_COUNTNAS) && !a.na_bg && a.nnz_hint > 0 && a.nstrata > spu &&
-		    a.nrow > (1 << ROWPANEL_BIG_SHIFT) && lds_w <= 160 * 1024 && leaf_len <= 112.0 && leaf_len >= 8.0 &&
-		    a.inner * nchunks >= 2048) {
-			if (a.table_mode == 1)
-				return 0;                       // (this form needs no table)
-			HIP_TRY(hipMemsetAsync(a.out, 0, (size_t) a.out_len * 8, s));
-			const void *fp = a.Rtype == SVT_REALSXP ? (const void *) rowstats_whole_pipe_kernel<double, true>
-								: (const void *) rowstats_whole_pipe_kernel<int, true>;
-			(void) hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_w);
-			if (a.Rtype == SVT_REALSXP)
-				hipLaunchKernelGGL((rowstats_whole_pipe_kernel<double, true>), dim3(256), dim3(ROWPANEL_NT), lds_w, s, a, nchunks);
-			else
-				hipLaunchKernelGGL((rowstats_whole_pipe_kernel<int, true>), dim3(256), dim3(ROWPANEL_NT), lds_w, s, a, nchunks);
-			HIP_TRY(hipGetLastError());
-			return 0;
-		}
-	}
-	// many output columns of few short leaves, all rows in LDS: the whole-column kernel
-	{
-		const size_t lds_whole = (size_t) a.nrow * (oc == SVT_OP_CENTERED_X2_SUM ? 16 : 8);
-		const double leaf_len = a.ncol > 0 ? (double) a.nnz_hint / (double) a.ncol : 0.0;
-		if (sumlike && !a.na_bg && a.nnz_hint > 0 && a.inner >= 1024 && a.nrow > (1 << ROWPANEL_BIG_SHIFT) &&
-		    lds_whole <= 160 * 1024 && leaf_len <= 512.0 && a.nstrata * leaf_len <= 65536.0) {
-			if (a.table_mode == 1)
-				return 0;                       // (this form needs no table)
-			int G = 64;
-			while (G > 8 && leaf_len <= G / 2) G >>= 1;
-			if (G == 64 && ((int64_t) (leaf_len + 31.0) / 32) * 32 < ((int64_t) (leaf_len + 63.0) / 64) * 64) G = 32;
-			const void *fn = a.Rtype == SVT_REALSXP ? (const void *) rowstats_whole_kernel<double>
-								: (const void *) rowstats_whole_kernel<int>;
-			(void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_whole);
-			if ((oc == SVT_OP_SUM || oc == SVT_OP_COUNTNAS) && a.nstrata <= 4 * (ROWPANEL_NT / 64) && leaf_len <= 112.0 &&
-			    a.inner >= 1024) {
-				const void *fp = a.Rtype == SVT_REALSXP ? (const void *) rowstats_whole_pipe_kernel<double, false>
-									: (const void *) rowstats_whole_pipe_kernel<int, false>;
-				(void) hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_whole);
-				const unsigned ng = (unsigned) (a.inner < 256 ? a.inner : 256);       // one workgroup per CU
-				if (a.Rtype == SVT_REALSXP)
-					hipLaunchKernelGGL((rowstats_whole_pipe_kernel<double, false>), dim3(ng), dim3(ROWPANEL_NT), lds_whole, s, a, (int64_t) 1);
-				else
-					hipLaunchKernelGGL((rowstats_whole_pipe_kernel<int, false>), dim3(ng), dim3(ROWPANEL_NT), lds_whole, s, a, (int64_t) 1);
-				HIP_TRY(hipGetLastError());
-				return 0;
-			}
-			if (a.Rtype == SVT_REALSXP)
-				hipLaunchKernelGGL(rowstats_whole_kernel<double>, dim3((unsigned) a.inner), dim3(ROWPANEL_NT),
-						   lds_whole, s, a, G);
-			else
-				hipLaunchKernelGGL(rowstats_whole_kernel<int>, dim3((unsigned) a.inner), dim3(ROWPANEL_NT),
-						   lds_whole, s, a, G);
-			HIP_TRY(hipGetLastError());
-			return 0;
-		}
-	}
-	const bool big = sumlike && !a.na_bg && a.nrow >= (2LL << ROWPANEL_BIG_SHIFT);
-	const int ps = big ? ROWPANEL_BIG_SHIFT : ROWPANEL_SHIFT;
-	const int64_t prow = 1LL << ps;
-	const int64_t npan = (a.nrow + prow - 1) / prow;
+	const RowStatsRoute rt = rowstats_route(a);
 	int32_t *pt = (int32_t *) ws;
-	if (a.inner > 65535)
-		return svt_set_error("row stats: more than 65535 output columns per panel row");
-	if (a.table_mode != 2)
-		launch_rowpanel_table(a.col_ptr, a.row_idx, a.ncol, a.nnz_hint, npan, ps, pt, s);
-	if (a.table_mode == 1) {
+	if (rt.form == RS_PANEL) {
+		if (a.inner > 65535)
+			return svt_set_error("row stats: more than 65535 output columns per panel row");
+		if (a.table_mode != ROWSTATS_TABLE_READY)
+			launch_rowpanel_table(a.col_ptr, a.row_idx, a.ncol, a.nnz_hint, rt.npan, rt.ps, pt, s);
+	}
+	if (a.table_mode == ROWSTATS_TABLE_ONLY) {      // (the other forms need no table)
 		HIP_TRY(hipGetLastError());
 		return 0;
 	}
-	// lanes per leaf segment ~ mean segment length (nnz unknown here: the
-	// caller passes it in a.nnz_hint, 0 = assume long segments)
-	int G = 64;
-	if (a.nnz_hint > 0 && a.ncol > 0) {
-		const double seg = (double) a.nnz_hint / ((double) a.ncol * (double) npan);
-		while (G > 8 && seg <= G / 2) G >>= 1;
-		// long segments: 32 lanes where they waste fewer load slots than 64 (81 nonzeros: three trips of
-		// 32 = 96 slots instead of two of 64 = 128; 0.45 -> 0.39 ms at BASELINE config 2)
-		if (G == 64 && ((int64_t) (seg + 31.0) / 32) * 32 < ((int64_t) (seg + 63.0) / 64) * 64) G = 32;
+	switch (rt.form) {
+	case RS_PIPE_UNITS:
+		HIP_TRY(hipMemsetAsync(a.out, 0, (size_t) a.out_len * 8, s));
+		launch_rowstats_typed(a.Rtype, rowstats_whole_pipe_kernel<double, true>, rowstats_whole_pipe_kernel<int, true>,
+				      dim3(256), rt.lds, s, a, rt.nchunks);
+		break;
+	case RS_PIPE:
+		launch_rowstats_typed(a.Rtype, rowstats_whole_pipe_kernel<double, false>, rowstats_whole_pipe_kernel<int, false>,
+				      dim3((unsigned) (a.inner < 256 ? a.inner : 256)),       // one workgroup per CU
+				      rt.lds, s, a, rt.nchunks);
+		break;
+	case RS_WHOLE:
+		launch_rowstats_typed(a.Rtype, rowstats_whole_kernel<double>, rowstats_whole_kernel<int>,
+				      dim3((unsigned) a.inner), rt.lds, s, a, rt.G);
+		break;
+	case RS_PANEL:
+		if (rt.nsplit > 1)
+			HIP_TRY(hipMemsetAsync(a.out, 0, (size_t) a.out_len * (a.opcode == SVT_OP_ANYNA ? 4 : 8), s));
+		launch_rowstats_typed(a.Rtype, rowstats_panel_kernel<double>, rowstats_panel_kernel<int>,
+				      dim3((unsigned) rt.npan, (unsigned) a.inner, (unsigned) rt.nsplit), rt.lds, s,
+				      a, (const int32_t *) pt, rt.npan, rt.G, rt.ps);
+		break;
 	}
-	// strata ranges: aim at two workgroups per CU when the panels alone are fewer
-	int64_t nsplit = 1;
-	if (big) {
-		nsplit = (2 * 256 + npan * a.inner / 2) / (npan * a.inner);
-		const int64_t cap = a.nstrata / (4 * (ROWPANEL_NT / G));      // >= 4 segments per lane group
-		if (nsplit > cap) nsplit = cap;
-		if (nsplit > 1024) nsplit = 1024;
-		if (nsplit < 1) nsplit = 1;
-	}
-	const int NT = ROWPANEL_NT;
-	const bool centered = oc == SVT_OP_CENTERED_X2_SUM;
-	const size_t lds = sumlike && !a.na_bg ? (size_t) prow * (centered ? 16 : 8) : (size_t) prow * 16;
-	if (nsplit > 1)
-		HIP_TRY(hipMemsetAsync(a.out, 0, (size_t) a.out_len * (oc == SVT_OP_ANYNA ? 4 : 8), s));
-	dim3 grid((unsigned) npan, (unsigned) a.inner, (unsigned) nsplit);
-	if (lds > 64 * 1024)
-		(void) hipFuncSetAttribute(a.Rtype == SVT_REALSXP ? (const void *) rowstats_panel_kernel<double> :
-					   (const void *) rowstats_panel_kernel<int>,
-					   hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-	if (a.Rtype == SVT_REALSXP)
-		hipLaunchKernelGGL(rowstats_panel_kernel<double>, grid, dim3(NT), lds, s, a, pt, npan, G, ps);
-	else
-		hipLaunchKernelGGL(rowstats_panel_kernel<int>, grid, dim3(NT), lds, s, a, pt, npan, G, ps);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
 
-int launch_rowstats(const RowStatsArgs &a, int64_t nnz, hipStream_t s)
+// memory atomics
+int launch_rowstats(const RowStatsArgs &a, hipStream_t s)
 {
-	(void) nnz;
 	if (a.out_len <= 0)
 		return 0;
 	const bool is_dbl = a.Rtype == SVT_REALSXP;
@@ -939,13 +802,11 @@ int launch_rowstats(const RowStatsArgs &a, int64_t nnz, hipStream_t s)
 	hipLaunchKernelGGL(rowstats_init_kernel, dim3(nb_out), dim3(256), 0, s, a);
 	if (a.ncol > 0 && a.nstrata > 0) {
 		const unsigned nb = (unsigned) ((a.ncol + 3) / 4);
-		if (is_dbl) hipLaunchKernelGGL(rowstats_scatter_kernel<double>, dim3(nb), dim3(256), 0, s, a);
-		else hipLaunchKernelGGL(rowstats_scatter_kernel<int>, dim3(nb), dim3(256), 0, s, a);
+		hipLaunchKernelGGL(is_dbl ? rowstats_scatter_kernel<double> : rowstats_scatter_kernel<int>, dim3(nb), dim3(256), 0, s, a);
 	}
-	if (a.opcode == SVT_OP_MIN || a.opcode == SVT_OP_MAX) {
-		if (is_dbl) hipLaunchKernelGGL(rowstats_minmax_finish_kernel<double>, dim3(nb_out), dim3(256), 0, s, a);
-		else hipLaunchKernelGGL(rowstats_minmax_finish_kernel<int>, dim3(nb_out), dim3(256), 0, s, a);
-	}
+	if (a.opcode == SVT_OP_MIN || a.opcode == SVT_OP_MAX)
+		hipLaunchKernelGGL(is_dbl ? rowstats_minmax_finish_kernel<double> : rowstats_minmax_finish_kernel<int>,
+				   dim3(nb_out), dim3(256), 0, s, a);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -987,11 +848,26 @@ __device__ inline int64_t col_beg(const GroupSumArgs &a, int64_t j)
 	return a.col_ptr64 ? a.col_ptr64[j] : (int64_t) a.col_ptr32[j];
 }
 
+// 1-based slot of group id g: NA groups take the last one (src/rowsum_methods.c:44-64)
+__host__ __device__ inline int group_slot(int g, int ngroup)
+{
+	return g == NA_INT ? ngroup : g;
+}
+// the same as a 0-based 16-bit id.  (check_group, src/rowsum_methods.c:15-37, has refused ids outside 1 .. ngroup at
+// the entry points; a caller of the device level that did not gets them folded into the last group: the kernels
+// index LDS cells with the id)
+__device__ inline uint32_t group_slot16(int g, int ngroup)
+{
+	const uint32_t u = (uint32_t) (group_slot(g, ngroup) - 1), top = (uint32_t) (ngroup - 1);
+	return u > top ? top : u;
+}
+
 // One workgroup per column, group accumulators in LDS (ds_add_f64), one
 // coalesced store of the finished column: compute_rowsum_doubles,
-// src/rowsum_methods.c:44-64.
+// src/rowsum_methods.c:44-64.  `tab`: a.group itself (int) or its 16-bit copy (group16_kernel).
+template <typename G>
 __global__ void __launch_bounds__(256)
-rowsum_f64_lds_kernel(GroupSumArgs a)
+rowsum_f64_lds_kernel(GroupSumArgs a, const G *__restrict__ tab)
 {
 	extern __shared__ double acc[];
 	const int64_t j = blockIdx.x;
@@ -1004,9 +880,8 @@ rowsum_f64_lds_kernel(GroupSumArgs a)
 		const double v = val[k];
 		if (a.na_rm && v != v)
 			continue;
-		int g = a.group[a.row_idx[k]];
-		if (g == NA_INT) g = a.ngroup;
-		atomicAdd(&acc[g - 1], v);
+		const G g = tab[a.row_idx[k]];
+		atomicAdd(&acc[sizeof(G) == 2 ? (uint32_t) g : group_slot16((int) g, a.ngroup)], v);
 	}
 	__syncthreads();
 	double *out = (double *) a.out + j * (int64_t) a.ngroup;
@@ -1030,9 +905,7 @@ groupsum_atomic_kernel(GroupSumArgs a, int64_t out_len)
 	const int64_t beg = col_beg(a, j), end = col_beg(a, j + 1);
 	int64_t colbase = 0;
 	if (TARGET == 1) {
-		int g = a.group[j];
-		if (g == NA_INT) g = a.ngroup;
-		colbase = (int64_t) (g - 1) * a.nrow;
+		colbase = (int64_t) (group_slot(a.group[j], a.ngroup) - 1) * a.nrow;
 	} else {
 		colbase = j * (int64_t) a.ngroup;
 	}
@@ -1046,9 +919,7 @@ groupsum_atomic_kernel(GroupSumArgs a, int64_t out_len)
 		if (TARGET == 1) {
 			i = colbase + a.row_idx[k];
 		} else {
-			int g = a.group[a.row_idx[k]];
-			if (g == NA_INT) g = a.ngroup;
-			i = colbase + g - 1;
+			i = colbase + group_slot(a.group[a.row_idx[k]], a.ngroup) - 1;
 		}
 		if (is_dbl) {
 			atomicAdd((double *) a.out + i, (double) v);
@@ -1098,20 +969,13 @@ __global__ void groupsum_int_exact_kernel(GroupSumArgs a, int64_t out_len, int64
 	const int64_t j0 = TARGET == 0 ? c : 0, j1 = TARGET == 0 ? c + 1 : a.ncol;
 	for (int64_t j = j0; j < j1; j++) {
 		if (TARGET == 1) {
-			int g = a.group[j];
-			if (g == NA_INT) g = a.ngroup;
-			if (g - 1 != c) continue;
+			if (group_slot(a.group[j], a.ngroup) - 1 != c) continue;
 		}
 		const int64_t beg = col_beg(a, j), end = col_beg(a, j + 1);
 		for (int64_t k = beg; k < end; k++) {
 			int64_t r;
-			if (TARGET == 0) {
-				int g = a.group[a.row_idx[k]];
-				if (g == NA_INT) g = a.ngroup;
-				r = g - 1;
-			} else {
-				r = a.row_idx[k];
-			}
+			if (TARGET == 0) r = group_slot(a.group[a.row_idx[k]], a.ngroup) - 1;
+			else r = a.row_idx[k];
 			const int cur = out[r], v = val[k];
 			if (v == NA_INT) {
 				if (!a.na_rm) out[r] = NA_INT;
@@ -1160,12 +1024,6 @@ static int groupsum_common(const GroupSumArgs &a, int64_t out_len, bool colsum,
 	return 0;
 }
 
-int launch_rowsum(const GroupSumArgs &a, hipStream_t s)
-{
-	const int64_t out_len = (int64_t) a.ngroup * a.ncol;
-	return groupsum_common(a, out_len, false, s);
-}
-
 // The gather of group[row] is what bounds rowsum (one 64-byte sector from L2 per nonzero): a
 // 16-bit, zero-based copy of the table halves its footprint in L2 (4 MB -> 2 MB at 1e6 rows;
 // 0.657 -> 0.593 ms at BASELINE config 3, copy included; four nonzeros per thread in flight
@@ -1175,36 +1033,17 @@ int launch_rowsum(const GroupSumArgs &a, hipStream_t s)
 __global__ void group16_kernel(const int *__restrict__ g, int64_t n, int ngroup, uint16_t *__restrict__ g16)
 {
 	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-	// (check_group, src/rowsum_methods.c:15-37, has refused ids outside 1 .. ngroup at the entry points; a caller of the
-	// device level that did not gets them folded into the last group: the kernels index LDS cells with the id)
-	if (i < n) {
-		int v = g[i];
-		if (v == NA_INT) v = ngroup;
-		unsigned u = (unsigned) (v - 1);
-		if (u > (unsigned) (ngroup - 1)) u = (unsigned) (ngroup - 1);
-		g16[i] = (uint16_t) u;
-	}
+	if (i < n)
+		g16[i] = (uint16_t) group_slot16(g[i], ngroup);
 }
-__global__ void __launch_bounds__(256)
-rowsum_f64_lds16_kernel(GroupSumArgs a, const uint16_t *__restrict__ g16)
+
+// the 16-bit table of a.group on the stream (the caller frees it with hipFreeAsync); needs ngroup < 65535
+static int make_group16(const GroupSumArgs &a, uint16_t **g16, hipStream_t s)
 {
-	extern __shared__ double acc[];
-	const int64_t j = blockIdx.x;
-	for (int g = threadIdx.x; g < a.ngroup; g += blockDim.x)
-		acc[g] = 0.0;
-	__syncthreads();
-	const double *__restrict__ val = (const double *) a.val;
-	const int64_t beg = col_beg(a, j), end = col_beg(a, j + 1);
-	for (int64_t k = beg + threadIdx.x; k < end; k += blockDim.x) {
-		const double v = val[k];
-		if (a.na_rm && v != v)
-			continue;
-		atomicAdd(&acc[g16[a.row_idx[k]]], v);
-	}
-	__syncthreads();
-	double *out = (double *) a.out + j * (int64_t) a.ngroup;
-	for (int g = threadIdx.x; g < a.ngroup; g += blockDim.x)
-		out[g] = acc[g];
+	HIP_TRY(hipMallocAsync((void **) g16, (size_t) a.nrow * 2 + 16, s));
+	hipLaunchKernelGGL(group16_kernel, dim3((unsigned) ((a.nrow + 255) / 256)), dim3(256), 0, s,
+			   a.group, a.nrow, a.ngroup, *g16);
+	return 0;
 }
 
 // Round 3: a workgroup takes C columns, one wavefront each, and walks them through the SAME window of
@@ -1220,23 +1059,19 @@ rowsum_f64_lds16_kernel(GroupSumArgs a, const uint16_t *__restrict__ g16)
 // C is chosen so that the last round of workgroups is as full as possible (14 at 1e4 columns: 715 workgroups
 // in 3 rounds).
 #define ROWSUM_WIN 49152
-template <bool NARM>
-__global__ void __launch_bounds__(1024)
-rowsum_f64_cols_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx,
-		       const double *__restrict__ val, int64_t ncol, int64_t nrow, int ngroup,
-		       const uint16_t *__restrict__ g16, double *__restrict__ out, int C)
+// The walk of one wavefront over column j (none: j >= ncol; it still meets the barriers): use(k, r, v) for every
+// nonzero k of row r; VALS: the values are fetched along with the rows (v is 0.0 otherwise).
+template <bool VALS, typename Use>
+__device__ __forceinline__ void rowsum_window_walk(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx,
+						   const double *__restrict__ val, const int64_t ncol, const int64_t nrow,
+						   const int64_t j, Use use)
 {
-	extern __shared__ double acc[];                 // [C][ngroup]
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t j = (int64_t) blockIdx.x * C + w;
-	for (int g = threadIdx.x; g < C * ngroup; g += C * 64) acc[g] = 0.0;
-	__syncthreads();
-	double *mine = acc + w * ngroup;
+	const int lane = threadIdx.x & 63;
 	const bool have = j < ncol;
 	const int64_t beg = have ? col_ptr[j] : 0, end = have ? col_ptr[j + 1] : 0;
 	int64_t k = beg;
 	int32_t r = k + lane < end ? row_idx[k + lane] : 0x7FFFFFFF;
-	double v = k + lane < end ? val[k + lane] : 0.0;
+	double v = VALS && k + lane < end ? val[k + lane] : 0.0;
 	for (int64_t R = ROWSUM_WIN; ; R += ROWSUM_WIN) {
 		const int32_t Rc = R < 0x7FFFFFFF ? (int32_t) R : 0x7FFFFFFF;
 		for (;;) {
@@ -1244,14 +1079,31 @@ rowsum_f64_cols_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__res
 			const int cnt = __popcll(__ballot(in));
 			const int64_t kn = k + cnt;             // (the rows of a column ascend: the lanes inside the window are the first cnt)
 			const int32_t rn = kn + lane < end ? row_idx[kn + lane] : 0x7FFFFFFF;
-			const double vn = kn + lane < end ? val[kn + lane] : 0.0;
-			if (in && !(NARM && v != v)) atomicAdd(&mine[g16[r]], v);
+			const double vn = VALS && kn + lane < end ? val[kn + lane] : 0.0;
+			if (in) use(k + lane, r, v);
 			k = kn; r = rn; v = vn;
 			if (cnt < 64) break;
 		}
 		if (R >= nrow) break;
 		__syncthreads();
 	}
+}
+
+template <bool NARM>
+__global__ void __launch_bounds__(1024)
+rowsum_f64_cols_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx,
+		       const double *__restrict__ val, int64_t ncol, int64_t nrow, int ngroup,
+		       const uint16_t *__restrict__ g16, double *__restrict__ out, int C)
+{
+	extern __shared__ double acc[];                 // [C][ngroup]
+	const int w = threadIdx.x >> 6;
+	for (int g = threadIdx.x; g < C * ngroup; g += C * 64) acc[g] = 0.0;
+	__syncthreads();
+	double *mine = acc + w * ngroup;
+	rowsum_window_walk<true>(col_ptr, row_idx, val, ncol, nrow, (int64_t) blockIdx.x * C + w,
+		[&](const int64_t, const int32_t r, const double v) {
+			if (!(NARM && v != v)) atomicAdd(&mine[g16[r]], v);
+		});
 	__syncthreads();
 	for (int g = threadIdx.x; g < C * ngroup; g += C * 64) {
 		const int64_t jj = (int64_t) blockIdx.x * C + g / ngroup;
@@ -1273,18 +1125,10 @@ rowsum_gid_kernel(const int32_t *__restrict__ row_idx, int64_t nnz, const int *_
 	for (int64_t k = ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) * 2; k < nnz;
 	     k += (int64_t) gridDim.x * blockDim.x * 2) {
 		// two ids per thread: one 4-byte store
-		// (the entry points have checked 1 <= group <= ngroup or NA, check_group, src/rowsum_methods.c:258-281; a caller of the
-		// device-level function that did not gets its stray ids folded into the last group, never an id past the LDS cells)
-		const uint32_t top = (uint32_t) (ngroup - 1);
-		const int g0 = group[row_idx[k]];
-		uint32_t a = (uint32_t) ((g0 == NA_INT ? ngroup : g0) - 1);
-		a = a > top ? top : a;
-		if (k + 1 < nnz) {
-			const int g1 = group[row_idx[k + 1]];
-			uint32_t b = (uint32_t) ((g1 == NA_INT ? ngroup : g1) - 1);
-			b = b > top ? top : b;
-			*(uint32_t *) (gid + k) = (a & 0xFFFFu) | (b << 16);
-		} else
+		const uint32_t a = group_slot16(group[row_idx[k]], ngroup);
+		if (k + 1 < nnz)
+			*(uint32_t *) (gid + k) = (a & 0xFFFFu) | (group_slot16(group[row_idx[k + 1]], ngroup) << 16);
+		else
 			gid[k] = (uint16_t) a;
 	}
 }
@@ -1321,59 +1165,6 @@ rowsum_f64_gid_kernel(const int64_t *__restrict__ col_ptr, const double *__restr
 	}
 }
 
-// columns per workgroup of rowsum_f64_cols_kernel (0: the operand does not suit it)
-static int rowsum_cols_per_wg(const GroupSumArgs &a)
-{
-	const int64_t cap = (int64_t) (160 * 1024) / ((int64_t) a.ngroup * 8);
-	int cmax = cap > 16 ? 16 : (int) cap;
-	if (cmax < 4 || a.ncol < 64 || a.col_ptr64 == NULL)
-		return 0;
-	int best = 0;
-	int64_t best_cost = 0;
-	for (int c = cmax; c >= 4; c--) {
-		const int64_t nwg = (a.ncol + c - 1) / c, rounds = (nwg + 255) / 256;
-		const int64_t cost = rounds * c;
-		if (best == 0 || cost < best_cost) { best = c; best_cost = cost; }
-	}
-	return best;
-}
-
-// Long f64 columns with few groups: LDS accumulators, no memory atomics.
-int launch_rowsum_lds(const GroupSumArgs &a, hipStream_t s)
-{
-	if (a.ncol <= 0 || a.ngroup <= 0)
-		return 0;
-	if (a.ngroup < 65535 && a.nrow >= 65536) {
-		uint16_t *g16 = NULL;
-		HIP_TRY(hipMallocAsync((void **) &g16, (size_t) a.nrow * 2 + 16, s));
-		hipLaunchKernelGGL(group16_kernel, dim3((unsigned) ((a.nrow + 255) / 256)), dim3(256), 0, s,
-				   a.group, a.nrow, a.ngroup, g16);
-		const int C = rowsum_cols_per_wg(a);
-		if (C > 0) {
-			const size_t lds = (size_t) C * a.ngroup * 8;
-			const dim3 grid((unsigned) ((a.ncol + C - 1) / C));
-			if (a.na_rm) {
-				(void) hipFuncSetAttribute((const void *) rowsum_f64_cols_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-				hipLaunchKernelGGL(rowsum_f64_cols_kernel<true>, grid, dim3(C * 64), lds, s, a.col_ptr64, a.row_idx,
-						   (const double *) a.val, a.ncol, a.nrow, a.ngroup, g16, (double *) a.out, C);
-			} else {
-				(void) hipFuncSetAttribute((const void *) rowsum_f64_cols_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-				hipLaunchKernelGGL(rowsum_f64_cols_kernel<false>, grid, dim3(C * 64), lds, s, a.col_ptr64, a.row_idx,
-						   (const double *) a.val, a.ncol, a.nrow, a.ngroup, g16, (double *) a.out, C);
-			}
-		} else
-		hipLaunchKernelGGL(rowsum_f64_lds16_kernel, dim3((unsigned) a.ncol), dim3(256),
-				   (size_t) a.ngroup * 8, s, a, g16);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipFreeAsync(g16, s));
-		return 0;
-	}
-	hipLaunchKernelGGL(rowsum_f64_lds_kernel, dim3((unsigned) a.ncol), dim3(256),
-			   (size_t) a.ngroup * 8, s, a);
-	HIP_TRY(hipGetLastError());
-	return 0;
-}
-
 // The same ids by the walk of rowsum_f64_cols_kernel (round 5): a wavefront per column, 16 columns per workgroup, all of
 // them inside the same window of ROWSUM_WIN rows at a time, looking up the 16-bit copy of the table -- the lookups of
 // the whole chip then go to one band of 96 KB of it instead of all over 4 MB of int32 while the offsets stream through
@@ -1382,54 +1173,100 @@ __global__ void __launch_bounds__(1024)
 rowsum_gid_cols_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ row_idx, int64_t ncol,
 		       int64_t nrow, const uint16_t *__restrict__ g16, uint16_t *__restrict__ gid, int C)
 {
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t j = (int64_t) blockIdx.x * C + w;
-	const bool have = j < ncol;
-	const int64_t beg = have ? col_ptr[j] : 0, end = have ? col_ptr[j + 1] : 0;
-	int64_t k = beg;
-	int32_t r = k + lane < end ? row_idx[k + lane] : 0x7FFFFFFF;
-	for (int64_t R = ROWSUM_WIN; ; R += ROWSUM_WIN) {
-		const int32_t Rc = R < 0x7FFFFFFF ? (int32_t) R : 0x7FFFFFFF;
-		for (;;) {
-			const bool in = r < Rc;
-			const int cnt = __popcll(__ballot(in));
-			const int64_t kn = k + cnt;             // (the rows of a column ascend: the lanes inside the window are the first cnt)
-			const int32_t rn = kn + lane < end ? row_idx[kn + lane] : 0x7FFFFFFF;
-			if (in) gid[k + lane] = g16[r];
-			k = kn; r = rn;
-			if (cnt < 64) break;
-		}
-		if (R >= nrow) break;
-		__syncthreads();
-	}
+	rowsum_window_walk<false>(col_ptr, row_idx, (const double *) NULL, ncol, nrow,
+				  (int64_t) blockIdx.x * C + (threadIdx.x >> 6),
+				  [&](const int64_t k, const int32_t r, const double) { gid[k] = g16[r]; });
 }
 
-// The 16-bit group id of every nonzero (gid: nnz ids); needs ngroup <= 65535.
-int launch_rowsum_gid(const GroupSumArgs &a, int64_t nnz, uint16_t *gid, hipStream_t s)
+// columns (a wavefront each) per workgroup, cmin .. cmax: the count with the fullest last round of workgroups on 256
+// CUs, the largest such
+static int rowsum_cols_per_wg(int64_t ncol, int cmax, int cmin)
 {
-	if (nnz <= 0)
+	int best = cmax;
+	int64_t best_cost = -1;
+	for (int c = cmax; c >= cmin; c--) {
+		const int64_t nwg = (ncol + c - 1) / c, rounds = (nwg + 255) / 256, cost = rounds * c;
+		if (best_cost < 0 || cost < best_cost) { best = c; best_cost = cost; }
+	}
+	return best;
+}
+
+// the kernels with C columns per workgroup (their last parameter): NARM instantiation, dynamic LDS, launch
+template <typename... P, typename... A>
+static void launch_rowsum_cols(int na_rm, void (*narm)(P...), void (*plain)(P...), int64_t ncol, int ngroup, int C,
+			       hipStream_t s, A... args)
+{
+	void (*kernel)(P...) = na_rm ? narm : plain;
+	const size_t lds = (size_t) C * ngroup * 8;
+	(void) hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+	hipLaunchKernelGGL(kernel, dim3((unsigned) ((ncol + C - 1) / C)), dim3(C * 64), lds, s, args..., C);
+}
+
+// Long f64 columns with few groups: LDS accumulators, no memory atomics.
+static int launch_rowsum_lds(const GroupSumArgs &a, hipStream_t s)
+{
+	if (a.ncol <= 0 || a.ngroup <= 0)
+		return 0;
+	if (a.ngroup < 65535 && a.nrow >= 65536) {
+		uint16_t *g16 = NULL;
+		if (make_group16(a, &g16, s))
+			return -1;
+		const int64_t cap = (int64_t) (160 * 1024) / ((int64_t) a.ngroup * 8);
+		const int cmax = cap > 16 ? 16 : (int) cap;
+		if (cmax >= 4 && a.ncol >= 64 && a.col_ptr64 != NULL)
+			launch_rowsum_cols(a.na_rm, rowsum_f64_cols_kernel<true>, rowsum_f64_cols_kernel<false>, a.ncol, a.ngroup,
+					   rowsum_cols_per_wg(a.ncol, cmax, 4), s, a.col_ptr64, a.row_idx, (const double *) a.val,
+					   a.ncol, a.nrow, a.ngroup, (const uint16_t *) g16, (double *) a.out);
+		else
+			hipLaunchKernelGGL(rowsum_f64_lds_kernel<uint16_t>, dim3((unsigned) a.ncol), dim3(256),
+					   (size_t) a.ngroup * 8, s, a, (const uint16_t *) g16);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipFreeAsync(g16, s));
+		return 0;
+	}
+	hipLaunchKernelGGL(rowsum_f64_lds_kernel<int>, dim3((unsigned) a.ncol), dim3(256),
+			   (size_t) a.ngroup * 8, s, a, a.group);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// rowsum of doubles: the LDS kernels for few groups and leaves long enough to fill them (a.nnz: the operand's
+// nonzeros), else -- and for ints, and for the int32 'p' slot of a dgCMatrix, which the LDS kernels do not read --
+// the atomic one
+int launch_rowsum(const GroupSumArgs &a, hipStream_t s)
+{
+	if (a.Rtype == SVT_REALSXP && a.col_ptr64 != NULL && a.ngroup <= 8192 && a.ncol > 0 &&
+	    a.nnz / a.ncol >= a.ngroup / 4)
+		return launch_rowsum_lds(a, s);
+	return groupsum_common(a, (int64_t) a.ngroup * a.ncol, false, s);
+}
+
+int launch_colsum(const GroupSumArgs &a, hipStream_t s)
+{
+	return groupsum_common(a, (int64_t) a.ngroup * a.nrow, true, s);
+}
+
+// The 16-bit group id of every nonzero (gid: a.nnz ids); needs ngroup <= 65535.
+int launch_rowsum_gid(const GroupSumArgs &a, uint16_t *gid, hipStream_t s)
+{
+	if (a.nnz <= 0)
 		return 0;
 	if (a.col_ptr64 != NULL && a.ncol >= 64 && a.nrow >= 65536 && a.ngroup >= 1 && a.ngroup < 65535) {
 		// (group16_kernel folds NA into the last group as the flat kernel does; stray ids are the caller's: check_group)
 		uint16_t *g16 = NULL;
-		HIP_TRY(hipMallocAsync((void **) &g16, (size_t) a.nrow * 2 + 16, s));
-		hipLaunchKernelGGL(group16_kernel, dim3((unsigned) ((a.nrow + 255) / 256)), dim3(256), 0, s,
-				   a.group, a.nrow, a.ngroup, g16);
-		int C = 16; int64_t best = -1;
-		for (int c = 16; c >= 8; c--) {             // the fullest last round of workgroups
-			const int64_t nwg = (a.ncol + c - 1) / c, cost = (nwg + 255) / 256 * c;
-			if (best < 0 || cost < best) { best = cost; C = c; }
-		}
+		if (make_group16(a, &g16, s))
+			return -1;
+		const int C = rowsum_cols_per_wg(a.ncol, 16, 8);
 		hipLaunchKernelGGL(rowsum_gid_cols_kernel, dim3((unsigned) ((a.ncol + C - 1) / C)), dim3(C * 64), 0, s,
 				   a.col_ptr64, a.row_idx, a.ncol, a.nrow, g16, gid, C);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipFreeAsync(g16, s));
 		return 0;
 	}
-	int64_t nb = ((nnz + 1) / 2 + 255) / 256;
+	int64_t nb = ((a.nnz + 1) / 2 + 255) / 256;
 	if (nb > 256 * 32) nb = 256 * 32;
 	if (nb < 1) nb = 1;
-	hipLaunchKernelGGL(rowsum_gid_kernel, dim3((unsigned) nb), dim3(256), 0, s, a.row_idx, nnz, a.group, a.ngroup, gid);
+	hipLaunchKernelGGL(rowsum_gid_kernel, dim3((unsigned) nb), dim3(256), 0, s, a.row_idx, a.nnz, a.group, a.ngroup, gid);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -1443,32 +1280,10 @@ int launch_rowsum_prepared(const GroupSumArgs &a, const uint16_t *gid, hipStream
 	const int64_t cap = (int64_t) (160 * 1024) / ((int64_t) a.ngroup * 8);
 	if (cap < 1 || a.col_ptr64 == NULL)
 		return 1;
-	int C = cap > 16 ? 16 : (int) cap;
-	{       // as rowsum_cols_per_wg(): the fullest last round of workgroups
-		int best = C; int64_t best_cost = -1;
-		for (int c = C; c >= (C >= 4 ? 4 : 1); c--) {
-			const int64_t nwg = (a.ncol + c - 1) / c, rounds = (nwg + 255) / 256, cost = rounds * c;
-			if (best_cost < 0 || cost < best_cost) { best = c; best_cost = cost; }
-		}
-		C = best;
-	}
-	const size_t lds = (size_t) C * a.ngroup * 8;
-	const dim3 grid((unsigned) ((a.ncol + C - 1) / C));
-	if (a.na_rm) {
-		(void) hipFuncSetAttribute((const void *) rowsum_f64_gid_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-		hipLaunchKernelGGL(rowsum_f64_gid_kernel<true>, grid, dim3(C * 64), lds, s, a.col_ptr64, (const double *) a.val,
-				   gid, a.ncol, a.ngroup, (double *) a.out, C);
-	} else {
-		(void) hipFuncSetAttribute((const void *) rowsum_f64_gid_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-		hipLaunchKernelGGL(rowsum_f64_gid_kernel<false>, grid, dim3(C * 64), lds, s, a.col_ptr64, (const double *) a.val,
-				   gid, a.ncol, a.ngroup, (double *) a.out, C);
-	}
+	const int cmax = cap > 16 ? 16 : (int) cap;
+	launch_rowsum_cols(a.na_rm, rowsum_f64_gid_kernel<true>, rowsum_f64_gid_kernel<false>, a.ncol, a.ngroup,
+			   rowsum_cols_per_wg(a.ncol, cmax, cmax >= 4 ? 4 : 1), s, a.col_ptr64, (const double *) a.val, gid,
+			   a.ncol, a.ngroup, (double *) a.out);
 	HIP_TRY(hipGetLastError());
 	return 0;
-}
-
-int launch_colsum(const GroupSumArgs &a, hipStream_t s)
-{
-	const int64_t out_len = (int64_t) a.ngroup * a.nrow;
-	return groupsum_common(a, out_len, true, s);
 }

@@ -163,11 +163,15 @@ struct RowStatsArgs {
 	int *warn_flag;
 	int64_t nnz_hint;       // nonzeros of the operand (launch tuning only), 0 = unknown
 	int na_bg;              // NaArray: implicit entries are NAs (SparseArray_matrixStats.c:756-1019)
-	int table_mode;         // launch_rowstats_panel: 0 = build the table of run bounds and use it, 1 = build it only,
-	                        // 2 = it is in `ws` already (same operand, same operation class)
+	int table_mode;         // launch_rowstats_panel, ROWSTATS_TABLE_*
 };
-size_t rowstats_scratch_bytes(int opcode, int out_Rtype, int64_t out_len);
-int launch_rowstats(const RowStatsArgs &a, int64_t nnz, hipStream_t s);      // memory atomics
+enum {
+	ROWSTATS_TABLE_BUILD = 0,   // build the table of run bounds and use it
+	ROWSTATS_TABLE_ONLY = 1,    // build it only
+	ROWSTATS_TABLE_READY = 2    // it is in `ws` already (same operand, same operation class)
+};
+size_t rowstats_scratch_bytes(int opcode, int64_t out_len);
+int launch_rowstats(const RowStatsArgs &a, hipStream_t s);      // memory atomics
 size_t rowstats_panel_ws_bytes(int64_t nrow, int64_t ncol);
 int launch_rowstats_panel(const RowStatsArgs &a, void *ws, hipStream_t s);      // LDS row panels
 void launch_rowpanel_table(const int64_t *col_ptr, const int32_t *row_idx, int64_t ncol, int64_t nnz_hint,
@@ -236,6 +240,7 @@ struct GroupSumArgs {
 	const void *val;
 	int Rtype;
 	int64_t nrow, ncol;
+	int64_t nnz;                // nonzeros of the operand (launch_rowsum: route choice; launch_rowsum_gid: ids to write)
 	const int *group;           // device
 	int ngroup;
 	int na_rm;
@@ -244,9 +249,8 @@ struct GroupSumArgs {
 	int *ovflow_flag;
 };
 size_t groupsum_scratch_bytes(int Rtype, int64_t out_len);
-int launch_rowsum(const GroupSumArgs &a, hipStream_t s);
-int launch_rowsum_lds(const GroupSumArgs &a, hipStream_t s);   // f64, ngroup <= 8192
-int launch_rowsum_gid(const GroupSumArgs &a, int64_t nnz, uint16_t *gid, hipStream_t s);
+int launch_rowsum(const GroupSumArgs &a, hipStream_t s);       // doubles: LDS or atomic kernels by shape
+int launch_rowsum_gid(const GroupSumArgs &a, uint16_t *gid, hipStream_t s);
 int launch_rowsum_prepared(const GroupSumArgs &a, const uint16_t *gid, hipStream_t s);   // f64, ngroup * 8 <= LDS
 int launch_colsum(const GroupSumArgs &a, hipStream_t s);
 

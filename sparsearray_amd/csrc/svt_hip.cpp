@@ -913,6 +913,19 @@ extern "C" size_t svt_dev_rowstats_ws_bytes(int64_t nrow, int64_t ncol)
 	return rowstats_panel_ws_bytes(nrow, ncol);
 }
 
+// the operand and the operation of a row statistic; the caller adds center, scratch, warn_flag and table_mode
+static RowStatsArgs rowstats_args(const svt_dev_csc *A, int opcode, int na_rm, int64_t inner, int64_t nstrata, void *out)
+{
+	RowStatsArgs a;
+	memset(&a, 0, sizeof(a));
+	a.col_ptr = A->col_ptr; a.row_idx = A->row_idx; a.val = A->val;
+	a.Rtype = A->Rtype; a.ncol = A->ncol; a.nrow = A->nrow;
+	a.inner = inner; a.nstrata = nstrata; a.out_len = inner * A->nrow;
+	a.opcode = opcode; a.na_rm = na_rm; a.out = out; a.nnz_hint = A->nnz;
+	a.na_bg = A->na_background != 0;
+	return a;
+}
+
 static int dev_rowsums(const svt_dev_csc *A, int na_rm, int64_t inner, double *out, void *ws, size_t ws_bytes,
 		       void *stream, int table_mode)
 {
@@ -920,14 +933,7 @@ static int dev_rowsums(const svt_dev_csc *A, int na_rm, int64_t inner, double *o
 		return svt_set_error("'inner' must divide the number of leaves");
 	if (ws_bytes < rowstats_panel_ws_bytes(A->nrow, A->ncol))
 		return svt_set_error("svt_dev_rowsums: workspace too small");
-	RowStatsArgs a;
-	memset(&a, 0, sizeof(a));
-	a.col_ptr = A->col_ptr; a.row_idx = A->row_idx; a.val = A->val;
-	a.Rtype = A->Rtype; a.ncol = A->ncol; a.nrow = A->nrow;
-	a.inner = inner; a.nstrata = A->ncol / inner;
-	a.out_len = inner * A->nrow;
-	a.opcode = SVT_OP_SUM; a.na_rm = na_rm; a.out = out; a.nnz_hint = A->nnz;
-	a.na_bg = A->na_background;
+	RowStatsArgs a = rowstats_args(A, SVT_OP_SUM, na_rm, inner, A->ncol / inner, out);
 	a.table_mode = table_mode;
 	return launch_rowstats_panel(a, ws, (hipStream_t) stream);
 }
@@ -935,7 +941,7 @@ static int dev_rowsums(const svt_dev_csc *A, int na_rm, int64_t inner, double *o
 extern "C" int svt_dev_rowsums(const svt_dev_csc *A, int na_rm, int64_t inner,
 			       double *out, void *ws, size_t ws_bytes, void *stream)
 {
-	return dev_rowsums(A, na_rm, inner, out, ws, ws_bytes, stream, 0);
+	return dev_rowsums(A, na_rm, inner, out, ws, ws_bytes, stream, ROWSTATS_TABLE_BUILD);
 }
 
 // The table of run bounds per row panel depends on the operand alone (one pass over its offsets, a quarter of
@@ -943,13 +949,13 @@ extern "C" int svt_dev_rowsums(const svt_dev_csc *A, int na_rm, int64_t inner,
 // the same operand with the same `inner` read it.
 extern "C" int svt_dev_rowsums_prepare(const svt_dev_csc *A, int64_t inner, void *ws, size_t ws_bytes, void *stream)
 {
-	return dev_rowsums(A, 0, inner, NULL, ws, ws_bytes, stream, 1);
+	return dev_rowsums(A, 0, inner, NULL, ws, ws_bytes, stream, ROWSTATS_TABLE_ONLY);
 }
 
 extern "C" int svt_dev_rowsums_prepared(const svt_dev_csc *A, int na_rm, int64_t inner,
 					double *out, void *ws, size_t ws_bytes, void *stream)
 {
-	return dev_rowsums(A, na_rm, inner, out, ws, ws_bytes, stream, 2);
+	return dev_rowsums(A, na_rm, inner, out, ws, ws_bytes, stream, ROWSTATS_TABLE_READY);
 }
 
 extern "C" size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz)
@@ -1201,12 +1207,18 @@ extern "C" int svt_aperm_SVT(const svt_view *x, const int *perm, int64_t *out_co
 	return abi_status([&] { return aperm_SVT_impl(x, perm, out_col_ptr, out_row_idx, out_val); });
 }
 
-// rowsum of doubles: the LDS kernel for few groups and leaves long enough to fill them, else the atomic one
-static int launch_rowsum_f64(const GroupSumArgs &a, int64_t nnz, hipStream_t stream)
+// the operand, the groups and the result of a rowsum / colsum; the caller adds scratch and ovflow_flag.
+// col_ptr32: the int32 'p' slot of a dgCMatrix in place of A->col_ptr
+static GroupSumArgs groupsum_args(const svt_dev_csc *A, const int32_t *col_ptr32, const int *group, int ngroup,
+				  int na_rm, void *out)
 {
-	if (a.ngroup <= 8192 && a.ncol > 0 && nnz / a.ncol >= a.ngroup / 4)
-		return launch_rowsum_lds(a, stream);
-	return launch_rowsum(a, stream);
+	GroupSumArgs a;
+	memset(&a, 0, sizeof(a));
+	a.col_ptr64 = col_ptr32 ? NULL : A->col_ptr; a.col_ptr32 = col_ptr32;
+	a.row_idx = A->row_idx; a.val = A->val; a.Rtype = A->Rtype;
+	a.nrow = A->nrow; a.ncol = A->ncol; a.nnz = A->nnz;
+	a.group = group; a.ngroup = ngroup; a.na_rm = na_rm; a.out = out;
+	return a;
 }
 
 extern "C" int svt_dev_rowsum(const svt_dev_csc *A, const int *group, int ngroup,
@@ -1214,12 +1226,7 @@ extern "C" int svt_dev_rowsum(const svt_dev_csc *A, const int *group, int ngroup
 {
 	if (A->Rtype != SVT_REALSXP)
 		return svt_set_error("svt_dev_rowsum: f64 input only");
-	GroupSumArgs a;
-	memset(&a, 0, sizeof(a));
-	a.col_ptr64 = A->col_ptr; a.row_idx = A->row_idx; a.val = A->val;
-	a.Rtype = A->Rtype; a.nrow = A->nrow; a.ncol = A->ncol;
-	a.group = group; a.ngroup = ngroup; a.na_rm = na_rm; a.out = out;
-	return launch_rowsum_f64(a, A->nnz, (hipStream_t) stream);
+	return launch_rowsum(groupsum_args(A, NULL, group, ngroup, na_rm, out), (hipStream_t) stream);
 }
 
 // rowsum(x, group) for a (x, group) pair that is used more than once: the group of every nonzero, as a 16-bit
@@ -1237,11 +1244,7 @@ extern "C" int svt_dev_rowsum_prepare(const svt_dev_csc *A, const int *group, in
 		return svt_set_error("svt_dev_rowsum_prepare: between 1 and 65535 groups");
 	if (gid_bytes < svt_dev_rowsum_gid_bytes(A))
 		return svt_set_error("svt_dev_rowsum_prepare: id buffer too small");
-	GroupSumArgs a;
-	memset(&a, 0, sizeof(a));
-	a.col_ptr64 = A->col_ptr; a.row_idx = A->row_idx; a.nrow = A->nrow; a.ncol = A->ncol;
-	a.group = group; a.ngroup = ngroup;
-	return launch_rowsum_gid(a, A->nnz, (uint16_t *) gid, (hipStream_t) stream);
+	return launch_rowsum_gid(groupsum_args(A, NULL, group, ngroup, 0, NULL), (uint16_t *) gid, (hipStream_t) stream);
 }
 
 extern "C" int svt_dev_rowsum_prepared(const svt_dev_csc *A, const void *gid, int ngroup, int na_rm,
@@ -1253,11 +1256,8 @@ extern "C" int svt_dev_rowsum_prepared(const svt_dev_csc *A, const void *gid, in
 		return svt_set_error("svt_dev_rowsum_prepared: between 1 and 65535 groups");
 	if ((int64_t) ngroup * 8 > 160 * 1024)
 		return svt_set_error("svt_dev_rowsum_prepared: more groups than a workgroup's LDS holds (20480)");
-	GroupSumArgs a;
-	memset(&a, 0, sizeof(a));
-	a.col_ptr64 = A->col_ptr; a.val = A->val; a.Rtype = A->Rtype; a.nrow = A->nrow; a.ncol = A->ncol;
-	a.ngroup = ngroup; a.na_rm = na_rm; a.out = out;
-	const int rc = launch_rowsum_prepared(a, (const uint16_t *) gid, (hipStream_t) stream);
+	const int rc = launch_rowsum_prepared(groupsum_args(A, NULL, NULL, ngroup, na_rm, out), (const uint16_t *) gid,
+					      (hipStream_t) stream);
 	if (rc > 0)
 		return svt_set_error("svt_dev_rowsum_prepared: unsupported shape");
 	return rc;
@@ -2545,19 +2545,14 @@ static int rowStats_SVT_impl(const svt_view *x, int opcode, int na_rm,
 	if (A.h == NULL) return -1;
 	DevBuf O, C, S, W;
 	if (O.alloc((size_t) out_len * osz) ||
-	    S.alloc(rowstats_scratch_bytes(opcode, out_Rtype, out_len)) ||
+	    S.alloc(rowstats_scratch_bytes(opcode, out_len)) ||
 	    W.alloc(16) || W.zero())
 		return -1;
 	if (center != NULL && C.upload(center, (size_t) out_len * 8))
 		return -1;
-	RowStatsArgs a;
-	a.col_ptr = A.h->col_ptr; a.row_idx = A.h->row_idx; a.val = A.h->val;
-	a.Rtype = A.h->Rtype; a.ncol = A.h->ncol; a.nrow = A.h->nrow;
-	a.inner = inner; a.nstrata = nstrata; a.out_len = out_len;
-	a.opcode = opcode; a.na_rm = na_rm;
+	RowStatsArgs a = rowstats_args(A.h, opcode, na_rm, inner, nstrata, O.p);
 	a.center = center ? C.as<double>() : NULL;
-	a.out = O.p; a.scratch = S.p; a.warn_flag = W.as<int>(); a.nnz_hint = A.h->nnz;
-	a.na_bg = x->na_background != 0;
+	a.scratch = S.p; a.warn_flag = W.as<int>();
 	if (a.na_bg && inner > 65535)
 		return svt_set_unsupported("row statistics of NaArray objects: more than 65535 output columns");
 	if (inner <= 65535) {
@@ -2565,7 +2560,7 @@ static int rowStats_SVT_impl(const svt_view *x, int opcode, int na_rm,
 		if (T.alloc(rowstats_panel_ws_bytes(a.nrow, a.ncol)) || launch_rowstats_panel(a, T.p, 0))
 			return -1;
 		HIP_TRY(hipDeviceSynchronize());
-	} else if (launch_rowstats(a, A.h->nnz, 0)) {
+	} else if (launch_rowstats(a, 0)) {
 		return -1;
 	}
 	int w = 0;
@@ -2615,17 +2610,9 @@ static int groupsum_host(const svt_dev_csc *A, const int32_t *col_ptr32,
 	if (G.upload(group, (size_t) glen * 4) || O.alloc((size_t) out_len * osz) ||
 	    S.alloc(groupsum_scratch_bytes(A->Rtype, out_len)) || W.alloc(16) || W.zero())
 		return -1;
-	GroupSumArgs a;
-	memset(&a, 0, sizeof(a));
-	a.col_ptr64 = col_ptr32 ? NULL : A->col_ptr;
-	a.col_ptr32 = col_ptr32;
-	a.row_idx = A->row_idx; a.val = A->val; a.Rtype = A->Rtype;
-	a.nrow = A->nrow; a.ncol = A->ncol;
-	a.group = G.as<int>(); a.ngroup = ngroup; a.na_rm = na_rm;
-	a.out = O.p; a.scratch = S.p; a.ovflow_flag = W.as<int>();
-	const int rc = colsum ? launch_colsum(a, 0)
-			      : A->Rtype == SVT_REALSXP ? launch_rowsum_f64(a, A->nnz, 0) : launch_rowsum(a, 0);
-	if (rc) return -1;
+	GroupSumArgs a = groupsum_args(A, col_ptr32, G.as<int>(), ngroup, na_rm, O.p);
+	a.scratch = S.p; a.ovflow_flag = W.as<int>();
+	if (colsum ? launch_colsum(a, 0) : launch_rowsum(a, 0)) return -1;
 	int w = 0;
 	if (staged_download(out, O.p, (size_t) out_len * osz)) return -1;
 	HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
@@ -2687,25 +2674,11 @@ static int xsum_dgC(int nrow, int ncol, const double *xx, const int *xi, const i
 	if (P.upload(xp, (size_t) (ncol + 1) * 4) || I.upload(xi, (size_t) nnz * 4) ||
 	    X.upload(xx, (size_t) nnz * 8))
 		return -1;
-	const int64_t out_len = colsum ? (int64_t) nrow * ngroup : (int64_t) ngroup * ncol;
-	if (out_len > 0x7FFFFFFFLL)
-		return svt_set_error("too many groups (matrix of sums will be too big)");
-	if (out_len == 0)
-		return 0;
-	DevBuf G, O, S;
-	if (G.upload(group, (size_t) (colsum ? ncol : nrow) * 4) ||
-	    O.alloc((size_t) out_len * 8) || S.alloc(16))
-		return -1;
-	GroupSumArgs a;
-	memset(&a, 0, sizeof(a));
-	a.col_ptr32 = P.as<int32_t>();      // (the LDS kernel reads col_ptr64: the int32 'p' slot takes the atomic one)
-	a.row_idx = I.as<int32_t>(); a.val = X.p; a.Rtype = SVT_REALSXP;
-	a.nrow = nrow; a.ncol = ncol; a.group = G.as<int>(); a.ngroup = ngroup;
-	a.na_rm = na_rm; a.out = O.p; a.scratch = S.p;
-	if (colsum ? launch_colsum(a, 0) : launch_rowsum(a, 0))
-		return -1;
-	if (staged_download(out, O.p, (size_t) out_len * 8)) return -1;
-	return 0;
+	svt_dev_csc D;                      // (the int32 'p' slot goes beside it: the atomic kernels read either flavour)
+	memset(&D, 0, sizeof(D));
+	D.Rtype = SVT_REALSXP; D.nrow = nrow; D.ncol = ncol; D.nnz = nnz;
+	D.row_idx = I.as<int32_t>(); D.val = X.p;
+	return groupsum_host(&D, P.as<int32_t>(), group, ngroup, na_rm, colsum, out, NULL);
 }
 
 // C_rowsum_dgCMatrix / C_colsum_dgCMatrix, src/rowsum_methods.c:328-356, 404-439

@@ -169,7 +169,10 @@ OPS_ROW = ["rowSums", "rowMeans", "rowVars", "rowSds", "rowMins", "rowMaxs",
 
 @pytest.mark.parametrize("na_rm", [False, True])
 @pytest.mark.parametrize("shape,density", [((1000, 300), 0.01), ((20000, 12), 0.2),
-                                           ((60, 50, 8), 0.05)])
+                                           ((60, 50, 8), 0.05),
+                                           # dims = 2: 70000 output columns, past the 65535 the row-panel grid
+                                           # takes -- the memory-atomic row statistics
+                                           ((8, 70000, 3), 0.1)])
 def test_matrixstats_double(hip, oracle, shape, density, na_rm):
     ncol = int(np.prod(shape[1:]))
     x2 = _sprinkle(_svt(shape[0], ncol, density, 11), 11, SPECIAL_D[:2] + [3.5, -2.0])
