@@ -225,6 +225,23 @@ int svt_colStats_SVT(const svt_view *x, int opcode, int na_rm, double center,
    center: NULL or prod(dim[0..dims-1]) doubles.  out: same length. */
 int svt_rowStats_SVT(const svt_view *x, int opcode, int na_rm,
 		     const double *center, int dims, void *out, int *warn);
+/* Every row statistic of the R API in one call.  C_rowStats_SVT (above) mirrors the reference and takes six
+   operations; rowAnys / rowAlls / rowProds go through a transposition and the column statistics there
+   (.OLD_rowStats_SparseArray, R/SparseArray-matrixStats.R:122-190, with the TODO of :109-121), and rowMeans /
+   rowVars / rowSds / rowRanges are composed of two to four calls (:440, :457: "do all this in a single pass").
+   This entry point takes those six plus SVT_OP_ANY, _ALL, _PROD, _RANGE, _MEAN, _VAR1 and _SD1: one operand on the
+   device (the resident cache applies), svt_dev_rowstats(), one download.  Same checks, messages, zero-extent
+   handling and constant fills as svt_rowStats_SVT.  mean / var1 / sd1 are the plain IEEE expressions of the R
+   methods (:511-516, :645-660): sum / nvals, centered_X2_sum / (nvals - 1) and its square root, nvals = the number
+   of strata, less the NAs when na_rm; there is no "fewer than two values" rule here.  prod multiplies in no fixed
+   order: results are not bit-reproducible.
+   center (var1 / sd1 / centered_X2_sum): NULL or prod(dim[0..dims-1]) doubles.  out: prod(dim[0..dims-1]) elements
+   of svt_colStats_out_Rtype(); SVT_OP_RANGE: twice that, the minima, then the maxima.
+   Status: > 0 for more than 65535 output columns with one of the seven added operations; < 0 ("operation not yet
+   supported on NaArray objects") for an added operation other than SVT_OP_RANGE on a NaArray.
+   This call is not sharded over the device list of svt_set_devices(): it runs on the first entry. */
+int svt_rowStatsFull_SVT(const svt_view *x, int opcode, int na_rm,
+			 const double *center, int dims, void *out, int *warn);
 
 /* C_rowsum_SVT / C_colsum_SVT, src/rowsum_methods.c:281-325, 363-401.
    group: 1-based, NA allowed.  out: ngroup x ncol (rowsum) or nrow x ngroup
@@ -431,6 +448,21 @@ int svt_dev_rowsums(const svt_dev_csc *A, int na_rm, int64_t inner,
 int svt_dev_rowsums_prepare(const svt_dev_csc *A, int64_t inner, void *ws, size_t ws_bytes, void *stream);
 int svt_dev_rowsums_prepared(const svt_dev_csc *A, int na_rm, int64_t inner,
 			     double *out, void *ws, size_t ws_bytes, void *stream);
+
+/* Any row statistic of a resident operand: the six operations of svt_rowStats_SVT plus SVT_OP_ANY, _ALL, _PROD,
+   _RANGE, _MEAN, _VAR1 and _SD1 (see svt_rowStatsFull_SVT for their rules).  out[(j % inner) * nrow + r], inner * nrow
+   elements of svt_colStats_out_Rtype(); SVT_OP_RANGE: twice that, the minima, then the maxima.  center: device,
+   inner * nrow doubles or NULL (centered_X2_sum, var1, sd1).  warn_flag: device int, set to 1 when an integer min /
+   max / range cell had nothing to look at (may be NULL).
+   Asynchronous on `stream`; allocates nothing and does not synchronise.  ws: svt_dev_rowstats_ws_bytes_op() bytes
+   for this (operand, opcode, inner): the table of run bounds, which mean / var1 / sd1 build once for their two or
+   three passes, plus their sums, NA counts and center, which never leave the device.
+   Status: > 0 for more than 65535 output columns with an added operation or a NaArray operand; < 0 for an added
+   operation other than SVT_OP_RANGE on a NaArray operand and for any / all on doubles.
+   One device: the caller shards. */
+size_t svt_dev_rowstats_ws_bytes_op(const svt_dev_csc *A, int opcode, int64_t inner);
+int svt_dev_rowstats(const svt_dev_csc *A, int opcode, int na_rm, const double *center, int64_t inner,
+		     void *out, int *warn_flag, void *ws, size_t ws_bytes, void *stream);
 
 /* rowsum(): out (ngroup x ncol, zeroed by the callee); group is a device
    array of nrow 1-based group ids (NA -> last group).  f64 input only at

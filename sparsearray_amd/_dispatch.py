@@ -72,6 +72,9 @@ class CAbiDispatcher:
                           ("tcrossprod2_SVT_SVT", (I, [V, V, P]))):
             if hasattr(self.lib, self.prefix + name):
                 protos[name] = sig
+        # every row statistic in one call (include/svt_hip.h): HIP library only
+        if hasattr(self.lib, self.prefix + "rowStatsFull_SVT"):
+            protos["rowStatsFull_SVT"] = (I, [V, I, I, P, I, P, POINTER(I)])
         for name, (res, args) in protos.items():
             f = self._fn(name)
             f.restype = res
@@ -219,14 +222,14 @@ class CAbiDispatcher:
             byref(out_Rtype), byref(warn)))
         return naked_result(op, x.type, out_d, out_i), bool(warn.value)
 
-    def _stat_out(self, op, x, shape):
+    def _stat_out(self, op, x, shape, per_cell=1):
         oc = self._opcode(op)
         rt = self._fn("colStats_out_Rtype")(oc, x.Rtype)
         if rt < 0:
             self._check(rt)
         dtype = np.float64 if rt == REALSXP else np.int32
         n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
-        flat = np.zeros(max(n, 1), dtype=dtype)
+        flat = np.zeros(max(n * per_cell, 1), dtype=dtype)
         return oc, flat, n
 
     def C_colStats_SVT(self, x, op, na_rm, center, dims):
@@ -242,8 +245,18 @@ class CAbiDispatcher:
         return ans, bool(warn.value)
 
     def C_rowStats_SVT(self, x, op, na_rm, center, dims):
+        return self._row_stats("rowStats_SVT", x, op, na_rm, center, dims)
+
+    def C_rowStatsFull_SVT(self, x, op, na_rm, center, dims):
+        """svt_rowStatsFull_SVT.  Returns the flat buffer (column-major prod(dim[:dims]) elements; "range": the
+        minima, then as many maxima) and the warning flag: the caller shapes it."""
+        return self._row_stats("rowStatsFull_SVT", x, op, na_rm, center, dims, flat_result=True)
+
+    def _row_stats(self, fname, x, op, na_rm, center, dims, flat_result=False):
         shape = tuple(x.dim[:dims])
-        oc, flat, n = self._stat_out(op, x, shape)
+        per_cell = 2 if op == "range" else 1
+        oc, flat, n = self._stat_out(op, x, shape, per_cell)
+        nout = per_cell * n
         warn = c_int(0)
         cptr = None
         if center is not None:
@@ -253,8 +266,10 @@ class CAbiDispatcher:
                 raise SparseArrayError("unexpected 'center' length")
             cptr = _ptr(center)
         xv = make_view(x)
-        self._check(self._fn("rowStats_SVT")(
+        self._check(self._fn(fname)(
             byref(xv), oc, int(na_rm), cptr, int(dims), _ptr(flat), byref(warn)))
+        if flat_result:
+            return flat[:nout], bool(warn.value)
         flat = flat[:n]
         ans = flat.reshape(shape, order="F") if len(shape) > 1 else flat
         return ans, bool(warn.value)

@@ -43,6 +43,14 @@ class SparseArrayUnsupported(SparseArrayError):
 _SUPPORTED_MULT_TYPES = ("double", "integer")
 
 
+# row statistics that C_rowStats_SVT does not take: one C_rowStatsFull_SVT call where the library has it
+_ROWSTATS_FULL_OPS = ("any", "all", "prod", "range", "mean", "var1", "sd1")
+
+
+def _shaped(flat: np.ndarray, shape) -> np.ndarray:
+    return flat.reshape(shape, order="F") if len(shape) > 1 else flat
+
+
 def _check_crossprod_input_type(type_: str):
     # R/SparseMatrix-mult.R:13-20
     if type_ not in _SUPPORTED_MULT_TYPES:
@@ -327,13 +335,14 @@ class Session:
                 "length(dim(x)) for the row*() functions")
         if dims == 0:
             return self._colStats(op, x, na_rm, center, x.ndim)
-        if x.na_background and op not in ("countNAs", "anyNA", "min", "max", "sum"):
+        if x.na_background and op not in ("countNAs", "anyNA", "min", "max", "sum", "range"):
             # rowAnys/Alls/Prods/Means/Vars/Sds: no NaArray methods (commented out in
             # R/NaArray-matrixStats.R:187-330)
             raise SparseArrayError(f"unable to find an inherited method for the row {op} "
                                    f"statistic for signature 'x = \"NaArray\"'")
+        full = self._has_rowStatsFull()
         if op not in ("countNAs", "anyNA", "min", "max", "sum",
-                      "centered_X2_sum"):
+                      "centered_X2_sum") and not full:
             return self._OLD_rowStats(op, x, na_rm, center, dims)
         if center is not None:
             ans_dim = x.dim[:dims]
@@ -347,12 +356,52 @@ class Session:
                 center = np.reshape(center, ans_dim, order="F")
             else:
                 raise SparseArrayError("unexpected 'center' length")
+        if op in ("any", "all", "prod") and not isinstance(na_rm, (bool, np.bool_)):
+            raise SparseArrayError("'na.rm' must be TRUE or FALSE")      # (the check of _colStats on the composed route)
+        if op in _ROWSTATS_FULL_OPS:
+            # The R methods compose these (a transposition and colStats; two to four C_rowStats_SVT calls).  The
+            # HIP library offers each in one call (svt_rowStatsFull_SVT, include/svt_hip.h); same checks above.
+            if full:
+                try:
+                    flat, warn = self.SparseArray_Call("C_rowStatsFull_SVT", x, op,
+                                                       bool(na_rm), center, dims)
+                except SparseArrayUnsupported:
+                    flat = None
+                if flat is not None:
+                    if warn:
+                        warnings.warn("NAs introduced by coercion of "
+                                      "infinite values to integers")
+                    shape = tuple(x.dim[:dims])
+                    flat = np.asarray(flat).reshape(-1)
+                    if op == "range":                        # the minima, then the maxima
+                        n = flat.size // 2
+                        return np.stack([_shaped(flat[:n], shape), _shaped(flat[n:], shape)], axis=-1)
+                    return _shaped(flat, shape)
+            return self._rowStats_composed(op, x, na_rm, center, dims)
         ans, warn = self.SparseArray_Call("C_rowStats_SVT", x, op,
                                           bool(na_rm), center, dims)
         if warn:
             warnings.warn("NAs introduced by coercion of "
                           "infinite values to integers")
         return ans
+
+    def _rowStats_composed(self, op, x, na_rm, center, dims):
+        # what the R methods do for the operations C_rowStats_SVT does not take
+        if op in ("any", "all", "prod"):
+            return self._OLD_rowStats(op, x, na_rm, None, dims)
+        if op == "range":                                    # :440, :457
+            mins = self._rowStats("min", x, na_rm, dims=dims)
+            maxs = self._rowStats("max", x, na_rm, dims=dims)
+            return np.stack([mins, maxs], axis=-1)
+        nvals = self._rowCountVals(x, na_rm, dims)
+        with np.errstate(all="ignore"):
+            if op == "mean":                                 # :511-516
+                return self._rowStats("sum", x, na_rm, dims=dims) / nvals
+            if center is None:                               # :645-660
+                center = self._rowStats("sum", x, na_rm, dims=dims) / nvals
+            cx2 = self._rowStats("centered_X2_sum", x, na_rm, center, dims)
+            var = cx2 / (nvals - 1)
+            return np.sqrt(var) if op == "sd1" else var
 
     def aperm(self, x, perm=None):
         """aperm(x, perm) (R/SparseArray-aperm.R:24-60); perm is 1-based, default: reversal."""
@@ -407,9 +456,12 @@ class Session:
         return np.stack([mins, maxs], axis=-1)
 
     def rowRanges(self, x, na_rm=False, dims=1):
-        mins = self.rowMins(x, na_rm, dims)
-        maxs = self.rowMaxs(x, na_rm, dims)
-        return np.stack([mins, maxs], axis=-1)
+        if self._has_rowStatsFull() and int(dims) != 0:
+            return self._rowStats("range", x, na_rm, dims=dims)
+        return self._rowStats_composed("range", x, na_rm, None, dims)
+
+    def _has_rowStatsFull(self):
+        return getattr(self._call, "has_entry", lambda name: False)("C_rowStatsFull_SVT")
 
     def colSums(self, x, na_rm=False, dims=1): return self._colStats("sum", x, na_rm, dims=dims)
     def rowSums(self, x, na_rm=False, dims=1): return self._rowStats("sum", x, na_rm, dims=dims)
@@ -421,10 +473,9 @@ class Session:
         # :511-516
         if x.na_background:
             return self._rowStats("mean", x, na_rm, dims=dims)     # raises: no NaArray method
-        sums = self.rowSums(x, na_rm, dims)
-        nvals = self._rowCountVals(x, na_rm, dims)
-        with np.errstate(all="ignore"):
-            return sums / nvals
+        if self._has_rowStatsFull() and int(dims) != 0:
+            return self._rowStats("mean", x, na_rm, dims=dims)
+        return self._rowStats_composed("mean", x, na_rm, None, dims)
 
     colSums2, rowSums2, colMeans2, rowMeans2 = colSums, rowSums, colMeans, rowMeans
 
@@ -438,14 +489,13 @@ class Session:
         # :645-660
         if x.na_background:
             return self._rowStats("var1", x, na_rm, dims=dims)     # raises: no NaArray method
-        nvals = self._rowCountVals(x, na_rm, dims)
-        with np.errstate(all="ignore"):
-            if center is None:
-                center = self.rowSums(x, na_rm, dims) / nvals
-            cx2 = self._rowStats("centered_X2_sum", x, na_rm, center, dims)
-            return cx2 / (nvals - 1)
+        if self._has_rowStatsFull() and int(dims) != 0:
+            return self._rowStats("var1", x, na_rm, center, dims)
+        return self._rowStats_composed("var1", x, na_rm, center, dims)
 
     def rowSds(self, x, na_rm=False, center=None, dims=1):
+        if self._has_rowStatsFull() and int(dims) != 0 and not x.na_background:
+            return self._rowStats("sd1", x, na_rm, center, dims)
         with np.errstate(all="ignore"):
             return np.sqrt(self.rowVars(x, na_rm, center, dims))
 

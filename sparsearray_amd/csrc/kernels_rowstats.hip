@@ -11,7 +11,12 @@
 //   sum-like ops : IEEE addition (NA/NaN propagate by themselves)
 //   min / max    : "any NA wins, else any NaN wins, else the extremum", plus
 //                  the implicit zero when a cell is covered fewer than
-//                  nstrata times (:914-961)
+//                  nstrata times (:914-961); range is both in one walk
+//   any / all    : three flag bits and the coverage (the rules of colstats_final,
+//                  kernels_colstats.hip, on a row cell with nstrata - cov zeros)
+//   prod         : IEEE multiplication, NA / NaN flags and the coverage.  Like the
+//                  sums, the products are formed in the order the lanes arrive, not
+//                  in the reference's: results are not bit-reproducible
 // Roofline: HBM (12 B per nonzero + the dense output); the atomic rate of the
 // memory side is the practical bound for scattered 8-byte adds.
 #include "svt_common.h"
@@ -19,6 +24,8 @@
 #define RF_NA   1
 #define RF_NAN  2
 #define RF_HAVE 4
+#define RF_TRUE 8       // any / all: a non-NA value != 0
+#define RF_ZERO 16      // any / all: a stored value == 0
 
 // --------------------------------------------------------------------------
 // row stats
@@ -45,10 +52,13 @@ size_t rowstats_scratch_bytes(int opcode, int64_t out_len)
 	return (size_t) out_len * 16 + 16;
 }
 
-// The three rules below are the whole of the reference's row statistics; every route states them through these
-// functions.  A cell is entry `i` of four arrays -- `acc` (a double; an int flag for anyNA on a zero background; an
-// ordered 64-bit key for min / max), `cen` (centered_X2_sum), `flg` and `cov` (min / max, and the coverage under the
-// NaArray background) -- which live in `out` / the min-max scratch on the memory-atomic route and in LDS on the others.
+// The three rules below are the whole of the reference's row statistics (and of the row forms of any / all / prod /
+// range, which the reference composes from a transposition and the column statistics); every route states them
+// through these functions.  A cell is entry `i` of five arrays -- `acc` (a double; an int flag for anyNA on a zero
+// background; an ordered 64-bit key for min / max / the minimum of range), `hi` (the maximum of range), `cen`
+// (centered_X2_sum), `flg` and `cov` (min / max / range / any / all / prod, and the coverage under the NaArray
+// background) -- which live in `out` / the min-max scratch on the memory-atomic route and in LDS on the others.
+// any / all / prod / range are served by the LDS row-panel form only.
 // NABG: the route can see a NaArray operand at all (`nabg`: this one is); cells covered fewer than nstrata times then
 // hold implicit NAs:
 //   countNAs / anyNA: count the stored non-NA values, result nstrata - count (!= 0)
@@ -60,12 +70,17 @@ size_t rowstats_scratch_bytes(int opcode, int64_t out_len)
 // the LDS routes keep c for the update rule (NULL: the rule reads a.center itself).
 template <bool NABG, typename I>
 __device__ __forceinline__ void rowstats_init_cell(const RowStatsArgs &a, const bool nabg, const bool first,
-						   const int64_t cell, const I i, void *acc, double *cen, int *flg,
-						   unsigned int *cov)
+						   const int64_t cell, const I i, void *acc, unsigned long long *hi,
+						   double *cen, int *flg, unsigned int *cov)
 {
 	const int oc = a.opcode;
-	if (oc == SVT_OP_MIN || oc == SVT_OP_MAX) {
-		((unsigned long long *) acc)[i] = oc == SVT_OP_MIN ? ~0ULL : 0ULL;
+	if (oc == SVT_OP_MIN || oc == SVT_OP_MAX || oc == SVT_OP_RANGE) {
+		((unsigned long long *) acc)[i] = oc == SVT_OP_MAX ? 0ULL : ~0ULL;
+		if (oc == SVT_OP_RANGE) hi[i] = 0ULL;
+		flg[i] = 0;
+		cov[i] = 0;
+	} else if (oc == SVT_OP_ANY || oc == SVT_OP_ALL || oc == SVT_OP_PROD) {
+		if (oc == SVT_OP_PROD) ((double *) acc)[i] = 1.0;
 		flg[i] = 0;
 		cov[i] = 0;
 	} else if (oc == SVT_OP_CENTERED_X2_SUM) {
@@ -83,7 +98,8 @@ __device__ __forceinline__ void rowstats_init_cell(const RowStatsArgs &a, const 
 // one nonzero into its cell
 template <typename T, bool NABG, typename I>
 __device__ __forceinline__ void rowstats_update(const int oc, const bool narm, const bool nabg, const T v, const I i,
-						void *acc, const double *cen, int *flg, unsigned int *cov)
+						void *acc, unsigned long long *hi, const double *cen, int *flg,
+						unsigned int *cov)
 {
 	const bool is_dbl = sizeof(T) == 8;
 	const bool bg = NABG && nabg;
@@ -109,7 +125,29 @@ __device__ __forceinline__ void rowstats_update(const int oc, const bool narm, c
 		atomicAdd(accd + i, x * (x - 2 * c));
 		break;
 	}
-	default: {               // min / max, :537-597
+	case SVT_OP_ANY: case SVT_OP_ALL:   // src/Rvector_summarization.c:260-313; ints and logicals only
+		atomicAdd(cov + i, 1u);
+		atomicOr(flg + i, miss ? RF_NA : (v != (T) 0 ? RF_TRUE : RF_ZERO));
+		break;
+	case SVT_OP_PROD: {      // a missing value: skipped (na.rm); else an NA is flagged, a NaN / NA_real_ takes part
+		atomicAdd(cov + i, 1u);
+		if (miss) {
+			if (narm) break;
+			if (!is_dbl || svt_is_na((double) v)) atomicOr(flg + i, RF_NA);
+			if (!is_dbl) break;
+		}
+		// LDS has no atomic multiply: a 64-bit compare-and-swap loop (the lanes of a leaf segment hit different
+		// rows, so a retry needs two segments of one round on the same row at the same moment).  The first guess is
+		// a plain read: a stale one costs a retry, never a wrong product
+		unsigned long long *p = (unsigned long long *) acc + i, seen = *p, was;
+		do {
+			was = seen;
+			const double m = __longlong_as_double((long long) was) * (double) v;
+			seen = atomicCAS(p, was, (unsigned long long) __double_as_longlong(m));
+		} while (seen != was);
+		break;
+	}
+	default: {               // min / max / range, :537-597
 		atomicAdd(cov + i, 1u);
 		if (miss) {
 			const bool isna = is_dbl ? svt_is_na((double) v) : true;
@@ -120,22 +158,22 @@ __device__ __forceinline__ void rowstats_update(const int oc, const bool narm, c
 		const unsigned long long key = is_dbl ?
 			f64_to_ordered((double) v) :
 			(unsigned long long) ((long long) (int) v + 0x80000000LL);
-		if (oc == SVT_OP_MIN) atomicMin((unsigned long long *) acc + i, key);
-		else atomicMax((unsigned long long *) acc + i, key);
+		if (oc != SVT_OP_MAX) atomicMin((unsigned long long *) acc + i, key);
+		if (oc != SVT_OP_MIN) atomicMax((oc == SVT_OP_RANGE ? hi : (unsigned long long *) acc) + i, key);
 	}
 	}
 }
 
-// a finished min / max cell into out[cell]: NA > NaN > extremum; the implicit zero (the NA background) joins when the
-// cell was covered fewer than nstrata times (:914-961); an int cell with nothing is NA and warns (:930-931)
+// a finished minimum (`is_min`) or maximum cell into out[cell]: NA > NaN > extremum; the implicit zero (the NA
+// background) joins when the cell was covered fewer than nstrata times (:914-961); an int cell with nothing is NA and
+// warns (:930-931).  range calls it once for each half of `out`.
 template <typename T, bool NABG>
-__device__ __forceinline__ void rowstats_minmax_finish(const RowStatsArgs &a, const bool nabg, const int64_t cell,
-						       const unsigned long long best, const int fl,
-						       const unsigned int cv)
+__device__ __forceinline__ void rowstats_minmax_finish(const RowStatsArgs &a, const bool nabg, const bool is_min,
+						       const int64_t cell, const unsigned long long best,
+						       const int fl, const unsigned int cv)
 {
 	const bool is_dbl = sizeof(T) == 8;
 	const bool bg = NABG && nabg;
-	const bool is_min = a.opcode == SVT_OP_MIN;
 	const bool narm = a.na_rm != 0;
 	const bool partial = (int64_t) cv < a.nstrata;
 	bool have = (fl & RF_HAVE) != 0;
@@ -175,7 +213,8 @@ __global__ void rowstats_init_kernel(RowStatsArgs a)
 		return;
 	const bool minmax = a.opcode == SVT_OP_MIN || a.opcode == SVT_OP_MAX;
 	MinMaxScratch ms = split_scratch(a.scratch, a.out_len);
-	rowstats_init_cell<false>(a, false, true, i, i, minmax ? (void *) ms.best : a.out, (double *) NULL, ms.flags, ms.cov);
+	rowstats_init_cell<false>(a, false, true, i, i, minmax ? (void *) ms.best : a.out, (unsigned long long *) NULL,
+				  (double *) NULL, ms.flags, ms.cov);
 }
 
 template <typename T>
@@ -195,7 +234,8 @@ rowstats_scatter_kernel(RowStatsArgs a)
 	void *acc = minmax ? (void *) ms.best : a.out;
 
 	for (int64_t k = beg + lane; k < end; k += SVT_WAVE)
-		rowstats_update<T, false>(a.opcode, a.na_rm != 0, false, val[k], base + row[k], acc, a.center, ms.flags, ms.cov);
+		rowstats_update<T, false>(a.opcode, a.na_rm != 0, false, val[k], base + row[k], acc, (unsigned long long *) NULL,
+					  a.center, ms.flags, ms.cov);
 }
 
 template <typename T>
@@ -205,7 +245,7 @@ __global__ void rowstats_minmax_finish_kernel(RowStatsArgs a)
 	if (i >= a.out_len)
 		return;
 	MinMaxScratch ms = split_scratch(a.scratch, a.out_len);
-	rowstats_minmax_finish<T, false>(a, false, i, ms.best[i], ms.flags[i], ms.cov[i]);
+	rowstats_minmax_finish<T, false>(a, false, a.opcode == SVT_OP_MIN, i, ms.best[i], ms.flags[i], ms.cov[i]);
 }
 
 // --------------------------------------------------------------------------
@@ -219,7 +259,9 @@ __global__ void rowstats_minmax_finish_kernel(RowStatsArgs a)
 // come from a table built by one binary search per (leaf, panel boundary)
 // (rowpanel_table_kernel).  Traffic: A once (12 B/nz) + the table + out once.
 // --------------------------------------------------------------------------
-// Panel length: 2048 rows by default (16 bytes of LDS per row serve every operation); the
+// Panel length: 2048 rows by default.  LDS per row: 8 bytes for the sum-like operations on a zero background and for
+// any / all (flags + coverage), 16 for the centered sum (+ the center), min / max and prod (a key or a double +
+// flags + coverage) and every NaArray operand, 24 for range (two keys + flags + coverage); the
 // sum-like operations on a zero-background operand with many rows take 8192-row panels -- four
 // times longer leaf segments (81 instead of 20 nonzeros at BASELINE config 2: whole 128-byte
 // lines instead of fragments of them) -- and, when that leaves fewer workgroups than the chip
@@ -431,14 +473,18 @@ rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t np
 	const bool narm = a.na_rm != 0;
 	const int oc = a.opcode;
 	const bool is_minmax = oc == SVT_OP_MIN || oc == SVT_OP_MAX;
+	const bool is_anyall = oc == SVT_OP_ANY || oc == SVT_OP_ALL;
 	double *accd = (double *) lds64;
 	double *cen = accd + prow;                           // centered_X2_sum only
-	int *flg = (int *) (lds64 + prow);                   // min/max only
+	unsigned long long *hi = lds64 + prow;               // range only
+	// flags and coverage (min / max / range / any / all / prod; the NaArray background): after the 64-bit cells the
+	// operation keeps (range two per row, any / all none)
+	int *flg = (int *) (lds64 + (is_anyall ? 0 : oc == SVT_OP_RANGE ? 2 * prow : prow));
 	unsigned int *cov = (unsigned int *) (flg + prow);
 	const bool nabg = a.na_bg != 0;
 
 	for (int r = tid; r < np; r += NT)
-		rowstats_init_cell<true>(a, nabg, blockIdx.z == 0, cell0 + r, r, lds64, cen, flg, cov);
+		rowstats_init_cell<true>(a, nabg, blockIdx.z == 0, cell0 + r, r, lds64, hi, cen, flg, cov);
 	__syncthreads();
 	const int32_t *__restrict__ pt0 = pt + q * a.ncol, *__restrict__ pt1 = pt0 + a.ncol;
 	rowstats_walk((const T *) a.val, a.row_idx, r0, s_lo, s_hi, G,
@@ -447,7 +493,7 @@ rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t np
 			const int64_t base = a.col_ptr[j];
 			kb = base + pt0[j]; ke = base + pt1[j];
 		},
-		[&](const T v, const int r) { rowstats_update<T, true>(oc, narm, nabg, v, r, lds64, cen, flg, cov); });
+		[&](const T v, const int r) { rowstats_update<T, true>(oc, narm, nabg, v, r, lds64, hi, cen, flg, cov); });
 	__syncthreads();
 	if (split) {                                 // partial cells of this strata range
 		for (int r = tid; r < np; r += NT) {
@@ -462,7 +508,19 @@ rowstats_panel_kernel(RowStatsArgs a, const int32_t *__restrict__ pt, int64_t np
 	for (int r = tid; r < np; r += NT) {
 		const int64_t cell = cell0 + r;
 		if (is_minmax) {
-			rowstats_minmax_finish<T, true>(a, nabg, cell, lds64[r], flg[r], cov[r]);
+			rowstats_minmax_finish<T, true>(a, nabg, oc == SVT_OP_MIN, cell, lds64[r], flg[r], cov[r]);
+		} else if (oc == SVT_OP_RANGE) {             // minima, then maxima (the layout of svt_colRanges_dgCMatrix)
+			rowstats_minmax_finish<T, true>(a, nabg, true, cell, lds64[r], flg[r], cov[r]);
+			rowstats_minmax_finish<T, true>(a, nabg, false, a.out_len + cell, hi[r], flg[r], cov[r]);
+		} else if (is_anyall || oc == SVT_OP_PROD) {
+			// colstats_final (kernels_colstats.hip) on a row cell: nstrata - cov implicit zeros
+			const bool brk_na = (flg[r] & RF_NA) && !narm, zeros = (int64_t) cov[r] < a.nstrata;
+			if (oc == SVT_OP_ANY)
+				((int *) a.out)[cell] = (flg[r] & RF_TRUE) ? 1 : (brk_na ? NA_INT : 0);
+			else if (oc == SVT_OP_ALL)
+				((int *) a.out)[cell] = ((flg[r] & RF_ZERO) || zeros) ? 0 : (brk_na ? NA_INT : 1);
+			else        // (Inf or NaN with an implicit zero gives NaN, as on the column side)
+				((double *) a.out)[cell] = brk_na ? svt_na_real() : (zeros ? accd[r] * 0.0 : accd[r]);
 		} else if (nabg && (oc == SVT_OP_ANYNA || oc == SVT_OP_COUNTNAS)) {
 			const double nas = (double) a.nstrata - accd[r];
 			if (oc == SVT_OP_ANYNA) ((int *) a.out)[cell] = nas != 0.0;
@@ -496,7 +554,8 @@ rowstats_whole_kernel(RowStatsArgs a, int G)
 	double *cen = accd + np;                             // centered_X2_sum only
 	const int64_t cell0 = i * a.nrow;
 	for (int r = tid; r < np; r += NT)
-		rowstats_init_cell<false>(a, false, true, cell0 + r, r, lds64, cen, (int *) NULL, (unsigned int *) NULL);
+		rowstats_init_cell<false>(a, false, true, cell0 + r, r, lds64, (unsigned long long *) NULL, cen, (int *) NULL,
+					  (unsigned int *) NULL);
 	__syncthreads();
 	rowstats_walk((const T *) a.val, a.row_idx, 0, 0, a.nstrata, G,
 		[&](const int64_t s, int64_t &kb, int64_t &ke) {
@@ -504,7 +563,8 @@ rowstats_whole_kernel(RowStatsArgs a, int G)
 			kb = a.col_ptr[j]; ke = a.col_ptr[j + 1];
 		},
 		[&](const T v, const int r) {
-			rowstats_update<T, false>(oc, narm, false, v, r, lds64, cen, (int *) NULL, (unsigned int *) NULL);
+			rowstats_update<T, false>(oc, narm, false, v, r, lds64, (unsigned long long *) NULL, cen, (int *) NULL,
+						  (unsigned int *) NULL);
 		});
 	__syncthreads();
 	for (int r = tid; r < np; r += NT) {
@@ -537,7 +597,8 @@ rowstats_whole_pipe_kernel(RowStatsArgs a, int64_t nchunks)
 	// (sums and NA counts only: the rule's other operations fold away)
 	const int oc = a.opcode == SVT_OP_COUNTNAS ? SVT_OP_COUNTNAS : SVT_OP_SUM;
 	auto apply = [&](const T v, const int r) {
-		rowstats_update<T, false>(oc, narm, false, v, r, lds64, (const double *) NULL, (int *) NULL, (unsigned int *) NULL);
+		rowstats_update<T, false>(oc, narm, false, v, r, lds64, (unsigned long long *) NULL, (const double *) NULL,
+					  (int *) NULL, (unsigned int *) NULL);
 	};
 	int64_t kb[U], ke[U];
 	T v[U][TT];
@@ -733,7 +794,10 @@ static RowStatsRoute rowstats_route(const RowStatsArgs &a)
 		if (rt.nsplit > 1024) rt.nsplit = 1024;
 		if (rt.nsplit < 1) rt.nsplit = 1;
 	}
-	rt.lds = sumlike && !a.na_bg ? (size_t) prow * (centered ? 16 : 8) : (size_t) prow * 16;
+	// bytes of LDS per row (see ROWPANEL_MIN)
+	const bool anyall = oc == SVT_OP_ANY || oc == SVT_OP_ALL;
+	const int per_row = oc == SVT_OP_RANGE ? 24 : a.na_bg ? 16 : (sumlike && !centered) || anyall ? 8 : 16;
+	rt.lds = (size_t) prow * per_row;
 	return rt;
 }
 
@@ -792,9 +856,86 @@ int launch_rowstats_panel(const RowStatsArgs &a, void *ws, hipStream_t s)
 	return 0;
 }
 
-// memory atomics
+// What the table of run bounds in `ws` depends on besides the operand: the panel shift of the shape's route, 0
+// when its form reads no table.  Two passes over one operand with the same nonzero key share the table.
+int rowstats_table_key(const RowStatsArgs &a)
+{
+	const RowStatsRoute rt = rowstats_route(a);
+	return rt.form == RS_PANEL ? rt.ps : 0;
+}
+
+// mean / var1 / sd1 in one call: the R methods compose them from rowSums, rowCountNAs and the centered sum
+// (R/SparseArray-matrixStats.R:511-516, 645-660) with a trip to the host between them; here the passes follow each
+// other on the stream, joined by this elementwise kernel.  Plain IEEE arithmetic, the expressions of the R code:
+//   nvals = nstrata - nas (nas == NULL: nstrata);  MODE 0: dst = num / nvals (the mean, the center)
+//   MODE 1: dst = num / (nvals - 1) (var1);  MODE 2: its square root (sd1).  No "fewer than two values" rule.
+// `dst` may be `num`.
+__global__ void rowstats_moments_kernel(int mode, int64_t n, double nstrata, const double *num, const double *nas,
+					double *dst)
+{
+	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n)
+		return;
+	const double nvals = nas ? nstrata - nas[i] : nstrata;
+	const double q = mode == 0 ? num[i] / nvals : num[i] / (nvals - 1.0);
+	dst[i] = mode == 2 ? sqrt(q) : q;
+}
+
+size_t rowstats_fused_ws_bytes(int64_t out_len)
+{
+	return (size_t) (out_len > 0 ? out_len : 0) * 24 + 64;     // sums, NA counts, center
+}
+
+// a.opcode: SVT_OP_MEAN, SVT_OP_VAR1 or SVT_OP_SD1 on a zero-background operand with at most 65535 output columns;
+// a.center: the caller's center (device) or NULL; `ws`: rowstats_panel_ws_bytes() bytes for the table, which is built
+// by the first pass that needs it and read by the others; `fws`: rowstats_fused_ws_bytes() bytes.
+int launch_rowstats_fused(const RowStatsArgs &a, void *ws, void *fws, hipStream_t s)
+{
+	if (a.out_len <= 0)
+		return 0;
+	double *sums = (double *) fws, *nas = sums + a.out_len, *center = nas + a.out_len;
+	RowStatsArgs p = a;
+	int built = 0;
+	auto pass = [&](const int opcode, const double *c, double *out) {
+		p.opcode = opcode; p.center = c; p.out = out;
+		const int key = rowstats_table_key(p);
+		p.table_mode = key != 0 && key == built ? ROWSTATS_TABLE_READY : ROWSTATS_TABLE_BUILD;
+		if (key != 0) built = key;
+		return launch_rowstats_panel(p, ws, s);
+	};
+	const unsigned nb = (unsigned) ((a.out_len + 255) / 256);
+	auto moments = [&](const int mode, const double *num, double *dst) {
+		hipLaunchKernelGGL(rowstats_moments_kernel, dim3(nb), dim3(256), 0, s, mode, a.out_len, (double) a.nstrata, num,
+				   a.na_rm ? (const double *) nas : (const double *) NULL, dst);
+	};
+	if (a.na_rm && pass(SVT_OP_COUNTNAS, NULL, nas))
+		return -1;
+	if (a.opcode == SVT_OP_MEAN) {
+		if (pass(SVT_OP_SUM, NULL, sums))
+			return -1;
+		moments(0, sums, (double *) a.out);
+	} else {
+		const double *c = a.center;
+		if (c == NULL) {
+			if (pass(SVT_OP_SUM, NULL, sums))
+				return -1;
+			moments(0, sums, center);
+			c = center;
+		}
+		if (pass(SVT_OP_CENTERED_X2_SUM, c, (double *) a.out))
+			return -1;
+		moments(a.opcode == SVT_OP_SD1 ? 2 : 1, (const double *) a.out, (double *) a.out);
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// memory atomics (the six operations of the reference's C_rowStats_SVT only)
 int launch_rowstats(const RowStatsArgs &a, hipStream_t s)
 {
+	if (a.opcode != SVT_OP_COUNTNAS && a.opcode != SVT_OP_ANYNA && a.opcode != SVT_OP_MIN && a.opcode != SVT_OP_MAX &&
+	    a.opcode != SVT_OP_SUM && a.opcode != SVT_OP_CENTERED_X2_SUM)
+		return svt_set_unsupported("row statistics: this operation is not served with more than 65535 output columns");
 	if (a.out_len <= 0)
 		return 0;
 	const bool is_dbl = a.Rtype == SVT_REALSXP;

@@ -174,6 +174,8 @@ size_t rowstats_scratch_bytes(int opcode, int64_t out_len);
 int launch_rowstats(const RowStatsArgs &a, hipStream_t s);      // memory atomics
 size_t rowstats_panel_ws_bytes(int64_t nrow, int64_t ncol);
 int launch_rowstats_panel(const RowStatsArgs &a, void *ws, hipStream_t s);      // LDS row panels
+size_t rowstats_fused_ws_bytes(int64_t out_len);
+int launch_rowstats_fused(const RowStatsArgs &a, void *ws, void *fws, hipStream_t s);   // mean / var1 / sd1
 void launch_rowpanel_table(const int64_t *col_ptr, const int32_t *row_idx, int64_t ncol, int64_t nnz_hint,
 			   int64_t npan, int ps, int32_t *pt, hipStream_t s);
 bool launch_rowpanel_table_scan(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,

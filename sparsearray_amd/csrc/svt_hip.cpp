@@ -958,6 +958,80 @@ extern "C" int svt_dev_rowsums_prepared(const svt_dev_csc *A, int na_rm, int64_t
 	return dev_rowsums(A, na_rm, inner, out, ws, ws_bytes, stream, ROWSTATS_TABLE_READY);
 }
 
+// ---- every row statistic in one call (svt_dev_rowstats, svt_rowStatsFull_SVT) ----
+static bool rowstats_reference_op(int opcode)       // the six of C_rowStats_SVT
+{
+	return opcode == SVT_OP_COUNTNAS || opcode == SVT_OP_ANYNA || opcode == SVT_OP_MIN || opcode == SVT_OP_MAX ||
+		opcode == SVT_OP_SUM || opcode == SVT_OP_CENTERED_X2_SUM;
+}
+static bool rowstats_fused_op(int opcode)
+{
+	return opcode == SVT_OP_MEAN || opcode == SVT_OP_VAR1 || opcode == SVT_OP_SD1;
+}
+// the checks of C_rowStats_SVT for the thirteen operations taken here
+static int check_rowstats_op(int opcode, int Rtype, int na_background)
+{
+	if (check_stat_op(opcode, Rtype))
+		return -1;
+	if (opcode == SVT_OP_SUM_X_X2 || opcode == SVT_OP_VAR2 || opcode == SVT_OP_SD2)
+		return svt_set_unsupported("op code %d is not reachable from the R API for col/row stats and is not "
+					   "implemented on the device", opcode);
+	// :639-642; rowAnys / Alls / Prods / Means / Vars / Sds have no NaArray methods (R/NaArray-matrixStats.R:187-330)
+	if (na_background && opcode != SVT_OP_RANGE && (opcode == SVT_OP_CENTERED_X2_SUM || !rowstats_reference_op(opcode)))
+		return svt_set_error("operation not yet supported on NaArray objects");
+	return 0;
+}
+
+// workspace: the table of run bounds | sums, NA counts, center (mean / var1 / sd1) | the min / max scratch of the
+// memory-atomic route (more than 65535 output columns)
+static size_t rowstats_ws_table_bytes(const svt_dev_csc *A)
+{
+	return (rowstats_panel_ws_bytes(A->nrow, A->ncol) + 255) / 256 * 256;
+}
+extern "C" size_t svt_dev_rowstats_ws_bytes_op(const svt_dev_csc *A, int opcode, int64_t inner)
+{
+	const int64_t out_len = inner > 0 ? inner * A->nrow : 0;
+	size_t n = rowstats_ws_table_bytes(A);
+	if (rowstats_fused_op(opcode)) n += rowstats_fused_ws_bytes(out_len);
+	if (inner > 65535) n += rowstats_scratch_bytes(opcode, out_len);
+	return n;
+}
+
+static int dev_rowstats_impl(const svt_dev_csc *A, int opcode, int na_rm, const double *center, int64_t inner, void *out,
+			     int *warn_flag, void *ws, size_t ws_bytes, void *stream)
+{
+	if (check_rowstats_op(opcode, A->Rtype, A->na_background))
+		return -1;
+	if (inner <= 0 || A->ncol % inner != 0)
+		return svt_set_error("'inner' must divide the number of leaves");
+	const int64_t nstrata = A->ncol / inner;
+	if (nstrata > 0xFFFFFFFFLL)
+		return svt_set_unsupported("too many strata for the device coverage counters");
+	if (inner > 65535 && A->na_background)
+		return svt_set_unsupported("row statistics of NaArray objects: more than 65535 output columns");
+	if (inner > 65535 && !rowstats_reference_op(opcode))
+		return svt_set_unsupported("row statistics: this operation is not served with more than 65535 output columns");
+	if (ws_bytes < svt_dev_rowstats_ws_bytes_op(A, opcode, inner))
+		return svt_set_error("svt_dev_rowstats: workspace too small");
+	RowStatsArgs a = rowstats_args(A, opcode, na_rm, inner, nstrata, out);
+	a.center = opcode == SVT_OP_CENTERED_X2_SUM || rowstats_fused_op(opcode) ? center : NULL;
+	a.warn_flag = warn_flag;
+	char *after_table = (char *) ws + rowstats_ws_table_bytes(A);
+	if (inner > 65535) {
+		a.scratch = after_table;
+		return launch_rowstats(a, (hipStream_t) stream);
+	}
+	if (rowstats_fused_op(opcode))
+		return launch_rowstats_fused(a, ws, after_table, (hipStream_t) stream);
+	return launch_rowstats_panel(a, ws, (hipStream_t) stream);
+}
+
+extern "C" int svt_dev_rowstats(const svt_dev_csc *A, int opcode, int na_rm, const double *center, int64_t inner,
+				void *out, int *warn_flag, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] { return dev_rowstats_impl(A, opcode, na_rm, center, inner, out, warn_flag, ws, ws_bytes, stream); });
+}
+
 extern "C" size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz)
 {
 	return transpose_ws_bytes_box(nrow, nnz, box_nnz_get());
@@ -2573,6 +2647,68 @@ extern "C" int svt_rowStats_SVT(const svt_view *x, int opcode, int na_rm,
 				const double *center, int dims, void *out, int *warn)
 {
 	return abi_status([&] { return rowStats_SVT_impl(x, opcode, na_rm, center, dims, out, warn); });
+}
+
+// Every row statistic the R API offers in one call: the checks and constant fills of rowStats_SVT_impl, one
+// operand on the device (the resident cache applies), svt_dev_rowstats, one download.  Not sharded over the device list.
+static int rowStatsFull_SVT_impl(const svt_view *x, int opcode, int na_rm,
+				 const double *center, int dims, void *out, int *warn)
+{
+	*warn = 0;
+	if (ensure_init() || check_view(x) || check_stat_op(opcode, x->Rtype))
+		return -1;
+	if (dims < 1 || dims > x->ndim - 1)
+		return svt_set_error("'dims' must be >= 1 and <= %d", x->ndim - 1);
+	if (check_rowstats_op(opcode, x->Rtype, x->na_background))
+		return -1;
+	const bool range = opcode == SVT_OP_RANGE;
+	const int out_Rtype = svt_colStats_out_Rtype(opcode, x->Rtype);
+	const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
+	int64_t inner = 1, nstrata = 1;
+	for (int a = 1; a < dims; a++) inner *= x->dim[a];
+	for (int a = dims; a < x->ndim; a++) nstrata *= x->dim[a];
+	const int64_t out_len = inner * x->dim[0], nout = out_len * (range ? 2 : 1);
+	if (out_len == 0)
+		return 0;
+	if ((opcode == SVT_OP_MIN || opcode == SVT_OP_MAX || range) && nstrata == 0) {
+		// constant fill, :970-982
+		for (int64_t i = 0; i < nout; i++) {
+			if (out_Rtype == SVT_REALSXP)
+				((double *) out)[i] = (range ? i < out_len : opcode == SVT_OP_MIN) ? INFINITY : -INFINITY;
+			else
+				((int *) out)[i] = NA_INT;
+		}
+		if (out_Rtype != SVT_REALSXP) *warn = 1;
+		return 0;
+	}
+	if (nstrata > 0xFFFFFFFFLL)
+		return svt_set_unsupported("too many strata for the device coverage counters");
+	if (inner > 65535 && x->na_background)
+		return svt_set_unsupported("row statistics of NaArray objects: more than 65535 output columns");
+	if (inner > 65535 && !rowstats_reference_op(opcode))      // (before the operand is uploaded)
+		return svt_set_unsupported("row statistics: this operation is not served with more than 65535 output columns");
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	DevBuf O, C, W, T;
+	if (O.alloc((size_t) nout * osz) || W.alloc(16) || W.zero() ||
+	    T.alloc(svt_dev_rowstats_ws_bytes_op(A.h, opcode, inner)))
+		return -1;
+	if (center != NULL && C.upload(center, (size_t) out_len * 8))
+		return -1;
+	if (dev_rowstats_impl(A.h, opcode, na_rm, center ? C.as<double>() : NULL, inner, O.p, W.as<int>(), T.p,
+			      svt_dev_rowstats_ws_bytes_op(A.h, opcode, inner), 0))
+		return -1;
+	HIP_TRY(hipDeviceSynchronize());
+	int w = 0;
+	if (staged_download(out, O.p, (size_t) nout * osz)) return -1;
+	HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
+	if (w) *warn = 1;
+	return 0;
+}
+extern "C" int svt_rowStatsFull_SVT(const svt_view *x, int opcode, int na_rm,
+				    const double *center, int dims, void *out, int *warn)
+{
+	return abi_status([&] { return rowStatsFull_SVT_impl(x, opcode, na_rm, center, dims, out, warn); });
 }
 
 // ==================================================================================

@@ -77,6 +77,10 @@ def _lib():
         lib.svt_dev_rowsums.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
         lib.svt_dev_rowsums_prepare.argtypes = [c_void_p, c_int64, c_void_p, c_size_t, c_void_p]
         lib.svt_dev_rowsums_prepared.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.svt_dev_rowstats_ws_bytes_op.restype = c_size_t
+        lib.svt_dev_rowstats_ws_bytes_op.argtypes = [c_void_p, c_int, c_int64]
+        lib.svt_dev_rowstats.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]
         lib.svt_dev_rowsum.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
         lib.svt_dev_rowsum_gid_bytes.restype = c_size_t
         lib.svt_dev_rowsum_gid_bytes.argtypes = [c_void_p]
@@ -427,6 +431,33 @@ def rowsums(A: DeviceCSC, na_rm=False, inner=1, out=None, ws=None):
     _check(_lib().svt_dev_rowsums(A.handle, int(na_rm), inner, out.data_ptr(), ws.data_ptr(),
                                   ws.numel(), _stream()))
     return out
+
+
+def rowstats(A: DeviceCSC, op: str, na_rm=False, center=None, inner=1, out=None, ws=None):
+    """Any row statistic of a resident operand in one asynchronous call (include/svt_hip.h, svt_dev_rowstats): the
+    six operations of C_rowStats_SVT plus "any", "all", "prod", "range", "mean", "var1" and "sd1".  ``center``: a
+    float64 device tensor of inner * nrow elements ("centered_X2_sum", "var1", "sd1").  Returns (out, warn): ``out``
+    has inner * nrow elements, float64 or int32 by the operation and the operand's type -- "range": 2 x (inner *
+    nrow), the minima, then the maxima; ``warn`` is a device int32 tensor, nonzero when an integer min / max / range
+    cell had no value."""
+    oc = OPCODES[op]
+    dev = A.val.device
+    n = inner * A.nrow
+    rt = _lib().svt_colStats_out_Rtype(oc, A.Rtype)
+    dtype = torch.float64 if rt == REALSXP else torch.int32
+    if out is None:
+        out = torch.empty((2, n) if op == "range" else n, dtype=dtype, device=dev)
+    assert out.dtype == dtype and out.is_contiguous() and out.numel() == (2 * n if op == "range" else n)
+    if ws is None:
+        ws = torch.empty(_lib().svt_dev_rowstats_ws_bytes_op(A.handle, oc, inner), dtype=torch.uint8, device=dev)
+    cptr = None
+    if center is not None:
+        assert center.dtype == torch.float64 and center.is_cuda and center.is_contiguous() and center.numel() == n
+        cptr = center.data_ptr()
+    warn = torch.zeros(1, dtype=torch.int32, device=dev)
+    _check(_lib().svt_dev_rowstats(A.handle, oc, int(na_rm), cptr, inner, out.data_ptr(), warn.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), _stream()))
+    return out, warn
 
 
 class RowSumsPlan:
