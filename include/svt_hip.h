@@ -209,6 +209,27 @@ int svt_colMedians_SVT(const svt_view *x, int na_rm, double *out);
 /* rowMedians(x): the same on t(x), transposed on the device.  out: nrow(x) doubles. */
 int svt_rowMedians_SVT(const svt_view *x, int na_rm, double *out);
 
+/* colQuantiles(x, probs, na.rm, type = 7) of a 2-D SVT.  The reference has no method (colQuantiles and colIQRs are in
+   its list of statistics to add, R/SparseArray-matrixStats.R:5-12); the rule is matrixStats::colQuantiles(type = 7),
+   i.e. base R's quantile.default type 7, on each column's nrow values, the implicit zeros included.  With the n values
+   left after the NA rule sorted ascending as x[1..n], in IEEE double exactly as written (no fused multiply-add):
+       index = 1 + (n - 1) * p;  lo = floor(index);  hi = ceiling(index);  q = x[lo]
+       if (index > lo && x[hi] != x[lo]) { h = index - lo;  q = (1 - h) * x[lo] + h * x[hi] }
+   -Inf and +Inf as neighbours give NaN (not NA), two equal neighbours that value.  NA rule as svt_colMedians_SVT:
+   na_rm drops NA/NaN from the stored values; otherwise any NA/NaN makes every quantile of the column NA_real_; n == 0
+   gives NA_real_.  Stored zeros count among the zeros.  Integer / logical values are read as doubles.
+   probs: nprobs >= 0 doubles (host), each finite and in [0, 1] (else error "'probs' outside [0,1]", raised before
+   anything is uploaded); unsorted and repeated entries are allowed and the output keeps their order.
+   out: ncol(x) * nprobs doubles (rowQuantiles: nrow(x) * nprobs), column-major: out[j + q * ncol].  A 0-column operand
+   or nprobs == 0 writes nothing.  Errors: not 2-D, NaArray ("colQuantiles() is not supported on NaArray objects").
+   Status > 0 only for more than 2^31-1 columns; the operand's nonzero count is not limited.
+   rowQuantiles(x) is colQuantiles(t(x)) with t() on the device (boxed past 2^31 nonzeros, as for rowMedians).
+   colIQRs / rowIQRs are this call with probs = (0.25, 0.75) and Q3 - Q1 on the host.
+   These calls are not sharded over the device list of svt_set_devices(): they run on the first entry.
+   Not offered: colMads, colRanks, colOrderStats, quantile types other than 7, N-d operands, NaArray operands. */
+int svt_colQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out);
+int svt_rowQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out);
+
 /* C_summarize_SVT, src/SparseArray_summarization.c:112-142.  The result is
    left in out_d[0..1] or out_i[0..1] according to *out_Rtype. */
 int svt_summarize_SVT(const svt_view *x, int opcode, int na_rm, double center,
@@ -435,6 +456,14 @@ int svt_dev_colstats(const svt_dev_csc *A, int opcode, int na_rm,
 size_t svt_dev_colmedians_ws_bytes(int64_t nnz, int64_t ncol);
 int svt_dev_colmedians(const svt_dev_csc *A, int na_rm, double *out, void *ws, size_t ws_bytes,
 		       void *stream);
+
+/* colQuantiles on the device (see svt_colQuantiles_SVT): probs (nprobs doubles, already validated by the caller) and
+   out (ncol * nprobs doubles, out[j + q * ncol]) are device pointers; ws: svt_dev_colquantiles_ws_bytes() bytes (a
+   too small one is an error).  Asynchronous on `stream`, allocates nothing, does not synchronise: one counting
+   launch whatever nprobs is, one select launch for the (column, prob) pairs it could not decide. */
+size_t svt_dev_colquantiles_ws_bytes(int64_t nnz, int64_t ncol, int nprobs);
+int svt_dev_colquantiles(const svt_dev_csc *A, const double *probs, int nprobs, int na_rm,
+			 double *out, void *ws, size_t ws_bytes, void *stream);
 
 /* row sums: out[(j % inner) * nrow + r] = sum over the leaves j that map to
    that cell.  Every output cell is owned by one workgroup (LDS row panels, no

@@ -65,6 +65,9 @@ class CAbiDispatcher:
         if hasattr(self.lib, self.prefix + "colMedians_SVT"):      # HIP library (the oracle's is Python)
             protos["colMedians_SVT"] = (I, [V, I, P])
             protos["rowMedians_SVT"] = (I, [V, I, P])
+        if hasattr(self.lib, self.prefix + "colQuantiles_SVT"):    # HIP library (api.py states the rule in numpy)
+            protos["colQuantiles_SVT"] = (I, [V, P, I, I, P])
+            protos["rowQuantiles_SVT"] = (I, [V, P, I, I, P])
         # x %*% y in one call (device-side transposition): HIP library only
         for name, sig in (("matmul_SVT_mat", (I, [V, P, I, I, I, P])),
                           ("matmul_SVT_SVT", (I, [V, V, P])),
@@ -143,6 +146,20 @@ class CAbiDispatcher:
         xv = make_view(x)
         self._check(self._fn("rowMedians_SVT")(byref(xv), int(bool(na_rm)), _ptr(out)))
         return out
+
+    # colQuantiles / rowQuantiles, type 7 (include/svt_hip.h; HIP library only) ----
+    def _quantiles(self, fname, x, probs, na_rm, nout):
+        probs = np.ascontiguousarray(probs, dtype=np.float64)
+        out = np.zeros((nout, probs.size), dtype=np.float64, order="F")
+        xv = make_view(x)
+        self._check(self._fn(fname)(byref(xv), _ptr(probs), int(probs.size), int(bool(na_rm)), _ptr(out)))
+        return out
+
+    def C_colQuantiles_SVT(self, x: SVT_SparseArray, probs, na_rm: bool):
+        return self._quantiles("colQuantiles_SVT", x, probs, na_rm, x.dim[1] if x.ndim == 2 else 0)
+
+    def C_rowQuantiles_SVT(self, x: SVT_SparseArray, probs, na_rm: bool):
+        return self._quantiles("rowQuantiles_SVT", x, probs, na_rm, x.dim[0] if x.ndim == 2 else 0)
 
     # resident operands (include/svt_hip.h; HIP library only) --------------------
     def resident_set_limit(self, nbytes: int):

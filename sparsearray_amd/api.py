@@ -325,6 +325,107 @@ class Session:
             return self.SparseArray_Call("C_rowMedians_SVT", x, bool(na_rm))   # t(x) on the device
         return self.colMedians(self.t(x), na_rm=na_rm)
 
+    # colQuantiles / rowQuantiles / colIQRs / rowIQRs.  The reference has no method (they are in its list of statistics
+    # to add, R/SparseArray-matrixStats.R:5-12); the rule is matrixStats::colQuantiles(type = 7), i.e. base R's
+    # quantile.default type 7, on each column's nrow values with the implicit zeros included.  Not offered: colMads,
+    # colRanks, colOrderStats, other quantile types, N-d operands, NaArray operands.
+    def _check_quantiles_args(self, what, x, probs, na_rm, type):
+        if x.ndim != 2:
+            raise SparseArrayError(
+                f"the {what}() method for SparseArray objects only supports 2D "
+                "objects (i.e. SparseMatrix objects) at the moment")
+        if x.na_background:
+            raise SparseArrayError("colQuantiles() is not supported on NaArray objects")
+        if not isinstance(na_rm, (bool, np.bool_)):
+            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
+        if isinstance(type, (bool, np.bool_)) or type != 7:
+            raise SparseArrayError(f"{what}(): only type = 7 is supported")
+        try:
+            probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise SparseArrayError("'probs' must be a numeric vector")
+        if not np.all((probs >= 0.0) & (probs <= 1.0)):       # (NaN fails both comparisons)
+            raise SparseArrayError("'probs' outside [0,1]")
+        return probs
+
+    @staticmethod
+    def _leaf_quantiles(vals, nrow, probs, na_rm, ans):
+        """Type 7 quantiles of one leaf's nrow values into ans[:], without realising the zeros: the sorted column is
+        [negatives | zeros | positives], so the ranks are read out of the leaf's sorted non-NA nonzeros."""
+        miss = np.isnan(vals)
+        if miss.any():
+            if not na_rm:
+                ans[:] = NA_real
+                return
+            vals = vals[~miss]
+        n = len(vals) + (nrow - len(miss))            # na.rm drops stored values; the padding keeps its size
+        if n == 0:
+            ans[:] = NA_real
+            return
+        nz = np.sort(vals[vals != 0.0])               # (a stored zero counts among the zeros)
+        neg = int((nz < 0.0).sum())
+        zeros = n - len(nz)
+
+        def value(r):                                 # 0-based rank of the virtual column
+            return float(nz[r]) if r < neg else 0.0 if r < neg + zeros else float(nz[r - zeros])
+
+        for q, p in enumerate(probs.tolist()):
+            index = 1 + (n - 1) * p                   # plain IEEE double: one product, one sum
+            lo, hi = int(np.floor(index)), int(np.ceil(index))
+            xlo = value(lo - 1)
+            if index > lo:
+                xhi = value(hi - 1)
+                if xhi != xlo:
+                    h = index - lo
+                    xlo = (1 - h) * xlo + h * xhi     # two products and one sum, each rounded (Inf - Inf: NaN)
+            ans[q] = xlo
+
+    def colQuantiles(self, x, probs=(0.0, 0.25, 0.5, 0.75, 1.0), na_rm=False, type=7):
+        """colQuantiles(x, probs, na.rm, type = 7): an (ncol, P) array, the columns in the order of ``probs``."""
+        probs = self._check_quantiles_args("colQuantiles", x, probs, na_rm, type)
+        nrow, ncol = x.dim
+        if nrow == 0:
+            return np.full((ncol, probs.size), NA_real)
+        has = getattr(self._call, "has_entry", lambda name: False)
+        if has("C_colQuantiles_SVT"):
+            return self.SparseArray_Call("C_colQuantiles_SVT", x, probs, bool(na_rm))
+        # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
+        ans = np.zeros((ncol, probs.size))
+        for j, lf in enumerate(x.leaves):
+            if lf is None:
+                vals = np.zeros(0)
+            elif lf[1] is None:                       # lacunar leaf: all ones
+                vals = np.ones(len(lf[0]))
+            else:
+                raw = np.asarray(lf[1])
+                vals = raw.astype(np.float64)
+                if raw.dtype != np.float64:
+                    vals[raw == NA_integer] = np.nan
+            self._leaf_quantiles(vals, nrow, probs, bool(na_rm), ans[j])
+        return ans
+
+    def rowQuantiles(self, x, probs=(0.0, 0.25, 0.5, 0.75, 1.0), na_rm=False, type=7):
+        """rowQuantiles(x) = colQuantiles(t(x)): an (nrow, P) array."""
+        probs = self._check_quantiles_args("rowQuantiles", x, probs, na_rm, type)
+        has = getattr(self._call, "has_entry", lambda name: False)
+        if has("C_rowQuantiles_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
+            return self.SparseArray_Call("C_rowQuantiles_SVT", x, probs, bool(na_rm))   # t(x) on the device
+        return self.colQuantiles(self.t(x), probs=probs, na_rm=na_rm)
+
+    @staticmethod
+    def _iqr(q):
+        with np.errstate(invalid="ignore"):
+            d = q[:, 1] - q[:, 0]                     # Q3 - Q1
+        d[is_NA_real(q[:, 0]) | is_NA_real(q[:, 1])] = NA_real
+        return d
+
+    def colIQRs(self, x, na_rm=False):
+        """colIQRs(x, na.rm): one colQuantiles call with probs = (0.25, 0.75), then Q3 - Q1."""
+        return self._iqr(self.colQuantiles(x, (0.25, 0.75), na_rm=na_rm))
+
+    def rowIQRs(self, x, na_rm=False):
+        return self._iqr(self.rowQuantiles(x, (0.25, 0.75), na_rm=na_rm))
+
     def _rowStats(self, op, x, na_rm=False, center=None, dims=1):
         # .rowStats_SparseArray, R/SparseArray-matrixStats.R:197-259
         dims = int(dims)

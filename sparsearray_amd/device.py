@@ -72,6 +72,9 @@ def _lib():
         lib.svt_dev_colmedians_ws_bytes.restype = c_size_t
         lib.svt_dev_colmedians_ws_bytes.argtypes = [c_int64, c_int64]
         lib.svt_dev_colmedians.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.svt_dev_colquantiles_ws_bytes.restype = c_size_t
+        lib.svt_dev_colquantiles_ws_bytes.argtypes = [c_int64, c_int64, c_int]
+        lib.svt_dev_colquantiles.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
         lib.svt_dev_rowstats_ws_bytes.restype = c_size_t
         lib.svt_dev_rowstats_ws_bytes.argtypes = [c_int64, c_int64]
         lib.svt_dev_rowsums.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -336,6 +339,29 @@ def colmedians(A: DeviceCSC, na_rm=False, out=None, ws=None):
                          device=A.val.device)
     _check(_lib().svt_dev_colmedians(A.handle, int(na_rm), out.data_ptr(), ws.data_ptr(),
                                      ws.numel(), _stream()))
+    return out
+
+
+def colquantiles(A: DeviceCSC, probs, na_rm=False, out=None, ws=None):
+    """colQuantiles(type = 7) of a resident 2-D operand (include/svt_hip.h, svt_dev_colquantiles).  ``probs``: a
+    sequence, or a float64 tensor already on the device (every entry finite and in [0, 1]: checked here for a
+    sequence, the caller's promise for a tensor).  Returns the (P, ncol) C-contiguous tensor that is the
+    column-major ncol x P result."""
+    dev = A.val.device
+    if not isinstance(probs, torch.Tensor):
+        p = np.asarray(probs, dtype=np.float64).reshape(-1)
+        if not np.all((p >= 0.0) & (p <= 1.0)):
+            raise SparseArrayError("'probs' outside [0,1]")
+        probs = torch.as_tensor(p, device=dev)
+    assert probs.dtype == torch.float64 and probs.is_cuda and probs.is_contiguous()
+    P = int(probs.numel())
+    if out is None:
+        out = torch.empty((P, A.ncol), dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == P * A.ncol
+    if ws is None:
+        ws = torch.empty(_lib().svt_dev_colquantiles_ws_bytes(A.nnz, A.ncol, P), dtype=torch.uint8, device=dev)
+    _check(_lib().svt_dev_colquantiles(A.handle, probs.data_ptr(), P, int(na_rm), out.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), _stream()))
     return out
 
 

@@ -1,0 +1,209 @@
+"""colQuantiles() / rowQuantiles() / colIQRs() / rowIQRs(): the reference has no method; the rule is base R's
+quantile.default type 7 on each column's nrow values, the implicit zeros included (include/svt_hip.h).  Here the
+host statement of sparsearray_amd/api.py (what the oracle session runs: its dispatcher has no entry point) is checked
+against the plain definition on the dense column, at tolerance 0: both sides evaluate the same IEEE operations."""
+import numpy as np
+import pytest
+
+from helpers import assert_equal
+from sparsearray_amd import NA_integer, NA_real, SVT_SparseArray, SparseArrayError, is_NA_real
+
+PROBS_SETS = [
+    (0, 0.25, 0.5, 0.75, 1),
+    (0.5,),
+    (1 / 3, 0.1, 0.9, 0.999, 1e-9),
+    (0.75, 0.25, 0.25),
+    (),
+]
+
+
+def dense_colquantiles(a, probs, na_rm):
+    """quantile(type = 7) of every column of the dense matrix ``a`` (NaN = missing), R's rule as written:
+    index = 1 + (n - 1) * p; lo = floor(index); hi = ceiling(index); q = x[lo];
+    if (index > lo && x[hi] != x[lo]) { h = index - lo; q = (1 - h) * x[lo] + h * x[hi] }."""
+    a = np.asarray(a, dtype=np.float64)
+    probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+    out = np.empty((a.shape[1], probs.size))
+    with np.errstate(all="ignore"):
+        for j in range(a.shape[1]):
+            col = a[:, j]
+            miss = np.isnan(col)
+            if miss.any() and not na_rm:
+                out[j] = NA_real
+                continue
+            x = np.sort(col[~miss])
+            n = x.size
+            if n == 0:
+                out[j] = NA_real
+                continue
+            for q, p in enumerate(probs):
+                index = 1 + (n - 1) * p
+                lo, hi = int(np.floor(index)), int(np.ceil(index))
+                v = x[lo - 1]
+                if index > lo and x[hi - 1] != x[lo - 1]:
+                    h = index - lo
+                    v = (1 - h) * x[lo - 1] + h * x[hi - 1]
+                out[j, q] = v
+    return out
+
+
+def dense_iqrs(a, na_rm):
+    q = dense_colquantiles(a, (0.25, 0.75), na_rm)
+    with np.errstate(all="ignore"):
+        d = q[:, 1] - q[:, 0]
+    d[is_NA_real(q[:, 0]) | is_NA_real(q[:, 1])] = NA_real
+    return d
+
+
+def quantile_cases():
+    """The colMedians case families of tests/test_medians.py, plus infinities as the two neighbours."""
+    rng = np.random.default_rng(5)
+    cases = []
+    # man/SparseArray-matrixStats.Rd:183-187 (the 2D example object)
+    m0 = np.zeros(24, dtype=np.int32)
+    m0[np.array([1, 2, 8, 10, 15, 16, 17, 24]) - 1] = np.arange(1, 9) * 10
+    m0 = np.asfortranarray(m0.reshape((6, 4), order="F"))
+    m0[4, 1] = NA_integer
+    cases.append(("man page m0", m0, "integer"))
+    for nrow in (1, 2, 7, 8):
+        a = np.round(rng.normal(size=(nrow, 40)), 1)
+        a[rng.random(a.shape) < 0.5] = 0.0
+        cases.append((f"small {nrow}", a, "double"))
+    a = np.round(rng.normal(size=(101, 60)), 2)
+    a[rng.random(a.shape) < 0.6] = 0.0
+    a[:, 0] = 0.0                                   # empty leaf
+    a[:, 1] = np.abs(a[:, 1]) + 1                   # all positive
+    a[:, 2] = -np.abs(a[:, 2]) - 1                  # all negative
+    a[:51, 3] = 5.0; a[51:, 3] = 0.0                # bare majority of positives, odd n
+    a[3, 4] = np.nan
+    a[5, 5] = NA_real
+    a[7, 6] = np.inf
+    a[:, 7] = np.nan                                # nothing left under na.rm
+    a[9, 8] = -np.inf
+    cases.append(("mixed 101", a, "double"))
+    b = a[:100].copy()                              # even n
+    b[:50, 9] = 2.0; b[50:, 9] = 0.0                # exactly half positive
+    b[:50, 10] = -2.0; b[50:, 10] = 0.0             # exactly half negative
+    b[:50, 11] = -2.0; b[50:, 11] = 3.0             # half / half, no zeros
+    cases.append(("mixed 100", b, "double"))
+    c = rng.integers(-5, 6, (64, 30)).astype(np.int32)
+    c[rng.random(c.shape) < 0.5] = 0
+    c[2, 3] = NA_integer
+    cases.append(("int 64", c, "integer"))
+    # -Inf / +Inf as neighbours: NaN, not NA; two equal infinities: that infinity
+    inf = np.inf
+    d = np.array([[-inf, inf, -inf, -inf, 0.0, inf, np.nan],
+                  [inf, inf, -inf, 0.0, inf, -inf, inf]])
+    cases.append(("infinite neighbours", d, "double"))
+    e = np.zeros((4, 3))
+    e[:, 0] = [-inf, -inf, inf, inf]
+    e[:, 1] = [-inf, 1.0, 2.0, inf]
+    e[:, 2] = [inf, 0.0, 0.0, -inf]
+    cases.append(("infinite neighbours 4", e, "double"))
+    return cases
+
+
+def as_float(a, type_):
+    f = np.asarray(a, dtype=np.float64).copy()
+    if type_ == "integer":
+        f[np.asarray(a) == NA_integer] = np.nan
+    return f
+
+
+def check_session_on_cases(session, na_rm, what):
+    for name, a, type_ in quantile_cases():
+        x = SVT_SparseArray.from_dense(np.asfortranarray(a), type_)
+        f = as_float(a, type_)
+        for probs in PROBS_SETS:
+            got = session.colQuantiles(x, probs, na_rm=na_rm)
+            assert got.shape == (a.shape[1], len(probs))
+            assert_equal(got, dense_colquantiles(f, probs, na_rm), tol=0, strict_na=True,
+                         what=f"{what} {name} {probs}")
+            got = session.rowQuantiles(x, probs, na_rm=na_rm)
+            assert got.shape == (a.shape[0], len(probs))
+            assert_equal(got, dense_colquantiles(f.T, probs, na_rm), tol=0, strict_na=True,
+                         what=f"{what} {name} rows {probs}")
+
+
+@pytest.mark.parametrize("na_rm", [False, True])
+def test_host_statement_is_the_dense_rule(oracle, na_rm):
+    check_session_on_cases(oracle, na_rm, "oracle")
+
+
+def test_infinite_neighbours_give_nan_not_na(oracle):
+    d = np.array([[-np.inf], [np.inf]])
+    q = oracle.colQuantiles(SVT_SparseArray.from_dense(np.asfortranarray(d), "double"), (0.0, 0.5, 1.0))
+    assert q[0, 0] == -np.inf and q[0, 2] == np.inf
+    assert np.isnan(q[0, 1]) and not is_NA_real(q[0, 1])
+
+
+def test_default_probs(oracle):
+    _, a, type_ = quantile_cases()[5]
+    x = SVT_SparseArray.from_dense(np.asfortranarray(a), type_)
+    assert_equal(oracle.colQuantiles(x), dense_colquantiles(a, (0, 0.25, 0.5, 0.75, 1), False), tol=0,
+                 strict_na=True)
+
+
+@pytest.mark.parametrize("na_rm", [False, True])
+def test_half_is_the_median(oracle, na_rm):
+    """None of these operands holds values near the overflow or subnormal range, where (a + b) / 2 and
+    a / 2 + b / 2 could differ."""
+    for name, a, type_ in quantile_cases():
+        x = SVT_SparseArray.from_dense(np.asfortranarray(a), type_)
+        assert_equal(oracle.colQuantiles(x, (0.5,), na_rm=na_rm)[:, 0], oracle.colMedians(x, na_rm=na_rm),
+                     tol=0, strict_na=True, what=name)
+        assert_equal(oracle.rowQuantiles(x, (0.5,), na_rm=na_rm)[:, 0], oracle.rowMedians(x, na_rm=na_rm),
+                     tol=0, strict_na=True, what=name + " rows")
+
+
+@pytest.mark.parametrize("na_rm", [False, True])
+def test_iqrs(oracle, na_rm):
+    for name, a, type_ in quantile_cases():
+        x = SVT_SparseArray.from_dense(np.asfortranarray(a), type_)
+        f = as_float(a, type_)
+        got = oracle.colIQRs(x, na_rm=na_rm)
+        assert got.shape == (a.shape[1],)
+        assert_equal(got, dense_iqrs(f, na_rm), tol=0, strict_na=True, what=name)
+        got = oracle.rowIQRs(x, na_rm=na_rm)
+        assert got.shape == (a.shape[0],)
+        assert_equal(got, dense_iqrs(f.T, na_rm), tol=0, strict_na=True, what=name + " rows")
+
+
+def test_zero_extents(oracle):
+    x0 = SVT_SparseArray((0, 3), "double", [None] * 3)
+    q = oracle.colQuantiles(x0)
+    assert q.shape == (3, 5) and is_NA_real(q).all()
+    assert oracle.rowQuantiles(x0).shape == (0, 5)
+    assert is_NA_real(oracle.colIQRs(x0)).all() and oracle.colIQRs(x0).shape == (3,)
+    x1 = SVT_SparseArray((4, 0), "double", [])
+    assert oracle.colQuantiles(x1, (0.1, 0.2)).shape == (0, 2)
+    r = oracle.rowQuantiles(x1, (0.1, 0.2))
+    assert r.shape == (4, 2) and is_NA_real(r).all()
+    x = SVT_SparseArray.from_dense(np.asfortranarray(np.eye(3)), "double")
+    assert oracle.colQuantiles(x, ()).shape == (3, 0)
+    assert oracle.rowQuantiles(x, ()).shape == (3, 0)
+
+
+def test_argument_checks(oracle):
+    x = SVT_SparseArray.from_dense(np.asfortranarray(np.eye(3)), "double")
+    x3 = SVT_SparseArray((2, 2, 2), "double", [None] * 4)
+    with pytest.raises(SparseArrayError, match=r"the colQuantiles\(\) method for SparseArray objects only supports 2D"):
+        oracle.colQuantiles(x3)
+    with pytest.raises(SparseArrayError, match=r"the rowQuantiles\(\) method for SparseArray objects only supports 2D"):
+        oracle.rowQuantiles(x3)
+    with pytest.raises(SparseArrayError, match="only supports 2D"):
+        oracle.colIQRs(x3)
+    na = SVT_SparseArray.from_dense(np.asfortranarray(np.eye(3)), "double", na_background=True)
+    for fn in (oracle.colQuantiles, oracle.rowQuantiles, oracle.colIQRs, oracle.rowIQRs):
+        with pytest.raises(SparseArrayError, match=r"colQuantiles\(\) is not supported on NaArray objects"):
+            fn(na)
+    for fn in (oracle.colQuantiles, oracle.rowQuantiles):
+        with pytest.raises(SparseArrayError, match="only type = 7 is supported"):
+            fn(x, type=5)
+        for bad in (1.5, -0.1, np.nan):
+            with pytest.raises(SparseArrayError, match=r"'probs' outside \[0,1\]"):
+                fn(x, (0.5, bad))
+        with pytest.raises(SparseArrayError, match="'na.rm' must be TRUE or FALSE"):
+            fn(x, (0.5,), na_rm=1)
+    with pytest.raises(SparseArrayError, match="'na.rm' must be TRUE or FALSE"):
+        oracle.colIQRs(x, na_rm="yes")
