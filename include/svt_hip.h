@@ -451,6 +451,22 @@ int svt_dev_colstats(const svt_dev_csc *A, int opcode, int na_rm,
 		     double center, int64_t inner, void *out, int *warn_flag,
 		     void *stream);
 
+/* Which launch form svt_dev_colstats() -- and every host entry point that ends in it: svt_colStats_SVT,
+   svt_summarize_SVT, the dgCMatrix column statistics -- takes for `nseg` generalized columns holding `nnz` nonzeros in
+   all.  A pure host query (no device, no handle), the same function the launcher calls; for tests and fuzzers that
+   must know which kernel they exercise.  The form follows from nseg and the AVERAGE length nnz / nseg alone:
+     0  one thread per column            (average < 4, at least 4096 columns)
+     1  16 lanes per column              (average < 160)
+     2  one wavefront per column         (160 <= average < 1024)
+     3  one workgroup per column, the column kept in registers for the centred pass   (1024 <= average <= 10240)
+     4  one workgroup per column, streaming   (average > 10240)
+     5  split: *nchunk workgroups per column, partial states combined in chunk order   (fewer than 512 columns,
+        average >= 65536)
+   Forms 1, 2 and 3 keep a column of at most 256, 1024 and 12288 nonzeros in registers and read a longer one
+   twice (var1, sd1, centered_X2_sum); that choice is made per column, inside the launch.
+   *nchunk (may be NULL): chunks per column for form 5, else 1. */
+int svt_dev_colstats_form(int64_t nseg, int64_t nnz, int *nchunk);
+
 /* colMedians on the device (see svt_colMedians_SVT): out = ncol doubles (device);
    ws: svt_dev_colmedians_ws_bytes() bytes (two f64 key arrays + the sort's scratch). */
 size_t svt_dev_colmedians_ws_bytes(int64_t nnz, int64_t ncol);
@@ -492,6 +508,20 @@ int svt_dev_rowsums_prepared(const svt_dev_csc *A, int na_rm, int64_t inner,
 size_t svt_dev_rowstats_ws_bytes_op(const svt_dev_csc *A, int opcode, int64_t inner);
 int svt_dev_rowstats(const svt_dev_csc *A, int opcode, int na_rm, const double *center, int64_t inner,
 		     void *out, int *warn_flag, void *ws, size_t ws_bytes, void *stream);
+
+/* Which form one pass of svt_dev_rowstats() / svt_dev_rowsums() takes for an operand of nrow x ncol leaves with `nnz`
+   nonzeros (what svt_dev_csc says of it).  A pure host query, the function the launchers call:
+     0  pipelined whole-column kernel over (output column, chunk of 64 leaves) units
+     1  pipelined whole-column kernel, one output column at a time
+     2  whole-column kernel (all rows of an output column in LDS)
+     3  row panels in LDS behind the table of run bounds; *panel_shift = log2 of the rows per panel, *nsplit = the
+        ranges the strata are cut into (cells then added to a zeroed `out`)
+     4  memory atomics (more than 65535 output columns)
+   opcode: an operation served in one pass.  SVT_OP_MEAN, _VAR1 and _SD1 queue the passes SVT_OP_COUNTNAS (na_rm),
+   SVT_OP_SUM and SVT_OP_CENTERED_X2_SUM: ask for those.  panel_shift and nsplit may be NULL; they are 0 and 1 for
+   the other forms. */
+int svt_dev_rowstats_form(int64_t nrow, int64_t ncol, int64_t nnz, int na_background, int opcode, int64_t inner,
+			  int *panel_shift, int64_t *nsplit);
 
 /* rowsum(): out (ngroup x ncol, zeroed by the callee); group is a device
    array of nrow 1-based group ids (NA -> last group).  f64 input only at

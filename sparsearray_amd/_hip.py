@@ -35,6 +35,7 @@ EXPORTS = [
     "svt_dev_crossprod_pbc_ws_bytes", "svt_dev_crossprod_pbc", "svt_dev_crossprod_pbc_phase", "svt_dev_crossprod_pbc_from",
     "svt_get_num_procs", "svt_get_max_threads", "svt_set_max_threads", "svt_dev_aperm_ws_bytes", "svt_dev_aperm_perm_ws_bytes", "svt_dev_aperm", "svt_dev_aperm_route_counts", "svt_aperm_SVT", "svt_transpose_2D_SVT", "svt_dev_transpose_ws_bytes", "svt_dev_transpose", "svt_dev_set_box_nnz", "svt_dev_boxed_calls", "svt_dev_colstats", "svt_dev_rowstats_ws_bytes", "svt_dev_rowsums", "svt_dev_rowsum",
     "svt_rowStatsFull_SVT", "svt_dev_rowstats_ws_bytes_op", "svt_dev_rowstats",
+    "svt_dev_colstats_form", "svt_dev_rowstats_form",
 ]
 
 
@@ -109,6 +110,35 @@ def set_shard_min_nnz(n: int) -> None:
     lib.svt_set_shard_min_nnz.argtypes = [ctypes.c_int64]
     lib.svt_set_shard_min_nnz.restype = None
     lib.svt_set_shard_min_nnz(int(n))
+
+
+COLSTATS_FORMS = ("thread", "lanes16", "wavefront", "workgroup_cached", "workgroup_streaming", "split")
+ROWSTATS_FORMS = ("pipe_units", "pipe", "whole_column", "panel", "memory_atomics")
+
+
+def colstats_form(nseg: int, nnz: int):
+    """(form, nchunk): the launch form of the column statistics for ``nseg`` generalized columns with ``nnz``
+    nonzeros in all, one of COLSTATS_FORMS (include/svt_hip.h, svt_dev_colstats_form).  Needs no GPU."""
+    lib = load_library()
+    lib.svt_dev_colstats_form.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]
+    lib.svt_dev_colstats_form.restype = ctypes.c_int
+    nchunk = ctypes.c_int(1)
+    form = lib.svt_dev_colstats_form(int(nseg), int(nnz), ctypes.byref(nchunk))
+    return COLSTATS_FORMS[form], nchunk.value
+
+
+def rowstats_form(nrow: int, ncol: int, nnz: int, op: str, inner: int = 1, na_background: bool = False):
+    """(form, panel_shift, nsplit): the form one pass of the row statistics takes, one of ROWSTATS_FORMS
+    (include/svt_hip.h, svt_dev_rowstats_form).  ``ncol`` counts leaves.  Needs no GPU."""
+    from .api import OPCODES
+    lib = load_library()
+    lib.svt_dev_rowstats_form.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]
+    lib.svt_dev_rowstats_form.restype = ctypes.c_int
+    ps, nsplit = ctypes.c_int(0), ctypes.c_int64(1)
+    form = lib.svt_dev_rowstats_form(int(nrow), int(ncol), int(nnz), int(bool(na_background)), OPCODES[op], int(inner),
+                                     ctypes.byref(ps), ctypes.byref(nsplit))
+    return ROWSTATS_FORMS[form], ps.value, nsplit.value
 
 
 def hip_dispatcher():

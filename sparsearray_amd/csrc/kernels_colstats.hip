@@ -591,48 +591,64 @@ static int launch_colstats_split(const StatsArgs &a, int nchunk, hipStream_t s)
 	return 0;
 }
 
+// The launch form of a shape: decided from the number of generalized columns and their AVERAGE length alone
+// (a column far from the average still takes the form of its launch; inside colstats_kernel<T, NT, CAP> it
+// then picks the register-cached or the re-read branch by its own length, nz <= NT * CAP).
+ColStatsRoute colstats_route(int64_t nseg, int64_t nnz)
+{
+	ColStatsRoute rt = { COLSTATS_LANES16, 1 };
+	if (nseg <= 0)
+		return rt;
+	const int64_t avg = nnz / nseg;
+	if (nseg < 512 && avg >= 65536 && nseg <= 65535) {
+		// few long segments: ~1024 workgroups in all, >= 16K elements each
+		int64_t nchunk = (1024 + nseg - 1) / nseg;
+		if (nchunk > avg / 16384) nchunk = avg / 16384;
+		if (nchunk >= 2) {
+			rt.form = COLSTATS_SPLIT;
+			rt.nchunk = (int) nchunk;
+			return rt;
+		}
+	}
+	if (avg >= 1024)                             // (cached: also faster for one-pass ops, all loads in flight)
+		rt.form = avg <= 256 * 40 ? COLSTATS_GROUP_CACHED : COLSTATS_GROUP_STREAM;
+	else if (avg < 4 && nseg >= 4096)
+		rt.form = COLSTATS_THREAD;
+	else if (avg < 160)                          // short leaves (config 1 / config 5, ~100 nonzeros)
+		rt.form = COLSTATS_LANES16;
+	else
+		rt.form = COLSTATS_WAVE;
+	return rt;
+}
+
+template <int NT, int CAP>
+static void launch_colstats_form(const StatsArgs &a, hipStream_t s)
+{
+	const dim3 grid((unsigned) ((a.nseg + 256 / NT - 1) / (256 / NT))), block(256);
+	if (a.Rtype == SVT_REALSXP) hipLaunchKernelGGL((colstats_kernel<double, NT, CAP>), grid, block, 0, s, a);
+	else hipLaunchKernelGGL((colstats_kernel<int, NT, CAP>), grid, block, 0, s, a);
+}
+
 int launch_colstats(const StatsArgs &a, int64_t nnz, hipStream_t s)
 {
 	if (a.nseg <= 0)
 		return 0;
 	if (a.nseg > 0x7FFFFFFFLL)
 		return svt_set_error("too many generalized columns");
-	const int64_t avg = nnz / a.nseg;
-	const bool is_dbl = a.Rtype == SVT_REALSXP;
-	if (a.nseg < 512 && avg >= 65536 && a.nseg <= 65535) {
-		// few long segments: ~1024 workgroups in all, >= 16K elements each
-		int64_t nchunk = (1024 + a.nseg - 1) / a.nseg;
-		if (nchunk > avg / 16384) nchunk = avg / 16384;
-		if (nchunk >= 2)
-			return launch_colstats_split(a, (int) nchunk, s);
+	const ColStatsRoute rt = colstats_route(a.nseg, nnz);
+	switch (rt.form) {
+	case COLSTATS_SPLIT:
+		return launch_colstats_split(a, rt.nchunk, s);
+	case COLSTATS_GROUP_CACHED: launch_colstats_form<256, 48>(a, s); break;
+	case COLSTATS_GROUP_STREAM: launch_colstats_form<256, 0>(a, s); break;
+	case COLSTATS_WAVE: launch_colstats_form<64, 16>(a, s); break;
+	case COLSTATS_LANES16: launch_colstats_form<16, 16>(a, s); break;
+	case COLSTATS_THREAD: {
+		const dim3 gridt((unsigned) ((a.nseg + 255) / 256)), block(256);
+		if (a.Rtype == SVT_REALSXP) hipLaunchKernelGGL(colstats_thread_kernel<double>, gridt, block, 0, s, a);
+		else hipLaunchKernelGGL(colstats_thread_kernel<int>, gridt, block, 0, s, a);
+		break;
 	}
-	if (avg >= 1024) {
-		dim3 grid((unsigned) a.nseg), block(256);
-		if (avg <= 256 * 40) {               // (also faster for one-pass ops: all loads in flight)
-			if (is_dbl) hipLaunchKernelGGL((colstats_kernel<double, 256, 48>), grid, block, 0, s, a);
-			else hipLaunchKernelGGL((colstats_kernel<int, 256, 48>), grid, block, 0, s, a);
-		} else {
-			if (is_dbl) hipLaunchKernelGGL((colstats_kernel<double, 256, 0>), grid, block, 0, s, a);
-			else hipLaunchKernelGGL((colstats_kernel<int, 256, 0>), grid, block, 0, s, a);
-		}
-	} else {
-		dim3 grid((unsigned) ((a.nseg + 3) / 4)), block(256);
-		if (avg < 4 && a.nseg >= 4096) {
-			dim3 gridt((unsigned) ((a.nseg + 255) / 256));
-			if (is_dbl) hipLaunchKernelGGL(colstats_thread_kernel<double>, gridt, block, 0, s, a);
-			else hipLaunchKernelGGL(colstats_thread_kernel<int>, gridt, block, 0, s, a);
-		} else if (avg < 160) {
-			// short leaves (config 1 / config 5, ~100 nonzeros): 16 lanes per segment
-			dim3 grid16((unsigned) ((a.nseg + 15) / 16));
-			if (is_dbl) hipLaunchKernelGGL((colstats_kernel<double, 16, 16>), grid16, block, 0, s, a);
-			else hipLaunchKernelGGL((colstats_kernel<int, 16, 16>), grid16, block, 0, s, a);
-		} else if (avg >= 16) {
-			if (is_dbl) hipLaunchKernelGGL((colstats_kernel<double, 64, 16>), grid, block, 0, s, a);
-			else hipLaunchKernelGGL((colstats_kernel<int, 64, 16>), grid, block, 0, s, a);
-		} else {
-			if (is_dbl) hipLaunchKernelGGL((colstats_kernel<double, 64, 0>), grid, block, 0, s, a);
-			else hipLaunchKernelGGL((colstats_kernel<int, 64, 0>), grid, block, 0, s, a);
-		}
 	}
 	HIP_TRY(hipGetLastError());
 	return 0;

@@ -719,11 +719,11 @@ bool launch_rowpanel_table_scan(const int64_t *col_ptr, const int32_t *row_idx, 
 }
 
 // The form of the LDS routes a shape takes, and what its launch needs.
-enum RowStatsForm {
-	RS_PIPE_UNITS,          // rowstats_whole_pipe_kernel<T, true>
-	RS_PIPE,                // rowstats_whole_pipe_kernel<T, false>
-	RS_WHOLE,               // rowstats_whole_kernel
-	RS_PANEL                // the table of run bounds + rowstats_panel_kernel
+enum RowStatsForm {         // (the values are those of svt_dev_rowstats_form, include/svt_hip.h)
+	RS_PIPE_UNITS = 0,      // rowstats_whole_pipe_kernel<T, true>
+	RS_PIPE = 1,            // rowstats_whole_pipe_kernel<T, false>
+	RS_WHOLE = 2,           // rowstats_whole_kernel
+	RS_PANEL = 3            // the table of run bounds + rowstats_panel_kernel
 };
 struct RowStatsRoute {
 	RowStatsForm form;
@@ -799,6 +799,14 @@ static RowStatsRoute rowstats_route(const RowStatsArgs &a)
 	const int per_row = oc == SVT_OP_RANGE ? 24 : a.na_bg ? 16 : (sumlike && !centered) || anyall ? 8 : 16;
 	rt.lds = (size_t) prow * per_row;
 	return rt;
+}
+
+int rowstats_panel_form(const RowStatsArgs &a, int *ps, int64_t *nsplit)
+{
+	const RowStatsRoute rt = rowstats_route(a);
+	*ps = rt.form == RS_PANEL ? rt.ps : 0;
+	*nsplit = rt.form == RS_PANEL ? rt.nsplit : 1;
+	return (int) rt.form;
 }
 
 // the double or the int instantiation of a row-statistics kernel, ROWPANEL_NT lanes, `lds` bytes of dynamic LDS

@@ -140,6 +140,20 @@ struct StatsArgs {
 	int na_bg;          // NaArray: implicit values are NAs (Rvector_summarization.c:1078-1106)
 	int dgc;            // dgCMatrix flavour of var1 (src/sparseMatrix_utils.c:173-223): plain IEEE, no NA rule
 };
+// launch forms of the column statistics (values of svt_dev_colstats_form, include/svt_hip.h)
+enum {
+	COLSTATS_THREAD = 0,        // colstats_thread_kernel: one thread per segment
+	COLSTATS_LANES16 = 1,       // colstats_kernel<T, 16, 16>
+	COLSTATS_WAVE = 2,          // colstats_kernel<T, 64, 16>
+	COLSTATS_GROUP_CACHED = 3,  // colstats_kernel<T, 256, 48>
+	COLSTATS_GROUP_STREAM = 4,  // colstats_kernel<T, 256, 0>
+	COLSTATS_SPLIT = 5          // launch_colstats_split: nchunk workgroups per segment
+};
+struct ColStatsRoute {
+	int form;
+	int nchunk;         // COLSTATS_SPLIT: chunks per segment, else 1
+};
+ColStatsRoute colstats_route(int64_t nseg, int64_t nnz);
 int launch_colstats(const StatsArgs &a, int64_t nnz, hipStream_t s);
 size_t colmedians_ws_bytes(int64_t nnz, int64_t ncol);
 int launch_colmedians(const int64_t *col_ptr, const void *val, int Rtype, int64_t nrow, int64_t ncol,
@@ -178,6 +192,9 @@ size_t rowstats_scratch_bytes(int opcode, int64_t out_len);
 int launch_rowstats(const RowStatsArgs &a, hipStream_t s);      // memory atomics
 size_t rowstats_panel_ws_bytes(int64_t nrow, int64_t ncol);
 int launch_rowstats_panel(const RowStatsArgs &a, void *ws, hipStream_t s);      // LDS row panels
+// the form launch_rowstats_panel() takes for `a` (values of svt_dev_rowstats_form, include/svt_hip.h); *ps, *nsplit:
+// panel shift and strata ranges of the panel form, 0 and 1 otherwise
+int rowstats_panel_form(const RowStatsArgs &a, int *ps, int64_t *nsplit);
 size_t rowstats_fused_ws_bytes(int64_t out_len);
 int launch_rowstats_fused(const RowStatsArgs &a, void *ws, void *fws, hipStream_t s);   // mean / var1 / sd1
 void launch_rowpanel_table(const int64_t *col_ptr, const int32_t *row_idx, int64_t ncol, int64_t nnz_hint,

@@ -887,6 +887,13 @@ extern "C" int svt_dev_colstats(const svt_dev_csc *A, int opcode, int na_rm,
 	return abi_status([&] { return dev_colstats_ex(A, opcode, na_rm, center, inner, out, warn_flag, stream, 0); });
 }
 
+extern "C" int svt_dev_colstats_form(int64_t nseg, int64_t nnz, int *nchunk)
+{
+	const ColStatsRoute rt = colstats_route(nseg, nnz);
+	if (nchunk) *nchunk = rt.nchunk;
+	return rt.form;
+}
+
 extern "C" size_t svt_dev_colmedians_ws_bytes(int64_t nnz, int64_t ncol)
 {
 	return colmedians_ws_bytes(nnz, ncol);
@@ -1053,6 +1060,24 @@ extern "C" int svt_dev_rowstats(const svt_dev_csc *A, int opcode, int na_rm, con
 				void *out, int *warn_flag, void *ws, size_t ws_bytes, void *stream)
 {
 	return abi_status([&] { return dev_rowstats_impl(A, opcode, na_rm, center, inner, out, warn_flag, ws, ws_bytes, stream); });
+}
+
+extern "C" int svt_dev_rowstats_form(int64_t nrow, int64_t ncol, int64_t nnz, int na_background, int opcode,
+				     int64_t inner, int *panel_shift, int64_t *nsplit)
+{
+	int ps = 0;
+	int64_t ns = 1;
+	int form = 4;           // more than 65535 output columns: memory atomics (dev_rowstats_impl)
+	if (inner <= 65535) {
+		svt_dev_csc A;
+		memset(&A, 0, sizeof(A));
+		A.nrow = nrow; A.ncol = ncol; A.nnz = nnz; A.na_background = na_background;
+		const RowStatsArgs a = rowstats_args(&A, opcode, 0, inner, inner > 0 ? ncol / inner : 0, NULL);
+		form = rowstats_panel_form(a, &ps, &ns);
+	}
+	if (panel_shift) *panel_shift = ps;
+	if (nsplit) *nsplit = ns;
+	return form;
 }
 
 extern "C" size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz)

@@ -318,6 +318,16 @@ def crossprod_csc_dense(A: DeviceCSC, Y: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def colstats_form(A: DeviceCSC, inner=1):
+    """(form, nchunk) of colstats(A, ..., inner=inner) (svt_dev_colstats_form)."""
+    return _hip.colstats_form(A.ncol // inner, A.nnz)
+
+
+def rowstats_form(A: DeviceCSC, op: str, inner=1, na_background=False):
+    """(form, panel_shift, nsplit) of one pass of rowstats(A, op, inner=inner) (svt_dev_rowstats_form)."""
+    return _hip.rowstats_form(A.nrow, A.ncol, A.nnz, op, inner, na_background)
+
+
 def colstats(A: DeviceCSC, op: str, na_rm=False, center=float("nan"), inner=1):
     oc = OPCODES[op]
     rt = _lib().svt_colStats_out_Rtype(oc, A.Rtype)

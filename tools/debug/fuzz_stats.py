@@ -1,9 +1,12 @@
 """Differential fuzzing of the column-statistics launch paths (thread / 16-lane / wavefront / workgroup
 per generalized column, split long segments) and the row-sum panels against plain torch reductions.
+One case in five is skewed: segments of NT * CAP - 1, NT * CAP and NT * CAP + 1 nonzeros (what the launch form the case
+takes keeps in registers, svt_dev_colstats_form) and an empty one among the binomial rest.
 Run on the GPU box:  python tools/debug/fuzz_stats.py [ncases] [seed]"""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from sparsearray_amd._hip import colstats_form
 from sparsearray_amd.device import DeviceCSC, colstats, rowsums
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
@@ -26,6 +29,14 @@ for case in range(ncases):
     counts = rng.binomial(nrow, min(dens, 1.0), size=ncol)
     if case % 5 == 0 and ncol > 3:
         counts[rng.integers(0, ncol, max(1, ncol // 10))] = 0            # empty leaves
+    if case % 5 == 2 and ncol // inner >= 4:
+        # lengths on both sides of the register limit of the form this launch takes, and an empty segment
+        cap = {"lanes16": 256, "wavefront": 1024, "workgroup_cached": 12288}.get(colstats_form(ncol // inner, int(counts.sum()))[0])
+        planted = [n for n in [0] + ([cap - 1, cap, cap + 1] if cap else []) if n <= nrow * inner]
+        for g, n in zip(rng.choice(ncol // inner, len(planted), replace=False), planted):
+            for leaf in range(g * inner, (g + 1) * inner):      # the segment's leaves filled in turn
+                counts[leaf] = min(n, nrow)
+                n -= counts[leaf]
     cp = np.zeros(ncol + 1, dtype=np.int64); cp[1:] = np.cumsum(counts)
     nnz = int(cp[-1])
     ri = np.concatenate([np.sort(rng.choice(nrow, size=c, replace=False)) for c in counts]).astype(np.int32) if nnz else np.zeros(0, np.int32)
@@ -62,7 +73,8 @@ for case in range(ncases):
     torch.cuda.synchronize()
     worst = max(worst, err)
     flag = "" if err <= 1e-9 else "   <-- MISMATCH"
-    print(f"{case:3d} nrow {nrow:7d} leaves {ncol:6d} inner {inner:3d} nnz {nnz:9d}  err {err:.2e}{flag}", flush=True)
+    form = colstats_form(nseg, nnz)[0] + (" skewed" if case % 5 == 2 and nseg >= 4 else "")
+    print(f"{case:3d} nrow {nrow:7d} leaves {ncol:6d} inner {inner:3d} nnz {nnz:9d}  err {err:.2e}  {form}{flag}", flush=True)
     if flag:
         sys.exit(1)
 print("worst error", worst)
