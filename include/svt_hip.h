@@ -433,6 +433,29 @@ int svt_dev_crossprod_pbc_from(const svt_dev_pbc *P, const svt_dev_csc *A,
 			       int64_t out_stride_k, void *ws, size_t ws_bytes,
 			       void *stream, int64_t first_col);
 
+/* What svt_dev_crossprod_pbc_from() with the same (P, K, tr_y, output strides, first_col) launches under the present
+   settings of the knobs (spare CUs, gather pacing, round launches): a pure host query that calls the functions the
+   launch calls and enqueues nothing; for tests and fuzzers that must know which kernel, split count and launch count
+   they exercise.  The device's CU count enters as in the launch.
+     kind              0 none (no records: the general kernels answer in phase 2), 1 LDS-DMA, 2 gather
+     kernel            SVT_PBC_KERNEL_*: the product kernel of phase 1
+     NV                accumulator vectors per lane, (CBW + 15) / 16   (0 for the general kernels)
+     nsplit            row splits whose partial sums the reduce kernel adds (gatherx: one per XCD with rows)
+     panels_per_split  row panels per split (gather / gather2: over the whole operand, not per row chunk)
+     direct            1: the product kernel writes `out` itself, no partials
+     launches          launches of the product kernel: rounds of column blocks plus the cut last round (LDS-DMA),
+                       row chunks (gather, gather2), 1 (gatherx), 0 (general)
+     tail_splits       row splits of the cut last round (1: no such round), tail_blocks its column blocks */
+enum { SVT_PBC_KERNEL_GENERAL = 0, SVT_PBC_KERNEL_DMA = 1, SVT_PBC_KERNEL_GATHER = 2, SVT_PBC_KERNEL_GATHER2 = 3,
+       SVT_PBC_KERNEL_GATHERX = 4 };
+typedef struct svt_pbc_plan {
+	int kind, kernel, NV, nsplit;
+	int64_t panels_per_split;
+	int direct, launches, tail_splits, tail_blocks;
+} svt_pbc_plan;
+int svt_dev_crossprod_pbc_plan(const svt_dev_pbc *P, int K, int tr_y, int64_t out_stride_c,
+			       int64_t out_stride_k, int64_t first_col, svt_pbc_plan *plan);
+
 /* The two phases of svt_dev_crossprod_pbc() separately (so that each can be
    timed): phase 1 = the LDS-panel product kernel (partial sums into ws),
    phase 2 = deterministic sum of the partials into `out` + the general path

@@ -33,6 +33,7 @@ EXPORTS = [
     "svt_dev_dense_prepare", "svt_dev_crossprod_prepared",
     "svt_dev_pbc_build", "svt_dev_pbc_release", "svt_dev_pbc_trim",
     "svt_dev_crossprod_pbc_ws_bytes", "svt_dev_crossprod_pbc", "svt_dev_crossprod_pbc_phase", "svt_dev_crossprod_pbc_from",
+    "svt_dev_crossprod_pbc_plan",
     "svt_get_num_procs", "svt_get_max_threads", "svt_set_max_threads", "svt_dev_aperm_ws_bytes", "svt_dev_aperm_perm_ws_bytes", "svt_dev_aperm", "svt_dev_aperm_route_counts", "svt_aperm_SVT", "svt_transpose_2D_SVT", "svt_dev_transpose_ws_bytes", "svt_dev_transpose", "svt_dev_set_box_nnz", "svt_dev_boxed_calls", "svt_dev_colstats", "svt_dev_rowstats_ws_bytes", "svt_dev_rowsums", "svt_dev_rowsum",
     "svt_rowStatsFull_SVT", "svt_dev_rowstats_ws_bytes_op", "svt_dev_rowstats",
     "svt_dev_colstats_form", "svt_dev_rowstats_form",
@@ -139,6 +140,33 @@ def rowstats_form(nrow: int, ncol: int, nnz: int, op: str, inner: int = 1, na_ba
     form = lib.svt_dev_rowstats_form(int(nrow), int(ncol), int(nnz), int(bool(na_background)), OPCODES[op], int(inner),
                                      ctypes.byref(ps), ctypes.byref(nsplit))
     return ROWSTATS_FORMS[form], ps.value, nsplit.value
+
+
+PBC_KINDS = ("none", "dma", "gather")
+PBC_KERNELS = ("general", "dma", "gather", "gather2", "gatherx")
+
+
+class _PbcPlanStruct(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("kernel", ctypes.c_int), ("NV", ctypes.c_int), ("nsplit", ctypes.c_int),
+                ("panels_per_split", ctypes.c_int64), ("direct", ctypes.c_int), ("launches", ctypes.c_int),
+                ("tail_splits", ctypes.c_int), ("tail_blocks", ctypes.c_int)]
+
+
+def pbc_plan(handle, K: int, tr_y: bool, stride_c: int, stride_k: int, first_col: int = 0) -> dict:
+    """What svt_dev_crossprod_pbc_from() with these arguments launches on the layout ``handle`` (include/svt_hip.h,
+    svt_dev_crossprod_pbc_plan): kind one of PBC_KINDS, kernel one of PBC_KERNELS, NV, nsplit, panels_per_split,
+    direct, launches, tail_splits, tail_blocks.  Launches nothing."""
+    lib = init()
+    lib.svt_dev_crossprod_pbc_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(_PbcPlanStruct)]
+    lib.svt_dev_crossprod_pbc_plan.restype = ctypes.c_int
+    st = _PbcPlanStruct()
+    if lib.svt_dev_crossprod_pbc_plan(handle, int(K), int(bool(tr_y)), int(stride_c), int(stride_k), int(first_col),
+                                      ctypes.byref(st)) != 0:
+        raise HipBackendError(lib.svt_last_error().decode())
+    d = {f: int(getattr(st, f)) for f, _ in _PbcPlanStruct._fields_}
+    d["kind"], d["kernel"], d["direct"] = PBC_KINDS[st.kind], PBC_KERNELS[st.kernel], bool(st.direct)
+    return d
 
 
 def hip_dispatcher():

@@ -2040,6 +2040,78 @@ extern "C" size_t svt_dev_crossprod_pbc_ws_bytes(const svt_dev_pbc *P, int K)
 	       crossprod_ws_bytes(pbc_padded_rows(P), P->ncol, K) + dirty_ws_bytes(P->ncol, Kp);
 }
 
+// first workgroup column block of a product restricted to the leaves from first_col on (LDS-DMA kernel only)
+static int pbc_block0(const svt_dev_pbc *P, bool dma, int64_t first_col)
+{
+	int block0 = 0;
+	if (dma && first_col > 0) {
+		block0 = (int) (first_col / ((int64_t) 16 * P->CBW));
+		if (block0 > P->nblocks - 1) block0 = (int) P->nblocks - 1;
+	}
+	return block0;
+}
+
+// one split, whole 64-wide dense tiles, result laid out like the partials:
+// the product kernel writes `out` directly
+static bool pbc_direct(const svt_dev_pbc *P, int K, int nsplit, int64_t out_stride_c, int64_t out_stride_k)
+{
+	const int64_t Kp = ((int64_t) K + 63) / 64 * 64;
+	return nsplit == 1 && Kp == K && out_stride_c == 1 && out_stride_k == P->ncol;
+}
+
+// panels per launch of the unpaced gather kernels (pbc_phase_impl: "Row chunks as consecutive launches")
+static int64_t pbc_gather_chunk(const svt_dev_pbc *P, int64_t Kp, int nsplit)
+{
+	const bool wide = Kp % 128 == 0;
+	int64_t cpanels = wide ? PBG2_CHUNK_PANELS : PBG_CHUNK_PANELS;
+#ifdef SVT_TUNING
+	if (getenv("SVT_PBG_CHUNK")) cpanels = atoll(getenv("SVT_PBG_CHUNK"));
+#endif
+	if (P->logR < 10) cpanels <<= 10 - P->logR;          // (the chunk sizes were measured with 1024-row panels)
+	return (int64_t) nsplit * cpanels;
+}
+
+// Launches of the LDS-DMA kernel over the column blocks block0 .. nblocks - 1 (pbc_phase_impl: "Many column blocks,
+// no row split" and "The last round"): blocks [block0, last_full) in launches of `step` blocks (per_launch of them
+// where rounds are launched one by one, else all at once), then the last tail_blocks blocks cut into ts row splits of
+// tpps panels (tail_blocks == 0: no such round).
+struct PbcRounds {
+	int per_launch, tail_blocks, ts, last_full, step;
+	int64_t tpps;
+};
+static PbcRounds pbc_rounds(const svt_dev_pbc *P, int K, int nsplit, int64_t pps, bool direct, int block0)
+{
+	const int kt_ = (int) ((((int64_t) K + 63) / 64 * 64) / 64);
+	int per_launch = 0;
+	if (nsplit == 1 && !pbc_sparing(P, K) && g_pbc_rounds != 0 &&
+	    (int64_t) (P->nblocks - block0) * kt_ >= 2 * pbc_cus())
+		per_launch = pbc_cus() / kt_ > 0 ? pbc_cus() / kt_ : 1;
+	// The last round: `rem` column blocks (54 of 256 CUs busy at config 2b) are cut by rows so that they fill
+	// the chip -- ts row splits of a quarter of the panels each instead of one more full round; their partial
+	// sums go to the (unused: the product writes `out` directly) partials area of the workspace and are summed in
+	// split order behind them.  12.2 rounds then cost 12 + 1 / ts instead of 13.
+	int tail_blocks = 0, ts = 1;
+	int64_t tpps = pps;
+	if (per_launch > 0 && direct && g_pbc_rounds == 1) {
+		const int rem = (int) ((P->nblocks - block0) % per_launch);
+		if (rem > 0 && rem * kt_ * 2 <= pbc_cus()) {
+			ts = pbc_cus() / (rem * kt_);
+			if (ts > 8) ts = 8;
+			while (ts > 1 && P->npanels / ts < 8) ts--;
+			tpps = (P->npanels + ts - 1) / ts;
+			ts = (int) ((P->npanels + tpps - 1) / tpps);
+			const int64_t tcols = (int64_t) rem * 16 * P->CBW;
+			if (ts > 1 && (int64_t) ts * tcols <= P->ncol)      // (fits the partials area: Kp * ncol doubles)
+				tail_blocks = rem;
+		}
+	}
+	PbcRounds r;
+	r.per_launch = per_launch; r.tail_blocks = tail_blocks; r.ts = ts; r.tpps = tpps;
+	r.last_full = (int) P->nblocks - tail_blocks;
+	r.step = per_launch > 0 ? per_launch : (int) P->nblocks;
+	return r;
+}
+
 template <int NV>
 static void launch_dma(const svt_dev_pbc *P, const double *Y, int64_t ldY, int K, int nsplit,
 		       int64_t pps, double *part, int64_t Kp, PbcFlags fl, hipStream_t s, int block0, int nb_launch = 0,
@@ -2160,11 +2232,7 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 	// a dense operand given by rows is transposed on the device first (phase 1) and the product
 	// runs on the column-major copy: same kernel, same speed + one 2 x |Y| pass
 	const bool via_copy = tr_y && dma;
-	int block0 = 0;
-	if (dma && first_col > 0) {
-		block0 = (int) (first_col / ((int64_t) 16 * P->CBW));
-		if (block0 > P->nblocks - 1) block0 = (int) P->nblocks - 1;
-	}
+	const int block0 = pbc_block0(P, dma, first_col);
 	const int64_t c_begin = (int64_t) block0 * 16 * P->CBW;
 	const int nsplit = gath ? pick_nsplit_gather(P, K, &pps) : dma ? pick_nsplit(P, K, &pps) : 0;
 	PbcFlags fl;
@@ -2177,7 +2245,7 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 	const int64_t ldc = via_copy ? P->nrow : ldY;
 	// one split, whole 64-wide dense tiles, result laid out like the partials:
 	// the product kernel writes `out` directly
-	const bool direct = nsplit == 1 && Kp == K && out_stride_c == 1 && out_stride_k == P->ncol;
+	const bool direct = pbc_direct(P, K, nsplit, out_stride_c, out_stride_k);
 	if (direct) part = out;
 	if (phase == 1) {
 		// flags, the per-column counters and (paced gather kernel) the progress words: ONE small kernel.  A
@@ -2235,12 +2303,7 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 			// same pace, so a row of Yt fetched for one group is still in L2 for the others; over a
 			// whole operand they drift apart by more rows than the L2 holds and every record's 512
 			// bytes come from the Infinity Cache or HBM (81.8 ms at BASELINE config 4, i.e. HBM speed).
-			int64_t cpanels = wide ? PBG2_CHUNK_PANELS : PBG_CHUNK_PANELS;
-#ifdef SVT_TUNING
-			if (getenv("SVT_PBG_CHUNK")) cpanels = atoll(getenv("SVT_PBG_CHUNK"));
-#endif
-			if (P->logR < 10) cpanels <<= 10 - P->logR;          // (the chunk sizes were measured with 1024-row panels)
-			const int64_t chunk = (int64_t) nsplit * cpanels;
+			const int64_t chunk = pbc_gather_chunk(P, Kp, nsplit);
 			for (int64_t p0 = 0; p0 < P->npanels; p0 += chunk) {
 				const int64_t p1 = p0 + chunk < P->npanels ? p0 + chunk : P->npanels;
 				const int64_t cpps = (p1 - p0 + nsplit - 1) / nsplit;
@@ -2262,32 +2325,11 @@ static int pbc_phase_impl(const svt_dev_pbc *P, const svt_dev_csc *A,
 		// workgroups of later rounds start whenever a CU frees up, spread over all panel positions, and
 		// the 5 MB dense tile they all stage no longer fits the XCD's 4 MiB L2 (4030 cycles per panel in
 		// the first round, 4650 later); launch by launch every round starts aligned.
-		const int kt_ = (int) (Kp / 64);
-		int per_launch = 0;
-		if (nsplit == 1 && !pbc_sparing(P, K) && g_pbc_rounds != 0 &&
-		    (int64_t) (P->nblocks - block0) * kt_ >= 2 * pbc_cus())
-			per_launch = pbc_cus() / kt_ > 0 ? pbc_cus() / kt_ : 1;
-		// The last round: `rem` column blocks (54 of 256 CUs busy at config 2b) are cut by rows so that they fill
-		// the chip -- ts row splits of a quarter of the panels each instead of one more full round; their partial
-		// sums go to the (unused: the product writes `out` directly) partials area of the workspace and are summed in
-		// split order behind them.  12.2 rounds then cost 12 + 1 / ts instead of 13.
-		int tail_blocks = 0, ts = 1;
-		int64_t tpps = pps;
-		if (per_launch > 0 && direct && g_pbc_rounds == 1) {
-			const int rem = (int) ((P->nblocks - block0) % per_launch);
-			if (rem > 0 && rem * kt_ * 2 <= pbc_cus()) {
-				ts = pbc_cus() / (rem * kt_);
-				if (ts > 8) ts = 8;
-				while (ts > 1 && P->npanels / ts < 8) ts--;
-				tpps = (P->npanels + ts - 1) / ts;
-				ts = (int) ((P->npanels + tpps - 1) / tpps);
-				const int64_t tcols = (int64_t) rem * 16 * P->CBW;
-				if (ts > 1 && (int64_t) ts * tcols <= P->ncol)      // (fits the partials area: Kp * ncol doubles)
-					tail_blocks = rem;
-			}
-		}
-		const int last_full = (int) P->nblocks - tail_blocks;
-		for (int b0 = block0; b0 < last_full; b0 += per_launch > 0 ? per_launch : (int) P->nblocks) {
+		// (the last, partly filled round is cut by rows: pbc_rounds)
+		const PbcRounds rd = pbc_rounds(P, K, nsplit, pps, direct, block0);
+		const int per_launch = rd.per_launch, tail_blocks = rd.tail_blocks, ts = rd.ts, last_full = rd.last_full;
+		const int64_t tpps = rd.tpps;
+		for (int b0 = block0; b0 < last_full; b0 += rd.step) {
 			const int nbl = per_launch > 0 ? (b0 + per_launch <= last_full ? per_launch : last_full - b0)
 						       : tail_blocks > 0 ? last_full - b0 : 0;
 			if (nv == 1) launch_dma<1>(P, Yc, ldc, K, nsplit, pps, part, Kp, fl, s, b0, nbl);
@@ -2379,4 +2421,52 @@ extern "C" int svt_dev_crossprod_pbc_from(const svt_dev_pbc *P, const svt_dev_cs
 	if (pbc_phase(P, A, Y, ldY, K, tr_y, out, out_stride_c, out_stride_k, ws, ws_bytes, stream, 1, first_col))
 		return -1;
 	return pbc_phase(P, A, Y, ldY, K, tr_y, out, out_stride_c, out_stride_k, ws, ws_bytes, stream, 2, first_col);
+}
+
+// What svt_dev_crossprod_pbc_from() with the same arguments launches now (include/svt_hip.h): the functions the launch
+// itself calls, nothing enqueued.
+extern "C" int svt_dev_crossprod_pbc_plan(const svt_dev_pbc *P, int K, int tr_y, int64_t out_stride_c,
+					  int64_t out_stride_k, int64_t first_col, svt_pbc_plan *plan)
+{
+	(void) tr_y;                        // (a dense operand given by rows is copied first: same product launches)
+	if (P == NULL || plan == NULL)
+		return svt_set_error("svt_dev_crossprod_pbc_plan: NULL layout or plan");
+	memset(plan, 0, sizeof(*plan));
+	plan->kind = PBC_KIND_NONE;
+	plan->kernel = SVT_PBC_KERNEL_GENERAL;
+	plan->tail_splits = 1;
+	if (P->ncol <= 0 || K <= 0)
+		return 0;
+	const int kind = P->rec != NULL ? P->kind : PBC_KIND_NONE;
+	plan->kind = kind;
+	if (kind == PBC_KIND_NONE)
+		return 0;
+	const bool dma = kind == PBC_KIND_DMA, gath = kind == PBC_KIND_GATHER;
+	const int64_t Kp = ((int64_t) K + 63) / 64 * 64;
+	int64_t pps = 1;
+	const int nsplit = gath ? pick_nsplit_gather(P, K, &pps) : pick_nsplit(P, K, &pps);
+	const bool direct = pbc_direct(P, K, nsplit, out_stride_c, out_stride_k);
+	plan->NV = (P->CBW + 15) / 16;
+	plan->nsplit = nsplit;
+	plan->panels_per_split = pps;
+	plan->direct = direct ? 1 : 0;
+	if (gath && pbgx_ok(P, K)) {
+		plan->kernel = SVT_PBC_KERNEL_GATHERX;
+		plan->launches = 1;
+	} else if (gath) {
+		plan->kernel = Kp % 128 == 0 ? SVT_PBC_KERNEL_GATHER2 : SVT_PBC_KERNEL_GATHER;
+		const int64_t chunk = pbc_gather_chunk(P, Kp, nsplit);
+		plan->launches = (int) ((P->npanels + chunk - 1) / chunk);
+	} else {
+		plan->kernel = SVT_PBC_KERNEL_DMA;
+		const int block0 = pbc_block0(P, dma, first_col);
+		const PbcRounds rd = pbc_rounds(P, K, nsplit, pps, direct, block0);
+		plan->launches = (rd.last_full > block0 ? (rd.last_full - block0 + rd.step - 1) / rd.step : 0) +
+				 (rd.tail_blocks > 0 ? 1 : 0);
+		if (rd.tail_blocks > 0) {
+			plan->tail_splits = rd.ts;
+			plan->tail_blocks = rd.tail_blocks;
+		}
+	}
+	return 0;
 }

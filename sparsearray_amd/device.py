@@ -235,6 +235,23 @@ class PbcPlan:
                                             int(tr_y), out.data_ptr(), stride_c, stride_k,
                                             self.ws.data_ptr(), self.ws.numel(), _stream()))
 
+    def run_from(self, first_col, Y, ldY, out, stride_c=1, stride_k=None, tr_y=False):
+        """The product restricted to the leaves from ``first_col`` on (svt_dev_crossprod_pbc_from)."""
+        if stride_k is None:
+            stride_k = self.A.ncol
+        lib = _lib()
+        lib.svt_dev_crossprod_pbc_from.argtypes = lib.svt_dev_crossprod_pbc.argtypes + [c_int64]
+        _check(lib.svt_dev_crossprod_pbc_from(self._p, self.A.handle, Y.data_ptr(), ldY, self.K,
+                                              int(tr_y), out.data_ptr(), stride_c, stride_k,
+                                              self.ws.data_ptr(), self.ws.numel(), _stream(), int(first_col)))
+
+    def plan(self, stride_c=1, stride_k=None, tr_y=False, first_col=0) -> dict:
+        """What run() / run_from() with these arguments launches under the present knobs: kind, kernel, NV, nsplit,
+        panels_per_split, direct, launches, tail_splits, tail_blocks (svt_dev_crossprod_pbc_plan).  Launches nothing."""
+        if stride_k is None:
+            stride_k = self.A.ncol
+        return _hip.pbc_plan(self._p, self.K, tr_y, stride_c, stride_k, first_col)
+
     def run_phase(self, phase, Y, ldY, out, stride_c=1, stride_k=None, tr_y=False):
         if stride_k is None:
             stride_k = self.A.ncol
