@@ -155,13 +155,12 @@ struct ColStatsRoute {
 };
 ColStatsRoute colstats_route(int64_t nseg, int64_t nnz);
 int launch_colstats(const StatsArgs &a, int64_t nnz, hipStream_t s);
-size_t colmedians_ws_bytes(int64_t nnz, int64_t ncol);
-int launch_colmedians(const int64_t *col_ptr, const void *val, int Rtype, int64_t nrow, int64_t ncol,
-		      int64_t nnz, int na_rm, double *out, void *ws, hipStream_t s);
-// colQuantiles (type 7): probs and out on the device, out[j + q * ncol]
-size_t colquantiles_ws_bytes(int64_t nnz, int64_t ncol, int nprobs);
-int launch_colquantiles(const int64_t *col_ptr, const void *val, int Rtype, int64_t nrow, int64_t ncol, int64_t nnz,
-			const double *probs, int nprobs, int na_rm, double *out, void *ws, hipStream_t s);
+// colMedians / colQuantiles (kernels_median.hip): out on the device; ORDER_QUANTILES (type 7): probs on the device too,
+// out[j + q * ncol]; ORDER_MEDIANS: probs and nprobs are not read
+enum { ORDER_MEDIANS = 0, ORDER_QUANTILES = 1 };
+size_t order_stat_ws_bytes(int what, int64_t ncol);
+int launch_order_stat(int what, const int64_t *col_ptr, const void *val, int Rtype, int64_t nrow, int64_t ncol,
+		      int64_t nnz, const double *probs, int nprobs, int na_rm, double *out, void *ws, hipStream_t s);
 
 struct RowStatsArgs {
 	const int64_t *col_ptr;

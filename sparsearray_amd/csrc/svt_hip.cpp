@@ -896,46 +896,40 @@ extern "C" int svt_dev_colstats_form(int64_t nseg, int64_t nnz, int *nchunk)
 
 extern "C" size_t svt_dev_colmedians_ws_bytes(int64_t nnz, int64_t ncol)
 {
-	return colmedians_ws_bytes(nnz, ncol);
-}
-
-static int dev_colmedians_impl(const svt_dev_csc *A, int na_rm, double *out, void *ws,
-				  size_t ws_bytes, void *stream)
-{
-	if (A->na_background)
-		return svt_set_error("colMedians() is not supported on NaArray objects");
-	if (ws_bytes < colmedians_ws_bytes(A->nnz, A->ncol))
-		return svt_set_error("svt_dev_colmedians: workspace too small");
-	return launch_colmedians(A->col_ptr, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, na_rm, out, ws,
-				 (hipStream_t) stream);
-}
-extern "C" int svt_dev_colmedians(const svt_dev_csc *A, int na_rm, double *out, void *ws,
-				  size_t ws_bytes, void *stream)
-{
-	return abi_status([&] { return dev_colmedians_impl(A, na_rm, out, ws, ws_bytes, stream); });
+	(void) nnz;
+	return order_stat_ws_bytes(ORDER_MEDIANS, ncol);
 }
 
 extern "C" size_t svt_dev_colquantiles_ws_bytes(int64_t nnz, int64_t ncol, int nprobs)
 {
-	return colquantiles_ws_bytes(nnz, ncol, nprobs);
+	(void) nnz; (void) nprobs;
+	return order_stat_ws_bytes(ORDER_QUANTILES, ncol);
 }
 
-static int dev_colquantiles_impl(const svt_dev_csc *A, const double *probs, int nprobs, int na_rm, double *out,
-				    void *ws, size_t ws_bytes, void *stream)
+static int dev_order_stat_impl(const svt_dev_csc *A, int what, const double *probs, int nprobs, int na_rm, double *out,
+				  void *ws, size_t ws_bytes, void *stream)
 {
+	const bool quant = what == ORDER_QUANTILES;
 	if (A->na_background)
-		return svt_set_error("colQuantiles() is not supported on NaArray objects");
-	if (nprobs < 0)
+		return svt_set_error("%s() is not supported on NaArray objects", quant ? "colQuantiles" : "colMedians");
+	if (quant && nprobs < 0)
 		return svt_set_error("svt_dev_colquantiles: 'nprobs' must be >= 0");
-	if (ws_bytes < colquantiles_ws_bytes(A->nnz, A->ncol, nprobs))
-		return svt_set_error("svt_dev_colquantiles: workspace too small");
-	return launch_colquantiles(A->col_ptr, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, probs, nprobs, na_rm, out,
-				   ws, (hipStream_t) stream);
+	if (ws_bytes < order_stat_ws_bytes(what, A->ncol))
+		return svt_set_error("svt_dev_%s: workspace too small", quant ? "colquantiles" : "colmedians");
+	return launch_order_stat(what, A->col_ptr, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, probs, nprobs, na_rm, out,
+				 ws, (hipStream_t) stream);
+}
+extern "C" int svt_dev_colmedians(const svt_dev_csc *A, int na_rm, double *out, void *ws,
+				  size_t ws_bytes, void *stream)
+{
+	return abi_status([&] { return dev_order_stat_impl(A, ORDER_MEDIANS, NULL, 0, na_rm, out, ws, ws_bytes, stream); });
 }
 extern "C" int svt_dev_colquantiles(const svt_dev_csc *A, const double *probs, int nprobs, int na_rm, double *out,
 				    void *ws, size_t ws_bytes, void *stream)
 {
-	return abi_status([&] { return dev_colquantiles_impl(A, probs, nprobs, na_rm, out, ws, ws_bytes, stream); });
+	return abi_status([&] {
+		return dev_order_stat_impl(A, ORDER_QUANTILES, probs, nprobs, na_rm, out, ws, ws_bytes, stream);
+	});
 }
 
 extern "C" size_t svt_dev_rowstats_ws_bytes(int64_t nrow, int64_t ncol)
@@ -2541,95 +2535,69 @@ extern "C" int svt_colStats_SVT(const svt_view *x, int opcode, int na_rm, double
 
 // colMedians(): .colMedians_SVT_SparseMatrix, R/SparseArray-matrixStats.R:761-784 (pure R in the
 // reference, with a TODO asking for a .Call version).  out: ncol(x) doubles.
-static int medians_SVT(const svt_view *x, int na_rm, int by_row, double *out)
-{
-	if (ensure_init() || check_view(x))
-		return -1;
-	if (x->ndim != 2)       // stopifnot_2D_object(), R/SparseArray-matrixStats.R:51-57
-		return svt_set_error("the %s() method for SparseArray objects only supports 2D "
-				     "objects (i.e. SparseMatrix objects) at the moment",
-				     by_row ? "rowMedians" : "colMedians");
-	if (x->Rtype != SVT_REALSXP && x->Rtype != SVT_INTSXP && x->Rtype != SVT_LGLSXP)
-		return svt_set_error("colMedians(): unsupported type");
-	if (x->na_background)
-		return svt_set_error("colMedians() is not supported on NaArray objects");
-	const int64_t nout = x->dim[by_row ? 0 : 1];
-	if (nout == 0)
-		return 0;
-	CscGuard A(x);
-	if (A.h == NULL) return -1;
-	// rowMedians(x) = colMedians(t(x)), :802-815; t() on the device
-	const OwnedCsc T = by_row ? transposed_for(A) : OwnedCsc(NULL, false);
-	if (by_row && T.t == NULL) return -1;
-	const svt_dev_csc *M = by_row ? T.t : A.h;
-	DevBuf O, W;
-	if (O.alloc((size_t) nout * 8) || W.alloc(colmedians_ws_bytes(M->nnz, nout)))
-		return -1;
-	if (launch_colmedians(M->col_ptr, M->val, M->Rtype, M->nrow, nout, M->nnz, na_rm,
-			      O.as<double>(), W.p, 0))
-		return -1;
-	HIP_TRY(hipDeviceSynchronize());
-	return staged_download(out, O.p, (size_t) nout * 8);
-}
-
-extern "C" int svt_colMedians_SVT(const svt_view *x, int na_rm, double *out)
-{
-	return abi_status([&] { return medians_SVT(x, na_rm, 0, out); });
-}
-
-extern "C" int svt_rowMedians_SVT(const svt_view *x, int na_rm, double *out)
-{
-	return abi_status([&] { return medians_SVT(x, na_rm, 1, out); });
-}
-
 // colQuantiles(x, probs, na.rm, type = 7): no method in the reference (R/SparseArray-matrixStats.R:5-12); the rule is
 // base R's quantile.default type 7 (kernels_median.hip).  out: ncol(x) * nprobs doubles, column-major.
-static int quantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, int by_row, double *out)
+static int order_stat_SVT(const svt_view *x, int what, const double *probs, int nprobs, int na_rm, int by_row,
+			  double *out)
 {
+	const bool quant = what == ORDER_QUANTILES;
+	const char *col = quant ? "colQuantiles" : "colMedians";
 	if (ensure_init() || check_view(x))
 		return -1;
 	if (x->ndim != 2)       // stopifnot_2D_object(), R/SparseArray-matrixStats.R:51-57
 		return svt_set_error("the %s() method for SparseArray objects only supports 2D "
 				     "objects (i.e. SparseMatrix objects) at the moment",
-				     by_row ? "rowQuantiles" : "colQuantiles");
+				     by_row ? (quant ? "rowQuantiles" : "rowMedians") : col);
 	if (x->Rtype != SVT_REALSXP && x->Rtype != SVT_INTSXP && x->Rtype != SVT_LGLSXP)
-		return svt_set_error("colQuantiles(): unsupported type");
+		return svt_set_error("%s(): unsupported type", col);
 	if (x->na_background)
-		return svt_set_error("colQuantiles() is not supported on NaArray objects");
-	if (nprobs < 0 || (nprobs > 0 && probs == NULL))
-		return svt_set_error("invalid 'probs'");
-	for (int q = 0; q < nprobs; q++)        // (before anything is uploaded; NaN fails both comparisons)
-		if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
-			return svt_set_error("'probs' outside [0,1]");
+		return svt_set_error("%s() is not supported on NaArray objects", col);
+	if (quant) {
+		if (nprobs < 0 || (nprobs > 0 && probs == NULL))
+			return svt_set_error("invalid 'probs'");
+		for (int q = 0; q < nprobs; q++)        // (before anything is uploaded; NaN fails both comparisons)
+			if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
+				return svt_set_error("'probs' outside [0,1]");
+	}
 	const int64_t nout = x->dim[by_row ? 0 : 1];
-	if (nout == 0 || nprobs == 0)
+	if (nout == 0 || (quant && nprobs == 0))
 		return 0;
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	// rowQuantiles(x) = colQuantiles(t(x)); t() on the device
+	// rowMedians(x) = colMedians(t(x)), :802-815, and rowQuantiles(x) = colQuantiles(t(x)); t() on the device
 	const OwnedCsc T = by_row ? transposed_for(A) : OwnedCsc(NULL, false);
 	if (by_row && T.t == NULL) return -1;
 	const svt_dev_csc *M = by_row ? T.t : A.h;
 	DevBuf P, O, W;
-	const size_t out_bytes = (size_t) nout * (size_t) nprobs * 8;
-	if (P.upload(probs, (size_t) nprobs * 8) || O.alloc(out_bytes) ||
-	    W.alloc(colquantiles_ws_bytes(M->nnz, nout, nprobs)))
+	const size_t out_bytes = (size_t) nout * (quant ? (size_t) nprobs : 1) * 8;
+	if ((quant && P.upload(probs, (size_t) nprobs * 8)) || O.alloc(out_bytes) ||
+	    W.alloc(order_stat_ws_bytes(what, nout)))
 		return -1;
-	if (launch_colquantiles(M->col_ptr, M->val, M->Rtype, M->nrow, nout, M->nnz, P.as<double>(), nprobs, na_rm,
-				O.as<double>(), W.p, 0))
+	if (launch_order_stat(what, M->col_ptr, M->val, M->Rtype, M->nrow, nout, M->nnz, P.as<double>(), nprobs, na_rm,
+			      O.as<double>(), W.p, 0))
 		return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	return staged_download(out, O.p, out_bytes);
 }
 
+extern "C" int svt_colMedians_SVT(const svt_view *x, int na_rm, double *out)
+{
+	return abi_status([&] { return order_stat_SVT(x, ORDER_MEDIANS, NULL, 0, na_rm, 0, out); });
+}
+
+extern "C" int svt_rowMedians_SVT(const svt_view *x, int na_rm, double *out)
+{
+	return abi_status([&] { return order_stat_SVT(x, ORDER_MEDIANS, NULL, 0, na_rm, 1, out); });
+}
+
 extern "C" int svt_colQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out)
 {
-	return abi_status([&] { return quantiles_SVT(x, probs, nprobs, na_rm, 0, out); });
+	return abi_status([&] { return order_stat_SVT(x, ORDER_QUANTILES, probs, nprobs, na_rm, 0, out); });
 }
 
 extern "C" int svt_rowQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out)
 {
-	return abi_status([&] { return quantiles_SVT(x, probs, nprobs, na_rm, 1, out); });
+	return abi_status([&] { return order_stat_SVT(x, ORDER_QUANTILES, probs, nprobs, na_rm, 1, out); });
 }
 
 // C_summarize_SVT, src/SparseArray_summarization.c:112-142

@@ -6,6 +6,7 @@ import pytest
 
 from helpers import assert_equal, assert_identical, random_csc
 from sparsearray_amd import NA_integer, NA_real, SVT_SparseArray, SparseArrayError, is_NA_real
+from test_medians import _dense_colmedians
 from test_quantiles_cpu import (PROBS_SETS, as_float, check_session_on_cases, dense_colquantiles, dense_iqrs,
                                 quantile_cases)
 
@@ -140,7 +141,7 @@ def test_hip_colquantiles_select_against_dense_rule(hip, select_operand):
 
 
 def test_hip_colmedians_is_the_half_quantile(hip, select_operand):
-    """The median kernel and the quantile kernel share the select helpers: identical bits."""
+    """The median rule and the quantile rule run the same select: identical bits on this operand."""
     type_, x, dense, want = select_operand
     for na_rm in (False, True):
         med = hip.colMedians(x, na_rm=na_rm)
@@ -200,3 +201,33 @@ def test_device_colquantiles_resident(hip):
         colquantiles(A, probs, out=out1, ws=ws[:nbytes - 1])
     with pytest.raises(SparseArrayError, match=r"'probs' outside \[0,1\]"):
         colquantiles(A, (0.5, 2.0))
+
+
+@pytest.mark.parametrize("ncol", [1, 3, 40])
+def test_device_order_stats_stay_inside_their_workspace(hip, ncol):
+    """colmedians and colquantiles carve their per-column arrays out of a caller's workspace of exactly the advertised
+    size, at an odd address: right results, and not a byte touched before or after it."""
+    import torch
+    from sparsearray_amd.device import DeviceCSC, _lib, colmedians, colquantiles
+    nrow = 3000
+    cp, ri, v = random_csc(nrow, ncol, 0.6, seed=52)
+    A = DeviceCSC.from_host(nrow, cp, ri, v)
+    dense = np.zeros((nrow, ncol))
+    for j in range(ncol):
+        dense[ri[cp[j]:cp[j + 1]], j] = v[cp[j]:cp[j + 1]]
+    probs = (0.25, 0.5, 0.75, 0.1)
+    runs = (
+        (_lib().svt_dev_colmedians_ws_bytes(A.nnz, ncol), ncol * 28 + 1024, lambda ws: colmedians(A, ws=ws),
+         _dense_colmedians(dense, False)),
+        (_lib().svt_dev_colquantiles_ws_bytes(A.nnz, ncol, len(probs)), ncol * 44 + 1024,
+         lambda ws: colquantiles(A, probs, ws=ws).T, dense_colquantiles(dense, probs, False)),
+    )
+    for nbytes, advertised, run, want in runs:
+        assert nbytes == advertised
+        pad = 519
+        arena = torch.full((pad + nbytes + pad,), 0xA5, dtype=torch.uint8, device="cuda")
+        ws = arena[pad:pad + nbytes]
+        assert_equal(run(ws).cpu().numpy(), want, tol=0, strict_na=True, what=f"ncol={ncol}")
+        assert bool((arena[:pad] == 0xA5).all()) and bool((arena[pad + nbytes:] == 0xA5).all())
+        with pytest.raises(SparseArrayError, match="workspace too small"):
+            run(ws[:nbytes - 1])

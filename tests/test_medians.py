@@ -7,6 +7,7 @@ import pytest
 
 from helpers import assert_equal
 from sparsearray_amd import NA_integer, NA_real, SVT_SparseArray, is_NA_real
+from test_quantiles_cpu import dense_colquantiles
 
 
 def _dense_colmedians(a, na_rm):
@@ -80,6 +81,33 @@ def test_oracle_colmedians_is_the_dense_median(oracle, na_rm):
     assert is_NA_real(oracle.colMedians(x0)).all()
     with pytest.raises(Exception, match="only supports 2D"):
         oracle.colMedians(SVT_SparseArray((2, 2, 2), "double", [None] * 4))
+
+
+def _check_median_keeps_its_own_finish(session):
+    """The median of an even column is (lo + hi) * 0.5, the quantile at 0.5 is 0.5 * lo + 0.5 * hi: the first
+    overflows where the second does not, and they round a subnormal pair differently.  Every column has four stored
+    values (no zeros): on the device all three go through the select kernel."""
+    big = np.array([1.5e308, 1.6e308, 1e308, 1.7e308])
+    a = np.stack([big, np.array([5e-324, 1e-323, -1.0, 3.0]), -big], axis=1)
+    half = dense_colquantiles(a, (0.5,), False)[:, 0]
+    x = SVT_SparseArray.from_dense(np.asfortranarray(a), "double")
+    xt = SVT_SparseArray.from_dense(np.asfortranarray(a.T), "double")
+    with np.errstate(over="ignore"):                    # (the overflow is the point)
+        med = np.array([np.median(a[:, j]) for j in range(3)])
+        assert np.array_equal(med, [np.inf, 1e-323, -np.inf])
+        assert (med != half).all()
+        assert_equal(session.colMedians(x), med, tol=0, strict_na=True, what="colMedians")
+        assert_equal(session.rowMedians(xt), med, tol=0, strict_na=True, what="rowMedians")
+    assert_equal(session.colQuantiles(x, (0.5,))[:, 0], half, tol=0, strict_na=True, what="colQuantiles(0.5)")
+
+
+def test_oracle_median_keeps_its_own_finish(oracle):
+    _check_median_keeps_its_own_finish(oracle)
+
+
+@pytest.mark.gpu
+def test_hip_median_keeps_its_own_finish(hip):
+    _check_median_keeps_its_own_finish(hip)
 
 
 @pytest.mark.gpu
