@@ -226,9 +226,32 @@ int svt_rowMedians_SVT(const svt_view *x, int na_rm, double *out);
    rowQuantiles(x) is colQuantiles(t(x)) with t() on the device (boxed past 2^31 nonzeros, as for rowMedians).
    colIQRs / rowIQRs are this call with probs = (0.25, 0.75) and Q3 - Q1 on the host.
    These calls are not sharded over the device list of svt_set_devices(): they run on the first entry.
-   Not offered: colMads, colRanks, colOrderStats, quantile types other than 7, N-d operands, NaArray operands. */
+   Not offered: colRanks, colOrderStats, quantile types other than 7, N-d operands, NaArray operands. */
 int svt_colQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out);
 int svt_rowQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out);
+
+/* colMads(x, center, constant, na.rm) of a 2-D SVT: stats::mad without low / high on each column's nrow values, the
+   implicit zeros included (colMads is in the reference's list of statistics to add, R/SparseArray-matrixStats.R:5-12,
+   rowMads in its TODO).  Every operation is IEEE double, each rounded on its own.  Per column, with stored values x
+   (NA / NaN = missing):
+     1. the NA rule of svt_colMedians_SVT: a missing value without na_rm gives NA_real_; na_rm drops the missing stored
+        values and the padding keeps its size; n values remain, n == 0 gives NA_real_;
+     2. c = center[j], or with center == NULL the column's median by the median's own rule (the middle value, or
+        (lo + hi) * 0.5 -- not the 0.5 quantile);
+     3. c NA or NaN (the median of -Inf and +Inf is NaN) gives NA_real_;
+     4. t_i = fabs(x_i - c), one subtraction; every zero, stored or implicit, becomes fabs(0.0 - c).  A t_i that is NaN
+        (x_i and c the same infinity) gives NA_real_, also under na_rm: stats::mad takes the median of the deviations
+        without na.rm;
+     5. M = the median of the n values t by the median's rule; the result is constant * M, one product.  `constant` is
+        not checked (stats::mad's default is 1.4826).
+   center: NULL or ncol(x) doubles on the host (rowMads: nrow(x)).  out: ncol(x) doubles (rowMads: nrow(x)).
+   rowMads(x) is colMads(t(x)) with t() on the device, as for rowMedians.  Limits and errors are svt_colMedians_SVT's:
+   2-D operands, double / integer / logical values, at most 2^31-1 columns (status > 0 beyond), any number of nonzeros;
+   NaArray operands are an error ("colMads() is not supported on NaArray objects"); not sharded over the device list. */
+int svt_colMads_SVT(const svt_view *x, const double *center /* NULL or ncol(x) */, double constant, int na_rm,
+		    double *out);
+int svt_rowMads_SVT(const svt_view *x, const double *center /* NULL or nrow(x) */, double constant, int na_rm,
+		    double *out);
 
 /* C_summarize_SVT, src/SparseArray_summarization.c:112-142.  The result is
    left in out_d[0..1] or out_i[0..1] according to *out_Rtype. */
@@ -503,6 +526,18 @@ int svt_dev_colmedians(const svt_dev_csc *A, int na_rm, double *out, void *ws, s
 size_t svt_dev_colquantiles_ws_bytes(int64_t nnz, int64_t ncol, int nprobs);
 int svt_dev_colquantiles(const svt_dev_csc *A, const double *probs, int nprobs, int na_rm,
 			 double *out, void *ws, size_t ws_bytes, void *stream);
+
+/* colMads on the device (see svt_colMads_SVT): center (NULL = the medians, else ncol doubles) and out (ncol doubles)
+   are device pointers.  Asynchronous on `stream`, allocates nothing, reads nothing back: without a center the median's
+   two launches into a center array inside ws, then one counting launch over the deviations (which answers a column whose
+   median is 0 and more than half of whose values are zeros from the median's counts, without reading it again) and one
+   select launch for the columns it could not decide.
+   ws: svt_dev_colmads_ws_bytes(nnz, ncol) = max(ncol, 1) * 64 + 1024 bytes: the per-column arrays of the two counting
+   passes (28 bytes a column each), the centers (8), and room to align the three to 256 bytes.  A smaller one is an
+   error ("svt_dev_colmads: workspace too small"). */
+size_t svt_dev_colmads_ws_bytes(int64_t nnz, int64_t ncol);
+int svt_dev_colmads(const svt_dev_csc *A, const double *center /* device, NULL = medians */, double constant,
+		    int na_rm, double *out, void *ws, size_t ws_bytes, void *stream);
 
 /* row sums: out[(j % inner) * nrow + r] = sum over the leaves j that map to
    that cell.  Every output cell is owned by one workgroup (LDS row panels, no

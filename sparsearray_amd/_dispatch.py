@@ -68,6 +68,9 @@ class CAbiDispatcher:
         if hasattr(self.lib, self.prefix + "colQuantiles_SVT"):    # HIP library (api.py states the rule in numpy)
             protos["colQuantiles_SVT"] = (I, [V, P, I, I, P])
             protos["rowQuantiles_SVT"] = (I, [V, P, I, I, P])
+        if hasattr(self.lib, self.prefix + "colMads_SVT"):         # HIP library (api.py states the rule in numpy)
+            protos["colMads_SVT"] = (I, [V, P, c_double, I, P])
+            protos["rowMads_SVT"] = (I, [V, P, c_double, I, P])
         # x %*% y in one call (device-side transposition): HIP library only
         for name, sig in (("matmul_SVT_mat", (I, [V, P, I, I, I, P])),
                           ("matmul_SVT_SVT", (I, [V, V, P])),
@@ -160,6 +163,26 @@ class CAbiDispatcher:
 
     def C_rowQuantiles_SVT(self, x: SVT_SparseArray, probs, na_rm: bool):
         return self._quantiles("rowQuantiles_SVT", x, probs, na_rm, x.dim[0] if x.ndim == 2 else 0)
+
+    # colMads / rowMads (include/svt_hip.h; HIP library only) ----------------------
+    def _mads(self, fname, x, center, constant, na_rm, axis):
+        nout = x.dim[axis] if x.ndim == 2 else 0
+        if center is not None:
+            center = np.ascontiguousarray(center, dtype=np.float64)
+            if x.ndim == 2 and (center.ndim != 1 or center.size != nout):       # (the library sees a pointer only)
+                raise SparseArrayError("'center' must be NULL, a single number, or a vector with one element per "
+                                       + ("column" if axis == 1 else "row"))
+        out = np.zeros(nout, dtype=np.float64)
+        xv = make_view(x)
+        self._check(self._fn(fname)(byref(xv), None if center is None else _ptr(center), float(constant),
+                                    int(bool(na_rm)), _ptr(out)))
+        return out
+
+    def C_colMads_SVT(self, x: SVT_SparseArray, center, constant: float, na_rm: bool):
+        return self._mads("colMads_SVT", x, center, constant, na_rm, 1)
+
+    def C_rowMads_SVT(self, x: SVT_SparseArray, center, constant: float, na_rm: bool):
+        return self._mads("rowMads_SVT", x, center, constant, na_rm, 0)
 
     # resident operands (include/svt_hip.h; HIP library only) --------------------
     def resident_set_limit(self, nbytes: int):

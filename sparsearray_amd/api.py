@@ -327,8 +327,8 @@ class Session:
 
     # colQuantiles / rowQuantiles / colIQRs / rowIQRs.  The reference has no method (they are in its list of statistics
     # to add, R/SparseArray-matrixStats.R:5-12); the rule is matrixStats::colQuantiles(type = 7), i.e. base R's
-    # quantile.default type 7, on each column's nrow values with the implicit zeros included.  Not offered: colMads,
-    # colRanks, colOrderStats, other quantile types, N-d operands, NaArray operands.
+    # quantile.default type 7, on each column's nrow values with the implicit zeros included.  Not offered: colRanks,
+    # colOrderStats, other quantile types, N-d operands, NaArray operands.
     def _check_quantiles_args(self, what, x, probs, na_rm, type):
         if x.ndim != 2:
             raise SparseArrayError(
@@ -392,17 +392,21 @@ class Session:
         # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
         ans = np.zeros((ncol, probs.size))
         for j, lf in enumerate(x.leaves):
-            if lf is None:
-                vals = np.zeros(0)
-            elif lf[1] is None:                       # lacunar leaf: all ones
-                vals = np.ones(len(lf[0]))
-            else:
-                raw = np.asarray(lf[1])
-                vals = raw.astype(np.float64)
-                if raw.dtype != np.float64:
-                    vals[raw == NA_integer] = np.nan
-            self._leaf_quantiles(vals, nrow, probs, bool(na_rm), ans[j])
+            self._leaf_quantiles(self._leaf_doubles(lf), nrow, probs, bool(na_rm), ans[j])
         return ans
+
+    @staticmethod
+    def _leaf_doubles(lf):
+        """The stored values of one leaf as doubles, NaN for an integer NA."""
+        if lf is None:
+            return np.zeros(0)
+        if lf[1] is None:                             # lacunar leaf: all ones
+            return np.ones(len(lf[0]))
+        raw = np.asarray(lf[1])
+        vals = raw.astype(np.float64)
+        if raw.dtype != np.float64:
+            vals[raw == NA_integer] = np.nan
+        return vals
 
     def rowQuantiles(self, x, probs=(0.0, 0.25, 0.5, 0.75, 1.0), na_rm=False, type=7):
         """rowQuantiles(x) = colQuantiles(t(x)): an (nrow, P) array."""
@@ -425,6 +429,97 @@ class Session:
 
     def rowIQRs(self, x, na_rm=False):
         return self._iqr(self.rowQuantiles(x, (0.25, 0.75), na_rm=na_rm))
+
+    # colMads / rowMads.  The reference has no method (colMads is in its list of statistics to add,
+    # R/SparseArray-matrixStats.R:5-12, rowMads in its TODO); the rule is stats::mad without low / high on each
+    # column's nrow values with the implicit zeros included (include/svt_hip.h, svt_colMads_SVT).
+    def _check_mads_args(self, what, x, center, na_rm, nout_axis):
+        if x.ndim != 2:
+            raise SparseArrayError(
+                f"the {what}() method for SparseArray objects only supports 2D "
+                "objects (i.e. SparseMatrix objects) at the moment")
+        if x.na_background:
+            raise SparseArrayError("colMads() is not supported on NaArray objects")
+        if not isinstance(na_rm, (bool, np.bool_)):
+            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
+        if center is None:
+            return None
+        nout = x.dim[nout_axis]
+        bad = SparseArrayError("'center' must be NULL, a single number, or a vector with one element per "
+                               + ("column" if nout_axis == 1 else "row"))
+        if isinstance(center, (str, bytes)):
+            raise bad
+        try:
+            c = np.asarray(center, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise bad
+        if c.ndim == 0:
+            return np.full(nout, float(c))
+        if c.ndim != 1 or c.size != nout:
+            raise bad
+        return np.ascontiguousarray(c)
+
+    @staticmethod
+    def _padded_median(outside, below, block, n, blk):
+        """The median of n values of which the sorted ``outside`` are stored, ``below`` of them less than the ``block``
+        others, which all equal ``blk``: the middle value, or (lo + hi) * 0.5."""
+        def value(r):                                 # 0-based rank of the virtual column
+            return float(outside[r]) if r < below else blk if r < below + block else float(outside[r - block])
+
+        lo = value((n - 1) >> 1)
+        return lo if n & 1 else (lo + value(n >> 1)) * 0.5
+
+    @classmethod
+    def _leaf_mad(cls, vals, nrow, c, constant, na_rm):
+        """colMads of one leaf's nrow values without realising the zeros: the sorted deviations are [below | block of
+        the values equal to fabs(0 - c) | above]."""
+        miss = np.isnan(vals)
+        if miss.any():
+            if not na_rm:
+                return NA_real
+            vals = vals[~miss]
+        n = len(vals) + (nrow - len(miss))            # na.rm drops stored values; the padding keeps its size
+        if n == 0:
+            return NA_real
+        with np.errstate(all="ignore"):
+            if c is None:                             # the median's own rule: [negatives | zeros | positives]
+                nz = np.sort(vals[vals != 0.0])
+                c = cls._padded_median(nz, int((nz < 0.0).sum()), n - len(nz), n, 0.0)
+            if c != c:
+                return NA_real
+            t = np.abs(vals - c)                      # one subtraction each
+            b = abs(0.0 - c)                          # every zero, stored or implicit
+            if np.isnan(t).any():                     # a value that is the center's infinity
+                return NA_real
+            out = np.sort(t[t != b])
+            m = cls._padded_median(out, int((out < b).sum()), n - len(out), n, b)
+            return float(np.float64(constant) * np.float64(m))
+
+    def colMads(self, x, center=None, constant=1.4826, na_rm=False):
+        """colMads(x, center, constant, na.rm): constant * median(|x - center|) of every column, ``center`` the
+        column's median unless given (a single number, or one per column)."""
+        center = self._check_mads_args("colMads", x, center, na_rm, 1)
+        constant = float(constant)
+        nrow, ncol = x.dim
+        if nrow == 0:
+            return np.full(ncol, NA_real)
+        has = getattr(self._call, "has_entry", lambda name: False)
+        if has("C_colMads_SVT"):
+            return self.SparseArray_Call("C_colMads_SVT", x, center, constant, bool(na_rm))
+        # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
+        ans = np.zeros(ncol)
+        for j, lf in enumerate(x.leaves):
+            ans[j] = self._leaf_mad(self._leaf_doubles(lf), nrow, None if center is None else float(center[j]),
+                                    constant, bool(na_rm))
+        return ans
+
+    def rowMads(self, x, center=None, constant=1.4826, na_rm=False):
+        """rowMads(x) = colMads(t(x)); ``center``: a single number, or one per row."""
+        center = self._check_mads_args("rowMads", x, center, na_rm, 0)
+        has = getattr(self._call, "has_entry", lambda name: False)
+        if has("C_rowMads_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
+            return self.SparseArray_Call("C_rowMads_SVT", x, center, float(constant), bool(na_rm))   # t(x) on the device
+        return self.colMads(self.t(x), center=center, constant=constant, na_rm=na_rm)
 
     def _rowStats(self, op, x, na_rm=False, center=None, dims=1):
         # .rowStats_SparseArray, R/SparseArray-matrixStats.R:197-259

@@ -155,12 +155,14 @@ struct ColStatsRoute {
 };
 ColStatsRoute colstats_route(int64_t nseg, int64_t nnz);
 int launch_colstats(const StatsArgs &a, int64_t nnz, hipStream_t s);
-// colMedians / colQuantiles (kernels_median.hip): out on the device; ORDER_QUANTILES (type 7): probs on the device too,
-// out[j + q * ncol]; ORDER_MEDIANS: probs and nprobs are not read
-enum { ORDER_MEDIANS = 0, ORDER_QUANTILES = 1 };
+// colMedians / colQuantiles / colMads (kernels_median.hip): out on the device.  ORDER_QUANTILES (type 7): vec = the probs,
+// on the device too, out[j + q * ncol].  ORDER_MADS: vec = one center per column on the device, or NULL for the column's
+// median; the result is constant * (median of the deviations).  ORDER_MEDIANS: vec, nprobs and constant are not read
+enum { ORDER_MEDIANS = 0, ORDER_QUANTILES = 1, ORDER_MADS = 2 };
 size_t order_stat_ws_bytes(int what, int64_t ncol);
 int launch_order_stat(int what, const int64_t *col_ptr, const void *val, int Rtype, int64_t nrow, int64_t ncol,
-		      int64_t nnz, const double *probs, int nprobs, int na_rm, double *out, void *ws, hipStream_t s);
+		      int64_t nnz, const double *vec, int nprobs, double constant, int na_rm, double *out, void *ws,
+		      hipStream_t s);
 
 struct RowStatsArgs {
 	const int64_t *col_ptr;

@@ -906,29 +906,52 @@ extern "C" size_t svt_dev_colquantiles_ws_bytes(int64_t nnz, int64_t ncol, int n
 	return order_stat_ws_bytes(ORDER_QUANTILES, ncol);
 }
 
-static int dev_order_stat_impl(const svt_dev_csc *A, int what, const double *probs, int nprobs, int na_rm, double *out,
-				  void *ws, size_t ws_bytes, void *stream)
+extern "C" size_t svt_dev_colmads_ws_bytes(int64_t nnz, int64_t ncol)
+{
+	(void) nnz;
+	return order_stat_ws_bytes(ORDER_MADS, ncol);
+}
+
+// The names of an order statistic (ORDER_*): its col and row methods, and its device entry point.
+static const char *const order_stat_names[3][3] = {
+	{ "colMedians", "rowMedians", "colmedians" },
+	{ "colQuantiles", "rowQuantiles", "colquantiles" },
+	{ "colMads", "rowMads", "colmads" },
+};
+
+// vec: the probs (ORDER_QUANTILES) or the centers, NULL for the medians (ORDER_MADS), on the device.
+static int dev_order_stat_impl(const svt_dev_csc *A, int what, const double *vec, int nprobs, double constant, int na_rm,
+				  double *out, void *ws, size_t ws_bytes, void *stream)
 {
 	const bool quant = what == ORDER_QUANTILES;
 	if (A->na_background)
-		return svt_set_error("%s() is not supported on NaArray objects", quant ? "colQuantiles" : "colMedians");
+		return svt_set_error("%s() is not supported on NaArray objects", order_stat_names[what][0]);
 	if (quant && nprobs < 0)
 		return svt_set_error("svt_dev_colquantiles: 'nprobs' must be >= 0");
 	if (ws_bytes < order_stat_ws_bytes(what, A->ncol))
-		return svt_set_error("svt_dev_%s: workspace too small", quant ? "colquantiles" : "colmedians");
-	return launch_order_stat(what, A->col_ptr, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, probs, nprobs, na_rm, out,
-				 ws, (hipStream_t) stream);
+		return svt_set_error("svt_dev_%s: workspace too small", order_stat_names[what][2]);
+	return launch_order_stat(what, A->col_ptr, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, vec, nprobs, constant, na_rm,
+				 out, ws, (hipStream_t) stream);
 }
 extern "C" int svt_dev_colmedians(const svt_dev_csc *A, int na_rm, double *out, void *ws,
 				  size_t ws_bytes, void *stream)
 {
-	return abi_status([&] { return dev_order_stat_impl(A, ORDER_MEDIANS, NULL, 0, na_rm, out, ws, ws_bytes, stream); });
+	return abi_status([&] {
+		return dev_order_stat_impl(A, ORDER_MEDIANS, NULL, 0, 0.0, na_rm, out, ws, ws_bytes, stream);
+	});
 }
 extern "C" int svt_dev_colquantiles(const svt_dev_csc *A, const double *probs, int nprobs, int na_rm, double *out,
 				    void *ws, size_t ws_bytes, void *stream)
 {
 	return abi_status([&] {
-		return dev_order_stat_impl(A, ORDER_QUANTILES, probs, nprobs, na_rm, out, ws, ws_bytes, stream);
+		return dev_order_stat_impl(A, ORDER_QUANTILES, probs, nprobs, 0.0, na_rm, out, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_colmads(const svt_dev_csc *A, const double *center, double constant, int na_rm, double *out,
+			       void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		return dev_order_stat_impl(A, ORDER_MADS, center, 0, constant, na_rm, out, ws, ws_bytes, stream);
 	});
 }
 
@@ -2537,17 +2560,20 @@ extern "C" int svt_colStats_SVT(const svt_view *x, int opcode, int na_rm, double
 // reference, with a TODO asking for a .Call version).  out: ncol(x) doubles.
 // colQuantiles(x, probs, na.rm, type = 7): no method in the reference (R/SparseArray-matrixStats.R:5-12); the rule is
 // base R's quantile.default type 7 (kernels_median.hip).  out: ncol(x) * nprobs doubles, column-major.
-static int order_stat_SVT(const svt_view *x, int what, const double *probs, int nprobs, int na_rm, int by_row,
-			  double *out)
+// colMads(x, center, constant, na.rm): no method in the reference either; stats::mad without low / high
+// (kernels_median.hip).  vec: the centers, one per result, or NULL for the medians.  out: ncol(x) doubles.
+static int order_stat_SVT(const svt_view *x, int what, const double *vec, int nprobs, double constant, int na_rm,
+			  int by_row, double *out)
 {
 	const bool quant = what == ORDER_QUANTILES;
-	const char *col = quant ? "colQuantiles" : "colMedians";
+	const char *col = order_stat_names[what][0];
+	const double *probs = vec;
 	if (ensure_init() || check_view(x))
 		return -1;
 	if (x->ndim != 2)       // stopifnot_2D_object(), R/SparseArray-matrixStats.R:51-57
 		return svt_set_error("the %s() method for SparseArray objects only supports 2D "
 				     "objects (i.e. SparseMatrix objects) at the moment",
-				     by_row ? (quant ? "rowQuantiles" : "rowMedians") : col);
+				     order_stat_names[what][by_row ? 1 : 0]);
 	if (x->Rtype != SVT_REALSXP && x->Rtype != SVT_INTSXP && x->Rtype != SVT_LGLSXP)
 		return svt_set_error("%s(): unsupported type", col);
 	if (x->na_background)
@@ -2564,17 +2590,18 @@ static int order_stat_SVT(const svt_view *x, int what, const double *probs, int 
 		return 0;
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	// rowMedians(x) = colMedians(t(x)), :802-815, and rowQuantiles(x) = colQuantiles(t(x)); t() on the device
+	// rowMedians(x) = colMedians(t(x)), :802-815, rowQuantiles(x) = colQuantiles(t(x)) and rowMads(x) = colMads(t(x));
+	// t() on the device
 	const OwnedCsc T = by_row ? transposed_for(A) : OwnedCsc(NULL, false);
 	if (by_row && T.t == NULL) return -1;
 	const svt_dev_csc *M = by_row ? T.t : A.h;
 	DevBuf P, O, W;
 	const size_t out_bytes = (size_t) nout * (quant ? (size_t) nprobs : 1) * 8;
-	if ((quant && P.upload(probs, (size_t) nprobs * 8)) || O.alloc(out_bytes) ||
-	    W.alloc(order_stat_ws_bytes(what, nout)))
+	const size_t vec_bytes = quant ? (size_t) nprobs * 8 : what == ORDER_MADS && vec ? (size_t) nout * 8 : 0;
+	if ((vec_bytes && P.upload(vec, vec_bytes)) || O.alloc(out_bytes) || W.alloc(order_stat_ws_bytes(what, nout)))
 		return -1;
-	if (launch_order_stat(what, M->col_ptr, M->val, M->Rtype, M->nrow, nout, M->nnz, P.as<double>(), nprobs, na_rm,
-			      O.as<double>(), W.p, 0))
+	if (launch_order_stat(what, M->col_ptr, M->val, M->Rtype, M->nrow, nout, M->nnz, P.as<double>(), nprobs, constant,
+			      na_rm, O.as<double>(), W.p, 0))
 		return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	return staged_download(out, O.p, out_bytes);
@@ -2582,22 +2609,32 @@ static int order_stat_SVT(const svt_view *x, int what, const double *probs, int 
 
 extern "C" int svt_colMedians_SVT(const svt_view *x, int na_rm, double *out)
 {
-	return abi_status([&] { return order_stat_SVT(x, ORDER_MEDIANS, NULL, 0, na_rm, 0, out); });
+	return abi_status([&] { return order_stat_SVT(x, ORDER_MEDIANS, NULL, 0, 0.0, na_rm, 0, out); });
 }
 
 extern "C" int svt_rowMedians_SVT(const svt_view *x, int na_rm, double *out)
 {
-	return abi_status([&] { return order_stat_SVT(x, ORDER_MEDIANS, NULL, 0, na_rm, 1, out); });
+	return abi_status([&] { return order_stat_SVT(x, ORDER_MEDIANS, NULL, 0, 0.0, na_rm, 1, out); });
 }
 
 extern "C" int svt_colQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out)
 {
-	return abi_status([&] { return order_stat_SVT(x, ORDER_QUANTILES, probs, nprobs, na_rm, 0, out); });
+	return abi_status([&] { return order_stat_SVT(x, ORDER_QUANTILES, probs, nprobs, 0.0, na_rm, 0, out); });
 }
 
 extern "C" int svt_rowQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out)
 {
-	return abi_status([&] { return order_stat_SVT(x, ORDER_QUANTILES, probs, nprobs, na_rm, 1, out); });
+	return abi_status([&] { return order_stat_SVT(x, ORDER_QUANTILES, probs, nprobs, 0.0, na_rm, 1, out); });
+}
+
+extern "C" int svt_colMads_SVT(const svt_view *x, const double *center, double constant, int na_rm, double *out)
+{
+	return abi_status([&] { return order_stat_SVT(x, ORDER_MADS, center, 0, constant, na_rm, 0, out); });
+}
+
+extern "C" int svt_rowMads_SVT(const svt_view *x, const double *center, double constant, int na_rm, double *out)
+{
+	return abi_status([&] { return order_stat_SVT(x, ORDER_MADS, center, 0, constant, na_rm, 1, out); });
 }
 
 // C_summarize_SVT, src/SparseArray_summarization.c:112-142

@@ -75,6 +75,9 @@ def _lib():
         lib.svt_dev_colquantiles_ws_bytes.restype = c_size_t
         lib.svt_dev_colquantiles_ws_bytes.argtypes = [c_int64, c_int64, c_int]
         lib.svt_dev_colquantiles.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.svt_dev_colmads_ws_bytes.restype = c_size_t
+        lib.svt_dev_colmads_ws_bytes.argtypes = [c_int64, c_int64]
+        lib.svt_dev_colmads.argtypes = [c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
         lib.svt_dev_rowstats_ws_bytes.restype = c_size_t
         lib.svt_dev_rowstats_ws_bytes.argtypes = [c_int64, c_int64]
         lib.svt_dev_rowsums.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -389,6 +392,24 @@ def colquantiles(A: DeviceCSC, probs, na_rm=False, out=None, ws=None):
         ws = torch.empty(_lib().svt_dev_colquantiles_ws_bytes(A.nnz, A.ncol, P), dtype=torch.uint8, device=dev)
     _check(_lib().svt_dev_colquantiles(A.handle, probs.data_ptr(), P, int(na_rm), out.data_ptr(), ws.data_ptr(),
                                        ws.numel(), _stream()))
+    return out
+
+
+def colmads(A: DeviceCSC, center=None, constant=1.4826, na_rm=False, out=None, ws=None):
+    """colMads() of a resident 2-D operand (include/svt_hip.h, svt_dev_colmads).  ``center``: None for the column
+    medians, or a float64 tensor of ncol entries already on the device."""
+    dev = A.val.device
+    if center is not None:
+        assert center.dtype == torch.float64 and center.is_cuda and center.is_contiguous()
+        if center.numel() != A.ncol:
+            raise SparseArrayError("'center' must be NULL, a single number, or a vector with one element per column")
+    if out is None:
+        out = torch.empty(A.ncol, dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == A.ncol
+    if ws is None:
+        ws = torch.empty(_lib().svt_dev_colmads_ws_bytes(A.nnz, A.ncol), dtype=torch.uint8, device=dev)
+    _check(_lib().svt_dev_colmads(A.handle, None if center is None else center.data_ptr(), float(constant), int(na_rm),
+                                  out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return out
 
 
