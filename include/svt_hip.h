@@ -226,7 +226,7 @@ int svt_rowMedians_SVT(const svt_view *x, int na_rm, double *out);
    rowQuantiles(x) is colQuantiles(t(x)) with t() on the device (boxed past 2^31 nonzeros, as for rowMedians).
    colIQRs / rowIQRs are this call with probs = (0.25, 0.75) and Q3 - Q1 on the host.
    These calls are not sharded over the device list of svt_set_devices(): they run on the first entry.
-   Not offered: colRanks, colOrderStats, quantile types other than 7, N-d operands, NaArray operands. */
+   Not offered: colOrderStats, quantile types other than 7, N-d operands, NaArray operands. */
 int svt_colQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out);
 int svt_rowQuantiles_SVT(const svt_view *x, const double *probs, int nprobs, int na_rm, double *out);
 
@@ -252,6 +252,32 @@ int svt_colMads_SVT(const svt_view *x, const double *center /* NULL or ncol(x) *
 		    double *out);
 int svt_rowMads_SVT(const svt_view *x, const double *center /* NULL or nrow(x) */, double constant, int na_rm,
 		    double *out);
+
+/* colRanks(x, ties.method, preserveShape) of a 2-D SVT: rank(na.last = "keep", ties.method) of each column's nrow
+   values, the implicit zeros included (matrixStats::colRanks; the reference has no method).  Per column, with the
+   missing stored values (NaN / NA for doubles, NA_integer_ for integers and logicals) left out, and for a non-missing
+   value v:
+     L = the non-missing values < v (the implicit zeros count when 0 < v);
+     E = the values == v under IEEE == (-0.0, a stored 0.0 and the implicit zeros are one tie group; v counts);
+     SVT_TIES_MAX L + E (matrixStats' default), SVT_TIES_MIN L + 1, SVT_TIES_AVERAGE (double) (2L + E + 1) * 0.5,
+     SVT_TIES_DENSE 1 + the distinct values < v (the zeros are one distinct value if the column holds any).
+   +-Inf are ordinary values.  A missing value gets NA and is counted in nobody's L or E; there is no na.rm.
+   out: nrow(x) * ncol(x) cells, int32 (NA_integer_) for max / min / dense, double (NA_real_ for NaN and NA alike) for
+   average.  colRanks with preserve_shape == 0 (matrixStats' default) fills the TRANSPOSED shape, out[j + i * ncol],
+   ncol x nrow; with preserve_shape != 0 out[i + j * nrow].  rowRanks(x) is colRanks(t(x), preserveShape = FALSE):
+   out[i + j * nrow], nrow x ncol, t() on the device (boxed past 2^31 nonzeros).  Cell indices are 64-bit; zero extents
+   write nothing.  The device computes the compact form of svt_dev_colranks; it is expanded on the host.
+   Errors: not 2-D ("the colRanks() method for SparseArray objects only supports 2D objects ..."; rowRanks() in the row
+   form), NaArray operands ("colRanks() is not supported on NaArray objects"), another `ties` ("'ties.method' must be
+   "max", "average", "min" or "dense""); double / integer / logical values.  Status > 0: more than 2^31-1 columns, or
+   2^32 or more stored values in columns too long to be sorted in LDS.  Not sharded over the device list.
+   Not offered: ties.method "first", "last" and "random" (every implicit zero would need a rank of its own). */
+#define SVT_TIES_MAX 0
+#define SVT_TIES_AVERAGE 1
+#define SVT_TIES_MIN 2
+#define SVT_TIES_DENSE 3
+int svt_colRanks_SVT(const svt_view *x, int ties, int preserve_shape, void *out);
+int svt_rowRanks_SVT(const svt_view *x, int ties, void *out);
 
 /* C_summarize_SVT, src/SparseArray_summarization.c:112-142.  The result is
    left in out_d[0..1] or out_i[0..1] according to *out_Rtype. */
@@ -538,6 +564,25 @@ int svt_dev_colquantiles(const svt_dev_csc *A, const double *probs, int nprobs, 
 size_t svt_dev_colmads_ws_bytes(int64_t nnz, int64_t ncol);
 int svt_dev_colmads(const svt_dev_csc *A, const double *center /* device, NULL = medians */, double constant,
 		    int na_rm, double *out, void *ws, size_t ws_bytes, void *stream);
+
+/* colRanks on the device in the compact form a sparse matrix allows (the rule: svt_colRanks_SVT): all zeros of a
+   column tie, so the result is rank_nz[k], one rank for every stored position k of the CSC (64-bit positions), and
+   zero_rank[j], the rank of column j's zeros -- 4 or 8 bytes per nonzero instead of nrow * ncol cells.  Both are int32
+   for SVT_TIES_MAX / MIN / DENSE and double for SVT_TIES_AVERAGE.  A stored 0.0 or -0.0 gets zero_rank[j]; zero_rank[j]
+   is NA when the column holds no zero at all, stored or implicit.
+   Columns are served by their stored length, inside one call: svt_dev_colranks_form(col_nnz), a pure host query,
+   answers 0 (short: a wavefront per column, counted in LDS), 1 (a workgroup per column, sorted in LDS) or 2 (long:
+   gathered and sorted in the workspace).  ws: svt_dev_colranks_ws_bytes(ncol, long_nnz), long_nnz = the sum of the
+   stored lengths of the columns of form 2 (0 is returned for 2^32 or more: not offered).  A workspace below
+   svt_dev_colranks_ws_bytes(ncol, 0) is an error ("svt_dev_colranks: workspace too small"); if it was made for fewer
+   long nonzeros than the operand holds, nothing is written for the long columns and *flag, a device word that every
+   call clears first, is set to 1.  The sort of the long columns runs over the long nonzeros the workspace has room
+   for (at most nnz), so a workspace made for the exact long_nnz costs least.
+   Asynchronous on `stream`, allocates nothing, reads nothing back. */
+int svt_dev_colranks_form(int64_t col_nnz);
+size_t svt_dev_colranks_ws_bytes(int64_t ncol, int64_t long_nnz);
+int svt_dev_colranks(const svt_dev_csc *A, int ties, void *rank_nz, void *zero_rank, int *flag, void *ws,
+		     size_t ws_bytes, void *stream);
 
 /* row sums: out[(j % inner) * nrow + r] = sum over the leaves j that map to
    that cell.  Every output cell is owned by one workgroup (LDS row panels, no

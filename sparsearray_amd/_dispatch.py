@@ -15,7 +15,7 @@ from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_void_p
 
 import numpy as np
 
-from .api import OPCODES, SparseArrayError, SparseArrayUnsupported, naked_result
+from .api import OPCODES, TIES_METHODS, SparseArrayError, SparseArrayUnsupported, naked_result
 from .svt import (INTSXP, LGLSXP, REALSXP, SVT_SparseArray, make_view,
                   r_type_of, svt_view)
 
@@ -71,6 +71,9 @@ class CAbiDispatcher:
         if hasattr(self.lib, self.prefix + "colMads_SVT"):         # HIP library (api.py states the rule in numpy)
             protos["colMads_SVT"] = (I, [V, P, c_double, I, P])
             protos["rowMads_SVT"] = (I, [V, P, c_double, I, P])
+        if hasattr(self.lib, self.prefix + "colRanks_SVT"):        # HIP library (api.py states the rule in numpy)
+            protos["colRanks_SVT"] = (I, [V, I, I, P])
+            protos["rowRanks_SVT"] = (I, [V, I, P])
         # x %*% y in one call (device-side transposition): HIP library only
         for name, sig in (("matmul_SVT_mat", (I, [V, P, I, I, I, P])),
                           ("matmul_SVT_SVT", (I, [V, V, P])),
@@ -183,6 +186,27 @@ class CAbiDispatcher:
 
     def C_rowMads_SVT(self, x: SVT_SparseArray, center, constant: float, na_rm: bool):
         return self._mads("rowMads_SVT", x, center, constant, na_rm, 0)
+
+    # colRanks / rowRanks (include/svt_hip.h; HIP library only) ---------------------
+    @staticmethod
+    def _ranks_out(x, ties, transposed):
+        """(SVT_TIES_* code, result array): ``ties`` a name or a code; an unknown one is left to the library."""
+        code = TIES_METHODS.get(ties, -1) if isinstance(ties, str) else int(ties)
+        nrow, ncol = (x.dim[0], x.dim[1]) if x.ndim == 2 else (0, 0)
+        shape = (ncol, nrow) if transposed else (nrow, ncol)
+        return code, np.zeros(shape, dtype=np.float64 if code == TIES_METHODS["average"] else np.int32, order="F")
+
+    def C_colRanks_SVT(self, x: SVT_SparseArray, ties, preserve_shape: bool):
+        code, out = self._ranks_out(x, ties, not preserve_shape)
+        xv = make_view(x)
+        self._check(self._fn("colRanks_SVT")(byref(xv), code, int(bool(preserve_shape)), _ptr(out)))
+        return out
+
+    def C_rowRanks_SVT(self, x: SVT_SparseArray, ties):
+        code, out = self._ranks_out(x, ties, False)
+        xv = make_view(x)
+        self._check(self._fn("rowRanks_SVT")(byref(xv), code, _ptr(out)))
+        return out
 
     # resident operands (include/svt_hip.h; HIP library only) --------------------
     def resident_set_limit(self, nbytes: int):

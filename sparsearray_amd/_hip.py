@@ -23,6 +23,7 @@ EXPORTS = [
     "svt_colMedians_SVT", "svt_rowMedians_SVT", "svt_dev_colmedians_ws_bytes", "svt_dev_colmedians",
     "svt_colQuantiles_SVT", "svt_rowQuantiles_SVT", "svt_dev_colquantiles_ws_bytes", "svt_dev_colquantiles",
     "svt_colMads_SVT", "svt_rowMads_SVT", "svt_dev_colmads_ws_bytes", "svt_dev_colmads",
+    "svt_colRanks_SVT", "svt_rowRanks_SVT", "svt_dev_colranks_form", "svt_dev_colranks_ws_bytes", "svt_dev_colranks",
     "svt_resident_set_limit", "svt_resident_clear", "svt_resident_stats", "svt_dev_pbc_bytes", "svt_dev_pbc_set_spare_cus", "svt_dev_pbc_spare_cus", "svt_dev_pbc_set_gather_pacing", "svt_dev_pbc_set_round_launches", "svt_dev_matmul_csc_csc_ws_bytes", "svt_dev_matmul_csc_csc", "svt_dev_rowsums_prepare", "svt_dev_rowsums_prepared", "svt_dev_rowsum_gid_bytes", "svt_dev_rowsum_prepare", "svt_dev_rowsum_prepared", "svt_dev_matmul_csc_csc_prepare", "svt_dev_matmul_csc_csc_prepared",
     "svt_dev_crossprod_csc_csc_ws_bytes", "svt_dev_crossprod_csc_csc", "svt_dev_crossprod_csc_csc_set_panel", "svt_sparse_crossprod_set_cost", "svt_dev_crossprod_csc_csc_dense_buffer",
     "svt_summarize_SVT", "svt_colStats_out_Rtype", "svt_colStats_SVT",

@@ -42,6 +42,9 @@ class SparseArrayUnsupported(SparseArrayError):
 
 _SUPPORTED_MULT_TYPES = ("double", "integer")
 
+# ties.method of colRanks / rowRanks -> SVT_TIES_* (include/svt_hip.h)
+TIES_METHODS = {"max": 0, "average": 1, "min": 2, "dense": 3}
+
 
 # row statistics that C_rowStats_SVT does not take: one C_rowStatsFull_SVT call where the library has it
 _ROWSTATS_FULL_OPS = ("any", "all", "prod", "range", "mean", "var1", "sd1")
@@ -520,6 +523,85 @@ class Session:
         if has("C_rowMads_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
             return self.SparseArray_Call("C_rowMads_SVT", x, center, float(constant), bool(na_rm))   # t(x) on the device
         return self.colMads(self.t(x), center=center, constant=constant, na_rm=na_rm)
+
+    # colRanks / rowRanks.  The reference has no method; the rule is matrixStats::colRanks(x, ties.method,
+    # preserveShape), i.e. rank(na.last = "keep", ties.method) of each column's nrow values with the implicit zeros
+    # included (include/svt_hip.h, svt_colRanks_SVT).  Not offered: ties.method "first", "last" and "random" (every
+    # implicit zero would need a rank of its own), N-d operands, NaArray operands.
+    def _check_ranks_args(self, what, x, ties_method, preserve_shape):
+        if x.ndim != 2:
+            raise SparseArrayError(
+                f"the {what}() method for SparseArray objects only supports 2D "
+                "objects (i.e. SparseMatrix objects) at the moment")
+        if x.na_background:
+            raise SparseArrayError("colRanks() is not supported on NaArray objects")
+        if not isinstance(ties_method, str) or ties_method not in TIES_METHODS:
+            raise SparseArrayError("'ties.method' must be \"max\", \"average\", \"min\" or \"dense\"")
+        if not isinstance(preserve_shape, (bool, np.bool_)):
+            raise SparseArrayError("'preserveShape' must be TRUE or FALSE")
+
+    @staticmethod
+    def _leaf_ranks(vals, nrow, ties_method):
+        """The ranks of one leaf's stored values among its nrow values, and the rank of its zeros (None when it holds
+        no zero, stored or implicit), without realising the zeros: the non-missing stored values are sorted, the block
+        of the zeros has nrow - length + stored zeros members.  A missing value's rank is NA."""
+        average = ties_method == "average"
+        na = NA_real if average else NA_integer
+        ranks = np.full(len(vals), na, dtype=np.float64 if average else np.int32)
+        ok = ~np.isnan(vals)
+        v = vals[ok] + 0.0                              # -0.0 is 0.0
+        s = np.sort(v)
+        z = nrow - len(vals)                            # implicit zeros
+        nzs = int((s == 0.0).sum())
+        pos = v > 0.0
+        L = np.searchsorted(s, v, "left") + z * pos
+        E = np.searchsorted(s, v, "right") - np.searchsorted(s, v, "left") + z * (v == 0.0)
+        u = np.unique(s)
+        D = np.searchsorted(u, v, "left") + (pos & (z > 0 and nzs == 0))
+        neg, dneg = int((s < 0.0).sum()), int((u < 0.0).sum())
+
+        def rank(L, E, D):
+            if ties_method == "max":
+                return L + E
+            if ties_method == "min":
+                return L + 1
+            if ties_method == "dense":
+                return D + 1
+            return (2 * L + E + 1).astype(np.float64) * 0.5 if isinstance(L, np.ndarray) else (2 * L + E + 1) * 0.5
+
+        ranks[ok] = rank(L, E, D)
+        zero = rank(neg, z + nzs, dneg) if z + nzs > 0 else na
+        return ranks, zero
+
+    def colRanks(self, x, ties_method="max", preserve_shape=False):
+        """colRanks(x, ties.method, preserveShape): the rank of every value within its column, NA for a missing one;
+        int32 for "max" / "min" / "dense", float64 for "average".  As in matrixStats the result is TRANSPOSED,
+        (ncol, nrow), unless ``preserve_shape``."""
+        self._check_ranks_args("colRanks", x, ties_method, preserve_shape)
+        nrow, ncol = x.dim
+        dtype = np.float64 if ties_method == "average" else np.int32
+        shape = (nrow, ncol) if preserve_shape else (ncol, nrow)
+        if nrow == 0 or ncol == 0:
+            return np.zeros(shape, dtype=dtype, order="F")
+        has = getattr(self._call, "has_entry", lambda name: False)
+        if has("C_colRanks_SVT"):
+            return self.SparseArray_Call("C_colRanks_SVT", x, ties_method, bool(preserve_shape))
+        # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
+        ans = np.zeros((nrow, ncol), dtype=dtype, order="F")
+        for j, lf in enumerate(x.leaves):
+            ranks, zero = self._leaf_ranks(self._leaf_doubles(lf), nrow, ties_method)
+            ans[:, j] = zero
+            if lf is not None:
+                ans[np.asarray(lf[0]), j] = ranks
+        return ans if preserve_shape else np.asfortranarray(ans.T)
+
+    def rowRanks(self, x, ties_method="max"):
+        """rowRanks(x) = colRanks(t(x), preserveShape = FALSE): an (nrow, ncol) array."""
+        self._check_ranks_args("rowRanks", x, ties_method, False)
+        has = getattr(self._call, "has_entry", lambda name: False)
+        if has("C_rowRanks_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
+            return self.SparseArray_Call("C_rowRanks_SVT", x, ties_method)          # t(x) on the device
+        return self.colRanks(self.t(x), ties_method=ties_method, preserve_shape=False)
 
     def _rowStats(self, op, x, na_rm=False, center=None, dims=1):
         # .rowStats_SparseArray, R/SparseArray-matrixStats.R:197-259

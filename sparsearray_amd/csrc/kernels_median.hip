@@ -38,7 +38,7 @@
 // (at most 8 x 8) per nonzero and request of an undecided column (short columns stay in the L2).
 // colMads(x, center, constant, na.rm): stats::mad without low / high, stated at MadRule below -- the same two kernels
 // over the deviations fabs(x - c), whose block of equal values is fabs(0.0 - c) instead of 0.0.
-// Not built: colRanks, colOrderStats, quantile types other than 7, the low / high medians of mad, N-d operands,
+// Not built: colOrderStats (colRanks is kernels_ranks.hip: a sort per column, not a select), quantile types other than 7, the low / high medians of mad, N-d operands,
 // NaArray operands.
 #include "svt_common.h"
 

@@ -163,6 +163,13 @@ size_t order_stat_ws_bytes(int what, int64_t ncol);
 int launch_order_stat(int what, const int64_t *col_ptr, const void *val, int Rtype, int64_t nrow, int64_t ncol,
 		      int64_t nnz, const double *vec, int nprobs, double constant, int na_rm, double *out, void *ws,
 		      hipStream_t s);
+// colRanks in the compact form (kernels_ranks.hip): rank_nz one rank per stored value, zero_rank one per column, int32
+// or (SVT_TIES_AVERAGE) double; flag: a device word, cleared first, set when the workspace was made for fewer long
+// nonzeros than the operand holds.  ranks_form(): 0, 1 or 2 by a column's stored length (svt_dev_colranks_form).
+int ranks_form(int64_t col_nnz);
+size_t ranks_ws_bytes(int64_t ncol, int64_t long_nnz);
+int launch_ranks(const int64_t *col_ptr, const void *val, int Rtype, int64_t nrow, int64_t ncol, int64_t nnz, int ties,
+		 void *rank_nz, void *zero_rank, int *flag, void *ws, size_t ws_bytes, hipStream_t s);
 
 struct RowStatsArgs {
 	const int64_t *col_ptr;

@@ -955,6 +955,34 @@ extern "C" int svt_dev_colmads(const svt_dev_csc *A, const double *center, doubl
 	});
 }
 
+// colRanks in the compact form (kernels_ranks.hip)
+extern "C" int svt_dev_colranks_form(int64_t col_nnz) { return ranks_form(col_nnz); }
+extern "C" size_t svt_dev_colranks_ws_bytes(int64_t ncol, int64_t long_nnz) { return ranks_ws_bytes(ncol, long_nnz); }
+
+static int check_ties(int ties)
+{
+	if (ties != SVT_TIES_MAX && ties != SVT_TIES_AVERAGE && ties != SVT_TIES_MIN && ties != SVT_TIES_DENSE)
+		return svt_set_error("'ties.method' must be \"max\", \"average\", \"min\" or \"dense\"");
+	return 0;
+}
+
+extern "C" int svt_dev_colranks(const svt_dev_csc *A, int ties, void *rank_nz, void *zero_rank, int *flag, void *ws,
+				size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		if (flag == NULL)
+			return svt_set_error("svt_dev_colranks: 'flag' must be a device word");
+		// (the flag is cleared on every call, before any early return)
+		HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), (hipStream_t) stream));
+		if (A->na_background)
+			return svt_set_error("colRanks() is not supported on NaArray objects");
+		if (check_ties(ties))
+			return -1;
+		return launch_ranks(A->col_ptr, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, ties, rank_nz, zero_rank, flag, ws,
+				    ws_bytes, (hipStream_t) stream);
+	});
+}
+
 extern "C" size_t svt_dev_rowstats_ws_bytes(int64_t nrow, int64_t ncol)
 {
 	return rowstats_panel_ws_bytes(nrow, ncol);
@@ -2635,6 +2663,107 @@ extern "C" int svt_colMads_SVT(const svt_view *x, const double *center, double c
 extern "C" int svt_rowMads_SVT(const svt_view *x, const double *center, double constant, int na_rm, double *out)
 {
 	return abi_status([&] { return order_stat_SVT(x, ORDER_MADS, center, 0, constant, na_rm, 1, out); });
+}
+
+// colRanks(x, ties.method, preserveShape) / rowRanks(x, ties.method): no method in the reference; the rule is
+// matrixStats::colRanks (include/svt_hip.h).  The device answers in the compact form (kernels_ranks.hip: a rank per
+// stored value, a rank per column for its zeros), which is expanded here: every cell of a column gets the zeros' rank,
+// then the stored positions theirs.  M, the operand whose columns are ranked, is x or t(x); transposed != 0 fills
+// out[j + i * ncol(M)], else out[i + j * nrow(M)].
+template <typename R>
+static void expand_ranks(const int64_t *cp, const int32_t *ri, const R *rank_nz, const R *zero_rank, int64_t mrow,
+			 int64_t mcol, bool transposed, R *out)
+{
+	const size_t cells = (size_t) mrow * (size_t) mcol * sizeof(R);
+	if (transposed) {
+		// a row of the result is the zeros' ranks of all columns, then the stored values of the columns are scattered
+		team_run(team_size(cells), [&](int t, int nt) {
+			for (int64_t i = mrow * t / nt; i < mrow * (t + 1) / nt; i++)
+				memcpy(out + i * mcol, zero_rank, (size_t) mcol * sizeof(R));
+		});
+		team_run(team_size(cells), [&](int t, int nt) {
+			for (int64_t j = mcol * t / nt; j < mcol * (t + 1) / nt; j++)
+				for (int64_t k = cp[j]; k < cp[j + 1]; k++)
+					out[j + (int64_t) ri[k] * mcol] = rank_nz[k];
+		});
+		return;
+	}
+	team_run(team_size(cells), [&](int t, int nt) {
+		for (int64_t j = mcol * t / nt; j < mcol * (t + 1) / nt; j++) {
+			R *col = out + j * mrow;
+			for (int64_t i = 0; i < mrow; i++) col[i] = zero_rank[j];
+			for (int64_t k = cp[j]; k < cp[j + 1]; k++) col[ri[k]] = rank_nz[k];
+		}
+	});
+}
+
+static int ranks_SVT(const svt_view *x, int ties, int preserve_shape, int by_row, void *out)
+{
+	if (ensure_init() || check_view(x))
+		return -1;
+	if (x->ndim != 2)
+		return svt_set_error("the %s() method for SparseArray objects only supports 2D "
+				     "objects (i.e. SparseMatrix objects) at the moment", by_row ? "rowRanks" : "colRanks");
+	if (x->Rtype != SVT_REALSXP && x->Rtype != SVT_INTSXP && x->Rtype != SVT_LGLSXP)
+		return svt_set_error("colRanks(): unsupported type");
+	if (x->na_background)
+		return svt_set_error("colRanks() is not supported on NaArray objects");
+	if (check_ties(ties))
+		return -1;
+	if (x->dim[0] == 0 || x->dim[1] == 0)
+		return 0;                                       // zero extents: no cell to write
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	const OwnedCsc T = by_row ? transposed_for(A) : OwnedCsc(NULL, false);
+	if (by_row && T.t == NULL) return -1;
+	const svt_dev_csc *M = by_row ? T.t : A.h;
+	const int64_t mrow = M->nrow, mcol = M->ncol, nnz = M->nnz;
+	if (mcol > 0x7FFFFFFFLL)
+		return svt_set_unsupported("colRanks: more than 2^31-1 columns");
+	// the structure comes back for the expansion; the column lengths also say how much the long columns hold
+	std::vector<int64_t> cp((size_t) mcol + 1);
+	std::vector<int32_t> ri((size_t) nnz);
+	HIP_TRY(hipMemcpy(cp.data(), M->col_ptr, cp.size() * 8, hipMemcpyDeviceToHost));
+	if (nnz > 0 && staged_download(ri.data(), M->row_idx, (size_t) nnz * 4))
+		return -1;
+	int64_t long_nnz = 0;
+	for (int64_t j = 0; j < mcol; j++)
+		if (ranks_form(cp[(size_t) j + 1] - cp[(size_t) j]) == 2) long_nnz += cp[(size_t) j + 1] - cp[(size_t) j];
+	if (long_nnz > 0xFFFFFFFFLL)
+		return svt_set_unsupported("colRanks: 2^32 or more stored values in the columns sorted in the workspace");
+	const size_t esz = ties == SVT_TIES_AVERAGE ? 8 : 4;
+	const size_t wsb = ranks_ws_bytes(mcol, long_nnz);
+	DevBuf RN, RZ, F, W;
+	if (RN.alloc((size_t) nnz * esz) || RZ.alloc((size_t) mcol * esz) || F.alloc(sizeof(int)) || W.alloc(wsb))
+		return -1;
+	if (launch_ranks(M->col_ptr, M->val, M->Rtype, mrow, mcol, nnz, ties, RN.p, RZ.p, F.as<int>(), W.p, wsb, 0))
+		return -1;
+	HIP_TRY(hipDeviceSynchronize());
+	int flag = 0;
+	HIP_TRY(hipMemcpy(&flag, F.p, sizeof(int), hipMemcpyDeviceToHost));
+	if (flag)
+		return svt_set_error("colRanks: the workspace did not hold the long columns");
+	std::vector<char> rn((size_t) nnz * esz), rz((size_t) mcol * esz);
+	if ((nnz > 0 && staged_download(rn.data(), RN.p, rn.size())) || staged_download(rz.data(), RZ.p, rz.size()))
+		return -1;
+	const bool transposed = by_row || !preserve_shape;
+	if (esz == 8)
+		expand_ranks<double>(cp.data(), ri.data(), (const double *) rn.data(), (const double *) rz.data(), mrow, mcol,
+				     transposed, (double *) out);
+	else
+		expand_ranks<int32_t>(cp.data(), ri.data(), (const int32_t *) rn.data(), (const int32_t *) rz.data(), mrow, mcol,
+				      transposed, (int32_t *) out);
+	return 0;
+}
+
+extern "C" int svt_colRanks_SVT(const svt_view *x, int ties, int preserve_shape, void *out)
+{
+	return abi_status([&] { return ranks_SVT(x, ties, preserve_shape, 0, out); });
+}
+
+extern "C" int svt_rowRanks_SVT(const svt_view *x, int ties, void *out)
+{
+	return abi_status([&] { return ranks_SVT(x, ties, 0, 1, out); });
 }
 
 // C_summarize_SVT, src/SparseArray_summarization.c:112-142

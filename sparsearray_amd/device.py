@@ -78,6 +78,10 @@ def _lib():
         lib.svt_dev_colmads_ws_bytes.restype = c_size_t
         lib.svt_dev_colmads_ws_bytes.argtypes = [c_int64, c_int64]
         lib.svt_dev_colmads.argtypes = [c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.svt_dev_colranks_form.argtypes = [c_int64]
+        lib.svt_dev_colranks_ws_bytes.restype = c_size_t
+        lib.svt_dev_colranks_ws_bytes.argtypes = [c_int64, c_int64]
+        lib.svt_dev_colranks.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         lib.svt_dev_rowstats_ws_bytes.restype = c_size_t
         lib.svt_dev_rowstats_ws_bytes.argtypes = [c_int64, c_int64]
         lib.svt_dev_rowsums.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -411,6 +415,55 @@ def colmads(A: DeviceCSC, center=None, constant=1.4826, na_rm=False, out=None, w
     _check(_lib().svt_dev_colmads(A.handle, None if center is None else center.data_ptr(), float(constant), int(na_rm),
                                   out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return out
+
+
+def colranks_form_limits():
+    """(last stored length of form 0, last stored length of form 1) of svt_dev_colranks_form, found by bisection."""
+    form = _lib().svt_dev_colranks_form
+
+    def last(f):
+        lo, hi = 0, 1 << 40                             # form(lo) <= f < form(hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if form(mid) <= f else (lo, mid)
+        return lo
+    return last(0), last(1)
+
+
+def colranks_long_nnz(A: DeviceCSC) -> int:
+    """The stored values in the columns that svt_dev_colranks sorts in its workspace (form 2)."""
+    lens = A.col_ptr[1:] - A.col_ptr[:-1]
+    return int(lens[lens > colranks_form_limits()[1]].sum().item())
+
+
+def colranks(A: DeviceCSC, ties_method="max", rank_nz=None, zero_rank=None, ws=None, flag=None):
+    """colRanks() of a resident 2-D operand in the compact form (include/svt_hip.h, svt_dev_colranks): returns
+    (rank_nz, zero_rank), one rank per stored value and one per column for its zeros, int32 tensors, or float64 ones
+    for "average".  Without ``ws`` the workspace is sized from the column lengths (one read-back); a given one that was
+    made for fewer long nonzeros than the operand holds raises.  ``flag``: a caller's int32 device word for that
+    condition; it is then left to the caller to read, and the call stays asynchronous."""
+    from .api import TIES_METHODS
+    if ties_method not in TIES_METHODS:
+        raise SparseArrayError("'ties.method' must be \"max\", \"average\", \"min\" or \"dense\"")
+    dev = A.val.device
+    dtype = torch.float64 if ties_method == "average" else torch.int32
+    if rank_nz is None:
+        rank_nz = torch.empty(A.nnz, dtype=dtype, device=dev)
+    if zero_rank is None:
+        zero_rank = torch.empty(A.ncol, dtype=dtype, device=dev)
+    assert rank_nz.dtype == dtype and rank_nz.is_contiguous() and rank_nz.numel() == A.nnz
+    assert zero_rank.dtype == dtype and zero_rank.is_contiguous() and zero_rank.numel() == A.ncol
+    if ws is None:
+        ws = torch.empty(_lib().svt_dev_colranks_ws_bytes(A.ncol, colranks_long_nnz(A)), dtype=torch.uint8, device=dev)
+    own_flag = flag is None
+    if own_flag:
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    assert flag.dtype == torch.int32 and flag.is_cuda and flag.numel() == 1
+    _check(_lib().svt_dev_colranks(A.handle, TIES_METHODS[ties_method], rank_nz.data_ptr(), zero_rank.data_ptr(),
+                                   flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    if own_flag and int(flag.item()):
+        raise SparseArrayError("svt_dev_colranks: the workspace was made for fewer long nonzeros than the operand holds")
+    return rank_nz, zero_rank
 
 
 def matmul_csc_csc(A: DeviceCSC, B: DeviceCSC, out=None, ws=None):
