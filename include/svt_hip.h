@@ -665,6 +665,21 @@ int svt_set_max_threads(int nthread);
 size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz);
 int svt_dev_transpose(const svt_dev_csc *A, int64_t *out_col_ptr, int32_t *out_row_idx,
 		      void *out_val, void *ws, size_t ws_bytes, void *stream);
+/* Alignment, for svt_dev_transpose() and svt_dev_aperm() alike: the caller aligns `ws` and the three output arrays
+   to 256 bytes (what a device allocation has; `ws` is carved into arrays at multiples of 256 bytes from its start).
+   The calls write nothing outside [ws, ws + the advertised size) and the three outputs at the sizes given above. */
+/* Which form svt_dev_transpose() takes for an nrow x ncol operand of nnz nonzeros (nslab = 1), or the step "first
+   two axes change places" of svt_dev_aperm() for nslab matrices of nrow x ncol holding nnz nonzeros in all
+   (nslab > 1) -- the decision of the launch itself, by the same functions.  Host only: no launch, no device needed.
+     out[0]  1: the bucketed form (count, scatter, finish); 0: the key sort (t()) / another route (aperm)
+     out[1]  fbits: a fine bucket is 2^fbits rows (0 .. 6)        out[2]  cbits: 2^cbits fine buckets per coarse one (4, 5)
+     out[3]  nfb: fine buckets per matrix                          out[4]  ncoarse: coarse buckets per matrix
+     out[5]  ngroups: groups of 256 columns per matrix
+     out[6]  8-bit passes of the key sort over the row index, ceil(bits(nrow) / 8)
+     out[7]  why not: 0 taken; 1 the shape rule refuses (out[1..5] are then -1, -1, 0, 0, 0); 2 the shape rule
+             accepts, but the tables of the form need more than the workspace of t() sets aside for them
+   Returns 0, or -1 for a NULL `out` or nslab < 1. */
+int svt_dev_transpose_plan(int64_t nrow, int64_t ncol, int64_t nnz, int64_t nslab, int64_t out[8]);
 /* Box limit of the transposition and of the aperm that moves the rows, process-wide (tests, timing):
    n > 0 sends every such operand of more than n nonzeros through the boxed driver with boxes of at
    most n nonzeros (or one column / one index of the axis that becomes the rows); n <= 0 restores the

@@ -36,7 +36,7 @@ EXPORTS = [
     "svt_dev_pbc_build", "svt_dev_pbc_release", "svt_dev_pbc_trim",
     "svt_dev_crossprod_pbc_ws_bytes", "svt_dev_crossprod_pbc", "svt_dev_crossprod_pbc_phase", "svt_dev_crossprod_pbc_from",
     "svt_dev_crossprod_pbc_plan",
-    "svt_get_num_procs", "svt_get_max_threads", "svt_set_max_threads", "svt_dev_aperm_ws_bytes", "svt_dev_aperm_perm_ws_bytes", "svt_dev_aperm", "svt_dev_aperm_route_counts", "svt_aperm_SVT", "svt_transpose_2D_SVT", "svt_dev_transpose_ws_bytes", "svt_dev_transpose", "svt_dev_set_box_nnz", "svt_dev_boxed_calls", "svt_dev_colstats", "svt_dev_rowstats_ws_bytes", "svt_dev_rowsums", "svt_dev_rowsum",
+    "svt_get_num_procs", "svt_get_max_threads", "svt_set_max_threads", "svt_dev_aperm_ws_bytes", "svt_dev_aperm_perm_ws_bytes", "svt_dev_aperm", "svt_dev_aperm_route_counts", "svt_aperm_SVT", "svt_transpose_2D_SVT", "svt_dev_transpose_ws_bytes", "svt_dev_transpose", "svt_dev_transpose_plan", "svt_dev_set_box_nnz", "svt_dev_boxed_calls", "svt_dev_colstats", "svt_dev_rowstats_ws_bytes", "svt_dev_rowsums", "svt_dev_rowsum",
     "svt_rowStatsFull_SVT", "svt_dev_rowstats_ws_bytes_op", "svt_dev_rowstats",
     "svt_dev_colstats_form", "svt_dev_rowstats_form",
 ]
@@ -168,6 +168,26 @@ def pbc_plan(handle, K: int, tr_y: bool, stride_c: int, stride_k: int, first_col
         raise HipBackendError(lib.svt_last_error().decode())
     d = {f: int(getattr(st, f)) for f, _ in _PbcPlanStruct._fields_}
     d["kind"], d["kernel"], d["direct"] = PBC_KINDS[st.kind], PBC_KERNELS[st.kernel], bool(st.direct)
+    return d
+
+
+TRANSPOSE_PLAN_FIELDS = ("bucketed", "fbits", "cbits", "nfb", "ncoarse", "ngroups", "key_sort_passes", "why_not")
+TRANSPOSE_PLAN_WHY = ("taken", "shape", "reserve")
+
+
+def transpose_plan(nrow: int, ncol: int, nnz: int, nslab: int = 1) -> dict:
+    """The form t() takes for an ``nrow`` x ``ncol`` operand of ``nnz`` nonzeros, or (``nslab`` > 1) the step "first
+    two axes change places" of aperm() for ``nslab`` such matrices holding ``nnz`` nonzeros in all (include/svt_hip.h,
+    svt_dev_transpose_plan): bucketed, fbits, cbits, nfb, ncoarse, ngroups, key_sort_passes, why_not (one of
+    TRANSPOSE_PLAN_WHY).  Needs no GPU."""
+    lib = load_library()
+    lib.svt_dev_transpose_plan.argtypes = [ctypes.c_int64] * 4 + [ctypes.POINTER(ctypes.c_int64)]
+    lib.svt_dev_transpose_plan.restype = ctypes.c_int
+    out = (ctypes.c_int64 * 8)()
+    if lib.svt_dev_transpose_plan(int(nrow), int(ncol), int(nnz), int(nslab), out) != 0:
+        raise HipBackendError(lib.svt_last_error().decode())
+    d = dict(zip(TRANSPOSE_PLAN_FIELDS, (int(x) for x in out)))
+    d["bucketed"], d["why_not"] = bool(d["bucketed"]), TRANSPOSE_PLAN_WHY[d["why_not"]]
     return d
 
 

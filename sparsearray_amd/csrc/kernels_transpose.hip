@@ -207,7 +207,7 @@ transpose_count_kernel(const int64_t *__restrict__ col_ptr, const int32_t *__res
 	const int cshift = sh.fbits + sh.cbits;         // log2(rows per coarse bucket)
 	int64_t beg = 0, end = 0;
 	if (have) { beg = col_ptr[c]; end = col_ptr[c + 1]; }
-	for (int64_t w0 = 0; w0 < sh.nfb; w0 += T1_HIST) {          // (one sweep unless there are > 32768 fine buckets)
+	for (int64_t w0 = 0; w0 < sh.nfb; w0 += T1_HIST) {          // (one sweep unless there are > T1_HIST = 65536 fine buckets)
 		const int64_t w1 = w0 + T1_HIST < sh.nfb ? w0 + T1_HIST : sh.nfb;
 		for (int x = threadIdx.x; x < (int) ((w1 - w0 + 1) >> 1); x += T1_NT) hist[x] = 0;
 		__syncthreads();
@@ -878,6 +878,17 @@ static int launch_transpose_bucketed(const int64_t *col_ptr, const int32_t *row_
 	return 0;
 }
 
+// The route of t() below 2^31 nonzeros: 0 the bucketed form (*sh, *reserve filled), 1 t2_shape() refuses the operand,
+// 2 the head of its workspace does not fit what t2_reserve() sets aside; 1 and 2 take the key sort.
+static int t_route(int64_t nrow, int64_t ncol, int64_t nnz, T2Shape *sh, size_t *reserve)
+{
+	*reserve = t2_reserve(nrow, nnz);
+	// (one matrix: t2_shape() leaves nslab = 1, srow = nrow, scol = ncol)
+	if (!t2_shape(nrow, ncol, nnz, sh))
+		return 1;
+	return t2_head(*sh).total > *reserve ? 2 : 0;
+}
+
 int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype,
 		     int64_t nrow, int64_t ncol, int64_t nnz, int64_t *out_ptr, int32_t *out_idx,
 		     void *out_val, void *ws, hipStream_t s)
@@ -889,9 +900,8 @@ int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void 
 		return 0;
 	}
 	T2Shape sh;
-	const size_t reserve = t2_reserve(nrow, nnz);
-	// (one matrix: t2_shape() leaves nslab = 1, srow = nrow, scol = ncol)
-	if (!t2_shape(nrow, ncol, nnz, &sh) || t2_head(sh).total > reserve)
+	size_t reserve = 0;
+	if (t_route(nrow, ncol, nnz, &sh, &reserve) != 0)
 		return launch_transpose_sorted(col_ptr, row_idx, val, Rtype, nrow, ncol, nnz, out_ptr, out_idx, out_val, ws, s);
 	g_route[R_T_BUCKETED]++;
 	return launch_transpose_bucketed(col_ptr, row_idx, val, Rtype, nrow, ncol, nnz, sh, out_ptr, out_idx, out_val, ws, reserve, s);
@@ -1704,6 +1714,35 @@ static size_t aperm_swap01_bytes(int64_t nnz, const int64_t *dim, int ndim, T2Sh
 	return t2_body(res, (size_t) nnz, (size_t) (sh->ncoarse + 1) * (size_t) (sh->nslab * sh->scol)).total;
 }
 
+// svt_dev_transpose_plan (include/svt_hip.h): the decision of launch_transpose() (nslab = 1) or of aperm_swap01_bytes()
+// (nslab > 1: `nslab` matrices of nrow x ncol, nnz nonzeros in all), by the same functions.  No launch, no device.
+extern "C" int svt_dev_transpose_plan(int64_t nrow, int64_t ncol, int64_t nnz, int64_t nslab, int64_t out[8])
+{
+	if (out == NULL || nslab < 1)
+		return svt_set_error("svt_dev_transpose_plan: NULL result or nslab < 1");
+	T2Shape sh;
+	memset(&sh, 0, sizeof(sh));
+	int why;
+	if (nnz <= 0 || nnz >= ((int64_t) 1 << 31)) {
+		why = 1;                                            // (no nonzeros: a memset; 2^31 and more: the boxed driver)
+	} else if (nslab == 1) {
+		size_t reserve = 0;
+		why = t_route(nrow, ncol, nnz, &sh, &reserve);
+	} else {
+		const int64_t dim[3] = {nrow, ncol, nslab};
+		why = aperm_swap01_bytes(nnz, dim, 3, &sh, NULL) > 0 ? 0 : 1;
+	}
+	out[0] = why == 0;
+	out[1] = why == 1 ? -1 : sh.fbits;
+	out[2] = why == 1 ? -1 : sh.cbits;
+	out[3] = why == 1 ? 0 : sh.nfb;
+	out[4] = why == 1 ? 0 : sh.ncoarse;
+	out[5] = why == 1 ? 0 : sh.ngroups;
+	out[6] = (key_bits(nrow) + 7) / 8;
+	out[7] = why;
+	return 0;
+}
+
 // the first two axes change places, the others stay: one batched bucketed transposition, no sort
 static int aperm_swap01(const ApermCall &c)
 {
@@ -1847,11 +1886,18 @@ static size_t aperm_general_bytes(int64_t nnz, const int64_t *dim, int ndim, siz
 	if (ndim < 3 || nnz <= 0)
 		return 0;
 	size_t need = 0;
-	for (int q = 1; q < ndim; q++) {
-		int perm[8];
-		perm[0] = q; perm[1] = 0;
-		for (int a = 1, i = 2; a < ndim; a++)
+	// The plan depends on perm through q = perm[0] and through whether a step C is left to do: only then may the slab form
+	// stand in for a refused step B (slab_first).  Both kinds of every q: c(q, 1, others) and c(q, others, 1).  (Sized from
+	// the first kind alone, a slab_first plan whose step B is refused carved its intermediate out of a workspace that had
+	// none set aside, and the step's key sort behind it wrote past the end.)
+	for (int qc = 2; qc < 2 * ndim; qc++) {
+		const int q = qc / 2, with_c = qc & 1;
+		int perm[8], i = 1;
+		perm[0] = q;
+		if (!with_c) perm[i++] = 0;
+		for (int a = 1; a < ndim; a++)
 			if (a != q) perm[i++] = a;
+		if (with_c) perm[i++] = 0;
 		ApermPlan3 pl;
 		if (!aperm_general_plan(nnz, dim, ndim, perm, &pl))
 			continue;

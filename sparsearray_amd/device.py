@@ -151,33 +151,47 @@ class DeviceCSC:
     def handle(self):
         return c_void_p(self._h)
 
-    def t(self) -> "DeviceCSC":
-        """t(x) on the device (2-d operands)."""
+    def _outputs(self, nleaves, out):
+        """The (col_ptr, row_idx, val) triple a transposition / permutation writes: ``out`` checked, or new tensors."""
         dev = self.val.device
-        cp = torch.empty(self.nrow + 1, dtype=torch.int64, device=dev)
-        ri = torch.empty(self.nnz, dtype=torch.int32, device=dev)
-        vv = torch.empty(self.nnz, dtype=self.val.dtype, device=dev)
-        ws = torch.empty(_lib().svt_dev_transpose_ws_bytes(self.nrow, self.nnz), dtype=torch.uint8, device=dev)
+        if out is None:
+            return (torch.empty(nleaves + 1, dtype=torch.int64, device=dev),
+                    torch.empty(self.nnz, dtype=torch.int32, device=dev),
+                    torch.empty(self.nnz, dtype=self.val.dtype, device=dev))
+        cp, ri, vv = out
+        assert cp.dtype == torch.int64 and cp.numel() == nleaves + 1 and cp.is_contiguous() and cp.is_cuda
+        assert ri.dtype == torch.int32 and ri.numel() == self.nnz and ri.is_contiguous() and ri.is_cuda
+        assert vv.dtype == self.val.dtype and vv.numel() == self.nnz and vv.is_contiguous() and vv.is_cuda
+        return cp, ri, vv
+
+    def t(self, ws=None, out=None) -> "DeviceCSC":
+        """t(x) on the device (2-d operands).  ``ws``: a uint8 tensor of at least svt_dev_transpose_ws_bytes() bytes,
+        ``out``: the (col_ptr, row_idx, val) tensors of the result; by default both are allocated here."""
+        cp, ri, vv = self._outputs(self.nrow, out)
+        if ws is None:
+            ws = torch.empty(_lib().svt_dev_transpose_ws_bytes(self.nrow, self.nnz), dtype=torch.uint8,
+                             device=self.val.device)
+        assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda
         _check(_lib().svt_dev_transpose(self.handle, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(),
                                         ws.data_ptr(), ws.numel(), _stream()))
         return DeviceCSC(self.ncol, cp, ri, vv, logical=self.Rtype == LGLSXP)
 
-    def aperm(self, dim, perm):
+    def aperm(self, dim, perm, ws=None, out=None):
         """aperm(x, perm) on the device for the N-d array of extents ``dim`` stored in
         this layout (dim[0] == nrow, prod(dim[1:]) == ncol); ``perm`` is 1-based.
         Returns (DeviceCSC of the permuted array, its dim).  The workspace is the permutation's own need
         (svt_dev_aperm_perm_ws_bytes): past the box limit a permutation that moves the rows takes the boxed
-        driver, a leaf-preserving one needs the scratch of one scan."""
+        driver, a leaf-preserving one needs the scratch of one scan.  ``ws`` (uint8) and ``out`` (the result's
+        (col_ptr, row_idx, val) tensors) may be given; by default both are allocated here."""
         dim = np.asarray(dim, dtype=np.int64)
         perm = np.asarray(perm, dtype=np.int32)
         new_dim = tuple(int(dim[p - 1]) for p in perm)
         new_nl = int(np.prod(new_dim[1:], dtype=np.int64)) if len(new_dim) > 1 else 1
-        dev = self.val.device
-        cp = torch.empty(new_nl + 1, dtype=torch.int64, device=dev)
-        ri = torch.empty(self.nnz, dtype=torch.int32, device=dev)
-        vv = torch.empty(self.nnz, dtype=self.val.dtype, device=dev)
-        nb = _lib().svt_dev_aperm_perm_ws_bytes(self.nnz, len(dim), dim.ctypes.data, perm.ctypes.data)
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        cp, ri, vv = self._outputs(new_nl, out)
+        if ws is None:
+            nb = _lib().svt_dev_aperm_perm_ws_bytes(self.nnz, len(dim), dim.ctypes.data, perm.ctypes.data)
+            ws = torch.empty(nb, dtype=torch.uint8, device=self.val.device)
+        assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda
         _check(_lib().svt_dev_aperm(self.handle, len(dim), dim.ctypes.data, perm.ctypes.data,
                                     cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
                                     ws.numel(), _stream()))
@@ -274,6 +288,12 @@ class PbcPlan:
                 self._p = None
         except Exception:
             pass
+
+
+def transpose_plan(nrow: int, ncol: int, nnz: int, nslab: int = 1) -> dict:
+    """Which form ``DeviceCSC.t()`` takes for such an operand, or (``nslab`` > 1) the batched transposition of aperm's
+    "first two axes change places" (svt_dev_transpose_plan; _hip.transpose_plan).  Launches nothing, needs no GPU."""
+    return _hip.transpose_plan(nrow, ncol, nnz, nslab)
 
 
 def aperm_route_counts(reset=False) -> dict:

@@ -264,14 +264,15 @@ def test_device_aperm(hip, perm):
 @pytest.mark.parametrize("dim,nnz,perm,dtype", [
     ((3000, 2500, 5), 750_000, (2, 1, 3), "double"),       # F = 16 rows, 10 groups of 256 columns (the last of 196)
     ((3000, 2500, 5), 750_000, (2, 1, 3), "integer"),
-    ((1234, 777, 3, 2), 400_000, (2, 1, 3, 4), "double"),  # 4-d: six slabs, ragged groups and buckets
-    ((5000, 300, 7), 900_000, (2, 1, 3), "double"),        # tall slabs
-    ((700, 40, 23), 20000, (2, 1, 3), "double"),           # too few nonzeros per column and bucket: the key sort
+    # (the routes below are asserted, on the same shapes, by tests/test_hip_transpose_cases.py)
+    ((1234, 777, 3, 2), 400_000, (2, 1, 3, 4), "double"),  # 4-d, six slabs of 54 nonzeros per row: the batched form refuses, key sort
+    ((5000, 300, 7), 900_000, (2, 1, 3), "double"),        # tall slabs of 26 per row: refused too, key sort
+    ((700, 40, 23), 20000, (2, 1, 3), "double"),           # refused, and a slab shape (dim[1] = 40, 869 per slab): the slab form
     # 3-d: c(2,3,1) = c(2,1,3) then c(1,3,2), c(3,2,1) = c(2,1,3) then c(3,1,2) through an intermediate array
     ((3000, 2500, 5), 750_000, (2, 3, 1), "double"),
     ((3000, 2500, 5), 750_000, (3, 2, 1), "double"),
     ((3000, 2500, 5), 750_000, (3, 2, 1), "integer"),
-    ((5000, 300, 7), 900_000, (2, 3, 1), "integer"),
+    ((5000, 300, 7), 900_000, (2, 3, 1), "integer"),        # the 3-d form refused with its first step: key sort
 ])
 def test_device_aperm_first_two_axes_swapped(hip, dim, nnz, perm, dtype):
     """aperm(x, c(2, 1, 3, ...)): every slab of the remaining axes is a matrix transposed on its own -- the bucketed
@@ -331,17 +332,20 @@ def test_device_aperm_slab_form(hip, dim, nnz, perm, dtype):
 
 
 @pytest.mark.parametrize("dim,nnz,perm,dtype", [
-    # general permutations of arrays with four and five axes (round 5): a leaf-preserving step, the first two axes
-    # swapped (batched bucketed transposition), a leaf-preserving step -- no sort
-    ((1500, 900, 4, 3), 1_500_000, (2, 4, 1, 3), "double"),     # q = 2: no first step
-    ((1500, 900, 4, 3), 1_500_000, (3, 1, 4, 2), "double"),     # dim[2] = 4: slab form refused? (perm[1] == 1: slab form takes it)
-    ((1500, 4, 900, 3), 1_500_000, (3, 2, 4, 1), "double"),     # q = 3: all three steps
-    ((1500, 4, 900, 3), 1_500_000, (3, 4, 2, 1), "integer"),
-    ((1200, 5, 3, 700, 2), 1_200_000, (4, 5, 1, 3, 2), "double"),   # five axes
-    ((1200, 5, 3, 700, 2), 1_200_000, (4, 1, 2, 3, 5), "double"),   # q = 4, the rest in order after the swap? (no last step)
-    # shapes the bucketed transposition refuses: the library's own radix sort of (new leaf, position) pairs
+    # general permutations of arrays with four and five axes (round 5).  The routes, asserted on the same operands by
+    # tests/test_hip_transpose_cases.py (a_general_*): the composed form's step B, the batched transposition of
+    # 1500 x 900 x 12 or 1200 x 700 x 30, is refused (fine buckets below 512 nonzeros), and slabs of 125 000 / 40 000
+    # nonzeros are no slab-form shapes, so these take the 32-bit key sort ...
+    ((1500, 900, 4, 3), 1_500_000, (2, 4, 1, 3), "double"),     # q = 2: key sort
+    ((1500, 900, 4, 3), 1_500_000, (3, 1, 4, 2), "double"),     # ... but this one: perm[1] == 1, dim[2] = 4, 555 per slab: the slab form alone
+    ((1500, 4, 900, 3), 1_500_000, (3, 2, 4, 1), "double"),     # q = 3: key sort
+    ((1500, 4, 900, 3), 1_500_000, (3, 4, 2, 1), "integer"),    # key sort
+    ((1200, 5, 3, 700, 2), 1_200_000, (4, 5, 1, 3, 2), "double"),   # five axes: key sort
+    ((1200, 5, 3, 700, 2), 1_200_000, (4, 1, 2, 3, 5), "double"),   # q = 4, perm[1] == 1, slabs too long for the slab form: key sort
+    # the composed form with the slab form as its steps A + B (450 nonzeros per slab), then whole leaves move
     ((300, 6, 5, 4), 9000, (2, 4, 3, 1), "double"),
     ((300, 6, 5, 4), 9000, (4, 3, 2, 1), "integer"),
+    # 240 000 leaves after step B, more than 2 * nnz + 1024: the general form declines, key sort
     ((40, 30, 20, 10, 3), 50_000, (5, 3, 1, 4, 2), "double"),
 ])
 def test_device_aperm_general_permutations(hip, dim, nnz, perm, dtype):
