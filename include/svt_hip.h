@@ -796,6 +796,64 @@ int svt_aperm_SVT(const svt_view *x, const int *perm, int64_t *out_col_ptr,
 int svt_transpose_2D_SVT(const svt_view *x, int64_t *out_col_ptr,
 			 int32_t *out_row_idx, void *out_val);
 
+/* x[i, j] of a 2-D operand by an N-index (C_subset_SVT_by_Nindex, src/SparseArray_subsetting.c:223-297, 759-843):
+   result cell (p, q) is x[i[p], j[q]]; indices in any order, any number of times; an entry is stored in the result
+   exactly when its source entry is stored, and its value is copied bit for bit; offsets ascend inside every result
+   column; Rtype and na_background pass through.  Not offered: L-index / M-index subsetting, subassignment, N-d operands.
+
+   Device level, two primitives over tiles of svt_dev_subset_tile() nonzeros (kernels_subset.hip), each a `_count`
+   call that writes the result's column pointers and returns its nonzero count, and a `_fill` call into arrays the
+   caller sized from it.  Subscripts are device arrays of 0-based int32.
+     column gather  out column q = column cols[q] of A.  out_col_ptr int64[ncols_sel + 1]; out_row_idx int32[*out_nnz],
+                    out_val like A's.  ncols_sel <= 2^31 - 2; *out_nnz may exceed 2^31 (repeats) and A->nnz.
+     row filter     `rows` strictly increasing: the entries of those rows, row rows[p] renumbered p.  out_col_ptr
+                    int64[A->ncol + 1].  The fill call reads the workspace as the count call left it (the same A).
+   A `_count` call launches on `stream` and synchronises it once, to return *out_nnz and read the validation flag; a
+   `_fill` call is asynchronous.  `_count` answers 0; < 0 for an index outside [0, extent) or a workspace below
+   svt_dev_subset_*_ws_bytes(); > 0 (rows) for a subscript in range that is not strictly increasing -- the caller
+   then takes t(), the column gather with the row subscript, t().  Every index is checked before it is used as an
+   address; on < 0 and > 0 nothing is written outside `ws` (out_col_ptr and *out_nnz keep their contents).
+   ncols_sel == 0 writes out_col_ptr[0] = 0 without a launch or a synchronisation; an operand without nonzeros has its
+   subscripts checked all the same.  Alignment as for svt_dev_transpose(). */
+int svt_dev_subset_tile(void);
+size_t svt_dev_subset_cols_ws_bytes(int64_t ncols_sel);
+int svt_dev_subset_cols_count(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, int64_t *out_col_ptr,
+			      int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_subset_cols_fill(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, const int64_t *out_col_ptr,
+			     int32_t *out_row_idx, void *out_val, void *stream);
+size_t svt_dev_subset_rows_ws_bytes(int64_t nrow, int64_t ncol, int64_t nnz);
+int svt_dev_subset_rows_count(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, int64_t *out_col_ptr,
+			      int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_subset_rows_fill(const svt_dev_csc *A, const int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val,
+			     const void *ws, size_t ws_bytes, void *stream);
+/* The composition x[rows, cols] (the one statement of it; svt_subset_SVT_begin and DeviceCSC.subset both call it):
+   the column gather first, then the rows by the filter, or, when the filter answers > 0, by t() -> gather -> t()
+   (svt_dev_transpose as it is).  nrows_sel / ncols_sel < 0: the whole axis (the pointer is not read); both < 0: a copy.
+   Results, intermediates and workspaces come from `alloc(bytes, ctx)` -- device memory aligned to 256 bytes, NULL on
+   failure -- and go back through `release(p, ctx)`, which may be called while work on `stream` that uses the block is
+   still queued (a stream-ordered allocator, or one that waits like hipFree).  The three result arrays (*out_col_ptr
+   int64[ncol' + 1]; *out_row_idx, *out_val of at least one element) are the caller's to release.  Synchronises
+   `stream` once per count call; the last fill / transposition is still queued on return.  < 0: a bad index. */
+typedef void *(*svt_dev_alloc_fn)(size_t bytes, void *ctx);
+typedef void (*svt_dev_free_fn)(void *p, void *ctx);
+int svt_dev_subset(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, const int32_t *cols, int64_t ncols_sel,
+		   svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz,
+		   int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream);
+/* counts[0] column gathers, [1] row filters, [2] general-row compositions (each also counts its one gather) of this
+   process, counted where the work is launched (the fill calls); reset != 0 zeroes them. */
+void svt_dev_subset_route_counts(int64_t counts[3], int reset);
+
+/* Host level.  `rows` / `cols`: 1-based as an N-index arrives, or NULL for the whole axis.  begin checks the
+   subscripts on the host (NA_INTEGER or an index outside 1..extent: < 0, before anything is uploaded), uploads x
+   (through the resident cache when it is on), runs svt_dev_subset and leaves the result on the device: *out_nnz is
+   its nonzero count, its extents are the subscripts' lengths.  end copies it into out_col_ptr int64[ncol' + 1],
+   out_row_idx int32[nnz], out_val (x's type) and releases it; all three NULL: release only.  NaArray operands are
+   taken; ndim != 2 answers > 0.  Runs on the first device of the list (not sharded). */
+typedef struct svt_subset_result svt_subset_result;
+int svt_subset_SVT_begin(const svt_view *x, const int *rows, int64_t nrows_sel, const int *cols, int64_t ncols_sel,
+			 svt_subset_result **res, int64_t *out_nnz);
+int svt_subset_SVT_end(svt_subset_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val);
+
 #ifdef __cplusplus
 }
 #endif

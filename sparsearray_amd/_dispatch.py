@@ -444,6 +444,39 @@ class CAbiDispatcher:
         ans.na_background = x.na_background
         return ans
 
+    # x[i, j] by an N-index (src/SparseArray_subsetting.c:223-297; include/svt_hip.h; HIP library only) -------------
+    def C_subset_SVT_by_Nindex(self, x: SVT_SparseArray, *index):
+        """``index``: one subscript per dimension, 1-based int32 arrays, or None for the whole axis.  Returns x[i, j] as
+        an SVT_SparseArray, its leaves rebuilt from the CSC layout the way t() does.  The library takes 2-D operands;
+        for any other it sees the first two subscripts and answers "not supported here"."""
+        if len(index) != x.ndim:
+            raise SparseArrayError("incorrect number of subscripts")
+        sub = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (index + (None,))[:2]]
+        # (a pointer tells "no subscript" from an empty one: an empty array is handed over as one unread element)
+        buf = [None if v is None else (v if v.size else np.zeros(1, np.int32)) for v in sub]
+        begin, end = self._fn("subset_SVT_begin"), self._fn("subset_SVT_end")
+        begin.restype = end.restype = ctypes.c_int
+        begin.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]
+        end.argtypes = [c_void_p] * 4
+        view = make_view(x)
+        res, nnz = c_void_p(0), ctypes.c_int64(0)
+        self._check(begin(ctypes.addressof(view), *[a for v, b in zip(sub, buf) for a in
+                                                     ((None, 0) if v is None else (b.ctypes.data, v.size))],
+                          byref(res), byref(nnz)))
+        new_dim = tuple(d if v is None else int(v.size) for d, v in zip(x.dim, sub))
+        n = int(nnz.value)
+        cp = np.zeros(new_dim[1] + 1, dtype=np.int64)
+        ri = np.zeros(max(n, 1), dtype=np.int32)
+        vv = np.zeros(max(n, 1), dtype=x.np_dtype)
+        self._check(end(res, cp.ctypes.data, ri.ctypes.data, vv.ctypes.data))
+        dn = None
+        if x.dimnames is not None:
+            dn = [names if v is None or names is None else [names[k - 1] for k in v.tolist()]
+                  for names, v in zip(x.dimnames, sub)]
+        ans = SVT_SparseArray.from_csc(new_dim, x.type, cp, ri[:n], vv[:n], dimnames=dn)
+        ans.na_background = x.na_background
+        return ans
+
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""
         return self._dgc("rowsum_dgCMatrix", x, group, ngroup, na_rm,

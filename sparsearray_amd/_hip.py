@@ -39,6 +39,9 @@ EXPORTS = [
     "svt_get_num_procs", "svt_get_max_threads", "svt_set_max_threads", "svt_dev_aperm_ws_bytes", "svt_dev_aperm_perm_ws_bytes", "svt_dev_aperm", "svt_dev_aperm_route_counts", "svt_aperm_SVT", "svt_transpose_2D_SVT", "svt_dev_transpose_ws_bytes", "svt_dev_transpose", "svt_dev_transpose_plan", "svt_dev_set_box_nnz", "svt_dev_boxed_calls", "svt_dev_colstats", "svt_dev_rowstats_ws_bytes", "svt_dev_rowsums", "svt_dev_rowsum",
     "svt_rowStatsFull_SVT", "svt_dev_rowstats_ws_bytes_op", "svt_dev_rowstats",
     "svt_dev_colstats_form", "svt_dev_rowstats_form",
+    "svt_dev_subset_tile", "svt_dev_subset_cols_ws_bytes", "svt_dev_subset_cols_count", "svt_dev_subset_cols_fill",
+    "svt_dev_subset_rows_ws_bytes", "svt_dev_subset_rows_count", "svt_dev_subset_rows_fill", "svt_dev_subset",
+    "svt_dev_subset_route_counts", "svt_subset_SVT_begin", "svt_subset_SVT_end",
 ]
 
 

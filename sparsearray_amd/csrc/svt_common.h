@@ -253,6 +253,23 @@ int launch_transpose(const int64_t *col_ptr, const int32_t *row_idx, const void 
 		     int64_t nrow, int64_t ncol, int64_t nnz, int64_t *out_ptr, int32_t *out_idx,
 		     void *out_val, void *ws, hipStream_t s);
 
+// x[i, j] by an N-index (kernels_subset.hip): the column gather and the row filter, each a count call that leaves
+// out_col_ptr and a fill call.  The count launchers are asynchronous and leave in the head of `ws` [int: 1 an index out
+// of range, 2 (rows) the subscript not strictly increasing][int64 at byte 8: the nonzeros of the result]; with the flag
+// up nothing is written outside `ws`.
+int subset_tile(void);
+size_t subset_cols_ws_bytes(int64_t ncols_sel);
+int launch_subset_cols_count(const int64_t *col_ptr, int64_t ncol, const int32_t *cols, int64_t ncols_sel,
+			     int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_subset_cols_fill(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype, int64_t ncol,
+			    int64_t nnz, const int32_t *cols, int64_t ncols_sel, const int64_t *out_col_ptr,
+			    int32_t *out_row_idx, void *out_val, hipStream_t s);
+size_t subset_rows_ws_bytes(int64_t nrow, int64_t ncol, int64_t nnz);
+int launch_subset_rows_count(const int64_t *col_ptr, const int32_t *row_idx, int64_t nrow, int64_t ncol, int64_t nnz,
+			     const int32_t *rows, int64_t nrows_sel, int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_subset_rows_fill(const int32_t *row_idx, const void *val, int Rtype, int64_t nrow, int64_t ncol, int64_t nnz,
+			    int32_t *out_row_idx, void *out_val, const void *ws, hipStream_t s);
+
 void aperm_route_counts(int64_t *out, int reset);
 size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim);
 // aperm, with the boxed driver for the permutations that move the rows past the box limit (read once per call and

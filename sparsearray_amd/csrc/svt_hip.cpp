@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <mutex>
@@ -1155,6 +1156,282 @@ extern "C" int svt_dev_transpose(const svt_dev_csc *A, int64_t *out_col_ptr, int
 	return abi_status([&] { return dev_transpose_impl(A, out_col_ptr, out_row_idx, out_val, ws, ws_bytes, stream); });
 }
 
+// ---- x[i, j] by an N-index (kernels_subset.hip; C_subset_SVT_by_Nindex, src/SparseArray_subsetting.c:223-297) ----
+enum { SUBSET_GATHER = 0, SUBSET_FILTER = 1, SUBSET_GENERAL = 2 };
+static std::atomic<int64_t> g_subset_route[3];
+
+extern "C" int svt_dev_subset_tile(void)
+{
+	return subset_tile();
+}
+
+extern "C" void svt_dev_subset_route_counts(int64_t *counts, int reset)
+{
+	for (int i = 0; i < 3; i++) {
+		if (counts) counts[i] = g_subset_route[i].load();
+		if (reset) g_subset_route[i] = 0;
+	}
+}
+
+// what a count launcher left in the head of its workspace: one copy, the call's one synchronisation
+static int subset_read_head(const void *ws, hipStream_t s, int *flag, int64_t *total)
+{
+	int64_t head[2] = { 0, 0 };
+	HIP_TRY(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	*flag = (int) (head[0] & 0xFFFFFFFFLL);
+	*total = head[1];
+	return 0;
+}
+
+extern "C" size_t svt_dev_subset_cols_ws_bytes(int64_t ncols_sel)
+{
+	return subset_cols_ws_bytes(ncols_sel);
+}
+
+static int dev_subset_cols_count_impl(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, int64_t *out_col_ptr,
+				      int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	if (ncols_sel < 0 || ncols_sel > 0x7FFFFFFELL)
+		return svt_set_error("svt_dev_subset_cols_count: between 0 and 2^31-2 columns");
+	if (ws_bytes < subset_cols_ws_bytes(ncols_sel))
+		return svt_set_error("svt_dev_subset_cols_count: workspace too small");
+	if (ncols_sel == 0) {
+		HIP_TRY(hipMemsetAsync(out_col_ptr, 0, 8, (hipStream_t) stream));
+		*out_nnz = 0;
+		return 0;
+	}
+	if (launch_subset_cols_count(A->col_ptr, A->ncol, cols, ncols_sel, out_col_ptr, ws, (hipStream_t) stream))
+		return -1;
+	int flag = 0;
+	int64_t total = 0;
+	if (subset_read_head(ws, (hipStream_t) stream, &flag, &total))
+		return -1;
+	if (flag)
+		return svt_set_error("subscript out of bounds");
+	*out_nnz = total;
+	return 0;
+}
+extern "C" int svt_dev_subset_cols_count(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, int64_t *out_col_ptr,
+					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] { return dev_subset_cols_count_impl(A, cols, ncols_sel, out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+
+static int dev_subset_cols_fill_impl(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, const int64_t *out_col_ptr,
+				     int32_t *out_row_idx, void *out_val, void *stream)
+{
+	g_subset_route[SUBSET_GATHER]++;
+	if (ncols_sel <= 0 || A->nnz == 0)
+		return 0;
+	return launch_subset_cols_fill(A->col_ptr, A->row_idx, A->val, A->Rtype, A->ncol, A->nnz, cols, ncols_sel, out_col_ptr,
+				       out_row_idx, out_val, (hipStream_t) stream);
+}
+extern "C" int svt_dev_subset_cols_fill(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, const int64_t *out_col_ptr,
+					int32_t *out_row_idx, void *out_val, void *stream)
+{
+	return abi_status([&] { return dev_subset_cols_fill_impl(A, cols, ncols_sel, out_col_ptr, out_row_idx, out_val, stream); });
+}
+
+extern "C" size_t svt_dev_subset_rows_ws_bytes(int64_t nrow, int64_t ncol, int64_t nnz)
+{
+	return subset_rows_ws_bytes(nrow, ncol, nnz);
+}
+
+static int dev_subset_rows_count_impl(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, int64_t *out_col_ptr,
+				      int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	if (nrows_sel < 0)
+		return svt_set_error("svt_dev_subset_rows_count: 'nrows_sel' must be >= 0");
+	if (ws_bytes < subset_rows_ws_bytes(A->nrow, A->ncol, A->nnz))
+		return svt_set_error("svt_dev_subset_rows_count: workspace too small");
+	if (launch_subset_rows_count(A->col_ptr, A->row_idx, A->nrow, A->ncol, A->nnz, rows, nrows_sel, out_col_ptr, ws,
+				     (hipStream_t) stream))
+		return -1;
+	int flag = 0;
+	int64_t total = 0;
+	if (subset_read_head(ws, (hipStream_t) stream, &flag, &total))
+		return -1;
+	if (flag & 1)
+		return svt_set_error("subscript out of bounds");
+	if (flag)
+		return svt_set_unsupported("svt_dev_subset_rows_count: the subscript is not strictly increasing");
+	*out_nnz = total;
+	return 0;
+}
+extern "C" int svt_dev_subset_rows_count(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, int64_t *out_col_ptr,
+					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] { return dev_subset_rows_count_impl(A, rows, nrows_sel, out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+
+static int dev_subset_rows_fill_impl(const svt_dev_csc *A, int32_t *out_row_idx, void *out_val, const void *ws,
+				     size_t ws_bytes, void *stream)
+{
+	if (ws_bytes < subset_rows_ws_bytes(A->nrow, A->ncol, A->nnz))
+		return svt_set_error("svt_dev_subset_rows_fill: workspace too small");
+	g_subset_route[SUBSET_FILTER]++;
+	return launch_subset_rows_fill(A->row_idx, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, out_row_idx, out_val, ws,
+				       (hipStream_t) stream);
+}
+extern "C" int svt_dev_subset_rows_fill(const svt_dev_csc *A, const int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val,
+					const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile prefixes in `ws` place the entries)
+	return abi_status([&] { return dev_subset_rows_fill_impl(A, out_row_idx, out_val, ws, ws_bytes, stream); });
+}
+
+// The composition x[rows, cols], stated once: columns first (cheap, and it shrinks the operand), then the rows by the
+// filter when the subscript is strictly increasing, else t() -> column gather with the row subscript -> t().  Every
+// array -- results, intermediates, workspaces -- comes from the caller's allocator.
+struct SubsetMem {
+	svt_dev_alloc_fn alloc;
+	svt_dev_free_fn release;
+	void *ctx;
+	void *get(size_t n)
+	{
+		void *p = alloc(n > 0 ? n : 16, ctx);
+		if (p == NULL) svt_set_error("svt_dev_subset: device allocation failed (%zu bytes)", n);
+		return p;
+	}
+	void put(void *p) { if (p) release(p, ctx); }
+};
+struct SubsetCsc {               // a CSC of three such arrays, given back with this object unless taken
+	SubsetMem &mem;
+	svt_dev_csc c;
+	explicit SubsetCsc(SubsetMem &m) : mem(m) { memset(&c, 0, sizeof(c)); }
+	SubsetCsc(const SubsetCsc &) = delete;
+	~SubsetCsc() { drop(); }
+	void drop()
+	{
+		mem.put(c.col_ptr); mem.put(c.row_idx); mem.put(c.val);
+		c.col_ptr = NULL; c.row_idx = NULL; c.val = NULL;
+	}
+	int shape(const svt_dev_csc *like, int64_t nrow, int64_t ncol)
+	{
+		drop();
+		c.Rtype = like->Rtype; c.na_background = like->na_background;
+		c.nrow = nrow; c.ncol = ncol; c.nnz = 0;
+		c.col_ptr = (int64_t *) mem.get(((size_t) ncol + 1) * 8);
+		return c.col_ptr ? 0 : -1;
+	}
+	int entries(int64_t nnz)
+	{
+		const size_t n = nnz > 0 ? (size_t) nnz : 1;
+		c.nnz = nnz;
+		c.row_idx = (int32_t *) mem.get(n * 4);
+		c.val = mem.get(n * elt_size(c.Rtype));
+		return c.row_idx && c.val ? 0 : -1;
+	}
+};
+struct SubsetWs {
+	SubsetMem &mem;
+	void *p = NULL;
+	size_t n = 0;
+	explicit SubsetWs(SubsetMem &m) : mem(m) {}
+	SubsetWs(const SubsetWs &) = delete;
+	~SubsetWs() { mem.put(p); }
+	int get(size_t bytes) { p = mem.get(bytes); n = bytes; return p ? 0 : -1; }
+};
+
+static int subset_gather_into(SubsetMem &mem, const svt_dev_csc *A, const int32_t *cols, int64_t n, SubsetCsc &out, void *s)
+{
+	SubsetWs ws(mem);
+	int64_t nnz = 0;
+	if (out.shape(A, A->nrow, n) || ws.get(subset_cols_ws_bytes(n)) ||
+	    dev_subset_cols_count_impl(A, cols, n, out.c.col_ptr, &nnz, ws.p, ws.n, s) || out.entries(nnz))
+		return -1;
+	return dev_subset_cols_fill_impl(A, cols, n, out.c.col_ptr, out.c.row_idx, out.c.val, s);
+}
+
+static int subset_transpose_into(SubsetMem &mem, const svt_dev_csc *A, SubsetCsc &out, void *s)
+{
+	SubsetWs ws(mem);
+	if (out.shape(A, A->ncol, A->nrow) || out.entries(A->nnz) ||
+	    ws.get(transpose_ws_bytes_box(A->nrow, A->nnz, box_nnz_get())))
+		return -1;
+	return dev_transpose_impl(A, out.c.col_ptr, out.c.row_idx, out.c.val, ws.p, ws.n, s);
+}
+
+// 0 done, -1 error, 1 the subscript is in range but not strictly increasing (nothing of `out` is of use)
+static int subset_filter_into(SubsetMem &mem, const svt_dev_csc *A, const int32_t *rows, int64_t n, SubsetCsc &out, void *s)
+{
+	SubsetWs ws(mem);
+	int64_t nnz = 0;
+	if (out.shape(A, n, A->ncol) || ws.get(subset_rows_ws_bytes(A->nrow, A->ncol, A->nnz)))
+		return -1;
+	if (dev_subset_rows_count_impl(A, rows, n, out.c.col_ptr, &nnz, ws.p, ws.n, s)) {
+		if (!g_unsupported) return -1;
+		svt_clear_unsupported();
+		return 1;
+	}
+	if (out.entries(nnz))
+		return -1;
+	return dev_subset_rows_fill_impl(A, out.c.row_idx, out.c.val, ws.p, ws.n, s);
+}
+
+// rows in any order, with repeats (all in range: the filter's count call has looked): a column gather on t(A)
+static int subset_rows_general_into(SubsetMem &mem, const svt_dev_csc *A, const int32_t *rows, int64_t n, SubsetCsc &out, void *s)
+{
+	g_subset_route[SUBSET_GENERAL]++;
+	if (A->nnz == 0) {
+		if (out.shape(A, n, A->ncol) || out.entries(0))
+			return -1;
+		HIP_TRY(hipMemsetAsync(out.c.col_ptr, 0, ((size_t) A->ncol + 1) * 8, (hipStream_t) s));
+		return 0;
+	}
+	SubsetCsc T(mem), G(mem);
+	if (subset_transpose_into(mem, A, T, s) || subset_gather_into(mem, &T.c, rows, n, G, s))
+		return -1;
+	T.drop();
+	return subset_transpose_into(mem, &G.c, out, s);
+}
+
+static int dev_subset_impl(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, const int32_t *cols, int64_t ncols_sel,
+			   svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz,
+			   int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+{
+	if (alloc == NULL || release == NULL)
+		return svt_set_error("svt_dev_subset: an allocator is needed");
+	SubsetMem mem = { alloc, release, ctx };
+	SubsetCsc B(mem), R(mem);
+	const svt_dev_csc *cur = A;
+	if (ncols_sel >= 0) {
+		if (subset_gather_into(mem, A, cols, ncols_sel, B, stream))
+			return -1;
+		cur = &B.c;
+	}
+	if (nrows_sel >= 0) {
+		const int rc = subset_filter_into(mem, cur, rows, nrows_sel, R, stream);
+		if (rc < 0 || (rc > 0 && subset_rows_general_into(mem, cur, rows, nrows_sel, R, stream)))
+			return -1;
+	} else if (cur == A) {                              // x[, ]: a copy
+		hipStream_t s = (hipStream_t) stream;
+		if (R.shape(A, A->nrow, A->ncol) || R.entries(A->nnz))
+			return -1;
+		HIP_TRY(hipMemcpyAsync(R.c.col_ptr, A->col_ptr, ((size_t) A->ncol + 1) * 8, hipMemcpyDeviceToDevice, s));
+		if (A->nnz > 0) {
+			HIP_TRY(hipMemcpyAsync(R.c.row_idx, A->row_idx, (size_t) A->nnz * 4, hipMemcpyDeviceToDevice, s));
+			HIP_TRY(hipMemcpyAsync(R.c.val, A->val, (size_t) A->nnz * elt_size(A->Rtype), hipMemcpyDeviceToDevice, s));
+		}
+	} else {
+		std::swap(R.c, B.c);
+	}
+	*out_nnz = R.c.nnz;
+	*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
+	R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
+	return 0;
+}
+extern "C" int svt_dev_subset(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, const int32_t *cols,
+			      int64_t ncols_sel, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz,
+			      int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+{
+	return abi_status([&] {
+		return dev_subset_impl(A, rows, nrows_sel, cols, ncols_sel, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx,
+				       out_val, stream);
+	});
+}
+
 // A %*% B, both sparse (kernels_spmm.hip): out[r + k * ldo], r < A->nrow, k < B->ncol.
 extern "C" size_t svt_dev_matmul_csc_csc_ws_bytes(const svt_dev_csc *A)
 {
@@ -2279,6 +2556,103 @@ extern "C" int svt_transpose_2D_SVT(const svt_view *x, int64_t *out_col_ptr,
 				    int32_t *out_row_idx, void *out_val)
 {
 	return abi_status([&] { return transpose_2D_SVT_impl(x, out_col_ptr, out_row_idx, out_val); });
+}
+
+// x[i, j] by an N-index (C_subset_SVT_by_Nindex, src/SparseArray_subsetting.c:223-297, 759-843; 2-D operands): the
+// subscripts are checked here, on the host, before anything is uploaded; the composition is dev_subset_impl().
+struct svt_subset_result {
+	svt_dev_csc *h;              // owns its buffers
+};
+
+// 1-based subscript of an axis of `extent` -> 0-based, or the error of the reference's checks
+static int subset_index0(const int *idx, int64_t n, int extent, std::vector<int32_t> &out)
+{
+	if (n < 0 || (n > 0 && idx == NULL))
+		return svt_set_error("invalid subscript");
+	out.resize((size_t) n);
+	for (int64_t k = 0; k < n; k++) {
+		const int v = idx[k];
+		if (v == NA_INT)
+			return svt_set_error("subscript contains NAs");
+		if (v < 1 || v > extent)
+			return svt_set_error("subscript out of bounds");
+		out[(size_t) k] = v - 1;
+	}
+	return 0;
+}
+
+static void *subset_hip_alloc(size_t n, void *)
+{
+	void *p = NULL;
+	return hipMalloc(&p, n) == hipSuccess ? p : NULL;
+}
+static void subset_hip_free(void *p, void *) { (void) hipFree(p); }
+
+static int subset_SVT_begin_impl(const svt_view *x, const int *rows, int64_t nrows_sel, const int *cols, int64_t ncols_sel,
+				 svt_subset_result **res, int64_t *out_nnz)
+{
+	if (res == NULL || out_nnz == NULL)
+		return svt_set_error("svt_subset_SVT_begin: 'res' and 'out_nnz' are needed");
+	*res = NULL;
+	if (ensure_init() || check_view(x))
+		return -1;
+	if (x->ndim != 2)
+		return svt_set_unsupported("N-index subsetting on the device takes 2-D operands only");
+	std::vector<int32_t> r0, c0;
+	if ((rows != NULL && subset_index0(rows, nrows_sel, x->dim[0], r0)) ||
+	    (cols != NULL && subset_index0(cols, ncols_sel, x->dim[1], c0)))
+		return -1;
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	DevBuf dr, dc;
+	if ((rows != NULL && dr.upload(r0.data(), r0.size() * 4)) || (cols != NULL && dc.upload(c0.data(), c0.size() * 4)))
+		return -1;
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->Rtype = A.h->Rtype; h->owned = 1; h->na_background = A.h->na_background;
+	h->nrow = rows != NULL ? nrows_sel : A.h->nrow;
+	h->ncol = cols != NULL ? ncols_sel : A.h->ncol;
+	if (dev_subset_impl(A.h, dr.as<int32_t>(), rows != NULL ? nrows_sel : -1, dc.as<int32_t>(), cols != NULL ? ncols_sel : -1,
+			    subset_hip_alloc, subset_hip_free, NULL, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, NULL) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("device error while subsetting");
+		svt_release(h);
+		return -1;
+	}
+	svt_subset_result *r = (svt_subset_result *) calloc(1, sizeof(*r));
+	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
+	r->h = h;
+	*res = r;
+	*out_nnz = h->nnz;
+	return 0;
+}
+extern "C" int svt_subset_SVT_begin(const svt_view *x, const int *rows, int64_t nrows_sel, const int *cols, int64_t ncols_sel,
+				    svt_subset_result **res, int64_t *out_nnz)
+{
+	return abi_status([&] { return subset_SVT_begin_impl(x, rows, nrows_sel, cols, ncols_sel, res, out_nnz); });
+}
+
+static int subset_SVT_end_impl(svt_subset_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
+{
+	if (res == NULL) return 0;
+	const svt_dev_csc *h = res->h;
+	int rc = 0;
+	if (out_col_ptr != NULL || out_row_idx != NULL || out_val != NULL) {
+		if (out_col_ptr == NULL || (h->nnz > 0 && (out_row_idx == NULL || out_val == NULL)))
+			rc = svt_set_error("svt_subset_SVT_end: all three outputs, or none");
+		else if (hipMemcpy(out_col_ptr, h->col_ptr, ((size_t) h->ncol + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess)
+			rc = svt_set_error("svt_subset_SVT_end: D2H copy failed");
+		else if (h->nnz > 0 && (staged_download(out_row_idx, h->row_idx, (size_t) h->nnz * 4) ||
+					staged_download(out_val, h->val, (size_t) h->nnz * elt_size(h->Rtype))))
+			rc = -1;
+	}
+	svt_release(res->h);
+	free(res);
+	return rc;
+}
+extern "C" int svt_subset_SVT_end(svt_subset_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
+{
+	return abi_status([&] { return subset_SVT_end_impl(res, out_col_ptr, out_row_idx, out_val); });
 }
 
 // x %*% y over the device list: shard s takes the rows [r0, r1) of x, transposes them and multiplies them with the

@@ -17,6 +17,9 @@ from .api import OPCODES, SparseArrayError, SparseArrayUnsupported
 from .svt import INTSXP, LGLSXP, REALSXP
 
 _protos_done = False
+# svt_dev_alloc_fn / svt_dev_free_fn (include/svt_hip.h)
+_ALLOC_FN = ctypes.CFUNCTYPE(c_void_p, c_size_t, c_void_p)
+_FREE_FN = ctypes.CFUNCTYPE(None, c_void_p, c_void_p)
 
 
 def _lib():
@@ -110,6 +113,21 @@ def _lib():
         lib.svt_dev_aperm_perm_ws_bytes.argtypes = [c_int64, c_int, c_void_p, c_void_p]
         lib.svt_dev_aperm.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]
+        lib.svt_dev_subset_tile.restype = c_int
+        lib.svt_dev_subset_cols_ws_bytes.restype = c_size_t
+        lib.svt_dev_subset_cols_ws_bytes.argtypes = [c_int64]
+        lib.svt_dev_subset_cols_count.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                  c_void_p]
+        lib.svt_dev_subset_cols_fill.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.svt_dev_subset_rows_ws_bytes.restype = c_size_t
+        lib.svt_dev_subset_rows_ws_bytes.argtypes = [c_int64, c_int64, c_int64]
+        lib.svt_dev_subset_rows_count.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                  c_void_p]
+        lib.svt_dev_subset_rows_fill.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.svt_dev_subset.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, _ALLOC_FN, _FREE_FN, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.svt_dev_subset_route_counts.argtypes = [c_void_p, c_int]
+        lib.svt_dev_subset_route_counts.restype = None
         _protos_done = True
     return lib
 
@@ -197,6 +215,40 @@ class DeviceCSC:
                                     ws.numel(), _stream()))
         return DeviceCSC(new_dim[0], cp, ri, vv, logical=self.Rtype == LGLSXP), new_dim
 
+    def subset(self, rows=None, cols=None) -> "DeviceCSC":
+        """x[rows, cols] on the device (2-d operands; include/svt_hip.h, svt_dev_subset): ``rows`` / ``cols`` are
+        0-based int32 tensors or array-likes, in any order and with repeats, or None for the whole axis.  Returns a new
+        DeviceCSC of len(rows) x len(cols).  An index out of range raises SparseArrayError; nothing is read through
+        it.  Every array the composition needs is a torch allocation on the current stream."""
+        dev = self.val.device
+        sub = [None if v is None else _subscript(v, dev) for v in (rows, cols)]
+        live = {}
+
+        def alloc(nbytes, _ctx):
+            try:
+                t = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+            except RuntimeError:
+                return None
+            live[t.data_ptr()] = t
+            return t.data_ptr()
+
+        def release(p, _ctx):
+            live.pop(p, None)
+
+        nnz = c_int64(0)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(_lib().svt_dev_subset(self.handle, *[a for v in sub for a in ((None, -1) if v is None else
+                                                                               (v.data_ptr(), v.numel()))],
+                                     _ALLOC_FN(alloc), _FREE_FN(release), None, ctypes.byref(nnz),
+                                     *[ctypes.byref(o) for o in out], _stream()))
+        n = int(nnz.value)
+        nrow = self.nrow if sub[0] is None else sub[0].numel()
+        ncol = self.ncol if sub[1] is None else sub[1].numel()
+        cp = live[out[0].value].view(torch.int64)[:ncol + 1]
+        ri = live[out[1].value].view(torch.int32)[:n]
+        vv = live[out[2].value].view(self.val.dtype)[:n]
+        return DeviceCSC(nrow, cp, ri, vv, logical=self.Rtype == LGLSXP)
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
@@ -204,6 +256,67 @@ class DeviceCSC:
                 self._h = None
         except Exception:
             pass
+
+
+def _subscript(v, device) -> torch.Tensor:
+    """A subscript as a contiguous int32 device tensor (the values are checked on the device)."""
+    if not isinstance(v, torch.Tensor):
+        a = np.asarray(v)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise SparseArrayError("subscripts must be integers")
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise SparseArrayError("subscript out of bounds")
+        v = torch.as_tensor(a.astype(np.int32).reshape(-1), device=device)
+    assert v.dtype == torch.int32 and v.is_cuda
+    return v.contiguous().reshape(-1)
+
+
+def subset_tile() -> int:
+    """Nonzeros per workgroup tile of the column gather and the row filter (svt_dev_subset_tile).  Needs no GPU."""
+    lib = _hip.load_library()
+    lib.svt_dev_subset_tile.restype = c_int
+    return int(lib.svt_dev_subset_tile())
+
+
+def subset_route_counts(reset=False) -> dict:
+    """Column gathers, row filters and general-row compositions of this process so far (svt_dev_subset_route_counts)."""
+    buf = (c_int64 * 3)()
+    _lib().svt_dev_subset_route_counts(buf, int(bool(reset)))
+    return dict(zip(("column_gather", "row_filter", "general_rows"), (int(x) for x in buf)))
+
+
+def _subset_two_calls(A: DeviceCSC, idx, ws, rows: bool) -> DeviceCSC:
+    lib, dev = _lib(), A.val.device
+    idx = _subscript(idx, dev)
+    n = idx.numel()
+    if ws is None:
+        nb = lib.svt_dev_subset_rows_ws_bytes(A.nrow, A.ncol, A.nnz) if rows else lib.svt_dev_subset_cols_ws_bytes(n)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda
+    cp = torch.empty((A.ncol if rows else n) + 1, dtype=torch.int64, device=dev)
+    nnz = c_int64(0)
+    count = lib.svt_dev_subset_rows_count if rows else lib.svt_dev_subset_cols_count
+    _check(count(A.handle, idx.data_ptr(), n, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(), _stream()))
+    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    vv = torch.empty(nnz.value, dtype=A.val.dtype, device=dev)
+    if rows:
+        _check(lib.svt_dev_subset_rows_fill(A.handle, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), _stream()))
+    else:
+        _check(lib.svt_dev_subset_cols_fill(A.handle, idx.data_ptr(), n, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(),
+                                            _stream()))
+    return DeviceCSC(n if rows else A.nrow, cp, ri, vv, logical=A.Rtype == LGLSXP)
+
+
+def subset_cols(A: DeviceCSC, cols, ws=None) -> DeviceCSC:
+    """The column gather alone (svt_dev_subset_cols_count, then _fill): x[, cols], ``cols`` 0-based, any order, repeats."""
+    return _subset_two_calls(A, cols, ws, rows=False)
+
+
+def subset_rows(A: DeviceCSC, rows, ws=None) -> DeviceCSC:
+    """The row filter alone (svt_dev_subset_rows_count, then _fill): x[rows, ] for a strictly increasing 0-based
+    ``rows``; any other subscript in range raises SparseArrayUnsupported (take ``A.subset(rows=...)``)."""
+    return _subset_two_calls(A, rows, ws, rows=True)
 
 
 class CrossprodPlan:

@@ -1,0 +1,205 @@
+"""Operands and subscripts for x[i, j] by an N-index (Session.subset; src/SparseArray_subsetting.c:223-297 restricted to
+2-D operands), shared by tests/test_subset_cpu.py (the host statement of sparsearray_amd/api.py on the oracle session)
+and tests/test_hip_subset.py (the device route).
+
+The rule is numpy's on the dense matrix, ``dense[np.ix_(i0, j0)]``, at tolerance 0: values equal AS BITS (a float
+comparison cannot tell NaN payloads, NA_real_ or -0.0 apart), and the same for the mask of STORED entries -- nothing is
+created, nothing is dropped, so a stored 0.0 stays stored and an implicit zero stays implicit.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+from sparsearray_amd import NA_integer, NA_real, SVT_SparseArray
+
+NP_DTYPE = {"double": np.float64, "integer": np.int32, "logical": np.int32}
+# NA_real_, a NaN of another payload, a negative NaN, +-Inf, -0.0, a stored 0.0, an ordinary value
+SPECIALS_F64 = np.array([0x7FF00000000007A2, 0x7FF8000000000001, 0xFFF80000DEADBEEF, 0x7FF0000000000000,
+                         0xFFF0000000000000, 0x8000000000000000, 0x0000000000000000, 0x3FF8000000000000],
+                        dtype=np.uint64).view(np.float64)
+SPECIALS_I32 = np.array([NA_integer, 0, -1, 2 ** 31 - 1, 7], dtype=np.int32)
+SPECIALS_LGL = np.array([1, NA_integer, 0, 1, 1], dtype=np.int32)
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype == np.float64 else a.view(np.uint32)
+
+
+def build(dim, type, mask, palette="tracer", na_background=False, lacunar_cols=()):
+    """An SVT_SparseArray with exactly the entries of the boolean ``mask`` stored.  tracer: the value encodes the
+    position (never 0, never NA); specials: the table of the type cycled over the stored entries; ``lacunar_cols``:
+    leaves stored without values (all ones)."""
+    nrow, ncol = dim
+    mask = np.asarray(mask, dtype=bool).reshape(dim)
+    table = {"double": SPECIALS_F64, "integer": SPECIALS_I32, "logical": SPECIALS_LGL}[type]
+    leaves, k = [], 0
+    for c in range(ncol):
+        offs = np.flatnonzero(mask[:, c]).astype(np.int32)
+        if offs.size == 0:
+            leaves.append(None)
+            continue
+        if c in lacunar_cols:
+            leaves.append((offs, None))
+            continue
+        if palette == "tracer":
+            vals = (offs.astype(np.int64) + c * nrow + 1).astype(NP_DTYPE[type])
+            if type == "logical":
+                vals[:] = 1
+        else:
+            vals = table[(k + np.arange(offs.size)) % len(table)]
+            k += offs.size
+        leaves.append((offs, np.ascontiguousarray(vals, dtype=NP_DTYPE[type])))
+    return SVT_SparseArray(dim, type, leaves, na_background=na_background)
+
+
+def dense_and_stored(x):
+    """(dense values with the background filled in, mask of the stored entries) of a 2-D object"""
+    nrow, ncol = x.dim
+    dense = np.zeros((nrow, ncol), dtype=x.np_dtype, order="F")
+    if x.na_background:
+        dense[...] = NA_real if x.type == "double" else NA_integer
+    stored = np.zeros((nrow, ncol), dtype=bool, order="F")
+    for c, lf in enumerate(x.leaves):
+        if lf is None:
+            continue
+        dense[lf[0], c] = 1 if lf[1] is None else lf[1]
+        stored[lf[0], c] = True
+    return dense, stored
+
+
+def _rand_mask(dim, density, seed):
+    return np.random.default_rng(seed).random(dim) < density
+
+
+_OPERANDS = {
+    "double": lambda: build((37, 23), "double", _rand_mask((37, 23), 0.2, 1)),
+    "double_specials": lambda: build((37, 23), "double", _rand_mask((37, 23), 0.3, 2), "specials"),
+    "integer": lambda: build((29, 31), "integer", _rand_mask((29, 31), 0.25, 3)),
+    "integer_specials": lambda: build((29, 31), "integer", _rand_mask((29, 31), 0.25, 4), "specials"),
+    "logical": lambda: build((19, 17), "logical", _rand_mask((19, 17), 0.3, 5), "specials", lacunar_cols=(2, 3, 11)),
+    "na_double": lambda: build((23, 19), "double", _rand_mask((23, 19), 0.3, 6), "specials", na_background=True),
+    "na_integer": lambda: build((23, 19), "integer", _rand_mask((23, 19), 0.3, 7), na_background=True),
+    "zero_rows": lambda: build((0, 5), "double", np.zeros((0, 5), bool)),
+    "zero_cols": lambda: build((7, 0), "double", np.zeros((7, 0), bool)),
+    "all_zero": lambda: build((11, 13), "double", np.zeros((11, 13), bool)),
+    # a few tiles of the device kernels' 4096 nonzeros, one column much longer than the others, empty columns
+    "wide": lambda: build((600, 160), "double",
+                          _rand_mask((600, 160), 0.1, 8) & (np.arange(160) % 7 != 3)[None, :] | (np.arange(160) == 80)[None, :]),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def operand(name):
+    x = _OPERANDS[name]()
+    dense, stored = dense_and_stored(x)
+    dense.setflags(write=False)
+    stored.setflags(write=False)
+    return x, dense, stored
+
+
+def _perm(n, seed):
+    return (np.random.default_rng(seed).permutation(n) + 1).tolist()
+
+
+def _incr(n, keep, seed):
+    return (np.flatnonzero(np.random.default_rng(seed).random(n) < keep) + 1).tolist()
+
+
+# (name, operand, i, j): 1-based subscripts, None = the whole axis
+CASES = [
+    ("neither", "double", None, None),
+    ("i_increasing", "double", _incr(37, 0.5, 10), None),
+    ("j_increasing", "double", None, _incr(23, 0.5, 11)),
+    ("both_increasing", "double", _incr(37, 0.6, 12), _incr(23, 0.4, 13)),
+    ("i_range", "double", list(range(5, 30)), None),
+    ("i_reversed", "double", list(range(37, 0, -1)), None),
+    ("j_reversed", "double", None, list(range(23, 0, -1))),
+    ("both_permuted", "double", _perm(37, 14), _perm(23, 15)),
+    ("i_repeats", "double", [3, 3, 3, 1, 37, 1, 20, 20], None),
+    ("j_repeats", "double", None, [23, 1, 1, 1, 7, 23, 7]),
+    ("both_repeats_longer_than_the_axes", "double", (_perm(37, 16) * 2)[:60], (_perm(23, 17) * 3)[:50]),
+    ("i_sorted_with_a_repeat", "double", [1, 2, 2, 3, 10], None),
+    ("i_single", "double", [17], [4]),
+    ("i_empty", "double", [], None),
+    ("j_empty", "double", None, []),
+    ("both_empty", "double", [], []),
+    ("i_empty_j_repeats", "double", [], [2, 2, 5]),
+    ("specials_both", "double_specials", _perm(37, 18), (_perm(23, 19) * 2)[:30]),
+    ("specials_filter", "double_specials", _incr(37, 0.5, 20), None),
+    ("integer_both", "integer", _perm(29, 21), _incr(31, 0.5, 22)),
+    ("integer_specials_repeats", "integer_specials", [5, 5, 1, 29, 12], [31, 31, 2]),
+    ("logical_lacunar", "logical", _perm(19, 23), [3, 3, 4, 12, 1, 17]),
+    ("logical_filter", "logical", _incr(19, 0.6, 24), None),
+    ("na_double_both", "na_double", _perm(23, 25), (_perm(19, 26) * 2)[:25]),
+    ("na_double_filter", "na_double", _incr(23, 0.5, 27), None),
+    ("na_integer_repeats", "na_integer", [23, 1, 1, 8], None),
+    ("zero_rows_cols", "zero_rows", None, [5, 1, 1]),
+    ("zero_rows_empty_i", "zero_rows", [], [2]),
+    ("zero_cols_rows", "zero_cols", [7, 1, 1, 3], None),
+    ("zero_cols_empty_j", "zero_cols", [2, 3], []),
+    ("all_zero_both", "all_zero", [11, 1, 5, 5], [13, 2]),
+    ("all_zero_filter", "all_zero", [2, 4, 9], None),
+    ("wide_filter", "wide", _incr(600, 0.5, 28), None),
+    ("wide_permuted", "wide", _perm(600, 29), None),
+    ("wide_cols_repeats_then_rows", "wide", _incr(600, 0.7, 30), (_perm(160, 31) * 3)[:400]),
+    ("wide_both_permuted", "wide", (_perm(600, 32) * 2)[:700], _perm(160, 33)),
+]
+NAMES = [c[0] for c in CASES]
+BY_NAME = {c[0]: c for c in CASES}
+assert len(BY_NAME) == len(CASES)
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name):
+    """(dense, stored) of x[i, j] by numpy on the dense matrix and on the stored mask"""
+    _, op, i, j = BY_NAME[name]
+    x, dense, stored = operand(op)
+    i0 = np.arange(x.dim[0]) if i is None else np.asarray(i, dtype=np.int64) - 1
+    j0 = np.arange(x.dim[1]) if j is None else np.asarray(j, dtype=np.int64) - 1
+    want, want_stored = dense[np.ix_(i0, j0)], stored[np.ix_(i0, j0)]
+    want.setflags(write=False)
+    want_stored.setflags(write=False)
+    return want, want_stored
+
+
+def check_invariants(res, x):
+    """offsets strictly ascending and in range, no stored empty leaf, values of the type, type and background kept"""
+    assert isinstance(res, SVT_SparseArray)
+    assert res.type == x.type and res.na_background == x.na_background
+    assert len(res.leaves) == res.dim[1]
+    for lf in res.leaves:
+        if lf is None:
+            continue
+        offs = np.asarray(lf[0])
+        assert offs.size > 0 and offs.dtype == np.int32
+        assert offs[0] >= 0 and offs[-1] < res.dim[0] and np.all(np.diff(offs) > 0)
+        assert lf[1] is None or (len(lf[1]) == offs.size and np.asarray(lf[1]).dtype == x.np_dtype)
+    assert res.svt_is_null == all(lf is None for lf in res.leaves)
+
+
+def check(res, name, what=""):
+    _, op, i, j = BY_NAME[name]
+    x, _, _ = operand(op)
+    want, want_stored = expected(name)
+    what = f"{what}{name}"
+    check_invariants(res, x)
+    assert res.dim == want.shape, f"{what}: dim {res.dim}, want {want.shape}"
+    got, got_stored = dense_and_stored(res)
+    assert np.array_equal(got_stored, want_stored), f"{what}: the stored entries differ"
+    assert got.dtype == want.dtype and np.array_equal(bits(got), bits(want)), f"{what}: values differ as bits"
+
+
+def same_object(a, b, what=""):
+    """two results equal leaf by leaf: offsets, and values as bits (a lacunar leaf equals its expanded ones)"""
+    assert a.dim == b.dim and a.type == b.type and a.na_background == b.na_background, what
+    for c, (la, lb) in enumerate(zip(a.leaves, b.leaves)):
+        assert (la is None) == (lb is None), f"{what}: leaf {c}"
+        if la is None:
+            continue
+        assert np.array_equal(la[0], lb[0]), f"{what}: offsets of leaf {c}"
+        va = np.ones(len(la[0]), a.np_dtype) if la[1] is None else np.asarray(la[1])
+        vb = np.ones(len(lb[0]), b.np_dtype) if lb[1] is None else np.asarray(lb[1])
+        assert np.array_equal(bits(va), bits(vb)), f"{what}: values of leaf {c}"
