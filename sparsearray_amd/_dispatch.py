@@ -11,13 +11,13 @@ this package loads or names that checker.
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_void_p
+from ctypes import byref, c_int, c_void_p
 
 import numpy as np
 
+from ._abi import PROTOTYPES
 from .api import OPCODES, TIES_METHODS, SparseArrayError, SparseArrayUnsupported, naked_result
-from .svt import (INTSXP, LGLSXP, REALSXP, SVT_SparseArray, make_view,
-                  r_type_of, svt_view)
+from .svt import INTSXP, LGLSXP, REALSXP, SVT_SparseArray, make_view, r_type_of
 
 _RT = {"logical": LGLSXP, "integer": INTSXP, "double": REALSXP}
 
@@ -41,53 +41,13 @@ class CAbiDispatcher:
         return getattr(self.lib, self.prefix + name)
 
     def _declare(self):
-        V = POINTER(svt_view)
-        I = c_int
-        P = c_void_p
-        protos = {
-            "last_error": (c_char_p, []),
-            "crossprod2_SVT_mat": (I, [V, P, I, I, I, I, P]),
-            "crossprod2_mat_SVT": (I, [P, I, I, I, V, I, P]),
-            "crossprod2_SVT_SVT": (I, [V, V, P]),
-            "crossprod1_SVT": (I, [V, P]),
-            "summarize_SVT": (I, [V, I, I, c_double, P, P, POINTER(I), POINTER(I)]),
-            "colStats_out_Rtype": (I, [I, I]),
-            "colStats_SVT": (I, [V, I, I, c_double, I, P, POINTER(I)]),
-            "rowStats_SVT": (I, [V, I, I, P, I, P, POINTER(I)]),
-            "rowsum_SVT": (I, [V, P, I, I, P, POINTER(I)]),
-            "colsum_SVT": (I, [V, P, I, I, P, POINTER(I)]),
-            "rowsum_dgCMatrix": (I, [I, I, P, P, P, P, I, I, P]),
-            "colsum_dgCMatrix": (I, [I, I, P, P, P, P, I, I, P]),
-        }
-        for name in ("colMins_dgCMatrix", "colMaxs_dgCMatrix", "colRanges_dgCMatrix",
-                     "colVars_dgCMatrix"):
-            protos[name] = (I, [I, I, P, P, I, P])
-        if hasattr(self.lib, self.prefix + "colMedians_SVT"):      # HIP library (the oracle's is Python)
-            protos["colMedians_SVT"] = (I, [V, I, P])
-            protos["rowMedians_SVT"] = (I, [V, I, P])
-        if hasattr(self.lib, self.prefix + "colQuantiles_SVT"):    # HIP library (api.py states the rule in numpy)
-            protos["colQuantiles_SVT"] = (I, [V, P, I, I, P])
-            protos["rowQuantiles_SVT"] = (I, [V, P, I, I, P])
-        if hasattr(self.lib, self.prefix + "colMads_SVT"):         # HIP library (api.py states the rule in numpy)
-            protos["colMads_SVT"] = (I, [V, P, c_double, I, P])
-            protos["rowMads_SVT"] = (I, [V, P, c_double, I, P])
-        if hasattr(self.lib, self.prefix + "colRanks_SVT"):        # HIP library (api.py states the rule in numpy)
-            protos["colRanks_SVT"] = (I, [V, I, I, P])
-            protos["rowRanks_SVT"] = (I, [V, I, P])
-        # x %*% y in one call (device-side transposition): HIP library only
-        for name, sig in (("matmul_SVT_mat", (I, [V, P, I, I, I, P])),
-                          ("matmul_SVT_SVT", (I, [V, V, P])),
-                          ("tcrossprod1_SVT", (I, [V, P])),
-                          ("tcrossprod2_SVT_SVT", (I, [V, V, P]))):
-            if hasattr(self.lib, self.prefix + name):
-                protos[name] = sig
-        # every row statistic in one call (include/svt_hip.h): HIP library only
-        if hasattr(self.lib, self.prefix + "rowStatsFull_SVT"):
-            protos["rowStatsFull_SVT"] = (I, [V, I, I, P, I, P, POINTER(I)])
-        for name, (res, args) in protos.items():
-            f = self._fn(name)
-            f.restype = res
-            f.argtypes = args
+        """Every row of the prototype table (svt_<name>) whose <prefix><name> the library has: the HIP library has them
+        all, the checker the host-level subset."""
+        for name, (res, args) in PROTOTYPES.items():
+            mine = self.prefix + name[len("svt_"):]
+            if name.startswith("svt_") and hasattr(self.lib, mine):
+                f = getattr(self.lib, mine)
+                f.restype, f.argtypes = res, args
 
     def _check(self, rc):
         if rc != 0:
@@ -109,9 +69,7 @@ class CAbiDispatcher:
 
     def C_set_max_threads(self, nthread: int):
         """Returns the previous value (the reference returns it too, R/thread-control.R:60-66)."""
-        f = self._fn("set_max_threads")
-        f.argtypes = [ctypes.c_int]
-        return int(f(int(nthread)))
+        return int(self._fn("set_max_threads")(int(nthread)))
 
     # crossprod ---------------------------------------------------------------
     def C_crossprod2_SVT_mat(self, x: SVT_SparseArray, y: np.ndarray, tr_y: bool):
@@ -210,21 +168,14 @@ class CAbiDispatcher:
 
     # resident operands (include/svt_hip.h; HIP library only) --------------------
     def resident_set_limit(self, nbytes: int):
-        f = self._fn("resident_set_limit")
-        f.argtypes = [ctypes.c_size_t]
-        f.restype = c_int
-        self._check(f(int(nbytes)))
+        self._check(self._fn("resident_set_limit")(int(nbytes)))
 
     def resident_clear(self):
-        f = self._fn("resident_clear")
-        f.restype = None
-        f()
+        self._fn("resident_clear")()
 
     def resident_stats(self) -> dict:
-        f = self._fn("resident_stats")
-        f.restype = None
         b, e, h, m = ctypes.c_size_t(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        f(byref(b), byref(e), byref(h), byref(m))
+        self._fn("resident_stats")(byref(b), byref(e), byref(h), byref(m))
         return {"bytes": b.value, "entries": e.value, "hits": h.value, "misses": m.value}
 
     @property
@@ -388,11 +339,8 @@ class CAbiDispatcher:
         ri = np.zeros(max(nnz, 1), dtype=np.int32)
         vv = np.zeros(max(nnz, 1), dtype=x.np_dtype)
         view = make_view(x)
-        f = self._fn("aperm_SVT")
-        f.restype = ctypes.c_int
-        f.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        self._check(f(ctypes.addressof(view), perm.ctypes.data, cp.ctypes.data, ri.ctypes.data,
-                      vv.ctypes.data))
+        self._check(self._fn("aperm_SVT")(ctypes.addressof(view), perm.ctypes.data, cp.ctypes.data, ri.ctypes.data,
+                                          vv.ctypes.data))
         dn = None
         if x.dimnames is not None:
             dn = [x.dimnames[p - 1] for p in perm]
@@ -432,10 +380,8 @@ class CAbiDispatcher:
         ri = np.zeros(max(nnz, 1), dtype=np.int32)
         vv = np.zeros(max(nnz, 1), dtype=x.np_dtype)
         view = make_view(x)
-        f = self._fn("transpose_2D_SVT")
-        f.restype = ctypes.c_int
-        f.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
-        self._check(f(ctypes.addressof(view), cp.ctypes.data, ri.ctypes.data, vv.ctypes.data))
+        self._check(self._fn("transpose_2D_SVT")(ctypes.addressof(view), cp.ctypes.data, ri.ctypes.data,
+                                                 vv.ctypes.data))
         dn = None
         if x.dimnames is not None:
             dn = [x.dimnames[1], x.dimnames[0]]
@@ -455,9 +401,6 @@ class CAbiDispatcher:
         # (a pointer tells "no subscript" from an empty one: an empty array is handed over as one unread element)
         buf = [None if v is None else (v if v.size else np.zeros(1, np.int32)) for v in sub]
         begin, end = self._fn("subset_SVT_begin"), self._fn("subset_SVT_end")
-        begin.restype = end.restype = ctypes.c_int
-        begin.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]
-        end.argtypes = [c_void_p] * 4
         view = make_view(x)
         res, nnz = c_void_p(0), ctypes.c_int64(0)
         self._check(begin(ctypes.addressof(view), *[a for v, b in zip(sub, buf) for a in

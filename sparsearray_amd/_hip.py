@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes
 import os
 
+from ._abi import PROTOTYPES
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SVT_HIP_TUNING=1: the tuning build (make -C sparsearray_amd/csrc TUNING=1) with the knobs of
 # tools/tune_pbc.py compiled in; never what the product, the tests or the bench load.
@@ -15,34 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libsvt_hip_tuning.so" if os.environ.get("SVT_HIP
                         else "libsvt_hip.so")
 
 # Every symbol include/svt_hip.h declares (checked by tests/test_abi.py).
-EXPORTS = [
-    "svt_init", "svt_last_error", "svt_device_arch", "svt_set_devices", "svt_get_devices", "svt_set_shard_min_nnz",
-    "svt_crossprod2_SVT_mat", "svt_crossprod2_mat_SVT",
-    "svt_crossprod2_SVT_SVT", "svt_crossprod1_SVT",
-    "svt_matmul_SVT_mat", "svt_matmul_SVT_SVT", "svt_tcrossprod1_SVT", "svt_tcrossprod2_SVT_SVT",
-    "svt_colMedians_SVT", "svt_rowMedians_SVT", "svt_dev_colmedians_ws_bytes", "svt_dev_colmedians",
-    "svt_colQuantiles_SVT", "svt_rowQuantiles_SVT", "svt_dev_colquantiles_ws_bytes", "svt_dev_colquantiles",
-    "svt_colMads_SVT", "svt_rowMads_SVT", "svt_dev_colmads_ws_bytes", "svt_dev_colmads",
-    "svt_colRanks_SVT", "svt_rowRanks_SVT", "svt_dev_colranks_form", "svt_dev_colranks_ws_bytes", "svt_dev_colranks",
-    "svt_resident_set_limit", "svt_resident_clear", "svt_resident_stats", "svt_dev_pbc_bytes", "svt_dev_pbc_set_spare_cus", "svt_dev_pbc_spare_cus", "svt_dev_pbc_set_gather_pacing", "svt_dev_pbc_set_round_launches", "svt_dev_matmul_csc_csc_ws_bytes", "svt_dev_matmul_csc_csc", "svt_dev_rowsums_prepare", "svt_dev_rowsums_prepared", "svt_dev_rowsum_gid_bytes", "svt_dev_rowsum_prepare", "svt_dev_rowsum_prepared", "svt_dev_matmul_csc_csc_prepare", "svt_dev_matmul_csc_csc_prepared",
-    "svt_dev_crossprod_csc_csc_ws_bytes", "svt_dev_crossprod_csc_csc", "svt_dev_crossprod_csc_csc_set_panel", "svt_sparse_crossprod_set_cost", "svt_dev_crossprod_csc_csc_dense_buffer",
-    "svt_summarize_SVT", "svt_colStats_out_Rtype", "svt_colStats_SVT",
-    "svt_rowStats_SVT", "svt_rowsum_SVT", "svt_colsum_SVT",
-    "svt_rowsum_dgCMatrix", "svt_colsum_dgCMatrix",
-    "svt_colMins_dgCMatrix", "svt_colMaxs_dgCMatrix", "svt_colRanges_dgCMatrix", "svt_colVars_dgCMatrix",
-    "svt_upload", "svt_wrap_device_csc", "svt_release",
-    "svt_dev_crossprod_ws_bytes", "svt_dev_crossprod_csc_dense",
-    "svt_dev_dense_prepare", "svt_dev_crossprod_prepared",
-    "svt_dev_pbc_build", "svt_dev_pbc_release", "svt_dev_pbc_trim",
-    "svt_dev_crossprod_pbc_ws_bytes", "svt_dev_crossprod_pbc", "svt_dev_crossprod_pbc_phase", "svt_dev_crossprod_pbc_from",
-    "svt_dev_crossprod_pbc_plan",
-    "svt_get_num_procs", "svt_get_max_threads", "svt_set_max_threads", "svt_dev_aperm_ws_bytes", "svt_dev_aperm_perm_ws_bytes", "svt_dev_aperm", "svt_dev_aperm_route_counts", "svt_aperm_SVT", "svt_transpose_2D_SVT", "svt_dev_transpose_ws_bytes", "svt_dev_transpose", "svt_dev_transpose_plan", "svt_dev_set_box_nnz", "svt_dev_boxed_calls", "svt_dev_colstats", "svt_dev_rowstats_ws_bytes", "svt_dev_rowsums", "svt_dev_rowsum",
-    "svt_rowStatsFull_SVT", "svt_dev_rowstats_ws_bytes_op", "svt_dev_rowstats",
-    "svt_dev_colstats_form", "svt_dev_rowstats_form",
-    "svt_dev_subset_tile", "svt_dev_subset_cols_ws_bytes", "svt_dev_subset_cols_count", "svt_dev_subset_cols_fill",
-    "svt_dev_subset_rows_ws_bytes", "svt_dev_subset_rows_count", "svt_dev_subset_rows_fill", "svt_dev_subset",
-    "svt_dev_subset_route_counts", "svt_subset_SVT_begin", "svt_subset_SVT_end",
-]
+EXPORTS = list(PROTOTYPES)
 
 
 class HipBackendError(RuntimeError):
@@ -51,6 +26,18 @@ class HipBackendError(RuntimeError):
 
 _lib = None
 _ready = False
+
+
+def declare(lib: ctypes.CDLL) -> ctypes.CDLL:
+    """Sets the prototype of every function of the C ABI on ``lib`` (sparsearray_amd/_abi.py); a symbol the library
+    lacks raises."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        try:
+            f = getattr(lib, name)
+        except AttributeError:
+            raise HipBackendError(f"{lib._name} does not export {name}") from None
+        f.restype, f.argtypes = restype, argtypes
+    return lib
 
 
 def load_library() -> ctypes.CDLL:
@@ -69,11 +56,7 @@ def load_library() -> ctypes.CDLL:
             import torch  # noqa: F401
         except ImportError:
             pass
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.svt_last_error.restype = ctypes.c_char_p
-        _lib.svt_device_arch.restype = ctypes.c_char_p
-        _lib.svt_init.argtypes = [ctypes.c_int]
-        _lib.svt_init.restype = ctypes.c_int
+        _lib = declare(ctypes.CDLL(LIB_PATH))
     return _lib
 
 
@@ -97,14 +80,12 @@ def set_devices(ordinals) -> None:
     lib = init()
     ords = [int(d) for d in ordinals]
     arr = (ctypes.c_int * max(1, len(ords)))(*ords)
-    lib.svt_set_devices.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     if lib.svt_set_devices(arr, len(ords)) != 0:
         raise HipBackendError(lib.svt_last_error().decode())
 
 
 def get_devices() -> list:
     lib = init()
-    lib.svt_get_devices.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     arr = (ctypes.c_int * 16)()
     n = lib.svt_get_devices(arr, 16)
     return [arr[i] for i in range(min(n, 16))]
@@ -113,8 +94,6 @@ def get_devices() -> list:
 def set_shard_min_nnz(n: int) -> None:
     """Operands with fewer nonzeros stay on the first device of the list (0: always shard)."""
     lib = init()
-    lib.svt_set_shard_min_nnz.argtypes = [ctypes.c_int64]
-    lib.svt_set_shard_min_nnz.restype = None
     lib.svt_set_shard_min_nnz(int(n))
 
 
@@ -126,8 +105,6 @@ def colstats_form(nseg: int, nnz: int):
     """(form, nchunk): the launch form of the column statistics for ``nseg`` generalized columns with ``nnz``
     nonzeros in all, one of COLSTATS_FORMS (include/svt_hip.h, svt_dev_colstats_form).  Needs no GPU."""
     lib = load_library()
-    lib.svt_dev_colstats_form.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]
-    lib.svt_dev_colstats_form.restype = ctypes.c_int
     nchunk = ctypes.c_int(1)
     form = lib.svt_dev_colstats_form(int(nseg), int(nnz), ctypes.byref(nchunk))
     return COLSTATS_FORMS[form], nchunk.value
@@ -138,9 +115,6 @@ def rowstats_form(nrow: int, ncol: int, nnz: int, op: str, inner: int = 1, na_ba
     (include/svt_hip.h, svt_dev_rowstats_form).  ``ncol`` counts leaves.  Needs no GPU."""
     from .api import OPCODES
     lib = load_library()
-    lib.svt_dev_rowstats_form.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]
-    lib.svt_dev_rowstats_form.restype = ctypes.c_int
     ps, nsplit = ctypes.c_int(0), ctypes.c_int64(1)
     form = lib.svt_dev_rowstats_form(int(nrow), int(ncol), int(nnz), int(bool(na_background)), OPCODES[op], int(inner),
                                      ctypes.byref(ps), ctypes.byref(nsplit))
@@ -162,9 +136,6 @@ def pbc_plan(handle, K: int, tr_y: bool, stride_c: int, stride_k: int, first_col
     svt_dev_crossprod_pbc_plan): kind one of PBC_KINDS, kernel one of PBC_KERNELS, NV, nsplit, panels_per_split,
     direct, launches, tail_splits, tail_blocks.  Launches nothing."""
     lib = init()
-    lib.svt_dev_crossprod_pbc_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
-                                               ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(_PbcPlanStruct)]
-    lib.svt_dev_crossprod_pbc_plan.restype = ctypes.c_int
     st = _PbcPlanStruct()
     if lib.svt_dev_crossprod_pbc_plan(handle, int(K), int(bool(tr_y)), int(stride_c), int(stride_k), int(first_col),
                                       ctypes.byref(st)) != 0:
@@ -184,8 +155,6 @@ def transpose_plan(nrow: int, ncol: int, nnz: int, nslab: int = 1) -> dict:
     svt_dev_transpose_plan): bucketed, fbits, cbits, nfb, ncoarse, ngroups, key_sort_passes, why_not (one of
     TRANSPOSE_PLAN_WHY).  Needs no GPU."""
     lib = load_library()
-    lib.svt_dev_transpose_plan.argtypes = [ctypes.c_int64] * 4 + [ctypes.POINTER(ctypes.c_int64)]
-    lib.svt_dev_transpose_plan.restype = ctypes.c_int
     out = (ctypes.c_int64 * 8)()
     if lib.svt_dev_transpose_plan(int(nrow), int(ncol), int(nnz), int(nslab), out) != 0:
         raise HipBackendError(lib.svt_last_error().decode())

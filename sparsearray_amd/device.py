@@ -7,129 +7,19 @@ libsvt_hip.so (include/svt_hip.h, "device level").
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_double, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_int64, c_void_p
 
 import numpy as np
 import torch
 
 from . import _hip
+from ._abi import ALLOC_FN, FREE_FN
 from .api import OPCODES, SparseArrayError, SparseArrayUnsupported
 from .svt import INTSXP, LGLSXP, REALSXP
 
-_protos_done = False
-# svt_dev_alloc_fn / svt_dev_free_fn (include/svt_hip.h)
-_ALLOC_FN = ctypes.CFUNCTYPE(c_void_p, c_size_t, c_void_p)
-_FREE_FN = ctypes.CFUNCTYPE(None, c_void_p, c_void_p)
-
 
 def _lib():
-    global _protos_done
-    lib = _hip.init()
-    if not _protos_done:
-        lib.svt_wrap_device_csc.restype = c_void_p
-        lib.svt_wrap_device_csc.argtypes = [c_int, c_int64, c_int64, c_int64,
-                                            c_void_p, c_void_p, c_void_p]
-        lib.svt_release.argtypes = [c_void_p]
-        lib.svt_release.restype = None
-        lib.svt_dev_crossprod_ws_bytes.restype = c_size_t
-        lib.svt_dev_crossprod_ws_bytes.argtypes = [c_int64, c_int64, c_int]
-        lib.svt_dev_dense_prepare.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int,
-                                              c_int, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_crossprod_prepared.argtypes = [c_void_p, c_void_p, c_int, c_void_p,
-                                                   c_int64, c_int64, c_void_p]
-        lib.svt_dev_crossprod_csc_dense.argtypes = [c_void_p, c_void_p, c_int64, c_int,
-                                                    c_int, c_void_p, c_int64, c_int64,
-                                                    c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_pbc_build.restype = c_void_p
-        lib.svt_dev_pbc_build.argtypes = [c_void_p, c_int, c_int, c_int]
-        lib.svt_dev_pbc_release.argtypes = [c_void_p]
-        lib.svt_dev_pbc_release.restype = None
-        lib.svt_dev_pbc_set_spare_cus.argtypes = [c_int]
-        lib.svt_dev_pbc_set_spare_cus.restype = None
-        lib.svt_dev_pbc_spare_cus.restype = c_int
-        lib.svt_dev_pbc_set_gather_pacing.argtypes = [c_int, c_int]
-        lib.svt_dev_pbc_set_gather_pacing.restype = None
-        lib.svt_dev_crossprod_pbc_ws_bytes.restype = c_size_t
-        lib.svt_dev_crossprod_pbc_ws_bytes.argtypes = [c_void_p, c_int]
-        lib.svt_dev_crossprod_pbc.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int,
-                                              c_int, c_void_p, c_int64, c_int64, c_void_p,
-                                              c_size_t, c_void_p]
-        lib.svt_dev_crossprod_pbc_phase.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int,
-                                                    c_int, c_void_p, c_int64, c_int64, c_void_p,
-                                                    c_size_t, c_void_p, c_int]
-        lib.svt_dev_colstats.argtypes = [c_void_p, c_int, c_int, c_double, c_int64,
-                                         c_void_p, c_void_p, c_void_p]
-        lib.svt_dev_matmul_csc_csc_ws_bytes.restype = c_size_t
-        lib.svt_dev_matmul_csc_csc_ws_bytes.argtypes = [c_void_p]
-        lib.svt_dev_matmul_csc_csc.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t,
-                                               c_void_p, c_void_p]
-        lib.svt_dev_matmul_csc_csc_prepare.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_matmul_csc_csc_prepared.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t,
-                                                        c_void_p, c_void_p]
-        lib.svt_dev_crossprod_csc_csc_ws_bytes.restype = c_size_t
-        lib.svt_dev_crossprod_csc_csc_ws_bytes.argtypes = [c_void_p]
-        lib.svt_dev_crossprod_csc_csc.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_size_t,
-                                                  c_void_p, c_void_p]
-        lib.svt_dev_crossprod_csc_csc_set_panel.argtypes = [c_int, c_int]
-        lib.svt_dev_crossprod_csc_csc_set_panel.restype = None
-        lib.svt_dev_colmedians_ws_bytes.restype = c_size_t
-        lib.svt_dev_colmedians_ws_bytes.argtypes = [c_int64, c_int64]
-        lib.svt_dev_colmedians.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_colquantiles_ws_bytes.restype = c_size_t
-        lib.svt_dev_colquantiles_ws_bytes.argtypes = [c_int64, c_int64, c_int]
-        lib.svt_dev_colquantiles.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_colmads_ws_bytes.restype = c_size_t
-        lib.svt_dev_colmads_ws_bytes.argtypes = [c_int64, c_int64]
-        lib.svt_dev_colmads.argtypes = [c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_colranks_form.argtypes = [c_int64]
-        lib.svt_dev_colranks_ws_bytes.restype = c_size_t
-        lib.svt_dev_colranks_ws_bytes.argtypes = [c_int64, c_int64]
-        lib.svt_dev_colranks.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_rowstats_ws_bytes.restype = c_size_t
-        lib.svt_dev_rowstats_ws_bytes.argtypes = [c_int64, c_int64]
-        lib.svt_dev_rowsums.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_rowsums_prepare.argtypes = [c_void_p, c_int64, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_rowsums_prepared.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_rowstats_ws_bytes_op.restype = c_size_t
-        lib.svt_dev_rowstats_ws_bytes_op.argtypes = [c_void_p, c_int, c_int64]
-        lib.svt_dev_rowstats.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                         c_size_t, c_void_p]
-        lib.svt_dev_rowsum.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
-        lib.svt_dev_rowsum_gid_bytes.restype = c_size_t
-        lib.svt_dev_rowsum_gid_bytes.argtypes = [c_void_p]
-        lib.svt_dev_rowsum_prepare.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_rowsum_prepared.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
-        lib.svt_colStats_out_Rtype.argtypes = [c_int, c_int]
-        lib.svt_dev_transpose_ws_bytes.restype = c_size_t
-        lib.svt_dev_transpose_ws_bytes.argtypes = [c_int64, c_int64]
-        lib.svt_dev_transpose.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_set_box_nnz.argtypes = [c_int64]
-        lib.svt_dev_set_box_nnz.restype = None
-        lib.svt_dev_boxed_calls.argtypes = [c_int]
-        lib.svt_dev_boxed_calls.restype = c_int64
-        lib.svt_dev_aperm_ws_bytes.restype = c_size_t
-        lib.svt_dev_aperm_ws_bytes.argtypes = [c_int64, c_int, c_void_p]
-        lib.svt_dev_aperm_perm_ws_bytes.restype = c_size_t
-        lib.svt_dev_aperm_perm_ws_bytes.argtypes = [c_int64, c_int, c_void_p, c_void_p]
-        lib.svt_dev_aperm.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_subset_tile.restype = c_int
-        lib.svt_dev_subset_cols_ws_bytes.restype = c_size_t
-        lib.svt_dev_subset_cols_ws_bytes.argtypes = [c_int64]
-        lib.svt_dev_subset_cols_count.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                  c_void_p]
-        lib.svt_dev_subset_cols_fill.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.svt_dev_subset_rows_ws_bytes.restype = c_size_t
-        lib.svt_dev_subset_rows_ws_bytes.argtypes = [c_int64, c_int64, c_int64]
-        lib.svt_dev_subset_rows_count.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                  c_void_p]
-        lib.svt_dev_subset_rows_fill.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-        lib.svt_dev_subset.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, _ALLOC_FN, _FREE_FN, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        lib.svt_dev_subset_route_counts.argtypes = [c_void_p, c_int]
-        lib.svt_dev_subset_route_counts.restype = None
-        _protos_done = True
-    return lib
+    return _hip.init()
 
 
 def _check(rc):
@@ -239,7 +129,7 @@ class DeviceCSC:
         out = [c_void_p(0), c_void_p(0), c_void_p(0)]
         _check(_lib().svt_dev_subset(self.handle, *[a for v in sub for a in ((None, -1) if v is None else
                                                                                (v.data_ptr(), v.numel()))],
-                                     _ALLOC_FN(alloc), _FREE_FN(release), None, ctypes.byref(nnz),
+                                     ALLOC_FN(alloc), FREE_FN(release), None, ctypes.byref(nnz),
                                      *[ctypes.byref(o) for o in out], _stream()))
         n = int(nnz.value)
         nrow = self.nrow if sub[0] is None else sub[0].numel()
@@ -274,7 +164,6 @@ def _subscript(v, device) -> torch.Tensor:
 def subset_tile() -> int:
     """Nonzeros per workgroup tile of the column gather and the row filter (svt_dev_subset_tile).  Needs no GPU."""
     lib = _hip.load_library()
-    lib.svt_dev_subset_tile.restype = c_int
     return int(lib.svt_dev_subset_tile())
 
 
@@ -373,11 +262,9 @@ class PbcPlan:
         """The product restricted to the leaves from ``first_col`` on (svt_dev_crossprod_pbc_from)."""
         if stride_k is None:
             stride_k = self.A.ncol
-        lib = _lib()
-        lib.svt_dev_crossprod_pbc_from.argtypes = lib.svt_dev_crossprod_pbc.argtypes + [c_int64]
-        _check(lib.svt_dev_crossprod_pbc_from(self._p, self.A.handle, Y.data_ptr(), ldY, self.K,
-                                              int(tr_y), out.data_ptr(), stride_c, stride_k,
-                                              self.ws.data_ptr(), self.ws.numel(), _stream(), int(first_col)))
+        _check(_lib().svt_dev_crossprod_pbc_from(self._p, self.A.handle, Y.data_ptr(), ldY, self.K,
+                                                 int(tr_y), out.data_ptr(), stride_c, stride_k,
+                                                 self.ws.data_ptr(), self.ws.numel(), _stream(), int(first_col)))
 
     def plan(self, stride_c=1, stride_k=None, tr_y=False, first_col=0) -> dict:
         """What run() / run_from() with these arguments launches under the present knobs: kind, kernel, NV, nsplit,
@@ -414,8 +301,6 @@ def aperm_route_counts(reset=False) -> dict:
     names = ("t_bucketed", "t_key_sort", "leaf_preserving", "first_two_axes_swapped", "slab", "via_intermediate_3d",
              "general_composed", "key_sort_32", "key_sort_64", "slab_refused_at_run_time")
     buf = (c_int64 * 10)()
-    _lib().svt_dev_aperm_route_counts.argtypes = [c_void_p, c_int]
-    _lib().svt_dev_aperm_route_counts.restype = None
     _lib().svt_dev_aperm_route_counts(buf, int(bool(reset)))
     return dict(zip(names, (int(x) for x in buf)))
 
@@ -436,7 +321,6 @@ def boxed_calls(reset=False) -> int:
 
 def trim_layout_pool() -> None:
     """Returns the memory the layout pools keep for the next build to the driver (svt_dev_pbc_trim)."""
-    _lib().svt_dev_pbc_trim.restype = None
     _lib().svt_dev_pbc_trim()
 
 
@@ -460,7 +344,6 @@ def set_round_launches(on=True) -> None:
     """One launch per round of workgroups for products with many column blocks (svt_dev_pbc_set_round_launches):
     False / 0 = one launch, True / 1 = per round with the partly filled last round cut by rows (default), 2 = per
     round with the last round whole."""
-    _lib().svt_dev_pbc_set_round_launches.restype = None
     _lib().svt_dev_pbc_set_round_launches(int(on))
 
 
@@ -638,7 +521,6 @@ def crossprod_csc_csc_dense_buffer(X: DeviceCSC, Y: DeviceCSC, out=None):
     """The dense-buffer route of crossprod(X, Y) on resident operands (svt_dev_crossprod_csc_csc_dense_buffer;
     ``Y is X``: the unary form).  Allocates and synchronises inside.  Returns the (ncol(Y), ncol(X)) C-contiguous
     tensor that is the column-major result."""
-    _lib().svt_dev_crossprod_csc_csc_dense_buffer.argtypes = [c_void_p, c_void_p, c_void_p]
     if out is None:
         out = torch.empty((Y.ncol, X.ncol), dtype=torch.float64, device=Y.val.device)
     torch.cuda.synchronize()
@@ -649,8 +531,6 @@ def crossprod_csc_csc_dense_buffer(X: DeviceCSC, Y: DeviceCSC, out=None):
 def set_sparse_crossprod_cost(factor=1.0) -> None:
     """Route choice of the host entry points crossprod(x) / crossprod(x, y) (svt_sparse_crossprod_set_cost):
     < 0 never the sparse-aware kernel, 0 always, 1 the measured model."""
-    _lib().svt_sparse_crossprod_set_cost.argtypes = [c_double]
-    _lib().svt_sparse_crossprod_set_cost.restype = None
     _lib().svt_sparse_crossprod_set_cost(float(factor))
 
 

@@ -57,7 +57,6 @@ def test_pbc_refuses_layouts_no_kernel_reads(hip, cfg):
 def test_pbc_below_256_rows_runs_the_general_kernels(hip, oracle):
     """Below 256 rows the LDS-DMA layout is built without records (pbc_kind: PBC_KIND_NONE) and the general
     kernels, which add in the reference's order, answer every product, NaN or not."""
-    import ctypes
     from sparsearray_amd.device import CrossprodPlan, PbcPlan, _lib
     nrow, ncol, K = 200, 90, 24
     cp, ri, v = random_csc(nrow, ncol, 0.2, seed=26)
@@ -65,8 +64,6 @@ def test_pbc_below_256_rows_runs_the_general_kernels(hip, oracle):
     A = _dev(cp, ri, v, nrow)
     plan = PbcPlan(A, K)
     lib = _lib()
-    lib.svt_dev_pbc_bytes.restype = ctypes.c_size_t
-    lib.svt_dev_pbc_bytes.argtypes = [ctypes.c_void_p]
     assert lib.svt_dev_pbc_bytes(plan._p) < 12 * len(ri)       # a record stream takes >= 12 bytes per nonzero
     rng = np.random.default_rng(27)
     for poison in (False, True):

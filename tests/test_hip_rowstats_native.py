@@ -228,14 +228,7 @@ def test_more_than_65535_output_columns(hip, oracle):
 
 def _raw():
     from sparsearray_amd import _hip
-    lib = _hip.init()
-    P, I = ctypes.c_void_p, ctypes.c_int
-    for name in ("svt_rowStatsFull_SVT", "svt_rowStats_SVT"):
-        f = getattr(lib, name)
-        f.restype = I
-        f.argtypes = [P, I, I, P, I, P, ctypes.POINTER(I)]
-    lib.svt_last_error.restype = ctypes.c_char_p
-    return lib
+    return _hip.init()
 
 
 def test_raw_c_abi(hip):

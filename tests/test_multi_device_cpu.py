@@ -28,14 +28,10 @@ def test_set_devices_fails_loudly_without_gpu():
         pytest.skip("GPU present")
     from sparsearray_amd._hip import load_library
     lib = load_library()
-    lib.svt_set_devices.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
-    lib.svt_last_error.restype = ctypes.c_char_p
     arr = (ctypes.c_int * 2)(0, 0)
     assert lib.svt_set_devices(arr, 2) == -1
     assert b"no HIP device" in lib.svt_last_error()
-    lib.svt_get_devices.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     assert lib.svt_get_devices(arr, 2) == 0          # no list was set
-    lib.svt_set_shard_min_nnz.argtypes = [ctypes.c_int64]
     lib.svt_set_shard_min_nnz(0)                     # (no device needed)
 
 

@@ -29,20 +29,6 @@ def _lib():
     return _hip.init()
 
 
-def _protos(lib):
-    P, I = ctypes.c_void_p, ctypes.c_int
-    lib.svt_rowStats_SVT.restype = I
-    lib.svt_rowStats_SVT.argtypes = [P, I, I, P, I, P, ctypes.POINTER(I)]
-    lib.svt_colStats_SVT.restype = I
-    lib.svt_colStats_SVT.argtypes = [P, I, I, ctypes.c_double, I, P, ctypes.POINTER(I)]
-    lib.svt_rowsum_SVT.restype = I
-    lib.svt_rowsum_SVT.argtypes = [P, P, I, I, P, ctypes.POINTER(I)]
-    lib.svt_crossprod2_SVT_mat.restype = I
-    lib.svt_crossprod2_SVT_mat.argtypes = [P, P, I, I, I, I, P]
-    lib.svt_resident_set_limit.argtypes = [ctypes.c_size_t]
-    lib.svt_last_error.restype = ctypes.c_char_p
-
-
 def _ok(lib, rc):
     assert rc == 0, lib.svt_last_error().decode()
 
@@ -56,7 +42,6 @@ D5 = (20_000, 20_000, 64)
 def test_config5_full_size_row_min_max_var_and_col_var_dims2(hip):
     from sparsearray_amd import synth
     lib = _lib()
-    _protos(lib)
     dev = torch.device("cuda", 0)
     cp, ri, v = synth.random_device_csc(D5[0], D5[1] * D5[2], 0.005, seed=5, device=dev)
     hcp, hri, hv = cp.cpu().numpy(), ri.cpu().numpy(), v.cpu().numpy()
@@ -122,7 +107,6 @@ N2, M2, K2 = 1_000_000, 10_000, 128
 def test_config2_size_integer_and_logical_operands_bit_exact(hip, type_):
     from sparsearray_amd import synth
     lib = _lib()
-    _protos(lib)
     dev = torch.device("cuda", 0)
     cp, ri, v = synth.random_device_csc(N2, M2, 0.01, seed=21, device=dev)
     g = torch.Generator(device=dev).manual_seed(22)

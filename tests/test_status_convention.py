@@ -20,8 +20,6 @@ def test_unsupported_is_status_one_and_errors_are_minus_one(hip):
     out = np.zeros(80)
     warn = ctypes.c_int(0)
     f = lib.svt_colStats_SVT
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     # SVT_OP_RANGE = 7: never sent by the R API for col stats (copy_result_to_out() keeps the first scalar only,
     # src/SparseArray_matrixStats.c:179-197); not implemented on the device -> "not supported here"
     rc = f(ctypes.addressof(view), 7, 0, float("nan"), 1, out.ctypes.data, ctypes.byref(warn))

@@ -52,8 +52,6 @@ xv = make_view_from_csc((nrow, ncol), "double", cph, rih, vh)
 yv = make_view_from_csc((ncol, K), "double", bcp.cpu().numpy(), bri.cpu().numpy(), bv.cpu().numpy())
 res = np.zeros((nrow, K), order="F")
 fn = lib.svt_matmul_SVT_SVT
-fn.restype = ctypes.c_int
-fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
 for rep in range(3):
     t0 = time.perf_counter()
     rc = fn(ctypes.addressof(xv), ctypes.addressof(yv), res.ctypes.data)

@@ -14,11 +14,10 @@ from oracle import load_oracle
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 hl, orc = _hip.init(), load_oracle()
 P, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-for lib, pre in ((hl, "svt_"), (orc, "orc_")):
-    getattr(lib, pre + "colStats_SVT").argtypes = [P, I, I, D, I, P, P]
-    getattr(lib, pre + "rowStats_SVT").argtypes = [P, I, I, P, I, P, P]
-    getattr(lib, pre + "crossprod1_SVT").argtypes = [P, P]
-    getattr(lib, pre + "crossprod2_SVT_mat").argtypes = [P, P, I, I, I, I, P]
+orc.orc_colStats_SVT.argtypes = [P, I, I, D, I, P, P]
+orc.orc_rowStats_SVT.argtypes = [P, I, I, P, I, P, P]
+orc.orc_crossprod1_SVT.argtypes = [P, P]
+orc.orc_crossprod2_SVT_mat.argtypes = [P, P, I, I, I, I, P]
 
 
 def best(fn):

@@ -12,9 +12,6 @@ dev = torch.device("cuda", 0)
 cp, ri, v = synth.random_device_csc(nrow, ncol, 0.01, seed=1, device=dev)
 cp, ri, v = cp.cpu().numpy(), ri.cpu().numpy(), v.cpu().numpy()
 view = make_view_from_csc((nrow, ncol), "double", cp, ri, v)
-lib.svt_upload.restype = ctypes.c_void_p
-lib.svt_upload.argtypes = [ctypes.c_void_p]
-lib.svt_release.argtypes = [ctypes.c_void_p]
 for rep in range(3):
     t0 = time.perf_counter()
     h = lib.svt_upload(ctypes.addressof(view))
@@ -25,8 +22,6 @@ for rep in range(3):
 y = np.asfortranarray(np.random.default_rng(2).uniform(-1, 1, (nrow, K)))
 out = np.zeros((ncol, K), order="F")
 fn = lib.svt_crossprod2_SVT_mat
-fn.restype = ctypes.c_int
-fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
 for rep in range(2):
     t0 = time.perf_counter()
     rc = fn(ctypes.addressof(view), y.ctypes.data, nrow, K, 14, 0, out.ctypes.data)
@@ -34,7 +29,6 @@ for rep in range(2):
     print(f"C_crossprod2_SVT_mat host level: rc={rc} {dt*1e3:.1f} ms  ({len(ri)/dt/1e9:.2f} GNZ/s)")
 
 # resident operands: the same calls with the device copy (and its panel-blocked layout) kept
-lib.svt_resident_set_limit.argtypes = [ctypes.c_size_t]
 lib.svt_resident_set_limit(8 << 30)
 for rep in range(3):
     t0 = time.perf_counter()
@@ -44,8 +38,6 @@ for rep in range(3):
 from sparsearray_amd._dispatch import CAbiDispatcher
 op_sum = CAbiDispatcher(lib, "svt_")._opcode("sum")
 cs = lib.svt_colStats_SVT
-cs.restype = ctypes.c_int
-cs.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
 res = np.zeros(ncol)
 warn = ctypes.c_int(0)
 for lim in (8 << 30, 0):

@@ -34,16 +34,7 @@ DIMS = (
 def library():
     sys.path.insert(0, ROOT)
     from sparsearray_amd._hip import load_library
-    lib = load_library()
-    lib.svt_dev_transpose_ws_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
-    lib.svt_dev_transpose_ws_bytes.restype = ctypes.c_size_t
-    lib.svt_dev_aperm_ws_bytes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
-    lib.svt_dev_aperm_ws_bytes.restype = ctypes.c_size_t
-    lib.svt_dev_aperm_perm_ws_bytes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    lib.svt_dev_aperm_perm_ws_bytes.restype = ctypes.c_size_t
-    lib.svt_dev_set_box_nnz.argtypes = [ctypes.c_int64]
-    lib.svt_dev_set_box_nnz.restype = None
-    return lib
+    return load_library()
 
 
 def grid():
