@@ -641,6 +641,27 @@ int svt_dev_rowsum_prepare(const svt_dev_csc *A, const int *group, int ngroup, v
 int svt_dev_rowsum_prepared(const svt_dev_csc *A, const void *gid, int ngroup, int na_rm, double *out,
 			    void *stream);
 
+/* Which kernels the three calls above launch.  Pure host queries (no device, no handle), the functions the launchers
+   call; for tests and fuzzers that must know which kernel they exercise.
+   svt_dev_rowsum_form(): the form of svt_dev_rowsum() -- and of svt_rowsum_SVT and svt_rowsum_dgCMatrix, which end in
+   the same launcher -- for an nrow x ncol operand of `nnz` nonzeros and values of type Rtype; col_ptr32 != 0: the
+   offsets are the int32 'p' slot of a dgCMatrix.
+     0  memory atomics, a wavefront per column: integers, int32 offsets, more than 8192 groups, or columns shorter
+        than a quarter of the groups on average (nnz / ncol < ngroup / 4, both quotients truncated)
+     1  a workgroup per column, sums in LDS, the int group table                       (fewer than 65536 rows)
+     2  the same behind a 16-bit copy of the table          (fewer than 64 columns, or more than 5120 groups)
+     3  windowed: *cols_per_wg columns (a wavefront each) per workgroup walk the rows *window_rows at a time, their
+        sums -- cols_per_wg * ngroup * 8 bytes, at most 160 KiB -- in LDS
+   *cols_per_wg is 0 for the forms 0 to 2; *window_rows is the same for every operand.  Both may be NULL.
+   svt_dev_rowsum_prepare_form(): 0 two ids per thread (fewer than 65536 rows or 64 columns, 65535 groups), 1 the walk
+   of form 3 above with *cols_per_wg (8 to 16) columns per workgroup.
+   svt_dev_rowsum_prepared_form(): 0 and *cols_per_wg (1 to 16; 1 to 3 for more than 5120 groups), or 1 for a shape
+   svt_dev_rowsum_prepared() refuses (more than 20480 groups). */
+int svt_dev_rowsum_form(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, int Rtype, int col_ptr32,
+			int *cols_per_wg, int64_t *window_rows);
+int svt_dev_rowsum_prepare_form(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, int *cols_per_wg);
+int svt_dev_rowsum_prepared_form(int64_t ncol, int ngroup, int *cols_per_wg);
+
 /* Thread control (C_get_num_procs / C_get_max_threads / C_set_max_threads,
    src/thread_control.c:47-66; R/thread-control.R sets the team size around every
    .Call and restores it).  The device kernels have no thread team to size: the

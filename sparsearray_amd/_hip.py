@@ -121,6 +121,38 @@ def rowstats_form(nrow: int, ncol: int, nnz: int, op: str, inner: int = 1, na_ba
     return ROWSTATS_FORMS[form], ps.value, nsplit.value
 
 
+ROWSUM_FORMS = ("atomic", "lds_table", "lds_g16", "windowed")
+ROWSUM_ID_FORMS = ("flat", "windowed")
+
+
+def rowsum_form(nrow: int, ncol: int, nnz: int, ngroup: int, type: str = "double", col_ptr32: bool = False):
+    """(form, cols_per_wg, window_rows): the launch form of rowsum() for an ``nrow`` x ``ncol`` operand of ``nnz``
+    nonzeros, one of ROWSUM_FORMS (include/svt_hip.h, svt_dev_rowsum_form); ``col_ptr32``: the dgCMatrix entry point.
+    Needs no GPU."""
+    from .svt import INTSXP, REALSXP
+    lib = load_library()
+    C, win = ctypes.c_int(0), ctypes.c_int64(0)
+    form = lib.svt_dev_rowsum_form(int(nrow), int(ncol), int(nnz), int(ngroup), REALSXP if type == "double" else INTSXP,
+                                   int(bool(col_ptr32)), ctypes.byref(C), ctypes.byref(win))
+    return ROWSUM_FORMS[form], C.value, win.value
+
+
+def rowsum_prepare_form(nrow: int, ncol: int, nnz: int, ngroup: int):
+    """(form, cols_per_wg) of svt_dev_rowsum_prepare(), one of ROWSUM_ID_FORMS.  Needs no GPU."""
+    lib = load_library()
+    C = ctypes.c_int(0)
+    form = lib.svt_dev_rowsum_prepare_form(int(nrow), int(ncol), int(nnz), int(ngroup), ctypes.byref(C))
+    return ROWSUM_ID_FORMS[form], C.value
+
+
+def rowsum_prepared_form(ncol: int, ngroup: int):
+    """(supported, cols_per_wg) of svt_dev_rowsum_prepared() (svt_dev_rowsum_prepared_form).  Needs no GPU."""
+    lib = load_library()
+    C = ctypes.c_int(0)
+    rc = lib.svt_dev_rowsum_prepared_form(int(ncol), int(ngroup), ctypes.byref(C))
+    return rc == 0, C.value
+
+
 PBC_KINDS = ("none", "dma", "gather")
 PBC_KERNELS = ("general", "dma", "gather", "gather2", "gatherx")
 

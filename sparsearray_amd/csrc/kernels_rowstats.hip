@@ -1351,20 +1351,78 @@ static void launch_rowsum_cols(int na_rm, void (*narm)(P...), void (*plain)(P...
 	hipLaunchKernelGGL(kernel, dim3((unsigned) ((ncol + C - 1) / C)), dim3(C * 64), lds, s, args..., C);
 }
 
+// columns per workgroup the LDS cap allows for ngroup accumulators a column: 160 KiB / (ngroup * 8), at most 16
+static int rowsum_lds_cmax(int ngroup)
+{
+	const int64_t cap = (int64_t) (160 * 1024) / ((int64_t) ngroup * 8);
+	return cap > 16 ? 16 : (int) cap;
+}
+
+// The form launch_rowsum() takes (values of svt_dev_rowsum_form, include/svt_hip.h): the LDS kernels for doubles behind
+// 64-bit offsets with at most 8192 groups and leaves long enough to fill them (nnz: the operand's nonzeros), else --
+// and for ints, and for the int32 'p' slot of a dgCMatrix, which the LDS kernels do not read -- the atomic one.  Among
+// the LDS kernels: from 65536 rows on the 16-bit copy of the table, and with it the windowed kernel when at least 4
+// columns' accumulators fit in LDS and there are at least 64 columns.
+RowsumRoute rowsum_route(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, int Rtype, bool col_ptr32)
+{
+	RowsumRoute rt = { ROWSUM_ATOMIC, 0 };
+	if (!(Rtype == SVT_REALSXP && !col_ptr32 && ngroup <= 8192 && ncol > 0 && nnz / ncol >= ngroup / 4))
+		return rt;
+	rt.form = ROWSUM_LDS_TABLE;
+	if (ngroup <= 0 || !(ngroup < 65535 && nrow >= 65536))
+		return rt;
+	const int cmax = rowsum_lds_cmax(ngroup);
+	if (cmax >= 4 && ncol >= 64) {
+		rt.form = ROWSUM_WINDOWED;
+		rt.cols_per_wg = rowsum_cols_per_wg(ncol, cmax, 4);
+	} else {
+		rt.form = ROWSUM_LDS_G16;
+	}
+	return rt;
+}
+
+// The form launch_rowsum_gid() takes (values of svt_dev_rowsum_prepare_form)
+RowsumRoute rowsum_gid_route(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, bool col_ptr32)
+{
+	RowsumRoute rt = { ROWSUM_IDS_FLAT, 0 };
+	if (nnz > 0 && !col_ptr32 && ncol >= 64 && nrow >= 65536 && ngroup >= 1 && ngroup < 65535) {
+		rt.form = ROWSUM_IDS_WINDOWED;
+		rt.cols_per_wg = rowsum_cols_per_wg(ncol, 16, 8);
+	}
+	return rt;
+}
+
+// launch_rowsum_prepared(): 0 and the columns per workgroup, or 1 when the shape does not suit the kernel (one column's
+// accumulators do not fit in LDS, or the offsets are the int32 ones)
+int rowsum_prepared_route(int64_t ncol, int ngroup, bool col_ptr32, int *cols_per_wg)
+{
+	*cols_per_wg = 0;
+	if (ncol <= 0 || ngroup <= 0)
+		return 0;
+	const int cmax = rowsum_lds_cmax(ngroup);
+	if (cmax < 1 || col_ptr32)
+		return 1;
+	*cols_per_wg = rowsum_cols_per_wg(ncol, cmax, cmax >= 4 ? 4 : 1);
+	return 0;
+}
+
+int64_t rowsum_window_rows(void)
+{
+	return ROWSUM_WIN;
+}
+
 // Long f64 columns with few groups: LDS accumulators, no memory atomics.
-static int launch_rowsum_lds(const GroupSumArgs &a, hipStream_t s)
+static int launch_rowsum_lds(const GroupSumArgs &a, const RowsumRoute &rt, hipStream_t s)
 {
 	if (a.ncol <= 0 || a.ngroup <= 0)
 		return 0;
-	if (a.ngroup < 65535 && a.nrow >= 65536) {
+	if (rt.form != ROWSUM_LDS_TABLE) {
 		uint16_t *g16 = NULL;
 		if (make_group16(a, &g16, s))
 			return -1;
-		const int64_t cap = (int64_t) (160 * 1024) / ((int64_t) a.ngroup * 8);
-		const int cmax = cap > 16 ? 16 : (int) cap;
-		if (cmax >= 4 && a.ncol >= 64 && a.col_ptr64 != NULL)
+		if (rt.form == ROWSUM_WINDOWED)
 			launch_rowsum_cols(a.na_rm, rowsum_f64_cols_kernel<true>, rowsum_f64_cols_kernel<false>, a.ncol, a.ngroup,
-					   rowsum_cols_per_wg(a.ncol, cmax, 4), s, a.col_ptr64, a.row_idx, (const double *) a.val,
+					   rt.cols_per_wg, s, a.col_ptr64, a.row_idx, (const double *) a.val,
 					   a.ncol, a.nrow, a.ngroup, (const uint16_t *) g16, (double *) a.out);
 		else
 			hipLaunchKernelGGL(rowsum_f64_lds_kernel<uint16_t>, dim3((unsigned) a.ncol), dim3(256),
@@ -1379,14 +1437,12 @@ static int launch_rowsum_lds(const GroupSumArgs &a, hipStream_t s)
 	return 0;
 }
 
-// rowsum of doubles: the LDS kernels for few groups and leaves long enough to fill them (a.nnz: the operand's
-// nonzeros), else -- and for ints, and for the int32 'p' slot of a dgCMatrix, which the LDS kernels do not read --
-// the atomic one
+// rowsum by the form of rowsum_route()
 int launch_rowsum(const GroupSumArgs &a, hipStream_t s)
 {
-	if (a.Rtype == SVT_REALSXP && a.col_ptr64 != NULL && a.ngroup <= 8192 && a.ncol > 0 &&
-	    a.nnz / a.ncol >= a.ngroup / 4)
-		return launch_rowsum_lds(a, s);
+	const RowsumRoute rt = rowsum_route(a.nrow, a.ncol, a.nnz, a.ngroup, a.Rtype, a.col_ptr64 == NULL);
+	if (rt.form != ROWSUM_ATOMIC)
+		return launch_rowsum_lds(a, rt, s);
 	return groupsum_common(a, (int64_t) a.ngroup * a.ncol, false, s);
 }
 
@@ -1400,12 +1456,13 @@ int launch_rowsum_gid(const GroupSumArgs &a, uint16_t *gid, hipStream_t s)
 {
 	if (a.nnz <= 0)
 		return 0;
-	if (a.col_ptr64 != NULL && a.ncol >= 64 && a.nrow >= 65536 && a.ngroup >= 1 && a.ngroup < 65535) {
+	const RowsumRoute rt = rowsum_gid_route(a.nrow, a.ncol, a.nnz, a.ngroup, a.col_ptr64 == NULL);
+	if (rt.form == ROWSUM_IDS_WINDOWED) {
 		// (group16_kernel folds NA into the last group as the flat kernel does; stray ids are the caller's: check_group)
 		uint16_t *g16 = NULL;
 		if (make_group16(a, &g16, s))
 			return -1;
-		const int C = rowsum_cols_per_wg(a.ncol, 16, 8);
+		const int C = rt.cols_per_wg;
 		hipLaunchKernelGGL(rowsum_gid_cols_kernel, dim3((unsigned) ((a.ncol + C - 1) / C)), dim3(C * 64), 0, s,
 				   a.col_ptr64, a.row_idx, a.ncol, a.nrow, g16, gid, C);
 		HIP_TRY(hipGetLastError());
@@ -1426,13 +1483,11 @@ int launch_rowsum_prepared(const GroupSumArgs &a, const uint16_t *gid, hipStream
 {
 	if (a.ncol <= 0 || a.ngroup <= 0)
 		return 0;
-	const int64_t cap = (int64_t) (160 * 1024) / ((int64_t) a.ngroup * 8);
-	if (cap < 1 || a.col_ptr64 == NULL)
+	int C = 0;
+	if (rowsum_prepared_route(a.ncol, a.ngroup, a.col_ptr64 == NULL, &C))
 		return 1;
-	const int cmax = cap > 16 ? 16 : (int) cap;
 	launch_rowsum_cols(a.na_rm, rowsum_f64_gid_kernel<true>, rowsum_f64_gid_kernel<false>, a.ncol, a.ngroup,
-			   rowsum_cols_per_wg(a.ncol, cmax, cmax >= 4 ? 4 : 1), s, a.col_ptr64, (const double *) a.val, gid,
-			   a.ncol, a.ngroup, (double *) a.out);
+			   C, s, a.col_ptr64, (const double *) a.val, gid, a.ncol, a.ngroup, (double *) a.out);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }

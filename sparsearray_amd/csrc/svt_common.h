@@ -297,6 +297,26 @@ struct GroupSumArgs {
 	int *ovflow_flag;
 };
 size_t groupsum_scratch_bytes(int Rtype, int64_t out_len);
+// launch forms of rowsum() (values of svt_dev_rowsum_form, include/svt_hip.h) and of the prepared ids
+// (svt_dev_rowsum_prepare_form)
+enum {
+	ROWSUM_ATOMIC = 0,          // groupsum_atomic_kernel: a wavefront per column, memory atomics
+	ROWSUM_LDS_TABLE = 1,       // rowsum_f64_lds_kernel<int>: a workgroup per column, the int group table
+	ROWSUM_LDS_G16 = 2,         // rowsum_f64_lds_kernel<uint16_t>: the same behind the 16-bit copy of the table
+	ROWSUM_WINDOWED = 3         // rowsum_f64_cols_kernel: cols_per_wg columns per workgroup, window by window
+};
+enum {
+	ROWSUM_IDS_FLAT = 0,        // rowsum_gid_kernel: two ids per thread
+	ROWSUM_IDS_WINDOWED = 1     // rowsum_gid_cols_kernel: the walk of the windowed kernel
+};
+struct RowsumRoute {
+	int form;
+	int cols_per_wg;    // ROWSUM_WINDOWED / ROWSUM_IDS_WINDOWED: columns (a wavefront each) per workgroup, else 0
+};
+RowsumRoute rowsum_route(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, int Rtype, bool col_ptr32);
+RowsumRoute rowsum_gid_route(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, bool col_ptr32);
+int rowsum_prepared_route(int64_t ncol, int ngroup, bool col_ptr32, int *cols_per_wg);
+int64_t rowsum_window_rows(void);   // rows per window of the windowed forms
 int launch_rowsum(const GroupSumArgs &a, hipStream_t s);       // doubles: LDS or atomic kernels by shape
 int launch_rowsum_gid(const GroupSumArgs &a, uint16_t *gid, hipStream_t s);
 int launch_rowsum_prepared(const GroupSumArgs &a, const uint16_t *gid, hipStream_t s);   // f64, ngroup * 8 <= LDS

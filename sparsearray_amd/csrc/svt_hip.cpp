@@ -1707,6 +1707,30 @@ extern "C" int svt_dev_rowsum_prepared(const svt_dev_csc *A, const void *gid, in
 	return rc;
 }
 
+extern "C" int svt_dev_rowsum_form(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, int Rtype, int col_ptr32,
+				  int *cols_per_wg, int64_t *window_rows)
+{
+	const RowsumRoute rt = rowsum_route(nrow, ncol, nnz, ngroup, Rtype, col_ptr32 != 0);
+	if (cols_per_wg) *cols_per_wg = rt.cols_per_wg;
+	if (window_rows) *window_rows = rowsum_window_rows();
+	return rt.form;
+}
+
+extern "C" int svt_dev_rowsum_prepare_form(int64_t nrow, int64_t ncol, int64_t nnz, int ngroup, int *cols_per_wg)
+{
+	const RowsumRoute rt = rowsum_gid_route(nrow, ncol, nnz, ngroup, false);
+	if (cols_per_wg) *cols_per_wg = rt.cols_per_wg;
+	return rt.form;
+}
+
+extern "C" int svt_dev_rowsum_prepared_form(int64_t ncol, int ngroup, int *cols_per_wg)
+{
+	int C = 0;
+	const int rc = rowsum_prepared_route(ncol, ngroup, false, &C);
+	if (cols_per_wg) *cols_per_wg = C;
+	return rc;
+}
+
 // ==================================================================================
 // Sharded host entry points (svt_set_devices)
 // ==================================================================================

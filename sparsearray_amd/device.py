@@ -617,6 +617,21 @@ class RowSumsPlan:
         return out
 
 
+def rowsum_form(A: DeviceCSC, ngroup: int):
+    """(form, cols_per_wg, window_rows) of rowsum(A, group, ngroup) (svt_dev_rowsum_form)."""
+    return _hip.rowsum_form(A.nrow, A.ncol, A.nnz, ngroup, "double" if A.Rtype == REALSXP else "integer")
+
+
+def rowsum_prepare_form(A: DeviceCSC, ngroup: int):
+    """(form, cols_per_wg) of the ids RowsumPlan(A, group, ngroup) prepares (svt_dev_rowsum_prepare_form)."""
+    return _hip.rowsum_prepare_form(A.nrow, A.ncol, A.nnz, ngroup)
+
+
+def rowsum_prepared_form(A: DeviceCSC, ngroup: int):
+    """(supported, cols_per_wg) of RowsumPlan(A, group, ngroup).run() (svt_dev_rowsum_prepared_form)."""
+    return _hip.rowsum_prepared_form(A.ncol, ngroup)
+
+
 def rowsum(A: DeviceCSC, group: torch.Tensor, ngroup: int, na_rm=False, out=None):
     assert group.dtype == torch.int32 and group.numel() == A.nrow
     if out is None:
@@ -631,10 +646,14 @@ class RowsumPlan:
     (svt_dev_rowsum_prepare), a call then streams 10 bytes per nonzero and looks nothing up
     (svt_dev_rowsum_prepared; src/rowsum_methods.c:44-64 for the rules)."""
 
-    def __init__(self, A: DeviceCSC, group: torch.Tensor, ngroup: int):
+    def __init__(self, A: DeviceCSC, group: torch.Tensor, ngroup: int, gid=None):
+        """``gid``: the caller's uint8 device buffer of at least svt_dev_rowsum_gid_bytes() bytes for the ids."""
         assert group.dtype == torch.int32 and group.numel() == A.nrow
         self.A, self.ngroup = A, int(ngroup)
-        self.gid = torch.empty(_lib().svt_dev_rowsum_gid_bytes(A.handle), dtype=torch.uint8, device=A.val.device)
+        if gid is None:
+            gid = torch.empty(_lib().svt_dev_rowsum_gid_bytes(A.handle), dtype=torch.uint8, device=A.val.device)
+        assert gid.dtype == torch.uint8 and gid.is_contiguous() and gid.is_cuda
+        self.gid = gid
         _check(_lib().svt_dev_rowsum_prepare(A.handle, group.data_ptr(), self.ngroup, self.gid.data_ptr(),
                                              self.gid.numel(), _stream()))
 

@@ -524,3 +524,14 @@ def rowsum_cells(col_ptr, row_idx, val, group0, ngroup, na_rm=False):
     cell = group0[np.asarray(row_idx, dtype=np.int64)] + ngroup * col
     size = np.bincount(group0, minlength=ngroup).astype(np.int64)
     return Cells(val, cell, ngroup * ncol, np.tile(size, ncol), na_rm, False)
+
+
+def colsum_cells(col_ptr, row_idx, val, group0, ngroup, nrow, na_rm=False):
+    """colsum(): cell (i, g) = i + nrow * g holds row i of the columns in group g (0-based ``group0``, one per column)."""
+    col_ptr = np.asarray(col_ptr, dtype=np.int64)
+    ncol = len(col_ptr) - 1
+    col = np.repeat(np.arange(ncol, dtype=np.int64), np.diff(col_ptr))
+    group0 = np.asarray(group0, dtype=np.int64)
+    cell = np.asarray(row_idx, dtype=np.int64) + nrow * group0[col]
+    size = np.bincount(group0, minlength=ngroup).astype(np.int64)
+    return Cells(val, cell, nrow * ngroup, np.repeat(size, nrow), na_rm, False)
