@@ -420,6 +420,39 @@ struct DevBuf {
 	template <typename T> T *as() { return (T *) p; }
 };
 
+// The device word a launch raises (warn, overflow, workspace too small), zeroed.  read() ORs it into a host flag;
+// what a raised flag means is the caller's business.
+struct DevFlag {
+	DevBuf W;
+	int init() { return W.alloc(16) || W.zero(); }
+	int *ptr() { return W.as<int>(); }
+	int read(int *into)
+	{
+		int w = 0;
+		HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
+		if (w) *into = 1;
+		return 0;
+	}
+};
+
+static void split_dims(const svt_view *x, int dims, int64_t *inner, int64_t *outer)
+{
+	*inner = *outer = 1;
+	for (int a = 1; a < dims; a++) *inner *= x->dim[a];
+	for (int a = dims; a < x->ndim; a++) *outer *= x->dim[a];
+}
+
+// The view of `n` empty segments on the structure of A: what a statistic over zero-extent dims summarizes, once per
+// result.  P holds the offsets; a NULL col_ptr in the answer says that they could not be uploaded.
+static svt_dev_csc empty_segments(const svt_dev_csc *A, int64_t n, DevBuf &P)
+{
+	const std::vector<int64_t> cp((size_t) n + 1, 0);
+	svt_dev_csc E = *A;
+	E.owned = 0; E.ncol = n; E.nnz = 0; E.nrow = 0;
+	E.col_ptr = P.upload(cp.data(), cp.size() * 8) ? NULL : P.as<int64_t>();
+	return E;
+}
+
 // ---- SVT -> CSC marshal ----------------------------------------------------------
 static size_t elt_size(int Rtype) { return Rtype == SVT_REALSXP ? 8 : 4; }
 
@@ -2344,6 +2377,31 @@ struct OwnedCsc {            // a handle, released with this object only if this
 };
 static OwnedCsc transposed_for(const CscGuard &A);
 
+// The operand of a 2-D col/row method pair (medians, quantiles, MADs, ranks).  check(): stopifnot_2D_object()
+// (R/SparseArray-matrixStats.R:51-57), then the type and background rules, which name the col method for either call.
+// The object puts x on the device, resident or uploaded, and gives M, the operand whose columns are worked on: x, or
+// for the row method t(x) built on the device (rowMedians(x) = colMedians(t(x)), :802-815).  M == NULL: error set.
+struct ColOperand {
+	CscGuard A;
+	OwnedCsc T;
+	const svt_dev_csc *M;
+	ColOperand(const svt_view *x, int by_row)
+		: A(x), T(by_row && A.h ? transposed_for(A) : OwnedCsc(NULL, false)), M(by_row ? T.t : A.h) {}
+	static int check(const svt_view *x, int by_row, const char *col, const char *row)
+	{
+		if (ensure_init() || check_view(x))
+			return -1;
+		if (x->ndim != 2)
+			return svt_set_error("the %s() method for SparseArray objects only supports 2D "
+					     "objects (i.e. SparseMatrix objects) at the moment", by_row ? row : col);
+		if (x->Rtype != SVT_REALSXP && x->Rtype != SVT_INTSXP && x->Rtype != SVT_LGLSXP)
+			return svt_set_error("%s(): unsupported type", col);
+		if (x->na_background)
+			return svt_set_error("%s() is not supported on NaArray objects", col);
+		return 0;
+	}
+};
+
 // The sparse-aware route (kernels_gram.hip) multiplies only the pairs of nonzeros that meet in a row -- about
 // nnz(x) * nnz(y) / nrow of them (half that for the unary form), each an LDS atomic behind a gathered 12-byte read --
 // where the dense-buffer route below does `dense_ops` multiply-adds (the reference's Lpp_nops / Rpp_nops,
@@ -2902,18 +2960,15 @@ extern "C" int svt_tcrossprod2_SVT_SVT(const svt_view *x, const svt_view *y, dou
 static int run_colstats(const svt_dev_csc *A, int opcode, int na_rm, double center,
 			int64_t inner, void *out_host, int out_Rtype, int *warn)
 {
-	const int64_t nseg = A->ncol / inner;
-	const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
-	DevBuf O, W;
-	if (O.alloc((size_t) nseg * osz) || W.alloc(16) || W.zero())
+	const size_t out_bytes = (size_t) (A->ncol / inner) * elt_size(out_Rtype);
+	DevBuf O;
+	DevFlag W;
+	if (O.alloc(out_bytes) || W.init())
 		return -1;
-	if (svt_dev_colstats(A, opcode, na_rm, center, inner, O.p, W.as<int>(), 0))
+	if (svt_dev_colstats(A, opcode, na_rm, center, inner, O.p, W.ptr(), 0))
 		return -1;
-	int w = 0;
-	HIP_TRY(hipMemcpy(out_host, O.p, (size_t) nseg * osz, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
-	if (w) *warn = 1;
-	return 0;
+	HIP_TRY(hipMemcpy(out_host, O.p, out_bytes, hipMemcpyDeviceToHost));
+	return W.read(warn);
 }
 
 // A leaf-range statistic over the device list: shard s takes the units [u0, u1) -- leaves [u0 * unit, u1 * unit),
@@ -2950,31 +3005,24 @@ static int colStats_SVT_impl(const svt_view *x, int opcode, int na_rm, double ce
 		return svt_set_error("'dims' must be >= 1 and <= %d", x->ndim);
 	if (device_op_supported(opcode))
 		return -1;
-	int64_t inner = 1, nout = 1;
-	for (int a = 1; a < dims; a++) inner *= x->dim[a];
-	for (int a = dims; a < x->ndim; a++) nout *= x->dim[a];
+	int64_t inner, nout;
+	split_dims(x, dims, &inner, &nout);
 	if (nout == 0)
 		return 0;
 	const int out_Rtype = svt_colStats_out_Rtype(opcode, x->Rtype);
 	if (inner > 0 && shard_applies(x)) {      // shard s: output cells [g0, ...)
-		const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
+		const size_t osz = elt_size(out_Rtype);
 		return run_leaf_shards(x, inner, nout, warn, [&](const svt_dev_csc *A, int64_t g0, int *w) {
 			return run_colstats(A, opcode, na_rm, center, inner, (char *) out + (size_t) g0 * osz, out_Rtype, w);
 		});
 	}
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	if (inner == 0) {
-		// zero-extent inner dims: every result summarizes an empty vector.
-		// One empty leaf per result gives exactly that.
-		std::vector<int64_t> cp((size_t) nout + 1, 0);
-		DevBuf P;
-		if (P.upload(cp.data(), cp.size() * 8)) return -1;
-		svt_dev_csc E = *A.h;
-		E.owned = 0; E.ncol = nout; E.nnz = 0; E.nrow = 0; E.col_ptr = P.as<int64_t>();
-		return run_colstats(&E, opcode, na_rm, center, 1, out, out_Rtype, warn);
-	}
-	return run_colstats(A.h, opcode, na_rm, center, inner, out, out_Rtype, warn);
+	if (inner > 0)
+		return run_colstats(A.h, opcode, na_rm, center, inner, out, out_Rtype, warn);
+	DevBuf P;       // zero-extent inner dims: every result summarizes an empty vector
+	const svt_dev_csc E = empty_segments(A.h, nout, P);
+	return E.col_ptr ? run_colstats(&E, opcode, na_rm, center, 1, out, out_Rtype, warn) : -1;
 }
 extern "C" int svt_colStats_SVT(const svt_view *x, int opcode, int na_rm, double center,
 				int dims, void *out, int *warn)
@@ -2992,18 +3040,9 @@ static int order_stat_SVT(const svt_view *x, int what, const double *vec, int np
 			  int by_row, double *out)
 {
 	const bool quant = what == ORDER_QUANTILES;
-	const char *col = order_stat_names[what][0];
 	const double *probs = vec;
-	if (ensure_init() || check_view(x))
+	if (ColOperand::check(x, by_row, order_stat_names[what][0], order_stat_names[what][1]))
 		return -1;
-	if (x->ndim != 2)       // stopifnot_2D_object(), R/SparseArray-matrixStats.R:51-57
-		return svt_set_error("the %s() method for SparseArray objects only supports 2D "
-				     "objects (i.e. SparseMatrix objects) at the moment",
-				     order_stat_names[what][by_row ? 1 : 0]);
-	if (x->Rtype != SVT_REALSXP && x->Rtype != SVT_INTSXP && x->Rtype != SVT_LGLSXP)
-		return svt_set_error("%s(): unsupported type", col);
-	if (x->na_background)
-		return svt_set_error("%s() is not supported on NaArray objects", col);
 	if (quant) {
 		if (nprobs < 0 || (nprobs > 0 && probs == NULL))
 			return svt_set_error("invalid 'probs'");
@@ -3014,13 +3053,9 @@ static int order_stat_SVT(const svt_view *x, int what, const double *vec, int np
 	const int64_t nout = x->dim[by_row ? 0 : 1];
 	if (nout == 0 || (quant && nprobs == 0))
 		return 0;
-	CscGuard A(x);
-	if (A.h == NULL) return -1;
-	// rowMedians(x) = colMedians(t(x)), :802-815, rowQuantiles(x) = colQuantiles(t(x)) and rowMads(x) = colMads(t(x));
-	// t() on the device
-	const OwnedCsc T = by_row ? transposed_for(A) : OwnedCsc(NULL, false);
-	if (by_row && T.t == NULL) return -1;
-	const svt_dev_csc *M = by_row ? T.t : A.h;
+	const ColOperand X(x, by_row);
+	const svt_dev_csc *M = X.M;
+	if (M == NULL) return -1;
 	DevBuf P, O, W;
 	const size_t out_bytes = (size_t) nout * (quant ? (size_t) nprobs : 1) * 8;
 	const size_t vec_bytes = quant ? (size_t) nprobs * 8 : what == ORDER_MADS && vec ? (size_t) nout * 8 : 0;
@@ -3097,24 +3132,15 @@ static void expand_ranks(const int64_t *cp, const int32_t *ri, const R *rank_nz,
 
 static int ranks_SVT(const svt_view *x, int ties, int preserve_shape, int by_row, void *out)
 {
-	if (ensure_init() || check_view(x))
+	if (ColOperand::check(x, by_row, "colRanks", "rowRanks"))
 		return -1;
-	if (x->ndim != 2)
-		return svt_set_error("the %s() method for SparseArray objects only supports 2D "
-				     "objects (i.e. SparseMatrix objects) at the moment", by_row ? "rowRanks" : "colRanks");
-	if (x->Rtype != SVT_REALSXP && x->Rtype != SVT_INTSXP && x->Rtype != SVT_LGLSXP)
-		return svt_set_error("colRanks(): unsupported type");
-	if (x->na_background)
-		return svt_set_error("colRanks() is not supported on NaArray objects");
 	if (check_ties(ties))
 		return -1;
 	if (x->dim[0] == 0 || x->dim[1] == 0)
 		return 0;                                       // zero extents: no cell to write
-	CscGuard A(x);
-	if (A.h == NULL) return -1;
-	const OwnedCsc T = by_row ? transposed_for(A) : OwnedCsc(NULL, false);
-	if (by_row && T.t == NULL) return -1;
-	const svt_dev_csc *M = by_row ? T.t : A.h;
+	const ColOperand X(x, by_row);
+	const svt_dev_csc *M = X.M;
+	if (M == NULL) return -1;
 	const int64_t mrow = M->nrow, mcol = M->ncol, nnz = M->nnz;
 	if (mcol > 0x7FFFFFFFLL)
 		return svt_set_unsupported("colRanks: more than 2^31-1 columns");
@@ -3131,14 +3157,15 @@ static int ranks_SVT(const svt_view *x, int ties, int preserve_shape, int by_row
 		return svt_set_unsupported("colRanks: 2^32 or more stored values in the columns sorted in the workspace");
 	const size_t esz = ties == SVT_TIES_AVERAGE ? 8 : 4;
 	const size_t wsb = ranks_ws_bytes(mcol, long_nnz);
-	DevBuf RN, RZ, F, W;
-	if (RN.alloc((size_t) nnz * esz) || RZ.alloc((size_t) mcol * esz) || F.alloc(sizeof(int)) || W.alloc(wsb))
+	DevBuf RN, RZ, W;
+	DevFlag F;
+	if (RN.alloc((size_t) nnz * esz) || RZ.alloc((size_t) mcol * esz) || F.init() || W.alloc(wsb))
 		return -1;
-	if (launch_ranks(M->col_ptr, M->val, M->Rtype, mrow, mcol, nnz, ties, RN.p, RZ.p, F.as<int>(), W.p, wsb, 0))
+	if (launch_ranks(M->col_ptr, M->val, M->Rtype, mrow, mcol, nnz, ties, RN.p, RZ.p, F.ptr(), W.p, wsb, 0))
 		return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	int flag = 0;
-	HIP_TRY(hipMemcpy(&flag, F.p, sizeof(int), hipMemcpyDeviceToHost));
+	if (F.read(&flag)) return -1;
 	if (flag)
 		return svt_set_error("colRanks: the workspace did not hold the long columns");
 	std::vector<char> rn((size_t) nnz * esz), rz((size_t) mcol * esz);
@@ -3181,14 +3208,12 @@ static int summarize_SVT_impl(const svt_view *x, int opcode, int na_rm, double c
 	if (A.h == NULL) return -1;
 	svt_dev_csc V = *A.h;      // the whole array as one generalized column
 	V.owned = 0;
-	int64_t inner = V.ncol;
 	DevBuf P;
-	if (inner == 0) {          // some outer dim is 0: one empty segment
-		int64_t cp[2] = {0, 0};
-		if (P.upload(cp, sizeof(cp))) return -1;
-		V.ncol = 1; V.nrow = 0; V.nnz = 0; V.col_ptr = P.as<int64_t>();
-		inner = 1;
+	if (V.ncol == 0) {         // some outer dim is 0: one empty segment
+		V = empty_segments(A.h, 1, P);
+		if (V.col_ptr == NULL) return -1;
 	}
+	const int64_t inner = V.ncol;
 	const int ops[2] = { opcode == SVT_OP_RANGE ? SVT_OP_MIN : opcode, SVT_OP_MAX };
 	const int nops = opcode == SVT_OP_RANGE ? 2 : 1;
 	for (int t = 0; t < nops; t++) {
@@ -3208,100 +3233,31 @@ extern "C" int svt_summarize_SVT(const svt_view *x, int opcode, int na_rm, doubl
 	return abi_status([&] { return summarize_SVT_impl(x, opcode, na_rm, center, out_d, out_i, out_Rtype, warn); });
 }
 
-// C_rowStats_SVT, src/SparseArray_matrixStats.c:1121-1205
-static int rowStats_SVT_impl(const svt_view *x, int opcode, int na_rm,
-				const double *center, int dims, void *out, int *warn)
+// C_rowStats_SVT, src/SparseArray_matrixStats.c:1121-1205 (six_only: its six operations), and every row statistic
+// the R API offers in one call (svt_rowStatsFull_SVT: thirteen).  The checks and the constant fill, one operand on the
+// device (the resident cache applies), dev_rowstats_impl, one download.  Not sharded over the device list.
+static int rowStats_SVT_impl(const svt_view *x, int opcode, int na_rm, const double *center, int dims, bool six_only,
+			     void *out, int *warn)
 {
 	*warn = 0;
 	if (ensure_init() || check_view(x) || check_stat_op(opcode, x->Rtype))
 		return -1;
 	if (dims < 1 || dims > x->ndim - 1)
 		return svt_set_error("'dims' must be >= 1 and <= %d", x->ndim - 1);
-	if (x->na_background && opcode == SVT_OP_CENTERED_X2_SUM)   // :639-642
-		return svt_set_error("operation not yet supported on NaArray objects");
-	if (opcode != SVT_OP_COUNTNAS && opcode != SVT_OP_ANYNA &&
-	    opcode != SVT_OP_MIN && opcode != SVT_OP_MAX &&
-	    opcode != SVT_OP_SUM && opcode != SVT_OP_CENTERED_X2_SUM)
+	if (six_only && !rowstats_reference_op(opcode))
 		return svt_set_error("SparseArray internal error in C_rowStats_SVT():\n"
 				     "    operation not supported");
-	const int out_Rtype = svt_colStats_out_Rtype(opcode, x->Rtype);
-	const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
-	int64_t inner = 1, nstrata = 1;
-	for (int a = 1; a < dims; a++) inner *= x->dim[a];
-	for (int a = dims; a < x->ndim; a++) nstrata *= x->dim[a];
-	const int64_t out_len = inner * x->dim[0];
-	if (out_len == 0)
-		return 0;
-	if ((opcode == SVT_OP_MIN || opcode == SVT_OP_MAX) && nstrata == 0) {
-		// constant fill, :970-982
-		for (int64_t i = 0; i < out_len; i++) {
-			if (out_Rtype == SVT_REALSXP)
-				((double *) out)[i] = opcode == SVT_OP_MIN ? INFINITY : -INFINITY;
-			else
-				((int *) out)[i] = NA_INT;
-		}
-		if (out_Rtype != SVT_REALSXP) *warn = 1;
-		return 0;
-	}
-	if (nstrata > 0xFFFFFFFFLL)
-		return svt_set_unsupported("too many strata for the device coverage counters");
-	CscGuard A(x);
-	if (A.h == NULL) return -1;
-	DevBuf O, C, S, W;
-	if (O.alloc((size_t) out_len * osz) ||
-	    S.alloc(rowstats_scratch_bytes(opcode, out_len)) ||
-	    W.alloc(16) || W.zero())
-		return -1;
-	if (center != NULL && C.upload(center, (size_t) out_len * 8))
-		return -1;
-	RowStatsArgs a = rowstats_args(A.h, opcode, na_rm, inner, nstrata, O.p);
-	a.center = center ? C.as<double>() : NULL;
-	a.scratch = S.p; a.warn_flag = W.as<int>();
-	if (a.na_bg && inner > 65535)
-		return svt_set_unsupported("row statistics of NaArray objects: more than 65535 output columns");
-	if (inner <= 65535) {
-		DevBuf T;
-		if (T.alloc(rowstats_panel_ws_bytes(a.nrow, a.ncol)) || launch_rowstats_panel(a, T.p, 0))
-			return -1;
-		HIP_TRY(hipDeviceSynchronize());
-	} else if (launch_rowstats(a, 0)) {
-		return -1;
-	}
-	int w = 0;
-	if (staged_download(out, O.p, (size_t) out_len * osz)) return -1;
-	HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
-	if (w) *warn = 1;
-	return 0;
-}
-extern "C" int svt_rowStats_SVT(const svt_view *x, int opcode, int na_rm,
-				const double *center, int dims, void *out, int *warn)
-{
-	return abi_status([&] { return rowStats_SVT_impl(x, opcode, na_rm, center, dims, out, warn); });
-}
-
-// Every row statistic the R API offers in one call: the checks and constant fills of rowStats_SVT_impl, one
-// operand on the device (the resident cache applies), svt_dev_rowstats, one download.  Not sharded over the device list.
-static int rowStatsFull_SVT_impl(const svt_view *x, int opcode, int na_rm,
-				 const double *center, int dims, void *out, int *warn)
-{
-	*warn = 0;
-	if (ensure_init() || check_view(x) || check_stat_op(opcode, x->Rtype))
-		return -1;
-	if (dims < 1 || dims > x->ndim - 1)
-		return svt_set_error("'dims' must be >= 1 and <= %d", x->ndim - 1);
-	if (check_rowstats_op(opcode, x->Rtype, x->na_background))
+	if (check_rowstats_op(opcode, x->Rtype, x->na_background))       // (the NaArray rules, :639-642)
 		return -1;
 	const bool range = opcode == SVT_OP_RANGE;
 	const int out_Rtype = svt_colStats_out_Rtype(opcode, x->Rtype);
-	const size_t osz = out_Rtype == SVT_REALSXP ? 8 : 4;
-	int64_t inner = 1, nstrata = 1;
-	for (int a = 1; a < dims; a++) inner *= x->dim[a];
-	for (int a = dims; a < x->ndim; a++) nstrata *= x->dim[a];
+	int64_t inner, nstrata;
+	split_dims(x, dims, &inner, &nstrata);
 	const int64_t out_len = inner * x->dim[0], nout = out_len * (range ? 2 : 1);
 	if (out_len == 0)
 		return 0;
 	if ((opcode == SVT_OP_MIN || opcode == SVT_OP_MAX || range) && nstrata == 0) {
-		// constant fill, :970-982
+		// constant fill, :970-982 (range: the minima, then the maxima)
 		for (int64_t i = 0; i < nout; i++) {
 			if (out_Rtype == SVT_REALSXP)
 				((double *) out)[i] = (range ? i < out_len : opcode == SVT_OP_MIN) ? INFINITY : -INFINITY;
@@ -3311,34 +3267,37 @@ static int rowStatsFull_SVT_impl(const svt_view *x, int opcode, int na_rm,
 		if (out_Rtype != SVT_REALSXP) *warn = 1;
 		return 0;
 	}
+	// (what dev_rowstats_impl refuses, before the operand is uploaded)
 	if (nstrata > 0xFFFFFFFFLL)
 		return svt_set_unsupported("too many strata for the device coverage counters");
 	if (inner > 65535 && x->na_background)
 		return svt_set_unsupported("row statistics of NaArray objects: more than 65535 output columns");
-	if (inner > 65535 && !rowstats_reference_op(opcode))      // (before the operand is uploaded)
+	if (inner > 65535 && !rowstats_reference_op(opcode))
 		return svt_set_unsupported("row statistics: this operation is not served with more than 65535 output columns");
 	CscGuard A(x);
 	if (A.h == NULL) return -1;
-	DevBuf O, C, W, T;
-	if (O.alloc((size_t) nout * osz) || W.alloc(16) || W.zero() ||
-	    T.alloc(svt_dev_rowstats_ws_bytes_op(A.h, opcode, inner)))
+	const size_t out_bytes = (size_t) nout * elt_size(out_Rtype), ws_bytes = svt_dev_rowstats_ws_bytes_op(A.h, opcode, inner);
+	DevBuf O, C, T;
+	DevFlag W;
+	if (O.alloc(out_bytes) || W.init() || T.alloc(ws_bytes))
 		return -1;
 	if (center != NULL && C.upload(center, (size_t) out_len * 8))
 		return -1;
-	if (dev_rowstats_impl(A.h, opcode, na_rm, center ? C.as<double>() : NULL, inner, O.p, W.as<int>(), T.p,
-			      svt_dev_rowstats_ws_bytes_op(A.h, opcode, inner), 0))
+	if (dev_rowstats_impl(A.h, opcode, na_rm, center ? C.as<double>() : NULL, inner, O.p, W.ptr(), T.p, ws_bytes, 0))
 		return -1;
 	HIP_TRY(hipDeviceSynchronize());
-	int w = 0;
-	if (staged_download(out, O.p, (size_t) nout * osz)) return -1;
-	HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
-	if (w) *warn = 1;
-	return 0;
+	if (staged_download(out, O.p, out_bytes)) return -1;
+	return W.read(warn);
+}
+extern "C" int svt_rowStats_SVT(const svt_view *x, int opcode, int na_rm,
+				const double *center, int dims, void *out, int *warn)
+{
+	return abi_status([&] { return rowStats_SVT_impl(x, opcode, na_rm, center, dims, true, out, warn); });
 }
 extern "C" int svt_rowStatsFull_SVT(const svt_view *x, int opcode, int na_rm,
 				    const double *center, int dims, void *out, int *warn)
 {
-	return abi_status([&] { return rowStatsFull_SVT_impl(x, opcode, na_rm, center, dims, out, warn); });
+	return abi_status([&] { return rowStats_SVT_impl(x, opcode, na_rm, center, dims, false, out, warn); });
 }
 
 // ==================================================================================
@@ -3372,18 +3331,16 @@ static int groupsum_host(const svt_dev_csc *A, const int32_t *col_ptr32,
 	const size_t osz = elt_size(A->Rtype);
 	if (out_len == 0)
 		return 0;
-	DevBuf G, O, S, W;
+	DevBuf G, O, S;
+	DevFlag W;
 	if (G.upload(group, (size_t) glen * 4) || O.alloc((size_t) out_len * osz) ||
-	    S.alloc(groupsum_scratch_bytes(A->Rtype, out_len)) || W.alloc(16) || W.zero())
+	    S.alloc(groupsum_scratch_bytes(A->Rtype, out_len)) || W.init())
 		return -1;
 	GroupSumArgs a = groupsum_args(A, col_ptr32, G.as<int>(), ngroup, na_rm, O.p);
-	a.scratch = S.p; a.ovflow_flag = W.as<int>();
+	a.scratch = S.p; a.ovflow_flag = W.ptr();
 	if (colsum ? launch_colsum(a, 0) : launch_rowsum(a, 0)) return -1;
-	int w = 0;
 	if (staged_download(out, O.p, (size_t) out_len * osz)) return -1;
-	HIP_TRY(hipMemcpy(&w, W.p, 4, hipMemcpyDeviceToHost));
-	if (ovflow && w) *ovflow = 1;
-	return 0;
+	return W.read(ovflow);
 }
 
 static int xsum_SVT(const svt_view *x, const int *group, int ngroup, int na_rm,
@@ -3444,7 +3401,8 @@ static int xsum_dgC(int nrow, int ncol, const double *xx, const int *xi, const i
 	memset(&D, 0, sizeof(D));
 	D.Rtype = SVT_REALSXP; D.nrow = nrow; D.ncol = ncol; D.nnz = nnz;
 	D.row_idx = I.as<int32_t>(); D.val = X.p;
-	return groupsum_host(&D, P.as<int32_t>(), group, ngroup, na_rm, colsum, out, NULL);
+	int ovflow = 0;                     // (doubles: never raised)
+	return groupsum_host(&D, P.as<int32_t>(), group, ngroup, na_rm, colsum, out, &ovflow);
 }
 
 // C_rowsum_dgCMatrix / C_colsum_dgCMatrix, src/rowsum_methods.c:328-356, 404-439
@@ -3496,19 +3454,10 @@ static int colstat_dgC(int nrow, int ncol, const double *xx, const int *xp, int 
 	memset(&A, 0, sizeof(A));
 	A.Rtype = SVT_REALSXP; A.nrow = nrow; A.ncol = ncol; A.nnz = nnz;
 	A.col_ptr = P.as<int64_t>(); A.val = X.p;
-	const double NA = svt_na_real();
-	int rc;
-	switch (which) {
-	case 0: rc = dev_colstats_ex(&A, SVT_OP_MIN, na_rm, NA, 1, O.p, NULL, 0, 1); break;
-	case 1: rc = dev_colstats_ex(&A, SVT_OP_MAX, na_rm, NA, 1, O.p, NULL, 0, 1); break;
-	case 2:
-		rc = dev_colstats_ex(&A, SVT_OP_MIN, na_rm, NA, 1, O.p, NULL, 0, 1);
-		if (rc == 0)
-			rc = dev_colstats_ex(&A, SVT_OP_MAX, na_rm, NA, 1, O.as<double>() + ncol, NULL, 0, 1);
-		break;
-	default: rc = dev_colstats_ex(&A, SVT_OP_VAR1, na_rm, NA, 1, O.p, NULL, 0, 1); break;
-	}
-	if (rc) return -1;
+	static const int ops[4][2] = { { SVT_OP_MIN, -1 }, { SVT_OP_MAX, -1 }, { SVT_OP_MIN, SVT_OP_MAX }, { SVT_OP_VAR1, -1 } };
+	for (int t = 0; t < 2 && ops[which][t] >= 0; t++)
+		if (dev_colstats_ex(&A, ops[which][t], na_rm, svt_na_real(), 1, O.as<double>() + (size_t) t * ncol, NULL, 0, 1))
+			return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	return staged_download(out, O.p, (size_t) ncol * 8 * (which == 2 ? 2 : 1));
 }
