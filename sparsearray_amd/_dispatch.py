@@ -17,7 +17,7 @@ import numpy as np
 
 from ._abi import PROTOTYPES
 from .api import OPCODES, TIES_METHODS, SparseArrayError, SparseArrayUnsupported, naked_result
-from .svt import INTSXP, LGLSXP, REALSXP, SVT_SparseArray, make_view, r_type_of
+from .svt import INTSXP, LGLSXP, REALSXP, SVT_SparseArray, make_view, r_type_of, svt_view
 
 _RT = {"logical": LGLSXP, "integer": INTSXP, "double": REALSXP}
 
@@ -54,6 +54,25 @@ class CAbiDispatcher:
             msg = self._fn("last_error")()
             raise (SparseArrayUnsupported if rc > 0 else SparseArrayError)(msg.decode() if msg else f"error {rc}")
 
+    def _run(self, name, *args):
+        """<prefix><name>(*args) with the status checked.  An SVT_SparseArray goes over as a pointer to its leaf table
+        (which lives as long as the call), a numpy array as its address; anything else as it is."""
+        args = [make_view(a) if isinstance(a, SVT_SparseArray) else a for a in args]
+        self._check(self._fn(name)(*[byref(a) if isinstance(a, svt_view) else _ptr(a) if isinstance(a, np.ndarray) else a
+                                     for a in args]))
+
+    def _csc_result(self, x, new_dim, nnz, dimnames, fill):
+        """The SVT_SparseArray of ``new_dim`` whose ``nnz`` nonzeros ``fill(col_ptr, row_idx, val)`` writes in the CSC
+        layout (an array of no nonzeros is handed over as one unread element), its leaves rebuilt the way the glue
+        rebuilds the R leaves; the type and the background are those of ``x``."""
+        cp = np.zeros(int(np.prod(new_dim[1:], dtype=np.int64)) + 1, dtype=np.int64)
+        ri = np.zeros(max(nnz, 1), dtype=np.int32)
+        vv = np.zeros(max(nnz, 1), dtype=x.np_dtype)
+        fill(cp, ri, vv)
+        ans = SVT_SparseArray.from_csc(new_dim, x.type, cp, ri[:nnz], vv[:nnz], dimnames=dimnames)
+        ans.na_background = x.na_background
+        return ans
+
     # -- dispatcher ------------------------------------------------------------
     def __call__(self, name: str, *args):
         if not name.startswith("C_"):
@@ -71,52 +90,58 @@ class CAbiDispatcher:
         """Returns the previous value (the reference returns it too, R/thread-control.R:60-66)."""
         return int(self._fn("set_max_threads")(int(nthread)))
 
-    # crossprod ---------------------------------------------------------------
+    # crossprod / %*% / tcrossprod: a double matrix of ``shape``, column-major; the operands and flags in the C order, a
+    # dense operand as (address, nrow, ncol, Rtype) --------------------------------------------------------------------
+    def _product(self, name, shape, *args):
+        out = np.zeros(shape, dtype=np.float64, order="F")
+        flat = [b for a in args for b in ((a, a.shape[0], a.shape[1], _RT[r_type_of(a)]) if isinstance(a, np.ndarray)
+                                          else (a,))]
+        self._run(name, *flat, out)
+        return out
+
     def C_crossprod2_SVT_mat(self, x: SVT_SparseArray, y: np.ndarray, tr_y: bool):
         y = _F(y)
-        ans_ncol = y.shape[0] if tr_y else y.shape[1]
-        out = np.zeros((x.dim[1], ans_ncol), dtype=np.float64, order="F")
-        xv = make_view(x)
-        self._check(self._fn("crossprod2_SVT_mat")(
-            byref(xv), _ptr(y), y.shape[0], y.shape[1], _RT[r_type_of(y)],
-            int(tr_y), _ptr(out)))
-        return out
+        return self._product("crossprod2_SVT_mat", (x.dim[1], y.shape[0 if tr_y else 1]), x, y, int(tr_y))
 
     def C_crossprod2_mat_SVT(self, x: np.ndarray, y: SVT_SparseArray, tr_x: bool):
         x = _F(x)
-        ans_nrow = x.shape[0] if tr_x else x.shape[1]
-        out = np.zeros((ans_nrow, y.dim[1]), dtype=np.float64, order="F")
-        yv = make_view(y)
-        self._check(self._fn("crossprod2_mat_SVT")(
-            _ptr(x), x.shape[0], x.shape[1], _RT[r_type_of(x)], byref(yv),
-            int(tr_x), _ptr(out)))
-        return out
+        return self._product("crossprod2_mat_SVT", (x.shape[0 if tr_x else 1], y.dim[1]), x, y, int(tr_x))
 
     def C_crossprod2_SVT_SVT(self, x: SVT_SparseArray, y: SVT_SparseArray):
-        out = np.zeros((x.dim[1], y.dim[1]), dtype=np.float64, order="F")
-        xv, yv = make_view(x), make_view(y)
-        self._check(self._fn("crossprod2_SVT_SVT")(byref(xv), byref(yv), _ptr(out)))
-        return out
+        return self._product("crossprod2_SVT_SVT", (x.dim[1], y.dim[1]), x, y)
+
+    def C_crossprod1_SVT(self, x: SVT_SparseArray):
+        return self._product("crossprod1_SVT", (x.dim[1], x.dim[1]), x)
+
+    def C_matmul_SVT_mat(self, x: SVT_SparseArray, y: np.ndarray):
+        y = _F(y)
+        return self._product("matmul_SVT_mat", (x.dim[0], y.shape[1]), x, y)
+
+    def C_matmul_SVT_SVT(self, x: SVT_SparseArray, y: SVT_SparseArray):
+        return self._product("matmul_SVT_SVT", (x.dim[0], y.dim[1]), x, y)
+
+    def C_tcrossprod1_SVT(self, x: SVT_SparseArray):
+        return self._product("tcrossprod1_SVT", (x.dim[0], x.dim[0]), x)
+
+    def C_tcrossprod2_SVT_SVT(self, x: SVT_SparseArray, y: SVT_SparseArray):
+        return self._product("tcrossprod2_SVT_SVT", (x.dim[0], y.dim[0]), x, y)
 
     # colMedians (R/SparseArray-matrixStats.R:761-784) --------------------------------
     def C_colMedians_SVT(self, x: SVT_SparseArray, na_rm: bool):
         out = np.zeros(x.dim[1] if x.ndim == 2 else 0, dtype=np.float64)
-        xv = make_view(x)
-        self._check(self._fn("colMedians_SVT")(byref(xv), int(bool(na_rm)), _ptr(out)))
+        self._run("colMedians_SVT", x, int(bool(na_rm)), out)
         return out
 
     def C_rowMedians_SVT(self, x: SVT_SparseArray, na_rm: bool):
         out = np.zeros(x.dim[0] if x.ndim == 2 else 0, dtype=np.float64)
-        xv = make_view(x)
-        self._check(self._fn("rowMedians_SVT")(byref(xv), int(bool(na_rm)), _ptr(out)))
+        self._run("rowMedians_SVT", x, int(bool(na_rm)), out)
         return out
 
     # colQuantiles / rowQuantiles, type 7 (include/svt_hip.h; HIP library only) ----
     def _quantiles(self, fname, x, probs, na_rm, nout):
         probs = np.ascontiguousarray(probs, dtype=np.float64)
         out = np.zeros((nout, probs.size), dtype=np.float64, order="F")
-        xv = make_view(x)
-        self._check(self._fn(fname)(byref(xv), _ptr(probs), int(probs.size), int(bool(na_rm)), _ptr(out)))
+        self._run(fname, x, probs, int(probs.size), int(bool(na_rm)), out)
         return out
 
     def C_colQuantiles_SVT(self, x: SVT_SparseArray, probs, na_rm: bool):
@@ -134,9 +159,7 @@ class CAbiDispatcher:
                 raise SparseArrayError("'center' must be NULL, a single number, or a vector with one element per "
                                        + ("column" if axis == 1 else "row"))
         out = np.zeros(nout, dtype=np.float64)
-        xv = make_view(x)
-        self._check(self._fn(fname)(byref(xv), None if center is None else _ptr(center), float(constant),
-                                    int(bool(na_rm)), _ptr(out)))
+        self._run(fname, x, center, float(constant), int(bool(na_rm)), out)
         return out
 
     def C_colMads_SVT(self, x: SVT_SparseArray, center, constant: float, na_rm: bool):
@@ -156,19 +179,17 @@ class CAbiDispatcher:
 
     def C_colRanks_SVT(self, x: SVT_SparseArray, ties, preserve_shape: bool):
         code, out = self._ranks_out(x, ties, not preserve_shape)
-        xv = make_view(x)
-        self._check(self._fn("colRanks_SVT")(byref(xv), code, int(bool(preserve_shape)), _ptr(out)))
+        self._run("colRanks_SVT", x, code, int(bool(preserve_shape)), out)
         return out
 
     def C_rowRanks_SVT(self, x: SVT_SparseArray, ties):
         code, out = self._ranks_out(x, ties, False)
-        xv = make_view(x)
-        self._check(self._fn("rowRanks_SVT")(byref(xv), code, _ptr(out)))
+        self._run("rowRanks_SVT", x, code, out)
         return out
 
     # resident operands (include/svt_hip.h; HIP library only) --------------------
     def resident_set_limit(self, nbytes: int):
-        self._check(self._fn("resident_set_limit")(int(nbytes)))
+        self._run("resident_set_limit", int(nbytes))
 
     def resident_clear(self):
         self._fn("resident_clear")()
@@ -187,38 +208,6 @@ class CAbiDispatcher:
     def has_entry(self, name: str) -> bool:
         return hasattr(self.lib, self.prefix + name[2:])
 
-    def C_matmul_SVT_mat(self, x: SVT_SparseArray, y: np.ndarray):
-        y = _F(y)
-        out = np.zeros((x.dim[0], y.shape[1]), dtype=np.float64, order="F")
-        xv = make_view(x)
-        self._check(self._fn("matmul_SVT_mat")(
-            byref(xv), _ptr(y), y.shape[0], y.shape[1], _RT[r_type_of(y)], _ptr(out)))
-        return out
-
-    def C_matmul_SVT_SVT(self, x: SVT_SparseArray, y: SVT_SparseArray):
-        out = np.zeros((x.dim[0], y.dim[1]), dtype=np.float64, order="F")
-        xv, yv = make_view(x), make_view(y)
-        self._check(self._fn("matmul_SVT_SVT")(byref(xv), byref(yv), _ptr(out)))
-        return out
-
-    def C_tcrossprod1_SVT(self, x: SVT_SparseArray):
-        out = np.zeros((x.dim[0], x.dim[0]), dtype=np.float64, order="F")
-        xv = make_view(x)
-        self._check(self._fn("tcrossprod1_SVT")(byref(xv), _ptr(out)))
-        return out
-
-    def C_tcrossprod2_SVT_SVT(self, x: SVT_SparseArray, y: SVT_SparseArray):
-        out = np.zeros((x.dim[0], y.dim[0]), dtype=np.float64, order="F")
-        xv, yv = make_view(x), make_view(y)
-        self._check(self._fn("tcrossprod2_SVT_SVT")(byref(xv), byref(yv), _ptr(out)))
-        return out
-
-    def C_crossprod1_SVT(self, x: SVT_SparseArray):
-        out = np.zeros((x.dim[1], x.dim[1]), dtype=np.float64, order="F")
-        xv = make_view(x)
-        self._check(self._fn("crossprod1_SVT")(byref(xv), _ptr(out)))
-        return out
-
     # stats -------------------------------------------------------------------
     def _opcode(self, op: str) -> int:
         if op not in OPCODES:
@@ -231,10 +220,7 @@ class CAbiDispatcher:
         out_d = np.zeros(2, np.float64)
         out_i = np.zeros(2, np.int32)
         out_Rtype, warn = c_int(0), c_int(0)
-        xv = make_view(x)
-        self._check(self._fn("summarize_SVT")(
-            byref(xv), oc, int(na_rm), float(center), _ptr(out_d), _ptr(out_i),
-            byref(out_Rtype), byref(warn)))
+        self._run("summarize_SVT", x, oc, int(na_rm), float(center), out_d, out_i, byref(out_Rtype), byref(warn))
         return naked_result(op, x.type, out_d, out_i), bool(warn.value)
 
     def _stat_out(self, op, x, shape, per_cell=1):
@@ -251,10 +237,7 @@ class CAbiDispatcher:
         shape = tuple(x.dim[dims:])
         oc, flat, n = self._stat_out(op, x, shape)
         warn = c_int(0)
-        xv = make_view(x)
-        self._check(self._fn("colStats_SVT")(
-            byref(xv), oc, int(na_rm), float(center), int(dims), _ptr(flat),
-            byref(warn)))
+        self._run("colStats_SVT", x, oc, int(na_rm), float(center), int(dims), flat, byref(warn))
         flat = flat[:n]
         ans = flat.reshape(shape, order="F") if len(shape) > 1 else flat
         return ans, bool(warn.value)
@@ -273,16 +256,12 @@ class CAbiDispatcher:
         oc, flat, n = self._stat_out(op, x, shape, per_cell)
         nout = per_cell * n
         warn = c_int(0)
-        cptr = None
         if center is not None:
             center = np.ascontiguousarray(
                 np.reshape(np.asarray(center, np.float64), -1, order="F"))
             if center.size != n:
                 raise SparseArrayError("unexpected 'center' length")
-            cptr = _ptr(center)
-        xv = make_view(x)
-        self._check(self._fn(fname)(
-            byref(xv), oc, int(na_rm), cptr, int(dims), _ptr(flat), byref(warn)))
+        self._run(fname, x, oc, int(na_rm), center, int(dims), flat, byref(warn))
         if flat_result:
             return flat[:nout], bool(warn.value)
         flat = flat[:n]
@@ -295,9 +274,7 @@ class CAbiDispatcher:
         out = np.zeros(shape, dtype=dtype, order="F")
         group = np.ascontiguousarray(group, dtype=np.int32)
         ov = c_int(0)
-        xv = make_view(x)
-        self._check(self._fn(fname)(byref(xv), _ptr(group), int(ngroup),
-                                    int(na_rm), _ptr(out), byref(ov)))
+        self._run(fname, x, group, int(ngroup), int(na_rm), out, byref(ov))
         return out, bool(ov.value)
 
     def C_rowsum_SVT(self, x, group, ngroup, na_rm):
@@ -319,9 +296,7 @@ class CAbiDispatcher:
         xx = np.ascontiguousarray(xx, np.float64)
         group = np.ascontiguousarray(group, dtype=np.int32)
         out = np.zeros(shape, dtype=np.float64, order="F")
-        self._check(self._fn(fname)(int(nrow), int(ncol), _ptr(xx), _ptr(i),
-                                    _ptr(p), _ptr(group), int(ngroup),
-                                    int(na_rm), _ptr(out)))
+        self._run(fname, int(nrow), int(ncol), xx, i, p, group, int(ngroup), int(na_rm), out)
         return out
 
     # aperm (src/SparseArray_aperm.c:935-970) ------------------------------------
@@ -332,21 +307,9 @@ class CAbiDispatcher:
             raise SparseArrayError("'perm' must have one element per dimension")
         if sorted(perm.tolist()) != list(range(1, x.ndim + 1)):
             raise SparseArrayError(f"'perm' must be a permutation of 1:{x.ndim}")
-        new_dim = tuple(x.dim[p - 1] for p in perm)
-        nnz = x.nzcount()
-        new_nl = int(np.prod(new_dim[1:], dtype=np.int64)) if x.ndim > 1 else 1
-        cp = np.zeros(new_nl + 1, dtype=np.int64)
-        ri = np.zeros(max(nnz, 1), dtype=np.int32)
-        vv = np.zeros(max(nnz, 1), dtype=x.np_dtype)
-        view = make_view(x)
-        self._check(self._fn("aperm_SVT")(ctypes.addressof(view), perm.ctypes.data, cp.ctypes.data, ri.ctypes.data,
-                                          vv.ctypes.data))
-        dn = None
-        if x.dimnames is not None:
-            dn = [x.dimnames[p - 1] for p in perm]
-        ans = SVT_SparseArray.from_csc(new_dim, x.type, cp, ri[:nnz], vv[:nnz], dimnames=dn)
-        ans.na_background = x.na_background
-        return ans
+        dn = None if x.dimnames is None else [x.dimnames[p - 1] for p in perm]
+        return self._csc_result(x, tuple(x.dim[p - 1] for p in perm), x.nzcount(), dn,
+                                lambda cp, ri, vv: self._run("aperm_SVT", x, perm, cp, ri, vv))
 
     # column statistics of a dgCMatrix (src/sparseMatrix_utils.c:105-223) ---------------
     def _dgc_colstat(self, fname, x, na_rm, ncols_out):
@@ -354,8 +317,7 @@ class CAbiDispatcher:
         p = np.ascontiguousarray(p, np.int32)
         xx = np.ascontiguousarray(xx, np.float64)
         out = np.zeros((ncol, ncols_out) if ncols_out > 1 else ncol, dtype=np.float64, order="F")
-        self._check(self._fn(fname)(int(nrow), int(ncol), _ptr(xx), _ptr(p), int(bool(na_rm)),
-                                    _ptr(out)))
+        self._run(fname, int(nrow), int(ncol), xx, p, int(bool(na_rm)), out)
         return out
 
     def C_colMins_dgCMatrix(self, x, na_rm):
@@ -375,20 +337,9 @@ class CAbiDispatcher:
         """Returns t(x) as an SVT_SparseArray (the glue rebuilds the R leaves the same way)."""
         if x.ndim != 2:
             raise SparseArrayError("object to transpose must have exactly 2 dimensions")
-        nnz = x.nzcount()
-        cp = np.zeros(x.dim[0] + 1, dtype=np.int64)
-        ri = np.zeros(max(nnz, 1), dtype=np.int32)
-        vv = np.zeros(max(nnz, 1), dtype=x.np_dtype)
-        view = make_view(x)
-        self._check(self._fn("transpose_2D_SVT")(ctypes.addressof(view), cp.ctypes.data, ri.ctypes.data,
-                                                 vv.ctypes.data))
-        dn = None
-        if x.dimnames is not None:
-            dn = [x.dimnames[1], x.dimnames[0]]
-        ans = SVT_SparseArray.from_csc((x.dim[1], x.dim[0]), x.type, cp, ri[:nnz], vv[:nnz],
-                                       dimnames=dn)
-        ans.na_background = x.na_background
-        return ans
+        dn = None if x.dimnames is None else [x.dimnames[1], x.dimnames[0]]
+        return self._csc_result(x, (x.dim[1], x.dim[0]), x.nzcount(), dn,
+                                lambda cp, ri, vv: self._run("transpose_2D_SVT", x, cp, ri, vv))
 
     # x[i, j] by an N-index (src/SparseArray_subsetting.c:223-297; include/svt_hip.h; HIP library only) -------------
     def C_subset_SVT_by_Nindex(self, x: SVT_SparseArray, *index):
@@ -400,25 +351,16 @@ class CAbiDispatcher:
         sub = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (index + (None,))[:2]]
         # (a pointer tells "no subscript" from an empty one: an empty array is handed over as one unread element)
         buf = [None if v is None else (v if v.size else np.zeros(1, np.int32)) for v in sub]
-        begin, end = self._fn("subset_SVT_begin"), self._fn("subset_SVT_end")
-        view = make_view(x)
         res, nnz = c_void_p(0), ctypes.c_int64(0)
-        self._check(begin(ctypes.addressof(view), *[a for v, b in zip(sub, buf) for a in
-                                                     ((None, 0) if v is None else (b.ctypes.data, v.size))],
-                          byref(res), byref(nnz)))
+        self._run("subset_SVT_begin", x, *[a for v, b in zip(sub, buf) for a in ((None, 0) if v is None else (b, v.size))],
+                  byref(res), byref(nnz))
         new_dim = tuple(d if v is None else int(v.size) for d, v in zip(x.dim, sub))
-        n = int(nnz.value)
-        cp = np.zeros(new_dim[1] + 1, dtype=np.int64)
-        ri = np.zeros(max(n, 1), dtype=np.int32)
-        vv = np.zeros(max(n, 1), dtype=x.np_dtype)
-        self._check(end(res, cp.ctypes.data, ri.ctypes.data, vv.ctypes.data))
         dn = None
         if x.dimnames is not None:
             dn = [names if v is None or names is None else [names[k - 1] for k in v.tolist()]
                   for names, v in zip(x.dimnames, sub)]
-        ans = SVT_SparseArray.from_csc(new_dim, x.type, cp, ri[:n], vv[:n], dimnames=dn)
-        ans.na_background = x.na_background
-        return ans
+        return self._csc_result(x, new_dim, int(nnz.value), dn,
+                                lambda cp, ri, vv: self._run("subset_SVT_end", res, cp, ri, vv))
 
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""

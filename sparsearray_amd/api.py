@@ -12,10 +12,19 @@ as ``src/R_init_SparseArray.c:94,121-134``:
     C_colMins_dgCMatrix   C_colMaxs_dgCMatrix   C_colRanges_dgCMatrix  C_colVars_dgCMatrix
     C_transpose_2D_SVT    C_aperm_SVT           C_subset_SVT_by_Nindex (2-D operands)
 
+and the entry points the HIP library adds to them (include/svt_hip.h):
+
+    C_colMedians_SVT      C_colQuantiles_SVT    C_colMads_SVT         C_colRanks_SVT
+    C_rowMedians_SVT      C_rowQuantiles_SVT    C_rowMads_SVT         C_rowRanks_SVT
+    C_matmul_SVT_mat      C_matmul_SVT_SVT      C_tcrossprod1_SVT     C_tcrossprod2_SVT_SVT
+    C_rowStatsFull_SVT
+
 The product binds those names to the HIP library (``sparsearray_amd._hip``);
 there is no CPU implementation in this package.  A ``Session`` can be built
 around any other dispatcher with the same entry points -- the test-suite does
-that with the CPU oracle so both run through identical R-level logic.
+that with its CPU checker so both run through identical R-level logic.  The
+last five are optional: the dispatcher says whether it offers them
+(``Session._has``), and a Session without them composes what the R methods compose.
 
 Conventions: dense inputs/outputs are numpy arrays with R index semantics;
 "logical" results are int32 with ``NA_integer`` for NA.
@@ -48,10 +57,29 @@ TIES_METHODS = {"max": 0, "average": 1, "min": 2, "dense": 3}
 
 # row statistics that C_rowStats_SVT does not take: one C_rowStatsFull_SVT call where the library has it
 _ROWSTATS_FULL_OPS = ("any", "all", "prod", "range", "mean", "var1", "sd1")
+# those of them that the R methods compose out of C_rowStats_SVT calls; the others go through .OLD_rowStats_SparseArray
+_ROWSTATS_COMPOSED_OPS = ("range", "mean", "var1", "sd1")
 
 
 def _shaped(flat: np.ndarray, shape) -> np.ndarray:
     return flat.reshape(shape, order="F") if len(shape) > 1 else flat
+
+
+def _check_2D(what: str, x):
+    if x.ndim != 2:
+        raise SparseArrayError(
+            f"the {what}() method for SparseArray objects only supports 2D "
+            "objects (i.e. SparseMatrix objects) at the moment")
+
+
+def _check_not_NaArray(what: str, x):
+    if x.na_background:
+        raise SparseArrayError(f"{what}() is not supported on NaArray objects")
+
+
+def _check_flag(name: str, value):
+    if not isinstance(value, (bool, np.bool_)):
+        raise SparseArrayError(f"'{name}' must be TRUE or FALSE")
 
 
 def _check_crossprod_input_type(type_: str):
@@ -105,6 +133,10 @@ class Session:
     # SparseArray.Call(), R/thread-control.R:87-92
     def SparseArray_Call(self, name: str, *args):
         return self._call(name, *args)
+
+    def _has(self, name: str) -> bool:
+        """Whether the dispatcher offers an entry point the reference does not have."""
+        return getattr(self._call, "has_entry", lambda name: False)(name)
 
     # ------------------------------------------------------------------
     # crossprod / tcrossprod / %*%   (R/SparseMatrix-mult.R)
@@ -238,14 +270,13 @@ class Session:
         # The R methods transpose first (t() = C_transpose_2D_SVT on the host, R/SparseMatrix-mult.R:165-193).  The HIP
         # library offers both sparse forms in one call with the transpositions on the device (svt_tcrossprod*_SVT*,
         # include/svt_hip.h); same checks, same coercions, applied to the transposed operands.
-        has = getattr(self._call, "has_entry", lambda name: False)
         if xs and y is None:
-            if has("C_tcrossprod1_SVT") and x.ndim == 2:
+            if self._has("C_tcrossprod1_SVT") and x.ndim == 2:
                 _check_crossprod_input_type(x.type)
                 return self.SparseArray_Call("C_tcrossprod1_SVT", x)
             return self._crossprod1_SparseMatrix(self.t(x))
         if xs and ys:
-            if has("C_tcrossprod2_SVT_SVT") and x.ndim == 2 and y.ndim == 2:
+            if self._has("C_tcrossprod2_SVT_SVT") and x.ndim == 2 and y.ndim == 2:
                 if x.dim[1] != y.dim[1]:
                     raise SparseArrayError("non-conformable arguments")
                 if x.type == y.type:
@@ -269,13 +300,12 @@ class Session:
         # The R methods transpose x first (t() = C_transpose_2D_SVT on the host).  The
         # HIP library offers the product in one call, with the transposition on the
         # device (svt_matmul_SVT_*, include/svt_hip.h); same checks, same coercions.
-        has = getattr(self._call, "has_entry", lambda name: False)
         if xs and ys:
-            if has("C_matmul_SVT_SVT"):
+            if self._has("C_matmul_SVT_SVT"):
                 return self._matmul_fused(x, y)
             return self._crossprod2_SparseMatrix_SparseMatrix(self.t(x), y)
         if xs:
-            if has("C_matmul_SVT_mat"):
+            if self._has("C_matmul_SVT_mat"):
                 return self._matmul_fused(x, y)
             return self._crossprod2_SparseMatrix_matrix(self.t(x), y)
         if ys:
@@ -293,8 +323,7 @@ class Session:
                 "'dims' must be a single integer that is > 0 and <= "
                 "length(dim(x)) for the col*() functions, and >= 0 and < "
                 "length(dim(x)) for the row*() functions")
-        if not isinstance(na_rm, (bool, np.bool_)):
-            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
+        _check_flag("na.rm", na_rm)
         center = NA_real if center is None else float(center)
         ans, warn = self.SparseArray_Call("C_colStats_SVT", x, op,
                                           bool(na_rm), center, dims)
@@ -303,44 +332,35 @@ class Session:
                           "infinite values to integers")
         return ans
 
+    def _row_form(self, col, entry, x, *args):
+        """rowX(x) = colX(t(x)): one call of the row entry point, which transposes on the device.  An operand with a
+        zero extent takes the R-level composition, for the column form's answers to nrow == 0."""
+        if 0 in x.dim:
+            return col(self.t(x), *args)
+        return self.SparseArray_Call(entry, x, *args)
+
     def colMedians(self, x, na_rm=False):
         """colMedians(x, na.rm) (R/SparseArray-matrixStats.R:786-800; 2-D objects only)."""
-        if x.ndim != 2:
-            raise SparseArrayError(
-                "the colMedians() method for SparseArray objects only supports 2D "
-                "objects (i.e. SparseMatrix objects) at the moment")
-        if not isinstance(na_rm, (bool, np.bool_)):
-            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
+        _check_2D("colMedians", x)
+        _check_flag("na.rm", na_rm)
         if x.dim[0] == 0:
             return np.full(x.dim[1], NA_real)            # :771-772
         return self.SparseArray_Call("C_colMedians_SVT", x, bool(na_rm))
 
     def rowMedians(self, x, na_rm=False):
         """rowMedians(x) = colMedians(t(x)) (R/SparseArray-matrixStats.R:802-815)."""
-        if x.ndim != 2:
-            raise SparseArrayError(
-                "the rowMedians() method for SparseArray objects only supports 2D "
-                "objects (i.e. SparseMatrix objects) at the moment")
-        if not isinstance(na_rm, (bool, np.bool_)):
-            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_rowMedians_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
-            return self.SparseArray_Call("C_rowMedians_SVT", x, bool(na_rm))   # t(x) on the device
-        return self.colMedians(self.t(x), na_rm=na_rm)
+        _check_2D("rowMedians", x)
+        _check_flag("na.rm", na_rm)
+        return self._row_form(self.colMedians, "C_rowMedians_SVT", x, bool(na_rm))
 
     # colQuantiles / rowQuantiles / colIQRs / rowIQRs.  The reference has no method (they are in its list of statistics
     # to add, R/SparseArray-matrixStats.R:5-12); the rule is matrixStats::colQuantiles(type = 7), i.e. base R's
     # quantile.default type 7, on each column's nrow values with the implicit zeros included.  Not offered: colRanks,
     # colOrderStats, other quantile types, N-d operands, NaArray operands.
     def _check_quantiles_args(self, what, x, probs, na_rm, type):
-        if x.ndim != 2:
-            raise SparseArrayError(
-                f"the {what}() method for SparseArray objects only supports 2D "
-                "objects (i.e. SparseMatrix objects) at the moment")
-        if x.na_background:
-            raise SparseArrayError("colQuantiles() is not supported on NaArray objects")
-        if not isinstance(na_rm, (bool, np.bool_)):
-            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
+        _check_2D(what, x)
+        _check_not_NaArray("colQuantiles", x)
+        _check_flag("na.rm", na_rm)
         if isinstance(type, (bool, np.bool_)) or type != 7:
             raise SparseArrayError(f"{what}(): only type = 7 is supported")
         try:
@@ -351,73 +371,17 @@ class Session:
             raise SparseArrayError("'probs' outside [0,1]")
         return probs
 
-    @staticmethod
-    def _leaf_quantiles(vals, nrow, probs, na_rm, ans):
-        """Type 7 quantiles of one leaf's nrow values into ans[:], without realising the zeros: the sorted column is
-        [negatives | zeros | positives], so the ranks are read out of the leaf's sorted non-NA nonzeros."""
-        miss = np.isnan(vals)
-        if miss.any():
-            if not na_rm:
-                ans[:] = NA_real
-                return
-            vals = vals[~miss]
-        n = len(vals) + (nrow - len(miss))            # na.rm drops stored values; the padding keeps its size
-        if n == 0:
-            ans[:] = NA_real
-            return
-        nz = np.sort(vals[vals != 0.0])               # (a stored zero counts among the zeros)
-        neg = int((nz < 0.0).sum())
-        zeros = n - len(nz)
-
-        def value(r):                                 # 0-based rank of the virtual column
-            return float(nz[r]) if r < neg else 0.0 if r < neg + zeros else float(nz[r - zeros])
-
-        for q, p in enumerate(probs.tolist()):
-            index = 1 + (n - 1) * p                   # plain IEEE double: one product, one sum
-            lo, hi = int(np.floor(index)), int(np.ceil(index))
-            xlo = value(lo - 1)
-            if index > lo:
-                xhi = value(hi - 1)
-                if xhi != xlo:
-                    h = index - lo
-                    xlo = (1 - h) * xlo + h * xhi     # two products and one sum, each rounded (Inf - Inf: NaN)
-            ans[q] = xlo
-
     def colQuantiles(self, x, probs=(0.0, 0.25, 0.5, 0.75, 1.0), na_rm=False, type=7):
         """colQuantiles(x, probs, na.rm, type = 7): an (ncol, P) array, the columns in the order of ``probs``."""
         probs = self._check_quantiles_args("colQuantiles", x, probs, na_rm, type)
-        nrow, ncol = x.dim
-        if nrow == 0:
-            return np.full((ncol, probs.size), NA_real)
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_colQuantiles_SVT"):
-            return self.SparseArray_Call("C_colQuantiles_SVT", x, probs, bool(na_rm))
-        # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
-        ans = np.zeros((ncol, probs.size))
-        for j, lf in enumerate(x.leaves):
-            self._leaf_quantiles(self._leaf_doubles(lf), nrow, probs, bool(na_rm), ans[j])
-        return ans
-
-    @staticmethod
-    def _leaf_doubles(lf):
-        """The stored values of one leaf as doubles, NaN for an integer NA."""
-        if lf is None:
-            return np.zeros(0)
-        if lf[1] is None:                             # lacunar leaf: all ones
-            return np.ones(len(lf[0]))
-        raw = np.asarray(lf[1])
-        vals = raw.astype(np.float64)
-        if raw.dtype != np.float64:
-            vals[raw == NA_integer] = np.nan
-        return vals
+        if x.dim[0] == 0:
+            return np.full((x.dim[1], probs.size), NA_real)
+        return self.SparseArray_Call("C_colQuantiles_SVT", x, probs, bool(na_rm))
 
     def rowQuantiles(self, x, probs=(0.0, 0.25, 0.5, 0.75, 1.0), na_rm=False, type=7):
         """rowQuantiles(x) = colQuantiles(t(x)): an (nrow, P) array."""
         probs = self._check_quantiles_args("rowQuantiles", x, probs, na_rm, type)
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_rowQuantiles_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
-            return self.SparseArray_Call("C_rowQuantiles_SVT", x, probs, bool(na_rm))   # t(x) on the device
-        return self.colQuantiles(self.t(x), probs=probs, na_rm=na_rm)
+        return self._row_form(self.colQuantiles, "C_rowQuantiles_SVT", x, probs, bool(na_rm))
 
     @staticmethod
     def _iqr(q):
@@ -437,14 +401,9 @@ class Session:
     # R/SparseArray-matrixStats.R:5-12, rowMads in its TODO); the rule is stats::mad without low / high on each
     # column's nrow values with the implicit zeros included (include/svt_hip.h, svt_colMads_SVT).
     def _check_mads_args(self, what, x, center, na_rm, nout_axis):
-        if x.ndim != 2:
-            raise SparseArrayError(
-                f"the {what}() method for SparseArray objects only supports 2D "
-                "objects (i.e. SparseMatrix objects) at the moment")
-        if x.na_background:
-            raise SparseArrayError("colMads() is not supported on NaArray objects")
-        if not isinstance(na_rm, (bool, np.bool_)):
-            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
+        _check_2D(what, x)
+        _check_not_NaArray("colMads", x)
+        _check_flag("na.rm", na_rm)
         if center is None:
             return None
         nout = x.dim[nout_axis]
@@ -462,116 +421,30 @@ class Session:
             raise bad
         return np.ascontiguousarray(c)
 
-    @staticmethod
-    def _padded_median(outside, below, block, n, blk):
-        """The median of n values of which the sorted ``outside`` are stored, ``below`` of them less than the ``block``
-        others, which all equal ``blk``: the middle value, or (lo + hi) * 0.5."""
-        def value(r):                                 # 0-based rank of the virtual column
-            return float(outside[r]) if r < below else blk if r < below + block else float(outside[r - block])
-
-        lo = value((n - 1) >> 1)
-        return lo if n & 1 else (lo + value(n >> 1)) * 0.5
-
-    @classmethod
-    def _leaf_mad(cls, vals, nrow, c, constant, na_rm):
-        """colMads of one leaf's nrow values without realising the zeros: the sorted deviations are [below | block of
-        the values equal to fabs(0 - c) | above]."""
-        miss = np.isnan(vals)
-        if miss.any():
-            if not na_rm:
-                return NA_real
-            vals = vals[~miss]
-        n = len(vals) + (nrow - len(miss))            # na.rm drops stored values; the padding keeps its size
-        if n == 0:
-            return NA_real
-        with np.errstate(all="ignore"):
-            if c is None:                             # the median's own rule: [negatives | zeros | positives]
-                nz = np.sort(vals[vals != 0.0])
-                c = cls._padded_median(nz, int((nz < 0.0).sum()), n - len(nz), n, 0.0)
-            if c != c:
-                return NA_real
-            t = np.abs(vals - c)                      # one subtraction each
-            b = abs(0.0 - c)                          # every zero, stored or implicit
-            if np.isnan(t).any():                     # a value that is the center's infinity
-                return NA_real
-            out = np.sort(t[t != b])
-            m = cls._padded_median(out, int((out < b).sum()), n - len(out), n, b)
-            return float(np.float64(constant) * np.float64(m))
-
     def colMads(self, x, center=None, constant=1.4826, na_rm=False):
         """colMads(x, center, constant, na.rm): constant * median(|x - center|) of every column, ``center`` the
         column's median unless given (a single number, or one per column)."""
         center = self._check_mads_args("colMads", x, center, na_rm, 1)
         constant = float(constant)
-        nrow, ncol = x.dim
-        if nrow == 0:
-            return np.full(ncol, NA_real)
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_colMads_SVT"):
-            return self.SparseArray_Call("C_colMads_SVT", x, center, constant, bool(na_rm))
-        # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
-        ans = np.zeros(ncol)
-        for j, lf in enumerate(x.leaves):
-            ans[j] = self._leaf_mad(self._leaf_doubles(lf), nrow, None if center is None else float(center[j]),
-                                    constant, bool(na_rm))
-        return ans
+        if x.dim[0] == 0:
+            return np.full(x.dim[1], NA_real)
+        return self.SparseArray_Call("C_colMads_SVT", x, center, constant, bool(na_rm))
 
     def rowMads(self, x, center=None, constant=1.4826, na_rm=False):
         """rowMads(x) = colMads(t(x)); ``center``: a single number, or one per row."""
         center = self._check_mads_args("rowMads", x, center, na_rm, 0)
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_rowMads_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
-            return self.SparseArray_Call("C_rowMads_SVT", x, center, float(constant), bool(na_rm))   # t(x) on the device
-        return self.colMads(self.t(x), center=center, constant=constant, na_rm=na_rm)
+        return self._row_form(self.colMads, "C_rowMads_SVT", x, center, float(constant), bool(na_rm))
 
     # colRanks / rowRanks.  The reference has no method; the rule is matrixStats::colRanks(x, ties.method,
     # preserveShape), i.e. rank(na.last = "keep", ties.method) of each column's nrow values with the implicit zeros
     # included (include/svt_hip.h, svt_colRanks_SVT).  Not offered: ties.method "first", "last" and "random" (every
     # implicit zero would need a rank of its own), N-d operands, NaArray operands.
     def _check_ranks_args(self, what, x, ties_method, preserve_shape):
-        if x.ndim != 2:
-            raise SparseArrayError(
-                f"the {what}() method for SparseArray objects only supports 2D "
-                "objects (i.e. SparseMatrix objects) at the moment")
-        if x.na_background:
-            raise SparseArrayError("colRanks() is not supported on NaArray objects")
+        _check_2D(what, x)
+        _check_not_NaArray("colRanks", x)
         if not isinstance(ties_method, str) or ties_method not in TIES_METHODS:
             raise SparseArrayError("'ties.method' must be \"max\", \"average\", \"min\" or \"dense\"")
-        if not isinstance(preserve_shape, (bool, np.bool_)):
-            raise SparseArrayError("'preserveShape' must be TRUE or FALSE")
-
-    @staticmethod
-    def _leaf_ranks(vals, nrow, ties_method):
-        """The ranks of one leaf's stored values among its nrow values, and the rank of its zeros (None when it holds
-        no zero, stored or implicit), without realising the zeros: the non-missing stored values are sorted, the block
-        of the zeros has nrow - length + stored zeros members.  A missing value's rank is NA."""
-        average = ties_method == "average"
-        na = NA_real if average else NA_integer
-        ranks = np.full(len(vals), na, dtype=np.float64 if average else np.int32)
-        ok = ~np.isnan(vals)
-        v = vals[ok] + 0.0                              # -0.0 is 0.0
-        s = np.sort(v)
-        z = nrow - len(vals)                            # implicit zeros
-        nzs = int((s == 0.0).sum())
-        pos = v > 0.0
-        L = np.searchsorted(s, v, "left") + z * pos
-        E = np.searchsorted(s, v, "right") - np.searchsorted(s, v, "left") + z * (v == 0.0)
-        u = np.unique(s)
-        D = np.searchsorted(u, v, "left") + (pos & (z > 0 and nzs == 0))
-        neg, dneg = int((s < 0.0).sum()), int((u < 0.0).sum())
-
-        def rank(L, E, D):
-            if ties_method == "max":
-                return L + E
-            if ties_method == "min":
-                return L + 1
-            if ties_method == "dense":
-                return D + 1
-            return (2 * L + E + 1).astype(np.float64) * 0.5 if isinstance(L, np.ndarray) else (2 * L + E + 1) * 0.5
-
-        ranks[ok] = rank(L, E, D)
-        zero = rank(neg, z + nzs, dneg) if z + nzs > 0 else na
-        return ranks, zero
+        _check_flag("preserveShape", preserve_shape)
 
     def colRanks(self, x, ties_method="max", preserve_shape=False):
         """colRanks(x, ties.method, preserveShape): the rank of every value within its column, NA for a missing one;
@@ -579,29 +452,15 @@ class Session:
         (ncol, nrow), unless ``preserve_shape``."""
         self._check_ranks_args("colRanks", x, ties_method, preserve_shape)
         nrow, ncol = x.dim
-        dtype = np.float64 if ties_method == "average" else np.int32
-        shape = (nrow, ncol) if preserve_shape else (ncol, nrow)
         if nrow == 0 or ncol == 0:
-            return np.zeros(shape, dtype=dtype, order="F")
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_colRanks_SVT"):
-            return self.SparseArray_Call("C_colRanks_SVT", x, ties_method, bool(preserve_shape))
-        # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
-        ans = np.zeros((nrow, ncol), dtype=dtype, order="F")
-        for j, lf in enumerate(x.leaves):
-            ranks, zero = self._leaf_ranks(self._leaf_doubles(lf), nrow, ties_method)
-            ans[:, j] = zero
-            if lf is not None:
-                ans[np.asarray(lf[0]), j] = ranks
-        return ans if preserve_shape else np.asfortranarray(ans.T)
+            return np.zeros((nrow, ncol) if preserve_shape else (ncol, nrow),
+                            dtype=np.float64 if ties_method == "average" else np.int32, order="F")
+        return self.SparseArray_Call("C_colRanks_SVT", x, ties_method, bool(preserve_shape))
 
     def rowRanks(self, x, ties_method="max"):
         """rowRanks(x) = colRanks(t(x), preserveShape = FALSE): an (nrow, ncol) array."""
         self._check_ranks_args("rowRanks", x, ties_method, False)
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_rowRanks_SVT") and x.dim[1] > 0 and x.dim[0] > 0:
-            return self.SparseArray_Call("C_rowRanks_SVT", x, ties_method)          # t(x) on the device
-        return self.colRanks(self.t(x), ties_method=ties_method, preserve_shape=False)
+        return self._row_form(lambda tx, ties: self.colRanks(tx, ties, False), "C_rowRanks_SVT", x, ties_method)
 
     def _rowStats(self, op, x, na_rm=False, center=None, dims=1):
         # .rowStats_SparseArray, R/SparseArray-matrixStats.R:197-259
@@ -611,16 +470,18 @@ class Session:
                 "'dims' must be a single integer that is > 0 and <= "
                 "length(dim(x)) for the col*() functions, and >= 0 and < "
                 "length(dim(x)) for the row*() functions")
+        # The one place that picks the route of a row statistic: DESIGN.md, "Row statistics in one call"
+        # rowAnys/Alls/Prods/Means/Vars/Sds: no NaArray methods (commented out in R/NaArray-matrixStats.R:187-330)
+        no_method = x.na_background and op not in ("countNAs", "anyNA", "min", "max", "sum", "range")
+        full = self._has_rowStatsFull()
+        if op in _ROWSTATS_COMPOSED_OPS and not no_method and (dims == 0 or not full):
+            return self._rowStats_composed(op, x, na_rm, center, dims)
         if dims == 0:
             return self._colStats(op, x, na_rm, center, x.ndim)
-        if x.na_background and op not in ("countNAs", "anyNA", "min", "max", "sum", "range"):
-            # rowAnys/Alls/Prods/Means/Vars/Sds: no NaArray methods (commented out in
-            # R/NaArray-matrixStats.R:187-330)
+        if no_method:
             raise SparseArrayError(f"unable to find an inherited method for the row {op} "
                                    f"statistic for signature 'x = \"NaArray\"'")
-        full = self._has_rowStatsFull()
-        if op not in ("countNAs", "anyNA", "min", "max", "sum",
-                      "centered_X2_sum") and not full:
+        if op in ("any", "all", "prod") and not full:
             return self._OLD_rowStats(op, x, na_rm, center, dims)
         if center is not None:
             ans_dim = x.dim[:dims]
@@ -634,34 +495,34 @@ class Session:
                 center = np.reshape(center, ans_dim, order="F")
             else:
                 raise SparseArrayError("unexpected 'center' length")
-        if op in ("any", "all", "prod") and not isinstance(na_rm, (bool, np.bool_)):
-            raise SparseArrayError("'na.rm' must be TRUE or FALSE")      # (the check of _colStats on the composed route)
+        if op in ("any", "all", "prod"):
+            _check_flag("na.rm", na_rm)                          # (the check of _colStats on the composed route)
         if op in _ROWSTATS_FULL_OPS:
             # The R methods compose these (a transposition and colStats; two to four C_rowStats_SVT calls).  The
             # HIP library offers each in one call (svt_rowStatsFull_SVT, include/svt_hip.h); same checks above.
-            if full:
-                try:
-                    flat, warn = self.SparseArray_Call("C_rowStatsFull_SVT", x, op,
-                                                       bool(na_rm), center, dims)
-                except SparseArrayUnsupported:
-                    flat = None
-                if flat is not None:
-                    if warn:
-                        warnings.warn("NAs introduced by coercion of "
-                                      "infinite values to integers")
-                    shape = tuple(x.dim[:dims])
-                    flat = np.asarray(flat).reshape(-1)
-                    if op == "range":                        # the minima, then the maxima
-                        n = flat.size // 2
-                        return np.stack([_shaped(flat[:n], shape), _shaped(flat[n:], shape)], axis=-1)
-                    return _shaped(flat, shape)
-            return self._rowStats_composed(op, x, na_rm, center, dims)
+            try:
+                flat, warn = self.SparseArray_Call("C_rowStatsFull_SVT", x, op,
+                                                   bool(na_rm), center, dims)
+            except SparseArrayUnsupported:
+                return self._rowStats_composed(op, x, na_rm, center, dims)
+            if warn:
+                warnings.warn("NAs introduced by coercion of "
+                              "infinite values to integers")
+            shape = tuple(x.dim[:dims])
+            flat = np.asarray(flat).reshape(-1)
+            if op == "range":                        # the minima, then the maxima
+                n = flat.size // 2
+                return np.stack([_shaped(flat[:n], shape), _shaped(flat[n:], shape)], axis=-1)
+            return _shaped(flat, shape)
         ans, warn = self.SparseArray_Call("C_rowStats_SVT", x, op,
                                           bool(na_rm), center, dims)
         if warn:
             warnings.warn("NAs introduced by coercion of "
                           "infinite values to integers")
         return ans
+
+    def _has_rowStatsFull(self):
+        return self._has("C_rowStatsFull_SVT")
 
     def _rowStats_composed(self, op, x, na_rm, center, dims):
         # what the R methods do for the operations C_rowStats_SVT does not take
@@ -726,8 +587,8 @@ class Session:
         """``x[i, j]`` of a 2-D object by an N-index, 1-based like ``perm`` and ``group``; None keeps the whole axis
         (``subset(x)`` keeps them all).  Result cell (p, q) is x[i[p], j[q]]; indices may come in any order and any
         number of times; stored values are copied bit for bit, type and NA background kept.  One subscript per
-        dimension: ``subset(x, i, j, k)`` on a 3-D object reaches the library, which does not take it
-        (SparseArrayUnsupported); a session without the library raises SparseArrayError for it."""
+        dimension: ``subset(x, i, j, k)`` on a 3-D object reaches the entry point, which does not take it (the library:
+        SparseArrayUnsupported)."""
         index = (i, j) + more
         if i is None and j is None and not more:
             index = (None,) * x.ndim
@@ -736,44 +597,7 @@ class Session:
         if len(index) != x.ndim:
             raise SparseArrayError("incorrect number of subscripts")
         index = [self._check_Nindex(s, d) for s, d in zip(index, x.dim)]
-        has = getattr(self._call, "has_entry", lambda name: False)
-        if has("C_subset_SVT_begin"):
-            # ndim != 2: the library answers "not supported here" (SparseArrayUnsupported); this package has no CPU body
-            return self.SparseArray_Call("C_subset_SVT_by_Nindex", x, *index)
-        if x.ndim != 2:
-            raise SparseArrayError("subset() supports 2D objects (i.e. SparseMatrix objects) only at the moment")
-        # The statement of the rule on the host, one leaf at a time (what an R method without the library would do)
-        i, j = index
-        nrow, ncol = x.dim
-        cols = np.arange(ncol) if j is None else j.astype(np.int64) - 1
-        if i is not None:
-            i0 = i.astype(np.int64) - 1
-            order = np.argsort(i0, kind="stable")           # the places of the subscript, by the row they ask for
-            sorted_rows = i0[order]
-        memo = {}
-        leaves = []
-        for c in cols.tolist():
-            if c not in memo:
-                lf = x.leaves[c]
-                if lf is not None and i is not None:
-                    offs = np.asarray(lf[0], dtype=np.int64)
-                    lo = np.searchsorted(sorted_rows, offs, "left")
-                    hi = np.searchsorted(sorted_rows, offs, "right")
-                    cnt = hi - lo
-                    src = np.repeat(np.arange(offs.size), cnt)               # the stored entry of every result entry
-                    at = order[np.repeat(lo, cnt) + np.arange(src.size) - np.repeat(np.cumsum(cnt) - cnt, cnt)]
-                    by_place = np.argsort(at, kind="stable")
-                    new_offs = at[by_place].astype(np.int32)
-                    lf = None if new_offs.size == 0 else \
-                        (new_offs, None if lf[1] is None else np.asarray(lf[1])[src[by_place]])
-                memo[c] = lf
-            leaves.append(memo[c])
-        dn = None
-        if x.dimnames is not None:
-            dn = [names if s is None or names is None else [names[k - 1] for k in s.tolist()]
-                  for names, s in zip(x.dimnames, index)]
-        return SVT_SparseArray((nrow if i is None else int(i.size), int(cols.size)), x.type, leaves, dn,
-                               na_background=x.na_background)
+        return self.SparseArray_Call("C_subset_SVT_by_Nindex", x, *index)
 
     def _OLD_rowStats(self, op, x, na_rm, center, dims):
         # .OLD_rowStats_SparseArray (:122-190): "aperm(colStats(aperm(x), dims=ndim-dims))",
@@ -816,13 +640,7 @@ class Session:
         maxs = self.colMaxs(x, na_rm, dims)
         return np.stack([mins, maxs], axis=-1)
 
-    def rowRanges(self, x, na_rm=False, dims=1):
-        if self._has_rowStatsFull() and int(dims) != 0:
-            return self._rowStats("range", x, na_rm, dims=dims)
-        return self._rowStats_composed("range", x, na_rm, None, dims)
-
-    def _has_rowStatsFull(self):
-        return getattr(self._call, "has_entry", lambda name: False)("C_rowStatsFull_SVT")
+    def rowRanges(self, x, na_rm=False, dims=1): return self._rowStats("range", x, na_rm, dims=dims)
 
     def colSums(self, x, na_rm=False, dims=1): return self._colStats("sum", x, na_rm, dims=dims)
     def rowSums(self, x, na_rm=False, dims=1): return self._rowStats("sum", x, na_rm, dims=dims)
@@ -830,13 +648,7 @@ class Session:
     def rowProds(self, x, na_rm=False, dims=1): return self._rowStats("prod", x, na_rm, dims=dims)
     def colMeans(self, x, na_rm=False, dims=1): return self._colStats("mean", x, na_rm, dims=dims)
 
-    def rowMeans(self, x, na_rm=False, dims=1):
-        # :511-516
-        if x.na_background:
-            return self._rowStats("mean", x, na_rm, dims=dims)     # raises: no NaArray method
-        if self._has_rowStatsFull() and int(dims) != 0:
-            return self._rowStats("mean", x, na_rm, dims=dims)
-        return self._rowStats_composed("mean", x, na_rm, None, dims)
+    def rowMeans(self, x, na_rm=False, dims=1): return self._rowStats("mean", x, na_rm, dims=dims)
 
     colSums2, rowSums2, colMeans2, rowMeans2 = colSums, rowSums, colMeans, rowMeans
 
@@ -850,15 +662,13 @@ class Session:
         # :645-660
         if x.na_background:
             return self._rowStats("var1", x, na_rm, dims=dims)     # raises: no NaArray method
-        if self._has_rowStatsFull() and int(dims) != 0:
-            return self._rowStats("var1", x, na_rm, center, dims)
-        return self._rowStats_composed("var1", x, na_rm, center, dims)
+        return self._rowStats("var1", x, na_rm, center, dims)
 
     def rowSds(self, x, na_rm=False, center=None, dims=1):
-        if self._has_rowStatsFull() and int(dims) != 0 and not x.na_background:
-            return self._rowStats("sd1", x, na_rm, center, dims)
-        with np.errstate(all="ignore"):
-            return np.sqrt(self.rowVars(x, na_rm, center, dims))
+        if x.na_background:                                        # sqrt(rowVars(x)): it is rowVars that has no method
+            with np.errstate(all="ignore"):
+                return np.sqrt(self.rowVars(x, na_rm, center, dims))
+        return self._rowStats("sd1", x, na_rm, center, dims)
 
     # ------------------------------------------------------------------
     # whole-array summarization  (R/SparseArray-summarization.R)
@@ -949,8 +759,7 @@ class Session:
     def _dgc_colstat(self, name, x, na_rm):
         if not (isinstance(x, tuple) and len(x) == 4):
             raise SparseArrayError("is(x, \"dgCMatrix\") is not TRUE")
-        if not isinstance(na_rm, (bool, np.bool_)):
-            raise SparseArrayError("'na.rm' must be TRUE or FALSE")
+        _check_flag("na.rm", na_rm)
         return self.SparseArray_Call(name, x, bool(na_rm))
 
     def colMins_dgCMatrix(self, x, na_rm=False):

@@ -1,5 +1,5 @@
 """Operands and subscripts for x[i, j] by an N-index (Session.subset; src/SparseArray_subsetting.c:223-297 restricted to
-2-D operands), shared by tests/test_subset_cpu.py (the host statement of sparsearray_amd/api.py on the oracle session)
+2-D operands), shared by tests/test_subset_cpu.py (the host statement of oracle/rules.py on the oracle session)
 and tests/test_hip_subset.py (the device route).
 
 The rule is numpy's on the dense matrix, ``dense[np.ix_(i0, j0)]``, at tolerance 0: values equal AS BITS (a float

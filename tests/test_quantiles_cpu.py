@@ -1,6 +1,6 @@
 """colQuantiles() / rowQuantiles() / colIQRs() / rowIQRs(): the reference has no method; the rule is base R's
 quantile.default type 7 on each column's nrow values, the implicit zeros included (include/svt_hip.h).  Here the
-host statement of sparsearray_amd/api.py (what the oracle session runs: its dispatcher has no entry point) is checked
+host statement of oracle/rules.py (what the oracle session runs: an entry point of its dispatcher) is checked
 against the plain definition on the dense column, at tolerance 0: both sides evaluate the same IEEE operations."""
 import numpy as np
 import pytest

@@ -1,7 +1,7 @@
 """colRanks() / rowRanks(): the reference has no method; the rule is matrixStats::colRanks(x, ties.method,
 preserveShape) = rank(na.last = "keep", ties.method) of each column's nrow values, the implicit zeros included
-(include/svt_hip.h, svt_colRanks_SVT).  Here the host statement of sparsearray_amd/api.py (what the oracle session runs:
-its dispatcher has no entry point) is checked against the plain definition on the dense column -- L and E by comparison
+(include/svt_hip.h, svt_colRanks_SVT).  Here the host statement of oracle/rules.py (what the oracle session runs:
+an entry point of its dispatcher) is checked against the plain definition on the dense column -- L and E by comparison
 counts -- which the same test cross-checks against scipy.stats.rankdata(nan_policy="omit").  Everything at tolerance 0:
 ranks are integers, and (2L + E + 1) * 0.5 is exact."""
 import numpy as np

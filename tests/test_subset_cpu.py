@@ -1,5 +1,5 @@
-"""x[i, j] by an N-index without a GPU: the host statement of the rule in sparsearray_amd/api.py (Session.subset on a
-session whose dispatcher has no subsetting entry -- the oracle session) against numpy on the dense matrix,
+"""x[i, j] by an N-index without a GPU: the host statement of the rule in oracle/rules.py (Session.subset on the
+oracle session, whose dispatcher has it as its subsetting entry) against numpy on the dense matrix,
 ``dense[np.ix_(i, j)]``, at tolerance 0 (values and the mask of stored entries, as bits; tests/subset_cases.py), and the
 argument checks, which run before dispatch and are the same for every session.
 
