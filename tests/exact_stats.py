@@ -369,6 +369,13 @@ def exact_minmax(c: Cells, is_min, as_int=False):
     return m
 
 
+def exact_int_no_value(c: Cells):
+    """Integer min / max warn ("NAs introduced by coercion of infinite values to integers") exactly when some cell has
+    nothing to look at -- no value taking part, no implicit zero -- and no missing value decides it first
+    (src/Rvector_summarization.c:1108-1128)."""
+    return bool(np.any((c.n == 0) & (c.Z == 0) & ~c.poisoned))
+
+
 def exact_count_nas(c: Cells):
     return (c.r + c.implicit_na).astype(np.float64)
 

@@ -192,6 +192,18 @@ def _quiet(f, *a, **k):
             return f(*a, **k)
 
 
+NO_VALUE = "NAs introduced by coercion of infinite values to integers"
+
+
+def _warned(f, *a, **k):
+    """(f's result, whether it gave the integer "no value" warning); every other warning stays quiet."""
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        with np.errstate(all="ignore"):
+            res = f(*a, **k)
+    return res, any(NO_VALUE in str(m.message) for m in w)
+
+
 def _flat(a):
     return np.asarray(a).reshape(-1, order="F")
 
@@ -238,7 +250,9 @@ def check_stat(op, got, cells, rec, key, center=None, rows=False, is_int=False, 
 
 def run_column_case(sess, c, rec=None, who="", colstat=None):
     """Every column statistic of the case, both na_rm, through ``sess`` (col*() of a Session), or through
-    ``colstat(op, na_rm, center)`` when given (the device level)."""
+    ``colstat(op, na_rm, center) -> (result, warn word set)`` when given (the device level).  Integer min / max also
+    say that a cell had no value: the session by a warning, the device by its warn word, both exactly when
+    exact_stats.exact_int_no_value() says so."""
     is_int = c.type == "integer"
     ops = COL_OPS + (["any", "all"] if is_int else [])
     if c.palette == "e":
@@ -251,9 +265,11 @@ def run_column_case(sess, c, rec=None, who="", colstat=None):
             center = c.center if op == "centered_X2_sum" else None
             narm = na_rm and op not in ("anyNA", "countNAs")     # (colAnyNAs / colCountNAs have no na.rm)
             if colstat is not None:
-                got = colstat(op, narm, center)
+                got, warned = colstat(op, narm, center)
             else:
-                got = _quiet(sess._colStats, op, c.x, narm, center, c.dims)
+                got, warned = _warned(sess._colStats, op, c.x, narm, center, c.dims)
+            if is_int and op in ("min", "max"):
+                assert warned == ex.exact_int_no_value(cells), f"{c.name}/{c.palette} na_rm={na_rm} {op}: warning"
             check_stat(op, got, cells, rec, (who, "col " + op, c.form), center=center, is_int=is_int,
                        what=f"{c.name}/{c.palette} na_rm={na_rm}")
 

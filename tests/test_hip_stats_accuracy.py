@@ -16,14 +16,14 @@ ROW_PARAMS = [(n, p) for n in sc.ROW_ROUTES for p in sc.ROW_PALETTES[n]]
 
 
 def device_colstat(c):
-    """colstats() of the case as a resident operand: f(op, na_rm, center) -> host array."""
+    """colstats() of the case as a resident operand: f(op, na_rm, center) -> (host array, warn word set)."""
     from sparsearray_amd import device
     A = device.DeviceCSC.from_host(c.nrow, c.col_ptr, c.row_idx, c.val)
     assert device.colstats_form(A, c.inner)[0] == c.form
 
     def f(op, na_rm, center):
-        out, _ = device.colstats(A, op, na_rm, float("nan") if center is None else float(center), c.inner)
-        return out.cpu().numpy()
+        out, warn = device.colstats(A, op, na_rm, float("nan") if center is None else float(center), c.inner)
+        return out.cpu().numpy(), bool(warn.cpu().numpy().any())
     return f
 
 
