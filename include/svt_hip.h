@@ -875,6 +875,84 @@ int svt_subset_SVT_begin(const svt_view *x, const int *rows, int64_t nrows_sel, 
 			 svt_subset_result **res, int64_t *out_nnz);
 int svt_subset_SVT_end(svt_subset_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val);
 
+/* Arith and Math on SVT operands (C_Arith_SVT1_SVT2, C_Arith_SVT1_v2, C_unary_minus_SVT, C_Math_SVT;
+   R/SparseArray-Arith-methods.R, R/SparseArray-Math-methods.R; the element rules of src/SparseVec_Arith.c and
+   src/SparseVec_Math.c): the result is a new sparse operand in the device layout.  Two families (kernels_arith.hip):
+
+     merge  x op y, op one of SVT_ARITH_ADD / _SUB / _MULT, for two operands of the same nrow and the same number of
+            leaves (N-d operands are leaves x rows), each REALSXP or INTSXP.  At every position stored in x or in y the
+            value is op(x or 0, y or 0) in the result's type, and it is stored unless it == 0 (-0.0 and integer 0 too;
+            NaN, NA and +-Inf stay -- which is what `*` against an implicit zero keeps).  A stored zero of an operand is
+            an ordinary value.  int op int is int: computed in double, a result <= INT_MIN or > INT_MAX is NA_integer_
+            and raises the overflow flag, NA_integer_ propagates.  With a double side the result is double and
+            NA_integer_ becomes NA_real_.
+     map    f(v) on the stored values of one operand, stored unless f(v) == 0.  kind SVT_ARITH_SCALAR: x op s, op one of
+            _MULT _DIV _POW _MOD _IDIV with the scalar s of type s_Rtype (an INTSXP s is passed as its double value);
+            / and ^ give double, an INTSXP x with an INTSXP s stays int (overflow as above; %% takes the sign of the
+            divisor, %/% floors), anything else is computed in double by R's rules for the operators.  kind
+            SVT_ARITH_NEG: -x, the type kept.  kind SVT_ARITH_MATH: one of SVT_MATH_ABS .. SVT_MATH_EXPM1 on a REALSXP
+            operand; SVT_MATH_SIN .. SVT_MATH_SIGNIF (the rest of the reference's list) answer > 0.
+
+   Both cut their work into tiles of svt_dev_arith_tile() entries (of x for the map, of the merged sequence of
+   x->nnz + y->nnz entries for the merge), place every result entry by 64-bit prefix sums, keep the rows ascending
+   inside every result column and give the same bits on every run.  `_count` writes out_col_ptr int64[ncol + 1], returns
+   *out_nnz and synchronises `stream` once; `_fill` is asynchronous, reads the workspace as the count call left it
+   (same operands, same operation), writes out_row_idx int32[*out_nnz] and out_val (svt_dev_arith_out_Rtype()), and ORs
+   1 into the device word `ovflow` (may be NULL) when an integer result overflowed.  Status: < 0 for extents that
+   differ, a workspace below svt_dev_arith_*_ws_bytes(), an unknown kind or opcode or one the family does not take, an
+   LGLSXP operand, a Math operation on an INTSXP operand; > 0 for an operand with na_background (the reference has
+   separate NaArray methods) and for the Math operations listed above.  On a non-zero status nothing is written outside
+   `ws`.  Alignment as for svt_dev_transpose(). */
+enum { SVT_ARITH_ADD = 1, SVT_ARITH_SUB = 2, SVT_ARITH_MULT = 3, SVT_ARITH_DIV = 4, SVT_ARITH_POW = 5, SVT_ARITH_MOD = 6,
+       SVT_ARITH_IDIV = 7 };
+enum { SVT_MATH_ABS = 1, SVT_MATH_SIGN = 2, SVT_MATH_SQRT = 3, SVT_MATH_FLOOR = 4, SVT_MATH_CEILING = 5, SVT_MATH_TRUNC = 6,
+       SVT_MATH_LOG1P = 7, SVT_MATH_EXPM1 = 8,
+       SVT_MATH_SIN = 9, SVT_MATH_ASIN = 10, SVT_MATH_SINH = 11, SVT_MATH_ASINH = 12, SVT_MATH_SINPI = 13, SVT_MATH_TAN = 14,
+       SVT_MATH_ATAN = 15, SVT_MATH_TANH = 16, SVT_MATH_ATANH = 17, SVT_MATH_TANPI = 18, SVT_MATH_ROUND = 19,
+       SVT_MATH_SIGNIF = 20 };
+enum { SVT_ARITH_MERGE = 0, SVT_ARITH_SCALAR = 1, SVT_ARITH_NEG = 2, SVT_ARITH_MATH = 3 };
+int svt_dev_arith_tile(void);
+/* SVT_INTSXP or SVT_REALSXP: the type of the result; 0 for a combination no family takes.  y_Rtype: the second
+   operand's or the scalar's type (not read for _NEG and _MATH).  Needs no GPU. */
+int svt_dev_arith_out_Rtype(int kind, int op, int x_Rtype, int y_Rtype);
+size_t svt_dev_arith_merge_ws_bytes(int64_t ncol, int64_t x_nnz, int64_t y_nnz);
+int svt_dev_arith_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr, int64_t *out_nnz,
+			      void *ws, size_t ws_bytes, void *stream);
+int svt_dev_arith_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+			     int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream);
+size_t svt_dev_arith_map_ws_bytes(int64_t ncol, int64_t nnz);
+int svt_dev_arith_map_count(const svt_dev_csc *x, int kind, int op, double s, int s_Rtype, int64_t *out_col_ptr,
+			    int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_arith_map_fill(const svt_dev_csc *x, int kind, int op, double s, int s_Rtype, const int64_t *out_col_ptr,
+			   int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream);
+/* The compositions count -> allocate -> fill, one per family, over the allocator of svt_dev_subset(): the workspace
+   comes from `alloc` and goes back through `release`; the three result arrays (*out_col_ptr int64[ncol + 1];
+   *out_row_idx, *out_val of at least one element, *out_Rtype their type) are the caller's to release.  `ovflow`: a
+   device word the caller zeroed, or NULL.  Synchronise `stream` once; the fill is still queued on return. */
+int svt_dev_arith_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+			void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+			void **out_val, int *ovflow, void *stream);
+int svt_dev_arith_map(const svt_dev_csc *x, int kind, int op, double s, int s_Rtype, svt_dev_alloc_fn alloc,
+		      svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr,
+		      int32_t **out_row_idx, void **out_val, int *ovflow, void *stream);
+
+/* Host level.  begin uploads the operand(s) (through the resident cache when it is on), runs the composition on the
+   first device of the list (not sharded) and leaves the result on the device: *out_Rtype its type, *out_nnz its
+   nonzero count, *ovflow set to 1 when an integer result overflowed ("NAs produced by integer overflow": the caller
+   warns); its extents are x's.  svt_Arith_SVT_end copies it into out_col_ptr int64[nleaves + 1], out_row_idx
+   int32[nnz], out_val and releases it; all three NULL: release only.  The dims of x and y must be identical (< 0:
+   "non-conformable arrays").  What the R methods check before the call (the operations that would not stay sparse, the
+   scalar's value) is the caller's business: the library computes what it is asked.  `digits` of svt_Math_SVT_begin is
+   read by SVT_MATH_ROUND / _SIGNIF only, which answer > 0. */
+typedef struct svt_arith_result svt_arith_result;
+int svt_Arith_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int *out_Rtype,
+			    int64_t *out_nnz, int *ovflow);
+int svt_Arith_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res, int *out_Rtype,
+			       int64_t *out_nnz, int *ovflow);
+int svt_unary_minus_SVT_begin(const svt_view *x, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
+int svt_Math_SVT_begin(const svt_view *x, int op, double digits, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
+int svt_Arith_SVT_end(svt_arith_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val);
+
 #ifdef __cplusplus
 }
 #endif

@@ -362,6 +362,38 @@ class CAbiDispatcher:
         return self._csc_result(x, new_dim, int(nnz.value), dn,
                                 lambda cp, ri, vv: self._run("subset_SVT_end", res, cp, ri, vv))
 
+    # Arith / unary minus / Math (src/SparseArray_Arith_methods.c, src/SparseArray_Math_methods.c; include/svt_hip.h; HIP
+    # library only): begin leaves the result on the device and says its type and size, end copies it out --------------
+    def _arith(self, begin, x, args, dimnames, with_ovflow=True):
+        """The SVT_SparseArray of x's dim that ``svt_<begin>(x, *args, &res, &Rtype, &nnz[, &ovflow])`` computes, and
+        the overflow flag."""
+        res, rt, nnz, ov = c_void_p(0), c_int(0), ctypes.c_int64(0), c_int(0)
+        self._run(begin, x, *args, byref(res), byref(rt), byref(nnz), *([byref(ov)] if with_ovflow else []))
+        n = int(nnz.value)
+        type_ = "double" if rt.value == REALSXP else "integer"
+        cp = np.zeros(int(np.prod(x.dim[1:], dtype=np.int64)) + 1, dtype=np.int64)
+        ri = np.zeros(max(n, 1), dtype=np.int32)
+        vv = np.zeros(max(n, 1), dtype=np.float64 if type_ == "double" else np.int32)
+        self._run("Arith_SVT_end", res, cp, ri, vv)
+        return SVT_SparseArray.from_csc(tuple(x.dim), type_, cp, ri[:n], vv[:n], dimnames=dimnames), bool(ov.value)
+
+    def C_Arith_SVT1_SVT2(self, x: SVT_SparseArray, y: SVT_SparseArray, op: str):
+        """Returns (x op y, overflow flag); the dimnames are the first non-NULL ones."""
+        from .api import ARITH_OPCODES
+        return self._arith("Arith_SVT_SVT_begin", x, (y, ARITH_OPCODES[op]), x.dimnames if x.dimnames is not None else y.dimnames)
+
+    def C_Arith_SVT1_v2(self, x: SVT_SparseArray, y: float, y_type: str, op: str):
+        """Returns (x op y, overflow flag) for the scalar ``y`` of R type ``y_type`` ("integer" / "double")."""
+        from .api import ARITH_OPCODES
+        return self._arith("Arith_SVT_scalar_begin", x, (ARITH_OPCODES[op], float(y), _RT[y_type]), x.dimnames)
+
+    def C_unary_minus_SVT(self, x: SVT_SparseArray):
+        return self._arith("unary_minus_SVT_begin", x, (), x.dimnames, with_ovflow=False)[0]
+
+    def C_Math_SVT(self, x: SVT_SparseArray, op: str, digits: float):
+        from .api import MATH_OPCODES
+        return self._arith("Math_SVT_begin", x, (MATH_OPCODES.get(op, 0), float(digits)), x.dimnames, with_ovflow=False)[0]
+
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""
         return self._dgc("rowsum_dgCMatrix", x, group, ngroup, na_rm,

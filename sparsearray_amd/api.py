@@ -11,6 +11,7 @@ as ``src/R_init_SparseArray.c:94,121-134``:
     C_rowsum_dgCMatrix    C_colsum_dgCMatrix
     C_colMins_dgCMatrix   C_colMaxs_dgCMatrix   C_colRanges_dgCMatrix  C_colVars_dgCMatrix
     C_transpose_2D_SVT    C_aperm_SVT           C_subset_SVT_by_Nindex (2-D operands)
+    C_Arith_SVT1_SVT2     C_Arith_SVT1_v2       C_unary_minus_SVT      C_Math_SVT (HIP library only)
 
 and the entry points the HIP library adds to them (include/svt_hip.h):
 
@@ -53,6 +54,15 @@ _SUPPORTED_MULT_TYPES = ("double", "integer")
 
 # ties.method of colRanks / rowRanks -> SVT_TIES_* (include/svt_hip.h)
 TIES_METHODS = {"max": 0, "average": 1, "min": 2, "dense": 3}
+
+# Arith operators -> SVT_ARITH_*, Math functions -> SVT_MATH_* (include/svt_hip.h).  MATH_OPCODES is SUPPORTED_MATH_OPS
+# of R/SparseArray-Math-methods.R:25-30 plus round / signif, in the header's order.
+ARITH_OPCODES = {"+": 1, "-": 2, "*": 3, "/": 4, "^": 5, "%%": 6, "%/%": 7}
+MATH_OPCODES = {name: k + 1 for k, name in enumerate(
+    ("abs", "sign", "sqrt", "floor", "ceiling", "trunc", "log1p", "expm1", "sin", "asin", "sinh", "asinh", "sinpi",
+     "tan", "atan", "tanh", "atanh", "tanpi", "round", "signif"))}
+_SUPPORTED_MATH_OPS = tuple(MATH_OPCODES)[:18]
+_ARITH_INPUT_TYPES = ("integer", "double")      # (and "complex", which no SVT_SparseArray of this package has)
 
 
 # row statistics that C_rowStats_SVT does not take: one C_rowStatsFull_SVT call where the library has it
@@ -598,6 +608,126 @@ class Session:
             raise SparseArrayError("incorrect number of subscripts")
         index = [self._check_Nindex(s, d) for s, d in zip(index, x.dim)]
         return self.SparseArray_Call("C_subset_SVT_by_Nindex", x, *index)
+
+    # ------------------------------------------------------------------
+    # Arith, unary minus, Math  (R/SparseArray-Arith-methods.R, R/SparseArray-Math-methods.R)
+    # ------------------------------------------------------------------
+    def _optional_entry(self, name: str, symbol: str):
+        """Entry points the reference has and only the HIP library backs (``symbol``: its function behind ``name``)."""
+        if not self._has("C_" + symbol):
+            raise SparseArrayUnsupported(f"{name} is not offered by this session's library")
+
+    @staticmethod
+    def _check_Arith_input_type(type_: str, what: str):
+        # check_Arith_input_type, R/SparseArray-Arith-methods.R:15-20
+        if type_ not in _ARITH_INPUT_TYPES:
+            raise SparseArrayError(f"arithmetic operation not supported on {what} of type() \"{type_}\"")
+
+    @staticmethod
+    def _sparsity_not_preserved(op: str, when: str):
+        # error_on_left_sparsity_not_preserved, R/SparseArray-Arith-methods.R:25-36
+        msg = f"'x {op} y' and 'y {op} x': operations" if op in ("+", "*") else f"x {op} y: operation"
+        raise SparseArrayError(f"{msg} not supported on SparseArray object x when {when} (result wouldn't be sparse)")
+
+    @staticmethod
+    def _scalar_class_type(y):
+        """(class(y), type(y), length, value) of the R vector a Python scalar or sequence stands for"""
+        a = np.asarray(y)
+        if a.dtype == np.bool_:
+            cls = typ = "logical"
+        elif np.issubdtype(a.dtype, np.integer) and (a.size == 0 or (a.min() >= -2 ** 31 and a.max() < 2 ** 31)):
+            cls = typ = "integer"
+        elif np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating):
+            cls, typ = "numeric", "double"
+        elif np.issubdtype(a.dtype, np.complexfloating):
+            cls = typ = "complex"
+        else:
+            cls = typ = "character" if a.dtype.kind in "US" else "list"
+        return cls, typ, int(a.size), (a.reshape(-1)[0] if a.size else None)
+
+    def _warn_overflow(self, ans_and_flag):
+        ans, ovflow = ans_and_flag
+        if ovflow:
+            warnings.warn("NAs produced by integer overflow")
+        return ans
+
+    def _Arith_SVT1_v2(self, op, x, y):
+        # .Arith_SVT1_v2, R/SparseArray-Arith-methods.R:95-133
+        self._check_Arith_input_type(x.type, "SparseArray object")
+        cls, ytype, length, v = self._scalar_class_type(y)
+        if ytype not in _ARITH_INPUT_TYPES:
+            raise SparseArrayError(f"arithmetic operations between SparseArray objects and {cls} vectors are not supported")
+        if op not in ("*", "/", "^", "%%", "%/%"):
+            raise SparseArrayError(f"\"{op}\" is not supported between a SparseArray object and a {cls} vector "
+                                   "(result wouldn't be sparse in general)")
+        if length != 1:
+            raise SparseArrayError("arithmetic operations are not supported between a SparseArray object and a vector "
+                                   "of length != 1")
+        if (ytype == "integer" and int(v) == NA_integer) or (ytype == "double" and np.isnan(v)):
+            self._sparsity_not_preserved(op, "y is NA or NaN")
+        if op == "*" and ytype == "double" and np.isinf(v):
+            self._sparsity_not_preserved(op, "y is Inf or -Inf")
+        if op == "^" and v <= 0:
+            self._sparsity_not_preserved(op, "y is non-positive")
+        if op != "*" and v == 0:
+            self._sparsity_not_preserved(op, "y == 0")
+        if (x.type == "double" and ytype == "integer") or op in ("/", "^"):
+            ytype = "double"
+        self._optional_entry("C_Arith_SVT1_v2", "Arith_SVT_scalar_begin")
+        return self._warn_overflow(self.SparseArray_Call("C_Arith_SVT1_v2", x, float(v), ytype, op))
+
+    def _Arith_SVT1_SVT2(self, op, x, y):
+        # .Arith_SVT1_SVT2, R/SparseArray-Arith-methods.R:152-185
+        self._check_Arith_input_type(x.type, "SparseArray object")
+        self._check_Arith_input_type(y.type, "SparseArray object")
+        if op not in ("+", "-", "*"):
+            raise SparseArrayError(f"\"{op}\" is not supported between SparseArray objects "
+                                   "(result wouldn't be sparse in general)")
+        if tuple(x.dim) != tuple(y.dim):
+            raise SparseArrayError("non-conformable arrays")
+        self._optional_entry("C_Arith_SVT1_SVT2", "Arith_SVT_SVT_begin")
+        return self._warn_overflow(self.SparseArray_Call("C_Arith_SVT1_SVT2", x, y, op))
+
+    def arith(self, op: str, e1, e2):
+        """``e1 op e2`` of the Arith group with an SVT_SparseArray on at least one side: two arrays of the same dim
+        (``+ - *``), or an array and a scalar (``* / ^ %% %/%``; on the left only for ``*``).  A Python int is an R
+        integer, a float a double.  Integer overflow warns "NAs produced by integer overflow"."""
+        if op not in ARITH_OPCODES:
+            raise SparseArrayError(f"invalid Arith operation \"{op}\"")
+        s1, s2 = isinstance(e1, SVT_SparseArray), isinstance(e2, SVT_SparseArray)
+        if s1 and s2:
+            return self._Arith_SVT1_SVT2(op, e1, e2)
+        if s1:
+            return self._Arith_SVT1_v2(op, e1, e2)
+        if not s2:
+            raise SparseArrayError("arith() needs an SVT_SparseArray operand")
+        if op != "*":                                       # R/SparseArray-Arith-methods.R:139-148
+            raise SparseArrayError(f"\"{op}\" is not supported between a {self._scalar_class_type(e1)[0]} vector on "
+                                   "the left and an SVT_SparseArray object on the right (result wouldn't be sparse "
+                                   "in general)")
+        return self._Arith_SVT1_v2(op, e2, e1)
+
+    def unary_minus(self, x):
+        # .unary_minus_SparseArray, R/SparseArray-Arith-methods.R:65-78
+        self._check_Arith_input_type(x.type, "SparseArray object")
+        self._optional_entry("C_unary_minus_SVT", "unary_minus_SVT_begin")
+        return self.SparseArray_Call("C_unary_minus_SVT", x)
+
+    def math(self, op: str, x, digits=None):
+        """A member of the Math group that propagates zeros, or ``round`` / ``signif`` with ``digits``
+        (R/SparseArray-Math-methods.R:39-81), on an object of type "double"."""
+        if op in ("round", "signif"):
+            digits = {"round": 0, "signif": 6}[op] if digits is None else digits
+        elif op not in _SUPPORTED_MATH_OPS:
+            raise SparseArrayError(f"{op}() is not supported on SparseArray objects (result wouldn't be sparse in general)")
+        if x.type != "double":
+            raise SparseArrayError(f"the {op}() method for SVT_SparseArray objects only supports input of type \"double\" "
+                                   "at the moment")
+        if op in ("round", "signif") and (isinstance(digits, (bool, np.bool_)) or np.ndim(digits) != 0
+                                          or not isinstance(digits, (int, float, np.integer, np.floating))):
+            raise SparseArrayError("'digits' must be a single number")
+        self._optional_entry("C_Math_SVT", "Math_SVT_begin")
+        return self.SparseArray_Call("C_Math_SVT", x, op, 0.0 if digits is None else float(digits))
 
     def _OLD_rowStats(self, op, x, na_rm, center, dims):
         # .OLD_rowStats_SparseArray (:122-190): "aperm(colStats(aperm(x), dims=ndim-dims))",

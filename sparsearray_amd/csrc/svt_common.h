@@ -270,6 +270,33 @@ int launch_subset_rows_count(const int64_t *col_ptr, const int32_t *row_idx, int
 int launch_subset_rows_fill(const int32_t *row_idx, const void *val, int Rtype, int64_t nrow, int64_t ncol, int64_t nnz,
 			    int32_t *out_row_idx, void *out_val, const void *ws, hipStream_t s);
 
+// Arith and Math (kernels_arith.hip): the map f(x) and the merge x op y, each a count launcher that leaves out_col_ptr
+// and, in the head of `ws`, [int64 at byte 8: the nonzeros of the result], and a fill launcher that reads `ws` as the
+// count launcher left it.  All asynchronous.  `entries`: nnz for the map, nnz(x) + nnz(y) for the merge.
+struct ArithMapArgs {
+	const int64_t *col_ptr;
+	const int32_t *row_idx;
+	const void *val;
+	int Rtype;
+	int64_t ncol, nnz;
+	int kind, op;           // SVT_ARITH_SCALAR / _NEG / _MATH and its opcode
+	double sd;              // the scalar, as a double and as an integer
+	int32_t si;
+	int out_Rtype;
+};
+struct ArithMergeArgs {
+	const int64_t *x_col_ptr; const int32_t *x_row_idx; const void *x_val; int x_Rtype; int64_t x_nnz;
+	const int64_t *y_col_ptr; const int32_t *y_row_idx; const void *y_val; int y_Rtype; int64_t y_nnz;
+	int64_t nrow, ncol;
+	int op;
+};
+int arith_tile(void);
+size_t arith_ws_bytes(int64_t ncol, int64_t entries, int merge);
+int launch_arith_map_count(const ArithMapArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_arith_map_fill(const ArithMapArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
+int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
+
 void aperm_route_counts(int64_t *out, int reset);
 size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim);
 // aperm, with the boxed driver for the permutations that move the rows past the box limit (read once per call and

@@ -7,6 +7,7 @@
 // launch the kernels and copy the result back.  No arithmetic of the hot path
 // happens on the host.
 #include "svt_common.h"
+#include "svt_arith_rules.h"
 #include <unistd.h>
 
 #include <stdarg.h>
@@ -19,6 +20,7 @@
 #include <chrono>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <vector>
 
@@ -1465,6 +1467,175 @@ extern "C" int svt_dev_subset(const svt_dev_csc *A, const int32_t *rows, int64_t
 	});
 }
 
+// ---- Arith and Math (kernels_arith.hip; the element rules in svt_arith_rules.h) ----
+extern "C" int svt_dev_arith_tile(void)
+{
+	return arith_tile();
+}
+extern "C" int svt_dev_arith_out_Rtype(int kind, int op, int x_Rtype, int y_Rtype)
+{
+	return svt_rule_out_Rtype(kind, op, x_Rtype, y_Rtype);
+}
+extern "C" size_t svt_dev_arith_merge_ws_bytes(int64_t ncol, int64_t x_nnz, int64_t y_nnz)
+{
+	return arith_ws_bytes(ncol, (x_nnz > 0 ? x_nnz : 0) + (y_nnz > 0 ? y_nnz : 0), 1);
+}
+extern "C" size_t svt_dev_arith_map_ws_bytes(int64_t ncol, int64_t nnz)
+{
+	return arith_ws_bytes(ncol, nnz, 0);
+}
+
+// the statuses that depend on the operation and the operands alone; *out_Rtype <- the type of the result
+static int arith_check(const char *who, int kind, int op, const svt_dev_csc *x, const svt_dev_csc *y, int s_Rtype, int *out_Rtype)
+{
+	if (x == NULL || (kind == SVT_ARITH_MERGE && y == NULL))
+		return svt_set_error("%s: an operand is needed", who);
+	if (x->Rtype == SVT_LGLSXP || (y != NULL && y->Rtype == SVT_LGLSXP))
+		return svt_set_error("arithmetic operation not supported on SparseArray object of type() \"logical\"");
+	if (y != NULL && (x->nrow != y->nrow || x->ncol != y->ncol))
+		return svt_set_error("non-conformable arrays");
+	if (kind == SVT_ARITH_MATH && op >= SVT_MATH_ABS && op <= SVT_MATH_SIGNIF && x->Rtype != SVT_REALSXP)
+		return svt_set_error("%s: Math operations take operands of type \"double\" only", who);
+	const int rt = svt_rule_out_Rtype(kind, op, x->Rtype, y != NULL ? y->Rtype : s_Rtype);
+	if (rt == 0 && !(kind == SVT_ARITH_MATH && op > SVT_MATH_EXPM1 && op <= SVT_MATH_SIGNIF))
+		return svt_set_error("%s: unknown operation (kind %d, opcode %d) or operand type", who, kind, op);
+	if (x->na_background || (y != NULL && y->na_background))
+		return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+	if (rt == 0)
+		return svt_set_unsupported("%s: Math opcode %d is not supported here", who, op);
+	*out_Rtype = rt;
+	return 0;
+}
+
+static ArithMergeArgs arith_merge_args(const svt_dev_csc *x, const svt_dev_csc *y, int op)
+{
+	ArithMergeArgs a;
+	a.x_col_ptr = x->col_ptr; a.x_row_idx = x->row_idx; a.x_val = x->val; a.x_Rtype = x->Rtype; a.x_nnz = x->nnz;
+	a.y_col_ptr = y->col_ptr; a.y_row_idx = y->row_idx; a.y_val = y->val; a.y_Rtype = y->Rtype; a.y_nnz = y->nnz;
+	a.nrow = x->nrow; a.ncol = x->ncol; a.op = op;
+	return a;
+}
+static ArithMapArgs arith_map_args(const svt_dev_csc *x, int kind, int op, double s, int out_Rtype)
+{
+	ArithMapArgs a;
+	a.col_ptr = x->col_ptr; a.row_idx = x->row_idx; a.val = x->val; a.Rtype = x->Rtype; a.ncol = x->ncol; a.nnz = x->nnz;
+	a.kind = kind; a.op = op; a.sd = s; a.out_Rtype = out_Rtype;
+	a.si = out_Rtype == SVT_INTSXP && kind == SVT_ARITH_SCALAR ? (int32_t) s : 0;
+	return a;
+}
+
+// One operation of either family (y == NULL: the map), the one statement of the checks and of count / fill.
+struct ArithCall {
+	const char *who;
+	int kind, op;
+	const svt_dev_csc *x, *y;
+	double s;
+	int s_Rtype;
+	int out_Rtype = 0;
+	size_t need() const
+	{
+		return y != NULL ? svt_dev_arith_merge_ws_bytes(x->ncol, x->nnz, y->nnz) : arith_ws_bytes(x->ncol, x->nnz, 0);
+	}
+	int check(size_t ws_bytes)
+	{
+		if (arith_check(who, kind, op, x, y, s_Rtype, &out_Rtype))
+			return -1;
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		return 0;
+	}
+	int count(int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+	{
+		if (check(ws_bytes))
+			return -1;
+		hipStream_t st = (hipStream_t) stream;
+		if (y != NULL ? launch_arith_merge_count(arith_merge_args(x, y, op), out_col_ptr, ws, st)
+			      : launch_arith_map_count(arith_map_args(x, kind, op, s, out_Rtype), out_col_ptr, ws, st))
+			return -1;
+		int flag = 0;
+		return subset_read_head(ws, st, &flag, out_nnz);
+	}
+	int fill(int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream)
+	{
+		if (check(ws_bytes))
+			return -1;
+		hipStream_t st = (hipStream_t) stream;
+		return y != NULL ? launch_arith_merge_fill(arith_merge_args(x, y, op), out_row_idx, out_val, ovflow, ws, st)
+				 : launch_arith_map_fill(arith_map_args(x, kind, op, s, out_Rtype), out_row_idx, out_val, ovflow, ws, st);
+	}
+	// count -> allocate -> fill over the caller's allocator
+	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype_p, int64_t *out_nnz,
+		    int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, int *ovflow, void *stream)
+	{
+		if (alloc == NULL || release == NULL)
+			return svt_set_error("%s: an allocator is needed", who);
+		if (check(need()))
+			return -1;
+		SubsetMem mem = { alloc, release, ctx };
+		SubsetCsc R(mem);
+		SubsetWs ws(mem);
+		int64_t nnz = 0;
+		if (R.shape(x, x->nrow, x->ncol) || ws.get(need()))
+			return -1;
+		R.c.Rtype = out_Rtype;
+		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, stream) || R.entries(nnz) ||
+		    fill(R.c.row_idx, R.c.val, ovflow, ws.p, ws.n, stream))
+			return -1;
+		*out_Rtype_p = out_Rtype;
+		*out_nnz = nnz;
+		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
+		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
+		return 0;
+	}
+};
+
+extern "C" int svt_dev_arith_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr,
+					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = { "svt_dev_arith_merge_count", SVT_ARITH_MERGE, op, x, y, 0.0, 0 };
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_arith_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+					int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes,
+					void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile prefixes in `ws` place the entries)
+	ArithCall c = { "svt_dev_arith_merge_fill", SVT_ARITH_MERGE, op, x, y, 0.0, 0 };
+	return abi_status([&] { return c.fill(out_row_idx, out_val, ovflow, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_arith_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc,
+				   svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr,
+				   int32_t **out_row_idx, void **out_val, int *ovflow, void *stream)
+{
+	ArithCall c = { "svt_dev_arith_merge", SVT_ARITH_MERGE, op, x, y, 0.0, 0 };
+	return abi_status([&] {
+		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, ovflow, stream);
+	});
+}
+extern "C" int svt_dev_arith_map_count(const svt_dev_csc *x, int kind, int op, double s, int s_Rtype, int64_t *out_col_ptr,
+				       int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = { "svt_dev_arith_map_count", kind == SVT_ARITH_MERGE ? -1 : kind, op, x, NULL, s, s_Rtype };
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_arith_map_fill(const svt_dev_csc *x, int kind, int op, double s, int s_Rtype, const int64_t *out_col_ptr,
+				      int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes,
+				      void *stream)
+{
+	(void) out_col_ptr;
+	ArithCall c = { "svt_dev_arith_map_fill", kind == SVT_ARITH_MERGE ? -1 : kind, op, x, NULL, s, s_Rtype };
+	return abi_status([&] { return c.fill(out_row_idx, out_val, ovflow, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_arith_map(const svt_dev_csc *x, int kind, int op, double s, int s_Rtype, svt_dev_alloc_fn alloc,
+				 svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr,
+				 int32_t **out_row_idx, void **out_val, int *ovflow, void *stream)
+{
+	ArithCall c = { "svt_dev_arith_map", kind == SVT_ARITH_MERGE ? -1 : kind, op, x, NULL, s, s_Rtype };
+	return abi_status([&] {
+		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, ovflow, stream);
+	});
+}
+
 // A %*% B, both sparse (kernels_spmm.hip): out[r + k * ldo], r < A->nrow, k < B->ncol.
 extern "C" size_t svt_dev_matmul_csc_csc_ws_bytes(const svt_dev_csc *A)
 {
@@ -2714,27 +2885,128 @@ extern "C" int svt_subset_SVT_begin(const svt_view *x, const int *rows, int64_t 
 	return abi_status([&] { return subset_SVT_begin_impl(x, rows, nrows_sel, cols, ncols_sel, res, out_nnz); });
 }
 
-static int subset_SVT_end_impl(svt_subset_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
+// The `end` of a begin / end pair: the result a `begin` left on the device copied out (all three outputs, or none:
+// release only) and released.
+static int result_end(const char *who, svt_dev_csc *h, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
 {
-	if (res == NULL) return 0;
-	const svt_dev_csc *h = res->h;
 	int rc = 0;
 	if (out_col_ptr != NULL || out_row_idx != NULL || out_val != NULL) {
 		if (out_col_ptr == NULL || (h->nnz > 0 && (out_row_idx == NULL || out_val == NULL)))
-			rc = svt_set_error("svt_subset_SVT_end: all three outputs, or none");
+			rc = svt_set_error("%s: all three outputs, or none", who);
 		else if (hipMemcpy(out_col_ptr, h->col_ptr, ((size_t) h->ncol + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess)
-			rc = svt_set_error("svt_subset_SVT_end: D2H copy failed");
+			rc = svt_set_error("%s: D2H copy failed", who);
 		else if (h->nnz > 0 && (staged_download(out_row_idx, h->row_idx, (size_t) h->nnz * 4) ||
 					staged_download(out_val, h->val, (size_t) h->nnz * elt_size(h->Rtype))))
 			rc = -1;
 	}
-	svt_release(res->h);
+	svt_release(h);
+	return rc;
+}
+
+static int subset_SVT_end_impl(svt_subset_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
+{
+	if (res == NULL) return 0;
+	const int rc = result_end("svt_subset_SVT_end", res->h, out_col_ptr, out_row_idx, out_val);
 	free(res);
 	return rc;
 }
 extern "C" int svt_subset_SVT_end(svt_subset_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
 {
 	return abi_status([&] { return subset_SVT_end_impl(res, out_col_ptr, out_row_idx, out_val); });
+}
+
+// Arith / Math on host operands (C_Arith_SVT1_SVT2, C_Arith_SVT1_v2, C_unary_minus_SVT, C_Math_SVT): the operands go
+// up through the resident cache, ArithCall::compose() runs on the first device, the result stays there until `end`.
+struct svt_arith_result {
+	svt_dev_csc *h;              // owns its buffers
+};
+
+static int arith_begin_impl(const char *who, int kind, int op, const svt_view *x, const svt_view *y, double s, int s_Rtype,
+			    svt_arith_result **res, int *out_Rtype, int64_t *out_nnz, int *ovflow)
+{
+	if (res == NULL || out_Rtype == NULL || out_nnz == NULL)
+		return svt_set_error("%s: 'res', 'out_Rtype' and 'out_nnz' are needed", who);
+	*res = NULL;
+	if (ensure_init() || check_view(x) || (y != NULL && check_view(y)))
+		return -1;
+	if (y != NULL) {
+		bool same = x->ndim == y->ndim;
+		for (int a = 0; same && a < x->ndim; a++) same = x->dim[a] == y->dim[a];
+		if (!same) return svt_set_error("non-conformable arrays");
+	}
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	std::optional<CscGuard> B;
+	if (y != NULL) {
+		B.emplace(y);
+		if (B->h == NULL) return -1;
+	}
+	DevFlag ov;
+	if (ov.init()) return -1;
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
+	ArithCall c = { who, kind, op, A.h, B ? B->h : NULL, s, s_Rtype };
+	int rt = 0;
+	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, ov.ptr(), NULL) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
+		svt_release(h);
+		return -1;
+	}
+	h->Rtype = rt;
+	int raised = 0;
+	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
+	if (ov.read(&raised) || r == NULL) {
+		svt_release(h);
+		free(r);
+		return r == NULL ? svt_set_error("out of memory") : -1;
+	}
+	r->h = h;
+	*res = r;
+	*out_Rtype = rt;
+	*out_nnz = h->nnz;
+	if (ovflow != NULL) *ovflow = raised;
+	return 0;
+}
+extern "C" int svt_Arith_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int *out_Rtype,
+				       int64_t *out_nnz, int *ovflow)
+{
+	return abi_status([&] {
+		if (y == NULL) return svt_set_error("svt_Arith_SVT_SVT_begin: two operands are needed");
+		return arith_begin_impl("svt_Arith_SVT_SVT_begin", SVT_ARITH_MERGE, op, x, y, 0.0, 0, res, out_Rtype, out_nnz, ovflow);
+	});
+}
+extern "C" int svt_Arith_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res,
+					  int *out_Rtype, int64_t *out_nnz, int *ovflow)
+{
+	return abi_status([&] {
+		return arith_begin_impl("svt_Arith_SVT_scalar_begin", SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype, res, out_Rtype, out_nnz,
+					ovflow);
+	});
+}
+extern "C" int svt_unary_minus_SVT_begin(const svt_view *x, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
+{
+	return abi_status([&] {
+		return arith_begin_impl("svt_unary_minus_SVT_begin", SVT_ARITH_NEG, 0, x, NULL, 0.0, 0, res, out_Rtype, out_nnz, NULL);
+	});
+}
+extern "C" int svt_Math_SVT_begin(const svt_view *x, int op, double digits, svt_arith_result **res, int *out_Rtype,
+				  int64_t *out_nnz)
+{
+	(void) digits;                                      // (round / signif: not supported here)
+	return abi_status([&] {
+		return arith_begin_impl("svt_Math_SVT_begin", SVT_ARITH_MATH, op, x, NULL, 0.0, 0, res, out_Rtype, out_nnz, NULL);
+	});
+}
+extern "C" int svt_Arith_SVT_end(svt_arith_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
+{
+	return abi_status([&] {
+		if (res == NULL) return 0;
+		const int rc = result_end("svt_Arith_SVT_end", res->h, out_col_ptr, out_row_idx, out_val);
+		free(res);
+		return rc;
+	});
 }
 
 // x %*% y over the device list: shard s takes the rows [r0, r1) of x, transposes them and multiplies them with the

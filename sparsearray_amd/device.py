@@ -112,32 +112,58 @@ class DeviceCSC:
         it.  Every array the composition needs is a torch allocation on the current stream."""
         dev = self.val.device
         sub = [None if v is None else _subscript(v, dev) for v in (rows, cols)]
-        live = {}
-
-        def alloc(nbytes, _ctx):
-            try:
-                t = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-            except RuntimeError:
-                return None
-            live[t.data_ptr()] = t
-            return t.data_ptr()
-
-        def release(p, _ctx):
-            live.pop(p, None)
-
+        mem = _TorchBlocks(dev)
         nnz = c_int64(0)
         out = [c_void_p(0), c_void_p(0), c_void_p(0)]
         _check(_lib().svt_dev_subset(self.handle, *[a for v in sub for a in ((None, -1) if v is None else
                                                                                (v.data_ptr(), v.numel()))],
-                                     ALLOC_FN(alloc), FREE_FN(release), None, ctypes.byref(nnz),
+                                     mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz),
                                      *[ctypes.byref(o) for o in out], _stream()))
-        n = int(nnz.value)
         nrow = self.nrow if sub[0] is None else sub[0].numel()
         ncol = self.ncol if sub[1] is None else sub[1].numel()
-        cp = live[out[0].value].view(torch.int64)[:ncol + 1]
-        ri = live[out[1].value].view(torch.int32)[:n]
-        vv = live[out[2].value].view(self.val.dtype)[:n]
-        return DeviceCSC(nrow, cp, ri, vv, logical=self.Rtype == LGLSXP)
+        return DeviceCSC(nrow, *mem.csc(out, ncol, int(nnz.value), self.val.dtype), logical=self.Rtype == LGLSXP)
+
+    def _arith_result(self, call):
+        """The new DeviceCSC that ``call(alloc, release, ctx, out_Rtype, nnz, col_ptr, row_idx, val, ovflow, stream)`` --
+        one of the two compositions svt_dev_arith_merge / svt_dev_arith_map -- leaves in torch allocations.  Its
+        ``ovflow`` attribute is the device word of the overflow flag (int32 tensor; nonzero once the fill has run: "NAs
+        produced by integer overflow"), left on the device so that the call stays asynchronous after its count."""
+        mem = _TorchBlocks(self.val.device)
+        ovflow = torch.zeros(1, dtype=torch.int32, device=self.val.device)
+        rt, nnz = ctypes.c_int(0), c_int64(0)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt), ctypes.byref(nnz), *[ctypes.byref(o) for o in out],
+                    ovflow.data_ptr(), _stream()))
+        dtype = torch.float64 if rt.value == REALSXP else torch.int32
+        R = DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype))
+        R.ovflow = ovflow
+        return R
+
+    def arith(self, op: str, other):
+        """``self op other`` on the device (include/svt_hip.h, svt_dev_arith_merge / svt_dev_arith_map): ``other`` a
+        DeviceCSC of the same nrow and ncol (op one of + - *) or a scalar (op one of * / ^ %% %/%; a Python int is an
+        R integer, a float a double).  Returns a new DeviceCSC; its ``ovflow`` tensor says whether an integer result
+        overflowed."""
+        from .api import ARITH_OPCODES
+        if op not in ARITH_OPCODES:
+            raise SparseArrayError(f"unknown Arith operation {op!r}")
+        if isinstance(other, DeviceCSC):
+            return self._arith_result(lambda *a: _lib().svt_dev_arith_merge(self.handle, other.handle, ARITH_OPCODES[op], *a))
+        s_Rtype = INTSXP if isinstance(other, (int, np.integer)) and not isinstance(other, (bool, np.bool_)) else REALSXP
+        return self._arith_result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_SCALAR, ARITH_OPCODES[op],
+                                                                      float(other), s_Rtype, *a))
+
+    def neg(self) -> "DeviceCSC":
+        """``-self`` on the device; the type is kept."""
+        return self._arith_result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_NEG, 0, 0.0, 0, *a))
+
+    def math(self, op: str) -> "DeviceCSC":
+        """One of abs sign sqrt floor ceiling trunc log1p expm1 on a double operand; the other zero-preserving members
+        of the Math group raise SparseArrayUnsupported."""
+        from .api import MATH_OPCODES
+        if op not in MATH_OPCODES:
+            raise SparseArrayError(f"unknown Math operation {op!r}")
+        return self._arith_result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_MATH, MATH_OPCODES[op], 0.0, 0, *a))
 
     def __del__(self):
         try:
@@ -146,6 +172,33 @@ class DeviceCSC:
                 self._h = None
         except Exception:
             pass
+
+
+class _TorchBlocks:
+    """svt_dev_alloc_fn / svt_dev_free_fn over torch allocations on the current stream (include/svt_hip.h,
+    svt_dev_subset): a block lives until the library releases it, or, for the result arrays it hands back, as the
+    tensors ``csc()`` returns."""
+
+    def __init__(self, device):
+        self.device, self.live = device, {}
+        self.alloc_fn, self.free_fn = ALLOC_FN(self._alloc), FREE_FN(self._release)
+
+    def _alloc(self, nbytes, _ctx):
+        try:
+            t = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        except RuntimeError:
+            return None
+        self.live[t.data_ptr()] = t
+        return t.data_ptr()
+
+    def _release(self, p, _ctx):
+        self.live.pop(p, None)
+
+    def csc(self, out, ncol, nnz, dtype):
+        """the (col_ptr, row_idx, val) tensors behind the three result pointers ``out``; nothing else is kept"""
+        live, self.live = self.live, {}
+        return (live[out[0].value].view(torch.int64)[:ncol + 1], live[out[1].value].view(torch.int32)[:nnz],
+                live[out[2].value].view(dtype)[:nnz])
 
 
 def _subscript(v, device) -> torch.Tensor:
@@ -159,6 +212,15 @@ def _subscript(v, device) -> torch.Tensor:
         v = torch.as_tensor(a.astype(np.int32).reshape(-1), device=device)
     assert v.dtype == torch.int32 and v.is_cuda
     return v.contiguous().reshape(-1)
+
+
+# kinds of svt_dev_arith_map / svt_dev_arith_out_Rtype (include/svt_hip.h)
+ARITH_MERGE, ARITH_SCALAR, ARITH_NEG, ARITH_MATH = 0, 1, 2, 3
+
+
+def arith_tile() -> int:
+    """Entries per workgroup tile of the Arith / Math kernels (svt_dev_arith_tile).  Needs no GPU."""
+    return int(_hip.load_library().svt_dev_arith_tile())
 
 
 def subset_tile() -> int:
