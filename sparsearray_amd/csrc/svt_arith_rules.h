@@ -121,6 +121,184 @@ SVT_HD inline double svt_rule_arith_double(int op, double x, double y)
 	return svt_rule_nan();
 }
 
+// ---- log1p ----
+// The device library's log1p is within one ulp of the exact value, not the nearest double: on 8747 ordinary arguments
+// 49 results were the neighbour (tests/test_hip_chains.py).  This one computes log(1 + x) in pairs of doubles (a value is
+// h + l, |l| <= ulp(h) / 2; error-free sums and fma products, Dekker / Knuth) to about 2^-95 and rounds once:
+//   1 + x = 2^e (m + ml), m in [0.75, 1.5) -- exact: the rounding error of 1 + x is kept in ml;
+//   r = (m + ml) c - 1 for the tabulated c next to 1 / m, |r| < 2^-7.5, exact up to 2^-106 (c = 1 around m = 1: r = x);
+//   log(1 + x) = e log(2) - log(c) + (r - r^2 / 2 + ... + r^16 / 16)        (the first term left out: 2^-121).
+// Every other argument -- a NaN, x <= -1, +Inf -- is the library's as before, and so is |x| < 2^-54 (below).
+struct svt_dd { double h, l; };
+SVT_HD inline svt_dd svt_dd_sum(double a, double b)             // a + b exactly
+{
+	const double s = a + b, bb = s - a;
+	return svt_dd{ s, (a - (s - bb)) + (b - bb) };
+}
+SVT_HD inline svt_dd svt_dd_sum_ordered(double a, double b)     // the same for |a| >= |b|
+{
+	const double s = a + b;
+	return svt_dd{ s, b - (s - a) };
+}
+SVT_HD inline svt_dd svt_dd_add(svt_dd a, svt_dd b)
+{
+	const svt_dd s = svt_dd_sum(a.h, b.h);
+	return svt_dd_sum_ordered(s.h, s.l + (a.l + b.l));
+}
+SVT_HD inline svt_dd svt_dd_mul(svt_dd a, svt_dd b)
+{
+	const double p = a.h * b.h;
+	return svt_dd_sum_ordered(p, fma(a.h, b.h, -p) + (a.h * b.l + a.l * b.h));
+}
+
+// c = the double nearest 1 / (0.75 + j / 128); (lh, ll) = -log(c): lh the nearest double, ll the nearest double of the rest
+static constexpr double svt_log1p_c[97] = {
+	0x1.5555555555555p+0, 0x1.51d07eae2f815p+0, 0x1.4e5e0a72f0539p+0, 0x1.4afd6a052bf5bp+0, 0x1.47ae147ae147bp+0, 0x1.446f86562d9fbp+0, 0x1.4141414141414p+0, 0x1.3e22cbce4a902p+0, 0x1.3b13b13b13b14p+0, 0x1.3813813813814p+0, 0x1.3521cfb2b78c1p+0, 0x1.323e34a2b10bfp+0, 0x1.2f684bda12f68p+0, 0x1.2c9fb4d812ca0p+0, 0x1.29e4129e4129ep+0, 0x1.27350b8812735p+0, 0x1.2492492492492p+0, 0x1.21fb78121fb78p+0, 0x1.1f7047dc11f70p+0, 0x1.1cf06ada2811dp+0, 0x1.1a7b9611a7b96p+0, 0x1.1811811811812p+0, 0x1.15b1e5f75270dp+0, 0x1.135c81135c811p+0, 0x1.1111111111111p+0, 0x1.0ecf56be69c90p+0, 0x1.0c9714fbcda3bp+0, 0x1.0a6810a6810a7p+0, 0x1.0842108421084p+0, 0x1.0624dd2f1a9fcp+0, 0x1.0410410410410p+0, 0x1.0204081020408p+0, 0x1.0000000000000p+0, 0x1.fc07f01fc07f0p-1, 0x1.f81f81f81f820p-1, 0x1.f44659e4a4271p-1, 0x1.f07c1f07c1f08p-1, 0x1.ecc07b301ecc0p-1, 0x1.e9131abf0b767p-1, 0x1.e573ac901e574p-1, 0x1.e1e1e1e1e1e1ep-1, 0x1.de5d6e3f8868ap-1, 0x1.dae6076b981dbp-1, 0x1.d77b654b82c34p-1, 0x1.d41d41d41d41dp-1, 0x1.d0cb58f6ec074p-1, 0x1.cd85689039b0bp-1, 0x1.ca4b3055ee191p-1, 0x1.c71c71c71c71cp-1, 0x1.c3f8f01c3f8f0p-1, 0x1.c0e070381c0e0p-1, 0x1.bdd2b899406f7p-1, 0x1.bacf914c1bad0p-1, 0x1.b7d6c3dda338bp-1, 0x1.b4e81b4e81b4fp-1, 0x1.b2036406c80d9p-1, 0x1.af286bca1af28p-1, 0x1.ac5701ac5701bp-1, 0x1.a98ef606a63bep-1, 0x1.a6d01a6d01a6dp-1, 0x1.a41a41a41a41ap-1, 0x1.a16d3f97a4b02p-1, 0x1.9ec8e951033d9p-1, 0x1.9c2d14ee4a102p-1, 0x1.999999999999ap-1, 0x1.970e4f80cb872p-1, 0x1.948b0fcd6e9e0p-1, 0x1.920fb49d0e229p-1, 0x1.8f9c18f9c18fap-1, 0x1.8d3018d3018d3p-1, 0x1.8acb90f6bf3aap-1, 0x1.886e5f0abb04ap-1, 0x1.8618618618618p-1, 0x1.83c977ab2beddp-1, 0x1.8181818181818p-1, 0x1.7f405fd017f40p-1, 0x1.7d05f417d05f4p-1, 0x1.7ad2208e0ecc3p-1, 0x1.78a4c8178a4c8p-1, 0x1.767dce434a9b1p-1, 0x1.745d1745d1746p-1, 0x1.724287f46debcp-1, 0x1.702e05c0b8170p-1, 0x1.6e1f76b4337c7p-1, 0x1.6c16c16c16c17p-1, 0x1.6a13cd1537290p-1, 0x1.6816816816817p-1, 0x1.661ec6a5122f9p-1, 0x1.642c8590b2164p-1, 0x1.623fa77016240p-1, 0x1.6058160581606p-1, 0x1.5e75bb8d015e7p-1, 0x1.5c9882b931057p-1, 0x1.5ac056b015ac0p-1, 0x1.58ed2308158edp-1, 0x1.571ed3c506b3ap-1, 0x1.5555555555555p-1
+};
+static constexpr double svt_log1p_l[97][2] = {
+	{ -0x1.269621134db91p-2, -0x1.e0efadd9db02ap-56 },
+	{ -0x1.1bf99635a6b95p-2, 0x1.e9575c2124912p-56 },
+	{ -0x1.1178e8227e47ap-2, -0x1.b8ce2d07f1cb7p-56 },
+	{ -0x1.07138604d5864p-2, 0x1.24e912b16ec8bp-60 },
+	{ -0x1.f991c6cb3b37ap-3, -0x1.ecca0cdf30143p-58 },
+	{ -0x1.e530effe71013p-3, 0x1.f7627ef82f3f0p-57 },
+	{ -0x1.d1037f2655e7bp-3, 0x1.3f3adb7b71cbcp-58 },
+	{ -0x1.bd087383bd8aap-3, 0x1.1165504ad749ep-59 },
+	{ -0x1.a93ed3c8ad9e5p-3, -0x1.bcafa9de97202p-57 },
+	{ -0x1.95a5adcf70182p-3, -0x1.8a16283fdbd1cp-57 },
+	{ -0x1.823c16551a3c0p-3, -0x1.6dcd318f4187ep-57 },
+	{ -0x1.6f0128b756ab9p-3, 0x1.37967087859b9p-59 },
+	{ -0x1.5bf406b543db0p-3, 0x1.1f5b44c0df7f7p-61 },
+	{ -0x1.4913d8333b563p-3, 0x1.0d5604930f137p-58 },
+	{ -0x1.365fcb0159014p-3, -0x1.bea08d2dca256p-57 },
+	{ -0x1.23d712a49c201p-3, -0x1.51c7e9efae297p-57 },
+	{ -0x1.1178e8227e47ap-3, 0x1.0e63a5f01c693p-58 },
+	{ -0x1.fe89139dbd565p-4, 0x1.ac9f4215f9394p-58 },
+	{ -0x1.da7276384469ep-4, -0x1.401fa71733017p-58 },
+	{ -0x1.b6ac88dad5b1dp-4, 0x1.002bf768e52d0p-58 },
+	{ -0x1.9335e5d594988p-4, 0x1.478a85704ccb7p-58 },
+	{ -0x1.700d30aeac0e8p-4, -0x1.a36a677b4c8b2p-59 },
+	{ -0x1.4d3115d207eacp-4, -0x1.da7d0b1e10b2fp-60 },
+	{ -0x1.2aa04a44717a1p-4, -0x1.aea2c72d05c08p-58 },
+	{ -0x1.08598b59e3a06p-4, 0x1.dd7009902bf32p-58 },
+	{ -0x1.ccb73cdddb2d0p-5, 0x1.e48fb0500efd5p-59 },
+	{ -0x1.894aa149fb34bp-5, 0x1.2ba0b44cfaee5p-59 },
+	{ -0x1.466aed42de3f9p-5, 0x1.9badefe942718p-60 },
+	{ -0x1.0415d89e74440p-5, -0x1.c05cf1d753621p-59 },
+	{ -0x1.8492528c8cac5p-6, 0x1.d192d0619fa68p-60 },
+	{ -0x1.0205658935837p-6, -0x1.27c8e8416e717p-60 },
+	{ -0x1.010157588de69p-7, -0x1.46662d417cecep-62 },
+	{ 0x0.0p+0, 0x0.0p+0 },
+	{ 0x1.fe02a6b106799p-8, -0x1.e44b7e3711e7fp-67 },
+	{ 0x1.fc0a8b0fc03c4p-7, -0x1.83092c5964281p-62 },
+	{ 0x1.7b91b07d5b126p-6, -0x1.6d80ab38e9430p-62 },
+	{ 0x1.f829b0e7832f8p-6, 0x1.33e3f04f1ef25p-60 },
+	{ 0x1.39e87b9febd68p-5, -0x1.5bfa937f551b7p-59 },
+	{ 0x1.77458f632dcffp-5, 0x1.8d3ca87b92968p-63 },
+	{ 0x1.b42dd711971b9p-5, 0x1.0a34531f67db5p-59 },
+	{ 0x1.f0a30c01162a8p-5, 0x1.85f325c5bbacdp-59 },
+	{ 0x1.16536eea37ae3p-4, 0x1.2189705cf74cap-58 },
+	{ 0x1.341d7961bd1d0p-4, -0x1.3599f227becbbp-58 },
+	{ 0x1.51b073f06183cp-4, -0x1.5b61c65e5741ap-58 },
+	{ 0x1.6f0d28ae56b4ep-4, -0x1.20db323097324p-59 },
+	{ 0x1.8c345d6319b23p-4, -0x1.294d2f5668495p-58 },
+	{ 0x1.a926d3a4ad562p-4, -0x1.d7a16eab1e2adp-59 },
+	{ 0x1.c5e548f5bc743p-4, 0x1.2eb0bf7c0b0d9p-59 },
+	{ 0x1.e27076e2af2eap-4, -0x1.61578001e015ap-60 },
+	{ 0x1.fec9131dbeabcp-4, -0x1.5746b9981b36cp-58 },
+	{ 0x1.0d77e7cd08e5bp-3, 0x1.9a5dc5e9030adp-57 },
+	{ 0x1.1b72ad52f67a2p-3, -0x1.fbe7ee5c69946p-57 },
+	{ 0x1.29552f81ff521p-3, 0x1.301771c407dc0p-57 },
+	{ 0x1.371fc201e8f75p-3, 0x1.e6cb62af18a02p-62 },
+	{ 0x1.44d2b6ccb7d1cp-3, 0x1.7d3d950f87e23p-59 },
+	{ 0x1.526e5e3a1b438p-3, -0x1.546ff8a470d3ap-57 },
+	{ 0x1.5ff3070a793d6p-3, -0x1.bc60efafc6f6cp-58 },
+	{ 0x1.6d60fe719d21bp-3, 0x1.d551d97132e87p-57 },
+	{ 0x1.7ab890210d907p-3, -0x1.1072534a57e7dp-57 },
+	{ 0x1.87fa06520c911p-3, -0x1.9f7fdbfa08d9ap-57 },
+	{ 0x1.9525a9cf456b6p-3, -0x1.26fb3e2b1d1dap-57 },
+	{ 0x1.a23bc1fe2b561p-3, 0x1.24dc46c1ea664p-57 },
+	{ 0x1.af3c94e80bff3p-3, 0x1.a3398064df33ep-57 },
+	{ 0x1.bc286742d8cd4p-3, 0x1.cfce744870f57p-58 },
+	{ 0x1.c8ff7c79a9a20p-3, -0x1.4f689f8434011p-57 },
+	{ 0x1.d5c216b4fbb94p-3, -0x1.a37794d03657dp-58 },
+	{ 0x1.e27076e2af2e8p-3, -0x1.61578001e015ep-59 },
+	{ 0x1.ef0adcbdc5935p-3, 0x1.e8637950dc20dp-57 },
+	{ 0x1.fb9186d5e3e29p-3, 0x1.355519b0de535p-57 },
+	{ 0x1.0402594b4d041p-2, -0x1.08ec217a5022dp-57 },
+	{ 0x1.0a324e27390e2p-2, 0x1.bdcfde8061c03p-56 },
+	{ 0x1.1058bf9ae4ad4p-2, 0x1.3f415699663ecp-63 },
+	{ 0x1.1675cababa60fp-2, 0x1.ce63eab883727p-61 },
+	{ 0x1.1c898c16999fbp-2, 0x1.9f1a39d500e3cp-56 },
+	{ 0x1.22941fbcf7966p-2, -0x1.dbd7ac258a2bdp-58 },
+	{ 0x1.2895a13de86a4p-2, 0x1.7ad24c13f040fp-56 },
+	{ 0x1.2e8e2bae11d31p-2, -0x1.1e99b72bd7bf2p-57 },
+	{ 0x1.347dd9a987d56p-2, -0x1.16ea62c048cfbp-56 },
+	{ 0x1.3a64c556945eap-2, 0x1.cbcd735d03424p-60 },
+	{ 0x1.404308686a7e4p-2, -0x1.f79f6c1059cdbp-57 },
+	{ 0x1.4618bc21c5ec2p-2, -0x1.7a42642661c62p-61 },
+	{ 0x1.4be5f957778a1p-2, -0x1.4b366b609027ap-58 },
+	{ 0x1.51aad872df82ep-2, -0x1.d8db0a7cc1543p-56 },
+	{ 0x1.5767717455a6cp-2, -0x1.fb2a49af933e8p-57 },
+	{ 0x1.5d1bdbf5809cap-2, -0x1.7dc9c7c23801fp-56 },
+	{ 0x1.62c82f2b9c796p-2, -0x1.090a0dd59fe35p-58 },
+	{ 0x1.686c81e9b14adp-2, 0x1.710af840538e3p-56 },
+	{ 0x1.6e08eaa2ba1e4p-2, -0x1.bfb1b39ca3a0fp-56 },
+	{ 0x1.739d7f6bbd007p-2, 0x1.ce24c53fad3f0p-58 },
+	{ 0x1.792a55fdd47a1p-2, 0x1.f057691fe9ed7p-56 },
+	{ 0x1.7eaf83b82afc2p-2, -0x1.698b43096b576p-59 },
+	{ 0x1.842d1da1e8b18p-2, 0x1.54ec519784677p-56 },
+	{ 0x1.89a3386c1425bp-2, 0x1.2d38c40881e0bp-57 },
+	{ 0x1.8f11e873662c8p-2, 0x1.f85da755a61a3p-56 },
+	{ 0x1.947941c2116fbp-2, 0x1.1266e8a3e8838p-57 },
+	{ 0x1.99d958117e08ap-2, -0x1.315b444ee1f38p-56 },
+	{ 0x1.9f323ecbf984dp-2, -0x1.a92e513217f58p-59 },
+};
+// (-1)^(k + 1) / k for k = 1 .. 16, in the same two parts
+static constexpr double svt_log1p_k[16][2] = {
+	{ 0x1.0000000000000p+0, 0x0.0p+0 },
+	{ -0x1.0000000000000p-1, 0x0.0p+0 },
+	{ 0x1.5555555555555p-2, 0x1.5555555555555p-56 },
+	{ -0x1.0000000000000p-2, 0x0.0p+0 },
+	{ 0x1.999999999999ap-3, -0x1.999999999999ap-57 },
+	{ -0x1.5555555555555p-3, -0x1.5555555555555p-57 },
+	{ 0x1.2492492492492p-3, 0x1.2492492492492p-57 },
+	{ -0x1.0000000000000p-3, 0x0.0p+0 },
+	{ 0x1.c71c71c71c71cp-4, 0x1.c71c71c71c71cp-58 },
+	{ -0x1.999999999999ap-4, 0x1.999999999999ap-58 },
+	{ 0x1.745d1745d1746p-4, -0x1.745d1745d1746p-59 },
+	{ -0x1.5555555555555p-4, -0x1.5555555555555p-58 },
+	{ 0x1.3b13b13b13b14p-4, -0x1.3b13b13b13b14p-58 },
+	{ -0x1.2492492492492p-4, -0x1.2492492492492p-58 },
+	{ 0x1.1111111111111p-4, 0x1.1111111111111p-60 },
+	{ -0x1.0000000000000p-4, 0x0.0p+0 },
+};
+// log(2) in three parts, the first with its low 11 bits clear: e * h is exact for |e| < 2048
+static constexpr double svt_log1p_ln2[3] = { 0x1.62e42fefa3800p-1, 0x1.ef35793c76730p-45, 0x1.f97b57a079a19p-103 };
+
+SVT_HD inline double svt_rule_log1p(double x)
+{
+	if (!(x > -1.0) || x == svt_rule_inf())
+		return log1p(x);
+	const svt_dd u = svt_dd_sum(1.0, x);
+	int e;
+	double m = frexp(u.h, &e);                              // u.h = m 2^e, m in [0.5, 1)
+	if (m < 0.75) { m *= 2.0; e--; }
+	const double ml = ldexp(u.l, -e);
+	const int j = (int) ((m - 0.75) * 128.0 + 0.5);
+	const double c = svt_log1p_c[j], p = m * c;
+	const svt_dd r = svt_dd_sum(p - 1.0, fma(m, c, -p) + ml * c);      // (p - 1 is exact: p in [0.5, 2])
+	svt_dd s = { svt_log1p_k[15][0], svt_log1p_k[15][1] };
+	for (int k = 14; k >= 0; k--)
+		s = svt_dd_add(svt_dd{ svt_log1p_k[k][0], svt_log1p_k[k][1] }, svt_dd_mul(r, s));
+	s = svt_dd_mul(r, s);
+	const double ee = (double) e;
+	svt_dd acc = svt_dd_sum(ee * svt_log1p_ln2[0], ee * svt_log1p_ln2[1]);
+	acc.l += ee * svt_log1p_ln2[2];
+	acc = svt_dd_add(acc, svt_dd{ svt_log1p_l[j][0], svt_log1p_l[j][1] });
+	return svt_dd_add(acc, s).h;
+}
+
 // the members of the Math group offered here, on a double
 SVT_HD inline double svt_rule_math(int op, double x)
 {
@@ -133,7 +311,7 @@ SVT_HD inline double svt_rule_math(int op, double x)
 	case SVT_MATH_TRUNC: return trunc(x);
 	// below 2^-54 both series round to x itself (|x^2 / 2| < ulp(x) / 4); said here because the device library
 	// answers 0 for the smallest denormals, and a zero result is an entry dropped
-	case SVT_MATH_LOG1P: return fabs(x) < 0x1p-54 ? x : log1p(x);
+	case SVT_MATH_LOG1P: return fabs(x) < 0x1p-54 ? x : svt_rule_log1p(x);
 	case SVT_MATH_EXPM1: return fabs(x) < 0x1p-54 ? x : expm1(x);
 	}
 	return svt_rule_nan();

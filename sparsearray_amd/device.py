@@ -496,8 +496,9 @@ def colmads(A: DeviceCSC, center=None, constant=1.4826, na_rm=False, out=None, w
 
 
 def colranks_form_limits():
-    """(last stored length of form 0, last stored length of form 1) of svt_dev_colranks_form, found by bisection."""
-    form = _lib().svt_dev_colranks_form
+    """(last stored length of form 0, last stored length of form 1) of svt_dev_colranks_form, found by bisection.
+    Needs no GPU."""
+    form = _hip.load_library().svt_dev_colranks_form
 
     def last(f):
         lo, hi = 0, 1 << 40                             # form(lo) <= f < form(hi)

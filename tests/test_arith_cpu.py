@@ -254,6 +254,23 @@ def test_host_math_rules_agree_with_the_case_module(rules, op):
     ac.compare(got, np.ones(x.size, bool), _expected_all(want, cls, is_NA_real(x)), f"host {op}", max_ulps=1)
 
 
+def test_host_log1p_is_the_nearest_double(rules):
+    """svt_rule_log1p against the correctly rounded value at 0 ulps: the arguments of the first chain of
+    tests/chain_cases.py (x * 0.001: where the device library's log1p was one ulp off for 49 of 8747), and 20 000 seeded
+    ones -- magnitudes from 2^-54 to 1e308, arguments down to -1 + 2^-53, table boundaries k / 128 and 2^k - 1"""
+    import chain_cases as cc
+    rng = np.random.default_rng(91)
+    x = np.concatenate([cc.operand("x").val * 0.001, np.array(ac.ULPS_INPUTS["log1p"]),
+                        np.exp(rng.uniform(np.log(2.0 ** -54), np.log(1e308), 6000)),
+                        -np.exp(rng.uniform(np.log(2.0 ** -54), 0.0, 4000)), rng.uniform(-1.0, 1.0, 4000),
+                        -1.0 + np.exp(rng.uniform(np.log(2.0 ** -53), 0.0, 3000)),
+                        rng.integers(-32, 2000, 2000) / 128 + rng.normal(size=2000) * 1e-12, 2.0 ** rng.integers(-54, 1023, 1000) - 1.0])
+    got = _from_hex(rules([f"M {MATH_OPCODES['log1p']} {a}" for a in _hex(x)]))
+    want, cls = ac._math("log1p", x)
+    from sparsearray_amd.svt import is_NA_real
+    ac.compare(got, np.ones(x.size, bool), _expected_all(want, cls, is_NA_real(x)), "host log1p", max_ulps=0)
+
+
 def test_host_int_rules_agree_with_the_case_module(rules):
     """NA propagation, %% with the divisor's sign, %/% flooring, a zero divisor, and the overflow edges: INT_MAX + 1 and
     -INT_MAX - 1 (= INT_MIN, which is NA_integer_) overflow, INT_MAX and -INT_MAX do not"""

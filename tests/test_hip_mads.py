@@ -7,6 +7,7 @@ import pytest
 from helpers import assert_equal, assert_identical, random_csc
 from sparsearray_amd import NA_integer, NA_real, SVT_SparseArray, SparseArrayError, is_NA_real
 from test_mads_cpu import check_argument_errors, check_mads_on_cases, dense_colmads
+from test_medians import last_digit_columns
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +28,10 @@ def _mad_select_operand(type_):
     takes the extra counting pass), deviations that differ only in low mantissa bits, the block of the zeros'
     deviation |c| in the middle of the deviations, at their bottom (c = 0, or every x beyond 2c) and at their top (every
     x inside (0, 2c)), 1e200-scale values, +-Inf, NA / NaN.  Without them: nonzero medians with few zeros, short columns
-    among many zeros (answered from the median's counts), columns with median 0 but fewer than half zeros (not so)."""
+    among many zeros (answered from the median's counts), columns with median 0 but fewer than half zeros (not so).
+    Doubles also: the columns of test_medians.last_digit_columns with the centers 0.5, 0 and 2 -- the deviations
+    0.5 + k 2^-52, 1 + k 2^-52 and 1 - k 2^-52 are exact and differ in their last bits only, about five copies of each:
+    msel_select gives up after its last digit pass with a handful of candidates, and rank k + 1 is one step above."""
     rng = np.random.default_rng(71)
     nrow = 5000
     scale = 1000 if type_ == "integer" else 1
@@ -84,8 +88,8 @@ def _mad_select_operand(type_):
         inf[:1250, 1] = -np.inf; inf[1250:3000, 1] = rng.normal(size=1750); inf[3000:, 1] = np.inf
         inf[:100, 2] = np.inf; inf[100:3000, 2] = np.abs(rng.normal(size=2900)) + 1
         inf[:3000, 3] = np.inf                                                 # median +Inf: its own deviation is NaN
-        a = np.concatenate([a, inf], axis=1)
-        cen += [0.0, np.inf, 1.5, -np.inf]
+        a = np.concatenate([a, last_digit_columns(nrow), inf], axis=1)
+        cen += [0.5, 0.0, 2.0] + [0.0, np.inf, 1.5, -np.inf]
         return SVT_SparseArray.from_dense(np.asfortranarray(a), "double"), a, np.array(cen)
     ai = a.astype(np.int32)
     ai[5, 9] = NA_integer; ai[:40, 11] = NA_integer

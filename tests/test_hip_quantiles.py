@@ -6,13 +6,14 @@ import pytest
 
 from helpers import assert_equal, assert_identical, random_csc
 from sparsearray_amd import NA_integer, NA_real, SVT_SparseArray, SparseArrayError, is_NA_real
-from test_medians import _dense_colmedians
+from test_medians import _dense_colmedians, last_digit_columns
 from test_quantiles_cpu import (PROBS_SETS, as_float, check_session_on_cases, dense_colquantiles, dense_iqrs,
                                 quantile_cases)
 
 pytestmark = pytest.mark.gpu
 
-SELECT_PROBS = (0, 0.01, 0.25, 1 / 3, 0.5, 0.75, 0.99, 1)
+# (the last four: at and on either side of the two middle ranks of a 5000-value column, see last_digit_columns)
+SELECT_PROBS = (0, 0.01, 0.25, 1 / 3, 0.5, 0.75, 0.99, 1, 2499 / 4999, 2500 / 4999, 0.49995, 0.50005)
 
 
 @pytest.mark.parametrize("na_rm", [False, True])
@@ -68,7 +69,8 @@ def _select_operand(type_):
     test_hip_colmedians_radix_select_against_numpy: normal values, heavy duplicates (more than 1024 equal keys in a
     column: msel_select gives up and rank k + 1 takes the extra counting pass), values that differ only in low
     mantissa bits, negative majorities, 1e200-scale values, +-Inf as interpolation neighbours, NA / NaN, and short
-    columns among many zeros."""
+    columns among many zeros; and (doubles) keys that differ in their last ten bits only, about five copies of each:
+    msel_select gives up after its last digit pass with a handful of candidates, and rank k + 1 is one ulp above."""
     rng = np.random.default_rng(67)
     nrow = 5000
     cols = []
@@ -110,7 +112,7 @@ def _select_operand(type_):
         inf[: nrow // 2, 0] = -np.inf; inf[nrow // 2:, 0] = np.inf             # the median's neighbours: -Inf, +Inf
         inf[:1250, 1] = -np.inf; inf[1250:3000, 1] = rng.normal(size=1750); inf[3000:, 1] = np.inf
         inf[:100, 2] = np.inf; inf[100:3000, 2] = np.abs(rng.normal(size=2900)) + 1
-        a = np.concatenate([a, inf], axis=1)
+        a = np.concatenate([a, last_digit_columns(nrow), inf], axis=1)
         return SVT_SparseArray.from_dense(np.asfortranarray(a), "double"), a
     ai = a.astype(np.int32)
     ai[5, 9] = NA_integer; ai[:40, 11] = NA_integer

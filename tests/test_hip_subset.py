@@ -1,7 +1,7 @@
 """x[i, j] by an N-index on the GPU (kernels_subset.hip; include/svt_hip.h, svt_dev_subset_*): the shared cases of
 tests/subset_cases.py through the host entry point, and the two device primitives on operands placed around the tile
 T = svt_dev_subset_tile() -- against numpy on the dense matrix, ``dense[np.ix_(i, j)]``, at tolerance 0 (values as
-bits).  No operand holds more than about 3 T nonzeros.
+bits).  No operand holds more than about 3 T nonzeros; one gather's RESULT holds 2100 T (the fixed grid's second trip).
 
 The device-level reference subsets a dense matrix of TRACERS (entry number + 1, 0 where nothing is stored) with
 np.ix_ and reads the result's CSC arrays off it: which entry lands where, so that values are compared as bits."""
@@ -83,11 +83,22 @@ def _layouts(T):
         "empty_run_inside_a_tile": [T - 3] + [0] * 100 + [10, 0, 0],  # ... and at T - 3, the last columns empty too
         "last_column_empty": [17, T, 0],
         "one_column_over_90_percent": [50, 2 * T + 3 * T // 4, 50, 0, 60],
+        # more column boundaries in a tile than the workgroup has threads: the one-lane-per-boundary loops take
+        # several trips (about 2700 boundaries in a full tile, 680 in the last one) ...
+        "many_short_columns": [0, 1, 2, 3] * (3 * T // 8),
+        # ... and so does a run of empty columns that all start at the same entry inside a tile
+        "empty_run_longer_than_the_workgroup": [T - 3] + [0] * 600 + [10],
     }
+
+
+def _nrow(T, name):
+    """3 T rows; fewer where the dense tracer matrix of the reference would be large for nothing"""
+    return {"many_short_columns": 64, "empty_run_longer_than_the_workgroup": T + 50}.get(name, NROW_TILES * T)
 
 
 NAMES = list(_layouts(4096))
 NROW_TILES = 3
+WORKGROUP = 256          # SUB_NT of kernels_subset.hip: the stride of the loops over the column boundaries of a tile
 
 
 @pytest.fixture(scope="module")
@@ -103,7 +114,7 @@ def _operand(T, name):
     key = (T, name)
     if key not in _cache:
         lens = _layouts(T)[name]
-        nrow = NROW_TILES * T
+        nrow = _nrow(T, name)
         rng = np.random.default_rng(len(name))
         cp = np.zeros(len(lens) + 1, dtype=np.int64)
         np.cumsum(lens, out=cp[1:])
@@ -116,6 +127,11 @@ def _operand(T, name):
             a.setflags(write=False)
         if name == "one_column_over_90_percent":
             assert max(lens) > 0.9 * sum(lens)
+        if name == "many_short_columns":                                # column starts per tile
+            starts = np.bincount(cp[:-1] // T, minlength=-(-int(cp[-1]) // T))
+            assert len(lens) == 3 * T // 2 and starts[:-1].min() >= 1000 and starts.min() > 2 * WORKGROUP
+        if name == "empty_run_longer_than_the_workgroup":
+            assert (cp == T - 3).sum() > 2 * WORKGROUP and cp[-1] > T
         _cache[key] = (nrow, cp, ri, val, tracer)
     return _cache[key]
 
@@ -216,6 +232,34 @@ def test_routes(tile):
     # the increasing subscript through the composition on purpose: t, gather, t -- the filter's arrays
     via = subset_cols(A.t(), inc).t()
     _same(_host(via), _host(A.subset(rows=inc)), "composition vs filter")
+
+
+def test_gather_of_more_tiles_than_its_grid(tile):
+    """The gather runs on a fixed grid and strides over the tiles of its result: a column of 3 T nonzeros gathered 700
+    times, an empty column and one of 5 entries after each, gives 2101 result tiles -- every workgroup takes a first
+    trip and the first ones a second.  The expectation is the three columns tiled with numpy (about 8.6 M entries)."""
+    from sparsearray_amd.device import subset_cols, subset_route_counts
+    GRID = 2048                          # SUB_GATHER_GRID of kernels_subset.hip
+    T, reps = tile, 700
+    nrow = 3 * T + 40
+    rng = np.random.default_rng(12)
+    lens = np.array([3 * T, 0, 5])
+    cp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    ri = np.concatenate([np.sort(rng.choice(nrow, size=n, replace=False)) for n in lens]).astype(np.int32)
+    val = sc.SPECIALS_F64[np.arange(ri.size) % len(sc.SPECIALS_F64)]
+    val[::5] = np.arange(1, ri.size + 1, dtype=np.float64)[::5]        # tracers among them: which entry landed where
+    cols = np.tile(np.array([0, 1, 2], dtype=np.int32), reps)
+    want_cp = np.concatenate([[0], np.cumsum(np.tile(lens, reps))]).astype(np.int64)
+    ntiles = -(-int(want_cp[-1]) // T)
+    # more tiles than the grid has workgroups, and still so with the grid halved
+    assert ntiles > GRID and ntiles > 2 * (GRID // 2) and want_cp[-1] == reps * (3 * T + 5)
+    A = _device(nrow, cp, ri, val)
+    subset_route_counts(reset=True)
+    R = subset_cols(A, cols)
+    got = _host(R)
+    assert subset_route_counts() == {"column_gather": 1, "row_filter": 0, "general_rows": 0}
+    assert R.nrow == nrow and R.ncol == cols.size
+    _same(got, (want_cp, np.tile(ri, reps), np.tile(val, reps)), "2101 tiles")
 
 
 @pytest.mark.parametrize("dtype", ["integer", "logical"])

@@ -24,6 +24,31 @@ def _dense_colmedians(a, na_rm):
     return out
 
 
+dense_colmedians = _dense_colmedians                  # (the rule under its public name: tests/chain_cases.py)
+
+
+def last_digit_columns(nrow=5000, seed=69):
+    """Full columns of ``nrow`` (even) values 1 + k * 2^-52 with k < 1024: every key shares its upper 54 bits with more
+    than 1024 others, so the select's bin never gets small before its last digit pass and it gives up with a handful
+    of candidates (msel_select, ``shift == 0``); rank k + 1 then comes from the caller's counting pass, with the next
+    key ONE ulp above.  Column 0: half the values below k = 512 and half from it on, 511 and 512 among them -- the two
+    middle ranks are adjacent distinct keys; column 1: k uniform; column 2: the two middle ranks inside seven copies of
+    one key."""
+    rng = np.random.default_rng(seed)
+    half = nrow // 2
+    assert nrow % 2 == 0 and half > 1024
+    k0 = np.concatenate([rng.integers(0, 512, half), rng.integers(512, 1024, half)])
+    k0[0], k0[half] = 511, 512
+    k1 = rng.integers(0, 1024, nrow)
+    k2 = np.concatenate([rng.integers(0, 300, half - 3), np.full(7, 300), rng.integers(301, 1024, half - 4)])
+    cols = np.stack([1.0 + rng.permutation(k) * 2.0 ** -52 for k in (k0, k1, k2)], axis=1)
+    s = np.sort(cols, axis=0)
+    assert s[half - 1, 0] == 1.0 + 511 * 2.0 ** -52 and s[half, 0] == 1.0 + 512 * 2.0 ** -52
+    assert s[half - 1, 2] == s[half, 2] == 1.0 + 300 * 2.0 ** -52
+    assert all(np.unique(cols[:, j], return_counts=True)[1].max() < 40 for j in range(3))
+    return cols
+
+
 def _cases():
     rng = np.random.default_rng(5)
     cases = []
@@ -178,6 +203,7 @@ def test_hip_colmedians_radix_select_against_numpy(hip, type_):
     a = np.concatenate([a, short], axis=1)
     if type_ == "double":
         a[17, 3] = np.inf; a[18, 3] = -np.inf; a[5, 9] = np.nan; a[6, 10] = NA_real; a[:40, 11] = np.nan
+        a = np.concatenate([a, last_digit_columns(nrow)], axis=1)              # the select's last digit decides nothing
         x = SVT_SparseArray.from_dense(np.asfortranarray(a), "double")
         dense = a
     else:
