@@ -369,6 +369,22 @@ typedef struct svt_dev_csc {
 	                          only; set by svt_upload(), 0 for wrapped buffers) */
 } svt_dev_csc;
 
+/*
+ * Workspaces.  One contract for every device-level entry point that takes `ws` (or the `gid` buffer of
+ * svt_dev_rowsum_prepare), stated here once; the comments below point to it:
+ *   - the caller aligns `ws` and the output arrays to 256 bytes (what a device allocation has; `ws` is carved into
+ *     arrays at multiples of 256 bytes from its start) and passes at least the bytes the matching `_ws_bytes()` /
+ *     `_gid_bytes()` query advertises.  A smaller `ws_bytes` is an error ("... workspace too small", "... id buffer
+ *     too small"), answered before anything is launched or written -- by the `_prepared` calls too;
+ *   - the call writes nothing outside [ws, ws + the advertised size) and its outputs at the sizes their comments give;
+ *   - every cell of every output is written, the not-finite flag of the sparse x sparse products included (also when
+ *     the result has no cells), unless the comment of the call says which cells it leaves alone and when;
+ *   - the result does not depend on what `ws` holds on entry: a call clears what it needs cleared.  A `_prepared`
+ *     call reads what its `_prepare` call left, and nothing else of the workspace's past.
+ * Tested in an arena of 0xA5 bytes with guard bands: tests/test_hip_ws_discipline.py for the products, the row
+ * statistics, colMedians and the prepared rowsum; the test files of the other families for theirs.
+ */
+
 /* Marshal + H2D.  Returns NULL on error. */
 svt_dev_csc *svt_upload(const svt_view *x);
 /* Wrap device buffers owned by the caller (e.g. a torch allocation). */
@@ -388,7 +404,7 @@ void svt_release(svt_dev_csc *h);
  *          out_stride_k]: (1, ncol) gives the column-major ncol x K result
  *          of C_crossprod2_SVT_mat, (K, 1) gives the K x ncol result of
  *          C_crossprod2_mat_SVT.
- *   ws     workspace of at least svt_dev_crossprod_ws_bytes() bytes.
+ *   ws     workspace of at least svt_dev_crossprod_ws_bytes() bytes ("Workspaces" above).
  * Asynchronous on `stream` (a hipStream_t).
  */
 size_t svt_dev_crossprod_ws_bytes(int64_t nrow, int64_t ncol, int K);
@@ -424,7 +440,7 @@ int svt_dev_crossprod_csc_dense(const svt_dev_csc *A, const void *Y,
  * svt_dev_pbc_build() allocates and synchronises (not for the launch path).
  * svt_dev_crossprod_pbc() has the semantics and the out-indexing of
  * svt_dev_crossprod_csc_dense() (A is needed for the general path that
- * takes over when Y holds NaN/Inf/NA); Y is f64.
+ * takes over when Y holds NaN/Inf/NA); Y is f64.  ws: svt_dev_crossprod_pbc_ws_bytes() bytes ("Workspaces" above).
  */
 typedef struct svt_dev_pbc svt_dev_pbc;
 svt_dev_pbc *svt_dev_pbc_build(const svt_dev_csc *A, int CBW, int WPB, int logR);
@@ -540,7 +556,7 @@ int svt_dev_colstats(const svt_dev_csc *A, int opcode, int na_rm,
 int svt_dev_colstats_form(int64_t nseg, int64_t nnz, int *nchunk);
 
 /* colMedians on the device (see svt_colMedians_SVT): out = ncol doubles (device);
-   ws: svt_dev_colmedians_ws_bytes() bytes (two f64 key arrays + the sort's scratch). */
+   ws: svt_dev_colmedians_ws_bytes() bytes (two f64 key arrays + the sort's scratch; "Workspaces" above). */
 size_t svt_dev_colmedians_ws_bytes(int64_t nnz, int64_t ncol);
 int svt_dev_colmedians(const svt_dev_csc *A, int na_rm, double *out, void *ws, size_t ws_bytes,
 		       void *stream);
@@ -586,7 +602,7 @@ int svt_dev_colranks(const svt_dev_csc *A, int ties, void *rank_nz, void *zero_r
 
 /* row sums: out[(j % inner) * nrow + r] = sum over the leaves j that map to
    that cell.  Every output cell is owned by one workgroup (LDS row panels, no
-   memory atomics); ws: svt_dev_rowstats_ws_bytes() bytes. */
+   memory atomics); ws: svt_dev_rowstats_ws_bytes() bytes ("Workspaces" above). */
 size_t svt_dev_rowstats_ws_bytes(int64_t nrow, int64_t ncol);
 int svt_dev_rowsums(const svt_dev_csc *A, int na_rm, int64_t inner,
 		    double *out, void *ws, size_t ws_bytes, void *stream);
@@ -604,7 +620,7 @@ int svt_dev_rowsums_prepared(const svt_dev_csc *A, int na_rm, int64_t inner,
    max / range cell had nothing to look at (may be NULL).
    Asynchronous on `stream`; allocates nothing and does not synchronise.  ws: svt_dev_rowstats_ws_bytes_op() bytes
    for this (operand, opcode, inner): the table of run bounds, which mean / var1 / sd1 build once for their two or
-   three passes, plus their sums, NA counts and center, which never leave the device.
+   three passes, plus their sums, NA counts and center, which never leave the device ("Workspaces" above).
    Status: > 0 for more than 65535 output columns with an added operation or a NaArray operand; < 0 for an added
    operation other than SVT_OP_RANGE on a NaArray operand and for any / all on doubles.
    One device: the caller shards. */
@@ -634,7 +650,8 @@ int svt_dev_rowsum(const svt_dev_csc *A, const int *group, int ngroup,
 /* The same for an (operand, grouping) pair used more than once: svt_dev_rowsum_prepare() writes the group of
    every nonzero -- a 16-bit 0-based id, NA -> the last group (src/rowsum_methods.c:51-54) -- into `gid`
    (svt_dev_rowsum_gid_bytes(A) bytes, device memory); svt_dev_rowsum_prepared() then streams 10 bytes per
-   nonzero (value + id) and looks nothing up.  1 <= ngroup <= 20480 (a column's sums live in LDS). */
+   nonzero (value + id) and looks nothing up.  1 <= ngroup <= 20480 (a column's sums live in LDS).  `gid` is a
+   workspace in the sense of "Workspaces" above; svt_dev_rowsum_prepared() is not told its size. */
 size_t svt_dev_rowsum_gid_bytes(const svt_dev_csc *A);
 int svt_dev_rowsum_prepare(const svt_dev_csc *A, const int *group, int ngroup, void *gid, size_t gid_bytes,
 			   void *stream);
@@ -686,9 +703,8 @@ int svt_set_max_threads(int nthread);
 size_t svt_dev_transpose_ws_bytes(int64_t nrow, int64_t nnz);
 int svt_dev_transpose(const svt_dev_csc *A, int64_t *out_col_ptr, int32_t *out_row_idx,
 		      void *out_val, void *ws, size_t ws_bytes, void *stream);
-/* Alignment, for svt_dev_transpose() and svt_dev_aperm() alike: the caller aligns `ws` and the three output arrays
-   to 256 bytes (what a device allocation has; `ws` is carved into arrays at multiples of 256 bytes from its start).
-   The calls write nothing outside [ws, ws + the advertised size) and the three outputs at the sizes given above. */
+/* Alignment and workspace, for svt_dev_transpose() and svt_dev_aperm() alike: "Workspaces" above; the outputs are the
+   three arrays at the sizes given above. */
 /* Which form svt_dev_transpose() takes for an nrow x ncol operand of nnz nonzeros (nslab = 1), or the step "first
    two axes change places" of svt_dev_aperm() for nslab matrices of nrow x ncol holding nnz nonzeros in all
    (nslab > 1) -- the decision of the launch itself, by the same functions.  Host only: no launch, no device needed.
@@ -721,7 +737,7 @@ int64_t svt_dev_boxed_calls(int reset);
    implicit zeros too): then `*not_finite` (device int, may be NULL; the second int of `ws` holds the same flag)
    is set and `out` must be recomputed by the dense route (svt_matmul_SVT_SVT does; a launch that finds the flag
    up already leaves `out` alone).  Otherwise every cell of the A->nrow x B->ncol result is written; ws:
-   svt_dev_matmul_csc_csc_ws_bytes(A) bytes.  Asynchronous.
+   svt_dev_matmul_csc_csc_ws_bytes(A) bytes ("Workspaces" above).  A result without cells has a flag of 0.  Asynchronous.
    What depends on A alone -- the table of run bounds and a look at all its values, one pass over the operand --
    can be done once per operand: svt_dev_matmul_csc_csc_prepare(A, ws) fills `ws`, which
    svt_dev_matmul_csc_csc_prepared() then only reads (plus its second int, the flag of the last product), as the
@@ -748,7 +764,9 @@ int svt_dev_matmul_csc_csc_prepared(const svt_dev_csc *A, const svt_dev_csc *B, 
    A non-finite value or an NA anywhere in either operand changes what the reference computes (its dirty-leaf
    loops multiply the implicit zeros too): `*not_finite` (device int, may be NULL; the first int of `ws` holds
    the same flag) is set and `out` must come from the dense-buffer route (svt_crossprod2_SVT_SVT /
-   svt_crossprod1_SVT do that).  ws: svt_dev_crossprod_csc_csc_ws_bytes(Xt) bytes.  Asynchronous. */
+   svt_crossprod1_SVT do that; a launch that finds the flag up leaves `out` alone).  A result without cells
+   (ncol(X) or ncol(Y) == 0) has a flag of 0.  ws: svt_dev_crossprod_csc_csc_ws_bytes(Xt) bytes ("Workspaces" above),
+   sized under the panel setting of the call.  Asynchronous. */
 size_t svt_dev_crossprod_csc_csc_ws_bytes(const svt_dev_csc *Xt);
 int svt_dev_crossprod_csc_csc(const svt_dev_csc *Xt, const svt_dev_csc *Y, int sym, double *out, int64_t ldo,
 			      void *ws, size_t ws_bytes, int *not_finite, void *stream);
@@ -835,7 +853,7 @@ int svt_transpose_2D_SVT(const svt_view *x, int64_t *out_col_ptr,
    then takes t(), the column gather with the row subscript, t().  Every index is checked before it is used as an
    address; on < 0 and > 0 nothing is written outside `ws` (out_col_ptr and *out_nnz keep their contents).
    ncols_sel == 0 writes out_col_ptr[0] = 0 without a launch or a synchronisation; an operand without nonzeros has its
-   subscripts checked all the same.  Alignment as for svt_dev_transpose(). */
+   subscripts checked all the same.  Alignment and workspace: "Workspaces" above. */
 int svt_dev_subset_tile(void);
 size_t svt_dev_subset_cols_ws_bytes(int64_t ncols_sel);
 int svt_dev_subset_cols_count(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, int64_t *out_col_ptr,
@@ -902,7 +920,7 @@ int svt_subset_SVT_end(svt_subset_result *res, int64_t *out_col_ptr, int32_t *ou
    differ, a workspace below svt_dev_arith_*_ws_bytes(), an unknown kind or opcode or one the family does not take, an
    LGLSXP operand, a Math operation on an INTSXP operand; > 0 for an operand with na_background (the reference has
    separate NaArray methods) and for the Math operations listed above.  On a non-zero status nothing is written outside
-   `ws`.  Alignment as for svt_dev_transpose(). */
+   `ws`.  Alignment and workspace: "Workspaces" above. */
 enum { SVT_ARITH_ADD = 1, SVT_ARITH_SUB = 2, SVT_ARITH_MULT = 3, SVT_ARITH_DIV = 4, SVT_ARITH_POW = 5, SVT_ARITH_MOD = 6,
        SVT_ARITH_IDIV = 7 };
 enum { SVT_MATH_ABS = 1, SVT_MATH_SIGN = 2, SVT_MATH_SQRT = 3, SVT_MATH_FLOOR = 4, SVT_MATH_CEILING = 5, SVT_MATH_TRUNC = 6,

@@ -543,11 +543,11 @@ size_t gram_ws_bytes(int64_t nx, int64_t nrow, int64_t a_nnz)
 int launch_gram(GramArgs a, int64_t a_nnz, int64_t b_nnz, void *ws, hipStream_t s)
 {
 	(void) b_nnz;
-	if (a.nx <= 0 || a.ny <= 0)
-		return 0;
 	int *flag = (int *) ws;
 	a.flag = flag;
 	HIP_TRY(hipMemsetAsync(flag, 0, 8, s));
+	if (a.nx <= 0 || a.ny <= 0)                     // (no cells; the flag the caller copies out is 0, not what ws held)
+		return 0;
 	if (!a.sym && a_nnz > 0) {                      // the values of X (symmetric: every value is some workgroup's Y value)
 		int64_t nb = (a_nnz + 256 * 8 - 1) / (256 * 8);
 		if (nb > 256 * 16) nb = 256 * 16;

@@ -548,9 +548,11 @@ def device_sparse_crossprod_block(A_block):
     """`local_product` for sharded_crossprod_sparse() on the device: the rank's leaf block of A (a DeviceCSC) against
     the gathered B through the sparse-aware kernel (svt_dev_crossprod_csc_csc on t(A_block), built once here).  The
     rank's rows of the result come back as the (ncol_A_local, ncol_B) tensor gather_columns() concatenates; the
-    kernel's not-finite flag of the last product is kept in `.flag` (nonzero: that product has to be redone by
-    the dense-buffer route, svt_dev_crossprod_csc_csc_dense_buffer)."""
-    from .device import DeviceCSC, crossprod_csc_csc
+    kernel's not-finite flag of the last product is kept in `.flag`.  A nonzero flag means the kernel left `out`
+    alone (a NaN, an Inf or an NA in either operand changes what the reference computes): the block is then redone
+    here by the dense-buffer route (svt_dev_crossprod_csc_csc_dense_buffer), on this rank alone -- the flag is read
+    back once per product, and no collective depends on it."""
+    from .device import DeviceCSC, crossprod_csc_csc, crossprod_csc_csc_dense_buffer
     At = A_block.t()
 
     def local_product(B_full):
@@ -558,6 +560,8 @@ def device_sparse_crossprod_block(A_block):
         B = DeviceCSC(A_block.nrow, cp, ri, v)
         out, flag = crossprod_csc_csc(At, B)          # (ncol_B, ncol_A_local) = column-major ncol_A_local x ncol_B
         local_product.flag = flag
+        if int(flag.item()):
+            crossprod_csc_csc_dense_buffer(A_block, B, out=out)
         return out.t().contiguous()
     local_product.flag = None
     return local_product

@@ -148,6 +148,38 @@ def check_case(session, case, lacunar=True, gpu=False):
 
 
 # ---------------------------------------------------------------------------
+# the arena of the workspace tests (test_hip_transpose_cases.py, test_hip_ws_discipline.py)
+# ---------------------------------------------------------------------------
+GUARD, ALIGN = 4096, 256            # include/svt_hip.h: ws and the outputs aligned to 256 bytes
+
+
+class Arena:
+    """[guard][part][guard][part] ... [guard] in one device allocation, everything 0xA5, every part at a multiple of
+    ALIGN bytes and of exactly its size (what lies between the end of a part and the next multiple is guard too).  The
+    first part is the workspace, the others the outputs."""
+
+    def __init__(self, sizes):
+        import torch
+        self.parts, o = [], GUARD
+        for n in sizes:
+            self.parts.append((o, n))
+            o = (o + n + ALIGN - 1) // ALIGN * ALIGN + GUARD
+        self.mem = torch.full((o,), 0xA5, dtype=torch.uint8, device="cuda")
+        assert self.mem.data_ptr() % ALIGN == 0
+
+    def part(self, i, dtype=None):
+        o, n = self.parts[i]
+        return self.mem[o:o + n] if dtype is None else self.mem[o:o + n].view(dtype)
+
+    def guards_intact(self):
+        edges = [0] + [e for o, n in self.parts for e in (o, o + n)] + [self.mem.numel()]
+        return all(bool((self.mem[a:b] == 0xA5).all()) for a, b in zip(edges[0::2], edges[1::2]))
+
+    def untouched(self):
+        return bool((self.mem == 0xA5).all())
+
+
+# ---------------------------------------------------------------------------
 # random inputs in the style of randomSparseArray(), R/randomSparseArray.R:11-38
 # ---------------------------------------------------------------------------
 def signif2(x):

@@ -7,13 +7,13 @@ import numpy as np
 import pytest
 
 import transpose_cases as tc
+from helpers import Arena
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 NAMES = [c["name"] for c in tc.CASES]
 TORCH_DTYPE = {"double": torch.float64, "integer": torch.int32, "logical": torch.int32}
-GUARD, ALIGN = 4096, 256            # include/svt_hip.h: ws and the outputs aligned to 256 bytes
 
 
 def _operand(name, dtype, val):
@@ -82,30 +82,6 @@ def _ws_bytes(c, nnz):
         return _lib().svt_dev_transpose_ws_bytes(c["dim"][0], nnz)
     dim, perm = np.asarray(c["dim"], dtype=np.int64), np.asarray(c["perm"], dtype=np.int32)
     return _lib().svt_dev_aperm_perm_ws_bytes(nnz, len(dim), dim.ctypes.data, perm.ctypes.data)
-
-
-class Arena:
-    """[guard][ws][guard][col_ptr][guard][row_idx][guard][val][guard], everything 0xA5, the four parts at multiples of
-    ALIGN bytes and of exactly their sizes (what lies between the end of a part and the next multiple is guard too)."""
-
-    def __init__(self, sizes):
-        self.parts, o = [], GUARD
-        for n in sizes:
-            self.parts.append((o, n))
-            o = (o + n + ALIGN - 1) // ALIGN * ALIGN + GUARD
-        self.mem = torch.full((o,), 0xA5, dtype=torch.uint8, device="cuda")
-        assert self.mem.data_ptr() % ALIGN == 0
-
-    def part(self, i, dtype=torch.uint8):
-        o, n = self.parts[i]
-        return self.mem[o:o + n].view(dtype)
-
-    def guards_intact(self):
-        edges = [0] + [e for o, n in self.parts for e in (o, o + n)] + [self.mem.numel()]
-        return all(bool((self.mem[a:b] == 0xA5).all()) for a, b in zip(edges[0::2], edges[1::2]))
-
-    def untouched(self):
-        return bool((self.mem == 0xA5).all())
 
 
 def _arena_case(name, dtype, boxed=False):
