@@ -971,6 +971,68 @@ int svt_unary_minus_SVT_begin(const svt_view *x, svt_arith_result **res, int *ou
 int svt_Math_SVT_begin(const svt_view *x, int op, double digits, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
 int svt_Arith_SVT_end(svt_arith_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val);
 
+/* Compare and Logic on SVT operands (C_Compare_SVT1_SVT2, C_Compare_SVT1_v2, C_Logic_SVT1_SVT2;
+   R/SparseArray-Compare-methods.R, R/SparseArray-Logic-methods.R; the element rules of src/SparseVec_Compare.c and
+   src/SparseVec_Logic.c): the result is a new LGLSXP operand in the device layout, its values int32 1 or NA_integer_.
+   They are further rules on the two kernel families of Arith (kernels_arith.hip), with the same tiles, the same
+   placement and the same workspaces: svt_dev_arith_merge_ws_bytes() sizes the workspace of the two merges,
+   svt_dev_arith_map_ws_bytes() that of the map.
+
+     compare merge  x op y, op one of SVT_COMPARE_NE / _LT / _GT (the three that are FALSE where both sides are zero),
+                    each operand LGLSXP, INTSXP or REALSXP (an LGLSXP operand is an int32 operand).  Both sides are
+                    taken as doubles, NA_integer_ as NA_real_; a NaN or NA on either side gives NA, which is stored.
+     compare map    x op s for any of the six operators and a scalar s of type s_Rtype (LGLSXP, INTSXP, REALSXP; an
+                    integer or logical s is passed as its double value, INT_MIN standing for NA), provided 0 op s is
+                    FALSE: x == 0, x >= 0, x < 1, a NaN or NA s and the like answer < 0, because the result would not
+                    be sparse and computing the stored positions alone would be silently wrong.
+     logic merge    x & y, x | y for two LGLSXP operands, by the three-valued tables.
+
+   At every position stored in x or in y the value is rule(x or 0, y or 0); it is stored unless it is 0 (FALSE).  A
+   stored zero of an operand is an ordinary value.  The count / fill contract is that of svt_dev_arith_*: `_count`
+   writes out_col_ptr int64[ncol + 1] and *out_nnz and synchronises `stream` once; `_fill` is asynchronous, reads the
+   workspace as the count call left it and writes out_row_idx int32[*out_nnz] and out_val int32[*out_nnz]; rows ascend
+   in every result column; two runs give the same bits; there is no overflow word.  Status: < 0 for extents that
+   differ, a workspace too small, an unknown opcode, a merge Compare with an op other than != < >, a map Compare whose
+   scalar makes 0 op s anything but FALSE, Logic with an operand that is not LGLSXP, an operand or scalar type outside
+   logical / integer / double; > 0 for an operand with na_background.  On a non-zero status nothing is written outside
+   `ws`: out_col_ptr and *out_nnz keep their contents.  Alignment and workspace: "Workspaces" above. */
+enum { SVT_COMPARE_EQ = 1, SVT_COMPARE_NE = 2, SVT_COMPARE_LE = 3, SVT_COMPARE_GE = 4, SVT_COMPARE_LT = 5,
+       SVT_COMPARE_GT = 6 };
+enum { SVT_LOGIC_AND = 1, SVT_LOGIC_OR = 2 };
+int svt_dev_compare_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr, int64_t *out_nnz,
+				void *ws, size_t ws_bytes, void *stream);
+int svt_dev_compare_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+			       int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_compare_map_count(const svt_dev_csc *x, int op, double s, int s_Rtype, int64_t *out_col_ptr, int64_t *out_nnz,
+			      void *ws, size_t ws_bytes, void *stream);
+int svt_dev_compare_map_fill(const svt_dev_csc *x, int op, double s, int s_Rtype, const int64_t *out_col_ptr,
+			     int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_logic_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr, int64_t *out_nnz,
+			      void *ws, size_t ws_bytes, void *stream);
+int svt_dev_logic_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+			     int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes, void *stream);
+/* The compositions count -> allocate -> fill over the allocator of svt_dev_subset(), like svt_dev_arith_merge: the
+   result arrays (*out_col_ptr int64[ncol + 1]; *out_row_idx, *out_val int32 of at least one element) are the caller's
+   to release.  Synchronise `stream` once; the fill is still queued on return. */
+int svt_dev_compare_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+			  void *ctx, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val,
+			  void *stream);
+int svt_dev_compare_map(const svt_dev_csc *x, int op, double s, int s_Rtype, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+			void *ctx, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val,
+			void *stream);
+int svt_dev_logic_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+			void *ctx, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val,
+			void *stream);
+
+/* Host level, like svt_Arith_*_begin: the operands go up (through the resident cache when it is on), the composition
+   runs on the first device of the list, the result (LGLSXP, the extents of x) stays on the device and *out_nnz is its
+   nonzero count.  The existing svt_Arith_SVT_end ends it, with int32 values.  The dims of x and y must be identical
+   (< 0: "non-conformable arrays").  Not offered: NaArray operands (> 0), character / raw / complex operands, == <= >=
+   between two arrays, dense-array operands. */
+int svt_Compare_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int64_t *out_nnz);
+int svt_Compare_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res, int64_t *out_nnz);
+int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int64_t *out_nnz);
+
 #ifdef __cplusplus
 }
 #endif

@@ -394,6 +394,35 @@ class CAbiDispatcher:
         from .api import MATH_OPCODES
         return self._arith("Math_SVT_begin", x, (MATH_OPCODES.get(op, 0), float(digits)), x.dimnames, with_ovflow=False)[0]
 
+    # Compare / Logic (src/SparseArray_Compare_methods.c, src/SparseArray_Logic_methods.c; include/svt_hip.h; HIP library
+    # only): the same begin / end pair, the result "logical" with explicit values (1 or NA) ---------------------------
+    def _logical_result(self, begin, x, args, dimnames):
+        res, nnz = c_void_p(0), ctypes.c_int64(0)
+        self._run(begin, x, *args, byref(res), byref(nnz))
+        n = int(nnz.value)
+        cp = np.zeros(int(np.prod(x.dim[1:], dtype=np.int64)) + 1, dtype=np.int64)
+        ri = np.zeros(max(n, 1), dtype=np.int32)
+        vv = np.zeros(max(n, 1), dtype=np.int32)
+        self._run("Arith_SVT_end", res, cp, ri, vv)
+        return SVT_SparseArray.from_csc(tuple(x.dim), "logical", cp, ri[:n], vv[:n], dimnames=dimnames)
+
+    def C_Compare_SVT1_v2(self, x: SVT_SparseArray, y: float, y_type: str, op: str):
+        """x op y for the scalar ``y`` of R type ``y_type`` ("logical" / "integer" / "double"; an integer or logical
+        NA goes over as INT_MIN, like every integer scalar as its double value)."""
+        from .api import COMPARE_OPCODES
+        return self._logical_result("Compare_SVT_scalar_begin", x, (COMPARE_OPCODES[op], float(y), _RT[y_type]), x.dimnames)
+
+    def C_Compare_SVT1_SVT2(self, x: SVT_SparseArray, y: SVT_SparseArray, op: str):
+        """x op y, op one of != < >; the dimnames are the first non-NULL ones."""
+        from .api import COMPARE_OPCODES
+        return self._logical_result("Compare_SVT_SVT_begin", x, (y, COMPARE_OPCODES[op]),
+                                    x.dimnames if x.dimnames is not None else y.dimnames)
+
+    def C_Logic_SVT1_SVT2(self, x: SVT_SparseArray, y: SVT_SparseArray, op: str):
+        from .api import LOGIC_OPCODES
+        return self._logical_result("Logic_SVT_SVT_begin", x, (y, LOGIC_OPCODES[op]),
+                                    x.dimnames if x.dimnames is not None else y.dimnames)
+
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""
         return self._dgc("rowsum_dgCMatrix", x, group, ngroup, na_rm,

@@ -12,6 +12,7 @@ as ``src/R_init_SparseArray.c:94,121-134``:
     C_colMins_dgCMatrix   C_colMaxs_dgCMatrix   C_colRanges_dgCMatrix  C_colVars_dgCMatrix
     C_transpose_2D_SVT    C_aperm_SVT           C_subset_SVT_by_Nindex (2-D operands)
     C_Arith_SVT1_SVT2     C_Arith_SVT1_v2       C_unary_minus_SVT      C_Math_SVT (HIP library only)
+    C_Compare_SVT1_v2     C_Compare_SVT1_SVT2   C_Logic_SVT1_SVT2      (HIP library only)
 
 and the entry points the HIP library adds to them (include/svt_hip.h):
 
@@ -63,6 +64,11 @@ MATH_OPCODES = {name: k + 1 for k, name in enumerate(
      "tan", "atan", "tanh", "atanh", "tanpi", "round", "signif"))}
 _SUPPORTED_MATH_OPS = tuple(MATH_OPCODES)[:18]
 _ARITH_INPUT_TYPES = ("integer", "double")      # (and "complex", which no SVT_SparseArray of this package has)
+# Compare operators -> SVT_COMPARE_*, Logic operators -> SVT_LOGIC_* (include/svt_hip.h; the reference's opcodes)
+COMPARE_OPCODES = {"==": 1, "!=": 2, "<=": 3, ">=": 4, "<": 5, ">": 6}
+LOGIC_OPCODES = {"&": 1, "|": 2}
+# COMPARE_INPUT_TYPES of R/SparseArray-Compare-methods.R:12-13 without "raw", in the order "bigger type" follows
+_COMPARE_INPUT_TYPES = ("logical", "integer", "double", "complex", "character")
 
 
 # row statistics that C_rowStats_SVT does not take: one C_rowStatsFull_SVT call where the library has it
@@ -728,6 +734,152 @@ class Session:
             raise SparseArrayError("'digits' must be a single number")
         self._optional_entry("C_Math_SVT", "Math_SVT_begin")
         return self.SparseArray_Call("C_Math_SVT", x, op, 0.0 if digits is None else float(digits))
+
+    # ------------------------------------------------------------------
+    # Compare, Logic, "!"  (R/SparseArray-Compare-methods.R, R/SparseArray-Logic-methods.R)
+    # ------------------------------------------------------------------
+    @staticmethod
+    def _check_Compare_input_type(type_: str, what: str):
+        # check_Compare_input_type, R/SparseArray-Compare-methods.R:15-20
+        if type_ not in _COMPARE_INPUT_TYPES:
+            raise SparseArrayError(f"comparison operation not supported on {what} of type() \"{type_}\"")
+
+    @staticmethod
+    def _check_Compare_op_on_complex_vals(op, x_type, y_type):
+        if "complex" in (x_type, y_type) and op in ("<=", ">=", "<", ">"):
+            raise SparseArrayError("invalid comparison with complex values")
+
+    @staticmethod
+    def _must_homogenize_for_Compare(x_type, y_type):
+        # must_homogenize_for_Compare (:32-56): what is left of it for the types an object of this package can have
+        if "character" in (x_type, y_type):
+            raise SparseArrayError("comparison operations are not implemented yet between SVT_SparseArray objects, or "
+                                   "between an SVT_SparseArray object and a single value, when one or the other is of "
+                                   "type() \"character\"")
+
+    def _Compare_SVT1_v2(self, op, x, y):
+        # .Compare_SVT1_v2, R/SparseArray-Compare-methods.R:60-121
+        self._check_Compare_input_type(x.type, "SparseArray object")
+        cls, ytype, length, v = self._scalar_class_type(y)
+        if ytype not in _COMPARE_INPUT_TYPES:
+            raise SparseArrayError(f"comparison operations between SparseArray objects and {cls} vectors are not supported")
+        self._check_Compare_op_on_complex_vals(op, x.type, ytype)
+        if length != 1:
+            raise SparseArrayError("comparison operations are not supported between a SparseArray object and a vector "
+                                   "of length != 1")
+        if ((ytype in ("logical", "integer") and int(v) == NA_integer) or (ytype == "double" and np.isnan(v))
+                or (ytype == "complex" and (np.isnan(v.real) or np.isnan(v.imag)))):
+            self._sparsity_not_preserved(op, "y is NA or NaN")
+        if ytype == "logical" and op in ("<=", "<"):
+            self._sparsity_not_preserved(op, "y is a logical or raw value")
+        biggest = max(x.type, ytype, key=_COMPARE_INPUT_TYPES.index)
+        if biggest == "character" and op in ("<=", "<"):
+            self._sparsity_not_preserved(op, "type(x) is \"character\" or y is a string")
+        v = str(v) if biggest == "character" else complex(v) if biggest == "complex" else float(v)
+        zero = "" if biggest == "character" else 0
+        if op == "==" and v == zero:
+            self._sparsity_not_preserved(op, "y is 0 or FALSE or the empty string")
+        if op == "!=" and v != zero:
+            self._sparsity_not_preserved(op, "y is not 0, FALSE, or the empty string")
+        if op == "<=" and v >= zero:
+            self._sparsity_not_preserved(op, "y is >= 0")
+        if op == ">=" and v <= zero:
+            self._sparsity_not_preserved(op, "y is <= 0, or FALSE, or the empty string")
+        if op == "<" and v > zero:
+            self._sparsity_not_preserved(op, "y is > 0")
+        if op == ">" and v < zero:
+            self._sparsity_not_preserved(op, "y is < 0")
+        self._must_homogenize_for_Compare(x.type, biggest)
+        if biggest == "complex":                            # (the reference takes it; this library has no complex type)
+            raise SparseArrayUnsupported("comparison with a complex value is not offered by this library")
+        self._optional_entry("C_Compare_SVT1_v2", "Compare_SVT_scalar_begin")
+        return self.SparseArray_Call("C_Compare_SVT1_v2", x, v, biggest, op)
+
+    def _Compare_SVT1_SVT2(self, op, x, y):
+        # .Compare_SVT1_SVT2, R/SparseArray-Compare-methods.R:133-173
+        self._check_Compare_input_type(x.type, "SparseArray object")
+        self._check_Compare_input_type(y.type, "SparseArray object")
+        self._check_Compare_op_on_complex_vals(op, x.type, y.type)
+        if op not in ("!=", "<", ">"):
+            suggest = {"==": "!=", "<=": "<", ">=": ">"}[op]
+            raise SparseArrayError(f"\"{op}\" is not supported between SparseArray objects (result wouldn't be sparse in "
+                                   f"general), but \"{suggest}\" is")
+        if tuple(x.dim) != tuple(y.dim):
+            raise SparseArrayError("non-conformable arrays")
+        self._must_homogenize_for_Compare(x.type, y.type)
+        self._optional_entry("C_Compare_SVT1_SVT2", "Compare_SVT_SVT_begin")
+        return self.SparseArray_Call("C_Compare_SVT1_SVT2", x, y, op)
+
+    def compare(self, op: str, e1, e2):
+        """``e1 op e2`` of the Compare group (``== != <= >= < >``) with an SVT_SparseArray on at least one side: two
+        arrays of the same dim (``!= < >``), or an array and a scalar against which zero compares FALSE (``x > 0``,
+        ``x != 0``, ``x >= 1``, ...; a scalar on the left flips the operator).  A Python bool is an R logical, an int an
+        integer, a float a double.  Returns a "logical" SVT_SparseArray whose stored values are TRUE or NA.  Dense
+        array operands are not offered."""
+        if op not in COMPARE_OPCODES:
+            raise SparseArrayError(f"invalid Compare operation \"{op}\"")
+        s1, s2 = isinstance(e1, SVT_SparseArray), isinstance(e2, SVT_SparseArray)
+        if not (s1 or s2):
+            raise SparseArrayError("compare() needs an SVT_SparseArray operand")
+        if any(isinstance(e, np.ndarray) and e.ndim >= 2 for e in (e1, e2)):
+            raise SparseArrayUnsupported("comparison with a dense array is not offered by this library")
+        if s1 and s2:
+            return self._Compare_SVT1_SVT2(op, e1, e2)
+        if s1:
+            return self._Compare_SVT1_v2(op, e1, e2)
+        flip = {"<=": ">=", ">=": "<=", "<": ">", ">": "<"}                     # flip_Compare_op, :22-23
+        return self._Compare_SVT1_v2(flip.get(op, op), e2, e1)
+
+    @staticmethod
+    def _check_Logic_input_type(type_: str, what: str):
+        # check_Logic_input_type, R/SparseArray-Logic-methods.R:18-23
+        if type_ != "logical":
+            raise SparseArrayError(f"'Logic' operation \"&\" and \"|\" not supported on {what} of type() \"{type_}\"")
+
+    def _Logic_SVT1_v2(self, op, x, y):
+        # .Logic_SVT1_v2, R/SparseArray-Logic-methods.R:43-67: no call; None stands for R's (logical) NA
+        self._check_Logic_input_type(x.type, "SparseArray object")
+        cls, ytype, length, v = ("logical", "logical", 1, None) if y is None else self._scalar_class_type(y)
+        if ytype != "logical":
+            raise SparseArrayError(f"\"{op}\" between a SparseArray object and a {cls} vector is not supported")
+        if length != 1:
+            raise SparseArrayError(f"\"{op}\" between a SparseArray object and a vector of length != 1 is not supported")
+        if v is None:
+            self._sparsity_not_preserved(op, "y is NA")
+        if op == "&" and not v:
+            return SVT_SparseArray(x.dim, x.type, [None] * len(x.leaves), dimnames=x.dimnames)
+        if op == "|" and v:
+            self._sparsity_not_preserved(op, "y is TRUE")
+        return x
+
+    def _Logic_SVT1_SVT2(self, op, x, y):
+        # .Logic_SVT1_SVT2, R/SparseArray-Logic-methods.R:77-102
+        self._check_Logic_input_type(x.type, "SparseArray object")
+        self._check_Logic_input_type(y.type, "SparseArray object")
+        if tuple(x.dim) != tuple(y.dim):
+            raise SparseArrayError("non-conformable arrays")
+        self._optional_entry("C_Logic_SVT1_SVT2", "Logic_SVT_SVT_begin")
+        return self.SparseArray_Call("C_Logic_SVT1_SVT2", x, y, op)
+
+    def logic(self, op: str, e1, e2):
+        """``e1 & e2`` / ``e1 | e2`` with a "logical" SVT_SparseArray on at least one side: two arrays of the same dim,
+        or an array and a single bool (``None`` for NA), which needs no call: ``x & TRUE`` and ``x | FALSE`` are ``x``,
+        ``x & FALSE`` is ``x`` without its leaves, ``x | TRUE`` and an NA raise.  Dense array operands are not offered."""
+        if op not in LOGIC_OPCODES:
+            raise SparseArrayError(f"invalid Logic operation \"{op}\"")
+        s1, s2 = isinstance(e1, SVT_SparseArray), isinstance(e2, SVT_SparseArray)
+        if not (s1 or s2):
+            raise SparseArrayError("logic() needs an SVT_SparseArray operand")
+        if any(isinstance(e, np.ndarray) and e.ndim >= 2 for e in (e1, e2)):
+            raise SparseArrayUnsupported("\"&\" and \"|\" with a dense array are not offered by this library")
+        if s1 and s2:
+            return self._Logic_SVT1_SVT2(op, e1, e2)
+        return self._Logic_SVT1_v2(op, e1, e2) if s1 else self._Logic_SVT1_v2(op, e2, e1)
+
+    def logical_not(self, x):
+        # the "!" method, R/SparseArray-Logic-methods.R:30-36
+        raise SparseArrayError("logical negation (\"!\") is not supported on SparseArray objects (result wouldn't be "
+                               "sparse in general)")
 
     def _OLD_rowStats(self, op, x, na_rm, center, dims):
         # .OLD_rowStats_SparseArray (:122-190): "aperm(colStats(aperm(x), dims=ndim-dims))",

@@ -24,6 +24,12 @@
 // (the first key of the next thread's or the next tile's y part: one key past the part is loaded), the y entry looks
 // at the x key before it (one key before the part is loaded) and emits nothing.
 //
+// Compare and Logic (C_Compare_SVT1_v2, C_Compare_SVT1_SVT2, C_Logic_SVT1_SVT2; the rules svt_rule_compare and
+// svt_rule_logic) are further rules on the same two families: the tile evaluators and the four tile kernels take the
+// rule as a template parameter (ARI_RULE_ARITH / _COMPARE / _LOGIC), the result of the two new rules is int32 whatever
+// the operands, and no overflow is raised.  Everything else -- tiles, column search, ranking, placement, the cut, the
+// ownership of a pair, the workspace -- is shared as it is.
+//
 // LDS: keys 8 * (2048 + 2), sources 4 * 2048, ballots and chunk prefixes 0.4 KB: 24.5 KB for the merge (6 workgroups
 // of a CU's 160 KB), 0.4 KB for the map.
 #include "svt_common.h"
@@ -149,10 +155,12 @@ struct AriMapOp {
 	int32_t si;         // and as an integer (integer results)
 };
 
-template <typename TX, typename TO>
+template <typename TX, typename TO, int RULE>
 __device__ inline TO ari_map_eval(const AriMapOp &m, TX v, int *ovf)
 {
-	if constexpr (std::is_same<TO, int32_t>::value) {
+	if constexpr (RULE == ARI_RULE_COMPARE) {
+		return svt_rule_compare(m.op, svt_rule_as_double(v), m.sd);
+	} else if constexpr (std::is_same<TO, int32_t>::value) {
 		if (m.kind == SVT_ARITH_NEG) return v == NA_INT ? NA_INT : -v;
 		return svt_rule_arith_int(m.op, v, m.si, ovf);
 	} else {
@@ -164,7 +172,7 @@ __device__ inline TO ari_map_eval(const AriMapOp &m, TX v, int *ovf)
 }
 
 // the results of this thread's entries of the tile (striped) and whether they are kept
-template <typename TX, typename TO>
+template <typename TX, typename TO, int RULE>
 __device__ inline void ari_map_tile(const TX *val, int64_t ts, int n, const AriMapOp &m, TO (&r)[ARI_ITEMS],
 				    bool (&keep)[ARI_ITEMS], int *ovf)
 {
@@ -173,13 +181,13 @@ __device__ inline void ari_map_tile(const TX *val, int64_t ts, int n, const AriM
 		const int i = it * ARI_NT + threadIdx.x;
 		keep[it] = false;
 		if (i < n) {
-			r[it] = ari_map_eval<TX, TO>(m, val[ts + i], ovf);
+			r[it] = ari_map_eval<TX, TO, RULE>(m, val[ts + i], ovf);
 			keep[it] = !ari_is_zero(r[it]);
 		}
 	}
 }
 
-template <typename TX, typename TO>
+template <typename TX, typename TO, int RULE>
 __global__ __launch_bounds__(ARI_NT) void arith_map_count_kernel(const int64_t *col_ptr, const TX *val, int64_t ncol, int64_t nnz,
 								 AriMapOp m, int64_t *tile_cnt, int32_t *local)
 {
@@ -191,12 +199,12 @@ __global__ __launch_bounds__(ARI_NT) void arith_map_count_kernel(const int64_t *
 	TO r[ARI_ITEMS];
 	bool keep[ARI_ITEMS];
 	int ovf = 0;
-	ari_map_tile<TX, TO>(val, ts, n, m, r, keep, &ovf);
+	ari_map_tile<TX, TO, RULE>(val, ts, n, m, r, keep, &ovf);
 	ari_rank(keep, sh);
 	ari_count_tail(P, ts, sh, tile_cnt, local);
 }
 
-template <typename TX, typename TO>
+template <typename TX, typename TO, int RULE>
 __global__ __launch_bounds__(ARI_NT) void arith_map_fill_kernel(const int32_t *row_idx, const TX *val, int64_t nnz, AriMapOp m,
 								const int64_t *tile_pre, int32_t *out_row_idx, TO *out_val,
 								int *ovflow)
@@ -207,7 +215,7 @@ __global__ __launch_bounds__(ARI_NT) void arith_map_fill_kernel(const int32_t *r
 	TO r[ARI_ITEMS];
 	bool keep[ARI_ITEMS];
 	int ovf = 0;
-	ari_map_tile<TX, TO>(val, ts, n, m, r, keep, &ovf);
+	ari_map_tile<TX, TO, RULE>(val, ts, n, m, r, keep, &ovf);
 	ari_rank(keep, sh);
 	const int64_t base = tile_pre[blockIdx.x];
 #pragma unroll
@@ -262,19 +270,20 @@ struct AriMergeShared {
 	int64_t rng[4];                 // column ranges of the two parts
 };
 
-template <typename TX, typename TY> struct AriMergeOut {
-	typedef typename std::conditional<std::is_same<TX, int32_t>::value && std::is_same<TY, int32_t>::value, int32_t, double>::type type;
+template <typename TX, typename TY, int RULE> struct AriMergeOut {
+	typedef typename std::conditional<RULE != ARI_RULE_ARITH || (std::is_same<TX, int32_t>::value && std::is_same<TY, int32_t>::value),
+					  int32_t, double>::type type;
 };
 
 // One tile of the merged sequence: merged places [ts, ts + n), x entries [a0, a0 + na), y entries [b0, b0 + nb).  Leaves
 // per striped place of this thread the result, its row and whether it is kept.
-template <typename TX, typename TY>
+template <typename TX, typename TY, int RULE>
 __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const AriSide &Y, const TY *yval, int64_t ncol, int64_t nrow,
 				      int op, int64_t a0, int na, int64_t b0, int nb, AriMergeShared &sh,
-				      typename AriMergeOut<TX, TY>::type (&r)[ARI_ITEMS], int32_t (&row)[ARI_ITEMS],
+				      typename AriMergeOut<TX, TY, RULE>::type (&r)[ARI_ITEMS], int32_t (&row)[ARI_ITEMS],
 				      bool (&keep)[ARI_ITEMS], int *ovf)
 {
-	typedef typename AriMergeOut<TX, TY>::type TO;
+	typedef typename AriMergeOut<TX, TY, RULE>::type TO;
 	const int tid = threadIdx.x, n = na + nb;
 	const AriColPtr xcp = { X.col_ptr }, ycp = { Y.col_ptr };
 	// the keys that are read: x entries [a0 - 1, a0 + na), y entries [b0, b0 + nb] (those that exist)
@@ -331,7 +340,11 @@ __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const Ar
 			row[it] = X.row_idx[a0 + idx];
 			if (s & ARI_PAIRED) yv = yval[b0 + (p - idx)];  // idx of x's and p - idx of y's come before place p
 		}
-		if constexpr (std::is_same<TO, int32_t>::value)
+		if constexpr (RULE == ARI_RULE_COMPARE)
+			r[it] = svt_rule_compare(op, svt_rule_as_double(xv), svt_rule_as_double(yv));
+		else if constexpr (RULE == ARI_RULE_LOGIC)
+			r[it] = svt_rule_logic(op, xv, yv);
+		else if constexpr (std::is_same<TO, int32_t>::value)
 			r[it] = svt_rule_arith_int(op, xv, yv, ovf);
 		else
 			r[it] = svt_rule_arith_double(op, svt_rule_as_double(xv), svt_rule_as_double(yv));
@@ -339,12 +352,12 @@ __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const Ar
 	}
 }
 
-template <typename TX, typename TY>
+template <typename TX, typename TY, int RULE>
 __global__ __launch_bounds__(ARI_NT) void arith_merge_count_kernel(AriSide X, const TX *xval, AriSide Y, const TY *yval, int64_t ncol,
 								   int64_t nrow, int op, const int64_t *cut, int64_t *tile_cnt,
 								   int32_t *local)
 {
-	typedef typename AriMergeOut<TX, TY>::type TO;
+	typedef typename AriMergeOut<TX, TY, RULE>::type TO;
 	__shared__ AriMergeShared sh;
 	const int64_t ts = (int64_t) blockIdx.x << ARI_SHIFT, total = X.nnz + Y.nnz;
 	const int n = (int) (total - ts < ARI_TILE ? total - ts : ARI_TILE);
@@ -355,19 +368,19 @@ __global__ __launch_bounds__(ARI_NT) void arith_merge_count_kernel(AriSide X, co
 	int32_t row[ARI_ITEMS];
 	bool keep[ARI_ITEMS];
 	int ovf = 0;
-	ari_merge_tile<TX, TY>(X, xval, Y, yval, ncol, nrow, op, a0, (int) (a1 - a0), ts - a0, n - (int) (a1 - a0), sh, r, row, keep,
+	ari_merge_tile<TX, TY, RULE>(X, xval, Y, yval, ncol, nrow, op, a0, (int) (a1 - a0), ts - a0, n - (int) (a1 - a0), sh, r, row, keep,
 			       &ovf);
 	ari_rank(keep, sh.r);
 	ari_count_tail(P, ts, sh.r, tile_cnt, local);
 }
 
-template <typename TX, typename TY>
+template <typename TX, typename TY, int RULE>
 __global__ __launch_bounds__(ARI_NT) void arith_merge_fill_kernel(AriSide X, const TX *xval, AriSide Y, const TY *yval, int64_t ncol,
 								  int64_t nrow, int op, const int64_t *cut, const int64_t *tile_pre,
-								  int32_t *out_row_idx, typename AriMergeOut<TX, TY>::type *out_val,
+								  int32_t *out_row_idx, typename AriMergeOut<TX, TY, RULE>::type *out_val,
 								  int *ovflow)
 {
-	typedef typename AriMergeOut<TX, TY>::type TO;
+	typedef typename AriMergeOut<TX, TY, RULE>::type TO;
 	__shared__ AriMergeShared sh;
 	const int64_t ts = (int64_t) blockIdx.x << ARI_SHIFT, total = X.nnz + Y.nnz;
 	const int n = (int) (total - ts < ARI_TILE ? total - ts : ARI_TILE);
@@ -376,7 +389,7 @@ __global__ __launch_bounds__(ARI_NT) void arith_merge_fill_kernel(AriSide X, con
 	int32_t row[ARI_ITEMS];
 	bool keep[ARI_ITEMS];
 	int ovf = 0;
-	ari_merge_tile<TX, TY>(X, xval, Y, yval, ncol, nrow, op, a0, (int) (a1 - a0), ts - a0, n - (int) (a1 - a0), sh, r, row, keep,
+	ari_merge_tile<TX, TY, RULE>(X, xval, Y, yval, ncol, nrow, op, a0, (int) (a1 - a0), ts - a0, n - (int) (a1 - a0), sh, r, row, keep,
 			       &ovf);
 	ari_rank(keep, sh.r);
 	const int64_t base = tile_pre[blockIdx.x];
@@ -434,14 +447,25 @@ static int arith_count_finish(const ArithWs &L, AriPtr P, int64_t ncol, int64_t 
 	return 0;
 }
 
-// f(x values, AriMapOp, result type tag) by the operand's and the result's type
+template <int RULE> using AriRule = std::integral_constant<int, RULE>;
+
+// f(x values, AriMapOp, result type tag, rule tag) by the rule and the operand's and the result's type; only the
+// combinations that are offered are instantiated (Compare: an int32 -- logical or integer -- or a double operand)
 template <class F>
 static inline int arith_map_by_types(const ArithMapArgs &a, F &&f)
 {
 	const AriMapOp m = { a.kind, a.op, a.sd, a.si };
-	if (a.Rtype == SVT_REALSXP && a.out_Rtype == SVT_REALSXP) f((const double *) a.val, m, (double *) NULL);
-	else if (a.Rtype == SVT_INTSXP && a.out_Rtype == SVT_REALSXP) f((const int32_t *) a.val, m, (double *) NULL);
-	else if (a.Rtype == SVT_INTSXP && a.out_Rtype == SVT_INTSXP) f((const int32_t *) a.val, m, (int32_t *) NULL);
+	if (a.rule == ARI_RULE_COMPARE) {
+		if (a.Rtype == SVT_REALSXP) f((const double *) a.val, m, (int32_t *) NULL, AriRule<ARI_RULE_COMPARE>());
+		else if (a.Rtype == SVT_INTSXP || a.Rtype == SVT_LGLSXP)
+			f((const int32_t *) a.val, m, (int32_t *) NULL, AriRule<ARI_RULE_COMPARE>());
+		else return svt_set_error("compare map: no kernel for this type");
+		return 0;
+	}
+	if (a.rule != ARI_RULE_ARITH) return svt_set_error("arith map: no kernel for this rule");
+	if (a.Rtype == SVT_REALSXP && a.out_Rtype == SVT_REALSXP) f((const double *) a.val, m, (double *) NULL, AriRule<ARI_RULE_ARITH>());
+	else if (a.Rtype == SVT_INTSXP && a.out_Rtype == SVT_REALSXP) f((const int32_t *) a.val, m, (double *) NULL, AriRule<ARI_RULE_ARITH>());
+	else if (a.Rtype == SVT_INTSXP && a.out_Rtype == SVT_INTSXP) f((const int32_t *) a.val, m, (int32_t *) NULL, AriRule<ARI_RULE_ARITH>());
 	else return svt_set_error("arith map: no kernel for these types");
 	return 0;
 }
@@ -456,10 +480,10 @@ int launch_arith_map_count(const ArithMapArgs &a, int64_t *out_col_ptr, void *ws
 	HIP_TRY(hipMemsetAsync(w, 0, 256, s));
 	HIP_TRY(hipMemsetAsync(tile + L.ntiles, 0, 8, s));
 	if (L.ntiles > 0) {
-		const int rc = arith_map_by_types(a, [&](auto *v, const AriMapOp &m, auto *o) {
+		const int rc = arith_map_by_types(a, [&](auto *v, const AriMapOp &m, auto *o, auto rule) {
 			typedef std::remove_const_t<std::remove_pointer_t<decltype(v)>> TX;
 			typedef std::remove_pointer_t<decltype(o)> TO;
-			hipLaunchKernelGGL((arith_map_count_kernel<TX, TO>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, a.col_ptr, v,
+			hipLaunchKernelGGL((arith_map_count_kernel<TX, TO, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, a.col_ptr, v,
 					   a.ncol, a.nnz, m, tile, (int32_t *) (w + L.local));
 		});
 		if (rc) return rc;
@@ -474,10 +498,10 @@ int launch_arith_map_fill(const ArithMapArgs &a, int32_t *out_row_idx, void *out
 	if (L.ntiles == 0)
 		return 0;
 	const int64_t *tile = (const int64_t *) ((const char *) ws + L.tile);
-	const int rc = arith_map_by_types(a, [&](auto *v, const AriMapOp &m, auto *o) {
+	const int rc = arith_map_by_types(a, [&](auto *v, const AriMapOp &m, auto *o, auto rule) {
 		typedef std::remove_const_t<std::remove_pointer_t<decltype(v)>> TX;
 		typedef std::remove_pointer_t<decltype(o)> TO;
-		hipLaunchKernelGGL((arith_map_fill_kernel<TX, TO>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, a.row_idx, v, a.nnz, m,
+		hipLaunchKernelGGL((arith_map_fill_kernel<TX, TO, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, a.row_idx, v, a.nnz, m,
 				   tile, out_row_idx, (TO *) out_val, ovflow);
 	});
 	if (rc) return rc;
@@ -485,14 +509,25 @@ int launch_arith_map_fill(const ArithMapArgs &a, int32_t *out_row_idx, void *out
 	return 0;
 }
 
-// f(x values, y values) by the two operands' types
-template <class F>
-static inline void arith_merge_by_types(const ArithMergeArgs &a, F &&f)
+// f(x values, y values, rule tag) by the two operands' types (a logical operand is an int32 operand)
+template <class F, class R>
+static inline void arith_merge_by_operands(const ArithMergeArgs &a, F &&f, R rule)
 {
-	if (a.x_Rtype == SVT_REALSXP && a.y_Rtype == SVT_REALSXP) f((const double *) a.x_val, (const double *) a.y_val);
-	else if (a.x_Rtype == SVT_REALSXP) f((const double *) a.x_val, (const int32_t *) a.y_val);
-	else if (a.y_Rtype == SVT_REALSXP) f((const int32_t *) a.x_val, (const double *) a.y_val);
-	else f((const int32_t *) a.x_val, (const int32_t *) a.y_val);
+	if (a.x_Rtype == SVT_REALSXP && a.y_Rtype == SVT_REALSXP) f((const double *) a.x_val, (const double *) a.y_val, rule);
+	else if (a.x_Rtype == SVT_REALSXP) f((const double *) a.x_val, (const int32_t *) a.y_val, rule);
+	else if (a.y_Rtype == SVT_REALSXP) f((const int32_t *) a.x_val, (const double *) a.y_val, rule);
+	else f((const int32_t *) a.x_val, (const int32_t *) a.y_val, rule);
+}
+// and by the rule: Arith and Compare for the four type pairs, Logic for int32 x int32 alone
+template <class F>
+static inline int arith_merge_by_types(const ArithMergeArgs &a, F &&f)
+{
+	if (a.rule == ARI_RULE_ARITH) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ARITH>());
+	else if (a.rule == ARI_RULE_COMPARE) arith_merge_by_operands(a, f, AriRule<ARI_RULE_COMPARE>());
+	else if (a.rule == ARI_RULE_LOGIC && a.x_Rtype != SVT_REALSXP && a.y_Rtype != SVT_REALSXP)
+		f((const int32_t *) a.x_val, (const int32_t *) a.y_val, AriRule<ARI_RULE_LOGIC>());
+	else return svt_set_error("arith merge: no kernel for this rule and these types");
+	return 0;
 }
 
 int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s)
@@ -509,12 +544,13 @@ int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void
 	if (L.ntiles > 0) {
 		hipLaunchKernelGGL(arith_merge_cut_kernel, dim3(blocks_for(L.ntiles + 1)), dim3(ARI_NT), 0, s, X, Y, a.ncol, a.nrow,
 				   L.ntiles, cut);
-		arith_merge_by_types(a, [&](auto *xv, auto *yv) {
+		const int rc = arith_merge_by_types(a, [&](auto *xv, auto *yv, auto rule) {
 			typedef std::remove_const_t<std::remove_pointer_t<decltype(xv)>> TX;
 			typedef std::remove_const_t<std::remove_pointer_t<decltype(yv)>> TY;
-			hipLaunchKernelGGL((arith_merge_count_kernel<TX, TY>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, X, xv, Y, yv,
-					   a.ncol, a.nrow, a.op, (const int64_t *) cut, tile, (int32_t *) (w + L.local));
+			hipLaunchKernelGGL((arith_merge_count_kernel<TX, TY, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0,
+					   s, X, xv, Y, yv, a.ncol, a.nrow, a.op, (const int64_t *) cut, tile, (int32_t *) (w + L.local));
 		});
+		if (rc) return rc;
 	}
 	const AriPtr P = { a.x_col_ptr, a.y_col_ptr };
 	return arith_count_finish(L, P, a.ncol, entries, out_col_ptr, w, s);
@@ -527,14 +563,15 @@ int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void 
 		return 0;
 	const char *w = (const char *) ws;
 	const AriSide X = { a.x_col_ptr, a.x_row_idx, a.x_nnz }, Y = { a.y_col_ptr, a.y_row_idx, a.y_nnz };
-	arith_merge_by_types(a, [&](auto *xv, auto *yv) {
+	const int rc = arith_merge_by_types(a, [&](auto *xv, auto *yv, auto rule) {
 		typedef std::remove_const_t<std::remove_pointer_t<decltype(xv)>> TX;
 		typedef std::remove_const_t<std::remove_pointer_t<decltype(yv)>> TY;
-		typedef typename AriMergeOut<TX, TY>::type TO;
-		hipLaunchKernelGGL((arith_merge_fill_kernel<TX, TY>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, X, xv, Y, yv, a.ncol,
-				   a.nrow, a.op, (const int64_t *) (w + L.cut), (const int64_t *) (w + L.tile), out_row_idx,
-				   (TO *) out_val, ovflow);
+		typedef typename AriMergeOut<TX, TY, decltype(rule)::value>::type TO;
+		hipLaunchKernelGGL((arith_merge_fill_kernel<TX, TY, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, X,
+				   xv, Y, yv, a.ncol, a.nrow, a.op, (const int64_t *) (w + L.cut), (const int64_t *) (w + L.tile),
+				   out_row_idx, (TO *) out_val, ovflow);
 	});
+	if (rc) return rc;
 	HIP_TRY(hipGetLastError());
 	return 0;
 }

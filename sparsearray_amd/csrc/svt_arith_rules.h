@@ -317,6 +317,44 @@ SVT_HD inline double svt_rule_math(int op, double x)
 	return svt_rule_nan();
 }
 
+// ---- Compare and Logic (src/SparseVec_Compare.c, src/SparseVec_Logic.c of the reference) ----
+// x op y for == != <= >= < >: NA when either side is a NaN (NA_real_ included), else 0 or 1.  The operands come
+// through svt_rule_as_double, so NA_integer_ arrives as NA_real_.  The reference separates Compare_int_int,
+// Compare_int_double and Compare_double_double; this one rule in double is exact for all of them, because every int32
+// is a double and the conversion keeps the order: two integers compare in double as they compare as integers.
+SVT_HD inline int32_t svt_rule_compare(int op, double x, double y)
+{
+	if (x != x || y != y)
+		return SVT_NA_INT;
+	switch (op) {
+	case SVT_COMPARE_EQ: return x == y;
+	case SVT_COMPARE_NE: return x != y;
+	case SVT_COMPARE_LE: return x <= y;
+	case SVT_COMPARE_GE: return x >= y;
+	case SVT_COMPARE_LT: return x < y;
+	case SVT_COMPARE_GT: return x > y;
+	}
+	return SVT_NA_INT;
+}
+
+// x & y, x | y on logical values (0, 1, NA): Logic_int_int.  & is FALSE next to a FALSE, else NA next to an NA; | is
+// TRUE next to a TRUE, else NA next to an NA.
+SVT_HD inline int32_t svt_rule_logic(int op, int32_t x, int32_t y)
+{
+	if (op == SVT_LOGIC_AND) {
+		if (x == 0 || y == 0)
+			return 0;
+		if (x == SVT_NA_INT || y == SVT_NA_INT)
+			return SVT_NA_INT;
+		return 1;
+	}
+	if (x == 1 || y == 1)                               // SVT_LOGIC_OR
+		return 1;
+	if (x == SVT_NA_INT || y == SVT_NA_INT)
+		return SVT_NA_INT;
+	return 0;
+}
+
 // the type of the result (SVT_INTSXP / SVT_REALSXP), or 0 for a combination that is not offered
 SVT_HD inline int svt_rule_out_Rtype(int kind, int op, int x_Rtype, int y_Rtype)
 {

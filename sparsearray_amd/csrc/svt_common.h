@@ -272,7 +272,10 @@ int launch_subset_rows_fill(const int32_t *row_idx, const void *val, int Rtype, 
 
 // Arith and Math (kernels_arith.hip): the map f(x) and the merge x op y, each a count launcher that leaves out_col_ptr
 // and, in the head of `ws`, [int64 at byte 8: the nonzeros of the result], and a fill launcher that reads `ws` as the
-// count launcher left it.  All asynchronous.  `entries`: nnz for the map, nnz(x) + nnz(y) for the merge.
+// count launcher left it.  All asynchronous.  `entries`: nnz for the map, nnz(x) + nnz(y) for the merge.  `rule`: the
+// element rule the tiles evaluate -- Arith and Math as `kind` and `op` say, or Compare / Logic (`op` a SVT_COMPARE_* /
+// SVT_LOGIC_* opcode, `kind` not read), whose result is int32 whatever the operands and has no overflow word.
+enum { ARI_RULE_ARITH = 0, ARI_RULE_COMPARE = 1, ARI_RULE_LOGIC = 2 };
 struct ArithMapArgs {
 	const int64_t *col_ptr;
 	const int32_t *row_idx;
@@ -283,12 +286,14 @@ struct ArithMapArgs {
 	double sd;              // the scalar, as a double and as an integer
 	int32_t si;
 	int out_Rtype;
+	int rule = ARI_RULE_ARITH;
 };
 struct ArithMergeArgs {
 	const int64_t *x_col_ptr; const int32_t *x_row_idx; const void *x_val; int x_Rtype; int64_t x_nnz;
 	const int64_t *y_col_ptr; const int32_t *y_row_idx; const void *y_val; int y_Rtype; int64_t y_nnz;
 	int64_t nrow, ncol;
 	int op;
+	int rule = ARI_RULE_ARITH;
 };
 int arith_tile(void);
 size_t arith_ws_bytes(int64_t ncol, int64_t entries, int merge);

@@ -1507,6 +1507,51 @@ static int arith_check(const char *who, int kind, int op, const svt_dev_csc *x, 
 	return 0;
 }
 
+// The same for Compare and Logic (`rule`: ARI_RULE_COMPARE / _LOGIC; `kind`: SVT_ARITH_MERGE for x op y, SVT_ARITH_SCALAR
+// for the map x op s).  Nothing here looks at a value on the device: every refusal comes before anything is launched.
+static inline bool logical_family_type(int Rtype)
+{
+	return Rtype == SVT_LGLSXP || Rtype == SVT_INTSXP || Rtype == SVT_REALSXP;
+}
+static int compare_check(const char *who, int rule, int kind, int op, const svt_dev_csc *x, const svt_dev_csc *y, double s,
+			 int s_Rtype)
+{
+	const bool merge = kind == SVT_ARITH_MERGE;
+	if (x == NULL || merge != (y != NULL))
+		return svt_set_error("%s: an operand is needed", who);
+	if (y != NULL && (x->nrow != y->nrow || x->ncol != y->ncol))
+		return svt_set_error("non-conformable arrays");
+	if (!logical_family_type(x->Rtype) || (y != NULL && !logical_family_type(y->Rtype)))
+		return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
+	if (rule == ARI_RULE_LOGIC) {
+		if (x->Rtype != SVT_LGLSXP || y->Rtype != SVT_LGLSXP)
+			return svt_set_error("'Logic' operation \"&\" and \"|\" not supported on SparseArray object of type() other than "
+					     "\"logical\"");
+		if (op != SVT_LOGIC_AND && op != SVT_LOGIC_OR)
+			return svt_set_error("%s: unknown operation (opcode %d)", who, op);
+	} else {
+		if (op < SVT_COMPARE_EQ || op > SVT_COMPARE_GT)
+			return svt_set_error("%s: unknown operation (opcode %d)", who, op);
+		if (merge && op != SVT_COMPARE_NE && op != SVT_COMPARE_LT && op != SVT_COMPARE_GT)
+			return svt_set_error("%s: only \"!=\", \"<\" and \">\" are supported between two sparse operands (result wouldn't be "
+					     "sparse in general)", who);
+		if (!merge) {
+			if (!logical_family_type(s_Rtype))
+				return svt_set_error("%s: the scalar must be of type \"logical\", \"integer\" or \"double\"", who);
+			if (svt_rule_compare(op, 0.0, s) != 0)
+				return svt_set_error("%s: 0 compared with the scalar is not FALSE (result wouldn't be sparse)", who);
+		}
+	}
+	if (x->na_background || (y != NULL && y->na_background))
+		return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+	return 0;
+}
+// the scalar of a Compare map as the double the rule sees: an integer or logical NA arrives as INT_MIN
+static inline double compare_scalar(double s, int s_Rtype)
+{
+	return s_Rtype != SVT_REALSXP && s == -2147483648.0 ? svt_rule_na_real() : s;
+}
+
 static ArithMergeArgs arith_merge_args(const svt_dev_csc *x, const svt_dev_csc *y, int op)
 {
 	ArithMergeArgs a;
@@ -1532,36 +1577,55 @@ struct ArithCall {
 	double s;
 	int s_Rtype;
 	int out_Rtype = 0;
+	int rule = ARI_RULE_ARITH;      // ARI_RULE_COMPARE / _LOGIC: `kind` says merge or map, the result is LGLSXP, no overflow word
+	ArithMergeArgs merge_args() const
+	{
+		ArithMergeArgs a = arith_merge_args(x, y, op);
+		a.rule = rule;
+		return a;
+	}
+	ArithMapArgs map_args() const
+	{
+		ArithMapArgs a = arith_map_args(x, kind, op, s, out_Rtype);
+		a.rule = rule;
+		if (rule == ARI_RULE_COMPARE) a.sd = compare_scalar(s, s_Rtype);
+		return a;
+	}
 	size_t need() const
 	{
 		return y != NULL ? svt_dev_arith_merge_ws_bytes(x->ncol, x->nnz, y->nnz) : arith_ws_bytes(x->ncol, x->nnz, 0);
 	}
 	int check(size_t ws_bytes)
 	{
-		if (arith_check(who, kind, op, x, y, s_Rtype, &out_Rtype))
-			return -1;
+		if (rule != ARI_RULE_ARITH) {
+			if (const int rc = compare_check(who, rule, kind, op, x, y, compare_scalar(s, s_Rtype), s_Rtype))
+				return rc;
+			out_Rtype = SVT_LGLSXP;
+		} else if (const int rc = arith_check(who, kind, op, x, y, s_Rtype, &out_Rtype)) {
+			return rc;
+		}
 		if (ws_bytes < need())
 			return svt_set_error("%s: workspace too small", who);
 		return 0;
 	}
 	int count(int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
 	{
-		if (check(ws_bytes))
-			return -1;
+		if (const int rc = check(ws_bytes))
+			return rc;
 		hipStream_t st = (hipStream_t) stream;
-		if (y != NULL ? launch_arith_merge_count(arith_merge_args(x, y, op), out_col_ptr, ws, st)
-			      : launch_arith_map_count(arith_map_args(x, kind, op, s, out_Rtype), out_col_ptr, ws, st))
+		if (y != NULL ? launch_arith_merge_count(merge_args(), out_col_ptr, ws, st)
+			      : launch_arith_map_count(map_args(), out_col_ptr, ws, st))
 			return -1;
 		int flag = 0;
 		return subset_read_head(ws, st, &flag, out_nnz);
 	}
 	int fill(int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream)
 	{
-		if (check(ws_bytes))
-			return -1;
+		if (const int rc = check(ws_bytes))
+			return rc;
 		hipStream_t st = (hipStream_t) stream;
-		return y != NULL ? launch_arith_merge_fill(arith_merge_args(x, y, op), out_row_idx, out_val, ovflow, ws, st)
-				 : launch_arith_map_fill(arith_map_args(x, kind, op, s, out_Rtype), out_row_idx, out_val, ovflow, ws, st);
+		return y != NULL ? launch_arith_merge_fill(merge_args(), out_row_idx, out_val, ovflow, ws, st)
+				 : launch_arith_map_fill(map_args(), out_row_idx, out_val, ovflow, ws, st);
 	}
 	// count -> allocate -> fill over the caller's allocator
 	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype_p, int64_t *out_nnz,
@@ -1634,6 +1698,89 @@ extern "C" int svt_dev_arith_map(const svt_dev_csc *x, int kind, int op, double 
 	return abi_status([&] {
 		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, ovflow, stream);
 	});
+}
+
+// ---- Compare and Logic: the same call object under another rule; the result is LGLSXP, there is no overflow word ----
+static ArithCall compare_call(const char *who, int rule, int kind, int op, const svt_dev_csc *x, const svt_dev_csc *y, double s,
+			      int s_Rtype)
+{
+	ArithCall c = { who, kind, op, x, y, s, s_Rtype };
+	c.rule = rule;
+	return c;
+}
+static int compare_compose(ArithCall c, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz,
+			   int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val, void *stream)
+{
+	return abi_status([&] {
+		int rt = 0;
+		void *val = NULL;
+		if (out_val == NULL)
+			return svt_set_error("%s: 'out_val' is needed", c.who);
+		const int rc = c.compose(alloc, release, ctx, &rt, out_nnz, out_col_ptr, out_row_idx, &val, NULL, stream);
+		if (rc == 0) *out_val = (int32_t *) val;
+		return rc;
+	});
+}
+
+extern "C" int svt_dev_compare_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr,
+					   int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_compare_merge_count", ARI_RULE_COMPARE, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_compare_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+					  int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile prefixes in `ws` place the entries)
+	ArithCall c = compare_call("svt_dev_compare_merge_fill", ARI_RULE_COMPARE, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_compare_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc,
+				     svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+				     int32_t **out_row_idx, int32_t **out_val, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_compare_merge", ARI_RULE_COMPARE, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+}
+extern "C" int svt_dev_compare_map_count(const svt_dev_csc *x, int op, double s, int s_Rtype, int64_t *out_col_ptr,
+					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_compare_map_count", ARI_RULE_COMPARE, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_compare_map_fill(const svt_dev_csc *x, int op, double s, int s_Rtype, const int64_t *out_col_ptr,
+					int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;
+	ArithCall c = compare_call("svt_dev_compare_map_fill", ARI_RULE_COMPARE, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_compare_map(const svt_dev_csc *x, int op, double s, int s_Rtype, svt_dev_alloc_fn alloc,
+				   svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+				   int32_t **out_row_idx, int32_t **out_val, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_compare_map", ARI_RULE_COMPARE, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
+	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+}
+extern "C" int svt_dev_logic_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr,
+					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_logic_merge_count", ARI_RULE_LOGIC, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_logic_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+					int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;
+	ArithCall c = compare_call("svt_dev_logic_merge_fill", ARI_RULE_LOGIC, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_logic_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc,
+				   svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+				   int32_t **out_row_idx, int32_t **out_val, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_logic_merge", ARI_RULE_LOGIC, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 
 // A %*% B, both sparse (kernels_spmm.hip): out[r + k * ldo], r < A->nrow, k < B->ncol.
@@ -2922,7 +3069,7 @@ struct svt_arith_result {
 };
 
 static int arith_begin_impl(const char *who, int kind, int op, const svt_view *x, const svt_view *y, double s, int s_Rtype,
-			    svt_arith_result **res, int *out_Rtype, int64_t *out_nnz, int *ovflow)
+			    svt_arith_result **res, int *out_Rtype, int64_t *out_nnz, int *ovflow, int rule = ARI_RULE_ARITH)
 {
 	if (res == NULL || out_Rtype == NULL || out_nnz == NULL)
 		return svt_set_error("%s: 'res', 'out_Rtype' and 'out_nnz' are needed", who);
@@ -2947,6 +3094,7 @@ static int arith_begin_impl(const char *who, int kind, int op, const svt_view *x
 	if (h == NULL) return svt_set_error("out of memory");
 	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
 	ArithCall c = { who, kind, op, A.h, B ? B->h : NULL, s, s_Rtype };
+	c.rule = rule;
 	int rt = 0;
 	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, ov.ptr(), NULL) ||
 	    hipStreamSynchronize(0) != hipSuccess) {
@@ -2998,6 +3146,30 @@ extern "C" int svt_Math_SVT_begin(const svt_view *x, int op, double digits, svt_
 	return abi_status([&] {
 		return arith_begin_impl("svt_Math_SVT_begin", SVT_ARITH_MATH, op, x, NULL, 0.0, 0, res, out_Rtype, out_nnz, NULL);
 	});
+}
+// Compare / Logic on host operands (C_Compare_SVT1_SVT2, C_Compare_SVT1_v2, C_Logic_SVT1_SVT2): the same begin under
+// another rule; the result is LGLSXP and svt_Arith_SVT_end ends it.
+static int compare_begin(const char *who, int rule, int op, const svt_view *x, const svt_view *y, bool merge, double s, int s_Rtype,
+			 svt_arith_result **res, int64_t *out_nnz)
+{
+	return abi_status([&] {
+		int rt = 0;
+		if (merge && y == NULL) return svt_set_error("%s: two operands are needed", who);
+		return arith_begin_impl(who, merge ? SVT_ARITH_MERGE : SVT_ARITH_SCALAR, op, x, y, s, s_Rtype, res, &rt, out_nnz, NULL, rule);
+	});
+}
+extern "C" int svt_Compare_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int64_t *out_nnz)
+{
+	return compare_begin("svt_Compare_SVT_SVT_begin", ARI_RULE_COMPARE, op, x, y, true, 0.0, 0, res, out_nnz);
+}
+extern "C" int svt_Compare_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res,
+					    int64_t *out_nnz)
+{
+	return compare_begin("svt_Compare_SVT_scalar_begin", ARI_RULE_COMPARE, op, x, NULL, false, s, s_Rtype, res, out_nnz);
+}
+extern "C" int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int64_t *out_nnz)
+{
+	return compare_begin("svt_Logic_SVT_SVT_begin", ARI_RULE_LOGIC, op, x, y, true, 0.0, 0, res, out_nnz);
 }
 extern "C" int svt_Arith_SVT_end(svt_arith_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
 {

@@ -165,6 +165,40 @@ class DeviceCSC:
             raise SparseArrayError(f"unknown Math operation {op!r}")
         return self._arith_result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_MATH, MATH_OPCODES[op], 0.0, 0, *a))
 
+    def _logical_result(self, call):
+        """The new logical DeviceCSC that ``call(alloc, release, ctx, nnz, col_ptr, row_idx, val, stream)`` -- one of
+        svt_dev_compare_merge / svt_dev_compare_map / svt_dev_logic_merge -- leaves in torch allocations; the call
+        stays asynchronous after its count."""
+        mem = _TorchBlocks(self.val.device)
+        nnz = c_int64(0)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz), *[ctypes.byref(o) for o in out], _stream()))
+        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), torch.int32), logical=True)
+
+    def compare(self, op: str, other) -> "DeviceCSC":
+        """``self op other`` on the device (include/svt_hip.h, svt_dev_compare_merge / svt_dev_compare_map): ``other`` a
+        DeviceCSC of the same nrow and ncol (op one of != < >) or a scalar against which zero compares FALSE (any of
+        == != <= >= < >; a Python bool is an R logical, an int an integer, a float a double).  Returns a logical
+        DeviceCSC whose values are 1 or NA_integer."""
+        from .api import COMPARE_OPCODES
+        if op not in COMPARE_OPCODES:
+            raise SparseArrayError(f"unknown Compare operation {op!r}")
+        if isinstance(other, DeviceCSC):
+            return self._logical_result(lambda *a: _lib().svt_dev_compare_merge(self.handle, other.handle, COMPARE_OPCODES[op], *a))
+        s_Rtype = (LGLSXP if isinstance(other, (bool, np.bool_)) else
+                   INTSXP if isinstance(other, (int, np.integer)) else REALSXP)
+        return self._logical_result(lambda *a: _lib().svt_dev_compare_map(self.handle, COMPARE_OPCODES[op], float(other),
+                                                                          s_Rtype, *a))
+
+    def logic(self, op: str, other: "DeviceCSC") -> "DeviceCSC":
+        """``self & other`` / ``self | other`` on the device for two logical operands (svt_dev_logic_merge)."""
+        from .api import LOGIC_OPCODES
+        if op not in LOGIC_OPCODES:
+            raise SparseArrayError(f"unknown Logic operation {op!r}")
+        if not isinstance(other, DeviceCSC):
+            raise SparseArrayError("logic() takes two DeviceCSC operands")
+        return self._logical_result(lambda *a: _lib().svt_dev_logic_merge(self.handle, other.handle, LOGIC_OPCODES[op], *a))
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
