@@ -1033,6 +1033,70 @@ int svt_Compare_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_
 int svt_Compare_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res, int64_t *out_nnz);
 int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int64_t *out_nnz);
 
+/* abind(), cbind() and rbind() of SVT operands (C_abind_SVT_SparseArray_objects, src/SparseArray_abind.c;
+   R/SparseArray-abind.R, R/NaArray-abind.R): nobj >= 1 objects bound along dimension `along` (1-based) into a new
+   operand in the device layout, leaves x rows with the outermost dimension slowest.  A pure copy (kernels_abind.hip).
+
+     along the rows (along == 1; concatenate_leaves, :129-181)  every object has the same number of leaves; result leaf L
+            is leaf L of object 0, then of object 1, ...; the rows of object n are shifted by off[n] = the nrow of the
+            objects before it, so rows stay ascending; the result's nrow is the sum, at most 2^31 - 1.
+     along a leaf dimension (along >= 2; concatenate_SVTs and the recursion, :94-125, 186-230)  every object has the same
+            nrow.  inner = prod(dim[1 .. along-2]), ext[n] = object n's extent along the binding dimension, start[n] = the
+            ext of the objects before it, D = their sum, outer = the product of the dimensions after it (the same for
+            every object: ncol_n == inner * ext[n] * outer).  Result leaf q = a + inner * (j + D * c) is leaf
+            a + inner * ((j - start[n]) + ext[n] * c) of the object n whose [start[n], start[n] + ext[n]) holds j.
+            cbind of matrices is inner == outer == 1; a new trailing dimension is ext[n] == 1 with outer == 1.
+
+   In both forms an entry is stored in the result exactly when its source entry is stored (a stored zero stays
+   stored), in the source's order.  ans_Rtype, the result's type, is at least the widest of logical < integer < double
+   over the objects (the R method coerces every object to it before the call; here the copy widens): a value whose
+   object has the result's type is copied bit for bit, logical -> integer leaves the bits as they are, integer or
+   logical -> double converts the value and NA_integer_ becomes NA_real_.  NaArray operands (na_background) are taken
+   when ALL objects have it, and the result has it.  Allowed, and never a launch over an empty range: nobj == 1 (a copy
+   that may widen), objects without nonzeros, objects of extent 0 along the binding dimension, a result without leaves.
+   Not offered: COO objects, binding with a dense array, deparse.level, sharding over the device list, an entry in the
+   R glue (integration/svt_hip_glue.c binds neither this nor subset nor Arith; INTEGRATION.md describes the call).
+
+   Device level.  `objs`: a host array of nobj handles.  `ext`: a host array of the nobj extents along the binding
+   dimension, or NULL for the rows form (`inner` is then not read).  The result is cut into pieces, each a whole leaf
+   of one object (out_nleaves * nobj of them in the rows form, out_nleaves else); svt_dev_abind_count writes
+   out_col_ptr int64[out_nleaves + 1] and *out_nnz and synchronises `stream` once; svt_dev_abind_fill is asynchronous,
+   takes the same operands, reads the workspace as the count call left it and writes out_row_idx int32[*out_nnz] and
+   out_val (ans_Rtype) in tiles of svt_dev_abind_tile() result entries; two runs give the same bits.  Status < 0,
+   answered on the host before anything is launched or written: nobj < 1, a NULL object, an ans_Rtype that is not
+   logical / integer / double or is narrower than an object's type, objects with and without na_background, leaf
+   counts that differ (rows form), nrow that differ or an ncol_n that is not inner * ext[n] * outer for one outer (leaf
+   form), rows that sum past 2^31 - 1, more than 2^31 - 2 pieces, a workspace below svt_dev_abind_ws_bytes(nobj,
+   out_nleaves, rows_form).  Also < 0, found by the count kernels: an object whose col_ptr descends or passes its nnz
+   (nothing is read through it).  On a non-zero status nothing is written outside `ws`: out_col_ptr and *out_nnz keep
+   their contents.  Alignment and workspace: "Workspaces" above. */
+int svt_dev_abind_tile(void);
+size_t svt_dev_abind_ws_bytes(int nobj, int64_t out_nleaves, int rows_form);
+int svt_dev_abind_count(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype,
+			int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_abind_fill(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype,
+		       const int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes,
+		       void *stream);
+/* The composition count -> allocate -> fill over the allocator of svt_dev_subset(): the workspace comes from `alloc`
+   and goes back through `release`; *out_nrow and *out_nleaves are the result's extents, its type is ans_Rtype, and the
+   three result arrays (*out_col_ptr int64[*out_nleaves + 1]; *out_row_idx, *out_val of at least one element) are the
+   caller's to release.  Synchronises `stream` once (not at all for a result without leaves); the fill is still queued
+   on return. */
+int svt_dev_abind(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype,
+		  svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nrow, int64_t *out_nleaves,
+		  int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream);
+
+/* Host level.  `objs`: nobj views of the same number of dimensions.  begin checks `along` and the dims on the host, with
+   the messages of the C entry point ("'along' must be >= 1 and <= the number of dimensions of the objects to bind",
+   "all the objects to bind must have the same number of dimensions") and, for extents that differ off the binding
+   dimension, "all the objects to bind must have the same extent along dimension <k> (they are bound along dimension
+   <along>)"; uploads the objects (through the resident cache when it is on), runs svt_dev_abind on the first device of
+   the list (not sharded) and leaves the result on the device: *out_nnz is its nonzero count, its type is ans_Rtype,
+   its dims are those of the objects with the extents summed along `along`.  The existing svt_Arith_SVT_end copies it
+   into out_col_ptr int64[nleaves + 1], out_row_idx int32[nnz], out_val and releases it. */
+int svt_abind_SVT_begin(const svt_view *const *objs, int nobj, int along, int ans_Rtype, svt_arith_result **res,
+			int64_t *out_nnz);
+
 #ifdef __cplusplus
 }
 #endif

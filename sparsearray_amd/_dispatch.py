@@ -423,6 +423,31 @@ class CAbiDispatcher:
         return self._logical_result("Logic_SVT_SVT_begin", x, (y, LOGIC_OPCODES[op]),
                                     x.dimnames if x.dimnames is not None else y.dimnames)
 
+    # abind / cbind / rbind (src/SparseArray_abind.c; include/svt_hip.h; HIP library only): begin leaves the result on the
+    # device, Arith_SVT_end copies it out ---------------------------------------------------------------------------
+    def C_abind_SVT_SparseArray_objects(self, objects, along: int, ans_type: str):
+        """The SVT_SparseArray (dim, type ``ans_type``, leaves; no dimnames) of ``objects`` bound along dimension
+        ``along`` (1-based).  The objects go over with their own types, the library widens on the device; NaArray
+        objects give an NaArray."""
+        objects = list(objects)
+        if not objects:
+            raise SparseArrayError("'objects' cannot be an empty list")
+        if ans_type not in _RT:
+            raise SparseArrayError("invalid requested type")
+        views = [make_view(x) for x in objects]
+        table = (ctypes.POINTER(svt_view) * len(views))(*[ctypes.pointer(v) for v in views])
+        res, nnz = c_void_p(0), ctypes.c_int64(0)
+        self._run("abind_SVT_begin", table, len(views), int(along), _RT[ans_type], byref(res), byref(nnz))
+        n, x = int(nnz.value), objects[0]
+        new_dim = tuple(sum(o.dim[k] for o in objects) if k == along - 1 else d for k, d in enumerate(x.dim))
+        cp = np.zeros(int(np.prod(new_dim[1:], dtype=np.int64)) + 1, dtype=np.int64)
+        ri = np.zeros(max(n, 1), dtype=np.int32)
+        vv = np.zeros(max(n, 1), dtype=np.float64 if ans_type == "double" else np.int32)
+        self._run("Arith_SVT_end", res, cp, ri, vv)
+        ans = SVT_SparseArray.from_csc(new_dim, ans_type, cp, ri[:n], vv[:n])
+        ans.na_background = x.na_background
+        return ans
+
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""
         return self._dgc("rowsum_dgCMatrix", x, group, ngroup, na_rm,

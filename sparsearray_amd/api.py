@@ -13,6 +13,7 @@ as ``src/R_init_SparseArray.c:94,121-134``:
     C_transpose_2D_SVT    C_aperm_SVT           C_subset_SVT_by_Nindex (2-D operands)
     C_Arith_SVT1_SVT2     C_Arith_SVT1_v2       C_unary_minus_SVT      C_Math_SVT (HIP library only)
     C_Compare_SVT1_v2     C_Compare_SVT1_SVT2   C_Logic_SVT1_SVT2      (HIP library only)
+    C_abind_SVT_SparseArray_objects                                      (HIP library only)
 
 and the entry points the HIP library adds to them (include/svt_hip.h):
 
@@ -614,6 +615,90 @@ class Session:
             raise SparseArrayError("incorrect number of subscripts")
         index = [self._check_Nindex(s, d) for s, d in zip(index, x.dim)]
         return self.SparseArray_Call("C_subset_SVT_by_Nindex", x, *index)
+
+    # ------------------------------------------------------------------
+    # abind, cbind, rbind  (.abind_SparseArray_objects, R/SparseArray-abind.R:53-99)
+    # ------------------------------------------------------------------
+    @staticmethod
+    def _add_missing_dims(x, ndim):
+        """``x`` with trailing extents of 1 up to ``ndim`` dimensions (the leaves are the same: one more leaf level of
+        extent 1 is the same flat list)."""
+        if x.ndim == ndim:
+            return x
+        dn = None if x.dimnames is None else list(x.dimnames) + [None] * (ndim - x.ndim)
+        return SVT_SparseArray(x.dim + (1,) * (ndim - x.ndim), x.type, x.leaves, dimnames=dn, svt_is_null=x.svt_is_null,
+                               na_background=x.na_background)
+
+    @staticmethod
+    def _combine_dimnames_along(objects, along):
+        """Off the binding dimension the first non-NULL names; along it NULL when no object has names there, otherwise
+        the concatenation, with "" for every position of an object that has none."""
+        ndim = objects[0].ndim
+        names = lambda x, k: None if x.dimnames is None else x.dimnames[k]      # noqa: E731
+        ans = []
+        for k in range(ndim):
+            if k != along - 1:
+                ans.append(next((names(x, k) for x in objects if names(x, k) is not None), None))
+            elif all(names(x, k) is None for x in objects):
+                ans.append(None)
+            else:
+                ans.append([s for x in objects for s in (list(names(x, k)) if names(x, k) is not None else [""] * x.dim[k])])
+        return None if all(n is None for n in ans) else ans
+
+    def abind(self, *objects, along=None, rev_along=None):
+        """``abind(..., along=, rev.along=)`` of SVT_SparseArray objects (1-based ``along``).  ``None`` objects are
+        dropped; no object gives ``None``; one object is returned as it is.  ``along`` defaults to the largest number of
+        dimensions N and may be N + 1 (a new dimension); ``rev_along = r`` means ``along = N + 1 - r``.  Objects of
+        fewer dimensions get trailing extents of 1.  The result's type is the widest of logical < integer < double.
+        All objects NaArrays gives an NaArray.  Not offered: COO objects, dense arrays among the objects,
+        ``deparse.level``."""
+        objects = [x for x in objects if x is not None]
+        if not objects:
+            return None
+        if any(isinstance(x, np.ndarray) for x in objects):
+            raise SparseArrayUnsupported("binding a SparseArray object with a dense array is not offered by this library")
+        if not all(isinstance(x, SVT_SparseArray) for x in objects):
+            raise SparseArrayError("abind() takes SVT_SparseArray objects")
+        N = max(x.ndim for x in objects)
+        for name, v in (("along", along), ("rev.along", rev_along)):
+            if v is not None and (isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer))):
+                raise SparseArrayError(f"'{name}' must be a single integer")
+        if along is not None and rev_along is not None:
+            raise SparseArrayError("only one of 'along' and 'rev.along' can be given")
+        if rev_along is not None:
+            if rev_along < 0:
+                raise SparseArrayError("'rev.along' must be >= 0")
+            along = N + 1 - int(rev_along)
+        along = N if along is None else int(along)
+        if along < 1 or along > N + 1:
+            raise SparseArrayError("'along' must be >= 1 and <= the largest number of dimensions of the objects to bind "
+                                   "plus 1")
+        ans_ndim = max(N, along)
+        objects = [self._add_missing_dims(x, ans_ndim) for x in objects]
+        x = objects[0]
+        for k in range(ans_ndim):                          # get_dims_to_bind
+            if k != along - 1 and any(y.dim[k] != x.dim[k] for y in objects):
+                raise SparseArrayError(f"all the objects to bind must have the same extent along dimension {k + 1} (they "
+                                       f"are bound along dimension {along})")
+        if len({y.na_background for y in objects}) != 1:
+            raise SparseArrayError("NaArray objects and ordinary SparseArray objects cannot be bound together")
+        if len(objects) == 1:
+            return x
+        ans_dimnames = self._combine_dimnames_along(objects, along)
+        # abind_SVT_SparseArray_objects (:36-51): the type of the objects' types combined; the library widens
+        ans_type = max((y.type for y in objects), key=("logical", "integer", "double").index)
+        self._optional_entry("C_abind_SVT_SparseArray_objects", "abind_SVT_begin")
+        ans = self.SparseArray_Call("C_abind_SVT_SparseArray_objects", objects, along, ans_type)
+        ans.dimnames = ans_dimnames
+        return ans
+
+    def rbind(self, *objects):
+        """``rbind(...)`` = ``arbind``: abind along the rows; ``deparse.level`` is not offered."""
+        return self.abind(*objects, along=1)
+
+    def cbind(self, *objects):
+        """``cbind(...)`` = ``acbind``: abind along the columns; ``deparse.level`` is not offered."""
+        return self.abind(*objects, along=2)
 
     # ------------------------------------------------------------------
     # Arith, unary minus, Math  (R/SparseArray-Arith-methods.R, R/SparseArray-Math-methods.R)

@@ -19,40 +19,18 @@
 // 16 KB of LDS (one int per entry) leave room for 8 workgroups per CU.
 #include "svt_common.h"
 #include "svt_scan.h"
+#include "svt_tile.h"
 
 #include <type_traits>
 
-#define SUB_NT 256
-#define SUB_ITEMS 16
-#define SUB_TILE (SUB_NT * SUB_ITEMS)
-#define SUB_CHUNKS (SUB_TILE / SVT_WAVE)
-#define SUB_SHIFT 12
+#define SUB_NT SVT_TILE_NT
+#define SUB_ITEMS SVT_TILE_ITEMS
+#define SUB_TILE SVT_TILE
+#define SUB_CHUNKS SVT_TILE_CHUNKS
+#define SUB_SHIFT SVT_TILE_SHIFT
 #define SUB_GATHER_GRID 2048            // the gather's grid: its tile count is known on the device only (out_col_ptr)
-static_assert(SUB_TILE == 1 << SUB_SHIFT && SUB_CHUNKS == SVT_WAVE, "one wavefront scans the chunk table of a tile");
 
 enum { SUB_BAD_INDEX = 1, SUB_NOT_INCREASING = 2 };
-
-// the last q in [0, n] with ptr[q] <= x (ptr[0 .. n] ascending, ptr[0] = 0 <= x): for x < ptr[n] the column that holds
-// entry x -- a non-empty one, the empty columns that start at the same place come before it
-__device__ inline int64_t sub_last_le(const int64_t *ptr, int64_t n, int64_t x)
-{
-	int64_t lo = 0, hi = n + 1;
-	while (hi - lo > 1) {
-		const int64_t mid = lo + (hi - lo) / 2;
-		if (ptr[mid] <= x) lo = mid; else hi = mid;
-	}
-	return lo;
-}
-// the first q in [0, n] with ptr[q] >= x (x <= ptr[n])
-__device__ inline int64_t sub_first_ge(const int64_t *ptr, int64_t n, int64_t x)
-{
-	int64_t lo = -1, hi = n;
-	while (hi - lo > 1) {
-		const int64_t mid = lo + (hi - lo) / 2;
-		if (ptr[mid] >= x) hi = mid; else lo = mid;
-	}
-	return hi;
-}
 
 // ---------------------------------------------------------------------------
 // column gather
@@ -84,7 +62,7 @@ __global__ __launch_bounds__(SUB_NT) void subset_cols_publish_kernel(const int64
 
 // One tile of SUB_TILE output entries per trip.  seg[i]: for the first entry of every column that starts inside the
 // tile, the column (relative to q0, the column of the tile's first entry); an inclusive max-scan spreads it over the
-// column's entries: per wavefront chunk with shuffles, then over the 64 chunk maxima by the first wavefront.
+// column's entries (svt_tile_max_scan, svt_tile.h).
 template <typename T>
 __global__ __launch_bounds__(SUB_NT) void subset_cols_copy_kernel(const int64_t *col_ptr, const int32_t *row_idx, const T *val,
 								   int64_t ncol, int64_t nnz, const int32_t *cols, int64_t ncols_sel,
@@ -93,7 +71,7 @@ __global__ __launch_bounds__(SUB_NT) void subset_cols_copy_kernel(const int64_t 
 	__shared__ int seg[SUB_TILE];
 	__shared__ int cmax[SUB_CHUNKS];
 	__shared__ int64_t qq[2];
-	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const int tid = threadIdx.x, w = tid >> 6;
 	const int64_t total = ocp[ncols_sel];
 	for (int64_t ts = (int64_t) blockIdx.x << SUB_SHIFT; ts < total; ts += (int64_t) gridDim.x << SUB_SHIFT) {
 		const int n = (int) (total - ts < SUB_TILE ? total - ts : SUB_TILE);
@@ -110,27 +88,7 @@ __global__ __launch_bounds__(SUB_NT) void subset_cols_copy_kernel(const int64_t 
 		}
 		__syncthreads();
 		int v[SUB_ITEMS];
-#pragma unroll
-		for (int it = 0; it < SUB_ITEMS; it++) {
-			int x = seg[it * SUB_NT + tid];
-			for (int o = 1; o < SVT_WAVE; o <<= 1) {
-				const int t = __shfl_up(x, o, SVT_WAVE);
-				if (lane >= o && t > x) x = t;
-			}
-			v[it] = x;
-			if (lane == SVT_WAVE - 1) cmax[it * (SUB_NT / SVT_WAVE) + w] = x;
-		}
-		__syncthreads();
-		if (tid < SVT_WAVE) {                      // exclusive max-scan of the chunk maxima, in place
-			int x = cmax[tid];
-			for (int o = 1; o < SVT_WAVE; o <<= 1) {
-				const int t = __shfl_up(x, o, SVT_WAVE);
-				if (lane >= o && t > x) x = t;
-			}
-			const int e = __shfl_up(x, 1, SVT_WAVE);
-			cmax[tid] = lane == 0 ? 0 : e;
-		}
-		__syncthreads();
+		svt_tile_max_scan(seg, cmax, v);
 #pragma unroll
 		for (int it = 0; it < SUB_ITEMS; it++) {
 			const int i = it * SUB_NT + tid;

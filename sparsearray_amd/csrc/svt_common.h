@@ -302,6 +302,38 @@ int launch_arith_map_fill(const ArithMapArgs &a, int32_t *out_row_idx, void *out
 int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
 int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
 
+// abind (kernels_abind.hip): the result as a sequence of pieces, each a whole leaf of one object.  The count launcher
+// copies the table of objects into `ws` (one asynchronous copy: the table must live until the stream has passed it) and
+// leaves out_col_ptr and, in the head of `ws`, [int: 1 an object's pointers do not ascend inside its nnz][int64 at byte
+// 8: the nonzeros of the result]; with the flag up nothing is written outside `ws`.  The fill launcher reads `ws` as
+// the count launcher left it.  Both asynchronous.
+struct AbindObj {               // one object, in the layout the count kernels read
+	const int64_t *col_ptr;
+	const int32_t *row_idx;
+	const void *val;
+	int64_t nnz;
+	int64_t nleaves;
+	int64_t shift;          // along the rows: off[n], the rows of the objects before; along a leaf dim: start[n]
+	int64_t ext;            // along a leaf dim: the extent along the binding dimension
+	int32_t Rtype;
+	int32_t pad;
+};
+struct AbindArgs {
+	const AbindObj *objs;   // host
+	int nobj;
+	int rows_form;
+	int64_t inner, D;       // along a leaf dim: prod of the dims between the rows and the binding one, sum of ext[]
+	int64_t npieces;        // rows: out_nleaves * nobj; leaf dim: out_nleaves
+	int64_t out_nleaves;
+	int64_t max_nnz;        // sum of the objects' nnz: the result's nonzeros (the copy's grid is sized from it)
+	int ans_Rtype;
+	int uniform;            // every object has the result's element size and needs no conversion
+};
+int abind_tile(void);
+size_t abind_ws_bytes(int nobj, int64_t npieces);
+int launch_abind_count(const AbindArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_abind_fill(const AbindArgs &a, int32_t *out_row_idx, void *out_val, const void *ws, hipStream_t s);
+
 void aperm_route_counts(int64_t *out, int reset);
 size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim);
 // aperm, with the boxed driver for the permutations that move the rows past the box limit (read once per call and

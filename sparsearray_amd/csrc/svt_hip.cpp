@@ -19,6 +19,7 @@
 #include <atomic>
 #include <chrono>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <optional>
 #include <thread>
@@ -1783,6 +1784,203 @@ extern "C" int svt_dev_logic_merge(const svt_dev_csc *x, const svt_dev_csc *y, i
 	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 
+// ---- abind / cbind / rbind (kernels_abind.hip; C_abind_SVT_SparseArray_objects, src/SparseArray_abind.c) ----
+extern "C" int svt_dev_abind_tile(void)
+{
+	return abind_tile();
+}
+extern "C" size_t svt_dev_abind_ws_bytes(int nobj, int64_t out_nleaves, int rows_form)
+{
+	if (nobj < 0) nobj = 0;
+	if (out_nleaves < 0) out_nleaves = 0;
+	return abind_ws_bytes(nobj, rows_form ? out_nleaves * nobj : out_nleaves);
+}
+
+static inline int abind_type_rank(int Rtype)
+{
+	return Rtype == SVT_LGLSXP ? 0 : Rtype == SVT_INTSXP ? 1 : Rtype == SVT_REALSXP ? 2 : -1;
+}
+
+// One call: every check that needs no GPU, the result's extents and the table of objects the count kernels read.
+struct AbindCall {
+	const char *who;
+	std::vector<AbindObj> table;
+	AbindArgs a;
+	int64_t out_nrow = 0;
+	int na_background = 0;
+
+	int plan(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype)
+	{
+		memset(&a, 0, sizeof(a));
+		if (nobj < 1 || objs == NULL)
+			return svt_set_error("%s: at least one object is needed", who);
+		for (int n = 0; n < nobj; n++)
+			if (objs[n] == NULL)
+				return svt_set_error("%s: object %d is NULL", who, n + 1);
+		if (abind_type_rank(ans_Rtype) < 0)
+			return svt_set_error("invalid requested type");
+		a.uniform = 1;
+		for (int n = 0; n < nobj; n++) {
+			const int r = abind_type_rank(objs[n]->Rtype);
+			if (r < 0)
+				return svt_set_error("%s: object %d has a type that is not logical, integer or double", who, n + 1);
+			if (r > abind_type_rank(ans_Rtype))
+				return svt_set_error("%s: the requested type is narrower than the type of object %d", who, n + 1);
+			if (elt_size(objs[n]->Rtype) != elt_size(ans_Rtype)) a.uniform = 0;
+			if ((objs[n]->na_background != 0) != (objs[0]->na_background != 0))
+				return svt_set_error("%s: NaArray objects and ordinary objects cannot be bound together", who);
+			if (objs[n]->nrow < 0 || objs[n]->ncol < 0 || objs[n]->nnz < 0)
+				return svt_set_error("%s: object %d has a negative extent", who, n + 1);
+		}
+		na_background = objs[0]->na_background != 0;
+		a.nobj = nobj;
+		a.rows_form = ext == NULL;
+		a.ans_Rtype = ans_Rtype;
+		table.resize((size_t) nobj);
+		int64_t run = 0;                                    // off[n] / start[n]
+		if (a.rows_form) {
+			for (int n = 0; n < nobj; n++) {
+				if (objs[n]->ncol != objs[0]->ncol)
+					return svt_set_error("%s: object %d has %lld leaves, object 1 has %lld", who, n + 1,
+							     (long long) objs[n]->ncol, (long long) objs[0]->ncol);
+				table[(size_t) n].shift = run;
+				run += objs[n]->nrow;
+				if (run > 0x7FFFFFFFLL)
+					return svt_set_error("%s: the rows of the objects sum past 2^31 - 1", who);
+			}
+			out_nrow = run;
+			a.out_nleaves = objs[0]->ncol;
+			if (a.out_nleaves > 0x7FFFFFFELL / nobj)
+				return svt_set_error("%s: more than 2^31 - 2 pieces", who);
+			a.npieces = a.out_nleaves * nobj;
+		} else {
+			if (inner < 0)
+				return svt_set_error("%s: 'inner' must be >= 0", who);
+			int64_t outer = -1;
+			for (int n = 0; n < nobj; n++) {
+				if (ext[n] < 0)
+					return svt_set_error("%s: object %d has a negative extent", who, n + 1);
+				if (objs[n]->nrow != objs[0]->nrow)
+					return svt_set_error("%s: object %d has %lld rows, object 1 has %lld", who, n + 1,
+							     (long long) objs[n]->nrow, (long long) objs[0]->nrow);
+				const int64_t slab = inner * ext[n];        // (svt_dev_csc counts leaves in int64; ext and inner come from int dims)
+				if (slab == 0 ? objs[n]->ncol != 0 : objs[n]->ncol % slab != 0)
+					return svt_set_error("%s: the leaves of object %d are not inner * ext * outer", who, n + 1);
+				if (slab != 0) {
+					if (outer < 0) outer = objs[n]->ncol / slab;
+					if (objs[n]->ncol / slab != outer)
+						return svt_set_error("%s: the leaves of object %d are not inner * ext * outer for the outer of "
+								     "the objects before it", who, n + 1);
+				}
+				table[(size_t) n].shift = run;
+				table[(size_t) n].ext = ext[n];
+				run += ext[n];
+			}
+			out_nrow = objs[0]->nrow;
+			a.inner = inner;
+			a.D = run;
+			a.out_nleaves = outer > 0 ? inner * run * outer : 0;
+			if (a.out_nleaves > 0x7FFFFFFELL)
+				return svt_set_error("%s: more than 2^31 - 2 pieces", who);
+			a.npieces = a.out_nleaves;
+		}
+		for (int n = 0; n < nobj; n++) {
+			AbindObj &o = table[(size_t) n];
+			o.col_ptr = objs[n]->col_ptr; o.row_idx = objs[n]->row_idx; o.val = objs[n]->val;
+			o.nnz = objs[n]->nnz; o.nleaves = objs[n]->ncol; o.Rtype = objs[n]->Rtype; o.pad = 0;
+			a.max_nnz += objs[n]->nnz;
+		}
+		a.objs = table.data();
+		return 0;
+	}
+	size_t need() const { return abind_ws_bytes(a.nobj, a.npieces); }
+
+	int count(int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		hipStream_t st = (hipStream_t) stream;
+		if (a.npieces == 0) {                               // a result without leaves: nothing to count
+			HIP_TRY(hipMemsetAsync(out_col_ptr, 0, 8, st));
+			*out_nnz = 0;
+			return 0;
+		}
+		if (launch_abind_count(a, out_col_ptr, ws, st))
+			return -1;
+		int flag = 0;
+		int64_t total = 0;
+		if (subset_read_head(ws, st, &flag, &total))        // (the table of objects has been copied by now)
+			return -1;
+		if (flag)
+			return svt_set_error("%s: the column pointers of an object descend or pass its nonzeros", who);
+		*out_nnz = total;
+		return 0;
+	}
+	int fill(int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		return launch_abind_fill(a, out_row_idx, out_val, ws, (hipStream_t) stream);
+	}
+	// count -> allocate -> fill over the caller's allocator
+	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+		    int32_t **out_row_idx, void **out_val, void *stream)
+	{
+		if (alloc == NULL || release == NULL)
+			return svt_set_error("%s: an allocator is needed", who);
+		SubsetMem mem = { alloc, release, ctx };
+		SubsetCsc R(mem);
+		SubsetWs ws(mem);
+		int64_t nnz = 0;
+		svt_dev_csc like;
+		memset(&like, 0, sizeof(like));
+		like.Rtype = a.ans_Rtype; like.na_background = na_background;
+		if (R.shape(&like, out_nrow, a.out_nleaves) || ws.get(need()))
+			return -1;
+		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, stream) || R.entries(nnz) || fill(R.c.row_idx, R.c.val, ws.p, ws.n, stream))
+			return -1;
+		*out_nnz = nnz;
+		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
+		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
+		return 0;
+	}
+};
+
+extern "C" int svt_dev_abind_count(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype,
+				   int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		AbindCall c = { "svt_dev_abind_count" };
+		if (c.plan(objs, nobj, inner, ext, ans_Rtype)) return -1;
+		return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_abind_fill(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype,
+				  const int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val, const void *ws,
+				  size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the piece starts in `ws` place the entries)
+	return abi_status([&] {
+		AbindCall c = { "svt_dev_abind_fill" };
+		if (c.plan(objs, nobj, inner, ext, ans_Rtype)) return -1;
+		return c.fill(out_row_idx, out_val, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_abind(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype,
+			     svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nrow, int64_t *out_nleaves,
+			     int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+{
+	return abi_status([&] {
+		AbindCall c = { "svt_dev_abind" };
+		if (c.plan(objs, nobj, inner, ext, ans_Rtype) ||
+		    c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream))
+			return -1;
+		*out_nrow = c.out_nrow;
+		*out_nleaves = c.a.out_nleaves;
+		return 0;
+	});
+}
+
 // A %*% B, both sparse (kernels_spmm.hip): out[r + k * ldo], r < A->nrow, k < B->ncol.
 extern "C" size_t svt_dev_matmul_csc_csc_ws_bytes(const svt_dev_csc *A)
 {
@@ -3170,6 +3368,70 @@ extern "C" int svt_Compare_SVT_scalar_begin(const svt_view *x, int op, double s,
 extern "C" int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int64_t *out_nnz)
 {
 	return compare_begin("svt_Logic_SVT_SVT_begin", ARI_RULE_LOGIC, op, x, y, true, 0.0, 0, res, out_nnz);
+}
+// abind on host operands (C_abind_SVT_SparseArray_objects): `along` and the dims are checked here, before anything is
+// uploaded; the objects go up through the resident cache, AbindCall::compose() runs on the first device, the result
+// stays there until svt_Arith_SVT_end.
+static int abind_SVT_begin_impl(const svt_view *const *objs, int nobj, int along, int ans_Rtype, svt_arith_result **res,
+				int64_t *out_nnz)
+{
+	const char *who = "svt_abind_SVT_begin";
+	if (res == NULL || out_nnz == NULL)
+		return svt_set_error("%s: 'res' and 'out_nnz' are needed", who);
+	*res = NULL;
+	if (nobj < 1 || objs == NULL)
+		return svt_set_error("'objects' cannot be an empty list");
+	if (ensure_init())
+		return -1;
+	for (int n = 0; n < nobj; n++)
+		if (check_view(objs[n]))
+			return -1;
+	const int ndim = objs[0]->ndim;
+	if (along < 1 || along > ndim)
+		return svt_set_error("'along' must be >= 1 and <= the number of dimensions of the objects to bind");
+	for (int n = 1; n < nobj; n++) {
+		if (objs[n]->ndim != ndim)
+			return svt_set_error("all the objects to bind must have the same number of dimensions");
+		for (int k = 0; k < ndim; k++)
+			if (k != along - 1 && objs[n]->dim[k] != objs[0]->dim[k])
+				return svt_set_error("all the objects to bind must have the same extent along dimension %d (they are "
+						     "bound along dimension %d)", k + 1, along);
+	}
+	int64_t inner = 1;
+	for (int k = 1; k < along - 1; k++) inner *= objs[0]->dim[k];
+	std::vector<int64_t> ext((size_t) nobj);
+	for (int n = 0; n < nobj; n++) ext[(size_t) n] = objs[n]->dim[along - 1];
+	std::vector<std::unique_ptr<CscGuard>> up;
+	std::vector<const svt_dev_csc *> handles;
+	for (int n = 0; n < nobj; n++) {
+		up.emplace_back(new CscGuard(objs[n]));
+		if (up.back()->h == NULL) return -1;
+		handles.push_back(up.back()->h);
+	}
+	AbindCall c = { who };
+	if (c.plan(handles.data(), nobj, inner, along == 1 ? NULL : ext.data(), ans_Rtype))
+		return -1;
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->owned = 1; h->Rtype = ans_Rtype; h->na_background = c.na_background;
+	h->nrow = c.out_nrow; h->ncol = c.a.out_nleaves;
+	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, NULL) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
+		svt_release(h);
+		return -1;
+	}
+	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
+	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
+	r->h = h;
+	*res = r;
+	*out_nnz = h->nnz;
+	return 0;
+}
+extern "C" int svt_abind_SVT_begin(const svt_view *const *objs, int nobj, int along, int ans_Rtype, svt_arith_result **res,
+				   int64_t *out_nnz)
+{
+	return abi_status([&] { return abind_SVT_begin_impl(objs, nobj, along, ans_Rtype, res, out_nnz); });
 }
 extern "C" int svt_Arith_SVT_end(svt_arith_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
 {

@@ -304,6 +304,68 @@ def subset_rows(A: DeviceCSC, rows, ws=None) -> DeviceCSC:
     return _subset_two_calls(A, rows, ws, rows=True)
 
 
+def abind_tile() -> int:
+    """Result entries per workgroup tile of the copy of abind (svt_dev_abind_tile).  Needs no GPU."""
+    return int(_hip.load_library().svt_dev_abind_tile())
+
+
+def _abind_operands(objects, along, dim):
+    """(handle array, inner, ext array or None, ans_Rtype, result dim) of abind(objects, along, dim): the dims are
+    checked here, the way svt_abind_SVT_begin checks those of host operands."""
+    objects = list(objects)
+    if not objects or not all(isinstance(o, DeviceCSC) for o in objects):
+        raise SparseArrayError("abind() takes one or more DeviceCSC operands")
+    dims = [(o.nrow, o.ncol) for o in objects] if dim is None else [tuple(int(d) for d in dd) for dd in dim]
+    if len(dims) != len(objects):
+        raise SparseArrayError("'dim' must hold the dim of every object")
+    nd = len(dims[0])
+    if not 1 <= along <= nd:
+        raise SparseArrayError("'along' must be >= 1 and <= the number of dimensions of the objects to bind")
+    for o, dd in zip(objects, dims):
+        if len(dd) != nd:
+            raise SparseArrayError("all the objects to bind must have the same number of dimensions")
+        if dd[0] != o.nrow or int(np.prod(dd[1:], dtype=np.int64)) != o.ncol:
+            raise SparseArrayError("'dim' does not match the operand's rows and leaves")
+        for k in range(nd):
+            if k != along - 1 and dd[k] != dims[0][k]:
+                raise SparseArrayError(f"all the objects to bind must have the same extent along dimension {k + 1} (they "
+                                       f"are bound along dimension {along})")
+    new_dim = tuple(sum(dd[k] for dd in dims) if k == along - 1 else d for k, d in enumerate(dims[0]))
+    handles = (c_void_p * len(objects))(*[o._h for o in objects])
+    ext = None if along == 1 else (c_int64 * len(objects))(*[dd[along - 1] for dd in dims])
+    inner = int(np.prod(dims[0][1:along - 1], dtype=np.int64)) if along > 2 else 1
+    ans_Rtype = max((o.Rtype for o in objects), key=(LGLSXP, INTSXP, REALSXP).index)
+    return objects, handles, inner, ext, ans_Rtype, new_dim
+
+
+def abind(objects, along=1, dim=None):
+    """abind() of resident operands along dimension ``along`` (1-based; include/svt_hip.h, svt_dev_abind).  ``dim``:
+    the dim of every object, one tuple each, for N-d operands (dim[0] == nrow, prod(dim[1:]) == ncol); None: every
+    object is the 2-D (nrow, ncol).  The result's type is the widest of logical < integer < double over the objects
+    (logical only when every object is logical) and the values widen on the device.  Returns (DeviceCSC, its dim); every
+    array is a torch allocation on the current stream."""
+    objects, handles, inner, ext, ans_Rtype, new_dim = _abind_operands(objects, int(along), dim)
+    mem = _TorchBlocks(objects[0].val.device)
+    nrow, nleaves, nnz = c_int64(0), c_int64(0), c_int64(0)
+    out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+    _check(_lib().svt_dev_abind(handles, len(objects), inner, ext, ans_Rtype, mem.alloc_fn, mem.free_fn, None,
+                                ctypes.byref(nrow), ctypes.byref(nleaves), ctypes.byref(nnz),
+                                *[ctypes.byref(o) for o in out], _stream()))
+    dtype = torch.float64 if ans_Rtype == REALSXP else torch.int32
+    R = DeviceCSC(int(nrow.value), *mem.csc(out, int(nleaves.value), int(nnz.value), dtype), logical=ans_Rtype == LGLSXP)
+    return R, new_dim
+
+
+def cbind(*objects) -> DeviceCSC:
+    """cbind() of resident 2-D operands of the same nrow: their columns one object after the other."""
+    return abind(objects, along=2)[0]
+
+
+def rbind(*objects) -> DeviceCSC:
+    """rbind() of resident 2-D operands of the same ncol: in every column their rows one object after the other."""
+    return abind(objects, along=1)[0]
+
+
 class CrossprodPlan:
     """Reusable workspace for crossprod(A, Y) with K dense columns."""
 
