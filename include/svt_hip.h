@@ -838,7 +838,8 @@ int svt_transpose_2D_SVT(const svt_view *x, int64_t *out_col_ptr,
 /* x[i, j] of a 2-D operand by an N-index (C_subset_SVT_by_Nindex, src/SparseArray_subsetting.c:223-297, 759-843):
    result cell (p, q) is x[i[p], j[q]]; indices in any order, any number of times; an entry is stored in the result
    exactly when its source entry is stored, and its value is copied bit for bit; offsets ascend inside every result
-   column; Rtype and na_background pass through.  Not offered: L-index / M-index subsetting, subassignment, N-d operands.
+   column; Rtype and na_background pass through.  Not offered: L-index / M-index subsetting, N-d operands.  (Subassignment
+   x[i, j] <- value: "Subassignment" at the end of this header.)
 
    Device level, two primitives over tiles of svt_dev_subset_tile() nonzeros (kernels_subset.hip), each a `_count`
    call that writes the result's column pointers and returns its nonzero count, and a `_fill` call into arrays the
@@ -1096,6 +1097,100 @@ int svt_dev_abind(const svt_dev_csc *const *objs, int nobj, int64_t inner, const
    into out_col_ptr int64[nleaves + 1], out_row_idx int32[nnz], out_val and releases it. */
 int svt_abind_SVT_begin(const svt_view *const *objs, int nobj, int along, int ans_Rtype, svt_arith_result **res,
 			int64_t *out_nnz);
+
+/* Subassignment x[i, j, ...] <- value by an N-index (.subassign_SVT_by_Nindex, R/SparseArray-subassignment.R:114-170;
+   C_subassign_SVT_with_short_Rvector, src/SparseArray_subassignment.c:1005-1230): the result is a new operand in the
+   device layout with x's extents.  Its type is the wider of x's and the value's, logical < integer < double; a value
+   of that type moves bit for bit, integer or logical -> double converts and NA_integer_ becomes NA_real_.  A leaf is
+   SELECTED when all its coordinates along dims 2..N are in the subscripts; a selected leaf is rebuilt from its dense
+   form, so an entry is stored in it exactly when the final value is not zero (-0.0 and integer 0 count as zero, a NaN
+   or NA does not, and a stored zero of x in it disappears even on a row outside i); every other leaf comes back
+   untouched, stored zeros included.  An empty selection is a copy of x in the result's type.
+
+     vector form  `vals`: nvals >= 1 values of v_Rtype.  The value of row subscript position p is vals[p % nvals], the
+                  same in every selected leaf; positions apply in order, so the last occurrence of a row wins; repeats
+                  among the leaves repeat the same assignment.  (The R method takes this form when length(value) <=
+                  length(i) and length(i) %% length(value) == 0; the library recycles whatever it is given.)
+     SVT form     `v`: an operand with the selection's extents (the reference's C_subassign_SVT_with_SVT is a stub).
+                  `rows` strictly increasing or the whole axis, `leaves` without repeats, in any order: leaf leaves[q]
+                  of the selection becomes leaf q of v with row r renamed rows[r].
+
+   On the device layout this is a merge (kernels_subassign.hip, kernels_arith.hip).  A PLACEMENT builds an operand Y
+   with x's extents that holds the new values which may have to be stored -- the non-zero values of the vector form,
+   every stored entry of v -- and two COVER TABLES, one byte per row and one per leaf, non-zero where the subscripts
+   reach.  The ASSIGN MERGE is one more rule on the merge kernels of Arith: at a place stored in Y the result is Y's
+   value; at a place stored in x alone it is dropped when its row and its leaf are both covered, x's value otherwise;
+   an entry is kept unless its leaf is covered and its value == 0.  So x[i, j] <- 0 builds an empty Y and costs one
+   pass over nnz(x), whatever the size of the selection.
+
+   Device level.  Subscripts are device arrays of 0-based int32, in any order and with repeats (vector form); a length
+   < 0 stands for the whole axis and the pointer is not read.  svt_dev_subassign_place_*_count writes y_col_ptr
+   int64[ncol + 1], cover_row uint8[nrow] and cover_leaf uint8[ncol] (a table may be NULL when its axis is whole: it is
+   then not written, and NULL is what the merge takes for "the whole axis"), returns *y_nnz and synchronises `stream`
+   once; svt_dev_subassign_place_*_fill is asynchronous, takes the same operands, reads the workspace as the count call
+   left it and writes y_row_idx int32[y_nnz] and y_val (the value's type) in tiles of svt_dev_subassign_tile() entries.
+   svt_dev_assign_merge_count / _fill follow svt_dev_arith_merge_count / _fill, with the workspace of
+   svt_dev_arith_merge_ws_bytes(ncol, x->nnz, y->nnz); the result's type is the wider of x's and y's and there is no
+   overflow word.  Every position is a 64-bit prefix sum and two runs give the same bits.  Status: < 0 for an index
+   outside [0, extent) (every index is checked before it is used as an address), a workspace below
+   svt_dev_subassign_place_ws_bytes(nrow, ncol) / svt_dev_arith_merge_ws_bytes(), nvals < 1 ("replacement has length
+   zero"), a type outside logical / integer / double, extents of v that differ from the selection's ("the selection and
+   supplied value must have the same dimensions"), extents of y that differ from x's; > 0 for an operand with
+   na_background and, SVT form, for rows in range that are not strictly increasing or a repeated leaf.  On a non-zero
+   status nothing is written outside `ws`.  Alignment and workspace: "Workspaces" above.
+
+   Not offered: L-index and M-index subassignment, a dense array value, NaArray operands, the SVT form with rows out of
+   order or repeated leaves, character / raw / complex types, sharding over the device list, an entry in the R glue
+   (INTEGRATION.md describes the call). */
+int svt_dev_subassign_tile(void);
+size_t svt_dev_subassign_place_ws_bytes(int64_t nrow, int64_t ncol);
+int svt_dev_subassign_place_vector_count(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+					 const int32_t *leaves, int64_t nleaves_sel, const void *vals, int64_t nvals, int v_Rtype,
+					 int64_t *y_col_ptr, unsigned char *cover_row, unsigned char *cover_leaf, int64_t *y_nnz,
+					 void *ws, size_t ws_bytes, void *stream);
+int svt_dev_subassign_place_vector_fill(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+					const int32_t *leaves, int64_t nleaves_sel, const void *vals, int64_t nvals, int v_Rtype,
+					const int64_t *y_col_ptr, int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws,
+					size_t ws_bytes, void *stream);
+int svt_dev_subassign_place_svt_count(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+				      const int32_t *leaves, int64_t nleaves_sel, const svt_dev_csc *v, int64_t *y_col_ptr,
+				      unsigned char *cover_row, unsigned char *cover_leaf, int64_t *y_nnz, void *ws, size_t ws_bytes,
+				      void *stream);
+int svt_dev_subassign_place_svt_fill(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+				     const int32_t *leaves, int64_t nleaves_sel, const svt_dev_csc *v, const int64_t *y_col_ptr,
+				     int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_assign_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
+			       const unsigned char *cover_leaf, int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes,
+			       void *stream);
+int svt_dev_assign_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
+			      const unsigned char *cover_leaf, const int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val,
+			      const void *ws, size_t ws_bytes, void *stream);
+/* The compositions place -> merge over the allocator of svt_dev_subset(): Y, the tables and the workspaces come from
+   `alloc` and go back through `release`; the three result arrays (*out_col_ptr int64[ncol + 1]; *out_row_idx, *out_val
+   of at least one element, *out_Rtype their type) are the caller's to release.  Synchronise `stream` twice (the two
+   count calls), once for an empty selection (the one-object case of svt_dev_abind: a copy that may widen); the last
+   fill is still queued on return. */
+int svt_dev_subassign_vector(const svt_dev_csc *x, const int32_t *rows, int64_t nrows_sel, const int32_t *leaves,
+			     int64_t nleaves_sel, const void *vals, int64_t nvals, int v_Rtype, svt_dev_alloc_fn alloc,
+			     svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr,
+			     int32_t **out_row_idx, void **out_val, void *stream);
+int svt_dev_subassign_svt(const svt_dev_csc *x, const int32_t *rows, int64_t nrows_sel, const int32_t *leaves,
+			  int64_t nleaves_sel, const svt_dev_csc *v, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx,
+			  int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val,
+			  void *stream);
+
+/* Host level.  `index`: x->ndim subscripts, 1-based as an N-index arrives, index[a] == NULL (or index == NULL) for the
+   whole axis, index_len[a] their lengths.  begin checks them on the host (NA_INTEGER or an index outside 1..extent: < 0,
+   "subscript contains out-of-bound indices or NAs", before anything is uploaded), expands those of dims 2..N into the
+   leaf list (the outermost dimension slowest; at most 2^31 - 2 leaves), uploads x and the value (through the resident
+   cache when it is on), runs the composition on the first device of the list (not sharded) and leaves the result on
+   the device: *out_Rtype its type, *out_nnz its nonzero count, its dims are x's.  The existing svt_Arith_SVT_end copies
+   it out and releases it.  `vals` is a host array of nvals values of v_Rtype; the dims of `v` must be the selection's.
+   What the R method checks before the call (the value's class, its length against the selection) is the caller's. */
+int svt_subassign_SVT_vector_begin(const svt_view *x, const int *const *index, const int64_t *index_len, const void *vals,
+				   int64_t nvals, int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
+int svt_subassign_SVT_SVT_begin(const svt_view *x, const int *const *index, const int64_t *index_len, const svt_view *v,
+				svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
 
 #ifdef __cplusplus
 }

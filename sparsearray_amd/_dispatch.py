@@ -448,6 +448,48 @@ class CAbiDispatcher:
         ans.na_background = x.na_background
         return ans
 
+    # x[i, j, ...] <- value by an N-index (src/SparseArray_subassignment.c:1005-1230; include/svt_hip.h; HIP library only):
+    # begin leaves the result on the device, Arith_SVT_end copies it out ------------------------------------------------
+    def _subassign(self, begin, x, Nindex, args):
+        """``Nindex``: one subscript per dimension, 1-based int32 arrays, or None for the whole axis.  Returns the
+        SVT_SparseArray of x's dim and dimnames that ``svt_<begin>(x, index, index_len, *args, &res, &Rtype, &nnz)``
+        computes; its type is what the library says (the wider of x's and the value's)."""
+        if len(Nindex) != x.ndim:
+            raise SparseArrayError("incorrect number of subscripts")
+        sub = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in Nindex]
+        # (a pointer tells "no subscript" from an empty one: an empty array is handed over as one unread element)
+        buf = [None if v is None else (v if v.size else np.zeros(1, np.int32)) for v in sub]
+        index = (c_void_p * x.ndim)(*[None if b is None else b.ctypes.data for b in buf])
+        index_len = np.array([-1 if v is None else v.size for v in sub], dtype=np.int64)
+        res, rt, nnz = c_void_p(0), c_int(0), ctypes.c_int64(0)
+        self._run(begin, x, index, index_len, *args, byref(res), byref(rt), byref(nnz))
+        n = int(nnz.value)
+        type_ = {LGLSXP: "logical", INTSXP: "integer", REALSXP: "double"}[rt.value]
+        cp = np.zeros(int(np.prod(x.dim[1:], dtype=np.int64)) + 1, dtype=np.int64)
+        ri = np.zeros(max(n, 1), dtype=np.int32)
+        vv = np.zeros(max(n, 1), dtype=np.float64 if type_ == "double" else np.int32)
+        self._run("Arith_SVT_end", res, cp, ri, vv)
+        return SVT_SparseArray.from_csc(tuple(x.dim), type_, cp, ri[:n], vv[:n], dimnames=x.dimnames)
+
+    def C_subassign_SVT_with_short_Rvector(self, x: SVT_SparseArray, Nindex, value: np.ndarray):
+        """``value``: a non-empty 1-D array, bool (logical), int32 (integer) or float64 (double), recycled over the row
+        subscript; NA_integer_ and NA_real_ travel as they are."""
+        value = np.ascontiguousarray(value).reshape(-1)
+        if value.dtype == np.bool_:
+            value, v_type = value.astype(np.int32), "logical"
+        else:
+            v_type = r_type_of(value)
+        if v_type not in _RT:
+            raise SparseArrayError("the supplied value must be of type \"logical\", \"integer\" or \"double\"")
+        if value.size == 0:
+            raise SparseArrayError("replacement has length zero")
+        return self._subassign("subassign_SVT_vector_begin", x, Nindex, (value, int(value.size), _RT[v_type]))
+
+    def C_subassign_SVT_with_SVT(self, x: SVT_SparseArray, Nindex, v: SVT_SparseArray):
+        """``v``: an SVT_SparseArray with the dims of the selection; rows strictly increasing, leaves without repeats
+        (anything else in range: SparseArrayUnsupported)."""
+        return self._subassign("subassign_SVT_SVT_begin", x, Nindex, (v,))
+
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""
         return self._dgc("rowsum_dgCMatrix", x, group, ngroup, na_rm,

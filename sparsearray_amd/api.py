@@ -14,6 +14,7 @@ as ``src/R_init_SparseArray.c:94,121-134``:
     C_Arith_SVT1_SVT2     C_Arith_SVT1_v2       C_unary_minus_SVT      C_Math_SVT (HIP library only)
     C_Compare_SVT1_v2     C_Compare_SVT1_SVT2   C_Logic_SVT1_SVT2      (HIP library only)
     C_abind_SVT_SparseArray_objects                                      (HIP library only)
+    C_subassign_SVT_with_short_Rvector  C_subassign_SVT_with_SVT         (HIP library only)
 
 and the entry points the HIP library adds to them (include/svt_hip.h):
 
@@ -615,6 +616,76 @@ class Session:
             raise SparseArrayError("incorrect number of subscripts")
         index = [self._check_Nindex(s, d) for s, d in zip(index, x.dim)]
         return self.SparseArray_Call("C_subset_SVT_by_Nindex", x, *index)
+
+    # ------------------------------------------------------------------
+    # x[i, j, ...] <- value by an N-index  (.subassign_SVT_by_Nindex, R/SparseArray-subassignment.R:114-170)
+    # ------------------------------------------------------------------
+    @staticmethod
+    def _set_type(x, type_: str):
+        """``type(x) <- type_`` for the widenings of logical < integer < double (NA_integer_ becomes NA_real_)."""
+        if type_ == x.type:
+            return x
+        if type_ == "double":
+            return x.with_type("double")
+        return SVT_SparseArray(x.dim, type_, x.leaves, x.dimnames, x.svt_is_null, x.na_background)     # logical -> integer
+
+    def subassign(self, x, value, i=None, j=None, *more):
+        """``x[i, j, ...] <- value`` by an N-index, 1-based; None keeps the whole axis.  ``value`` is a scalar or a
+        1-D vector (bool: logical, int: integer, float: double) that meets the short-form condition -- ``len(value) <=
+        len(i)`` and ``len(i) %% len(value) == 0``, ``len(i)`` the rows' extent for a missing ``i`` -- or an
+        SVT_SparseArray with the dims of the selection (then ``i`` strictly increasing, no subscript with repeats).
+        Returns a new object of the wider type of the two; dimnames are kept.  Not offered (SparseArrayUnsupported): a
+        vector outside the short form, a dense array value, NaArray operands, character / raw / complex values."""
+        index = (i, j) + more
+        if i is None and j is None and not more:
+            index = (None,) * x.ndim
+        elif x.ndim == 1 and j is None and not more:
+            index = (i,)
+        if len(index) != x.ndim:
+            raise SparseArrayError("incorrect number of subscripts")
+        is_svt = isinstance(value, SVT_SparseArray)
+        a = None
+        if not is_svt:
+            try:
+                a = np.asarray(value)
+            except (TypeError, ValueError):
+                a = None
+            if a is None or a.dtype == object:
+                raise SparseArrayError("the supplied value must be an ordinary vector or array, or an SVT_SparseArray "
+                                       "object, for this subassignment")
+        if x.na_background or (is_svt and value.na_background):
+            raise SparseArrayUnsupported("subassignment of NaArray objects is not offered by this library")
+        v_type = value.type if is_svt else self._scalar_class_type(a)[1]
+        if v_type not in ("logical", "integer", "double"):
+            raise SparseArrayUnsupported(f"subassignment with a value of type \"{v_type}\" is not offered by this library")
+        new_type = _common_type(x.type, v_type)
+        index = [self._check_Nindex(s, d) for s, d in zip(index, x.dim)]
+        selection_dim = tuple(d if s is None else int(s.size) for s, d in zip(index, x.dim))
+        if any(d == 0 for d in selection_dim):                      # a no-op, except for the type
+            return self._set_type(x, new_type)
+        if not is_svt and a.ndim <= 1:
+            a = a.reshape(-1)
+            if a.size == 0:
+                raise SparseArrayError("replacement has length zero")
+            if a.size > int(np.prod(selection_dim, dtype=object)):
+                raise SparseArrayError("the supplied value is longer than the selection")
+            if not (a.size <= selection_dim[0] and selection_dim[0] % a.size == 0):
+                raise SparseArrayUnsupported("subassignment with a vector that is recycled across the columns of the "
+                                             "selection (C_subassign_SVT_with_Rarray) is not offered by this library")
+            # storage.mode(value) <- new_type
+            if new_type == "double":
+                v = _dense_to_double(a.astype(np.int32)) if v_type != "double" else a.astype(np.float64)
+            else:
+                v = a.astype(np.bool_ if new_type == "logical" and a.dtype == np.bool_ else np.int32)
+            self._optional_entry("C_subassign_SVT_with_short_Rvector", "subassign_SVT_vector_begin")
+            return self.SparseArray_Call("C_subassign_SVT_with_short_Rvector", x, index, v)
+        if selection_dim != tuple(value.dim if is_svt else a.shape):
+            raise SparseArrayError("the selection and supplied value must have the same dimensions")
+        if not is_svt:
+            raise SparseArrayUnsupported("subassignment with a dense array value (C_subassign_SVT_with_Rarray) is not "
+                                         "offered by this library")
+        self._optional_entry("C_subassign_SVT_with_SVT", "subassign_SVT_SVT_begin")
+        return self.SparseArray_Call("C_subassign_SVT_with_SVT", x, index, value)
 
     # ------------------------------------------------------------------
     # abind, cbind, rbind  (.abind_SparseArray_objects, R/SparseArray-abind.R:53-99)

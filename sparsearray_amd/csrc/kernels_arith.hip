@@ -30,6 +30,11 @@
 // the operands, and no overflow is raised.  Everything else -- tiles, column search, ranking, placement, the cut, the
 // ownership of a pair, the workspace -- is shared as it is.
 //
+// Subassignment x[i, j] <- value is a fourth rule on the merge (ARI_RULE_ASSIGN, svt_rule_assign): y is the placed
+// operand kernels_subassign.hip builds, the rule reads two cover tables in place of an opcode, the result is double when
+// either side is and int32 else, and no overflow is raised.  It adds nothing to the LDS: the leaf of an x entry is found
+// again from the x part's column range (sh.rng), not kept next to its key.
+//
 // LDS: keys 8 * (2048 + 2), sources 4 * 2048, ballots and chunk prefixes 0.4 KB: 24.5 KB for the merge (6 workgroups
 // of a CU's 160 KB), 0.4 KB for the map.
 #include "svt_common.h"
@@ -271,15 +276,28 @@ struct AriMergeShared {
 };
 
 template <typename TX, typename TY, int RULE> struct AriMergeOut {
-	typedef typename std::conditional<RULE != ARI_RULE_ARITH || (std::is_same<TX, int32_t>::value && std::is_same<TY, int32_t>::value),
+	typedef typename std::conditional<RULE == ARI_RULE_COMPARE || RULE == ARI_RULE_LOGIC ||
+					  (std::is_same<TX, int32_t>::value && std::is_same<TY, int32_t>::value),
 					  int32_t, double>::type type;
 };
+// what a rule reads besides the two values: the opcode, or, for the subassignment rule, the cover tables (one byte per
+// row, one per leaf; NULL: the whole axis).  The kernels of the other rules keep their `int op` argument as it was.
+struct AriCover {
+	const unsigned char *row, *leaf;
+};
+template <int RULE> struct AriOp { typedef int type; };
+template <> struct AriOp<ARI_RULE_ASSIGN> { typedef AriCover type; };
+template <int RULE> static inline typename AriOp<RULE>::type ari_op(const ArithMergeArgs &a)
+{
+	if constexpr (RULE == ARI_RULE_ASSIGN) return AriCover{ a.cover_row, a.cover_leaf };
+	else return a.op;
+}
 
 // One tile of the merged sequence: merged places [ts, ts + n), x entries [a0, a0 + na), y entries [b0, b0 + nb).  Leaves
 // per striped place of this thread the result, its row and whether it is kept.
 template <typename TX, typename TY, int RULE>
 __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const AriSide &Y, const TY *yval, int64_t ncol, int64_t nrow,
-				      int op, int64_t a0, int na, int64_t b0, int nb, AriMergeShared &sh,
+				      const typename AriOp<RULE>::type &op, int64_t a0, int na, int64_t b0, int nb, AriMergeShared &sh,
 				      typename AriMergeOut<TX, TY, RULE>::type (&r)[ARI_ITEMS], int32_t (&row)[ARI_ITEMS],
 				      bool (&keep)[ARI_ITEMS], int *ovf)
 {
@@ -340,7 +358,20 @@ __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const Ar
 			row[it] = X.row_idx[a0 + idx];
 			if (s & ARI_PAIRED) yv = yval[b0 + (p - idx)];  // idx of x's and p - idx of y's come before place p
 		}
-		if constexpr (RULE == ARI_RULE_COMPARE)
+		if constexpr (RULE == ARI_RULE_ASSIGN) {
+			// the tables are read where the rule reads them: an entry of Y lies in a covered leaf; an x entry alone
+			// needs its row's byte, and its leaf's -- the column by a search inside the x part's column range, as the
+			// keys found it -- only when the row is covered or the value is a zero (else it is kept either way)
+			const bool in_y = (s & (ARI_FROM_Y | ARI_PAIRED)) != 0u;
+			bool rc = false, lc = true;
+			if (!in_y) {
+				rc = op.row == NULL || op.row[row[it]] != 0;
+				lc = (rc || ari_is_zero(xv)) &&
+				     (op.leaf == NULL || op.leaf[ari_last_le(xcp, sh.rng[0], sh.rng[1], a0 + idx)] != 0);
+			}
+			keep[it] = svt_rule_assign(in_y, xv, yv, rc, lc, &r[it]);
+			continue;
+		} else if constexpr (RULE == ARI_RULE_COMPARE)
 			r[it] = svt_rule_compare(op, svt_rule_as_double(xv), svt_rule_as_double(yv));
 		else if constexpr (RULE == ARI_RULE_LOGIC)
 			r[it] = svt_rule_logic(op, xv, yv);
@@ -354,8 +385,8 @@ __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const Ar
 
 template <typename TX, typename TY, int RULE>
 __global__ __launch_bounds__(ARI_NT) void arith_merge_count_kernel(AriSide X, const TX *xval, AriSide Y, const TY *yval, int64_t ncol,
-								   int64_t nrow, int op, const int64_t *cut, int64_t *tile_cnt,
-								   int32_t *local)
+								   int64_t nrow, typename AriOp<RULE>::type op, const int64_t *cut,
+								   int64_t *tile_cnt, int32_t *local)
 {
 	typedef typename AriMergeOut<TX, TY, RULE>::type TO;
 	__shared__ AriMergeShared sh;
@@ -376,9 +407,9 @@ __global__ __launch_bounds__(ARI_NT) void arith_merge_count_kernel(AriSide X, co
 
 template <typename TX, typename TY, int RULE>
 __global__ __launch_bounds__(ARI_NT) void arith_merge_fill_kernel(AriSide X, const TX *xval, AriSide Y, const TY *yval, int64_t ncol,
-								  int64_t nrow, int op, const int64_t *cut, const int64_t *tile_pre,
-								  int32_t *out_row_idx, typename AriMergeOut<TX, TY, RULE>::type *out_val,
-								  int *ovflow)
+								  int64_t nrow, typename AriOp<RULE>::type op, const int64_t *cut,
+								  const int64_t *tile_pre, int32_t *out_row_idx,
+								  typename AriMergeOut<TX, TY, RULE>::type *out_val, int *ovflow)
 {
 	typedef typename AriMergeOut<TX, TY, RULE>::type TO;
 	__shared__ AriMergeShared sh;
@@ -518,12 +549,13 @@ static inline void arith_merge_by_operands(const ArithMergeArgs &a, F &&f, R rul
 	else if (a.y_Rtype == SVT_REALSXP) f((const int32_t *) a.x_val, (const double *) a.y_val, rule);
 	else f((const int32_t *) a.x_val, (const int32_t *) a.y_val, rule);
 }
-// and by the rule: Arith and Compare for the four type pairs, Logic for int32 x int32 alone
+// and by the rule: Arith, Compare and the subassignment rule for the four type pairs, Logic for int32 x int32 alone
 template <class F>
 static inline int arith_merge_by_types(const ArithMergeArgs &a, F &&f)
 {
 	if (a.rule == ARI_RULE_ARITH) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ARITH>());
 	else if (a.rule == ARI_RULE_COMPARE) arith_merge_by_operands(a, f, AriRule<ARI_RULE_COMPARE>());
+	else if (a.rule == ARI_RULE_ASSIGN) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ASSIGN>());
 	else if (a.rule == ARI_RULE_LOGIC && a.x_Rtype != SVT_REALSXP && a.y_Rtype != SVT_REALSXP)
 		f((const int32_t *) a.x_val, (const int32_t *) a.y_val, AriRule<ARI_RULE_LOGIC>());
 	else return svt_set_error("arith merge: no kernel for this rule and these types");
@@ -548,7 +580,8 @@ int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void
 			typedef std::remove_const_t<std::remove_pointer_t<decltype(xv)>> TX;
 			typedef std::remove_const_t<std::remove_pointer_t<decltype(yv)>> TY;
 			hipLaunchKernelGGL((arith_merge_count_kernel<TX, TY, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0,
-					   s, X, xv, Y, yv, a.ncol, a.nrow, a.op, (const int64_t *) cut, tile, (int32_t *) (w + L.local));
+					   s, X, xv, Y, yv, a.ncol, a.nrow, ari_op<decltype(rule)::value>(a), (const int64_t *) cut, tile,
+					   (int32_t *) (w + L.local));
 		});
 		if (rc) return rc;
 	}
@@ -568,8 +601,8 @@ int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void 
 		typedef std::remove_const_t<std::remove_pointer_t<decltype(yv)>> TY;
 		typedef typename AriMergeOut<TX, TY, decltype(rule)::value>::type TO;
 		hipLaunchKernelGGL((arith_merge_fill_kernel<TX, TY, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, X,
-				   xv, Y, yv, a.ncol, a.nrow, a.op, (const int64_t *) (w + L.cut), (const int64_t *) (w + L.tile),
-				   out_row_idx, (TO *) out_val, ovflow);
+				   xv, Y, yv, a.ncol, a.nrow, ari_op<decltype(rule)::value>(a), (const int64_t *) (w + L.cut),
+				   (const int64_t *) (w + L.tile), out_row_idx, (TO *) out_val, ovflow);
 	});
 	if (rc) return rc;
 	HIP_TRY(hipGetLastError());

@@ -1,6 +1,7 @@
 // The element rules of Arith and Math on sparse operands (src/SparseVec_Arith.c, src/SparseVec_Math.c of the
-// reference; R's arithmetic.c for the operators), each stated once for the device kernels (kernels_arith.hip) and for
-// a host program (tests/arith_rules_main.cpp): plain C++, no HIP header needed.
+// reference; R's arithmetic.c for the operators), of Compare and Logic, and of subassignment, each stated once for the
+// device kernels (kernels_arith.hip) and for a host program (tests/arith_rules_main.cpp, compare_rules_main.cpp,
+// assign_rules_main.cpp): plain C++, no HIP header needed.
 #pragma once
 
 #include <math.h>
@@ -353,6 +354,41 @@ SVT_HD inline int32_t svt_rule_logic(int op, int32_t x, int32_t y)
 	if (x == SVT_NA_INT || y == SVT_NA_INT)
 		return SVT_NA_INT;
 	return 0;
+}
+
+// ---- subassignment x[i, j] <- value (src/SparseArray_subassignment.c of the reference) ----
+// a value in the result's type: the same type moves as bits, int32 -> double converts and NA_integer_ becomes NA_real_
+SVT_HD inline void svt_rule_widen(int32_t v, int32_t *out) { *out = v; }
+SVT_HD inline void svt_rule_widen(double v, double *out) { *out = v; }
+SVT_HD inline void svt_rule_widen(int32_t v, double *out) { *out = svt_rule_as_double(v); }
+
+// One place of x merged with the placed operand Y (the new values of the selected cells that may have to be stored; Y
+// has entries in covered leaves only).  in_y: Y stores the place (alone or next to an x entry) -- the result is Y's
+// value; else x alone stores it: dropped when its row and its leaf are both covered (the cell was assigned a zero),
+// x's value otherwise.  Returns whether the result is stored, *out its value: an entry is kept unless its leaf is
+// covered and its value == 0 (-0.0 and integer 0 too; a NaN or NA is kept) -- a selected leaf is rebuilt from its dense
+// form, so a stored zero of x in it goes even on a row outside i, while an uncovered leaf keeps every entry as it is.
+template <typename TX, typename TY, typename TO>
+SVT_HD inline bool svt_rule_assign(bool in_y, TX xv, TY yv, bool row_covered, bool leaf_covered, TO *out)
+{
+	if (in_y) {
+		svt_rule_widen(yv, out);
+	} else {
+		if (row_covered && leaf_covered)
+			return false;
+		svt_rule_widen(xv, out);
+	}
+	return !(leaf_covered && *out == (TO) 0);
+}
+
+// the wider of two types, logical < integer < double; 0 when either is none of them
+SVT_HD inline int svt_rule_assign_out_Rtype(int x_Rtype, int v_Rtype)
+{
+	const bool xo = x_Rtype == SVT_LGLSXP || x_Rtype == SVT_INTSXP || x_Rtype == SVT_REALSXP;
+	const bool vo = v_Rtype == SVT_LGLSXP || v_Rtype == SVT_INTSXP || v_Rtype == SVT_REALSXP;
+	if (!xo || !vo) return 0;
+	if (x_Rtype == SVT_REALSXP || v_Rtype == SVT_REALSXP) return SVT_REALSXP;
+	return x_Rtype == SVT_INTSXP || v_Rtype == SVT_INTSXP ? SVT_INTSXP : SVT_LGLSXP;
 }
 
 // the type of the result (SVT_INTSXP / SVT_REALSXP), or 0 for a combination that is not offered

@@ -274,8 +274,10 @@ int launch_subset_rows_fill(const int32_t *row_idx, const void *val, int Rtype, 
 // and, in the head of `ws`, [int64 at byte 8: the nonzeros of the result], and a fill launcher that reads `ws` as the
 // count launcher left it.  All asynchronous.  `entries`: nnz for the map, nnz(x) + nnz(y) for the merge.  `rule`: the
 // element rule the tiles evaluate -- Arith and Math as `kind` and `op` say, or Compare / Logic (`op` a SVT_COMPARE_* /
-// SVT_LOGIC_* opcode, `kind` not read), whose result is int32 whatever the operands and has no overflow word.
-enum { ARI_RULE_ARITH = 0, ARI_RULE_COMPARE = 1, ARI_RULE_LOGIC = 2 };
+// SVT_LOGIC_* opcode, `kind` not read), whose result is int32 whatever the operands and has no overflow word, or the
+// subassignment rule (merge only; y the placed operand of kernels_subassign.hip, `op` not read, `cover_row` /
+// `cover_leaf` one byte per row / per leaf, NULL: the whole axis; the result double when either side is, else int32).
+enum { ARI_RULE_ARITH = 0, ARI_RULE_COMPARE = 1, ARI_RULE_LOGIC = 2, ARI_RULE_ASSIGN = 3 };
 struct ArithMapArgs {
 	const int64_t *col_ptr;
 	const int32_t *row_idx;
@@ -294,6 +296,7 @@ struct ArithMergeArgs {
 	int64_t nrow, ncol;
 	int op;
 	int rule = ARI_RULE_ARITH;
+	const unsigned char *cover_row = NULL, *cover_leaf = NULL;     // ARI_RULE_ASSIGN
 };
 int arith_tile(void);
 size_t arith_ws_bytes(int64_t ncol, int64_t entries, int merge);
@@ -301,6 +304,29 @@ int launch_arith_map_count(const ArithMapArgs &a, int64_t *out_col_ptr, void *ws
 int launch_arith_map_fill(const ArithMapArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
 int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
 int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
+
+// Subassignment (kernels_subassign.hip): the placed operand Y of x[rows, leaves] <- value and the two cover tables,
+// for the merge under ARI_RULE_ASSIGN.  `rows` / `leaves`: device int32, 0-based; nrows_sel / nleaves_sel < 0: the whole
+// axis (the pointer is not read).  The vector form recycles `vals` (nvals >= 1 values of v_Rtype) over the row subscript,
+// the last occurrence of a row winning, and keeps the non-zero values only; the SVT form renames the rows of `v`'s
+// leaves (v_* : its arrays; rows strictly increasing, leaves without repeats).  The count launcher leaves y_col_ptr
+// int64[ncol + 1], the tables (a NULL table is not written) and, in the head of `ws`, [int: 1 a bad index, 2 rows not
+// strictly increasing or a repeated leaf (SVT form)][int64 at byte 8: the entries of Y]; with the flag up nothing is
+// written outside `ws`.  The fill launcher reads `ws` as the count launcher left it.  All asynchronous.
+struct SubassignArgs {
+	int64_t nrow, ncol;
+	const int32_t *rows; int64_t nrows_sel;
+	const int32_t *leaves; int64_t nleaves_sel;
+	const void *vals; int64_t nvals;        // the vector form
+	const int64_t *v_col_ptr; const int32_t *v_row_idx; const void *v_val; int64_t v_nnz;   // the SVT form (v_col_ptr != NULL)
+	int v_Rtype;
+};
+int subassign_tile(void);
+size_t subassign_ws_bytes(int64_t nrow, int64_t ncol);
+int launch_subassign_count(const SubassignArgs &a, int64_t *y_col_ptr, unsigned char *cover_row, unsigned char *cover_leaf, void *ws,
+			   hipStream_t s);
+int launch_subassign_fill(const SubassignArgs &a, const int64_t *y_col_ptr, int64_t y_nnz, int32_t *y_row_idx, void *y_val,
+			  const void *ws, hipStream_t s);
 
 // abind (kernels_abind.hip): the result as a sequence of pieces, each a whole leaf of one object.  The count launcher
 // copies the table of objects into `ws` (one asynchronous copy: the table must live until the stream has passed it) and

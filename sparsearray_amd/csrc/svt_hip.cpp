@@ -1553,6 +1553,22 @@ static inline double compare_scalar(double s, int s_Rtype)
 	return s_Rtype != SVT_REALSXP && s == -2147483648.0 ? svt_rule_na_real() : s;
 }
 
+// The same for the subassignment merge (ARI_RULE_ASSIGN): y is the placed operand; *out_Rtype <- the wider type
+static int assign_check(const char *who, const svt_dev_csc *x, const svt_dev_csc *y, int *out_Rtype)
+{
+	if (x == NULL || y == NULL)
+		return svt_set_error("%s: an operand is needed", who);
+	if (x->nrow != y->nrow || x->ncol != y->ncol)
+		return svt_set_error("%s: the placed operand must have the extents of x", who);
+	const int rt = svt_rule_assign_out_Rtype(x->Rtype, y->Rtype);
+	if (rt == 0)
+		return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
+	if (x->na_background || y->na_background)
+		return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+	*out_Rtype = rt;
+	return 0;
+}
+
 static ArithMergeArgs arith_merge_args(const svt_dev_csc *x, const svt_dev_csc *y, int op)
 {
 	ArithMergeArgs a;
@@ -1579,10 +1595,12 @@ struct ArithCall {
 	int s_Rtype;
 	int out_Rtype = 0;
 	int rule = ARI_RULE_ARITH;      // ARI_RULE_COMPARE / _LOGIC: `kind` says merge or map, the result is LGLSXP, no overflow word
+	const unsigned char *cover_row = NULL, *cover_leaf = NULL;      // ARI_RULE_ASSIGN (a merge): the two tables, NULL = the whole axis
 	ArithMergeArgs merge_args() const
 	{
 		ArithMergeArgs a = arith_merge_args(x, y, op);
 		a.rule = rule;
+		a.cover_row = cover_row; a.cover_leaf = cover_leaf;
 		return a;
 	}
 	ArithMapArgs map_args() const
@@ -1598,7 +1616,10 @@ struct ArithCall {
 	}
 	int check(size_t ws_bytes)
 	{
-		if (rule != ARI_RULE_ARITH) {
+		if (rule == ARI_RULE_ASSIGN) {
+			if (const int rc = assign_check(who, x, y, &out_Rtype))
+				return rc;
+		} else if (rule != ARI_RULE_ARITH) {
 			if (const int rc = compare_check(who, rule, kind, op, x, y, compare_scalar(s, s_Rtype), s_Rtype))
 				return rc;
 			out_Rtype = SVT_LGLSXP;
@@ -1978,6 +1999,217 @@ extern "C" int svt_dev_abind(const svt_dev_csc *const *objs, int nobj, int64_t i
 		*out_nrow = c.out_nrow;
 		*out_nleaves = c.a.out_nleaves;
 		return 0;
+	});
+}
+
+// ---- subassignment x[i, j] <- value: kernels_subassign.hip places the new values as an operand Y and marks what the
+// subscripts cover, the merge of kernels_arith.hip under ARI_RULE_ASSIGN (svt_rule_assign) makes the result ----
+extern "C" int svt_dev_subassign_tile(void)
+{
+	return subassign_tile();
+}
+extern "C" size_t svt_dev_subassign_place_ws_bytes(int64_t nrow, int64_t ncol)
+{
+	return subassign_ws_bytes(nrow, ncol);
+}
+
+// One placement, of either form (v != NULL: the SVT form): every check that needs no GPU, then count / fill.
+struct SubassignCall {
+	const char *who;
+	SubassignArgs a;
+
+	int plan(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel, const int32_t *leaves, int64_t nleaves_sel,
+		 const void *vals, int64_t nvals, int v_Rtype, const svt_dev_csc *v, bool svt_form)
+	{
+		memset(&a, 0, sizeof(a));
+		if (nrow < 0 || nrow > 0x7FFFFFFFLL || ncol < 0 || ncol > 0x7FFFFFFELL)
+			return svt_set_error("%s: extents outside 0 .. 2^31 - 1 rows, 0 .. 2^31 - 2 leaves", who);
+		if (nrows_sel > 0x7FFFFFFFLL || nleaves_sel > 0x7FFFFFFELL)
+			return svt_set_error("%s: at most 2^31 - 1 row subscripts and 2^31 - 2 leaves", who);
+		if ((nrows_sel > 0 && rows == NULL) || (nleaves_sel > 0 && leaves == NULL))
+			return svt_set_error("%s: a subscript is needed (a length < 0 stands for the whole axis)", who);
+		if (svt_form) {
+			if (v == NULL)
+				return svt_set_error("%s: the value operand is needed", who);
+			v_Rtype = v->Rtype;
+		} else if (nvals < 1 || vals == NULL) {
+			return svt_set_error("replacement has length zero");
+		}
+		if (!logical_family_type(v_Rtype))
+			return svt_set_error("%s: the value must be of type \"logical\", \"integer\" or \"double\"", who);
+		if (svt_form) {
+			if (v->nrow != (nrows_sel < 0 ? nrow : nrows_sel) || v->ncol != (nleaves_sel < 0 ? ncol : nleaves_sel))
+				return svt_set_error("the selection and supplied value must have the same dimensions");
+			if (v->na_background)
+				return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+			a.v_col_ptr = v->col_ptr; a.v_row_idx = v->row_idx; a.v_val = v->val; a.v_nnz = v->nnz;
+		}
+		a.nrow = nrow; a.ncol = ncol;
+		a.rows = rows; a.nrows_sel = nrows_sel < 0 ? -1 : nrows_sel;
+		a.leaves = leaves; a.nleaves_sel = nleaves_sel < 0 ? -1 : nleaves_sel;
+		a.vals = vals; a.nvals = nvals; a.v_Rtype = v_Rtype;
+		return 0;
+	}
+	size_t need() const { return subassign_ws_bytes(a.nrow, a.ncol); }
+	int count(int64_t *y_col_ptr, unsigned char *cover_row, unsigned char *cover_leaf, int64_t *y_nnz, void *ws, size_t ws_bytes,
+		  void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		if (y_col_ptr == NULL || y_nnz == NULL || (cover_row == NULL && a.nrows_sel >= 0) || (cover_leaf == NULL && a.nleaves_sel >= 0))
+			return svt_set_error("%s: 'y_col_ptr', 'y_nnz' and a cover table per subscript are needed", who);
+		hipStream_t st = (hipStream_t) stream;
+		if (launch_subassign_count(a, y_col_ptr, cover_row, cover_leaf, ws, st))
+			return -1;
+		int flag = 0;
+		int64_t total = 0;
+		if (subset_read_head(ws, st, &flag, &total))
+			return -1;
+		if (flag & 1)
+			return svt_set_error("subscript contains out-of-bound indices or NAs");
+		if (flag)
+			return svt_set_unsupported("%s: the row subscript is not strictly increasing, or a leaf is repeated", who);
+		*y_nnz = total;
+		return 0;
+	}
+	int fill(const int64_t *y_col_ptr, int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes, void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		return launch_subassign_fill(a, y_col_ptr, y_nnz, y_row_idx, y_val, ws, (hipStream_t) stream);
+	}
+	// place -> merge over the caller's allocator: the whole of x[rows, leaves] <- value
+	int compose(const svt_dev_csc *x, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz,
+		    int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+	{
+		if (alloc == NULL || release == NULL)
+			return svt_set_error("%s: an allocator is needed", who);
+		const int rt = svt_rule_assign_out_Rtype(x->Rtype, a.v_Rtype);
+		if (rt == 0)
+			return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
+		if (x->na_background)
+			return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+		if (a.nrows_sel == 0 || a.nleaves_sel == 0) {       // nothing selected: x, coerced (the one-object case of abind)
+			AbindCall c = { who };
+			const svt_dev_csc *objs[1] = { x };
+			if (c.plan(objs, 1, 0, NULL, rt) || c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream))
+				return -1;
+			*out_Rtype = rt;
+			return 0;
+		}
+		SubsetMem mem = { alloc, release, ctx };
+		SubsetCsc Y(mem);
+		SubsetWs ws(mem), cover(mem);
+		svt_dev_csc like;
+		memset(&like, 0, sizeof(like));
+		like.Rtype = a.v_Rtype;
+		const size_t row_bytes = ((size_t) x->nrow + 255) / 256 * 256;
+		if (Y.shape(&like, x->nrow, x->ncol) || ws.get(need()) || cover.get(row_bytes + (size_t) x->ncol))
+			return -1;
+		unsigned char *cover_row = a.nrows_sel < 0 ? NULL : (unsigned char *) cover.p;
+		unsigned char *cover_leaf = a.nleaves_sel < 0 ? NULL : (unsigned char *) cover.p + row_bytes;
+		int64_t y_nnz = 0;
+		if (count(Y.c.col_ptr, cover_row, cover_leaf, &y_nnz, ws.p, ws.n, stream) || Y.entries(y_nnz) ||
+		    fill(Y.c.col_ptr, y_nnz, Y.c.row_idx, Y.c.val, ws.p, ws.n, stream))
+			return -1;
+		ArithCall m = { who, SVT_ARITH_MERGE, 0, x, &Y.c, 0.0, 0 };
+		m.rule = ARI_RULE_ASSIGN;
+		m.cover_row = cover_row; m.cover_leaf = cover_leaf;
+		return m.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, stream);
+	}
+};
+
+extern "C" int svt_dev_subassign_place_vector_count(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+						    const int32_t *leaves, int64_t nleaves_sel, const void *vals, int64_t nvals,
+						    int v_Rtype, int64_t *y_col_ptr, unsigned char *cover_row, unsigned char *cover_leaf,
+						    int64_t *y_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		SubassignCall c = { "svt_dev_subassign_place_vector_count" };
+		if (c.plan(nrow, ncol, rows, nrows_sel, leaves, nleaves_sel, vals, nvals, v_Rtype, NULL, false)) return -1;
+		return c.count(y_col_ptr, cover_row, cover_leaf, y_nnz, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_subassign_place_vector_fill(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+						   const int32_t *leaves, int64_t nleaves_sel, const void *vals, int64_t nvals,
+						   int v_Rtype, const int64_t *y_col_ptr, int64_t y_nnz, int32_t *y_row_idx, void *y_val,
+						   const void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		SubassignCall c = { "svt_dev_subassign_place_vector_fill" };
+		if (c.plan(nrow, ncol, rows, nrows_sel, leaves, nleaves_sel, vals, nvals, v_Rtype, NULL, false)) return -1;
+		return c.fill(y_col_ptr, y_nnz, y_row_idx, y_val, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_subassign_place_svt_count(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+						 const int32_t *leaves, int64_t nleaves_sel, const svt_dev_csc *v, int64_t *y_col_ptr,
+						 unsigned char *cover_row, unsigned char *cover_leaf, int64_t *y_nnz, void *ws,
+						 size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		SubassignCall c = { "svt_dev_subassign_place_svt_count" };
+		if (c.plan(nrow, ncol, rows, nrows_sel, leaves, nleaves_sel, NULL, 0, 0, v, true)) return -1;
+		return c.count(y_col_ptr, cover_row, cover_leaf, y_nnz, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_subassign_place_svt_fill(int64_t nrow, int64_t ncol, const int32_t *rows, int64_t nrows_sel,
+						const int32_t *leaves, int64_t nleaves_sel, const svt_dev_csc *v, const int64_t *y_col_ptr,
+						int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes,
+						void *stream)
+{
+	return abi_status([&] {
+		SubassignCall c = { "svt_dev_subassign_place_svt_fill" };
+		if (c.plan(nrow, ncol, rows, nrows_sel, leaves, nleaves_sel, NULL, 0, 0, v, true)) return -1;
+		return c.fill(y_col_ptr, y_nnz, y_row_idx, y_val, ws, ws_bytes, stream);
+	});
+}
+
+static ArithCall assign_call(const char *who, const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
+			     const unsigned char *cover_leaf)
+{
+	ArithCall c = { who, SVT_ARITH_MERGE, 0, x, y, 0.0, 0 };
+	c.rule = ARI_RULE_ASSIGN;
+	c.cover_row = cover_row; c.cover_leaf = cover_leaf;
+	return c;
+}
+extern "C" int svt_dev_assign_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
+					  const unsigned char *cover_leaf, int64_t *out_col_ptr, int64_t *out_nnz, void *ws,
+					  size_t ws_bytes, void *stream)
+{
+	ArithCall c = assign_call("svt_dev_assign_merge_count", x, y, cover_row, cover_leaf);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_assign_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
+					 const unsigned char *cover_leaf, const int64_t *out_col_ptr, int32_t *out_row_idx,
+					 void *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile prefixes in `ws` place the entries)
+	ArithCall c = assign_call("svt_dev_assign_merge_fill", x, y, cover_row, cover_leaf);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+
+extern "C" int svt_dev_subassign_vector(const svt_dev_csc *x, const int32_t *rows, int64_t nrows_sel, const int32_t *leaves,
+					int64_t nleaves_sel, const void *vals, int64_t nvals, int v_Rtype, svt_dev_alloc_fn alloc,
+					svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr,
+					int32_t **out_row_idx, void **out_val, void *stream)
+{
+	return abi_status([&] {
+		SubassignCall c = { "svt_dev_subassign_vector" };
+		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
+		if (c.plan(x->nrow, x->ncol, rows, nrows_sel, leaves, nleaves_sel, vals, nvals, v_Rtype, NULL, false)) return -1;
+		return c.compose(x, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	});
+}
+extern "C" int svt_dev_subassign_svt(const svt_dev_csc *x, const int32_t *rows, int64_t nrows_sel, const int32_t *leaves,
+				     int64_t nleaves_sel, const svt_dev_csc *v, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+				     void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+				     void **out_val, void *stream)
+{
+	return abi_status([&] {
+		SubassignCall c = { "svt_dev_subassign_svt" };
+		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
+		if (c.plan(x->nrow, x->ncol, rows, nrows_sel, leaves, nleaves_sel, NULL, 0, 0, v, true)) return -1;
+		return c.compose(x, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 	});
 }
 
@@ -3369,6 +3601,123 @@ extern "C" int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int
 {
 	return compare_begin("svt_Logic_SVT_SVT_begin", ARI_RULE_LOGIC, op, x, y, true, 0.0, 0, res, out_nnz);
 }
+// x[i, j, ...] <- value on host operands (.subassign_SVT_by_Nindex, C_subassign_SVT_with_short_Rvector): the subscripts
+// are checked and those of dims 2..N expanded into the leaf list here, on the host, before anything is uploaded; the
+// composition is SubassignCall::compose() on the first device, the result stays there until svt_Arith_SVT_end.
+static int subassign_begin_impl(const char *who, const svt_view *x, const int *const *index, const int64_t *index_len,
+				const void *vals, int64_t nvals, int v_Rtype, const svt_view *v, bool svt_form, svt_arith_result **res,
+				int *out_Rtype, int64_t *out_nnz)
+{
+	if (res == NULL || out_Rtype == NULL || out_nnz == NULL)
+		return svt_set_error("%s: 'res', 'out_Rtype' and 'out_nnz' are needed", who);
+	*res = NULL;
+	if (svt_form && v == NULL)
+		return svt_set_error("%s: the value operand is needed", who);
+	if (ensure_init() || check_view(x) || (svt_form && check_view(v)))
+		return -1;
+	if (x->na_background || (svt_form && v->na_background))
+		return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+	if (!svt_form && (nvals < 1 || vals == NULL))
+		return svt_set_error("replacement has length zero");
+	const int ndim = x->ndim;
+	std::vector<std::vector<int32_t>> sub((size_t) ndim);
+	std::vector<int64_t> len((size_t) ndim);            // the selection's extent along every dimension
+	bool whole_leaves = true;
+	for (int a = 0; a < ndim; a++) {
+		const int *idx = index != NULL ? index[a] : NULL;
+		len[(size_t) a] = x->dim[a];
+		if (idx == NULL) continue;
+		const int64_t n = index_len != NULL ? index_len[a] : -1;
+		if (n < 0) return svt_set_error("%s: a subscript needs its length", who);
+		sub[(size_t) a].resize((size_t) n);
+		for (int64_t k = 0; k < n; k++) {
+			if (idx[k] == NA_INT || idx[k] < 1 || idx[k] > x->dim[a])
+				return svt_set_error("subscript contains out-of-bound indices or NAs");
+			sub[(size_t) a][(size_t) k] = idx[k] - 1;
+		}
+		len[(size_t) a] = n;
+		if (a > 0) whole_leaves = false;
+	}
+	if (svt_form) {
+		bool same = v->ndim == ndim;
+		for (int a = 0; same && a < ndim; a++) same = v->dim[a] == len[(size_t) a];
+		if (!same) return svt_set_error("the selection and supplied value must have the same dimensions");
+	}
+	// the selected leaves, the outermost dimension slowest -- the order of the leaves of a value of the selection's dims
+	std::vector<int32_t> leaves;
+	int64_t nleaves_sel = -1;
+	if (!whole_leaves) {
+		nleaves_sel = 1;
+		for (int a = 1; a < ndim; a++) {
+			if (len[(size_t) a] > 0 && nleaves_sel > 0x7FFFFFFELL / len[(size_t) a])
+				return svt_set_error("%s: the subscripts select more than 2^31 - 2 leaves", who);
+			nleaves_sel *= len[(size_t) a];
+		}
+		leaves.resize((size_t) nleaves_sel);
+		for (int64_t q = 0; q < nleaves_sel; q++) {
+			int64_t rest = q, leaf = 0, stride = 1;
+			for (int a = 1; a < ndim; a++) {
+				const int64_t k = rest % len[(size_t) a];
+				rest /= len[(size_t) a];
+				leaf += stride * (index[a] != NULL ? sub[(size_t) a][(size_t) k] : k);
+				stride *= x->dim[a];
+			}
+			leaves[(size_t) q] = (int32_t) leaf;
+		}
+	}
+	const bool whole_rows = index == NULL || index[0] == NULL;
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	std::optional<CscGuard> V;
+	if (svt_form) {
+		V.emplace(v);
+		if (V->h == NULL) return -1;
+	}
+	DevBuf dr, dl, dv;
+	if ((!whole_rows && !sub[0].empty() && dr.upload(sub[0].data(), sub[0].size() * 4)) ||
+	    (!leaves.empty() && dl.upload(leaves.data(), leaves.size() * 4)) ||
+	    (!svt_form && dv.upload(vals, (size_t) nvals * elt_size(v_Rtype))))
+		return -1;
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
+	SubassignCall c = { who };
+	int rt = 0;
+	if (c.plan(A.h->nrow, A.h->ncol, dr.as<int32_t>(), whole_rows ? -1 : len[0], dl.as<int32_t>(), nleaves_sel, dv.as<char>(), nvals,
+		   v_Rtype, svt_form ? V->h : NULL, svt_form) ||
+	    c.compose(A.h, subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, NULL) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
+		svt_release(h);
+		return -1;
+	}
+	h->Rtype = rt;
+	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
+	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
+	r->h = h;
+	*res = r;
+	*out_Rtype = rt;
+	*out_nnz = h->nnz;
+	return 0;
+}
+extern "C" int svt_subassign_SVT_vector_begin(const svt_view *x, const int *const *index, const int64_t *index_len, const void *vals,
+					      int64_t nvals, int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
+{
+	return abi_status([&] {
+		if (!logical_family_type(v_Rtype))
+			return svt_set_error("svt_subassign_SVT_vector_begin: the value must be of type \"logical\", \"integer\" or \"double\"");
+		return subassign_begin_impl("svt_subassign_SVT_vector_begin", x, index, index_len, vals, nvals, v_Rtype, NULL, false, res,
+					    out_Rtype, out_nnz);
+	});
+}
+extern "C" int svt_subassign_SVT_SVT_begin(const svt_view *x, const int *const *index, const int64_t *index_len, const svt_view *v,
+					   svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
+{
+	return abi_status([&] {
+		return subassign_begin_impl("svt_subassign_SVT_SVT_begin", x, index, index_len, NULL, 0, 0, v, true, res, out_Rtype, out_nnz);
+	});
+}
+
 // abind on host operands (C_abind_SVT_SparseArray_objects): `along` and the dims are checked here, before anything is
 // uploaded; the objects go up through the resident cache, AbindCall::compose() runs on the first device, the result
 // stays there until svt_Arith_SVT_end.

@@ -123,6 +123,31 @@ class DeviceCSC:
         ncol = self.ncol if sub[1] is None else sub[1].numel()
         return DeviceCSC(nrow, *mem.csc(out, ncol, int(nnz.value), self.val.dtype), logical=self.Rtype == LGLSXP)
 
+    def subassign(self, rows, leaves, value, logical: bool = False) -> "DeviceCSC":
+        """``x[rows, leaves] <- value`` on the device (include/svt_hip.h, svt_dev_subassign_vector / _svt): ``rows`` /
+        ``leaves`` are 0-based int32 tensors or array-likes, or None for the whole axis.  ``value``: a scalar or a 1-D
+        tensor / array (bool: logical, int32: integer -- logical with ``logical=True`` -- float64: double), recycled
+        over the row subscript, rows and leaves in any order and with repeats, the last occurrence of a row winning; or
+        a DeviceCSC of len(rows) x len(leaves), rows strictly increasing and leaves without repeats
+        (SparseArrayUnsupported otherwise).  Returns a new DeviceCSC of the wider type of the two; nothing is read
+        through an index out of range (SparseArrayError).  Every array is a torch allocation on the current stream."""
+        dev = self.val.device
+        sub = [None if v is None else _subscript(v, dev) for v in (rows, leaves)]
+        idx = [a for v in sub for a in ((None, -1) if v is None else (v.data_ptr(), v.numel()))]
+        if isinstance(value, DeviceCSC):
+            call = lambda *a: _lib().svt_dev_subassign_svt(self.handle, *idx, value.handle, *a)          # noqa: E731
+        else:
+            vals, v_Rtype = _assign_values(value, dev, logical)
+            call = lambda *a: _lib().svt_dev_subassign_vector(self.handle, *idx, vals.data_ptr(), vals.numel(),  # noqa: E731
+                                                              v_Rtype, *a)
+        mem = _TorchBlocks(dev)
+        rt, nnz = ctypes.c_int(0), c_int64(0)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt), ctypes.byref(nnz), *[ctypes.byref(o) for o in out],
+                    _stream()))
+        dtype = torch.float64 if rt.value == REALSXP else torch.int32
+        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype), logical=rt.value == LGLSXP)
+
     def _arith_result(self, call):
         """The new DeviceCSC that ``call(alloc, release, ctx, out_Rtype, nnz, col_ptr, row_idx, val, ovflow, stream)`` --
         one of the two compositions svt_dev_arith_merge / svt_dev_arith_map -- leaves in torch allocations.  Its
@@ -246,6 +271,81 @@ def _subscript(v, device) -> torch.Tensor:
         v = torch.as_tensor(a.astype(np.int32).reshape(-1), device=device)
     assert v.dtype == torch.int32 and v.is_cuda
     return v.contiguous().reshape(-1)
+
+
+def _assign_values(value, device, logical=False):
+    """(contiguous 1-D device tensor, its R type) of the new values of a vector subassignment."""
+    if isinstance(value, torch.Tensor):
+        v = value.reshape(-1)
+    else:
+        a = np.asarray(value)
+        if a.dtype != np.bool_ and np.issubdtype(a.dtype, np.integer):
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise SparseArrayError("integer values must fit in 32 bits")
+            a = a.astype(np.int32)
+        elif np.issubdtype(a.dtype, np.floating):
+            a = a.astype(np.float64)
+        v = torch.as_tensor(a.reshape(-1), device=device)
+    if v.dtype == torch.bool:
+        v, logical = v.to(torch.int32), True
+    if v.dtype not in (torch.int32, torch.float64):
+        raise SparseArrayError("the value must be logical, integer (int32) or double (float64)")
+    assert v.is_cuda
+    return v.contiguous(), (REALSXP if v.dtype == torch.float64 else LGLSXP if logical else INTSXP)
+
+
+def subassign_tile() -> int:
+    """Entries of the placed operand per workgroup tile of the placement's fill (svt_dev_subassign_tile).  Needs no GPU."""
+    return int(_hip.load_library().svt_dev_subassign_tile())
+
+
+def subassign_place(nrow, ncol, rows, leaves, value, logical=False, ws=None, tables=None, col_ptr=None):
+    """The placement alone (svt_dev_subassign_place_*_count, then _fill): returns (Y, cover_row, cover_leaf) -- the
+    placed operand of ``x[rows, leaves] <- value`` for an x of nrow x ncol and the two uint8 cover tables (None for a
+    whole axis).  ``ws`` (uint8), ``tables`` (the two uint8 tensors) and ``col_ptr`` (int64[ncol + 1]) may be given."""
+    lib = _lib()
+    dev = value.val.device if isinstance(value, DeviceCSC) else torch.device("cuda")
+    sub = [None if v is None else _subscript(v, dev) for v in (rows, leaves)]
+    idx = [a for v in sub for a in ((None, -1) if v is None else (v.data_ptr(), v.numel()))]
+    if ws is None:
+        ws = torch.empty(lib.svt_dev_subassign_place_ws_bytes(nrow, ncol), dtype=torch.uint8, device=dev)
+    if tables is None:
+        tables = [None if s is None else torch.empty(n, dtype=torch.uint8, device=dev) for s, n in zip(sub, (nrow, ncol))]
+    cp = torch.empty(ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
+    tab = [None if t is None else t.data_ptr() for t in tables]
+    nnz = c_int64(0)
+    if isinstance(value, DeviceCSC):
+        what, dtype, is_lgl = (value.handle,), value.val.dtype, value.Rtype == LGLSXP
+        count, fill = lib.svt_dev_subassign_place_svt_count, lib.svt_dev_subassign_place_svt_fill
+    else:
+        vals, v_Rtype = _assign_values(value, dev, logical)
+        what, dtype, is_lgl = (vals.data_ptr(), vals.numel(), v_Rtype), vals.dtype, v_Rtype == LGLSXP
+        count, fill = lib.svt_dev_subassign_place_vector_count, lib.svt_dev_subassign_place_vector_fill
+    _check(count(nrow, ncol, *idx, *what, cp.data_ptr(), *tab, ctypes.byref(nnz), ws.data_ptr(), ws.numel(), _stream()))
+    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    vv = torch.empty(nnz.value, dtype=dtype, device=dev)
+    _check(fill(nrow, ncol, *idx, *what, cp.data_ptr(), nnz.value, ri.data_ptr(), vv.data_ptr(), ws.data_ptr(), ws.numel(),
+                _stream()))
+    return DeviceCSC(nrow, cp, ri, vv, logical=is_lgl), tables[0], tables[1]
+
+
+def assign_merge(x: DeviceCSC, y: DeviceCSC, cover_row=None, cover_leaf=None, ws=None, col_ptr=None) -> DeviceCSC:
+    """The assign merge alone (svt_dev_assign_merge_count, then _fill): x with the placed operand ``y`` written over
+    it under the two cover tables (uint8 tensors; None: the whole axis)."""
+    lib, dev = _lib(), x.val.device
+    if ws is None:
+        ws = torch.empty(lib.svt_dev_arith_merge_ws_bytes(x.ncol, x.nnz, y.nnz), dtype=torch.uint8, device=dev)
+    cp = torch.empty(x.ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
+    tab = [None if t is None else t.data_ptr() for t in (cover_row, cover_leaf)]
+    nnz = c_int64(0)
+    _check(lib.svt_dev_assign_merge_count(x.handle, y.handle, *tab, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
+                                          _stream()))
+    double = REALSXP in (x.Rtype, y.Rtype)
+    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    vv = torch.empty(nnz.value, dtype=torch.float64 if double else torch.int32, device=dev)
+    _check(lib.svt_dev_assign_merge_fill(x.handle, y.handle, *tab, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), _stream()))
+    return DeviceCSC(x.nrow, cp, ri, vv, logical=x.Rtype == LGLSXP and y.Rtype == LGLSXP)
 
 
 # kinds of svt_dev_arith_map / svt_dev_arith_out_Rtype (include/svt_hip.h)
