@@ -1098,6 +1098,77 @@ int svt_dev_abind(const svt_dev_csc *const *objs, int nobj, int64_t inner, const
 int svt_abind_SVT_begin(const svt_view *const *objs, int nobj, int along, int ans_Rtype, svt_arith_result **res,
 			int64_t *out_nnz);
 
+/* Coercion between a dense array and a resident operand, and nzwhich() (as(a, "SVT_SparseArray") =
+   C_build_SVT_from_Rarray, as.array(x) = C_from_SVT_SparseArray_to_Rarray, nzwhich(x, arr.ind=) = C_nzwhich_SVT,
+   src/SVT_SparseArray_class.c; kernels_coerce.hip).  The dense array is a device buffer in R's layout: column-major,
+   nrow = dim[0] rows, nleaves = prod(dim[1:]) leaves, no padding between the leaves; its type is double, integer or
+   logical (logical is int32).  In this layout CSC order is flat cell order, so the three are streaming passes over
+   tiles of svt_dev_coerce_tile() cells or entries, and what a workgroup does does not depend on how the cells are cut
+   into leaves.  The element rules are stated once, in sparsearray_amd/csrc/svt_coerce_rules.h.
+
+     keep rule (collect_offsets_of_nonzero_* / collect_offsets_of_nonNA_*, src/Rvector_utils.c:556-594)  a cell is stored
+            when it is != 0: -0.0 and integer 0 are dropped; a NaN, NA_real_, +-Inf, a subnormal and NA_integer_ are
+            stored.  Under na_background a cell is stored when it is not NA: R_IsNA for a double (the NaN whose low word
+            is 1954; a plain NaN is stored), NA_integer_ for an integer or a logical; zeros are stored.
+     type   the result's type is the source's or a wider one, logical < integer < double: the same type moves bit for
+            bit, logical -> integer leaves the bits as they are, integer or logical -> double converts the value and
+            NA_integer_ becomes NA_real_ (the rule of abind).  A narrower type answers > 0: the reference coerces with
+            warnings, this library does not.
+
+   Dense -> sparse is a stream compaction over the flat cell index: the position of a kept cell is its rank among the
+   kept cells, out_col_ptr[q] the rank at cell q * nrow.  svt_dev_from_dense_count writes out_col_ptr int64[nleaves + 1]
+   and *out_nnz and synchronises `stream` once; it leaves in `ws` the tile bases and one bit per cell.
+   svt_dev_from_dense_fill is asynchronous, takes the same operands, reads the workspace as the count call left it (the
+   array is not tested again) and writes out_row_idx int32[*out_nnz] and out_val (ans_Rtype).  Every position is a 64-bit
+   prefix sum, none is decided by an atomic, two runs give the same bits.  Status < 0, answered on the host before
+   anything is launched or written (out_col_ptr and *out_nnz keep their contents): a type that is not logical / integer
+   / double, nrow < 0 or nleaves < 0, nrow > 2^31 - 1, nrow * nleaves past int64, a workspace below
+   svt_dev_from_dense_ws_bytes(nrow * nleaves).  Allowed, and never a launch over an empty range: nrow == 0 (every
+   pointer is 0) and nleaves == 0 (out_col_ptr[0] = 0); neither synchronises.  Alignment and workspace: "Workspaces"
+   above.
+
+   svt_dev_from_dense is the composition count -> allocate -> fill over the allocator of svt_dev_subset(): the workspace
+   comes from `alloc` and goes back through `release`; the three result arrays (*out_col_ptr int64[nleaves + 1];
+   *out_row_idx, *out_val of at least one element) are the caller's to release.  Synchronises `stream` once; the fill is
+   still queued on return.
+
+   Sparse -> dense.  svt_dev_to_dense writes EVERY cell of out[A->nrow * A->ncol] (out_Rtype, column-major, aligned to 16
+   bytes): the background -- zero, or NA of out_Rtype when na_background != 0; a parameter, because a wrapped operand
+   carries none -- and the stored values, by the type rule, at q * nrow + row_idx.  Asynchronous, no workspace, no launch
+   when the output has no cells.  A workgroup owns consecutive tiles of output cells, builds each in LDS and writes it
+   out once.  The operand is not trusted: the col_ptr of the leaves a tile touches are checked before any is followed
+   (one that descends or passes A->nnz: the tile gets the background alone), and an entry whose row is outside [0, nrow)
+   or whose cell lies before its tile is never used as an address; either raises the device word *bad (int32, only ever
+   set to nonzero, like `ovflow` of Arith; may be NULL), which stays on the device so that the call remains
+   asynchronous.  (Rows are looked at where the walk over a leaf's entries meets them; with the rows of every leaf
+   ascending, which the layout promises, that is every entry.)
+
+   svt_dev_nzwhich.  `dim`: a host array of ndim (1 .. 8) extents with dim[0] == nrow and prod(dim[1:]) == ncol (< 0
+   otherwise, on the host) and at most 2^31 - 1 leaves (< 0 past that, on the host: a tile numbers the leaves it touches
+   in 32 bits; the entries and the linear indices are 64-bit).  arr_ind == 0: out int64[nnz], the 0-based linear index leaf * nrow + row of every stored
+   entry in storage order (nzwhich_SVT_as_Lindex less the + 1; 64-bit where the reference switches to doubles past
+   INT_MAX).  arr_ind != 0: out int32[nnz * ndim], column-major, the 0-based coordinate tuples of
+   extract_nzcoo_and_nzvals_from_SVT; with nnz > INT_MAX < 0, "too many nonzero elements in SVT_SparseArray object to
+   return their "array coordinates" (n-tuples) in a matrix".  Asynchronous, no launch for nnz == 0.  A stored zero is an
+   entry like any other.  nzvals is the val array and nzcount is nnz: neither needs a call.
+
+   Not offered: host-level entry points and R glue (uploading a dense array costs more than the reference's loop over
+   it: the value is on resident data), narrowing coercions, type<- (C_set_SVT_type), COO -> SVT (it needs a sort),
+   dgCMatrix / CSC conversions, float32, character / raw / complex types, sharding over the device list, a dense array
+   with a leading dimension larger than nrow. */
+int svt_dev_coerce_tile(void);
+size_t svt_dev_from_dense_ws_bytes(int64_t ncells);
+int svt_dev_from_dense_count(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves, int ans_Rtype, int na_background,
+			     int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_from_dense_fill(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves, int ans_Rtype, int na_background,
+			    const int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes,
+			    void *stream);
+int svt_dev_from_dense(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves, int ans_Rtype, int na_background,
+		       svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+		       int32_t **out_row_idx, void **out_val, void *stream);
+int svt_dev_to_dense(const svt_dev_csc *A, int na_background, int out_Rtype, void *out, int *bad, void *stream);
+int svt_dev_nzwhich(const svt_dev_csc *A, int ndim, const int64_t *dim, int arr_ind, void *out, void *stream);
+
 /* Subassignment x[i, j, ...] <- value by an N-index (.subassign_SVT_by_Nindex, R/SparseArray-subassignment.R:114-170;
    C_subassign_SVT_with_short_Rvector, src/SparseArray_subassignment.c:1005-1230): the result is a new operand in the
    device layout with x's extents.  Its type is the wider of x's and the value's, logical < integer < double; a value

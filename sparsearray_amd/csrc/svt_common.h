@@ -360,6 +360,28 @@ size_t abind_ws_bytes(int nobj, int64_t npieces);
 int launch_abind_count(const AbindArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
 int launch_abind_fill(const AbindArgs &a, int32_t *out_row_idx, void *out_val, const void *ws, hipStream_t s);
 
+// Coercions dense array <-> operand and nzwhich (kernels_coerce.hip).  Dense -> sparse over tiles of coerce_tile() cells
+// of the column-major array x[nrow, nleaves], ncells = nrow * nleaves > 0: the count launcher leaves out_col_ptr and, in
+// `ws`, [head: int 0, int64 at byte 8: the kept cells][the tile bases][one bit per cell]; the fill launcher reads `ws` as
+// the count launcher left it.  launch_to_dense writes every cell of out[nrow * ncol] (out aligned to 16 bytes) and
+// raises *bad (may be NULL) for pointers or rows it refuses to follow; launch_nzwhich writes int64[nnz] linear indices or
+// (arr_ind) int32[nnz * ndim] coordinates, column-major.  All asynchronous; none launches over an empty range.
+struct FromDenseArgs {
+	const void *x;
+	int x_Rtype;
+	int64_t nrow, nleaves, ncells;
+	int ans_Rtype;
+	int na_background;
+};
+int coerce_tile(void);
+size_t from_dense_ws_bytes(int64_t ncells);
+int launch_from_dense_count(const FromDenseArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_from_dense_fill(const FromDenseArgs &a, int32_t *out_row_idx, void *out_val, const void *ws, hipStream_t s);
+int launch_to_dense(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype, int64_t nrow, int64_t ncol,
+		    int64_t nnz, int na_background, int out_Rtype, void *out, int *bad, hipStream_t s);
+int launch_nzwhich(const int64_t *col_ptr, const int32_t *row_idx, int64_t nrow, int64_t ncol, int64_t nnz, int ndim,
+		   const int64_t *dim, int arr_ind, void *out, hipStream_t s);
+
 void aperm_route_counts(int64_t *out, int reset);
 size_t aperm_ws_bytes(int64_t nnz, const int64_t *dim, int ndim);
 // aperm, with the boxed driver for the permutations that move the rows past the box limit (read once per call and

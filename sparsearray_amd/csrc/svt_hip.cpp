@@ -8,6 +8,7 @@
 // happens on the host.
 #include "svt_common.h"
 #include "svt_arith_rules.h"
+#include "svt_coerce_rules.h"
 #include <unistd.h>
 
 #include <stdarg.h>
@@ -1999,6 +2000,184 @@ extern "C" int svt_dev_abind(const svt_dev_csc *const *objs, int nobj, int64_t i
 		*out_nrow = c.out_nrow;
 		*out_nleaves = c.a.out_nleaves;
 		return 0;
+	});
+}
+
+// ---- coercions dense array <-> operand, nzwhich (kernels_coerce.hip; C_build_SVT_from_Rarray,
+// C_from_SVT_SparseArray_to_Rarray, C_nzwhich_SVT, src/SVT_SparseArray_class.c) ----
+extern "C" int svt_dev_coerce_tile(void)
+{
+	return coerce_tile();
+}
+extern "C" size_t svt_dev_from_dense_ws_bytes(int64_t ncells)
+{
+	return from_dense_ws_bytes(ncells);
+}
+
+// `from` to `to`: 0 the same type or a wider one; a narrower one is "not supported here", another type an error
+static int coerce_type_check(const char *who, int from_Rtype, int to_Rtype)
+{
+	const int st = svt_rule_coerce_status(from_Rtype, to_Rtype);
+	if (st < 0)
+		return svt_set_error("%s: the types must be logical, integer or double", who);
+	if (st > 0)
+		return svt_set_unsupported("%s: coercion to a narrower type is not supported here", who);
+	return 0;
+}
+
+// One call of dense -> sparse: every check that needs no GPU, then count / fill / their composition.
+struct FromDenseCall {
+	const char *who;
+	FromDenseArgs a;
+
+	int plan(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves, int ans_Rtype, int na_background)
+	{
+		memset(&a, 0, sizeof(a));
+		if (const int rc = coerce_type_check(who, x_Rtype, ans_Rtype))
+			return rc;
+		if (nrow < 0 || nleaves < 0)
+			return svt_set_error("%s: negative extent", who);
+		if (nrow > 0x7FFFFFFFLL)
+			return svt_set_error("%s: more than 2^31 - 1 rows", who);
+		if (nleaves > 0 && nrow > INT64_MAX / nleaves)
+			return svt_set_error("%s: nrow * nleaves overflows 64 bits", who);
+		a.x = x; a.x_Rtype = x_Rtype;
+		a.nrow = nrow; a.nleaves = nleaves; a.ncells = nrow * nleaves;
+		a.ans_Rtype = ans_Rtype; a.na_background = na_background != 0;
+		if (a.ncells > 0 && x == NULL)
+			return svt_set_error("%s: 'x' is NULL", who);
+		return 0;
+	}
+	size_t need() const { return from_dense_ws_bytes(a.ncells); }
+
+	int count(int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		hipStream_t st = (hipStream_t) stream;
+		if (a.ncells == 0) {                                // no rows or no leaves: nothing to count, every pointer is 0
+			HIP_TRY(hipMemsetAsync(out_col_ptr, 0, ((size_t) a.nleaves + 1) * 8, st));
+			*out_nnz = 0;
+			return 0;
+		}
+		if (launch_from_dense_count(a, out_col_ptr, ws, st))
+			return -1;
+		int flag = 0;
+		return subset_read_head(ws, st, &flag, out_nnz);
+	}
+	int fill(int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		return launch_from_dense_fill(a, out_row_idx, out_val, ws, (hipStream_t) stream);
+	}
+	// count -> allocate -> fill over the caller's allocator
+	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+		    int32_t **out_row_idx, void **out_val, void *stream)
+	{
+		if (alloc == NULL || release == NULL)
+			return svt_set_error("%s: an allocator is needed", who);
+		SubsetMem mem = { alloc, release, ctx };
+		SubsetCsc R(mem);
+		SubsetWs ws(mem);
+		int64_t nnz = 0;
+		svt_dev_csc like;
+		memset(&like, 0, sizeof(like));
+		like.Rtype = a.ans_Rtype; like.na_background = a.na_background;
+		if (R.shape(&like, a.nrow, a.nleaves) || ws.get(need()))
+			return -1;
+		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, stream) || R.entries(nnz) || fill(R.c.row_idx, R.c.val, ws.p, ws.n, stream))
+			return -1;
+		*out_nnz = nnz;
+		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
+		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
+		return 0;
+	}
+};
+
+extern "C" int svt_dev_from_dense_count(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves, int ans_Rtype, int na_background,
+					int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		FromDenseCall c = { "svt_dev_from_dense_count" };
+		if (c.plan(x, x_Rtype, nrow, nleaves, ans_Rtype, na_background)) return -1;
+		return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_from_dense_fill(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves, int ans_Rtype, int na_background,
+				       const int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val, const void *ws,
+				       size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile bases in `ws` place the entries)
+	return abi_status([&] {
+		FromDenseCall c = { "svt_dev_from_dense_fill" };
+		if (c.plan(x, x_Rtype, nrow, nleaves, ans_Rtype, na_background)) return -1;
+		return c.fill(out_row_idx, out_val, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_from_dense(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves, int ans_Rtype, int na_background,
+				  svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz,
+				  int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+{
+	return abi_status([&] {
+		FromDenseCall c = { "svt_dev_from_dense" };
+		if (c.plan(x, x_Rtype, nrow, nleaves, ans_Rtype, na_background)) return -1;
+		return c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	});
+}
+
+extern "C" int svt_dev_to_dense(const svt_dev_csc *A, int na_background, int out_Rtype, void *out, int *bad, void *stream)
+{
+	const char *who = "svt_dev_to_dense";
+	return abi_status([&] {
+		if (A == NULL)
+			return svt_set_error("%s: the operand is NULL", who);
+		if (const int rc = coerce_type_check(who, A->Rtype, out_Rtype))
+			return rc;
+		if (A->nrow < 0 || A->ncol < 0 || A->nnz < 0 || A->nrow > 0x7FFFFFFFLL)
+			return svt_set_error("%s: the operand has a negative extent or more than 2^31 - 1 rows", who);
+		if (A->ncol > 0 && A->nrow > INT64_MAX / A->ncol)
+			return svt_set_error("%s: nrow * ncol overflows 64 bits", who);
+		if (A->nrow == 0 || A->ncol == 0)
+			return 0;                                   // an output without cells
+		if (out == NULL || ((uintptr_t) out & 15) != 0)
+			return svt_set_error("%s: 'out' must be aligned to 16 bytes", who);
+		return launch_to_dense(A->col_ptr, A->row_idx, A->val, A->Rtype, A->nrow, A->ncol, A->nnz, na_background != 0,
+				       out_Rtype, out, bad, (hipStream_t) stream);
+	});
+}
+
+extern "C" int svt_dev_nzwhich(const svt_dev_csc *A, int ndim, const int64_t *dim, int arr_ind, void *out, void *stream)
+{
+	const char *who = "svt_dev_nzwhich";
+	return abi_status([&] {
+		if (A == NULL)
+			return svt_set_error("%s: the operand is NULL", who);
+		if (ndim < 1 || ndim > 8 || dim == NULL)
+			return svt_set_error("%s: between 1 and 8 dimensions", who);
+		int64_t leaves = 1;
+		for (int k = 0; k < ndim; k++) {
+			if (dim[k] < 0 || dim[k] > 0x7FFFFFFFLL)
+				return svt_set_error("%s: an extent outside 0 .. 2^31 - 1", who);
+			if (k > 0) {
+				if (dim[k] != 0 && leaves > INT64_MAX / dim[k])
+					return svt_set_error("%s: 'dim' does not match the operand's rows and leaves", who);
+				leaves *= dim[k];
+			}
+		}
+		if (dim[0] != A->nrow || leaves != A->ncol)
+			return svt_set_error("%s: 'dim' does not match the operand's rows and leaves", who);
+		if (A->ncol > 0x7FFFFFFFLL)                         // (a tile's leaves are numbered in 32 bits)
+			return svt_set_error("%s: more than 2^31 - 1 leaves", who);
+		if (A->nnz < 0 || (A->nnz > 0 && (A->nrow == 0 || A->ncol == 0)))
+			return svt_set_error("%s: nonzeros in an operand without cells", who);
+		if (arr_ind && A->nnz > 0x7FFFFFFFLL)
+			return svt_set_error("too many nonzero elements in SVT_SparseArray object to return their \"array coordinates\" "
+					     "(n-tuples) in a matrix");
+		if (A->nnz > 0 && out == NULL)
+			return svt_set_error("%s: 'out' is NULL", who);
+		return launch_nzwhich(A->col_ptr, A->row_idx, A->nrow, A->ncol, A->nnz, ndim, dim, arr_ind != 0, out,
+				      (hipStream_t) stream);
 	});
 }
 

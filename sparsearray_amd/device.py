@@ -55,6 +55,89 @@ class DeviceCSC:
                    torch.as_tensor(np.asarray(row_idx, np.int32), device=device),
                    torch.as_tensor(np.asarray(val), device=device))
 
+    @classmethod
+    def from_dense(cls, a: torch.Tensor, ans_type=None, na_background=False, logical=False) -> "DeviceCSC":
+        """The operand of a dense array that is on the device already (include/svt_hip.h, svt_dev_from_dense): ``a`` a
+        CUDA tensor of dtype float64 or int32 (integer; logical with ``logical=True``) or bool (logical, through
+        ``.to(torch.int32)``) with at least one dimension; the result has nrow = a.shape[0] and ncol = prod(a.shape[1:]).
+        A cell is stored when it is != 0, or, under ``na_background``, when it is not NA.  ``ans_type``: "logical",
+        "integer" or "double", the array's type (the default) or a wider one; a narrower one raises
+        SparseArrayUnsupported.  The memory layout decides the route and torch computes nothing: a column-major tensor
+        (``a.permute(*reversed(range(a.ndim))).is_contiguous()``, every 1-D tensor) is read in place; a C-contiguous one
+        is sparsified as the array of the reversed shape that it is in memory, then transposed by ``t()`` (2-D) or
+        ``aperm`` with the reversing permutation; any other layout raises SparseArrayError.  Every array is a torch
+        allocation on the current stream."""
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise SparseArrayError("from_dense() takes a CUDA tensor")
+        if a.dtype == torch.bool:
+            a, logical = a.to(torch.int32), True
+        if a.dtype not in (torch.int32, torch.float64):
+            raise SparseArrayError("the array must be logical (bool), integer (int32) or double (float64)")
+        if a.ndim < 1:
+            raise SparseArrayError("the array needs at least one dimension")
+        x_Rtype = REALSXP if a.dtype == torch.float64 else LGLSXP if logical else INTSXP
+        ans_Rtype = x_Rtype if ans_type is None else _rtype_of(ans_type)
+        shape, nd = tuple(int(d) for d in a.shape), a.ndim
+        if a.permute(*reversed(range(nd))).is_contiguous():
+            return cls._sparsify(a, shape, x_Rtype, ans_Rtype, na_background)
+        if not a.is_contiguous():
+            raise SparseArrayError("the array must be column-major or C-contiguous")
+        R = cls._sparsify(a, shape[::-1], x_Rtype, ans_Rtype, na_background)
+        return R.t() if nd == 2 else R.aperm(shape[::-1], list(range(nd, 0, -1)))[0]
+
+    @classmethod
+    def _sparsify(cls, a, dim, x_Rtype, ans_Rtype, na_background):
+        """svt_dev_from_dense on the memory of ``a`` read as the column-major array of extents ``dim``"""
+        nrow, nleaves = dim[0], int(np.prod(dim[1:], dtype=np.int64))
+        mem = _TorchBlocks(a.device)
+        nnz = c_int64(0)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(_lib().svt_dev_from_dense(a.data_ptr(), x_Rtype, nrow, nleaves, ans_Rtype, int(bool(na_background)),
+                                         mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz),
+                                         *[ctypes.byref(o) for o in out], _stream()))
+        dtype = torch.float64 if ans_Rtype == REALSXP else torch.int32
+        return cls(nrow, *mem.csc(out, nleaves, int(nnz.value), dtype), logical=ans_Rtype == LGLSXP)
+
+    def _dim(self, dim):
+        dim = (self.nrow, self.ncol) if dim is None else tuple(int(d) for d in dim)
+        if not dim or dim[0] != self.nrow or int(np.prod(dim[1:], dtype=np.int64)) != self.ncol:
+            raise SparseArrayError("'dim' does not match the operand's rows and leaves")
+        return dim
+
+    def to_dense(self, dim=None, out_type=None, na_background=False, out=None) -> torch.Tensor:
+        """The dense array of the operand, on the device (include/svt_hip.h, svt_dev_to_dense): a tensor of shape
+        ``dim`` (default (nrow, ncol)) that is a zero-copy view of the column-major buffer the kernel writes -- every
+        cell of it: zero, or NA under ``na_background``, where nothing is stored.  ``out_type``: the operand's type (the
+        default) or a wider one.  ``out``: the caller's flat contiguous buffer of nrow * ncol elements.  The result's
+        ``bad`` attribute is a device int32 word, nonzero once the kernel has run over an operand whose pointers or rows
+        it refused to follow; it is left on the device so that the call stays asynchronous."""
+        dim = self._dim(dim)
+        out_Rtype = self.Rtype if out_type is None else _rtype_of(out_type)
+        dtype = torch.float64 if out_Rtype == REALSXP else torch.int32
+        n, dev = self.nrow * self.ncol, self.val.device
+        if out is None:
+            out = torch.empty(n, dtype=dtype, device=dev)
+        if not (isinstance(out, torch.Tensor) and out.dtype == dtype and out.is_cuda and out.ndim == 1 and out.is_contiguous()
+                and out.numel() == n):
+            raise SparseArrayError(f"'out' must be a flat contiguous CUDA tensor of {n} elements of {dtype}")
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _check(_lib().svt_dev_to_dense(self.handle, int(bool(na_background)), out_Rtype, out.data_ptr(), bad.data_ptr(),
+                                       _stream()))
+        res = out.view(*reversed(dim)).permute(*reversed(range(len(dim))))
+        res.bad = bad
+        return res
+
+    def nzwhich(self, dim=None, arr_ind=False) -> torch.Tensor:
+        """nzwhich(x, arr.ind=) on the device (include/svt_hip.h, svt_dev_nzwhich), 0-based: an int64 tensor of nnz
+        linear indices into the column-major array of extents ``dim`` (default (nrow, ncol)), in storage order, or
+        (``arr_ind``) an int32 tensor of shape (nnz, ndim) of coordinates, a view of the column-major buffer.  With
+        ``val`` it is the COO form of the operand."""
+        dim = self._dim(dim)
+        nd, dev = len(dim), self.val.device
+        buf = torch.empty(self.nnz * nd if arr_ind else self.nnz, dtype=torch.int32 if arr_ind else torch.int64, device=dev)
+        _check(_lib().svt_dev_nzwhich(self.handle, nd, (c_int64 * nd)(*dim), int(bool(arr_ind)), buf.data_ptr(), _stream()))
+        return buf.view(nd, self.nnz).t() if arr_ind else buf
+
     @property
     def handle(self):
         return c_void_p(self._h)
@@ -402,6 +485,19 @@ def subset_rows(A: DeviceCSC, rows, ws=None) -> DeviceCSC:
     """The row filter alone (svt_dev_subset_rows_count, then _fill): x[rows, ] for a strictly increasing 0-based
     ``rows``; any other subscript in range raises SparseArrayUnsupported (take ``A.subset(rows=...)``)."""
     return _subset_two_calls(A, rows, ws, rows=True)
+
+
+def _rtype_of(type_name) -> int:
+    try:
+        return {"logical": LGLSXP, "integer": INTSXP, "double": REALSXP}[type_name]
+    except (KeyError, TypeError):
+        raise SparseArrayError("invalid requested type") from None
+
+
+def coerce_tile() -> int:
+    """Cells (dense <-> sparse) or entries (nzwhich) per workgroup tile of the coercion kernels (svt_dev_coerce_tile).
+    Needs no GPU."""
+    return int(_hip.load_library().svt_dev_coerce_tile())
 
 
 def abind_tile() -> int:
