@@ -838,8 +838,8 @@ int svt_transpose_2D_SVT(const svt_view *x, int64_t *out_col_ptr,
 /* x[i, j] of a 2-D operand by an N-index (C_subset_SVT_by_Nindex, src/SparseArray_subsetting.c:223-297, 759-843):
    result cell (p, q) is x[i[p], j[q]]; indices in any order, any number of times; an entry is stored in the result
    exactly when its source entry is stored, and its value is copied bit for bit; offsets ascend inside every result
-   column; Rtype and na_background pass through.  Not offered: L-index / M-index subsetting, N-d operands.  (Subassignment
-   x[i, j] <- value: "Subassignment" at the end of this header.)
+   column; Rtype and na_background pass through.  Not offered: N-d operands.  (Subassignment x[i, j] <- value, and
+   subsetting and subassignment by an L-index or M-index: at the end of this header.)
 
    Device level, two primitives over tiles of svt_dev_subset_tile() nonzeros (kernels_subset.hip), each a `_count`
    call that writes the result's column pointers and returns its nonzero count, and a `_fill` call into arrays the
@@ -1210,7 +1210,7 @@ int svt_dev_nzwhich(const svt_dev_csc *A, int ndim, const int64_t *dim, int arr_
    na_background and, SVT form, for rows in range that are not strictly increasing or a repeated leaf.  On a non-zero
    status nothing is written outside `ws`.  Alignment and workspace: "Workspaces" above.
 
-   Not offered: L-index and M-index subassignment, a dense array value, NaArray operands, the SVT form with rows out of
+   Not offered: a dense array value, NaArray operands, the SVT form with rows out of
    order or repeated leaves, character / raw / complex types, sharding over the device list, an entry in the R glue
    (INTEGRATION.md describes the call). */
 int svt_dev_subassign_tile(void);
@@ -1262,6 +1262,93 @@ int svt_subassign_SVT_vector_begin(const svt_view *x, const int *const *index, c
 				   int64_t nvals, int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
 int svt_subassign_SVT_SVT_begin(const svt_view *x, const int *const *index, const int64_t *index_len, const svt_view *v,
 				svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
+
+/* Subsetting and subassignment by a linear index (L-index) or a matrix subscript (M-index): x[which(...)],
+   x[cbind(i, j)], x[x > 10] <- 10 (.subset_SVT_by_Lindex / _by_Mindex, R/SparseArray-subsetting.R;
+   .subassign_SVT_by_Lindex / _by_Mindex, R/SparseArray-subassignment.R; C_subset_SVT_by_Lindex,
+   C_subassign_SVT_by_Lindex and subassign_leaf_by_OPBuf in the reference's src/).  An L-index over an N-d array is an
+   L-index over the (nrow x nleaves) device layout: cell L is row L % nrow of leaf L / nrow; an M-index row is the cell
+   sum(m_a * prod(dim[0 .. a-1])).  One device function turns either form into a checked cell number; no index is used as
+   an address before that (kernels_lindex.hip).
+
+   Device level.  An L-index is a device int64[K], 0-based, INT64_MIN for NA -- what svt_dev_nzwhich writes.  An M-index
+   is a device int32[K * ndim], column-major and 0-based -- what svt_dev_nzwhich writes with arr_ind -- with `dim` a host
+   array of ndim (1 .. 8) extents, dim[0] == nrow and prod(dim[1:]) == ncol (< 0 otherwise, on the host).  Where one
+   function takes both forms, ndim == 0 says L-index (`dim` is then not read).
+
+   Gather.  svt_dev_subset_lindex / _mindex write out[K] of A's type, one value per index in index order: the stored
+   value bit for bit (a stored zero, -0.0 or a NaN payload as it is), else the background (0, or NA when
+   A->na_background), and NA for an NA L-index.  One lookup per index: two col_ptr reads, then a binary search of row_idx
+   between them.  Asynchronous, no workspace, nothing launched for K == 0.  `bad` is a device int32 word the caller
+   zeroed, in the convention of svt_dev_to_dense: a first kernel checks every index and raises bit 1 for one outside the
+   array (an NA_integer_ coordinate of an M-index included), and the gather, which reads the word, then writes nothing;
+   bit 2: a col_ptr pair that descends or leaves [0, nnz] was not followed (that index reads the background).
+
+   Subassignment.  The value is brought to the wider type of the two (logical < integer < double, NA_integer_ becomes
+   NA_real_); positions apply in order, so the LAST occurrence of a cell wins; a cell whose final value is zero (-0.0 and
+   integer 0 too; a NaN or NA is stored) has no entry afterwards; a cell that no index reaches keeps x's entry bit for
+   bit, a stored zero included (the N-index form above rebuilds a selected leaf; this form does not).  It is a merge:
+     placement  svt_dev_subassign_place_lindex_count / _fill build the placed operand Y with x's extents: one entry per
+                DISTINCT assigned cell holding the cell's last value vals[p % nvals], zeros included -- a zero in Y is the
+                deletion mark.  The count call checks every index (one outside the array, an NA included: < 0, and nothing
+                was written outside `ws`), notes whether the cells are strictly increasing (the output of nzwhich() /
+                which() always is) and synchronises `stream` once to learn both.  Sorted route: position p is entry p of
+                Y, no sort, no de-duplication, *y_nnz = K without a second synchronisation.  Unsorted route: (cell, p)
+                through the library's stable radix sort on the bits of nrow * ncol - 1 (svt_dev_lindex_sort_passes()
+                passes of 8 bits), a flag per run end, a 64-bit scan; one more synchronisation for *y_nnz.  Either way
+                y_col_ptr int64[ncol + 1] comes from one binary search per leaf.  The fill call is asynchronous and
+                reads `ws` as the count call left it.  No atomic decides a position; two runs give the same bits.
+                ws: svt_dev_subassign_place_lindex_ws_bytes(K, ncol), 44 bytes per index plus the sort's tables.
+     merge      svt_dev_assign_cells_merge_count / _fill: the merge of svt_dev_arith_merge_* under the rule
+                svt_rule_assign_cells -- at a place stored in y the result is y's value widened, kept iff it is not zero;
+                at a place stored in x alone x's value widened, always kept.  No cover tables.  ws:
+                svt_dev_arith_merge_ws_bytes(ncol, nnz(x), nnz(y)).
+   svt_dev_subassign_lindex / _mindex are the composition over the allocator of svt_dev_subset(), like
+   svt_dev_subassign_vector; K == 0 is the widening copy of x.  Status < 0: an index outside the array or NA, nvals < 1
+   ("replacement has length zero"), a workspace smaller than its _ws_bytes, a type outside logical / integer / double;
+   > 0: an operand with na_background, K > 2^31 - 1 (the sort's payload is 32 bits).  On a non-zero status nothing is
+   written outside `ws`.  svt_dev_lindex_route_counts: counts[0] sorted, [1] unsorted placements of this process, counted
+   in the count call; reset != 0 zeroes them.
+
+   Not offered: NaArray subassignment, COO operands, character / raw / complex types, K >= 2^31 for the subassignment,
+   sharding over the device list, an entry in the R glue. */
+int svt_dev_subset_lindex(const svt_dev_csc *A, const int64_t *lindex, int64_t K, void *out, int *bad, void *stream);
+int svt_dev_subset_mindex(const svt_dev_csc *A, const int32_t *mindex, int64_t K, int ndim, const int64_t *dim, void *out, int *bad,
+			  void *stream);
+size_t svt_dev_subassign_place_lindex_ws_bytes(int64_t K, int64_t ncol);
+int svt_dev_lindex_sort_passes(int64_t nrow, int64_t ncol);
+int svt_dev_subassign_place_lindex_count(int64_t nrow, int64_t ncol, const void *index, int64_t K, int ndim, const int64_t *dim,
+					 const void *vals, int64_t nvals, int v_Rtype, int64_t *y_col_ptr, int64_t *y_nnz, void *ws,
+					 size_t ws_bytes, void *stream);
+int svt_dev_subassign_place_lindex_fill(int64_t nrow, int64_t ncol, const void *index, int64_t K, int ndim, const int64_t *dim,
+					const void *vals, int64_t nvals, int v_Rtype, const int64_t *y_col_ptr, int64_t y_nnz,
+					int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_assign_cells_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int64_t *out_col_ptr, int64_t *out_nnz, void *ws,
+				     size_t ws_bytes, void *stream);
+int svt_dev_assign_cells_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, const int64_t *out_col_ptr, int32_t *out_row_idx,
+				    void *out_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_subassign_lindex(const svt_dev_csc *x, const int64_t *lindex, int64_t K, const void *vals, int64_t nvals, int v_Rtype,
+			     svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz,
+			     int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream);
+int svt_dev_subassign_mindex(const svt_dev_csc *x, const int32_t *mindex, int64_t K, int ndim, const int64_t *dim, const void *vals,
+			     int64_t nvals, int v_Rtype, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype,
+			     int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream);
+void svt_dev_lindex_route_counts(int64_t counts[2], int reset);
+
+/* Host level.  `lindex`: K 1-based int64 cell numbers, INT64_MIN for NA; `mindex`: a K x x->ndim int matrix,
+   column-major, 1-based, NA_INTEGER for NA.  Every index is checked on the host before anything is uploaded (< 0:
+   "linear index (L-index) contains out-of-bound indices", "linear index (L-index) contains NAs" -- subassignment only; in
+   a subsetting L-index an NA gives NA --, "matrix subscript (M-index) contains out-of-bound indices", "matrix subscript
+   (M-index) contains NAs").  The subsetting calls upload x (through the resident cache when it is on), gather and
+   download `out`: K values of x's type.  The subassignment calls leave the result on the device like
+   svt_subassign_SVT_vector_begin, and svt_Arith_SVT_end ends them.  First device of the list; not sharded.  NaArray
+   subassignment and character / raw / complex operands: > 0. */
+int svt_subset_SVT_by_Lindex(const svt_view *x, const int64_t *lindex, int64_t K, void *out);
+int svt_subset_SVT_by_Mindex(const svt_view *x, const int *mindex, int64_t K, void *out);
+int svt_subassign_SVT_by_Lindex_begin(const svt_view *x, const int64_t *lindex, int64_t K, const void *vals, int64_t nvals,
+				      int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
+int svt_subassign_SVT_by_Mindex_begin(const svt_view *x, const int *mindex, int64_t K, const void *vals, int64_t nvals, int v_Rtype,
+				      svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
 
 #ifdef __cplusplus
 }

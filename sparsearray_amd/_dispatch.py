@@ -461,8 +461,13 @@ class CAbiDispatcher:
         buf = [None if v is None else (v if v.size else np.zeros(1, np.int32)) for v in sub]
         index = (c_void_p * x.ndim)(*[None if b is None else b.ctypes.data for b in buf])
         index_len = np.array([-1 if v is None else v.size for v in sub], dtype=np.int64)
+        return self._assigned(begin, x, (index, index_len) + tuple(args))
+
+    def _assigned(self, begin, x, args):
+        """The SVT_SparseArray of x's dim and dimnames that ``svt_<begin>(x, *args, &res, &Rtype, &nnz)`` leaves on the
+        device, copied out by Arith_SVT_end."""
         res, rt, nnz = c_void_p(0), c_int(0), ctypes.c_int64(0)
-        self._run(begin, x, index, index_len, *args, byref(res), byref(rt), byref(nnz))
+        self._run(begin, x, *args, byref(res), byref(rt), byref(nnz))
         n = int(nnz.value)
         type_ = {LGLSXP: "logical", INTSXP: "integer", REALSXP: "double"}[rt.value]
         cp = np.zeros(int(np.prod(x.dim[1:], dtype=np.int64)) + 1, dtype=np.int64)
@@ -489,6 +494,52 @@ class CAbiDispatcher:
         """``v``: an SVT_SparseArray with the dims of the selection; rows strictly increasing, leaves without repeats
         (anything else in range: SparseArrayUnsupported)."""
         return self._subassign("subassign_SVT_SVT_begin", x, Nindex, (v,))
+
+    # x[Lindex], x[Mindex] and their subassignments (src/SparseArray_subsetting.c, C_subset_SVT_by_Lindex / _by_Mindex;
+    # src/SparseArray_subassignment.c, C_subassign_SVT_by_Lindex / _by_Mindex; include/svt_hip.h; HIP library only) -----
+    @staticmethod
+    def _index_buffer(index, dtype):
+        """(the contiguous index, the buffer handed over: an empty index goes over as one unread element)"""
+        index = np.ascontiguousarray(index, dtype=dtype)
+        return index, (index if index.size else np.zeros(1, dtype))
+
+    def C_subset_SVT_by_Lindex(self, x: SVT_SparseArray, Lindex: np.ndarray):
+        """``Lindex``: 1-based int64, INT64_MIN for NA.  Returns the vector of x's type, one value per index."""
+        L, buf = self._index_buffer(np.reshape(Lindex, -1), np.int64)
+        out = np.zeros(max(L.size, 1), dtype=x.np_dtype)
+        self._run("subset_SVT_by_Lindex", x, buf, int(L.size), out)
+        return out[:L.size]
+
+    def C_subset_SVT_by_Mindex(self, x: SVT_SparseArray, Mindex: np.ndarray):
+        """``Mindex``: a K x ndim int32 matrix, 1-based, NA_integer_ for NA."""
+        M = np.asarray(Mindex, dtype=np.int32)
+        K = int(M.shape[0])
+        _, buf = self._index_buffer(M.reshape(-1, order="F"), np.int32)
+        out = np.zeros(max(K, 1), dtype=x.np_dtype)
+        self._run("subset_SVT_by_Mindex", x, buf, K, out)
+        return out[:K]
+
+    @staticmethod
+    def _assigned_value(value):
+        value = np.ascontiguousarray(value).reshape(-1)
+        if value.dtype == np.bool_:
+            value, v_type = value.astype(np.int32), "logical"
+        else:
+            v_type = r_type_of(value)
+        if v_type not in _RT:
+            raise SparseArrayError("the supplied value must be of type \"logical\", \"integer\" or \"double\"")
+        return value, int(value.size), _RT[v_type]
+
+    def C_subassign_SVT_by_Lindex(self, x: SVT_SparseArray, Lindex: np.ndarray, value: np.ndarray):
+        """``value``: a non-empty 1-D array, bool (logical), int32 (integer) or float64 (double), recycled over the
+        index."""
+        L, buf = self._index_buffer(np.reshape(Lindex, -1), np.int64)
+        return self._assigned("subassign_SVT_by_Lindex_begin", x, (buf, int(L.size)) + self._assigned_value(value))
+
+    def C_subassign_SVT_by_Mindex(self, x: SVT_SparseArray, Mindex: np.ndarray, value: np.ndarray):
+        M = np.asarray(Mindex, dtype=np.int32)
+        _, buf = self._index_buffer(M.reshape(-1, order="F"), np.int32)
+        return self._assigned("subassign_SVT_by_Mindex_begin", x, (buf, int(M.shape[0])) + self._assigned_value(value))
 
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""

@@ -688,6 +688,185 @@ class Session:
         return self.SparseArray_Call("C_subassign_SVT_with_SVT", x, index, value)
 
     # ------------------------------------------------------------------
+    # x[Lindex], x[Mindex], x[Lindex] <- value, x[Mindex] <- value  (.subset_SVT_by_Lindex / _by_Mindex,
+    # R/SparseArray-subsetting.R:28-71; .subassign_SVT_by_Lindex / _by_Mindex, R/SparseArray-subassignment.R:7-77)
+    # ------------------------------------------------------------------
+    _INT64_NA = np.iinfo(np.int64).min
+
+    @staticmethod
+    def _numeric_index(index, what):
+        if isinstance(index, (str, bytes)):
+            raise SparseArrayError(f"'{what}' must be an integer or numeric vector")
+        try:
+            a = np.asarray(index)
+        except (TypeError, ValueError):
+            raise SparseArrayError(f"'{what}' must be an integer or numeric vector")
+        if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+            raise SparseArrayError(f"'{what}' must be an integer or numeric vector")
+        return a
+
+    @classmethod
+    def _index0(cls, a, extent):
+        """extract_long_idx0 (src/OPBufTree.h:131-160) on every element of the numeric array ``a``: the 0-based index
+        as int64 -- a double is truncated toward zero after the - 1 --, with masks of the NAs (NA_integer_ of an int32
+        array, a NaN of a double one) and of the elements outside 1..extent."""
+        if np.issubdtype(a.dtype, np.floating):
+            na = np.isnan(a)
+            i0 = np.where(na, 0.0, a.astype(np.float64) - 1.0)
+            bad = ~na & ((i0 < 0.0) | (i0 >= float(extent)))
+            i0 = np.where(bad, 0.0, i0).astype(np.int64)
+        else:
+            na = (a == NA_integer) if a.dtype == np.int32 else np.zeros(a.shape, dtype=bool)
+            i0 = a.astype(np.int64) - 1
+            bad = ~na & ((i0 < 0) | (i0 >= extent))
+        return i0, na, bad
+
+    def _check_Lindex(self, Lindex, ncells, na_ok):
+        """A linear index as the 1-based int64 array the entry points take, INT64_MIN for NA."""
+        a = self._numeric_index(Lindex, "Lindex")
+        if a.ndim > 1:
+            raise SparseArrayError("'Lindex' must be an integer or numeric vector")
+        i0, na, bad = self._index0(a.reshape(-1), ncells)
+        # element by element, as the reference meets them: the first offender decides
+        first = np.flatnonzero(bad if na_ok else (bad | na))
+        if first.size:
+            if bad[first[0]]:
+                raise SparseArrayError("linear index (L-index) contains out-of-bound indices")
+            # (the reference has no text of its own here: _bad_Lindex_error falls through to its "internal error")
+            raise SparseArrayError("linear index (L-index) contains NAs")
+        return np.where(na, self._INT64_NA, i0 + 1).astype(np.int64)
+
+    def _check_Mindex(self, x, Mindex):
+        """A numeric matrix subscript as the 1-based K x ndim int32 matrix the entry points take."""
+        a = self._numeric_index(Mindex, "Mindex")
+        if a.ndim != 2:
+            raise SparseArrayError("'Mindex' must be a matrix")
+        if a.shape[1] != x.ndim:
+            raise SparseArrayError("ncol(Mindex) != length(dim(x))")
+        out = np.zeros(a.shape, dtype=np.int32)
+        nas, bads = [], []
+        for k, d in enumerate(x.dim):
+            i0, na, bad = self._index0(a[:, k], d)
+            out[:, k] = i0 + 1
+            nas.append(na)
+            bads.append(bad)
+        # row by row, a coordinate at a time, as build_OPBufTree_from_Mindex meets them: the first offender decides
+        na, bad = np.stack(nas, axis=1), np.stack(bads, axis=1)
+        first = np.flatnonzero((na | bad).reshape(-1))
+        if first.size:
+            if na.reshape(-1)[first[0]]:
+                raise SparseArrayError("matrix subscript (M-index) contains NAs")
+            raise SparseArrayError("matrix subscript (M-index) contains out-of-bound indices")
+        return out
+
+    @staticmethod
+    def _background_vector(x, n):
+        out = np.zeros(n, dtype=x.np_dtype)
+        if x.na_background:
+            out[:] = NA_real if x.type == "double" else NA_integer
+        return out
+
+    def _check_Lindex_operand(self, x, what):
+        if x.type not in ("logical", "integer", "double"):
+            raise SparseArrayUnsupported(f"{what} of an object of type \"{x.type}\" is not offered by this library")
+
+    def subset_by_Lindex(self, x, Lindex):
+        """``x[Lindex]`` by a linear index, 1-based over the column-major array (what ``which()`` gives): the vector of
+        x's type with one value per index, in index order; a cell without an entry reads 0 (NA for an NaArray), an NA
+        index reads NA.  A double index is truncated toward zero after the - 1."""
+        self._check_Lindex_operand(x, "subsetting by an L-index")
+        L = self._check_Lindex(Lindex, int(np.prod(x.dim, dtype=object)), na_ok=True)
+        self._optional_entry("C_subset_SVT_by_Lindex", "subset_SVT_by_Lindex")
+        return self.SparseArray_Call("C_subset_SVT_by_Lindex", x, L)
+
+    def subset_by_Mindex(self, x, Mindex):
+        """``x[Mindex]`` by a matrix subscript: a K x ndim numeric matrix of 1-based coordinates.  An NA or an
+        out-of-bound coordinate is an error; a character matrix is refused as the reference refuses it."""
+        try:
+            kind = np.asarray(Mindex).dtype.kind
+        except (TypeError, ValueError):
+            kind = "O"
+        if kind in "USO" or isinstance(Mindex, (str, bytes)):
+            if kind not in "US":
+                raise SparseArrayError("invalid matrix subscript type \"list\"")
+            if x.dimnames is None:
+                raise SparseArrayError("SparseArray object to subset has no dimnames")
+            raise SparseArrayError("subsetting a SparseArray object by a character matrix is not supported at the moment")
+        self._check_Lindex_operand(x, "subsetting by an M-index")
+        a = self._numeric_index(Mindex, "Mindex")
+        if a.ndim == 2 and a.shape[1] == x.ndim and x.ndim > 1 and x.svt_is_null:
+            # C_subset_SVT_by_Mindex (src/SparseArray_subsetting.c:693-696): an empty N-d array answers before it looks
+            return self._background_vector(x, a.shape[0])
+        M = self._check_Mindex(x, Mindex)
+        self._optional_entry("C_subset_SVT_by_Mindex", "subset_SVT_by_Mindex")
+        return self.SparseArray_Call("C_subset_SVT_by_Mindex", x, M)
+
+    @staticmethod
+    def _vector_value(value):
+        """adjust_left_type's first check: the value as an array, refused unless it is a vector"""
+        try:
+            a = None if isinstance(value, SVT_SparseArray) else np.asarray(value)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.dtype == object or a.ndim > 1:
+            raise SparseArrayError("the supplied value must be a vector for this form of subassignment to an "
+                                   "SVT_SparseArray object")
+        return a
+
+    def _subassign_by_index(self, x, a, K):
+        """The rest of adjust_left_type, and .normalize_right_value, for the vector ``a`` and an index of K elements:
+        (x in the wider type, the value in that type), or (x, None) for an empty index."""
+        v_type = self._scalar_class_type(a)[1]
+        if x.na_background:
+            raise SparseArrayUnsupported("subassignment of NaArray objects is not offered by this library")
+        if x.type not in ("logical", "integer", "double") or v_type not in ("logical", "integer", "double"):
+            raise SparseArrayUnsupported(f"subassignment with types \"{x.type}\" and \"{v_type}\" is not offered by this "
+                                         "library")
+        new_type = _common_type(x.type, v_type)
+        x = self._set_type(x, new_type)
+        if K == 0:
+            return x, None
+        a = a.reshape(-1)
+        if a.size == 0:
+            raise SparseArrayError("replacement has length zero")
+        if not (a.size == 1 or a.size == K or (a.size < K and K % a.size == 0)):
+            # (the reference defers to S4Vectors:::recycleVector, whose rules for the other lengths are not in its tree)
+            raise SparseArrayUnsupported("subassignment with a value whose length is not 1, not the index's and does not "
+                                         "divide it is not offered by this library")
+        if new_type == "double":
+            v = _dense_to_double(a.astype(np.int32)) if v_type != "double" else a.astype(np.float64)
+        else:
+            v = a.astype(np.bool_ if new_type == "logical" and a.dtype == np.bool_ else np.int32)
+        return x, v
+
+    def subassign_by_Lindex(self, x, Lindex, value):
+        """``x[Lindex] <- value`` by a linear index, 1-based: positions apply in order (the last occurrence of a cell
+        wins), a cell whose final value is zero has no entry afterwards, a cell no index reaches keeps its entry as it
+        is.  ``value``: a scalar or a vector of the index's length or of a length that divides it.  Returns a new
+        object of the wider type of the two.  An NA index is an error here."""
+        value = self._vector_value(value)
+        a = self._numeric_index(Lindex, "Lindex")
+        x, v = self._subassign_by_index(x, value, int(a.size))
+        if v is None:
+            return x
+        L = self._check_Lindex(a, int(np.prod(x.dim, dtype=object)), na_ok=False)
+        self._optional_entry("C_subassign_SVT_by_Lindex", "subassign_SVT_by_Lindex_begin")
+        return self.SparseArray_Call("C_subassign_SVT_by_Lindex", x, L, v)
+
+    def subassign_by_Mindex(self, x, Mindex, value):
+        """``x[Mindex] <- value`` by a K x ndim numeric matrix of 1-based coordinates; the rest as subassign_by_Lindex."""
+        value = self._vector_value(value)
+        a = self._numeric_index(Mindex, "Mindex")
+        if a.ndim != 2:
+            raise SparseArrayError("'Mindex' must be a matrix")
+        x, v = self._subassign_by_index(x, value, int(a.shape[0]))
+        if v is None:
+            return x
+        M = self._check_Mindex(x, a)
+        self._optional_entry("C_subassign_SVT_by_Mindex", "subassign_SVT_by_Mindex_begin")
+        return self.SparseArray_Call("C_subassign_SVT_by_Mindex", x, M, v)
+
+    # ------------------------------------------------------------------
     # abind, cbind, rbind  (.abind_SparseArray_objects, R/SparseArray-abind.R:53-99)
     # ------------------------------------------------------------------
     @staticmethod

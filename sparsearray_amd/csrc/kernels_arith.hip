@@ -35,6 +35,9 @@
 // either side is and int32 else, and no overflow is raised.  It adds nothing to the LDS: the leaf of an x entry is found
 // again from the x part's column range (sh.rng), not kept next to its key.
 //
+// Subassignment by an L-index or M-index is a fifth (ARI_RULE_ASSIGN_CELLS, svt_rule_assign_cells): y is the placed
+// operand kernels_lindex.hip builds, a zero in it deletes, an x entry alone always stays; it reads no table and no opcode.
+//
 // LDS: keys 8 * (2048 + 2), sources 4 * 2048, ballots and chunk prefixes 0.4 KB: 24.5 KB for the merge (6 workgroups
 // of a CU's 160 KB), 0.4 KB for the map.
 #include "svt_common.h"
@@ -371,6 +374,9 @@ __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const Ar
 			}
 			keep[it] = svt_rule_assign(in_y, xv, yv, rc, lc, &r[it]);
 			continue;
+		} else if constexpr (RULE == ARI_RULE_ASSIGN_CELLS) {
+			keep[it] = svt_rule_assign_cells((s & (ARI_FROM_Y | ARI_PAIRED)) != 0u, xv, yv, &r[it]);
+			continue;
 		} else if constexpr (RULE == ARI_RULE_COMPARE)
 			r[it] = svt_rule_compare(op, svt_rule_as_double(xv), svt_rule_as_double(yv));
 		else if constexpr (RULE == ARI_RULE_LOGIC)
@@ -549,13 +555,14 @@ static inline void arith_merge_by_operands(const ArithMergeArgs &a, F &&f, R rul
 	else if (a.y_Rtype == SVT_REALSXP) f((const int32_t *) a.x_val, (const double *) a.y_val, rule);
 	else f((const int32_t *) a.x_val, (const int32_t *) a.y_val, rule);
 }
-// and by the rule: Arith, Compare and the subassignment rule for the four type pairs, Logic for int32 x int32 alone
+// and by the rule: Arith, Compare and the two subassignment rules for the four type pairs, Logic for int32 x int32 alone
 template <class F>
 static inline int arith_merge_by_types(const ArithMergeArgs &a, F &&f)
 {
 	if (a.rule == ARI_RULE_ARITH) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ARITH>());
 	else if (a.rule == ARI_RULE_COMPARE) arith_merge_by_operands(a, f, AriRule<ARI_RULE_COMPARE>());
 	else if (a.rule == ARI_RULE_ASSIGN) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ASSIGN>());
+	else if (a.rule == ARI_RULE_ASSIGN_CELLS) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ASSIGN_CELLS>());
 	else if (a.rule == ARI_RULE_LOGIC && a.x_Rtype != SVT_REALSXP && a.y_Rtype != SVT_REALSXP)
 		f((const int32_t *) a.x_val, (const int32_t *) a.y_val, AriRule<ARI_RULE_LOGIC>());
 	else return svt_set_error("arith merge: no kernel for this rule and these types");

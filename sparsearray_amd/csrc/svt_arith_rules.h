@@ -381,6 +381,22 @@ SVT_HD inline bool svt_rule_assign(bool in_y, TX xv, TY yv, bool row_covered, bo
 	return !(leaf_covered && *out == (TO) 0);
 }
 
+// ---- subassignment by an L-index or M-index (subassign_leaf_by_OPBuf, src/SparseArray_subassignment.c) ----
+// One place of x merged with the placed operand Y of kernels_lindex.hip: Y holds one entry per assigned cell, the
+// cell's last value, a zero too.  in_y: Y stores the place -- the result is Y's value widened, stored iff it is not
+// zero (-0.0 and integer 0 are zero; a NaN or NA is stored).  Else x alone stores it: no index reached the cell, and
+// the entry stays as it is, a stored zero included.  There are no cover tables.
+template <typename TX, typename TY, typename TO>
+SVT_HD inline bool svt_rule_assign_cells(bool in_y, TX xv, TY yv, TO *out)
+{
+	if (in_y) {
+		svt_rule_widen(yv, out);
+		return !(*out == (TO) 0);
+	}
+	svt_rule_widen(xv, out);
+	return true;
+}
+
 // the wider of two types, logical < integer < double; 0 when either is none of them
 SVT_HD inline int svt_rule_assign_out_Rtype(int x_Rtype, int v_Rtype)
 {

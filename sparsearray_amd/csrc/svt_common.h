@@ -276,8 +276,10 @@ int launch_subset_rows_fill(const int32_t *row_idx, const void *val, int Rtype, 
 // element rule the tiles evaluate -- Arith and Math as `kind` and `op` say, or Compare / Logic (`op` a SVT_COMPARE_* /
 // SVT_LOGIC_* opcode, `kind` not read), whose result is int32 whatever the operands and has no overflow word, or the
 // subassignment rule (merge only; y the placed operand of kernels_subassign.hip, `op` not read, `cover_row` /
-// `cover_leaf` one byte per row / per leaf, NULL: the whole axis; the result double when either side is, else int32).
-enum { ARI_RULE_ARITH = 0, ARI_RULE_COMPARE = 1, ARI_RULE_LOGIC = 2, ARI_RULE_ASSIGN = 3 };
+// `cover_leaf` one byte per row / per leaf, NULL: the whole axis; the result double when either side is, else int32),
+// or the rule of the subassignment by cells (merge only; y the placed operand of kernels_lindex.hip, a zero in it the
+// deletion mark; no tables, `op` not read; the result typed like ARI_RULE_ASSIGN's).
+enum { ARI_RULE_ARITH = 0, ARI_RULE_COMPARE = 1, ARI_RULE_LOGIC = 2, ARI_RULE_ASSIGN = 3, ARI_RULE_ASSIGN_CELLS = 4 };
 struct ArithMapArgs {
 	const int64_t *col_ptr;
 	const int32_t *row_idx;
@@ -327,6 +329,33 @@ int launch_subassign_count(const SubassignArgs &a, int64_t *y_col_ptr, unsigned 
 			   hipStream_t s);
 int launch_subassign_fill(const SubassignArgs &a, const int64_t *y_col_ptr, int64_t y_nnz, int32_t *y_row_idx, void *y_val,
 			  const void *ws, hipStream_t s);
+
+// Subsetting and subassignment by an L-index or an M-index (kernels_lindex.hip).  `index`: device int64[K] 0-based cell
+// numbers with INT64_MIN for NA (ndim == 0), or device int32[K * ndim] 0-based coordinates, column-major (ndim >= 1,
+// `dim` the extents with dim[0] == nrow and prod(dim[1:]) == ncol; an NA_integer_ coordinate is a bad index).
+// launch_lindex_gather writes out[K] (A's type): the stored value, the background, or NA for an NA index; a first
+// kernel checks every index and raises *bad (1: an index outside the array, 2: a col_ptr pair that cannot be followed),
+// the gather reads *bad and writes nothing once it is up.  The placement builds the placed operand Y of
+// x[index] <- vals: one entry per distinct cell with the cell's last value, zeros included.  launch_lindex_check leaves
+// in the head of `ws` [int: 1 a bad index (NA included)][int at byte 16: 1 the cells are not strictly increasing] and
+// the cells as keys; launch_lindex_place (after the head was read: `unsorted` says which route) sorts and compacts
+// them when it must, writes y_col_ptr and leaves [int64 at byte 8: the entries of Y]; launch_lindex_fill reads `ws` as
+// they left it.  All asynchronous; none launches over an empty range.
+struct LindexArgs {
+	const void *index;
+	int64_t K;
+	int ndim;               // 0: an L-index
+	int64_t dim[8];
+	int64_t nrow, ncol;
+};
+size_t lindex_place_ws_bytes(int64_t K, int64_t ncol);
+int lindex_sort_passes(int64_t nrow, int64_t ncol);
+int launch_lindex_gather(const LindexArgs &a, const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype, int64_t nnz,
+			 int na_background, void *out, int *bad, hipStream_t s);
+int launch_lindex_check(const LindexArgs &a, void *ws, hipStream_t s);
+int launch_lindex_place(const LindexArgs &a, int unsorted, int64_t *y_col_ptr, void *ws, hipStream_t s);
+int launch_lindex_fill(const LindexArgs &a, const void *vals, int64_t nvals, int v_Rtype, int64_t y_nnz, int32_t *y_row_idx, void *y_val,
+		       const void *ws, hipStream_t s);
 
 // abind (kernels_abind.hip): the result as a sequence of pieces, each a whole leaf of one object.  The count launcher
 // copies the table of objects into `ws` (one asynchronous copy: the table must live until the stream has passed it) and

@@ -1597,6 +1597,7 @@ struct ArithCall {
 	int out_Rtype = 0;
 	int rule = ARI_RULE_ARITH;      // ARI_RULE_COMPARE / _LOGIC: `kind` says merge or map, the result is LGLSXP, no overflow word
 	const unsigned char *cover_row = NULL, *cover_leaf = NULL;      // ARI_RULE_ASSIGN (a merge): the two tables, NULL = the whole axis
+									// (ARI_RULE_ASSIGN_CELLS, a merge too, reads neither)
 	ArithMergeArgs merge_args() const
 	{
 		ArithMergeArgs a = arith_merge_args(x, y, op);
@@ -1617,7 +1618,7 @@ struct ArithCall {
 	}
 	int check(size_t ws_bytes)
 	{
-		if (rule == ARI_RULE_ASSIGN) {
+		if (rule == ARI_RULE_ASSIGN || rule == ARI_RULE_ASSIGN_CELLS) {
 			if (const int rc = assign_check(who, x, y, &out_Rtype))
 				return rc;
 		} else if (rule != ARI_RULE_ARITH) {
@@ -2389,6 +2390,256 @@ extern "C" int svt_dev_subassign_svt(const svt_dev_csc *x, const int32_t *rows, 
 		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
 		if (c.plan(x->nrow, x->ncol, rows, nrows_sel, leaves, nleaves_sel, NULL, 0, 0, v, true)) return -1;
 		return c.compose(x, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	});
+}
+
+// ---- subsetting and subassignment by an L-index or M-index: kernels_lindex.hip gathers, or places the new values as an
+// operand Y with one entry per assigned cell; the merge of kernels_arith.hip under ARI_RULE_ASSIGN_CELLS
+// (svt_rule_assign_cells) makes the result ----
+enum { LINDEX_SORTED = 0, LINDEX_UNSORTED = 1 };
+static std::atomic<int64_t> g_lindex_route[2];
+
+extern "C" void svt_dev_lindex_route_counts(int64_t *counts, int reset)
+{
+	for (int i = 0; i < 2; i++) {
+		if (counts) counts[i] = g_lindex_route[i].load();
+		if (reset) g_lindex_route[i] = 0;
+	}
+}
+extern "C" size_t svt_dev_subassign_place_lindex_ws_bytes(int64_t K, int64_t ncol)
+{
+	return lindex_place_ws_bytes(K, ncol);
+}
+extern "C" int svt_dev_lindex_sort_passes(int64_t nrow, int64_t ncol)
+{
+	return lindex_sort_passes(nrow, ncol);
+}
+
+// One index of either form (ndim == 0: an L-index) over an array of nrow x ncol cells: every check that needs no GPU,
+// then the gather, or the placement's count / fill and the composition with the merge.
+struct LindexCall {
+	const char *who;
+	LindexArgs a;
+
+	int plan(int64_t nrow, int64_t ncol, const void *index, int64_t K, int ndim, const int64_t *dim)
+	{
+		memset(&a, 0, sizeof(a));
+		if (nrow < 0 || nrow > 0x7FFFFFFFLL || ncol < 0 || ncol > 0x7FFFFFFELL)
+			return svt_set_error("%s: extents outside 0 .. 2^31 - 1 rows, 0 .. 2^31 - 2 leaves", who);
+		if (K < 0 || (K > 0 && index == NULL))
+			return svt_set_error("%s: an index of K >= 0 elements is needed", who);
+		if (K > 0x7FFFFFFFLL * 256)
+			return svt_set_error("%s: too many indices", who);
+		if (ndim < 0 || ndim > 8 || (ndim > 0 && dim == NULL))
+			return svt_set_error("%s: an M-index takes between 1 and 8 dimensions", who);
+		if (ndim > 0) {
+			int64_t leaves = 1;
+			for (int k = 0; k < ndim; k++) {
+				if (dim[k] < 0 || dim[k] > 0x7FFFFFFFLL)
+					return svt_set_error("%s: an extent outside 0 .. 2^31 - 1", who);
+				if (k > 0) {
+					if (dim[k] != 0 && leaves > INT64_MAX / dim[k])
+						return svt_set_error("%s: 'dim' does not match the operand's rows and leaves", who);
+					leaves *= dim[k];
+				}
+				a.dim[k] = dim[k];
+			}
+			if (dim[0] != nrow || leaves != ncol)
+				return svt_set_error("%s: 'dim' does not match the operand's rows and leaves", who);
+		}
+		a.index = index; a.K = K; a.ndim = ndim; a.nrow = nrow; a.ncol = ncol;
+		return 0;
+	}
+	const char *bad_index_message() const
+	{
+		return a.ndim == 0 ? "linear index (L-index) contains out-of-bound indices or NAs"
+				   : "matrix subscript (M-index) contains out-of-bound indices or NAs";
+	}
+	int gather(const svt_dev_csc *A, void *out, int *bad, void *stream)
+	{
+		if (!logical_family_type(A->Rtype))
+			return svt_set_error("%s: the operand must be of type \"logical\", \"integer\" or \"double\"", who);
+		if (A->nnz < 0)
+			return svt_set_error("%s: the operand has a negative nonzero count", who);
+		if (a.K == 0)
+			return 0;
+		if (out == NULL || bad == NULL)
+			return svt_set_error("%s: 'out' and 'bad' are needed", who);
+		return launch_lindex_gather(a, A->col_ptr, A->row_idx, A->val, A->Rtype, A->nnz, A->na_background != 0, out, bad,
+					    (hipStream_t) stream);
+	}
+
+	size_t need() const { return lindex_place_ws_bytes(a.K, a.ncol); }
+	int check_values(const void *vals, int64_t nvals, int v_Rtype, size_t ws_bytes) const
+	{
+		if (nvals < 1 || vals == NULL)
+			return svt_set_error("replacement has length zero");
+		if (!logical_family_type(v_Rtype))
+			return svt_set_error("%s: the value must be of type \"logical\", \"integer\" or \"double\"", who);
+		if (a.K > 0x7FFFFFFFLL)                             // (the sort's payload, the position, is 32 bits)
+			return svt_set_unsupported("%s: more than 2^31 - 1 indices are not supported here", who);
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		return 0;
+	}
+	int count(const void *vals, int64_t nvals, int v_Rtype, int64_t *y_col_ptr, int64_t *y_nnz, void *ws, size_t ws_bytes, void *stream)
+	{
+		if (const int rc = check_values(vals, nvals, v_Rtype, ws_bytes))
+			return rc;
+		if (y_col_ptr == NULL || y_nnz == NULL)
+			return svt_set_error("%s: 'y_col_ptr' and 'y_nnz' are needed", who);
+		hipStream_t st = (hipStream_t) stream;
+		if (launch_lindex_check(a, ws, st))
+			return -1;
+		int64_t head[3] = { 0, 0, 0 };                      // [flag][the entries of Y][unsorted, the route]
+		HIP_TRY(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		if (head[0] & 0xFFFFFFFFLL)
+			return svt_set_error("%s", bad_index_message());
+		const int unsorted = (head[2] & 0xFFFFFFFFLL) != 0;
+		g_lindex_route[unsorted ? LINDEX_UNSORTED : LINDEX_SORTED]++;
+		if (launch_lindex_place(a, unsorted, y_col_ptr, ws, st))
+			return -1;
+		*y_nnz = a.K;                                       // the sorted route: every index is an entry
+		if (unsorted) {
+			int flag = 0;
+			return subset_read_head(ws, st, &flag, y_nnz);
+		}
+		return 0;
+	}
+	int fill(const void *vals, int64_t nvals, int v_Rtype, int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes,
+		 void *stream)
+	{
+		if (const int rc = check_values(vals, nvals, v_Rtype, ws_bytes))
+			return rc;
+		if (y_nnz > 0 && (y_row_idx == NULL || y_val == NULL))
+			return svt_set_error("%s: 'y_row_idx' and 'y_val' are needed", who);
+		return launch_lindex_fill(a, vals, nvals, v_Rtype, y_nnz, y_row_idx, y_val, ws, (hipStream_t) stream);
+	}
+	// place -> merge over the caller's allocator: the whole of x[index] <- vals
+	int compose(const svt_dev_csc *x, const void *vals, int64_t nvals, int v_Rtype, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+		    void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+	{
+		if (alloc == NULL || release == NULL)
+			return svt_set_error("%s: an allocator is needed", who);
+		if (const int rc = check_values(vals, nvals, v_Rtype, need()))
+			return rc;
+		const int rt = svt_rule_assign_out_Rtype(x->Rtype, v_Rtype);
+		if (rt == 0)
+			return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
+		if (x->na_background)
+			return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+		if (a.K == 0) {                                     // nothing assigned: x, coerced (the one-object case of abind)
+			AbindCall c = { who };
+			const svt_dev_csc *objs[1] = { x };
+			if (c.plan(objs, 1, 0, NULL, rt) || c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream))
+				return -1;
+			*out_Rtype = rt;
+			return 0;
+		}
+		SubsetMem mem = { alloc, release, ctx };
+		SubsetCsc Y(mem);
+		SubsetWs ws(mem);
+		svt_dev_csc like;
+		memset(&like, 0, sizeof(like));
+		like.Rtype = v_Rtype;
+		if (Y.shape(&like, x->nrow, x->ncol) || ws.get(need()))
+			return -1;
+		int64_t y_nnz = 0;
+		if (count(vals, nvals, v_Rtype, Y.c.col_ptr, &y_nnz, ws.p, ws.n, stream) || Y.entries(y_nnz) ||
+		    fill(vals, nvals, v_Rtype, y_nnz, Y.c.row_idx, Y.c.val, ws.p, ws.n, stream))
+			return -1;
+		ArithCall m = { who, SVT_ARITH_MERGE, 0, x, &Y.c, 0.0, 0 };
+		m.rule = ARI_RULE_ASSIGN_CELLS;
+		return m.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, stream);
+	}
+};
+
+extern "C" int svt_dev_subset_lindex(const svt_dev_csc *A, const int64_t *lindex, int64_t K, void *out, int *bad, void *stream)
+{
+	return abi_status([&] {
+		LindexCall c = { "svt_dev_subset_lindex" };
+		if (A == NULL) return svt_set_error("%s: an operand is needed", c.who);
+		if (c.plan(A->nrow, A->ncol, lindex, K, 0, NULL)) return -1;
+		return c.gather(A, out, bad, stream);
+	});
+}
+extern "C" int svt_dev_subset_mindex(const svt_dev_csc *A, const int32_t *mindex, int64_t K, int ndim, const int64_t *dim, void *out,
+				     int *bad, void *stream)
+{
+	return abi_status([&] {
+		LindexCall c = { "svt_dev_subset_mindex" };
+		if (A == NULL) return svt_set_error("%s: an operand is needed", c.who);
+		if (ndim < 1) return svt_set_error("%s: an M-index takes between 1 and 8 dimensions", c.who);
+		if (c.plan(A->nrow, A->ncol, mindex, K, ndim, dim)) return -1;
+		return c.gather(A, out, bad, stream);
+	});
+}
+extern "C" int svt_dev_subassign_place_lindex_count(int64_t nrow, int64_t ncol, const void *index, int64_t K, int ndim,
+						    const int64_t *dim, const void *vals, int64_t nvals, int v_Rtype, int64_t *y_col_ptr,
+						    int64_t *y_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		LindexCall c = { "svt_dev_subassign_place_lindex_count" };
+		if (c.plan(nrow, ncol, index, K, ndim, dim)) return -1;
+		return c.count(vals, nvals, v_Rtype, y_col_ptr, y_nnz, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_subassign_place_lindex_fill(int64_t nrow, int64_t ncol, const void *index, int64_t K, int ndim,
+						   const int64_t *dim, const void *vals, int64_t nvals, int v_Rtype, const int64_t *y_col_ptr,
+						   int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes,
+						   void *stream)
+{
+	(void) y_col_ptr;                                   // (the scanned run ends in `ws` place the entries)
+	return abi_status([&] {
+		LindexCall c = { "svt_dev_subassign_place_lindex_fill" };
+		if (c.plan(nrow, ncol, index, K, ndim, dim)) return -1;
+		return c.fill(vals, nvals, v_Rtype, y_nnz, y_row_idx, y_val, ws, ws_bytes, stream);
+	});
+}
+
+static ArithCall assign_cells_call(const char *who, const svt_dev_csc *x, const svt_dev_csc *y)
+{
+	ArithCall c = { who, SVT_ARITH_MERGE, 0, x, y, 0.0, 0 };
+	c.rule = ARI_RULE_ASSIGN_CELLS;
+	return c;
+}
+extern "C" int svt_dev_assign_cells_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int64_t *out_col_ptr, int64_t *out_nnz,
+						void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = assign_cells_call("svt_dev_assign_cells_merge_count", x, y);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_assign_cells_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, const int64_t *out_col_ptr,
+					       int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile prefixes in `ws` place the entries)
+	ArithCall c = assign_cells_call("svt_dev_assign_cells_merge_fill", x, y);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+
+extern "C" int svt_dev_subassign_lindex(const svt_dev_csc *x, const int64_t *lindex, int64_t K, const void *vals, int64_t nvals,
+					int v_Rtype, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype,
+					int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+{
+	return abi_status([&] {
+		LindexCall c = { "svt_dev_subassign_lindex" };
+		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
+		if (c.plan(x->nrow, x->ncol, lindex, K, 0, NULL)) return -1;
+		return c.compose(x, vals, nvals, v_Rtype, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	});
+}
+extern "C" int svt_dev_subassign_mindex(const svt_dev_csc *x, const int32_t *mindex, int64_t K, int ndim, const int64_t *dim,
+					const void *vals, int64_t nvals, int v_Rtype, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+					void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+					void **out_val, void *stream)
+{
+	return abi_status([&] {
+		LindexCall c = { "svt_dev_subassign_mindex" };
+		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
+		if (ndim < 1) return svt_set_error("%s: an M-index takes between 1 and 8 dimensions", c.who);
+		if (c.plan(x->nrow, x->ncol, mindex, K, ndim, dim)) return -1;
+		return c.compose(x, vals, nvals, v_Rtype, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 	});
 }
 
@@ -3894,6 +4145,186 @@ extern "C" int svt_subassign_SVT_SVT_begin(const svt_view *x, const int *const *
 {
 	return abi_status([&] {
 		return subassign_begin_impl("svt_subassign_SVT_SVT_begin", x, index, index_len, NULL, 0, 0, v, true, res, out_Rtype, out_nnz);
+	});
+}
+
+// x[Lindex], x[Mindex] and their subassignments on host operands (C_subset_SVT_by_Lindex / _by_Mindex,
+// C_subassign_SVT_by_Lindex / _by_Mindex): the index is checked and brought to the 0-based cell numbers of the device
+// layout here, on the host, before anything is uploaded -- an M-index becomes an L-index on the way, so one device path
+// serves both.  First device of the list; not sharded.
+static int view_ncells(const svt_view *x, int64_t *ncells)
+{
+	int64_t n = 1;
+	for (int a = 0; a < x->ndim; a++) {
+		if (x->dim[a] != 0 && n > INT64_MAX / x->dim[a])
+			return svt_set_error("the array has more than 2^63 - 1 cells");
+		n *= x->dim[a];
+	}
+	*ncells = n;
+	return 0;
+}
+static int lindex_cells(const int64_t *lindex, int64_t K, int64_t ncells, bool na_ok, std::vector<int64_t> &out)
+{
+	if (K < 0 || (K > 0 && lindex == NULL))
+		return svt_set_error("invalid linear index (L-index)");
+	out.resize((size_t) K);
+	for (int64_t k = 0; k < K; k++) {
+		const int64_t v = lindex[k];
+		if (v == INT64_MIN) {
+			if (!na_ok) return svt_set_error("linear index (L-index) contains NAs");
+			out[(size_t) k] = INT64_MIN;
+			continue;
+		}
+		if (v < 1 || v > ncells)
+			return svt_set_error("linear index (L-index) contains out-of-bound indices");
+		out[(size_t) k] = v - 1;
+	}
+	return 0;
+}
+static int mindex_cells(const int *mindex, int64_t K, const svt_view *x, std::vector<int64_t> &out)
+{
+	if (K < 0 || (K > 0 && mindex == NULL))
+		return svt_set_error("matrix subscript (M-index) must be a numeric matrix");
+	out.resize((size_t) K);
+	for (int64_t k = 0; k < K; k++) {
+		int64_t cell = 0, stride = 1;
+		for (int a = 0; a < x->ndim; a++) {
+			const int m = mindex[k + (int64_t) a * K];
+			if (m == NA_INT)
+				return svt_set_error("matrix subscript (M-index) contains NAs");
+			if (m < 1 || m > x->dim[a])
+				return svt_set_error("matrix subscript (M-index) contains out-of-bound indices");
+			cell += (int64_t) (m - 1) * stride;
+			stride *= x->dim[a];
+		}
+		out[(size_t) k] = cell;
+	}
+	return 0;
+}
+
+static int subset_by_cells(const char *who, const svt_view *x, const std::vector<int64_t> &cells, void *out)
+{
+	const int64_t K = (int64_t) cells.size();
+	if (!logical_family_type(x->Rtype))
+		return svt_set_unsupported("%s: operands of type \"logical\", \"integer\" or \"double\" only", who);
+	if (K == 0)
+		return 0;
+	if (out == NULL)
+		return svt_set_error("%s: 'out' is needed", who);
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	DevBuf di, dout;
+	DevFlag bad;
+	if (di.upload(cells.data(), (size_t) K * 8) || dout.alloc((size_t) K * elt_size(x->Rtype)) || bad.init())
+		return -1;
+	LindexCall c = { who };
+	if (c.plan(A.h->nrow, A.h->ncol, di.p, K, 0, NULL) || c.gather(A.h, dout.p, bad.ptr(), NULL))
+		return -1;
+	HIP_TRY(hipStreamSynchronize(0));
+	int raised = 0;
+	if (bad.read(&raised))
+		return -1;
+	if (raised)
+		return svt_set_error("%s: the device refused an index or the operand's pointers", who);
+	return staged_download(out, dout.p, (size_t) K * elt_size(x->Rtype));
+}
+extern "C" int svt_subset_SVT_by_Lindex(const svt_view *x, const int64_t *lindex, int64_t K, void *out)
+{
+	return abi_status([&] {
+		int64_t ncells = 0;
+		std::vector<int64_t> cells;
+		if (ensure_init() || check_view(x) || view_ncells(x, &ncells) || lindex_cells(lindex, K, ncells, true, cells))
+			return -1;
+		return subset_by_cells("svt_subset_SVT_by_Lindex", x, cells, out);
+	});
+}
+extern "C" int svt_subset_SVT_by_Mindex(const svt_view *x, const int *mindex, int64_t K, void *out)
+{
+	return abi_status([&] {
+		int64_t ncells = 0;
+		std::vector<int64_t> cells;
+		if (ensure_init() || check_view(x) || view_ncells(x, &ncells) || mindex_cells(mindex, K, x, cells))
+			return -1;
+		return subset_by_cells("svt_subset_SVT_by_Mindex", x, cells, out);
+	});
+}
+
+static int subassign_by_cells(const char *who, const svt_view *x, const std::vector<int64_t> &cells, const void *vals, int64_t nvals,
+			      int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
+{
+	const int64_t K = (int64_t) cells.size();
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	DevBuf di, dv;
+	if ((K > 0 && di.upload(cells.data(), (size_t) K * 8)) || dv.upload(vals, (size_t) nvals * elt_size(v_Rtype)))
+		return -1;
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
+	LindexCall c = { who };
+	int rt = 0;
+	if (c.plan(A.h->nrow, A.h->ncol, di.p, K, 0, NULL) ||
+	    c.compose(A.h, dv.p, nvals, v_Rtype, subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val,
+		      NULL) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
+		svt_release(h);
+		return -1;
+	}
+	h->Rtype = rt;
+	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
+	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
+	r->h = h;
+	*res = r;
+	*out_Rtype = rt;
+	*out_nnz = h->nnz;
+	return 0;
+}
+// the checks both forms share, before the index is looked at
+static int subassign_by_index_head(const char *who, const svt_view *x, const void *vals, int64_t nvals, int v_Rtype,
+				   svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
+{
+	if (res == NULL || out_Rtype == NULL || out_nnz == NULL)
+		return svt_set_error("%s: 'res', 'out_Rtype' and 'out_nnz' are needed", who);
+	*res = NULL;
+	if (ensure_init() || check_view(x))
+		return -1;
+	if (!logical_family_type(v_Rtype))
+		return svt_set_error("%s: the value must be of type \"logical\", \"integer\" or \"double\"", who);
+	if (!logical_family_type(x->Rtype))
+		return svt_set_unsupported("%s: operands of type \"logical\", \"integer\" or \"double\" only", who);
+	if (x->na_background)
+		return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+	if (nvals < 1 || vals == NULL)
+		return svt_set_error("replacement has length zero");
+	return 0;
+}
+extern "C" int svt_subassign_SVT_by_Lindex_begin(const svt_view *x, const int64_t *lindex, int64_t K, const void *vals, int64_t nvals,
+						 int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
+{
+	const char *who = "svt_subassign_SVT_by_Lindex_begin";
+	return abi_status([&] {
+		int64_t ncells = 0;
+		std::vector<int64_t> cells;
+		if (const int rc = subassign_by_index_head(who, x, vals, nvals, v_Rtype, res, out_Rtype, out_nnz))
+			return rc;
+		if (view_ncells(x, &ncells) || lindex_cells(lindex, K, ncells, false, cells))
+			return -1;
+		return subassign_by_cells(who, x, cells, vals, nvals, v_Rtype, res, out_Rtype, out_nnz);
+	});
+}
+extern "C" int svt_subassign_SVT_by_Mindex_begin(const svt_view *x, const int *mindex, int64_t K, const void *vals, int64_t nvals,
+						 int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
+{
+	const char *who = "svt_subassign_SVT_by_Mindex_begin";
+	return abi_status([&] {
+		int64_t ncells = 0;
+		std::vector<int64_t> cells;
+		if (const int rc = subassign_by_index_head(who, x, vals, nvals, v_Rtype, res, out_Rtype, out_nnz))
+			return rc;
+		if (view_ncells(x, &ncells) || mindex_cells(mindex, K, x, cells))
+			return -1;
+		return subassign_by_cells(who, x, cells, vals, nvals, v_Rtype, res, out_Rtype, out_nnz);
 	});
 }
 

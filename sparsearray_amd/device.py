@@ -231,6 +231,88 @@ class DeviceCSC:
         dtype = torch.float64 if rt.value == REALSXP else torch.int32
         return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype), logical=rt.value == LGLSXP)
 
+    def _cell_index(self, index, dim, matrix):
+        """The arguments (pointer, K[, ndim, dim]) of an L-index (int64[K], 0-based, LINDEX_NA for NA) or an M-index
+        ((K, ndim) int32, 0-based; handed over column-major, which the result of ``nzwhich(arr_ind=True)`` already is)
+        and the tensor that keeps them alive."""
+        dev = self.val.device
+        if not matrix:
+            if not isinstance(index, torch.Tensor):
+                a = np.asarray(index)
+                if a.size and not np.issubdtype(a.dtype, np.integer):
+                    raise SparseArrayError("subscripts must be integers")
+                index = torch.as_tensor(a.astype(np.int64).reshape(-1), device=dev)
+            if index.dtype != torch.int64 or not index.is_cuda:
+                raise SparseArrayError("an L-index is an int64 CUDA tensor")
+            index = index.contiguous().reshape(-1)
+            return index, (index.data_ptr(), index.numel())
+        dim = self._dim(dim)
+        if not isinstance(index, torch.Tensor):
+            a = np.asarray(index)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise SparseArrayError("subscripts must be integers")
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise SparseArrayError("subscript out of bounds")
+            index = torch.as_tensor(a.astype(np.int32), device=dev)
+        if index.dtype != torch.int32 or not index.is_cuda or index.ndim != 2 or index.shape[1] != len(dim):
+            raise SparseArrayError("an M-index is a (K, ndim) int32 CUDA tensor")
+        flat = index.t().contiguous()
+        return flat, (flat.data_ptr(), int(index.shape[0]), len(dim), (c_int64 * len(dim))(*dim))
+
+    def _gather(self, index, dim, matrix):
+        keep, args = self._cell_index(index, dim, matrix)
+        out = torch.empty(args[1], dtype=self.val.dtype, device=self.val.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=self.val.device)
+        fn = _lib().svt_dev_subset_mindex if matrix else _lib().svt_dev_subset_lindex
+        _check(fn(self.handle, *args, out.data_ptr(), bad.data_ptr(), _stream()))
+        raised = int(bad.item()) if args[1] else 0          # (the one synchronisation: an index error is the caller's to see)
+        if raised & 1:
+            raise SparseArrayError(("matrix subscript (M-index)" if matrix else "linear index (L-index)") +
+                                   " contains out-of-bound indices")
+        if raised:
+            raise SparseArrayError("the operand's column pointers descend or leave its nonzeros")
+        return out
+
+    def subset_lindex(self, L) -> torch.Tensor:
+        """``x[L]`` by a linear index on the device (include/svt_hip.h, svt_dev_subset_lindex): ``L`` an int64 CUDA
+        tensor -- the result of ``nzwhich()`` plugs straight in -- or an integer array-like, 0-based over the
+        column-major array, LINDEX_NA for NA, in any order and with repeats.  Returns a tensor of the operand's dtype
+        with one value per index: the stored value bit for bit, else 0 (NA under na_background), NA for an NA index.
+        An index outside the array raises SparseArrayError and nothing was read through it."""
+        return self._gather(L, None, False)
+
+    def subset_mindex(self, M, dim=None) -> torch.Tensor:
+        """``x[M]`` by a matrix subscript (svt_dev_subset_mindex): ``M`` a (K, ndim) int32 CUDA tensor -- the result of
+        ``nzwhich(arr_ind=True)`` plugs straight in -- or an integer array-like of 0-based coordinates into the array
+        of extents ``dim`` (default (nrow, ncol))."""
+        return self._gather(M, dim, True)
+
+    def _subassign_cells(self, index, value, dim, logical, matrix):
+        keep, args = self._cell_index(index, dim, matrix)
+        vals, v_Rtype = _assign_values(value, self.val.device, logical)
+        fn = _lib().svt_dev_subassign_mindex if matrix else _lib().svt_dev_subassign_lindex
+        mem = _TorchBlocks(self.val.device)
+        rt, nnz = ctypes.c_int(0), c_int64(0)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(fn(self.handle, *args, vals.data_ptr(), vals.numel(), v_Rtype, mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt),
+                  ctypes.byref(nnz), *[ctypes.byref(o) for o in out], _stream()))
+        dtype = torch.float64 if rt.value == REALSXP else torch.int32
+        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype), logical=rt.value == LGLSXP)
+
+    def subassign_lindex(self, L, value, logical: bool = False) -> "DeviceCSC":
+        """``x[L] <- value`` by a linear index on the device (svt_dev_subassign_lindex): ``L`` as in subset_lindex, no
+        NA; ``value`` a scalar or 1-D tensor / array as in subassign(), entry p of the index taking
+        ``value[p % len(value)]``.  Positions apply in order (the last occurrence of a cell wins); a cell whose final
+        value is zero has no entry afterwards; a cell no index reaches keeps its entry bit for bit, a stored zero
+        included.  Returns a new DeviceCSC of the wider type of the two.  A strictly increasing index (what nzwhich()
+        gives) takes the sorted route, any other the library's radix sort (lindex_route_counts())."""
+        return self._subassign_cells(L, value, None, logical, False)
+
+    def subassign_mindex(self, M, value, dim=None, logical: bool = False) -> "DeviceCSC":
+        """``x[M] <- value`` by a matrix subscript (svt_dev_subassign_mindex): ``M`` as in subset_mindex, the rest as
+        subassign_lindex."""
+        return self._subassign_cells(M, value, dim, logical, True)
+
     def _arith_result(self, call):
         """The new DeviceCSC that ``call(alloc, release, ctx, out_Rtype, nnz, col_ptr, row_idx, val, ovflow, stream)`` --
         one of the two compositions svt_dev_arith_merge / svt_dev_arith_map -- leaves in torch allocations.  Its
@@ -428,6 +510,62 @@ def assign_merge(x: DeviceCSC, y: DeviceCSC, cover_row=None, cover_leaf=None, ws
     vv = torch.empty(nnz.value, dtype=torch.float64 if double else torch.int32, device=dev)
     _check(lib.svt_dev_assign_merge_fill(x.handle, y.handle, *tab, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
                                          ws.numel(), _stream()))
+    return DeviceCSC(x.nrow, cp, ri, vv, logical=x.Rtype == LGLSXP and y.Rtype == LGLSXP)
+
+
+# the NA of an L-index (include/svt_hip.h, svt_dev_subset_lindex)
+LINDEX_NA = -2 ** 63
+
+
+def lindex_route_counts(reset=False) -> dict:
+    """Sorted and unsorted placements of this process so far (svt_dev_lindex_route_counts)."""
+    buf = (c_int64 * 2)()
+    _lib().svt_dev_lindex_route_counts(buf, int(bool(reset)))
+    return {"sorted": int(buf[0]), "unsorted": int(buf[1])}
+
+
+def lindex_sort_passes(nrow: int, ncol: int) -> int:
+    """8-bit passes of the unsorted route's sort for an array of nrow x ncol cells (svt_dev_lindex_sort_passes).  Needs
+    no GPU."""
+    return int(_hip.load_library().svt_dev_lindex_sort_passes(nrow, ncol))
+
+
+def lindex_place(x: DeviceCSC, index, value, dim=None, matrix=False, logical=False, ws=None, col_ptr=None) -> DeviceCSC:
+    """The placement alone (svt_dev_subassign_place_lindex_count, then _fill): the placed operand Y of ``x[index] <-
+    value`` -- one entry per distinct assigned cell, zeros included.  ``ws`` (uint8) and ``col_ptr`` (int64[ncol + 1]) may
+    be given."""
+    lib, dev = _lib(), x.val.device
+    keep, args = x._cell_index(index, dim, matrix)
+    args = args if matrix else args + (0, None)
+    vals, v_Rtype = _assign_values(value, dev, logical)
+    if ws is None:
+        ws = torch.empty(lib.svt_dev_subassign_place_lindex_ws_bytes(args[1], x.ncol), dtype=torch.uint8, device=dev)
+    cp = torch.empty(x.ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
+    what = (x.nrow, x.ncol, *args, vals.data_ptr(), vals.numel(), v_Rtype, cp.data_ptr())
+    nnz = c_int64(0)
+    _check(lib.svt_dev_subassign_place_lindex_count(*what, ctypes.byref(nnz), ws.data_ptr(), ws.numel(), _stream()))
+    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    vv = torch.empty(nnz.value, dtype=vals.dtype, device=dev)
+    _check(lib.svt_dev_subassign_place_lindex_fill(*what, nnz.value, ri.data_ptr(), vv.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   _stream()))
+    return DeviceCSC(x.nrow, cp, ri, vv, logical=v_Rtype == LGLSXP)
+
+
+def assign_cells_merge(x: DeviceCSC, y: DeviceCSC, ws=None, col_ptr=None) -> DeviceCSC:
+    """The merge under the rule of the subassignment by cells alone (svt_dev_assign_cells_merge_count, then _fill): x
+    with the placed operand ``y`` written over it, a zero of ``y`` deleting."""
+    lib, dev = _lib(), x.val.device
+    if ws is None:
+        ws = torch.empty(lib.svt_dev_arith_merge_ws_bytes(x.ncol, x.nnz, y.nnz), dtype=torch.uint8, device=dev)
+    cp = torch.empty(x.ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
+    nnz = c_int64(0)
+    _check(lib.svt_dev_assign_cells_merge_count(x.handle, y.handle, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
+                                                _stream()))
+    double = REALSXP in (x.Rtype, y.Rtype)
+    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    vv = torch.empty(nnz.value, dtype=torch.float64 if double else torch.int32, device=dev)
+    _check(lib.svt_dev_assign_cells_merge_fill(x.handle, y.handle, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), _stream()))
     return DeviceCSC(x.nrow, cp, ri, vv, logical=x.Rtype == LGLSXP and y.Rtype == LGLSXP)
 
 
