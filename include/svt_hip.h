@@ -1034,6 +1034,70 @@ int svt_Compare_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_
 int svt_Compare_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res, int64_t *out_nnz);
 int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int64_t *out_nnz);
 
+/* sweep(x, MARGIN, STATS, op): Arith and Compare between a sparse operand and a device vector that holds one element
+   per row, per leaf, or per row of a group of leaves -- t(t(x) / colSums(x)), x * gene_weights (R's recycling of a
+   vector of length nrow), sweep(x, 1, q, ">").  The reference has no method: it refuses every vector of length != 1.  A
+   third kernel family next to the map and the merge (kernels_arith.hip):
+
+     sweep  f(v, stats[k]) on the stored values of x, stored unless the result == 0, where for an entry of row r in
+            leaf q   k = (with_rows ? r : 0) + (with_rows ? nrow : 1) * ((q / stride) % len).
+            with_rows 1, stride 1, len 1: one element per row.  with_rows 0, stride 1, len ncol: one per leaf (the
+            columns of a matrix, and what colSums(x, dims = 1) of an N-d array returns).  For the N-d array of extents
+            dim[] (dim[0] == nrow) and a run of consecutive dimensions a..b (1-based): with_rows = (a == 1),
+            stride = prod(dim[1 .. a-2]) (0-based; 1 when a <= 2), len = prod of the run's extents without dimension 1;
+            `stats` is then the column-major array of the run's extents.  stats_len must be (with_rows ? nrow : 1) * len.
+
+   Arith takes op one of SVT_ARITH_MULT / _DIV / _POW / _MOD / _IDIV (_ADD and _SUB answer < 0: the result wouldn't be
+   sparse in general), x INTSXP or REALSXP, stats INTSXP or REALSXP (device int32 / double); the result's type is
+   svt_dev_arith_out_Rtype(SVT_ARITH_SCALAR, op, x->Rtype, stats_Rtype), integer overflow gives NA_integer_ and ORs 1
+   into `ovflow`.  Compare takes the six operators, x and stats LGLSXP, INTSXP or REALSXP, and gives int32 1 /
+   NA_integer_.  Both evaluate the element rules of the maps.
+
+   Every element of `stats` must keep the result sparse, and the count call checks that on the device before anything
+   else runs: for * not NA / NaN and finite; for / %% %/% not NA / NaN and != 0; for ^ not NA / NaN and > 0; for Compare
+   not NA / NaN and 0 op s FALSE.  On an element that does not, the call answers < 0, *bad_index is the smallest such
+   index (0-based; -1 otherwise; bad_index may be NULL) and nothing is written outside `ws`.
+
+   Apart from that the contract is that of svt_dev_arith_map* / svt_dev_compare_map*: `_count` writes out_col_ptr
+   int64[ncol + 1] and *out_nnz and synchronises `stream` once (the refused element is read in that same
+   synchronisation); `_fill` is asynchronous and reads the workspace as the count call left it; rows ascend in every
+   result column; no atomic decides a position; two runs give the same bits.  Status: < 0 for a vector whose length
+   does not match the three integers, integers that do not divide the operand's leaves, a workspace below
+   svt_dev_sweep_ws_bytes(), an unknown opcode, a type outside the above; > 0 for an operand with na_background.  On a
+   non-zero status nothing is written outside `ws`.  Alignment and workspace: "Workspaces" above. */
+size_t svt_dev_sweep_ws_bytes(int64_t ncol, int64_t nnz);
+int svt_dev_arith_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+			      int with_rows, int64_t stride, int64_t len, int64_t *out_col_ptr, int64_t *out_nnz,
+			      int64_t *bad_index, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_arith_sweep_fill(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+			     int with_rows, int64_t stride, int64_t len, const int64_t *out_col_ptr, int32_t *out_row_idx,
+			     void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_compare_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+				int with_rows, int64_t stride, int64_t len, int64_t *out_col_ptr, int64_t *out_nnz,
+				int64_t *bad_index, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_compare_sweep_fill(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+			       int with_rows, int64_t stride, int64_t len, const int64_t *out_col_ptr, int32_t *out_row_idx,
+			       int32_t *out_val, const void *ws, size_t ws_bytes, void *stream);
+/* The compositions count -> allocate -> fill over the allocator of svt_dev_subset(), like svt_dev_arith_map and
+   svt_dev_compare_map. */
+int svt_dev_arith_sweep(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len, int with_rows,
+			int64_t stride, int64_t len, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx,
+			int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val,
+			int *ovflow, int64_t *bad_index, void *stream);
+int svt_dev_compare_sweep(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len, int with_rows,
+			  int64_t stride, int64_t len, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx,
+			  int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val,
+			  int64_t *bad_index, void *stream);
+/* Host level, like svt_Arith_SVT_scalar_begin / svt_Compare_SVT_scalar_begin: `stats` is a host vector of stats_len
+   elements of stats_Rtype, `margin` names nmargin dimensions of x (1-based, a strictly increasing run of consecutive
+   dimensions; anything else answers < 0) and the three integers are derived from x->dim.  The result stays on the
+   device and svt_Arith_SVT_end ends it.  First device of the list; not sharded.  NaArray operands answer > 0. */
+int svt_Arith_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
+			       const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res, int *out_Rtype,
+			       int64_t *out_nnz, int *ovflow);
+int svt_Compare_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
+				 const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res, int64_t *out_nnz);
+
 /* abind(), cbind() and rbind() of SVT operands (C_abind_SVT_SparseArray_objects, src/SparseArray_abind.c;
    R/SparseArray-abind.R, R/NaArray-abind.R): nobj >= 1 objects bound along dimension `along` (1-based) into a new
    operand in the device layout, leaves x rows with the outermost dimension slowest.  A pure copy (kernels_abind.hip).

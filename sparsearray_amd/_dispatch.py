@@ -423,6 +423,23 @@ class CAbiDispatcher:
         return self._logical_result("Logic_SVT_SVT_begin", x, (y, LOGIC_OPCODES[op]),
                                     x.dimnames if x.dimnames is not None else y.dimnames)
 
+    # sweep(x, MARGIN, STATS, FUN) (no counterpart in the reference; include/svt_hip.h, svt_Arith_SVT_vector_begin /
+    # svt_Compare_SVT_vector_begin; HIP library only): the same begin / end pairs with a host vector and the margin ------
+    def C_sweep_SVT(self, x: SVT_SparseArray, stats: np.ndarray, stats_type: str, margin, op: str):
+        """Returns (x op STATS along ``margin``, overflow flag).  ``stats``: a float64 array for ``stats_type`` "double",
+        an int32 one for "integer" / "logical"; ``margin``: 1-based dimension numbers.  An element the library refuses
+        is named in its message, 0-based."""
+        from .api import ARITH_OPCODES, COMPARE_OPCODES
+        stats = np.ascontiguousarray(stats, dtype=np.float64 if stats_type == "double" else np.int32).reshape(-1)
+        buf = stats if stats.size else np.zeros(1, stats.dtype)     # (an empty vector is handed over as one unread element)
+        m = np.ascontiguousarray(margin, dtype=np.int32).reshape(-1)
+        bad = ctypes.c_int64(-1)
+        if op in COMPARE_OPCODES:
+            args = (COMPARE_OPCODES[op], buf, stats.size, _RT[stats_type], m, m.size, byref(bad))
+            return self._logical_result("Compare_SVT_vector_begin", x, args, x.dimnames), False
+        args = (ARITH_OPCODES[op], buf, stats.size, _RT[stats_type], m, m.size, byref(bad))
+        return self._arith("Arith_SVT_vector_begin", x, args, x.dimnames)
+
     # abind / cbind / rbind (src/SparseArray_abind.c; include/svt_hip.h; HIP library only): begin leaves the result on the
     # device, Arith_SVT_end copies it out ---------------------------------------------------------------------------
     def C_abind_SVT_SparseArray_objects(self, objects, along: int, ans_type: str):

@@ -21,7 +21,7 @@ and the entry points the HIP library adds to them (include/svt_hip.h):
     C_colMedians_SVT      C_colQuantiles_SVT    C_colMads_SVT         C_colRanks_SVT
     C_rowMedians_SVT      C_rowQuantiles_SVT    C_rowMads_SVT         C_rowRanks_SVT
     C_matmul_SVT_mat      C_matmul_SVT_SVT      C_tcrossprod1_SVT     C_tcrossprod2_SVT_SVT
-    C_rowStatsFull_SVT
+    C_rowStatsFull_SVT    C_sweep_SVT (sweep(x, MARGIN, STATS, FUN): Arith / Compare with a vector per row or leaf)
 
 The product binds those names to the HIP library (``sparsearray_amd._hip``);
 there is no CPU implementation in this package.  A ``Session`` can be built
@@ -1164,6 +1164,109 @@ class Session:
             return self._Compare_SVT1_v2(op, e1, e2)
         flip = {"<=": ">=", ">=": "<=", "<": ">", ">": "<"}                     # flip_Compare_op, :22-23
         return self._Compare_SVT1_v2(flip.get(op, op), e2, e1)
+
+    # ------------------------------------------------------------------
+    # sweep(x, MARGIN, STATS, FUN).  The reference has no method: its Arith and Compare methods refuse every vector of
+    # length != 1, so t(t(x) / colSums(x)) and x * gene_weights have no sparse path there.  The rule is base R's sweep()
+    # on the dense array, offered where the result stays sparse: the scalar conditions of .Arith_SVT1_v2 and
+    # .Compare_SVT1_v2 asked of every element of STATS.
+    # ------------------------------------------------------------------
+    def sweep(self, x, MARGIN, STATS, FUN="/"):
+        """``sweep(x, MARGIN, STATS, FUN)``: ``x FUN STATS[k]`` with ``k`` the position along ``MARGIN`` (1-based: an int
+        or a strictly increasing run of consecutive dimensions; ``STATS`` has ``prod(dim(x)[MARGIN])`` elements, an
+        N-d one read column-major).  ``FUN``: one of ``* / ^ %% %/%`` or a comparison operator.  ``MARGIN = 1`` is what
+        R's recycling makes of ``x * w`` with ``length(w) == nrow(x)``.  Every element must keep the result sparse;
+        the first that does not is named (1-based).  The dimnames of ``x`` are kept."""
+        op = FUN
+        if op not in ARITH_OPCODES and op not in COMPARE_OPCODES:
+            raise SparseArrayError(f"invalid Arith or Compare operation \"{op}\"")
+        if not isinstance(x, SVT_SparseArray):
+            raise SparseArrayError("sweep() needs an SVT_SparseArray object as 'x' (a vector on the left and an "
+                                   "SVT_SparseArray object as 'STATS' is not supported)")
+        _check_not_NaArray("sweep", x)
+        compare = op in COMPARE_OPCODES
+        cls, ytype, length, _ = self._scalar_class_type(STATS)
+        if compare:
+            self._check_Compare_input_type(x.type, "SparseArray object")
+            if ytype not in _COMPARE_INPUT_TYPES:
+                raise SparseArrayError(f"comparison operations between SparseArray objects and {cls} vectors are not supported")
+            self._check_Compare_op_on_complex_vals(op, x.type, ytype)
+        else:
+            self._check_Arith_input_type(x.type, "SparseArray object")
+            if ytype not in _ARITH_INPUT_TYPES:
+                raise SparseArrayError(f"arithmetic operations between SparseArray objects and {cls} vectors are not supported")
+            if op not in ("*", "/", "^", "%%", "%/%"):
+                raise SparseArrayError(f"\"{op}\" is not supported between a SparseArray object and a {cls} vector "
+                                       "(result wouldn't be sparse in general)")
+        try:
+            ks = [MARGIN] if np.ndim(MARGIN) == 0 else list(MARGIN)
+            if any(isinstance(k, (bool, np.bool_)) or float(k) != int(k) for k in ks):
+                raise ValueError
+            margin = tuple(int(k) for k in ks)
+        except (TypeError, ValueError):
+            raise SparseArrayError("'MARGIN' must be a vector of dimension numbers")
+        if not margin or any(k < 1 or k > x.ndim for k in margin):
+            raise SparseArrayError("'MARGIN' does not match dim(x)")
+        if any(b != a + 1 for a, b in zip(margin, margin[1:])):
+            raise SparseArrayError("sweep() on SparseArray objects only supports a 'MARGIN' that is a strictly increasing run "
+                                   f"of consecutive dimensions; c({', '.join(map(str, margin))}) is not supported")
+        want = int(np.prod([x.dim[k - 1] for k in margin], dtype=np.int64))
+        if length != want:
+            raise SparseArrayError(f"length(STATS) is {length} but prod(dim(x)[MARGIN]) is {want}")
+        stats = np.asarray(STATS).reshape(-1, order="F")
+        if compare:
+            biggest = max(x.type, ytype, key=_COMPARE_INPUT_TYPES.index)
+            if biggest == "character":                      # (.Compare_SVT1_v2: <= and < first, then no operator at all)
+                if op in ("<=", "<"):
+                    self._sparsity_not_preserved(op, "type(x) is \"character\" or STATS holds strings")
+                self._must_homogenize_for_Compare(x.type, biggest)
+            if ytype == "complex":
+                nas = np.isnan(stats.real) | np.isnan(stats.imag)
+            else:
+                nas = np.isnan(stats) if ytype == "double" else stats.astype(np.int64) == NA_integer
+            v = stats.astype(np.complex128 if biggest == "complex" else np.float64)
+            v[nas] = 0
+            whens = [(nas, "is NA or NaN")]
+            if ytype == "logical" and op in ("<=", "<"):
+                whens.append((np.ones(length, bool), "is a logical or raw value"))
+            zero = {"==": (v == 0, "is 0 or FALSE or the empty string"), "!=": (v != 0, "is not 0, FALSE, or the empty string")}
+            if op in zero:
+                whens.append(zero[op])
+            elif biggest != "complex":
+                whens.append({"<=": (v >= 0, "is >= 0"), ">=": (v <= 0, "is <= 0, or FALSE, or the empty string"),
+                              "<": (v > 0, "is > 0"), ">": (v < 0, "is < 0")}[op])
+        else:
+            isint = ytype == "integer"
+            nas = stats.astype(np.int64) == NA_integer if isint else np.isnan(stats)
+            v = stats.astype(np.float64)
+            v[nas] = 1.0
+            whens = [(nas, "is NA or NaN")]
+            if op == "*" and not isint:
+                whens.append((np.isinf(v), "is Inf or -Inf"))
+            if op == "^":
+                whens.append((v <= 0, "is non-positive"))
+            if op != "*":
+                whens.append((v == 0, "== 0"))
+        bad = np.zeros(length, bool)
+        for mask, _ in whens:
+            bad |= mask
+        if bad.any():
+            k = int(np.argmax(bad))
+            self._sparsity_not_preserved(op, next(f"STATS[{k + 1}] {when}" for mask, when in whens if mask[k]))
+        if compare:
+            if biggest == "complex":                        # (the reference takes it; this library has no complex type)
+                raise SparseArrayUnsupported("comparison with a complex value is not offered by this library")
+            stype = biggest                                 # type(y) <- biggest_type, .Compare_SVT1_v2:113
+        else:
+            # .Arith_SVT1_v2:126-127
+            stype = "double" if (x.type == "double" and ytype == "integer") or op in ("/", "^") else ytype
+        if stype == "double" and ytype != "double":
+            stats = stats.astype(np.float64)                # (no NA is left to convert)
+        elif stype != "double":
+            stats = stats.astype(np.int32)
+        self._optional_entry("C_sweep_SVT", "Compare_SVT_vector_begin" if compare else "Arith_SVT_vector_begin")
+        ans, ovflow = self.SparseArray_Call("C_sweep_SVT", x, stats, stype, margin, op)
+        return ans if compare else self._warn_overflow((ans, ovflow))
 
     @staticmethod
     def _check_Logic_input_type(type_: str, what: str):

@@ -1,8 +1,10 @@
 // Arith and Math on resident sparse operands (C_Arith_SVT1_SVT2, C_Arith_SVT1_v2, C_unary_minus_SVT, C_Math_SVT of the
-// reference; the element rules are in svt_arith_rules.h).  Two families, both a count pass and a fill pass over the
+// reference; the element rules are in svt_arith_rules.h).  Three families, each a count pass and a fill pass over the
 // same tiles:
 //
 //   map     f(v) on the stored values of one operand; an entry is kept when its result is not zero
+//   sweep   f(v, stats[k]) on the stored values of one operand, k the entry's row, its leaf or both (sweep() and R's
+//           recycling of a vector of length nrow); kept when not zero; the vector is checked on the device first
 //   merge   x op y, op in + - *: the two entry sequences, each ascending by (column, row), merged; a position stored
 //           on one side meets an implicit zero, a position stored on both is ONE result entry
 //
@@ -441,6 +443,148 @@ __global__ __launch_bounds__(ARI_NT) void arith_merge_fill_kernel(AriSide X, con
 }
 
 // ---------------------------------------------------------------------------
+// sweep: f(v, stats[k]) on the stored values of one operand, k = (with_rows ? row : 0) + mult * ((leaf / stride) % len)
+// ---------------------------------------------------------------------------
+// The map's tile with two additions: the entry's row (the count pass reads row_idx only when stats has a row part) and
+// its leaf, found inside the tile's own column range [the leaf that holds entry ts, sh.qq[1]] as the merge finds the
+// column of a key.  A tile that lies inside one leaf (the common case of the leaf forms: q0 == q1) does no search and
+// one division per thread, and its gather is one address per wavefront; a tile that spans many leaves does one search of
+// log2(leaves in the tile) steps per entry, whatever the leaves' lengths.  The row form's gather is a plain global load
+// per entry: rows ascend inside a leaf, so a wavefront's 64 entries of one trip read ascending, often neighbouring,
+// elements.
+struct AriSweepOp {
+	int op, with_rows, narrow;      // narrow: ncol < 2^32, so a leaf number, stride and len fit 32 bits
+	int64_t mult;                   // with_rows ? nrow : 1
+	int64_t stride, len;
+};
+__device__ inline int64_t ari_sweep_leaf(const AriSweepOp &w, int64_t q)
+{
+	if (w.narrow)
+		return w.mult * (int64_t) ((uint32_t) q / (uint32_t) w.stride % (uint32_t) w.len);
+	return w.mult * (q / w.stride % w.len);
+}
+
+template <typename TX, typename TS, typename TO, int RULE>
+__device__ inline TO ari_sweep_eval(int op, TX v, TS s, int *ovf)
+{
+	if constexpr (RULE == ARI_RULE_COMPARE)
+		return svt_rule_compare(op, svt_rule_as_double(v), svt_rule_as_double(s));
+	else if constexpr (std::is_same<TO, int32_t>::value)
+		return svt_rule_arith_int(op, v, s, ovf);
+	else
+		return svt_rule_arith_double(op, svt_rule_as_double(v), svt_rule_as_double(s));
+}
+
+// the results of this thread's entries of the tile (striped), their rows (`rows`: read them even without a row part)
+// and whether they are kept; sh.qq as ari_tile_columns leaves it
+template <typename TX, typename TS, typename TO, int RULE>
+__device__ inline void ari_sweep_tile(const int64_t *col_ptr, const int32_t *row_idx, const TX *val, const TS *stats,
+				      const AriSweepOp &w, int64_t ts, int n, bool rows, AriShared &sh, int32_t (&row)[ARI_ITEMS],
+				      TO (&r)[ARI_ITEMS], bool (&keep)[ARI_ITEMS], int *ovf)
+{
+	TX v[ARI_ITEMS];
+#pragma unroll
+	for (int it = 0; it < ARI_ITEMS; it++) {
+		const int i = it * ARI_NT + threadIdx.x;
+		row[it] = 0;
+		if (i < n) {
+			v[it] = val[ts + i];
+			if (rows) row[it] = row_idx[ts + i];
+		}
+	}
+	__syncthreads();                                    // sh.qq
+	const AriColPtr cp = { col_ptr };
+	const int64_t q0 = sh.qq[0] > 0 ? sh.qq[0] - 1 : 0, q1 = sh.qq[1];        // col_ptr[q0] <= ts, the last entry is in leaf q1
+	const int64_t k0 = ari_sweep_leaf(w, q0);
+#pragma unroll
+	for (int it = 0; it < ARI_ITEMS; it++) {
+		const int i = it * ARI_NT + threadIdx.x;
+		keep[it] = false;
+		if (i < n) {
+			const int64_t kl = q0 >= q1 ? k0 : ari_sweep_leaf(w, ari_last_le(cp, q0, q1, ts + i));
+			r[it] = ari_sweep_eval<TX, TS, TO, RULE>(w.op, v[it], stats[(w.with_rows ? (int64_t) row[it] : 0) + kl], ovf);
+			keep[it] = !ari_is_zero(r[it]);
+		}
+	}
+}
+
+template <typename TX, typename TS, typename TO, int RULE>
+__global__ __launch_bounds__(ARI_NT) void arith_sweep_count_kernel(const int64_t *col_ptr, const int32_t *row_idx, const TX *val,
+								   const TS *stats, int64_t ncol, int64_t nnz, AriSweepOp w,
+								   int64_t *tile_cnt, int32_t *local)
+{
+	__shared__ AriShared sh;
+	const int64_t ts = (int64_t) blockIdx.x << ARI_SHIFT;
+	const int n = (int) (nnz - ts < ARI_TILE ? nnz - ts : ARI_TILE);
+	const AriPtr P = { col_ptr, NULL };
+	ari_tile_columns(P, ncol, ts, n, sh);
+	TO r[ARI_ITEMS];
+	int32_t row[ARI_ITEMS];
+	bool keep[ARI_ITEMS];
+	int ovf = 0;
+	ari_sweep_tile<TX, TS, TO, RULE>(col_ptr, row_idx, val, stats, w, ts, n, w.with_rows != 0, sh, row, r, keep, &ovf);
+	ari_rank(keep, sh);
+	ari_count_tail(P, ts, sh, tile_cnt, local);
+}
+
+template <typename TX, typename TS, typename TO, int RULE>
+__global__ __launch_bounds__(ARI_NT) void arith_sweep_fill_kernel(const int64_t *col_ptr, const int32_t *row_idx, const TX *val,
+								  const TS *stats, int64_t ncol, int64_t nnz, AriSweepOp w,
+								  const int64_t *tile_pre, int32_t *out_row_idx, TO *out_val, int *ovflow)
+{
+	__shared__ AriShared sh;
+	const int64_t ts = (int64_t) blockIdx.x << ARI_SHIFT;
+	const int n = (int) (nnz - ts < ARI_TILE ? nnz - ts : ARI_TILE);
+	const AriPtr P = { col_ptr, NULL };
+	ari_tile_columns(P, ncol, ts, n, sh);
+	TO r[ARI_ITEMS];
+	int32_t row[ARI_ITEMS];
+	bool keep[ARI_ITEMS];
+	int ovf = 0;
+	ari_sweep_tile<TX, TS, TO, RULE>(col_ptr, row_idx, val, stats, w, ts, n, true, sh, row, r, keep, &ovf);
+	ari_rank(keep, sh);
+	const int64_t base = tile_pre[blockIdx.x];
+#pragma unroll
+	for (int it = 0; it < ARI_ITEMS; it++) {
+		if (!keep[it]) continue;
+		const int64_t pos = ari_position(base, it, sh);
+		out_row_idx[pos] = row[it];
+		out_val[pos] = r[it];
+	}
+	if (ovf && ovflow != NULL) atomicOr(ovflow, 1);
+}
+
+// *bad <- the smallest index of an element of stats[0, n) that does not keep the result sparse (the word starts as all
+// ones).  The word is an error flag, not a position: the atomic decides no placement.
+template <typename TS, int RULE>
+__global__ __launch_bounds__(ARI_NT) void arith_sweep_valid_kernel(const TS *stats, int64_t n, int op, int s_Rtype,
+								   unsigned long long *bad)
+{
+	const int64_t step = (int64_t) gridDim.x * ARI_NT;
+	for (int64_t i = (int64_t) blockIdx.x * ARI_NT + threadIdx.x; i < n; i += step) {
+		const double s = (double) stats[i];
+		const bool ok = RULE == ARI_RULE_COMPARE ? svt_rule_compare_keeps_sparse(op, s, s_Rtype)
+							 : svt_rule_arith_keeps_sparse(op, s, s_Rtype);
+		if (!ok) {
+			atomicMin(bad, (unsigned long long) i);     // (this thread's later indices are larger)
+			break;
+		}
+	}
+}
+
+// arith_ptr_kernel for the sweep: nothing outside the workspace is written once an element was refused
+__global__ __launch_bounds__(ARI_NT) void arith_sweep_ptr_kernel(AriPtr P, int64_t ncol, int64_t total, const int64_t *tile_pre,
+								 int64_t ntiles, const int32_t *local, int64_t *out_col_ptr, int64_t *head)
+{
+	if ((unsigned long long) head[2] != ~0ULL) return;
+	const int64_t j = (int64_t) blockIdx.x * ARI_NT + threadIdx.x;
+	if (j == 0) head[1] = tile_pre[ntiles];
+	if (j > ncol) return;
+	const int64_t p = P(j);
+	out_col_ptr[j] = p >= total ? tile_pre[ntiles] : tile_pre[p >> ARI_SHIFT] + local[j];
+}
+
+// ---------------------------------------------------------------------------
 // launchers.  Workspace: [head 256: int64 total at byte 8][tile counts -> prefixes int64[ntiles + 1]]
 // [local int32[ncol + 1]][cut int64[ntiles + 1], the merge only][scratch of the scan]; the parts at multiples of 256
 // ---------------------------------------------------------------------------
@@ -610,6 +754,101 @@ int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void 
 		hipLaunchKernelGGL((arith_merge_fill_kernel<TX, TY, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0, s, X,
 				   xv, Y, yv, a.ncol, a.nrow, ari_op<decltype(rule)::value>(a), (const int64_t *) (w + L.cut),
 				   (const int64_t *) (w + L.tile), out_row_idx, (TO *) out_val, ovflow);
+	});
+	if (rc) return rc;
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// f(x values, stats values, result type tag, rule tag) by the rule and the three types: Compare for an int32 (logical or
+// integer) or double operand and vector; Arith with an int32 result for int32 x int32 alone
+template <class F>
+static inline int arith_sweep_by_types(const ArithSweepArgs &a, F &&f)
+{
+	const bool xd = a.Rtype == SVT_REALSXP, sd = a.stats_Rtype == SVT_REALSXP;
+	if (a.rule == ARI_RULE_COMPARE) {
+		if (xd && sd) f((const double *) a.val, (const double *) a.stats, (int32_t *) NULL, AriRule<ARI_RULE_COMPARE>());
+		else if (xd) f((const double *) a.val, (const int32_t *) a.stats, (int32_t *) NULL, AriRule<ARI_RULE_COMPARE>());
+		else if (sd) f((const int32_t *) a.val, (const double *) a.stats, (int32_t *) NULL, AriRule<ARI_RULE_COMPARE>());
+		else f((const int32_t *) a.val, (const int32_t *) a.stats, (int32_t *) NULL, AriRule<ARI_RULE_COMPARE>());
+		return 0;
+	}
+	if (a.rule != ARI_RULE_ARITH) return svt_set_error("arith sweep: no kernel for this rule");
+	if (a.out_Rtype == SVT_INTSXP) {
+		if (xd || sd) return svt_set_error("arith sweep: no kernel for these types");
+		f((const int32_t *) a.val, (const int32_t *) a.stats, (int32_t *) NULL, AriRule<ARI_RULE_ARITH>());
+	} else if (xd && sd) f((const double *) a.val, (const double *) a.stats, (double *) NULL, AriRule<ARI_RULE_ARITH>());
+	else if (xd) f((const double *) a.val, (const int32_t *) a.stats, (double *) NULL, AriRule<ARI_RULE_ARITH>());
+	else if (sd) f((const int32_t *) a.val, (const double *) a.stats, (double *) NULL, AriRule<ARI_RULE_ARITH>());
+	else f((const int32_t *) a.val, (const int32_t *) a.stats, (double *) NULL, AriRule<ARI_RULE_ARITH>());
+	return 0;
+}
+static inline AriSweepOp arith_sweep_op(const ArithSweepArgs &a)
+{
+	return AriSweepOp{ a.op, a.with_rows, a.ncol <= 0xFFFFFFFFLL, a.with_rows ? a.nrow : 1, a.stride, a.len };
+}
+
+int launch_arith_sweep_count(const ArithSweepArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s)
+{
+	const ArithWs L = arith_ws(a.ncol, a.nnz, false);
+	if (L.ntiles > 0x7FFFFFFFLL)
+		return svt_set_error("svt_dev_arith_sweep_count: too many nonzeros");
+	char *w = (char *) ws;
+	int64_t *tile = (int64_t *) (w + L.tile);
+	unsigned long long *bad = (unsigned long long *) (w + 16);
+	HIP_TRY(hipMemsetAsync(w, 0, 256, s));
+	HIP_TRY(hipMemsetAsync(bad, 0xFF, 8, s));
+	HIP_TRY(hipMemsetAsync(tile + L.ntiles, 0, 8, s));
+	const int64_t nstats = (a.with_rows ? a.nrow : 1) * a.len;
+	if (nstats > 0) {
+		const unsigned nb = blocks_for(nstats < 1024 * ARI_NT ? nstats : 1024 * ARI_NT);
+		const bool cmp = a.rule == ARI_RULE_COMPARE;
+		if (a.stats_Rtype == SVT_REALSXP) {
+			if (cmp) hipLaunchKernelGGL((arith_sweep_valid_kernel<double, ARI_RULE_COMPARE>), dim3(nb), dim3(ARI_NT), 0, s,
+						    (const double *) a.stats, nstats, a.op, a.stats_Rtype, bad);
+			else hipLaunchKernelGGL((arith_sweep_valid_kernel<double, ARI_RULE_ARITH>), dim3(nb), dim3(ARI_NT), 0, s,
+						(const double *) a.stats, nstats, a.op, a.stats_Rtype, bad);
+		} else {
+			if (cmp) hipLaunchKernelGGL((arith_sweep_valid_kernel<int32_t, ARI_RULE_COMPARE>), dim3(nb), dim3(ARI_NT), 0, s,
+						    (const int32_t *) a.stats, nstats, a.op, a.stats_Rtype, bad);
+			else hipLaunchKernelGGL((arith_sweep_valid_kernel<int32_t, ARI_RULE_ARITH>), dim3(nb), dim3(ARI_NT), 0, s,
+						(const int32_t *) a.stats, nstats, a.op, a.stats_Rtype, bad);
+		}
+		HIP_TRY(hipGetLastError());
+	}
+	if (L.ntiles > 0) {
+		const AriSweepOp op = arith_sweep_op(a);
+		const int rc = arith_sweep_by_types(a, [&](auto *v, auto *st, auto *o, auto rule) {
+			typedef std::remove_const_t<std::remove_pointer_t<decltype(v)>> TX;
+			typedef std::remove_const_t<std::remove_pointer_t<decltype(st)>> TS;
+			typedef std::remove_pointer_t<decltype(o)> TO;
+			hipLaunchKernelGGL((arith_sweep_count_kernel<TX, TS, TO, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT),
+					   0, s, a.col_ptr, a.row_idx, v, st, a.ncol, a.nnz, op, tile, (int32_t *) (w + L.local));
+		});
+		if (rc) return rc;
+	}
+	if (launch_exclusive_scan_i64(tile, L.ntiles + 1, w + L.scan, s))
+		return -1;
+	const AriPtr P = { a.col_ptr, NULL };
+	hipLaunchKernelGGL(arith_sweep_ptr_kernel, dim3(blocks_for(a.ncol + 1)), dim3(ARI_NT), 0, s, P, a.ncol, a.nnz, tile, L.ntiles,
+			   (const int32_t *) (w + L.local), out_col_ptr, (int64_t *) w);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int launch_arith_sweep_fill(const ArithSweepArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s)
+{
+	const ArithWs L = arith_ws(a.ncol, a.nnz, false);
+	if (L.ntiles == 0)
+		return 0;
+	const int64_t *tile = (const int64_t *) ((const char *) ws + L.tile);
+	const AriSweepOp op = arith_sweep_op(a);
+	const int rc = arith_sweep_by_types(a, [&](auto *v, auto *st, auto *o, auto rule) {
+		typedef std::remove_const_t<std::remove_pointer_t<decltype(v)>> TX;
+		typedef std::remove_const_t<std::remove_pointer_t<decltype(st)>> TS;
+		typedef std::remove_pointer_t<decltype(o)> TO;
+		hipLaunchKernelGGL((arith_sweep_fill_kernel<TX, TS, TO, decltype(rule)::value>), dim3((unsigned) L.ntiles), dim3(ARI_NT), 0,
+				   s, a.col_ptr, a.row_idx, v, st, a.ncol, a.nnz, op, tile, out_row_idx, (TO *) out_val, ovflow);
 	});
 	if (rc) return rc;
 	HIP_TRY(hipGetLastError());

@@ -1,7 +1,7 @@
 // The element rules of Arith and Math on sparse operands (src/SparseVec_Arith.c, src/SparseVec_Math.c of the
 // reference; R's arithmetic.c for the operators), of Compare and Logic, and of subassignment, each stated once for the
 // device kernels (kernels_arith.hip) and for a host program (tests/arith_rules_main.cpp, compare_rules_main.cpp,
-// assign_rules_main.cpp): plain C++, no HIP header needed.
+// assign_rules_main.cpp, sweep_rules_main.cpp): plain C++, no HIP header needed.
 #pragma once
 
 #include <math.h>
@@ -354,6 +354,36 @@ SVT_HD inline int32_t svt_rule_logic(int op, int32_t x, int32_t y)
 	if (x == SVT_NA_INT || y == SVT_NA_INT)
 		return SVT_NA_INT;
 	return 0;
+}
+
+// ---- sweep(x, MARGIN, STATS, op): x op STATS[k], one element of a vector per row or per leaf ----
+// Whether the element `s` of a vector of type s_Rtype keeps `x op s` sparse, i.e. whether 0 op s is zero (FALSE): the
+// scalar conditions of .Arith_SVT1_v2 and .Compare_SVT1_v2 (R/SparseArray-Arith-methods.R:113-124,
+// R/SparseArray-Compare-methods.R:75-112), asked of every element.  An integer or logical element arrives as its double
+// value, INT_MIN standing for NA, as the scalar of the maps does.
+SVT_HD inline double svt_rule_element(double s, int s_Rtype)
+{
+	return s_Rtype != SVT_REALSXP && s == -2147483648.0 ? svt_rule_na_real() : s;
+}
+// *: not NA / NaN and finite; / %% %/%: not NA / NaN and != 0; ^: not NA / NaN and > 0; + and -: no element does
+SVT_HD inline bool svt_rule_arith_keeps_sparse(int op, double s, int s_Rtype)
+{
+	const double v = svt_rule_element(s, s_Rtype);
+	if (v != v)
+		return false;
+	switch (op) {
+	case SVT_ARITH_MULT: return v != svt_rule_inf() && v != -svt_rule_inf();
+	case SVT_ARITH_DIV:
+	case SVT_ARITH_MOD:
+	case SVT_ARITH_IDIV: return v != 0.0;
+	case SVT_ARITH_POW: return v > 0.0;
+	}
+	return false;
+}
+// not NA / NaN, and 0 op s is FALSE
+SVT_HD inline bool svt_rule_compare_keeps_sparse(int op, double s, int s_Rtype)
+{
+	return svt_rule_compare(op, 0.0, svt_rule_element(s, s_Rtype)) == 0;
 }
 
 // ---- subassignment x[i, j] <- value (src/SparseArray_subassignment.c of the reference) ----

@@ -306,6 +306,27 @@ int launch_arith_map_count(const ArithMapArgs &a, int64_t *out_col_ptr, void *ws
 int launch_arith_map_fill(const ArithMapArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
 int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
 int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
+// The sweep, a third family: f(v, stats[k]) on the stored values of one operand, k = (with_rows ? row : 0) +
+// (with_rows ? nrow : 1) * ((leaf / stride) % len) -- one element of `stats` per row, per leaf, or per row of a group of
+// leaves.  `rule`: ARI_RULE_ARITH (op one of * / ^ %% %/%) or ARI_RULE_COMPARE.  The workspace is the map's
+// (arith_ws_bytes(ncol, nnz, 0)); the count launcher first checks every element of `stats` and leaves, in the head of
+// `ws`, [int64 at byte 8: the nonzeros of the result][uint64 at byte 16: the smallest index of an element that does not
+// keep the result sparse, or all ones]; with such an element out_col_ptr is not written.  All asynchronous.
+struct ArithSweepArgs {
+	const int64_t *col_ptr;
+	const int32_t *row_idx;
+	const void *val;
+	int Rtype;
+	int64_t nrow, ncol, nnz;
+	int rule, op;
+	const void *stats;
+	int stats_Rtype;
+	int with_rows;
+	int64_t stride, len;
+	int out_Rtype;
+};
+int launch_arith_sweep_count(const ArithSweepArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_arith_sweep_fill(const ArithSweepArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
 
 // Subassignment (kernels_subassign.hip): the placed operand Y of x[rows, leaves] <- value and the two cover tables,
 // for the merge under ARI_RULE_ASSIGN.  `rows` / `leaves`: device int32, 0-based; nrows_sel / nleaves_sel < 0: the whole

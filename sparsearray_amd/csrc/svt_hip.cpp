@@ -1807,6 +1807,178 @@ extern "C" int svt_dev_logic_merge(const svt_dev_csc *x, const svt_dev_csc *y, i
 	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 
+// ---- sweep: x op stats[k], Arith or Compare with one element of a device vector per row or per leaf ----
+// One operation of the third family: the one statement of its checks and of count / fill / compose.  The statuses are
+// those of the maps; what is added is the geometry of the vector and the element the device refused.
+struct SweepCall {
+	const char *who;
+	int rule, op;
+	const svt_dev_csc *x;
+	const void *stats;
+	int stats_Rtype;
+	int64_t stats_len;
+	int with_rows;
+	int64_t stride, len;
+	int out_Rtype = 0;
+
+	size_t need() const { return arith_ws_bytes(x->ncol, x->nnz, 0); }
+	int check(size_t ws_bytes)
+	{
+		if (x == NULL)
+			return svt_set_error("%s: an operand is needed", who);
+		if (rule == ARI_RULE_COMPARE) {
+			if (!logical_family_type(x->Rtype) || !logical_family_type(stats_Rtype))
+				return svt_set_error("%s: the operand and the vector must be of type \"logical\", \"integer\" or \"double\"", who);
+			if (op < SVT_COMPARE_EQ || op > SVT_COMPARE_GT)
+				return svt_set_error("%s: unknown operation (opcode %d)", who, op);
+			out_Rtype = SVT_LGLSXP;
+		} else {
+			if (x->Rtype == SVT_LGLSXP)
+				return svt_set_error("arithmetic operation not supported on SparseArray object of type() \"logical\"");
+			if (op == SVT_ARITH_ADD || op == SVT_ARITH_SUB)
+				return svt_set_error("%s: \"%s\" is not supported between a SparseArray object and a vector (result wouldn't be "
+						     "sparse in general)", who, op == SVT_ARITH_ADD ? "+" : "-");
+			out_Rtype = svt_rule_out_Rtype(SVT_ARITH_SCALAR, op, x->Rtype, stats_Rtype);
+			if (out_Rtype == 0)
+				return svt_set_error("%s: unknown operation (opcode %d) or operand type", who, op);
+		}
+		// the vector against the three integers of the index k = (with_rows ? row : 0) + (with_rows ? nrow : 1) * ((leaf / stride) % len)
+		if ((with_rows != 0 && with_rows != 1) || stride < 1 || len < 0 || stats_len < 0)
+			return svt_set_error("%s: invalid vector geometry", who);
+		if (x->ncol > 0 && (len < 1 || stride > x->ncol || len > x->ncol / stride || x->ncol % (stride * len) != 0))
+			return svt_set_error("%s: 'stride' and 'len' do not divide the operand's leaves", who);
+		const int64_t mult = with_rows ? x->nrow : 1;
+		if ((len != 0 && mult > INT64_MAX / len) || stats_len != mult * len)
+			return svt_set_error("%s: the vector's length does not match the extents it sweeps (%lld, expected %lld)", who,
+					     (long long) stats_len, (long long) (len != 0 && mult > INT64_MAX / len ? -1 : mult * len));
+		if (stats_len > 0 && stats == NULL)
+			return svt_set_error("%s: the vector is needed", who);
+		if (x->na_background)
+			return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		return 0;
+	}
+	ArithSweepArgs args() const
+	{
+		ArithSweepArgs a;
+		a.col_ptr = x->col_ptr; a.row_idx = x->row_idx; a.val = x->val; a.Rtype = x->Rtype;
+		a.nrow = x->nrow; a.ncol = x->ncol; a.nnz = x->nnz;
+		a.rule = rule; a.op = op; a.stats = stats; a.stats_Rtype = stats_Rtype;
+		a.with_rows = with_rows; a.stride = stride; a.len = len; a.out_Rtype = out_Rtype;
+		return a;
+	}
+	int count(int64_t *out_col_ptr, int64_t *out_nnz, int64_t *bad_index, void *ws, size_t ws_bytes, void *stream)
+	{
+		if (bad_index != NULL) *bad_index = -1;
+		if (const int rc = check(ws_bytes))
+			return rc;
+		hipStream_t st = (hipStream_t) stream;
+		if (launch_arith_sweep_count(args(), out_col_ptr, ws, st))
+			return -1;
+		int64_t head[3] = { 0, 0, 0 };                      // [1] the result's nonzeros, [2] the refused element
+		HIP_TRY(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		if (head[2] != -1) {
+			if (bad_index != NULL) *bad_index = head[2];
+			return svt_set_error("%s: element %lld of the vector does not keep the result sparse", who, (long long) head[2]);
+		}
+		*out_nnz = head[1];
+		return 0;
+	}
+	int fill(int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream)
+	{
+		if (const int rc = check(ws_bytes))
+			return rc;
+		return launch_arith_sweep_fill(args(), out_row_idx, out_val, ovflow, ws, (hipStream_t) stream);
+	}
+	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype_p, int64_t *out_nnz,
+		    int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, int *ovflow, int64_t *bad_index, void *stream)
+	{
+		if (bad_index != NULL) *bad_index = -1;
+		if (alloc == NULL || release == NULL)
+			return svt_set_error("%s: an allocator is needed", who);
+		if (const int rc = x == NULL ? check(0) : check(need()))
+			return rc;
+		SubsetMem mem = { alloc, release, ctx };
+		SubsetCsc R(mem);
+		SubsetWs ws(mem);
+		int64_t nnz = 0;
+		if (R.shape(x, x->nrow, x->ncol) || ws.get(need()))
+			return -1;
+		R.c.Rtype = out_Rtype;
+		if (count(R.c.col_ptr, &nnz, bad_index, ws.p, ws.n, stream) || R.entries(nnz) ||
+		    fill(R.c.row_idx, R.c.val, ovflow, ws.p, ws.n, stream))
+			return -1;
+		*out_Rtype_p = out_Rtype;
+		*out_nnz = nnz;
+		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
+		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
+		return 0;
+	}
+};
+
+extern "C" size_t svt_dev_sweep_ws_bytes(int64_t ncol, int64_t nnz)
+{
+	return arith_ws_bytes(ncol, nnz, 0);
+}
+extern "C" int svt_dev_arith_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+					 int with_rows, int64_t stride, int64_t len, int64_t *out_col_ptr, int64_t *out_nnz,
+					 int64_t *bad_index, void *ws, size_t ws_bytes, void *stream)
+{
+	SweepCall c = { "svt_dev_arith_sweep_count", ARI_RULE_ARITH, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, bad_index, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_arith_sweep_fill(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+					int with_rows, int64_t stride, int64_t len, const int64_t *out_col_ptr, int32_t *out_row_idx,
+					void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile prefixes in `ws` place the entries)
+	SweepCall c = { "svt_dev_arith_sweep_fill", ARI_RULE_ARITH, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] { return c.fill(out_row_idx, out_val, ovflow, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_arith_sweep(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+				   int with_rows, int64_t stride, int64_t len, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+				   void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+				   void **out_val, int *ovflow, int64_t *bad_index, void *stream)
+{
+	SweepCall c = { "svt_dev_arith_sweep", ARI_RULE_ARITH, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] {
+		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, ovflow, bad_index, stream);
+	});
+}
+extern "C" int svt_dev_compare_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+					   int with_rows, int64_t stride, int64_t len, int64_t *out_col_ptr, int64_t *out_nnz,
+					   int64_t *bad_index, void *ws, size_t ws_bytes, void *stream)
+{
+	SweepCall c = { "svt_dev_compare_sweep_count", ARI_RULE_COMPARE, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, bad_index, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_compare_sweep_fill(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+					  int with_rows, int64_t stride, int64_t len, const int64_t *out_col_ptr, int32_t *out_row_idx,
+					  int32_t *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;
+	SweepCall c = { "svt_dev_compare_sweep_fill", ARI_RULE_COMPARE, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_compare_sweep(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+				     int with_rows, int64_t stride, int64_t len, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+				     void *ctx, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val,
+				     int64_t *bad_index, void *stream)
+{
+	SweepCall c = { "svt_dev_compare_sweep", ARI_RULE_COMPARE, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] {
+		int rt = 0;
+		void *val = NULL;
+		if (out_val == NULL)
+			return svt_set_error("%s: 'out_val' is needed", c.who);
+		const int rc = c.compose(alloc, release, ctx, &rt, out_nnz, out_col_ptr, out_row_idx, &val, NULL, bad_index, stream);
+		if (rc == 0) *out_val = (int32_t *) val;
+		return rc;
+	});
+}
+
 // ---- abind / cbind / rbind (kernels_abind.hip; C_abind_SVT_SparseArray_objects, src/SparseArray_abind.c) ----
 extern "C" int svt_dev_abind_tile(void)
 {
@@ -4031,6 +4203,98 @@ extern "C" int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int
 {
 	return compare_begin("svt_Logic_SVT_SVT_begin", ARI_RULE_LOGIC, op, x, y, true, 0.0, 0, res, out_nnz);
 }
+// sweep(x, MARGIN, STATS, op) on host operands: the margin becomes the three integers of the device index here, the
+// operand and the vector go up, SweepCall::compose() runs on the first device, the result stays there until `end`.
+// `margin`: 1-based, a strictly increasing run of consecutive dimensions.  With dimension 1 in it the vector has a row
+// part and the leaves of the run's other dimensions are the fastest ones (stride 1); else the run starts `stride` leaves
+// apart.
+static int sweep_geometry(const char *who, const svt_view *x, const int *margin, int nmargin, int *with_rows, int64_t *stride,
+			  int64_t *len)
+{
+	if (margin == NULL || nmargin < 1 || nmargin > x->ndim)
+		return svt_set_error("%s: 'margin' must name between 1 and %d dimensions", who, x->ndim);
+	for (int a = 0; a < nmargin; a++)
+		if (margin[a] < 1 || margin[a] > x->ndim || (a > 0 && margin[a] != margin[a - 1] + 1))
+			return svt_set_error("%s: 'margin' must be a strictly increasing run of consecutive dimensions of the operand", who);
+	*with_rows = margin[0] == 1;
+	*stride = 1;
+	*len = 1;
+	for (int a = 1; a < margin[0] - 1; a++) *stride *= x->dim[a];
+	for (int a = 0; a < nmargin; a++)
+		if (margin[a] > 1) *len *= x->dim[margin[a] - 1];
+	return 0;
+}
+static int sweep_begin_impl(const char *who, int rule, const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
+			    const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz,
+			    int *ovflow)
+{
+	if (res == NULL || out_Rtype == NULL || out_nnz == NULL)
+		return svt_set_error("%s: 'res', 'out_Rtype' and 'out_nnz' are needed", who);
+	*res = NULL;
+	if (bad_index != NULL) *bad_index = -1;
+	if (ensure_init() || check_view(x))
+		return -1;
+	if (!logical_family_type(stats_Rtype))
+		return svt_set_error("%s: the vector must be of type \"logical\", \"integer\" or \"double\"", who);
+	int with_rows = 0;
+	int64_t stride = 1, len = 1;
+	if (sweep_geometry(who, x, margin, nmargin, &with_rows, &stride, &len))
+		return -1;
+	if (stats_len < 0 || (stats_len > 0 && stats == NULL))
+		return svt_set_error("%s: the vector is needed", who);
+	CscGuard A(x);
+	if (A.h == NULL) return -1;
+	DevBuf dv;
+	DevFlag ov;
+	if (dv.upload(stats, (size_t) stats_len * elt_size(stats_Rtype)) || ov.init())
+		return -1;
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
+	SweepCall c = { who, rule, op, A.h, dv.p, stats_Rtype, stats_len, with_rows, stride, len };
+	int rt = 0;
+	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, ov.ptr(), bad_index,
+		      NULL) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
+		svt_release(h);
+		return -1;
+	}
+	h->Rtype = rt;
+	int raised = 0;
+	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
+	if (ov.read(&raised) || r == NULL) {
+		svt_release(h);
+		free(r);
+		return r == NULL ? svt_set_error("out of memory") : -1;
+	}
+	r->h = h;
+	*res = r;
+	*out_Rtype = rt;
+	*out_nnz = h->nnz;
+	if (ovflow != NULL) *ovflow = raised;
+	return 0;
+}
+extern "C" int svt_Arith_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
+					  const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res, int *out_Rtype,
+					  int64_t *out_nnz, int *ovflow)
+{
+	return abi_status([&] {
+		return sweep_begin_impl("svt_Arith_SVT_vector_begin", ARI_RULE_ARITH, x, op, stats, stats_len, stats_Rtype, margin, nmargin,
+					bad_index, res, out_Rtype, out_nnz, ovflow);
+	});
+}
+extern "C" int svt_Compare_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
+					    const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res,
+					    int64_t *out_nnz)
+{
+	return abi_status([&] {
+		int rt = 0;
+		return sweep_begin_impl("svt_Compare_SVT_vector_begin", ARI_RULE_COMPARE, x, op, stats, stats_len, stats_Rtype, margin, nmargin,
+					bad_index, res, &rt, out_nnz, NULL);
+	});
+}
+
 // x[i, j, ...] <- value on host operands (.subassign_SVT_by_Nindex, C_subassign_SVT_with_short_Rvector): the subscripts
 // are checked and those of dims 2..N expanded into the leaf list here, on the host, before anything is uploaded; the
 // composition is SubassignCall::compose() on the first device, the result stays there until svt_Arith_SVT_end.

@@ -380,6 +380,48 @@ class DeviceCSC:
         return self._logical_result(lambda *a: _lib().svt_dev_compare_map(self.handle, COMPARE_OPCODES[op], float(other),
                                                                           s_Rtype, *a))
 
+    def sweep(self, op: str, stats, margin=2, dim=None, logical: bool = False) -> "DeviceCSC":
+        """``sweep(x, margin, stats, op)`` on the device (include/svt_hip.h, svt_dev_arith_sweep / svt_dev_compare_sweep):
+        every stored value meets the element of ``stats`` that belongs to its position along ``margin`` -- 1-based, an
+        int or a strictly increasing run of consecutive dimensions of the array of extents ``dim`` (default
+        (nrow, ncol): 1 the rows, 2 the columns).  ``t(t(x) / colSums(x))`` is ``x.sweep("/", colstats(x, "sum")[0])``,
+        R's ``x * w`` with ``len(w) == nrow`` is ``x.sweep("*", w, 1)``.  ``op``: one of ``* / ^ %% %/%`` or of the six
+        comparison operators.  ``stats``: a float64 or int32 tensor on the operand's device (bool, or int32 with
+        ``logical=True``: logical, Compare only), or an array-like; prod(dim[margin]) elements, an N-d one read
+        column-major.  Returns a new DeviceCSC, with ``ovflow`` for Arith, logical for Compare.  An element that would
+        not keep the result sparse (NA, zero under ``/``, ...) raises SparseArrayError naming its 0-based index and
+        value; the library finds it on the device and nothing was written."""
+        from .api import ARITH_OPCODES, COMPARE_OPCODES
+        compare = op in COMPARE_OPCODES
+        if not compare and op not in ARITH_OPCODES:
+            raise SparseArrayError(f"unknown Arith or Compare operation {op!r}")
+        if op in ("+", "-"):
+            raise SparseArrayError(f"\"{op}\" is not supported between a SparseArray object and a vector "
+                                   "(result wouldn't be sparse in general)")
+        with_rows, stride, length = sweep_form(self._dim(dim), margin)
+        if isinstance(stats, torch.Tensor):
+            if stats.device != self.val.device:
+                raise SparseArrayError("'stats' must be on the operand's device")
+            if stats.ndim > 1:
+                stats = stats.permute(*reversed(range(stats.ndim)))
+        else:
+            stats = np.asarray(stats).reshape(-1, order="F")
+        vals, s_Rtype = _assign_values(stats, self.val.device, logical)
+        bad = c_int64(-1)
+        geometry = (vals.data_ptr(), s_Rtype, vals.numel(), with_rows, stride, length)
+        try:
+            if compare:
+                return self._logical_result(lambda *a: _lib().svt_dev_compare_sweep(
+                    self.handle, COMPARE_OPCODES[op], *geometry, *a[:-1], ctypes.byref(bad), a[-1]))
+            return self._arith_result(lambda *a: _lib().svt_dev_arith_sweep(
+                self.handle, ARITH_OPCODES[op], *geometry, *a[:-1], ctypes.byref(bad), a[-1]))
+        except SparseArrayError as e:
+            if bad.value < 0:
+                raise
+            value = vals[bad.value].item()                      # (the error path's one read of an element)
+            raise SparseArrayError(f"sweep(\"{op}\"): stats[{bad.value}] = {value!r} does not keep the result sparse "
+                                   "(result wouldn't be sparse)") from e
+
     def logic(self, op: str, other: "DeviceCSC") -> "DeviceCSC":
         """``self & other`` / ``self | other`` on the device for two logical operands (svt_dev_logic_merge)."""
         from .api import LOGIC_OPCODES
@@ -576,6 +618,25 @@ ARITH_MERGE, ARITH_SCALAR, ARITH_NEG, ARITH_MATH = 0, 1, 2, 3
 def arith_tile() -> int:
     """Entries per workgroup tile of the Arith / Math kernels (svt_dev_arith_tile).  Needs no GPU."""
     return int(_hip.load_library().svt_dev_arith_tile())
+
+
+def sweep_form(dim, margin):
+    """(with_rows, stride, len) of ``sweep(x, margin, ...)`` for the array of extents ``dim`` (include/svt_hip.h,
+    svt_dev_arith_sweep): the entry of row r in leaf q meets element
+    ``(r if with_rows else 0) + (nrow if with_rows else 1) * ((q // stride) % len)`` of the column-major array of the
+    margin's extents.  ``margin``: 1-based, an int or a strictly increasing run of consecutive dimensions; any other
+    raises SparseArrayError.  Needs no GPU."""
+    dim = tuple(int(d) for d in dim)
+    m = (margin,) if isinstance(margin, (int, np.integer)) else tuple(margin)
+    if (not m or any(isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) for k in m)
+            or any(k < 1 or k > len(dim) for k in m)):
+        raise SparseArrayError(f"'margin' must name dimensions between 1 and {len(dim)}")
+    if any(b != a + 1 for a, b in zip(m, m[1:])):
+        raise SparseArrayError("'margin' must be a strictly increasing run of consecutive dimensions (e.g. 2 or (2, 3)); "
+                               f"{tuple(int(k) for k in m)} is not supported")
+    stride = int(np.prod(dim[1:max(m[0] - 1, 1)], dtype=np.int64))
+    length = int(np.prod([dim[k - 1] for k in m if k > 1], dtype=np.int64))
+    return int(m[0] == 1), stride, length
 
 
 def subset_tile() -> int:
