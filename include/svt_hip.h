@@ -1098,6 +1098,92 @@ int svt_Arith_SVT_vector_begin(const svt_view *x, int op, const void *stats, int
 int svt_Compare_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
 				 const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res, int64_t *out_nnz);
 
+/* pmin() / pmax() and is.na() / is.nan() / is.infinite() on SVT operands (.pminmax2 and .isFUN_SVT,
+   R/SparseArray-misc-methods.R; C_SVT_apply_isFUN): further rules on the three kernel families of Arith
+   (kernels_arith.hip; the element rules svt_rule_pminmax and svt_rule_isfun of svt_arith_rules.h), with the same tiles,
+   the same 64-bit placement and the same workspaces: svt_dev_arith_merge_ws_bytes() sizes the workspace of the merge,
+   svt_dev_arith_map_ws_bytes() that of the two maps, svt_dev_sweep_ws_bytes() that of the sweep.
+
+   `op` of the pminmax calls is SVT_PMINMAX_MIN or SVT_PMINMAX_MAX, ORed with SVT_PMINMAX_NA_RM for na.rm = TRUE; any
+   other value answers < 0.  Both sides are widened to the result's type svt_dev_pminmax_out_Rtype() -- the wider of
+   logical < integer < double; NA_integer_ becomes NA_real_ -- and the result is, without na.rm,
+   isna(x) ? x : isna(y) ? y : (y < x ? y : x) (pmax: y > x), with it isna(y) ? x : isna(x) ? y : the same; isna is NaN
+   or NA_real_ for a double, NA_integer_ else; ties take x; the chosen side's bits are returned unchanged.
+
+     pminmax merge  two operands of the same nrow and the same number of leaves, each LGLSXP, INTSXP or REALSXP.  At
+                    every position stored in x or in y the value is rule(x or 0, y or 0); it is stored unless it == 0
+                    (-0.0 and integer 0 too; a NaN or NA stays).  A stored zero of an operand is an ordinary value.
+     pminmax map    pmin(x, s) / pmax(x, s) for a scalar s of type s_Rtype (an integer or logical s is passed as its
+                    double value, INT_MIN standing for NA), provided pmin(0, s) == 0: s not NA / NaN, and >= 0 for pmin,
+                    <= 0 for pmax; any other s answers < 0.  With na.rm an NA entry of x becomes s.
+     pminmax sweep  the same rule as f(v, stats[k]), the vector and its geometry as in svt_dev_arith_sweep; every
+                    element must satisfy the scalar's condition, the first that does not is named in *bad_index and
+                    nothing is written outside `ws`.
+     isfun map      op SVT_IS_NA, SVT_IS_NAN or SVT_IS_INFINITE on the stored values of an LGLSXP, INTSXP or REALSXP
+                    operand: a new LGLSXP operand that stores int32 1 where the function is TRUE.  is.na is ISNAN for a
+                    double and NA_integer_ else; is.nan a NaN that is not NA_real_; is.infinite +-Inf; the last two are
+                    FALSE everywhere on an integer or logical operand (base R's answer).
+
+   The count / fill / composition contract is that of svt_dev_arith_* and svt_dev_compare_*: `_count` writes out_col_ptr
+   int64[ncol + 1] and *out_nnz and synchronises `stream` once; `_fill` is asynchronous, reads the workspace as the
+   count call left it (same operands, same operation) and writes out_row_idx int32[*out_nnz] and out_val; rows ascend in
+   every result column; no atomic decides a position; two runs give the same bits; there is no overflow word.  Status:
+   < 0 for extents that differ, a workspace too small, an unknown opcode, a type outside logical / integer / double, a
+   scalar or vector element that does not keep the result sparse; > 0 for an operand with na_background.  On a non-zero
+   status nothing is written outside `ws`.  Alignment and workspace: "Workspaces" above. */
+enum { SVT_PMINMAX_MIN = 1, SVT_PMINMAX_MAX = 2, SVT_PMINMAX_NA_RM = 4 };
+enum { SVT_IS_NA = 1, SVT_IS_NAN = 2, SVT_IS_INFINITE = 3 };
+/* SVT_LGLSXP, SVT_INTSXP or SVT_REALSXP: the wider of the two types; 0 when either is none of them.  Needs no GPU. */
+int svt_dev_pminmax_out_Rtype(int x_Rtype, int y_Rtype);
+int svt_dev_pminmax_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr, int64_t *out_nnz,
+				void *ws, size_t ws_bytes, void *stream);
+int svt_dev_pminmax_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+			       int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_pminmax_map_count(const svt_dev_csc *x, int op, double s, int s_Rtype, int64_t *out_col_ptr, int64_t *out_nnz,
+			      void *ws, size_t ws_bytes, void *stream);
+int svt_dev_pminmax_map_fill(const svt_dev_csc *x, int op, double s, int s_Rtype, const int64_t *out_col_ptr,
+			     int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_pminmax_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+				int with_rows, int64_t stride, int64_t len, int64_t *out_col_ptr, int64_t *out_nnz,
+				int64_t *bad_index, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_pminmax_sweep_fill(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+			       int with_rows, int64_t stride, int64_t len, const int64_t *out_col_ptr, int32_t *out_row_idx,
+			       void *out_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_isfun_map_count(const svt_dev_csc *x, int op, int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes,
+			    void *stream);
+int svt_dev_isfun_map_fill(const svt_dev_csc *x, int op, const int64_t *out_col_ptr, int32_t *out_row_idx, int32_t *out_val,
+			   const void *ws, size_t ws_bytes, void *stream);
+/* The compositions count -> allocate -> fill over the allocator of svt_dev_subset(), like svt_dev_arith_merge and
+   svt_dev_compare_map: the result arrays are the caller's to release, *out_Rtype is the type of *out_val.  Synchronise
+   `stream` once; the fill is still queued on return. */
+int svt_dev_pminmax_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+			  void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+			  void **out_val, void *stream);
+int svt_dev_pminmax_map(const svt_dev_csc *x, int op, double s, int s_Rtype, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+			void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+			void **out_val, void *stream);
+int svt_dev_pminmax_sweep(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len, int with_rows,
+			  int64_t stride, int64_t len, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx,
+			  int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val,
+			  int64_t *bad_index, void *stream);
+int svt_dev_isfun_map(const svt_dev_csc *x, int op, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx,
+		      int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val, void *stream);
+/* Host level, like svt_Arith_*_begin and svt_Compare_*_begin: the operands go up (through the resident cache when it is
+   on), the composition runs on the first device of the list (not sharded), the result (the extents of x) stays on the
+   device: *out_Rtype its type (LGLSXP for svt_isFUN_SVT_begin), *out_nnz its nonzero count.  svt_Arith_SVT_end ends
+   it.  The dims of x and y must be identical (< 0: "non-conformable arrays"); NaArray operands answer > 0.  `margin` of
+   the vector form as in svt_Arith_SVT_vector_begin.  The vector form has no counterpart in the reference and is one more
+   than the two-operand, the scalar and the isFUN forms need: it is what a host-level sweep(x, MARGIN, STATS, pmin) calls,
+   as svt_Arith_SVT_vector_begin is for the Arith operators. */
+int svt_pminmax_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int *out_Rtype,
+			      int64_t *out_nnz);
+int svt_pminmax_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res, int *out_Rtype,
+				 int64_t *out_nnz);
+int svt_pminmax_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
+				 const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res, int *out_Rtype,
+				 int64_t *out_nnz);
+int svt_isFUN_SVT_begin(const svt_view *x, int op, svt_arith_result **res, int64_t *out_nnz);
+
 /* abind(), cbind() and rbind() of SVT operands (C_abind_SVT_SparseArray_objects, src/SparseArray_abind.c;
    R/SparseArray-abind.R, R/NaArray-abind.R): nobj >= 1 objects bound along dimension `along` (1-based) into a new
    operand in the device layout, leaves x rows with the outermost dimension slowest.  A pure copy (kernels_abind.hip).

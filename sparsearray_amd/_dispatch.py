@@ -423,17 +423,42 @@ class CAbiDispatcher:
         return self._logical_result("Logic_SVT_SVT_begin", x, (y, LOGIC_OPCODES[op]),
                                     x.dimnames if x.dimnames is not None else y.dimnames)
 
+    # pmin / pmax and is.na / is.nan / is.infinite (.pminmax2 and C_SVT_apply_isFUN of the reference; include/svt_hip.h;
+    # HIP library only): the same begin / end pair; the library says the type of a pmin / pmax result ---------------
+    def C_pminmax_SVT1_SVT2(self, x: SVT_SparseArray, y: SVT_SparseArray, op: str, na_rm: bool):
+        """pmin(x, y) / pmax(x, y) (``op`` "pmin" / "pmax"); the dimnames are the first non-NULL ones."""
+        from .api import PMINMAX_NA_RM, PMINMAX_OPCODES
+        ans = self._assigned("pminmax_SVT_SVT_begin", x, (y, PMINMAX_OPCODES[op] | (PMINMAX_NA_RM if na_rm else 0)))
+        ans.dimnames = x.dimnames if x.dimnames is not None else y.dimnames
+        return ans
+
+    def C_pminmax_SVT1_v2(self, x: SVT_SparseArray, y: float, y_type: str, op: str, na_rm: bool):
+        """pmin(x, y) / pmax(x, y) for the scalar ``y`` of R type ``y_type`` ("logical" / "integer" / "double")."""
+        from .api import PMINMAX_NA_RM, PMINMAX_OPCODES
+        return self._assigned("pminmax_SVT_scalar_begin", x,
+                              (PMINMAX_OPCODES[op] | (PMINMAX_NA_RM if na_rm else 0), float(y), _RT[y_type]))
+
+    def C_SVT_apply_isFUN(self, x: SVT_SparseArray, isFUN: str):
+        """``isFUN``: "is.na", "is.nan" or "is.infinite"; returns the "logical" SVT_SparseArray."""
+        from .api import ISFUN_OPCODES
+        if isFUN not in ISFUN_OPCODES:
+            raise SparseArrayError(f"unknown isFUN \"{isFUN}\"")
+        return self._logical_result("isFUN_SVT_begin", x, (ISFUN_OPCODES[isFUN],), x.dimnames)
+
     # sweep(x, MARGIN, STATS, FUN) (no counterpart in the reference; include/svt_hip.h, svt_Arith_SVT_vector_begin /
     # svt_Compare_SVT_vector_begin; HIP library only): the same begin / end pairs with a host vector and the margin ------
-    def C_sweep_SVT(self, x: SVT_SparseArray, stats: np.ndarray, stats_type: str, margin, op: str):
+    def C_sweep_SVT(self, x: SVT_SparseArray, stats: np.ndarray, stats_type: str, margin, op: str, na_rm: bool = False):
         """Returns (x op STATS along ``margin``, overflow flag).  ``stats``: a float64 array for ``stats_type`` "double",
-        an int32 one for "integer" / "logical"; ``margin``: 1-based dimension numbers.  An element the library refuses
-        is named in its message, 0-based."""
-        from .api import ARITH_OPCODES, COMPARE_OPCODES
+        an int32 one for "integer" / "logical"; ``margin``: 1-based dimension numbers; ``na_rm``: read by "pmin" / "pmax".
+        An element the library refuses is named in its message, 0-based."""
+        from .api import ARITH_OPCODES, COMPARE_OPCODES, PMINMAX_NA_RM, PMINMAX_OPCODES
         stats = np.ascontiguousarray(stats, dtype=np.float64 if stats_type == "double" else np.int32).reshape(-1)
         buf = stats if stats.size else np.zeros(1, stats.dtype)     # (an empty vector is handed over as one unread element)
         m = np.ascontiguousarray(margin, dtype=np.int32).reshape(-1)
         bad = ctypes.c_int64(-1)
+        if op in PMINMAX_OPCODES:
+            args = (PMINMAX_OPCODES[op] | (PMINMAX_NA_RM if na_rm else 0), buf, stats.size, _RT[stats_type], m, m.size, byref(bad))
+            return self._assigned("pminmax_SVT_vector_begin", x, args), False
         if op in COMPARE_OPCODES:
             args = (COMPARE_OPCODES[op], buf, stats.size, _RT[stats_type], m, m.size, byref(bad))
             return self._logical_result("Compare_SVT_vector_begin", x, args, x.dimnames), False

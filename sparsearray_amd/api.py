@@ -69,6 +69,11 @@ _ARITH_INPUT_TYPES = ("integer", "double")      # (and "complex", which no SVT_S
 # Compare operators -> SVT_COMPARE_*, Logic operators -> SVT_LOGIC_* (include/svt_hip.h; the reference's opcodes)
 COMPARE_OPCODES = {"==": 1, "!=": 2, "<=": 3, ">=": 4, "<": 5, ">": 6}
 LOGIC_OPCODES = {"&": 1, "|": 2}
+# pmin / pmax -> SVT_PMINMAX_*, ORed with PMINMAX_NA_RM for na.rm = TRUE; is.na / is.nan / is.infinite -> SVT_IS_*
+PMINMAX_OPCODES = {"pmin": 1, "pmax": 2}
+PMINMAX_NA_RM = 4
+ISFUN_OPCODES = {"is.na": 1, "is.nan": 2, "is.infinite": 3}
+_PMINMAX_INPUT_TYPES = ("logical", "integer", "double")
 # COMPARE_INPUT_TYPES of R/SparseArray-Compare-methods.R:12-13 without "raw", in the order "bigger type" follows
 _COMPARE_INPUT_TYPES = ("logical", "integer", "double", "complex", "character")
 
@@ -1166,19 +1171,116 @@ class Session:
         return self._Compare_SVT1_v2(flip.get(op, op), e2, e1)
 
     # ------------------------------------------------------------------
+    # pmin(), pmax(), is.na(), is.nan(), is.infinite()  (R/SparseArray-misc-methods.R)
+    # ------------------------------------------------------------------
+    @staticmethod
+    def _check_pminmax_operand(name, x):
+        # (the reference has NaArray methods of its own, and its chain takes every type `<` takes; the device rule is
+        # stated for logical / integer / double)
+        if x.na_background:
+            raise SparseArrayUnsupported(f"{name}() on NaArray objects is not offered by this library")
+        if x.type not in _PMINMAX_INPUT_TYPES:
+            raise SparseArrayUnsupported(f"{name}() on a SparseArray object of type() \"{x.type}\" is not offered by this library")
+
+    def _pminmax2(self, name, x, y, na_rm):
+        """.pminmax2 (:111-137) for two SVT_SparseArray objects in one call, or -- an extension, as sweep()'s vector is --
+        for an object and a numeric or logical vector of length 1 on either side, where the result stays sparse."""
+        sx, sy = isinstance(x, SVT_SparseArray), isinstance(y, SVT_SparseArray)
+        if sx and sy:
+            self._check_pminmax_operand(name, x)
+            self._check_pminmax_operand(name, y)
+            if tuple(x.dim) != tuple(y.dim):
+                raise SparseArrayError("non-conformable arrays")
+            self._optional_entry("C_pminmax_SVT1_SVT2", "pminmax_SVT_SVT_begin")
+            ans = self.SparseArray_Call("C_pminmax_SVT1_SVT2", x, y, name, na_rm)
+            ans.dimnames = x.dimnames if x.dimnames is not None else y.dimnames     # get_first_non_NULL_dimnames, :135-136
+            return ans
+        if not (sx or sy):
+            raise SparseArrayError(f"{name}() needs an SVT_SparseArray object next to a vector of length 1")
+        if sy:                                              # (the cell rule gives the same value either way round)
+            x, y = y, x
+        self._check_pminmax_operand(name, x)
+        cls, ytype, length, v = self._scalar_class_type(y)
+        if ytype not in _PMINMAX_INPUT_TYPES:
+            raise SparseArrayUnsupported(f"{name}() between a SparseArray object and a {cls} vector is not offered by this library")
+        if length != 1:
+            raise SparseArrayError(f"{name}() is not supported between a SparseArray object and a vector of length != 1")
+        if (ytype != "double" and int(v) == NA_integer) or (ytype == "double" and np.isnan(v)):
+            raise SparseArrayError(f"{name}(x, y): operation not supported on SparseArray object x when y is NA or NaN "
+                                   f"(y = {v.item()!r}; result wouldn't be sparse)")
+        if (v < 0) if name == "pmin" else (v > 0):
+            raise SparseArrayError(f"{name}(x, y): operation not supported on SparseArray object x when y is "
+                                   f"{'< 0' if name == 'pmin' else '> 0'} (y = {v.item()!r}; result wouldn't be sparse)")
+        self._optional_entry("C_pminmax_SVT1_v2", "pminmax_SVT_scalar_begin")
+        ans = self.SparseArray_Call("C_pminmax_SVT1_v2", x, float(v), ytype, name, na_rm)
+        ans.dimnames = x.dimnames
+        return ans
+
+    def _psummarize(self, name, objects, na_rm):
+        # .psummarize, :142-164
+        objects = [o for o in objects if o is not None]
+        _check_flag("na.rm", na_rm)
+        if not objects:
+            raise SparseArrayError("no input")
+        x = objects[0]
+        if len(objects) == 1:
+            return x
+        y = objects[1] if len(objects) == 2 else self._psummarize(name, objects[1:], na_rm)
+        return self._pminmax2(name, x, y, bool(na_rm))
+
+    def pmin(self, *objects, na_rm=False):
+        """``pmin(...)`` of conformable SVT_SparseArray objects: None objects are dropped, one object comes back as it
+        is, more than two are folded from the right, ``pmin(a, pmin(b, c))``.  The result has the widest type and the
+        dimnames of the first object that has them.  An NA on either side gives NA unless ``na_rm``, which then gives
+        the other side.  A single int, float or bool among the objects is taken too where the result stays sparse
+        (``>= 0`` for pmin, ``<= 0`` for pmax, not NA): ``pmin(x, 10.0)`` caps the outliers."""
+        return self._psummarize("pmin", objects, na_rm)
+
+    def pmax(self, *objects, na_rm=False):
+        """``pmax(...)``; see pmin."""
+        return self._psummarize("pmax", objects, na_rm)
+
+    def _isFUN_SVT(self, isFUN, x):
+        # .isFUN_SVT, :57-64
+        if not isinstance(x, SVT_SparseArray):
+            raise SparseArrayError(f"{isFUN}() needs an SVT_SparseArray object")
+        if x.na_background:
+            raise SparseArrayUnsupported(f"{isFUN}() on NaArray objects is not offered by this library")
+        if x.type not in _PMINMAX_INPUT_TYPES:
+            raise SparseArrayUnsupported(f"{isFUN}() on a SparseArray object of type() \"{x.type}\" is not offered by this library")
+        self._optional_entry("C_SVT_apply_isFUN", "isFUN_SVT_begin")
+        return self.SparseArray_Call("C_SVT_apply_isFUN", x, isFUN)
+
+    def is_na(self, x):
+        """``is.na(x)``: a "logical" SVT_SparseArray that stores TRUE where an entry is NA or NaN."""
+        return self._isFUN_SVT("is.na", x)
+
+    def is_nan(self, x):
+        """``is.nan(x)``: TRUE where an entry is a NaN that is not NA; empty for an integer or logical object (base R's
+        answer; the reference stops with an internal error there)."""
+        return self._isFUN_SVT("is.nan", x)
+
+    def is_infinite(self, x):
+        """``is.infinite(x)``: TRUE where an entry is Inf or -Inf; empty for an integer or logical object."""
+        return self._isFUN_SVT("is.infinite", x)
+
+    # ------------------------------------------------------------------
     # sweep(x, MARGIN, STATS, FUN).  The reference has no method: its Arith and Compare methods refuse every vector of
     # length != 1, so t(t(x) / colSums(x)) and x * gene_weights have no sparse path there.  The rule is base R's sweep()
     # on the dense array, offered where the result stays sparse: the scalar conditions of .Arith_SVT1_v2 and
     # .Compare_SVT1_v2 asked of every element of STATS.
     # ------------------------------------------------------------------
-    def sweep(self, x, MARGIN, STATS, FUN="/"):
+    def sweep(self, x, MARGIN, STATS, FUN="/", na_rm=False):
         """``sweep(x, MARGIN, STATS, FUN)``: ``x FUN STATS[k]`` with ``k`` the position along ``MARGIN`` (1-based: an int
         or a strictly increasing run of consecutive dimensions; ``STATS`` has ``prod(dim(x)[MARGIN])`` elements, an
-        N-d one read column-major).  ``FUN``: one of ``* / ^ %% %/%`` or a comparison operator.  ``MARGIN = 1`` is what
+        N-d one read column-major).  ``FUN``: one of ``* / ^ %% %/%``, a comparison operator, or ``"pmin"`` / ``"pmax"``
+        (a cap or a floor per row or per leaf; ``na_rm`` as in pmin(); every element ``>= 0`` resp. ``<= 0`` and not NA;
+        the result has the wider of the two types).  ``MARGIN = 1`` is what
         R's recycling makes of ``x * w`` with ``length(w) == nrow(x)``.  Every element must keep the result sparse;
         the first that does not is named (1-based).  The dimnames of ``x`` are kept."""
         op = FUN
-        if op not in ARITH_OPCODES and op not in COMPARE_OPCODES:
+        pminmax = op in PMINMAX_OPCODES
+        if op not in ARITH_OPCODES and op not in COMPARE_OPCODES and not pminmax:
             raise SparseArrayError(f"invalid Arith or Compare operation \"{op}\"")
         if not isinstance(x, SVT_SparseArray):
             raise SparseArrayError("sweep() needs an SVT_SparseArray object as 'x' (a vector on the left and an "
@@ -1186,7 +1288,12 @@ class Session:
         _check_not_NaArray("sweep", x)
         compare = op in COMPARE_OPCODES
         cls, ytype, length, _ = self._scalar_class_type(STATS)
-        if compare:
+        if pminmax:
+            _check_flag("na.rm", na_rm)
+            self._check_pminmax_operand(op, x)
+            if ytype not in _PMINMAX_INPUT_TYPES:
+                raise SparseArrayUnsupported(f"{op}() between a SparseArray object and a {cls} vector is not offered by this library")
+        elif compare:
             self._check_Compare_input_type(x.type, "SparseArray object")
             if ytype not in _COMPARE_INPUT_TYPES:
                 raise SparseArrayError(f"comparison operations between SparseArray objects and {cls} vectors are not supported")
@@ -1214,7 +1321,12 @@ class Session:
         if length != want:
             raise SparseArrayError(f"length(STATS) is {length} but prod(dim(x)[MARGIN]) is {want}")
         stats = np.asarray(STATS).reshape(-1, order="F")
-        if compare:
+        if pminmax:
+            nas = np.isnan(stats) if ytype == "double" else stats.astype(np.int64) == NA_integer
+            v = stats.astype(np.float64)
+            v[nas] = 0.0
+            whens = [(nas, "is NA or NaN"), (v < 0, "is < 0") if op == "pmin" else (v > 0, "is > 0")]
+        elif compare:
             biggest = max(x.type, ytype, key=_COMPARE_INPUT_TYPES.index)
             if biggest == "character":                      # (.Compare_SVT1_v2: <= and < first, then no operator at all)
                 if op in ("<=", "<"):
@@ -1253,7 +1365,9 @@ class Session:
         if bad.any():
             k = int(np.argmax(bad))
             self._sparsity_not_preserved(op, next(f"STATS[{k + 1}] {when}" for mask, when in whens if mask[k]))
-        if compare:
+        if pminmax:
+            stype = ytype
+        elif compare:
             if biggest == "complex":                        # (the reference takes it; this library has no complex type)
                 raise SparseArrayUnsupported("comparison with a complex value is not offered by this library")
             stype = biggest                                 # type(y) <- biggest_type, .Compare_SVT1_v2:113
@@ -1264,6 +1378,11 @@ class Session:
             stats = stats.astype(np.float64)                # (no NA is left to convert)
         elif stype != "double":
             stats = stats.astype(np.int32)
+        if pminmax:
+            self._optional_entry("C_sweep_SVT", "pminmax_SVT_vector_begin")
+            ans = self.SparseArray_Call("C_sweep_SVT", x, stats, stype, margin, op, bool(na_rm))[0]
+            ans.dimnames = x.dimnames
+            return ans
         self._optional_entry("C_sweep_SVT", "Compare_SVT_vector_begin" if compare else "Arith_SVT_vector_begin")
         ans, ovflow = self.SparseArray_Call("C_sweep_SVT", x, stats, stype, margin, op)
         return ans if compare else self._warn_overflow((ans, ovflow))

@@ -40,6 +40,12 @@
 // Subassignment by an L-index or M-index is a fifth (ARI_RULE_ASSIGN_CELLS, svt_rule_assign_cells): y is the placed
 // operand kernels_lindex.hip builds, a zero in it deletes, an x entry alone always stays; it reads no table and no opcode.
 //
+// pmin / pmax (ARI_RULE_PMINMAX, svt_rule_pminmax: .pminmax2 of the reference cell by cell) is a sixth rule, on all three
+// families: both sides widened to the result's type, the opcode carrying min / max and na.rm, the scalar or vector element
+// checked as the Arith and Compare ones are.  is.na / is.nan / is.infinite (ARI_RULE_ISFUN, svt_rule_isfun) is a seventh,
+// on the map alone, with an int32 result.  Neither raises an overflow; neither adds a kernel body, a byte of LDS or a
+// workspace part.
+//
 // LDS: keys 8 * (2048 + 2), sources 4 * 2048, ballots and chunk prefixes 0.4 KB: 24.5 KB for the merge (6 workgroups
 // of a CU's 160 KB), 0.4 KB for the map.
 #include "svt_common.h"
@@ -170,6 +176,13 @@ __device__ inline TO ari_map_eval(const AriMapOp &m, TX v, int *ovf)
 {
 	if constexpr (RULE == ARI_RULE_COMPARE) {
 		return svt_rule_compare(m.op, svt_rule_as_double(v), m.sd);
+	} else if constexpr (RULE == ARI_RULE_ISFUN) {
+		return svt_rule_isfun(m.op, v);
+	} else if constexpr (RULE == ARI_RULE_PMINMAX) {
+		TO x;
+		svt_rule_widen(v, &x);
+		if constexpr (std::is_same<TO, int32_t>::value) return svt_rule_pminmax(m.op & ~SVT_PMINMAX_NA_RM, m.op & SVT_PMINMAX_NA_RM, x, m.si);
+		else return svt_rule_pminmax(m.op & ~SVT_PMINMAX_NA_RM, m.op & SVT_PMINMAX_NA_RM, x, m.sd);
 	} else if constexpr (std::is_same<TO, int32_t>::value) {
 		if (m.kind == SVT_ARITH_NEG) return v == NA_INT ? NA_INT : -v;
 		return svt_rule_arith_int(m.op, v, m.si, ovf);
@@ -383,7 +396,12 @@ __device__ inline void ari_merge_tile(const AriSide &X, const TX *xval, const Ar
 			r[it] = svt_rule_compare(op, svt_rule_as_double(xv), svt_rule_as_double(yv));
 		else if constexpr (RULE == ARI_RULE_LOGIC)
 			r[it] = svt_rule_logic(op, xv, yv);
-		else if constexpr (std::is_same<TO, int32_t>::value)
+		else if constexpr (RULE == ARI_RULE_PMINMAX) {
+			TO xw, yw;
+			svt_rule_widen(xv, &xw);
+			svt_rule_widen(yv, &yw);
+			r[it] = svt_rule_pminmax(op & ~SVT_PMINMAX_NA_RM, op & SVT_PMINMAX_NA_RM, xw, yw);
+		} else if constexpr (std::is_same<TO, int32_t>::value)
 			r[it] = svt_rule_arith_int(op, xv, yv, ovf);
 		else
 			r[it] = svt_rule_arith_double(op, svt_rule_as_double(xv), svt_rule_as_double(yv));
@@ -469,7 +487,12 @@ __device__ inline TO ari_sweep_eval(int op, TX v, TS s, int *ovf)
 {
 	if constexpr (RULE == ARI_RULE_COMPARE)
 		return svt_rule_compare(op, svt_rule_as_double(v), svt_rule_as_double(s));
-	else if constexpr (std::is_same<TO, int32_t>::value)
+	else if constexpr (RULE == ARI_RULE_PMINMAX) {
+		TO x, y;
+		svt_rule_widen(v, &x);
+		svt_rule_widen(s, &y);
+		return svt_rule_pminmax(op & ~SVT_PMINMAX_NA_RM, op & SVT_PMINMAX_NA_RM, x, y);
+	} else if constexpr (std::is_same<TO, int32_t>::value)
 		return svt_rule_arith_int(op, v, s, ovf);
 	else
 		return svt_rule_arith_double(op, svt_rule_as_double(v), svt_rule_as_double(s));
@@ -527,8 +550,11 @@ __global__ __launch_bounds__(ARI_NT) void arith_sweep_count_kernel(const int64_t
 	ari_count_tail(P, ts, sh, tile_cnt, local);
 }
 
+// (the second launch bound, for pmin / pmax alone: with no long-latency arithmetic behind the eight gathers of the vector
+// the compiler hoists them all and takes 82 VGPRs, 5 waves per SIMD against the Arith instantiations' 6; asked for 6 it
+// takes 50 and spills nothing.  The other rules' instantiations compile as before.)
 template <typename TX, typename TS, typename TO, int RULE>
-__global__ __launch_bounds__(ARI_NT) void arith_sweep_fill_kernel(const int64_t *col_ptr, const int32_t *row_idx, const TX *val,
+__global__ __launch_bounds__(ARI_NT, RULE == ARI_RULE_PMINMAX ? 6 : 1) void arith_sweep_fill_kernel(const int64_t *col_ptr, const int32_t *row_idx, const TX *val,
 								  const TS *stats, int64_t ncol, int64_t nnz, AriSweepOp w,
 								  const int64_t *tile_pre, int32_t *out_row_idx, TO *out_val, int *ovflow)
 {
@@ -564,7 +590,8 @@ __global__ __launch_bounds__(ARI_NT) void arith_sweep_valid_kernel(const TS *sta
 	for (int64_t i = (int64_t) blockIdx.x * ARI_NT + threadIdx.x; i < n; i += step) {
 		const double s = (double) stats[i];
 		const bool ok = RULE == ARI_RULE_COMPARE ? svt_rule_compare_keeps_sparse(op, s, s_Rtype)
-							 : svt_rule_arith_keeps_sparse(op, s, s_Rtype);
+				: RULE == ARI_RULE_PMINMAX ? svt_rule_pminmax_keeps_sparse(op, s, s_Rtype)
+							   : svt_rule_arith_keeps_sparse(op, s, s_Rtype);
 		if (!ok) {
 			atomicMin(bad, (unsigned long long) i);     // (this thread's later indices are larger)
 			break;
@@ -643,6 +670,21 @@ static inline int arith_map_by_types(const ArithMapArgs &a, F &&f)
 		else return svt_set_error("compare map: no kernel for this type");
 		return 0;
 	}
+	if (a.rule == ARI_RULE_ISFUN) {
+		if (a.Rtype == SVT_REALSXP) f((const double *) a.val, m, (int32_t *) NULL, AriRule<ARI_RULE_ISFUN>());
+		else if (a.Rtype == SVT_INTSXP || a.Rtype == SVT_LGLSXP)
+			f((const int32_t *) a.val, m, (int32_t *) NULL, AriRule<ARI_RULE_ISFUN>());
+		else return svt_set_error("isfun map: no kernel for this type");
+		return 0;
+	}
+	if (a.rule == ARI_RULE_PMINMAX) {                   // (a logical operand or result is an int32 one)
+		const bool xi = a.Rtype == SVT_INTSXP || a.Rtype == SVT_LGLSXP, oi = a.out_Rtype == SVT_INTSXP || a.out_Rtype == SVT_LGLSXP;
+		if (a.Rtype == SVT_REALSXP && a.out_Rtype == SVT_REALSXP) f((const double *) a.val, m, (double *) NULL, AriRule<ARI_RULE_PMINMAX>());
+		else if (xi && a.out_Rtype == SVT_REALSXP) f((const int32_t *) a.val, m, (double *) NULL, AriRule<ARI_RULE_PMINMAX>());
+		else if (xi && oi) f((const int32_t *) a.val, m, (int32_t *) NULL, AriRule<ARI_RULE_PMINMAX>());
+		else return svt_set_error("pminmax map: no kernel for these types");
+		return 0;
+	}
 	if (a.rule != ARI_RULE_ARITH) return svt_set_error("arith map: no kernel for this rule");
 	if (a.Rtype == SVT_REALSXP && a.out_Rtype == SVT_REALSXP) f((const double *) a.val, m, (double *) NULL, AriRule<ARI_RULE_ARITH>());
 	else if (a.Rtype == SVT_INTSXP && a.out_Rtype == SVT_REALSXP) f((const int32_t *) a.val, m, (double *) NULL, AriRule<ARI_RULE_ARITH>());
@@ -699,7 +741,8 @@ static inline void arith_merge_by_operands(const ArithMergeArgs &a, F &&f, R rul
 	else if (a.y_Rtype == SVT_REALSXP) f((const int32_t *) a.x_val, (const double *) a.y_val, rule);
 	else f((const int32_t *) a.x_val, (const int32_t *) a.y_val, rule);
 }
-// and by the rule: Arith, Compare and the two subassignment rules for the four type pairs, Logic for int32 x int32 alone
+// and by the rule: Arith, Compare, the two subassignment rules and pmin / pmax for the four type pairs, Logic for
+// int32 x int32 alone
 template <class F>
 static inline int arith_merge_by_types(const ArithMergeArgs &a, F &&f)
 {
@@ -707,6 +750,7 @@ static inline int arith_merge_by_types(const ArithMergeArgs &a, F &&f)
 	else if (a.rule == ARI_RULE_COMPARE) arith_merge_by_operands(a, f, AriRule<ARI_RULE_COMPARE>());
 	else if (a.rule == ARI_RULE_ASSIGN) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ASSIGN>());
 	else if (a.rule == ARI_RULE_ASSIGN_CELLS) arith_merge_by_operands(a, f, AriRule<ARI_RULE_ASSIGN_CELLS>());
+	else if (a.rule == ARI_RULE_PMINMAX) arith_merge_by_operands(a, f, AriRule<ARI_RULE_PMINMAX>());
 	else if (a.rule == ARI_RULE_LOGIC && a.x_Rtype != SVT_REALSXP && a.y_Rtype != SVT_REALSXP)
 		f((const int32_t *) a.x_val, (const int32_t *) a.y_val, AriRule<ARI_RULE_LOGIC>());
 	else return svt_set_error("arith merge: no kernel for this rule and these types");
@@ -773,6 +817,13 @@ static inline int arith_sweep_by_types(const ArithSweepArgs &a, F &&f)
 		else f((const int32_t *) a.val, (const int32_t *) a.stats, (int32_t *) NULL, AriRule<ARI_RULE_COMPARE>());
 		return 0;
 	}
+	if (a.rule == ARI_RULE_PMINMAX) {                   // int32 for two int32 sides, double with a double side
+		if (xd && sd) f((const double *) a.val, (const double *) a.stats, (double *) NULL, AriRule<ARI_RULE_PMINMAX>());
+		else if (xd) f((const double *) a.val, (const int32_t *) a.stats, (double *) NULL, AriRule<ARI_RULE_PMINMAX>());
+		else if (sd) f((const int32_t *) a.val, (const double *) a.stats, (double *) NULL, AriRule<ARI_RULE_PMINMAX>());
+		else f((const int32_t *) a.val, (const int32_t *) a.stats, (int32_t *) NULL, AriRule<ARI_RULE_PMINMAX>());
+		return 0;
+	}
 	if (a.rule != ARI_RULE_ARITH) return svt_set_error("arith sweep: no kernel for this rule");
 	if (a.out_Rtype == SVT_INTSXP) {
 		if (xd || sd) return svt_set_error("arith sweep: no kernel for these types");
@@ -802,15 +853,19 @@ int launch_arith_sweep_count(const ArithSweepArgs &a, int64_t *out_col_ptr, void
 	const int64_t nstats = (a.with_rows ? a.nrow : 1) * a.len;
 	if (nstats > 0) {
 		const unsigned nb = blocks_for(nstats < 1024 * ARI_NT ? nstats : 1024 * ARI_NT);
-		const bool cmp = a.rule == ARI_RULE_COMPARE;
+		const bool cmp = a.rule == ARI_RULE_COMPARE, pmm = a.rule == ARI_RULE_PMINMAX;
 		if (a.stats_Rtype == SVT_REALSXP) {
 			if (cmp) hipLaunchKernelGGL((arith_sweep_valid_kernel<double, ARI_RULE_COMPARE>), dim3(nb), dim3(ARI_NT), 0, s,
 						    (const double *) a.stats, nstats, a.op, a.stats_Rtype, bad);
+			else if (pmm) hipLaunchKernelGGL((arith_sweep_valid_kernel<double, ARI_RULE_PMINMAX>), dim3(nb), dim3(ARI_NT), 0, s,
+							 (const double *) a.stats, nstats, a.op, a.stats_Rtype, bad);
 			else hipLaunchKernelGGL((arith_sweep_valid_kernel<double, ARI_RULE_ARITH>), dim3(nb), dim3(ARI_NT), 0, s,
 						(const double *) a.stats, nstats, a.op, a.stats_Rtype, bad);
 		} else {
 			if (cmp) hipLaunchKernelGGL((arith_sweep_valid_kernel<int32_t, ARI_RULE_COMPARE>), dim3(nb), dim3(ARI_NT), 0, s,
 						    (const int32_t *) a.stats, nstats, a.op, a.stats_Rtype, bad);
+			else if (pmm) hipLaunchKernelGGL((arith_sweep_valid_kernel<int32_t, ARI_RULE_PMINMAX>), dim3(nb), dim3(ARI_NT), 0, s,
+							 (const int32_t *) a.stats, nstats, a.op, a.stats_Rtype, bad);
 			else hipLaunchKernelGGL((arith_sweep_valid_kernel<int32_t, ARI_RULE_ARITH>), dim3(nb), dim3(ARI_NT), 0, s,
 						(const int32_t *) a.stats, nstats, a.op, a.stats_Rtype, bad);
 		}

@@ -1,7 +1,8 @@
 // The element rules of Arith and Math on sparse operands (src/SparseVec_Arith.c, src/SparseVec_Math.c of the
-// reference; R's arithmetic.c for the operators), of Compare and Logic, and of subassignment, each stated once for the
-// device kernels (kernels_arith.hip) and for a host program (tests/arith_rules_main.cpp, compare_rules_main.cpp,
-// assign_rules_main.cpp, sweep_rules_main.cpp): plain C++, no HIP header needed.
+// reference; R's arithmetic.c for the operators), of Compare and Logic, of subassignment, and of pmin / pmax and is.na /
+// is.nan / is.infinite, each stated once for the device kernels (kernels_arith.hip) and for a host program
+// (tests/arith_rules_main.cpp, compare_rules_main.cpp, assign_rules_main.cpp, sweep_rules_main.cpp,
+// pminmax_rules_main.cpp): plain C++, no HIP header needed.
 #pragma once
 
 #include <math.h>
@@ -391,6 +392,42 @@ SVT_HD inline bool svt_rule_compare_keeps_sparse(int op, double s, int s_Rtype)
 SVT_HD inline void svt_rule_widen(int32_t v, int32_t *out) { *out = v; }
 SVT_HD inline void svt_rule_widen(double v, double *out) { *out = v; }
 SVT_HD inline void svt_rule_widen(int32_t v, double *out) { *out = svt_rule_as_double(v); }
+
+// ---- pmin(x, y) / pmax(x, y) (.pminmax2, R/SparseArray-misc-methods.R:111-137 of the reference) ----
+// is.na() of a value: a NaN (NA_real_ is one) for a double, NA_integer_ for an integer or a logical
+SVT_HD inline bool svt_rule_isna(double v) { return v != v; }
+SVT_HD inline bool svt_rule_isna(int32_t v) { return v == SVT_NA_INT; }
+// One cell of .pminmax2 on two values already widened to the result's type (svt_rule_widen), op SVT_PMINMAX_MIN or _MAX.
+// Its five steps are ans <- x; ans[nzwhich(y < x)] <- y (nzwhich takes an NA for a nonzero, so an NA on either side puts
+// y there); then ans[nzwhich(is.na(x))] <- x without na.rm, ans[nzwhich(is.na(y))] <- x with it.  Read for one cell:
+// without na.rm an NA x wins, then an NA y, else the comparison; with na.rm an NA y loses to x whatever x is, then an NA
+// x loses to y.  Ties take x.  The chosen side comes back as its bits: a NaN keeps its payload, NA_real_ stays NA_real_.
+template <typename T>
+SVT_HD inline T svt_rule_pminmax(int op, int na_rm, T x, T y)
+{
+	return svt_rule_isna(na_rm ? y : x) ? x : svt_rule_isna(na_rm ? x : y) ? y : (op == SVT_PMINMAX_MIN ? y < x : y > x) ? y : x;
+}
+// Whether the scalar or vector element `s` keeps pmin(x, s) / pmax(x, s) sparse, i.e. whether pmin(0, s) == 0: not NA /
+// NaN, and >= 0 for pmin, <= 0 for pmax (-0.0 passes both; +Inf passes pmin, -Inf pmax).  `op` may carry
+// SVT_PMINMAX_NA_RM: an NA element is refused with na.rm too, pmin(0, NA, na.rm = TRUE) being 0 but pmin(v, NA) v.
+SVT_HD inline bool svt_rule_pminmax_keeps_sparse(int op, double s, int s_Rtype)
+{
+	return (op & ~SVT_PMINMAX_NA_RM) == SVT_PMINMAX_MIN ? svt_rule_element(s, s_Rtype) >= 0.0 : svt_rule_element(s, s_Rtype) <= 0.0;
+}
+
+// ---- is.na(x), is.nan(x), is.infinite(x) (C_SVT_apply_isFUN, src/SparseArray_misc_methods.c of the reference) ----
+// 1 or 0.  is.na: ISNAN for a double (NA_real_ and every NaN), NA_integer_ for an integer or a logical; is.nan: a NaN
+// that is not NA_real_ (R_IsNaN: the low word is not 1954, the test svt_coerce_rules.h states for R_IsNA); is.infinite:
+// +-Inf.  An integer or logical value is never NaN or infinite: base R's answer (the reference stops with an internal
+// error for such an operand).
+SVT_HD inline int32_t svt_rule_isfun(int op, double v)
+{
+	union { double d; unsigned long long u; } b;
+	b.d = v;
+	return op == SVT_IS_NA ? v != v : op == SVT_IS_NAN ? v != v && (unsigned int) (b.u & 0xFFFFFFFFu) != 1954u
+							   : op == SVT_IS_INFINITE && (v == svt_rule_inf() || v == -svt_rule_inf());
+}
+SVT_HD inline int32_t svt_rule_isfun(int op, int32_t v) { return op == SVT_IS_NA && v == SVT_NA_INT; }
 
 // One place of x merged with the placed operand Y (the new values of the selected cells that may have to be stored; Y
 // has entries in covered leaves only).  in_y: Y stores the place (alone or next to an x entry) -- the result is Y's

@@ -278,8 +278,12 @@ int launch_subset_rows_fill(const int32_t *row_idx, const void *val, int Rtype, 
 // subassignment rule (merge only; y the placed operand of kernels_subassign.hip, `op` not read, `cover_row` /
 // `cover_leaf` one byte per row / per leaf, NULL: the whole axis; the result double when either side is, else int32),
 // or the rule of the subassignment by cells (merge only; y the placed operand of kernels_lindex.hip, a zero in it the
-// deletion mark; no tables, `op` not read; the result typed like ARI_RULE_ASSIGN's).
-enum { ARI_RULE_ARITH = 0, ARI_RULE_COMPARE = 1, ARI_RULE_LOGIC = 2, ARI_RULE_ASSIGN = 3, ARI_RULE_ASSIGN_CELLS = 4 };
+// deletion mark; no tables, `op` not read; the result typed like ARI_RULE_ASSIGN's), or pmin / pmax (map with the
+// scalar in `sd` / `si`, merge and sweep; `op` SVT_PMINMAX_MIN / _MAX, ORed with SVT_PMINMAX_NA_RM; the result int32
+// unless a side is double; no overflow word), or is.na / is.nan / is.infinite (map only; `op` a SVT_IS_* opcode; the
+// result int32).
+enum { ARI_RULE_ARITH = 0, ARI_RULE_COMPARE = 1, ARI_RULE_LOGIC = 2, ARI_RULE_ASSIGN = 3, ARI_RULE_ASSIGN_CELLS = 4,
+       ARI_RULE_PMINMAX = 5, ARI_RULE_ISFUN = 6 };
 struct ArithMapArgs {
 	const int64_t *col_ptr;
 	const int32_t *row_idx;
@@ -308,7 +312,7 @@ int launch_arith_merge_count(const ArithMergeArgs &a, int64_t *out_col_ptr, void
 int launch_arith_merge_fill(const ArithMergeArgs &a, int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, hipStream_t s);
 // The sweep, a third family: f(v, stats[k]) on the stored values of one operand, k = (with_rows ? row : 0) +
 // (with_rows ? nrow : 1) * ((leaf / stride) % len) -- one element of `stats` per row, per leaf, or per row of a group of
-// leaves.  `rule`: ARI_RULE_ARITH (op one of * / ^ %% %/%) or ARI_RULE_COMPARE.  The workspace is the map's
+// leaves.  `rule`: ARI_RULE_ARITH (op one of * / ^ %% %/%), ARI_RULE_COMPARE or ARI_RULE_PMINMAX.  The workspace is the map's
 // (arith_ws_bytes(ncol, nnz, 0)); the count launcher first checks every element of `stats` and leaves, in the head of
 // `ws`, [int64 at byte 8: the nonzeros of the result][uint64 at byte 16: the smallest index of an element that does not
 // keep the result sparse, or all ones]; with such an element out_col_ptr is not written.  All asynchronous.

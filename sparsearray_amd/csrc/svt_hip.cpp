@@ -1570,6 +1570,41 @@ static int assign_check(const char *who, const svt_dev_csc *x, const svt_dev_csc
 	return 0;
 }
 
+// The same for pmin / pmax (ARI_RULE_PMINMAX; `kind` as for Compare; `s`: the scalar as the rule sees it) and for is.na /
+// is.nan / is.infinite (ARI_RULE_ISFUN, a map without a scalar); *out_Rtype <- the type of the result
+static int pminmax_check(const char *who, int rule, int kind, int op, const svt_dev_csc *x, const svt_dev_csc *y, double s,
+			 int s_Rtype, int *out_Rtype)
+{
+	const bool merge = kind == SVT_ARITH_MERGE;
+	if (x == NULL || merge != (y != NULL))
+		return svt_set_error("%s: an operand is needed", who);
+	if (y != NULL && (x->nrow != y->nrow || x->ncol != y->ncol))
+		return svt_set_error("non-conformable arrays");
+	if (!logical_family_type(x->Rtype) || (y != NULL && !logical_family_type(y->Rtype)))
+		return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
+	if (rule == ARI_RULE_ISFUN) {
+		if (op != SVT_IS_NA && op != SVT_IS_NAN && op != SVT_IS_INFINITE)
+			return svt_set_error("%s: unknown operation (opcode %d)", who, op);
+		*out_Rtype = SVT_LGLSXP;
+	} else {
+		if ((op & ~SVT_PMINMAX_NA_RM) != SVT_PMINMAX_MIN && (op & ~SVT_PMINMAX_NA_RM) != SVT_PMINMAX_MAX)
+			return svt_set_error("%s: unknown operation (opcode %d)", who, op);
+		if (!merge) {
+			if (!logical_family_type(s_Rtype))
+				return svt_set_error("%s: the scalar must be of type \"logical\", \"integer\" or \"double\"", who);
+			if (s_Rtype != SVT_REALSXP && s == s && (s != trunc(s) || s < -2147483647.0 || s > 2147483647.0))
+				return svt_set_error("%s: the scalar is not a value of its integer or logical type", who);
+			if (!svt_rule_pminmax_keeps_sparse(op, s, SVT_REALSXP))
+				return svt_set_error("%s: %s of 0 and the scalar is not 0 (result wouldn't be sparse)", who,
+						     (op & ~SVT_PMINMAX_NA_RM) == SVT_PMINMAX_MIN ? "pmin" : "pmax");
+		}
+		*out_Rtype = svt_rule_assign_out_Rtype(x->Rtype, merge ? y->Rtype : s_Rtype);
+	}
+	if (x->na_background || (y != NULL && y->na_background))
+		return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+	return 0;
+}
+
 static ArithMergeArgs arith_merge_args(const svt_dev_csc *x, const svt_dev_csc *y, int op)
 {
 	ArithMergeArgs a;
@@ -1596,6 +1631,7 @@ struct ArithCall {
 	int s_Rtype;
 	int out_Rtype = 0;
 	int rule = ARI_RULE_ARITH;      // ARI_RULE_COMPARE / _LOGIC: `kind` says merge or map, the result is LGLSXP, no overflow word
+					// (ARI_RULE_PMINMAX / _ISFUN: the same, the result typed by pminmax_check)
 	const unsigned char *cover_row = NULL, *cover_leaf = NULL;      // ARI_RULE_ASSIGN (a merge): the two tables, NULL = the whole axis
 									// (ARI_RULE_ASSIGN_CELLS, a merge too, reads neither)
 	ArithMergeArgs merge_args() const
@@ -1609,7 +1645,8 @@ struct ArithCall {
 	{
 		ArithMapArgs a = arith_map_args(x, kind, op, s, out_Rtype);
 		a.rule = rule;
-		if (rule == ARI_RULE_COMPARE) a.sd = compare_scalar(s, s_Rtype);
+		if (rule == ARI_RULE_COMPARE || rule == ARI_RULE_PMINMAX) a.sd = compare_scalar(s, s_Rtype);
+		if (rule == ARI_RULE_PMINMAX) a.si = out_Rtype != SVT_REALSXP ? (int32_t) s : 0;       // (an NA or out-of-range scalar was refused)
 		return a;
 	}
 	size_t need() const
@@ -1620,6 +1657,9 @@ struct ArithCall {
 	{
 		if (rule == ARI_RULE_ASSIGN || rule == ARI_RULE_ASSIGN_CELLS) {
 			if (const int rc = assign_check(who, x, y, &out_Rtype))
+				return rc;
+		} else if (rule == ARI_RULE_PMINMAX || rule == ARI_RULE_ISFUN) {
+			if (const int rc = pminmax_check(who, rule, kind, op, x, y, compare_scalar(s, s_Rtype), s_Rtype, &out_Rtype))
 				return rc;
 		} else if (rule != ARI_RULE_ARITH) {
 			if (const int rc = compare_check(who, rule, kind, op, x, y, compare_scalar(s, s_Rtype), s_Rtype))
@@ -1807,6 +1847,80 @@ extern "C" int svt_dev_logic_merge(const svt_dev_csc *x, const svt_dev_csc *y, i
 	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 
+// ---- pmin / pmax and is.na / is.nan / is.infinite: the same call object under two more rules; no overflow word ----
+extern "C" int svt_dev_pminmax_out_Rtype(int x_Rtype, int y_Rtype)
+{
+	return svt_rule_assign_out_Rtype(x_Rtype, y_Rtype);
+}
+static int pminmax_compose(ArithCall c, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz,
+			   int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+{
+	return abi_status([&] {
+		if (out_Rtype == NULL || out_val == NULL)
+			return svt_set_error("%s: 'out_Rtype' and 'out_val' are needed", c.who);
+		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, stream);
+	});
+}
+extern "C" int svt_dev_pminmax_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr,
+					   int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_pminmax_merge_count", ARI_RULE_PMINMAX, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_pminmax_merge_fill(const svt_dev_csc *x, const svt_dev_csc *y, int op, const int64_t *out_col_ptr,
+					  int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile prefixes in `ws` place the entries)
+	ArithCall c = compare_call("svt_dev_pminmax_merge_fill", ARI_RULE_PMINMAX, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_pminmax_merge(const svt_dev_csc *x, const svt_dev_csc *y, int op, svt_dev_alloc_fn alloc,
+				     svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr,
+				     int32_t **out_row_idx, void **out_val, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_pminmax_merge", ARI_RULE_PMINMAX, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
+	return pminmax_compose(c, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+}
+extern "C" int svt_dev_pminmax_map_count(const svt_dev_csc *x, int op, double s, int s_Rtype, int64_t *out_col_ptr,
+					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_pminmax_map_count", ARI_RULE_PMINMAX, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_pminmax_map_fill(const svt_dev_csc *x, int op, double s, int s_Rtype, const int64_t *out_col_ptr,
+					int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;
+	ArithCall c = compare_call("svt_dev_pminmax_map_fill", ARI_RULE_PMINMAX, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_pminmax_map(const svt_dev_csc *x, int op, double s, int s_Rtype, svt_dev_alloc_fn alloc,
+				   svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr,
+				   int32_t **out_row_idx, void **out_val, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_pminmax_map", ARI_RULE_PMINMAX, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
+	return pminmax_compose(c, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+}
+extern "C" int svt_dev_isfun_map_count(const svt_dev_csc *x, int op, int64_t *out_col_ptr, int64_t *out_nnz, void *ws,
+				       size_t ws_bytes, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_isfun_map_count", ARI_RULE_ISFUN, SVT_ARITH_SCALAR, op, x, NULL, 0.0, 0);
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_isfun_map_fill(const svt_dev_csc *x, int op, const int64_t *out_col_ptr, int32_t *out_row_idx,
+				      int32_t *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;
+	ArithCall c = compare_call("svt_dev_isfun_map_fill", ARI_RULE_ISFUN, SVT_ARITH_SCALAR, op, x, NULL, 0.0, 0);
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_isfun_map(const svt_dev_csc *x, int op, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx,
+				 int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val, void *stream)
+{
+	ArithCall c = compare_call("svt_dev_isfun_map", ARI_RULE_ISFUN, SVT_ARITH_SCALAR, op, x, NULL, 0.0, 0);
+	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+}
+
 // ---- sweep: x op stats[k], Arith or Compare with one element of a device vector per row or per leaf ----
 // One operation of the third family: the one statement of its checks and of count / fill / compose.  The statuses are
 // those of the maps; what is added is the geometry of the vector and the element the device refused.
@@ -1832,6 +1946,12 @@ struct SweepCall {
 			if (op < SVT_COMPARE_EQ || op > SVT_COMPARE_GT)
 				return svt_set_error("%s: unknown operation (opcode %d)", who, op);
 			out_Rtype = SVT_LGLSXP;
+		} else if (rule == ARI_RULE_PMINMAX) {
+			if (!logical_family_type(x->Rtype) || !logical_family_type(stats_Rtype))
+				return svt_set_error("%s: the operand and the vector must be of type \"logical\", \"integer\" or \"double\"", who);
+			if ((op & ~SVT_PMINMAX_NA_RM) != SVT_PMINMAX_MIN && (op & ~SVT_PMINMAX_NA_RM) != SVT_PMINMAX_MAX)
+				return svt_set_error("%s: unknown operation (opcode %d)", who, op);
+			out_Rtype = svt_rule_assign_out_Rtype(x->Rtype, stats_Rtype);
 		} else {
 			if (x->Rtype == SVT_LGLSXP)
 				return svt_set_error("arithmetic operation not supported on SparseArray object of type() \"logical\"");
@@ -1976,6 +2096,33 @@ extern "C" int svt_dev_compare_sweep(const svt_dev_csc *x, int op, const void *s
 		const int rc = c.compose(alloc, release, ctx, &rt, out_nnz, out_col_ptr, out_row_idx, &val, NULL, bad_index, stream);
 		if (rc == 0) *out_val = (int32_t *) val;
 		return rc;
+	});
+}
+extern "C" int svt_dev_pminmax_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+					   int with_rows, int64_t stride, int64_t len, int64_t *out_col_ptr, int64_t *out_nnz,
+					   int64_t *bad_index, void *ws, size_t ws_bytes, void *stream)
+{
+	SweepCall c = { "svt_dev_pminmax_sweep_count", ARI_RULE_PMINMAX, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, bad_index, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_pminmax_sweep_fill(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+					  int with_rows, int64_t stride, int64_t len, const int64_t *out_col_ptr, int32_t *out_row_idx,
+					  void *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;
+	SweepCall c = { "svt_dev_pminmax_sweep_fill", ARI_RULE_PMINMAX, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] { return c.fill(out_row_idx, out_val, NULL, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_pminmax_sweep(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
+				     int with_rows, int64_t stride, int64_t len, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+				     void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+				     void **out_val, int64_t *bad_index, void *stream)
+{
+	SweepCall c = { "svt_dev_pminmax_sweep", ARI_RULE_PMINMAX, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
+	return abi_status([&] {
+		if (out_Rtype == NULL || out_val == NULL)
+			return svt_set_error("%s: 'out_Rtype' and 'out_val' are needed", c.who);
+		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, bad_index, stream);
 	});
 }
 
@@ -4203,6 +4350,29 @@ extern "C" int svt_Logic_SVT_SVT_begin(const svt_view *x, const svt_view *y, int
 {
 	return compare_begin("svt_Logic_SVT_SVT_begin", ARI_RULE_LOGIC, op, x, y, true, 0.0, 0, res, out_nnz);
 }
+// pmin / pmax and is.na / is.nan / is.infinite on host operands (.pminmax2, .isFUN_SVT): the same begin under the two
+// other rules; svt_Arith_SVT_end ends it.
+extern "C" int svt_pminmax_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int *out_Rtype,
+					 int64_t *out_nnz)
+{
+	return abi_status([&] {
+		if (y == NULL) return svt_set_error("svt_pminmax_SVT_SVT_begin: two operands are needed");
+		return arith_begin_impl("svt_pminmax_SVT_SVT_begin", SVT_ARITH_MERGE, op, x, y, 0.0, 0, res, out_Rtype, out_nnz, NULL,
+					ARI_RULE_PMINMAX);
+	});
+}
+extern "C" int svt_pminmax_SVT_scalar_begin(const svt_view *x, int op, double s, int s_Rtype, svt_arith_result **res,
+					    int *out_Rtype, int64_t *out_nnz)
+{
+	return abi_status([&] {
+		return arith_begin_impl("svt_pminmax_SVT_scalar_begin", SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype, res, out_Rtype, out_nnz,
+					NULL, ARI_RULE_PMINMAX);
+	});
+}
+extern "C" int svt_isFUN_SVT_begin(const svt_view *x, int op, svt_arith_result **res, int64_t *out_nnz)
+{
+	return compare_begin("svt_isFUN_SVT_begin", ARI_RULE_ISFUN, op, x, NULL, false, 0.0, 0, res, out_nnz);
+}
 // sweep(x, MARGIN, STATS, op) on host operands: the margin becomes the three integers of the device index here, the
 // operand and the vector go up, SweepCall::compose() runs on the first device, the result stays there until `end`.
 // `margin`: 1-based, a strictly increasing run of consecutive dimensions.  With dimension 1 in it the vector has a row
@@ -4292,6 +4462,15 @@ extern "C" int svt_Compare_SVT_vector_begin(const svt_view *x, int op, const voi
 		int rt = 0;
 		return sweep_begin_impl("svt_Compare_SVT_vector_begin", ARI_RULE_COMPARE, x, op, stats, stats_len, stats_Rtype, margin, nmargin,
 					bad_index, res, &rt, out_nnz, NULL);
+	});
+}
+extern "C" int svt_pminmax_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
+					    const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res,
+					    int *out_Rtype, int64_t *out_nnz)
+{
+	return abi_status([&] {
+		return sweep_begin_impl("svt_pminmax_SVT_vector_begin", ARI_RULE_PMINMAX, x, op, stats, stats_len, stats_Rtype, margin, nmargin,
+					bad_index, res, out_Rtype, out_nnz, NULL);
 	});
 }
 

@@ -380,20 +380,76 @@ class DeviceCSC:
         return self._logical_result(lambda *a: _lib().svt_dev_compare_map(self.handle, COMPARE_OPCODES[op], float(other),
                                                                           s_Rtype, *a))
 
-    def sweep(self, op: str, stats, margin=2, dim=None, logical: bool = False) -> "DeviceCSC":
+    def _typed_result(self, call):
+        """The new DeviceCSC that ``call(alloc, release, ctx, out_Rtype, nnz, col_ptr, row_idx, val, stream)`` -- one of
+        svt_dev_pminmax_merge / svt_dev_pminmax_map -- leaves in torch allocations, logical, integer or double as the
+        library says; the call stays asynchronous after its count."""
+        mem = _TorchBlocks(self.val.device)
+        rt, nnz = ctypes.c_int(0), c_int64(0)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt), ctypes.byref(nnz), *[ctypes.byref(o) for o in out],
+                    _stream()))
+        dtype = torch.float64 if rt.value == REALSXP else torch.int32
+        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype), logical=rt.value == LGLSXP)
+
+    def _pminmax(self, name: str, other, na_rm) -> "DeviceCSC":
+        from .api import PMINMAX_NA_RM, PMINMAX_OPCODES
+        op = PMINMAX_OPCODES[name] | (PMINMAX_NA_RM if na_rm else 0)
+        if isinstance(other, DeviceCSC):
+            return self._typed_result(lambda *a: _lib().svt_dev_pminmax_merge(self.handle, other.handle, op, *a))
+        s_Rtype = (LGLSXP if isinstance(other, (bool, np.bool_)) else
+                   INTSXP if isinstance(other, (int, np.integer)) else REALSXP)
+        try:
+            return self._typed_result(lambda *a: _lib().svt_dev_pminmax_map(self.handle, op, float(other), s_Rtype, *a))
+        except SparseArrayError as e:
+            if "result wouldn't be sparse" not in str(e):
+                raise
+            raise SparseArrayError(f"{name}(x, {other!r}): {name}(0, {other!r}) is not 0 (result wouldn't be sparse)") from e
+
+    def pmin(self, other, na_rm: bool = False) -> "DeviceCSC":
+        """``pmin(self, other)`` on the device (include/svt_hip.h, svt_dev_pminmax_merge / svt_dev_pminmax_map): ``other``
+        a DeviceCSC of the same nrow and ncol, or a scalar that is not NA / NaN and ``>= 0`` (a Python bool is an R
+        logical, an int an integer, a float a double) -- ``x.pmin(s)`` caps the outliers in one pass.  The result has the
+        wider of the two types; an NA on either side gives NA unless ``na_rm``, which then gives the other side."""
+        return self._pminmax("pmin", other, na_rm)
+
+    def pmax(self, other, na_rm: bool = False) -> "DeviceCSC":
+        """``pmax(self, other)``; as pmin, the scalar ``<= 0``."""
+        return self._pminmax("pmax", other, na_rm)
+
+    def _isfun(self, name: str) -> "DeviceCSC":
+        from .api import ISFUN_OPCODES
+        return self._logical_result(lambda *a: _lib().svt_dev_isfun_map(self.handle, ISFUN_OPCODES[name], *a))
+
+    def is_na(self) -> "DeviceCSC":
+        """``is.na(self)`` on the device (svt_dev_isfun_map): a logical DeviceCSC that stores 1 where an entry is NA or
+        NaN (NA_integer_ for an integer or logical operand)."""
+        return self._isfun("is.na")
+
+    def is_nan(self) -> "DeviceCSC":
+        """``is.nan(self)``: 1 where an entry is a NaN that is not NA_real_; empty for an integer or logical operand."""
+        return self._isfun("is.nan")
+
+    def is_infinite(self) -> "DeviceCSC":
+        """``is.infinite(self)``: 1 where an entry is +-Inf; empty for an integer or logical operand."""
+        return self._isfun("is.infinite")
+
+    def sweep(self, op: str, stats, margin=2, dim=None, logical: bool = False, na_rm: bool = False) -> "DeviceCSC":
         """``sweep(x, margin, stats, op)`` on the device (include/svt_hip.h, svt_dev_arith_sweep / svt_dev_compare_sweep):
         every stored value meets the element of ``stats`` that belongs to its position along ``margin`` -- 1-based, an
         int or a strictly increasing run of consecutive dimensions of the array of extents ``dim`` (default
         (nrow, ncol): 1 the rows, 2 the columns).  ``t(t(x) / colSums(x))`` is ``x.sweep("/", colstats(x, "sum")[0])``,
         R's ``x * w`` with ``len(w) == nrow`` is ``x.sweep("*", w, 1)``.  ``op``: one of ``* / ^ %% %/%`` or of the six
-        comparison operators.  ``stats``: a float64 or int32 tensor on the operand's device (bool, or int32 with
-        ``logical=True``: logical, Compare only), or an array-like; prod(dim[margin]) elements, an N-d one read
-        column-major.  Returns a new DeviceCSC, with ``ovflow`` for Arith, logical for Compare.  An element that would
+        comparison operators, or ``"pmin"`` / ``"pmax"`` (a cap or a floor per row or per leaf, with ``na_rm`` as in
+        pmin(); svt_dev_pminmax_sweep; the result has the wider of the two types).  ``stats``: a float64 or int32 tensor
+        on the operand's device (bool, or int32 with ``logical=True``: logical, for Compare and pmin / pmax, not for
+        Arith), or an array-like; prod(dim[margin]) elements, an N-d one read column-major.  Returns a new DeviceCSC,
+        with ``ovflow`` for Arith, logical for Compare, of the wider type for pmin / pmax.  An element that would
         not keep the result sparse (NA, zero under ``/``, ...) raises SparseArrayError naming its 0-based index and
         value; the library finds it on the device and nothing was written."""
-        from .api import ARITH_OPCODES, COMPARE_OPCODES
-        compare = op in COMPARE_OPCODES
-        if not compare and op not in ARITH_OPCODES:
+        from .api import ARITH_OPCODES, COMPARE_OPCODES, PMINMAX_NA_RM, PMINMAX_OPCODES
+        compare, pminmax = op in COMPARE_OPCODES, op in PMINMAX_OPCODES
+        if not compare and not pminmax and op not in ARITH_OPCODES:
             raise SparseArrayError(f"unknown Arith or Compare operation {op!r}")
         if op in ("+", "-"):
             raise SparseArrayError(f"\"{op}\" is not supported between a SparseArray object and a vector "
@@ -410,6 +466,10 @@ class DeviceCSC:
         bad = c_int64(-1)
         geometry = (vals.data_ptr(), s_Rtype, vals.numel(), with_rows, stride, length)
         try:
+            if pminmax:
+                return self._typed_result(lambda *a: _lib().svt_dev_pminmax_sweep(
+                    self.handle, PMINMAX_OPCODES[op] | (PMINMAX_NA_RM if na_rm else 0), *geometry, *a[:-1],
+                    ctypes.byref(bad), a[-1]))
             if compare:
                 return self._logical_result(lambda *a: _lib().svt_dev_compare_sweep(
                     self.handle, COMPARE_OPCODES[op], *geometry, *a[:-1], ctypes.byref(bad), a[-1]))
