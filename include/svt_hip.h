@@ -972,6 +972,57 @@ int svt_unary_minus_SVT_begin(const svt_view *x, svt_arith_result **res, int *ou
 int svt_Math_SVT_begin(const svt_view *x, int op, double digits, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz);
 int svt_Arith_SVT_end(svt_arith_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val);
 
+/* Sparse x sparse products with a SPARSE result (kernels_spgemm.hip): C = A %*% B, A m x n and B n x K resident 2-D
+   operands of REALSXP or INTSXP, C an m x K operand of REALSXP in the device layout.  svt_dev_matmul_csc_csc() is the
+   same product with a dense result; this one serves the product whose dense form cannot exist (1e6 x 1e4 at 1 % times
+   a 1e4 x 1e4 matrix with a few nonzeros per column: 80 GB dense, a few GB sparse) and the chain that stays on the
+   device (product -> sweep -> log1p -> colVars without a densification).
+
+   The rule.  For every cell (i, k) the value is the sum, in ASCENDING ORDER OF THE INNER INDEX j, of
+   (double) A[i, j] * (double) B[j, k] over the j where A stores an entry at (i, j) AND B stores one at (j, k); the
+   accumulator starts from +0.0, each product is rounded and then added (no fused multiply-add), an integer value is
+   converted as Arith converts it (NA_integer_ becomes NA_real_).  A cell is stored exactly when at least one such pair
+   meets in it and the sum is not == 0: -0.0 and a sum that cancels are dropped, a NaN stays, a stored zero of an operand
+   is an ordinary value (the rule of Arith above).  For finite operands the result is the dense product made sparse;
+   two runs give the same bits; the count pass and the fill pass form the same sums, so a cancellation cannot make
+   them disagree about the number of nonzeros.
+
+   `*not_finite` (device int32, may be NULL) is set to 1 when ANY stored value of A or of B is NaN, +-Inf, NA_real_ or
+   NA_integer_ -- all stored values, not only those a pair reads: there the reference's %*% multiplies the implicit
+   zeros too -- and to 0 otherwise.  The result is written completely under the rule either way; with the flag up its
+   dense form may differ from the reference's answer, with the flag down the two agree cell for cell.
+
+   The work is cut into items (result column, panel of svt_dev_spgemm_panel(nrow) rows of A); result positions are
+   64-bit prefix sums over the items, nnz(C) may exceed 2^31, rows ascend inside every result column.  `_count` writes
+   out_col_ptr int64[K + 1] (all zeros for an empty result) and *not_finite, returns *out_nnz and synchronises `stream`
+   once; `_fill` is asynchronous, takes the same operands on the workspace the count call left and writes out_row_idx
+   int32[*out_nnz] and out_val double[*out_nnz].  Status, each answered before anything is written: < 0 for extents that
+   do not conform ("non-conformable arguments"), a workspace below svt_dev_spgemm_ws_bytes() ("workspace too small"),
+   an LGLSXP operand or any other type; > 0 for an operand with na_background, for B with 2^31 - 1 nonzeros or more
+   (the limit of svt_dev_matmul_csc_csc), for more items than one launch takes and for an LDS request the device
+   refuses.  Alignment and workspace: "Workspaces" above.  svt_dev_spgemm() is the composition count -> allocate -> fill
+   over the allocator of svt_dev_subset(), like svt_dev_arith_merge: the workspace comes from `alloc` and goes back
+   through `release`, the three result arrays (*out_col_ptr int64[K + 1]; *out_row_idx, *out_val of at least one
+   element) are the caller's to release; one synchronisation of `stream`, the fill still queued on return. */
+int svt_dev_spgemm_panel(int64_t nrow);
+size_t svt_dev_spgemm_ws_bytes(const svt_dev_csc *A, int64_t K);
+int svt_dev_spgemm_count(const svt_dev_csc *A, const svt_dev_csc *B, int64_t *out_col_ptr, int64_t *out_nnz, void *ws,
+			 size_t ws_bytes, int *not_finite, void *stream);
+int svt_dev_spgemm_fill(const svt_dev_csc *A, const svt_dev_csc *B, const int64_t *out_col_ptr, int32_t *out_row_idx,
+			double *out_val, const void *ws, size_t ws_bytes, void *stream);
+int svt_dev_spgemm(const svt_dev_csc *A, const svt_dev_csc *B, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx,
+		   int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, double **out_val, int *not_finite,
+		   void *stream);
+/* Host level: x %*% y (tr_x = tr_y = 0), crossprod(x, y) (tr_x != 0: t(x) %*% y) and tcrossprod(x, y) (tr_y != 0:
+   x %*% t(y)) of two 2-D operands of REALSXP or INTSXP, each with its own type.  begin uploads the operands (through the
+   resident cache when it is on), transposes on the device where asked, runs svt_dev_spgemm on the first device of the
+   list (not sharded) and leaves the REALSXP result on the device: *out_nnz its nonzero count, *not_finite (host) the
+   flag above; its extents are those of the product.  svt_Arith_SVT_end copies it out and releases it.  < 0: an operand
+   that is not 2-D ("input objects must have 2 dimensions"), of another type or a NaArray, extents that do not conform
+   ("non-conformable arguments"); > 0: what the device call refuses. */
+int svt_matmul_SVT_SVT_sparse_begin(const svt_view *x, const svt_view *y, int tr_x, int tr_y, svt_arith_result **res,
+				    int64_t *out_nnz, int *not_finite);
+
 /* Compare and Logic on SVT operands (C_Compare_SVT1_SVT2, C_Compare_SVT1_v2, C_Logic_SVT1_SVT2;
    R/SparseArray-Compare-methods.R, R/SparseArray-Logic-methods.R; the element rules of src/SparseVec_Compare.c and
    src/SparseVec_Logic.c): the result is a new LGLSXP operand in the device layout, its values int32 1 or NA_integer_.

@@ -126,6 +126,20 @@ class CAbiDispatcher:
     def C_tcrossprod2_SVT_SVT(self, x: SVT_SparseArray, y: SVT_SparseArray):
         return self._product("tcrossprod2_SVT_SVT", (x.dim[0], y.dim[0]), x, y)
 
+    def C_matmul_SVT_SVT_sparse(self, x: SVT_SparseArray, y: SVT_SparseArray, tr_x: bool, tr_y: bool):
+        """x %*% y, t(x) %*% y (``tr_x``) or x %*% t(y) (``tr_y``) with a sparse result (no counterpart in the reference;
+        include/svt_hip.h, svt_matmul_SVT_SVT_sparse_begin; HIP library only): the begin / svt_Arith_SVT_end pair.
+        Returns (SVT_SparseArray of type "double" without dimnames, not_finite)."""
+        res, nnz, nf = c_void_p(0), ctypes.c_int64(0), c_int(0)
+        self._run("matmul_SVT_SVT_sparse_begin", x, y, int(bool(tr_x)), int(bool(tr_y)), byref(res), byref(nnz), byref(nf))
+        n = int(nnz.value)
+        dim = (x.dim[1 if tr_x else 0], y.dim[0 if tr_y else 1])
+        cp = np.zeros(dim[1] + 1, dtype=np.int64)
+        ri = np.zeros(max(n, 1), dtype=np.int32)
+        vv = np.zeros(max(n, 1), dtype=np.float64)
+        self._run("Arith_SVT_end", res, cp, ri, vv)
+        return SVT_SparseArray.from_csc(dim, "double", cp, ri[:n], vv[:n]), bool(nf.value)
+
     # colMedians (R/SparseArray-matrixStats.R:761-784) --------------------------------
     def C_colMedians_SVT(self, x: SVT_SparseArray, na_rm: bool):
         out = np.zeros(x.dim[1] if x.ndim == 2 else 0, dtype=np.float64)

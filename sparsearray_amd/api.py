@@ -335,6 +335,53 @@ class Session:
             return self._crossprod2_matrix_SparseMatrix(x, y, True)
         raise TypeError("%*% needs at least one SVT_SparseArray")
 
+    # The same three products with a SPARSE result (no counterpart in the reference, whose products are dense;
+    # include/svt_hip.h, svt_matmul_SVT_SVT_sparse_begin): the checks and words of .crossprod2_SparseMatrix_SparseMatrix
+    # on the operands as the product takes them; integer and double operands go over with their own types.
+    def _matmul_sparse(self, what, x, y, tr_x, tr_y):
+        dense = {"matmul_sparse": "%*%", "crossprod_sparse": "crossprod", "tcrossprod_sparse": "tcrossprod"}[what]
+        self._no_NaArray(dense, x, y)
+        if not (isinstance(x, SVT_SparseArray) and isinstance(y, SVT_SparseArray)):
+            raise SparseArrayError(f"{what}() needs two SVT_SparseArray objects")
+        if x.ndim != 2 or y.ndim != 2:
+            raise SparseArrayError("input objects must have 2 dimensions")
+        if x.dim[0 if tr_x else 1] != y.dim[1 if tr_y else 0]:
+            raise SparseArrayError("non-conformable arguments")
+        if x.type == y.type:
+            _check_crossprod_input_type(x.type)
+        else:
+            xy = _common_type(x.type, y.type)
+            _check_crossprod_input_type(xy)
+            # (integer x double goes over as it is and is widened on the device; a logical operand is coerced here)
+            x, y = [o if o.type in _SUPPORTED_MULT_TYPES else o.with_type(xy) for o in (x, y)]
+        self._optional_entry("C_matmul_SVT_SVT_sparse", "matmul_SVT_SVT_sparse_begin")
+        ans, not_finite = self.SparseArray_Call("C_matmul_SVT_SVT_sparse", x, y, bool(tr_x), bool(tr_y))
+        if not_finite:
+            raise SparseArrayUnsupported(f"{what}(): the operands hold non-finite or NA values, where the sparse product "
+                                         "is not the reference's dense answer made sparse; matmul() / crossprod() / "
+                                         "tcrossprod() give the reference's answer")
+        names = lambda o, k: None if o.dimnames is None else o.dimnames[k]      # noqa: E731
+        dn = [names(x, 1 if tr_x else 0), names(y, 0 if tr_y else 1)]
+        ans.dimnames = None if all(n is None for n in dn) else dn
+        return ans
+
+    def matmul_sparse(self, x, y):
+        """``x %*% y`` of two SVT_SparseMatrix objects as an SVT_SparseMatrix of type "double": every cell the sum of
+        its products in ascending order of the inner index, stored unless the sum == 0.  Dimnames
+        ``list(rownames(x), colnames(y))``.  Operands with a non-finite value or an NA raise SparseArrayUnsupported
+        (``matmul()`` gives the reference's answer there)."""
+        return self._matmul_sparse("matmul_sparse", x, y, False, False)
+
+    def crossprod_sparse(self, x, y=None):
+        """``crossprod(x, y)`` = ``t(x) %*% y`` with a sparse result (``y`` None: ``crossprod(x)``); dimnames
+        ``list(colnames(x), colnames(y))``.  See matmul_sparse()."""
+        return self._matmul_sparse("crossprod_sparse", x, x if y is None else y, True, False)
+
+    def tcrossprod_sparse(self, x, y=None):
+        """``tcrossprod(x, y)`` = ``x %*% t(y)`` with a sparse result (``y`` None: ``tcrossprod(x)``); dimnames
+        ``list(rownames(x), rownames(y))``.  See matmul_sparse()."""
+        return self._matmul_sparse("tcrossprod_sparse", x, x if y is None else y, False, True)
+
     # ------------------------------------------------------------------
     # matrixStats  (R/SparseArray-matrixStats.R)
     # ------------------------------------------------------------------

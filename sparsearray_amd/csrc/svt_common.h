@@ -224,6 +224,22 @@ int launch_spmm_prepare(const SpmmArgs &a, int64_t a_nnz, void *ws, hipStream_t 
 int launch_spmm_prepare_for(const SpmmArgs &a, int64_t a_nnz, int64_t b_nnz, void *ws, hipStream_t s, int *zero2);
 int launch_spmm_product(SpmmArgs a, int64_t a_nnz, int64_t b_nnz, const void *ws, hipStream_t s);
 
+// sparse x sparse product with a sparse result (kernels_spgemm.hip): a count launcher that leaves out_col_ptr
+// int64[K + 1], the caller's flag word (device, may be NULL) and, in the head of `ws`, [int: a value of A or of B is not
+// finite or an NA][int64 at byte 8: the nonzeros of the result], and a fill launcher that reads `ws` as the count
+// launcher left it.  Both asynchronous.  spgemm_check(): the refusals that depend on the launch (operand types, grid,
+// LDS), for the caller to ask before anything is written.
+struct SpgemmArgs {
+	const int64_t *a_ptr; const int32_t *a_idx; const void *a_val; int a_type; int64_t nrow, ninner;
+	const int64_t *b_ptr; const int32_t *b_idx; const void *b_val; int b_type; int64_t K;
+};
+int spgemm_panel(void);
+size_t spgemm_ws_bytes(int64_t nrow, int64_t ninner, int64_t K);
+int spgemm_check(const SpgemmArgs &a);
+int launch_spgemm_count(const SpgemmArgs &a, int64_t a_nnz, int64_t b_nnz, int64_t *out_col_ptr, int *not_finite, void *ws,
+			hipStream_t s);
+int launch_spgemm_fill(const SpgemmArgs &a, int32_t *out_row_idx, double *out_val, const void *ws, hipStream_t s);
+
 // sparse x sparse crossprod without a dense operand (kernels_gram.hip)
 struct GramArgs {
 	const int64_t *a_ptr; const int32_t *a_idx; const void *a_val; int a_type;   // t(X): nrow leaves of (column of X, value)

@@ -3045,6 +3045,109 @@ extern "C" int svt_dev_matmul_csc_csc(const svt_dev_csc *A, const svt_dev_csc *B
 	return abi_status([&] { return dev_matmul_csc_csc_impl(A, B, out, ldo, ws, ws_bytes, not_finite, stream); });
 }
 
+// A %*% B, both sparse, with a sparse result (kernels_spgemm.hip): the one statement of the checks and of count / fill
+extern "C" int svt_dev_spgemm_panel(int64_t nrow)
+{
+	(void) nrow;                                        // (one height for every operand today)
+	return spgemm_panel();
+}
+extern "C" size_t svt_dev_spgemm_ws_bytes(const svt_dev_csc *A, int64_t K)
+{
+	return spgemm_ws_bytes(A->nrow, A->ncol, K);
+}
+
+struct SpgemmCall {
+	const char *who;
+	const svt_dev_csc *A, *B;
+	SpgemmArgs args() const
+	{
+		SpgemmArgs a;
+		a.a_ptr = A->col_ptr; a.a_idx = A->row_idx; a.a_val = A->val; a.a_type = A->Rtype; a.nrow = A->nrow; a.ninner = A->ncol;
+		a.b_ptr = B->col_ptr; a.b_idx = B->row_idx; a.b_val = B->val; a.b_type = B->Rtype; a.K = B->ncol;
+		return a;
+	}
+	size_t need() const { return svt_dev_spgemm_ws_bytes(A, B->ncol); }
+	int check(size_t ws_bytes) const
+	{
+		if (A == NULL || B == NULL)
+			return svt_set_error("%s: two operands are needed", who);
+		if (A->ncol != B->nrow)
+			return svt_set_error("%s: non-conformable arguments", who);
+		if ((A->Rtype != SVT_REALSXP && A->Rtype != SVT_INTSXP) || (B->Rtype != SVT_REALSXP && B->Rtype != SVT_INTSXP))
+			return svt_set_error("%s: operands must be of type \"integer\" or \"double\"", who);
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		if (A->na_background || B->na_background)
+			return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+		// the limit of launch_spmm_product, kept for its sparse-result sibling
+		if (B->nnz >= (int64_t) 2147483647)
+			return svt_set_unsupported("%s: the second operand holds 2^31 - 1 nonzeros or more", who);
+		return spgemm_check(args());
+	}
+	int count(int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, int *not_finite, void *stream) const
+	{
+		if (const int rc = check(ws_bytes))
+			return rc;
+		hipStream_t st = (hipStream_t) stream;
+		if (launch_spgemm_count(args(), A->nnz, B->nnz, out_col_ptr, not_finite, ws, st))
+			return -1;
+		int flag = 0;
+		return subset_read_head(ws, st, &flag, out_nnz);
+	}
+	int fill(int32_t *out_row_idx, double *out_val, const void *ws, size_t ws_bytes, void *stream) const
+	{
+		if (const int rc = check(ws_bytes))
+			return rc;
+		return launch_spgemm_fill(args(), out_row_idx, out_val, ws, (hipStream_t) stream);
+	}
+	// count -> allocate -> fill over the caller's allocator
+	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+		    int32_t **out_row_idx, double **out_val, int *not_finite, void *stream) const
+	{
+		if (alloc == NULL || release == NULL)
+			return svt_set_error("%s: an allocator is needed", who);
+		if (A == NULL || B == NULL)
+			return svt_set_error("%s: two operands are needed", who);
+		if (check(need()))
+			return -1;
+		SubsetMem mem = { alloc, release, ctx };
+		SubsetCsc R(mem);
+		SubsetWs ws(mem);
+		int64_t nnz = 0;
+		if (R.shape(A, A->nrow, B->ncol) || ws.get(need()))
+			return -1;
+		R.c.Rtype = SVT_REALSXP; R.c.na_background = 0;
+		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, not_finite, stream) || R.entries(nnz) ||
+		    fill(R.c.row_idx, (double *) R.c.val, ws.p, ws.n, stream))
+			return -1;
+		*out_nnz = nnz;
+		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = (double *) R.c.val;
+		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
+		return 0;
+	}
+};
+
+extern "C" int svt_dev_spgemm_count(const svt_dev_csc *A, const svt_dev_csc *B, int64_t *out_col_ptr, int64_t *out_nnz, void *ws,
+				    size_t ws_bytes, int *not_finite, void *stream)
+{
+	const SpgemmCall c = { "svt_dev_spgemm_count", A, B };
+	return abi_status([&] { return c.count(out_col_ptr, out_nnz, ws, ws_bytes, not_finite, stream); });
+}
+extern "C" int svt_dev_spgemm_fill(const svt_dev_csc *A, const svt_dev_csc *B, const int64_t *out_col_ptr, int32_t *out_row_idx,
+				   double *out_val, const void *ws, size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the item bases in `ws` place the entries)
+	const SpgemmCall c = { "svt_dev_spgemm_fill", A, B };
+	return abi_status([&] { return c.fill(out_row_idx, out_val, ws, ws_bytes, stream); });
+}
+extern "C" int svt_dev_spgemm(const svt_dev_csc *A, const svt_dev_csc *B, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
+			      void *ctx, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, double **out_val,
+			      int *not_finite, void *stream)
+{
+	const SpgemmCall c = { "svt_dev_spgemm", A, B };
+	return abi_status([&] { return c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, not_finite, stream); });
+}
+
 // crossprod(X, Y) of two sparse operands on t(X) and Y (kernels_gram.hip)
 extern "C" size_t svt_dev_crossprod_csc_csc_ws_bytes(const svt_dev_csc *Xt)
 {
@@ -4969,6 +5072,62 @@ static int matmul_SVT_SVT_impl(const svt_view *x, const svt_view *y, double *out
 extern "C" int svt_matmul_SVT_SVT(const svt_view *x, const svt_view *y, double *out)
 {
 	return abi_status([&] { return matmul_SVT_SVT_impl(x, y, out); });
+}
+
+// x %*% y, crossprod(x, y) (tr_x) and tcrossprod(x, y) (tr_y) of two SVT_SparseMatrix objects with a SPARSE result
+// (kernels_spgemm.hip): the operands go up through the resident cache, are transposed on the device where asked,
+// SpgemmCall::compose() runs on the first device and the result stays there until svt_Arith_SVT_end.
+static int matmul_SVT_SVT_sparse_begin_impl(const svt_view *x, const svt_view *y, int tr_x, int tr_y, svt_arith_result **res,
+					    int64_t *out_nnz, int *not_finite)
+{
+	const char *who = "svt_matmul_SVT_SVT_sparse_begin";
+	if (res == NULL || out_nnz == NULL || not_finite == NULL)
+		return svt_set_error("%s: 'res', 'out_nnz' and 'not_finite' are needed", who);
+	*res = NULL;
+	if (ensure_init() || check_mult_view(x, "input objects") || check_mult_view(y, "input objects"))
+		return -1;
+	if (x->dim[tr_x ? 0 : 1] != y->dim[tr_y ? 1 : 0])
+		return svt_set_error("non-conformable arguments");
+	CscGuard X(x);
+	if (X.h == NULL) return -1;
+	CscGuard Y(y);
+	if (Y.h == NULL) return -1;
+	const OwnedCsc Tx = tr_x ? transposed_for(X) : OwnedCsc(NULL, false);
+	const OwnedCsc Ty = tr_y ? transposed_for(Y) : OwnedCsc(NULL, false);
+	const svt_dev_csc *A = tr_x ? Tx.t : X.h, *B = tr_y ? Ty.t : Y.h;
+	if (A == NULL || B == NULL) return -1;
+	DevFlag nf;
+	if (nf.init()) return -1;
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->owned = 1; h->Rtype = SVT_REALSXP; h->nrow = A->nrow; h->ncol = B->ncol;
+	const SpgemmCall c = { who, A, B };
+	double *val = NULL;
+	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &h->nnz, &h->col_ptr, &h->row_idx, &val, nf.ptr(), NULL) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
+		h->val = val;
+		svt_release(h);
+		return -1;
+	}
+	h->val = val;
+	int raised = 0;
+	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
+	if (nf.read(&raised) || r == NULL) {
+		svt_release(h);
+		free(r);
+		return r == NULL ? svt_set_error("out of memory") : -1;
+	}
+	r->h = h;
+	*res = r;
+	*out_nnz = h->nnz;
+	*not_finite = raised;
+	return 0;
+}
+extern "C" int svt_matmul_SVT_SVT_sparse_begin(const svt_view *x, const svt_view *y, int tr_x, int tr_y, svt_arith_result **res,
+					       int64_t *out_nnz, int *not_finite)
+{
+	return abi_status([&] { return matmul_SVT_SVT_sparse_begin_impl(x, y, tr_x, tr_y, res, out_nnz, not_finite); });
 }
 
 // C_crossprod1_SVT, src/SparseMatrix_mult.c:1104-1140

@@ -491,6 +491,11 @@ class DeviceCSC:
             raise SparseArrayError("logic() takes two DeviceCSC operands")
         return self._logical_result(lambda *a: _lib().svt_dev_logic_merge(self.handle, other.handle, LOGIC_OPCODES[op], *a))
 
+    def matmul_sparse(self, other: "DeviceCSC"):
+        """``self %*% other`` with a resident sparse result: (DeviceCSC of type double, not_finite), see
+        matmul_csc_csc_sparse()."""
+        return matmul_csc_csc_sparse(self, other)
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
@@ -1111,6 +1116,53 @@ def matmul_csc_csc(A: DeviceCSC, B: DeviceCSC, out=None, ws=None):
     _check(_lib().svt_dev_matmul_csc_csc(A.handle, B.handle, out.data_ptr(), A.nrow, ws.data_ptr(), ws.numel(),
                                          flag.data_ptr(), _stream()))
     return out, flag
+
+
+def spgemm_panel(nrow: int) -> int:
+    """Rows per panel of the sparse-result product for an operand of ``nrow`` rows (svt_dev_spgemm_panel).  Needs no
+    GPU."""
+    return int(_hip.load_library().svt_dev_spgemm_panel(int(nrow)))
+
+
+def matmul_csc_csc_sparse(A: DeviceCSC, B: DeviceCSC, ws=None):
+    """A %*% B for two resident sparse operands with a resident SPARSE result (include/svt_hip.h, svt_dev_spgemm; with
+    ``ws``, a uint8 tensor of at least svt_dev_spgemm_ws_bytes() bytes, svt_dev_spgemm_count then _fill).  Every cell
+    is the sum of its products in ascending order of the inner index, stored unless the sum == 0.  Returns
+    (DeviceCSC of type double, not_finite): not_finite is a device int32 tensor, nonzero when a stored value of A or
+    of B is not finite or an NA -- the result is complete under the rule, but its dense form may then differ from the
+    reference's ``%*%``."""
+    if not isinstance(A, DeviceCSC) or not isinstance(B, DeviceCSC):
+        raise SparseArrayError("matmul_csc_csc_sparse() takes two DeviceCSC operands")
+    lib, dev = _lib(), A.val.device
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    nnz = c_int64(0)
+    if ws is None:
+        mem = _TorchBlocks(dev)
+        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
+        _check(lib.svt_dev_spgemm(A.handle, B.handle, mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz),
+                                  *[ctypes.byref(o) for o in out], flag.data_ptr(), _stream()))
+        return DeviceCSC(A.nrow, *mem.csc(out, B.ncol, int(nnz.value), torch.float64)), flag
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda
+    cp = torch.empty(B.ncol + 1, dtype=torch.int64, device=dev)
+    _check(lib.svt_dev_spgemm_count(A.handle, B.handle, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
+                                    flag.data_ptr(), _stream()))
+    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    vv = torch.empty(nnz.value, dtype=torch.float64, device=dev)
+    _check(lib.svt_dev_spgemm_fill(A.handle, B.handle, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream()))
+    return DeviceCSC(A.nrow, cp, ri, vv), flag
+
+
+def crossprod_csc_csc_sparse(X: DeviceCSC, Y: DeviceCSC = None):
+    """crossprod(X, Y) = t(X) %*% Y with a resident sparse result (``Y`` None: the unary form, Y = X): ``X.t()`` on the
+    device, then matmul_csc_csc_sparse.  Returns (DeviceCSC, not_finite)."""
+    return matmul_csc_csc_sparse(X.t(), X if Y is None else Y)
+
+
+def tcrossprod_csc_csc_sparse(X: DeviceCSC, Y: DeviceCSC = None):
+    """tcrossprod(X, Y) = X %*% t(Y) with a resident sparse result (``Y`` None: Y = X).  Returns (DeviceCSC,
+    not_finite)."""
+    return matmul_csc_csc_sparse(X, (X if Y is None else Y).t())
 
 
 def crossprod_csc_csc(Xt: DeviceCSC, Y: DeviceCSC, sym=False, out=None, ws=None):
