@@ -24,6 +24,7 @@
 #include <mutex>
 #include <optional>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 static thread_local char g_err[1024];
@@ -1210,16 +1211,31 @@ extern "C" void svt_dev_subset_route_counts(int64_t *counts, int reset)
 	}
 }
 
-// what a count launcher left in the head of its workspace: one copy, the call's one synchronisation
-static int subset_read_head(const void *ws, hipStream_t s, int *flag, int64_t *total)
-{
-	int64_t head[2] = { 0, 0 };
-	HIP_TRY(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	*flag = (int) (head[0] & 0xFFFFFFFFLL);
-	*total = head[1];
-	return 0;
-}
+// what a count launcher left in the first `nwords` (2 or 3) 64-bit words of its workspace: one copy, the call's one
+// synchronisation
+struct WsHead {
+	int flag = 0;                // the low half of word 0
+	int64_t total = 0;           // word 1: the result's nonzeros
+	int64_t third = 0;           // word 2, as it is (sweep: the refused element; the L-index placement: unsorted)
+	int read(const void *ws, hipStream_t s, int nwords = 2)
+	{
+		int64_t head[3] = { 0, 0, 0 };
+		HIP_TRY(hipMemcpyAsync(head, ws, (size_t) nwords * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		flag = (int) (head[0] & 0xFFFFFFFFLL);
+		total = head[1];
+		third = head[2];
+		return 0;
+	}
+	static int total_of(const void *ws, hipStream_t s, int64_t *out_nnz)      // for a count that raises no flag
+	{
+		WsHead head;
+		if (head.read(ws, s))
+			return -1;
+		*out_nnz = head.total;
+		return 0;
+	}
+};
 
 extern "C" size_t svt_dev_subset_cols_ws_bytes(int64_t ncols_sel)
 {
@@ -1240,13 +1256,12 @@ static int dev_subset_cols_count_impl(const svt_dev_csc *A, const int32_t *cols,
 	}
 	if (launch_subset_cols_count(A->col_ptr, A->ncol, cols, ncols_sel, out_col_ptr, ws, (hipStream_t) stream))
 		return -1;
-	int flag = 0;
-	int64_t total = 0;
-	if (subset_read_head(ws, (hipStream_t) stream, &flag, &total))
+	WsHead head;
+	if (head.read(ws, (hipStream_t) stream))
 		return -1;
-	if (flag)
+	if (head.flag)
 		return svt_set_error("subscript out of bounds");
-	*out_nnz = total;
+	*out_nnz = head.total;
 	return 0;
 }
 extern "C" int svt_dev_subset_cols_count(const svt_dev_csc *A, const int32_t *cols, int64_t ncols_sel, int64_t *out_col_ptr,
@@ -1285,15 +1300,14 @@ static int dev_subset_rows_count_impl(const svt_dev_csc *A, const int32_t *rows,
 	if (launch_subset_rows_count(A->col_ptr, A->row_idx, A->nrow, A->ncol, A->nnz, rows, nrows_sel, out_col_ptr, ws,
 				     (hipStream_t) stream))
 		return -1;
-	int flag = 0;
-	int64_t total = 0;
-	if (subset_read_head(ws, (hipStream_t) stream, &flag, &total))
+	WsHead head;
+	if (head.read(ws, (hipStream_t) stream))
 		return -1;
-	if (flag & 1)
+	if (head.flag & 1)
 		return svt_set_error("subscript out of bounds");
-	if (flag)
+	if (head.flag)
 		return svt_set_unsupported("svt_dev_subset_rows_count: the subscript is not strictly increasing");
-	*out_nnz = total;
+	*out_nnz = head.total;
 	return 0;
 }
 extern "C" int svt_dev_subset_rows_count(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, int64_t *out_col_ptr,
@@ -1318,36 +1332,53 @@ extern "C" int svt_dev_subset_rows_fill(const svt_dev_csc *A, const int64_t *out
 	return abi_status([&] { return dev_subset_rows_fill_impl(A, out_row_idx, out_val, ws, ws_bytes, stream); });
 }
 
-// The composition x[rows, cols], stated once: columns first (cheap, and it shrinks the operand), then the rows by the
-// filter when the subscript is strictly increasing, else t() -> column gather with the row subscript -> t().  Every
-// array -- results, intermediates, workspaces -- comes from the caller's allocator.
-struct SubsetMem {
+// ---- the protocol of every entry point that leaves a new sparse operand behind, stated once ----
+// Every array -- the result's three, intermediates, workspaces -- comes from the caller's allocator: col_ptr and the
+// workspace first, then the count step (its read of the workspace head is the call's one synchronisation), row_idx and
+// val for the nonzeros it found, the fill step; the three arrays go to the caller, everything else is released on every
+// exit.  The families differ in their checks (each keeps its own order of refusals), their count and their fill.
+static int need_allocator(const char *who, svt_dev_alloc_fn alloc, svt_dev_free_fn release)
+{
+	return alloc == NULL || release == NULL ? svt_set_error("%s: an allocator is needed", who) : 0;
+}
+struct ResultDest {              // the caller's allocator and where the result's nonzero count and three arrays go
 	svt_dev_alloc_fn alloc;
 	svt_dev_free_fn release;
 	void *ctx;
+	int64_t *nnz;
+	int64_t **col_ptr;
+	int32_t **row_idx;
+	void **val;
+};
+struct ResultMem {
+	const char *who;             // the entry point a failed allocation names
+	svt_dev_alloc_fn alloc;
+	svt_dev_free_fn release;
+	void *ctx;
+	ResultMem(const char *w, const ResultDest &to) : who(w), alloc(to.alloc), release(to.release), ctx(to.ctx) {}
 	void *get(size_t n)
 	{
 		void *p = alloc(n > 0 ? n : 16, ctx);
-		if (p == NULL) svt_set_error("svt_dev_subset: device allocation failed (%zu bytes)", n);
+		if (p == NULL) svt_set_error("%s: device allocation failed (%zu bytes)", who, n);
 		return p;
 	}
 	void put(void *p) { if (p) release(p, ctx); }
 };
-struct SubsetCsc {               // a CSC of three such arrays, given back with this object unless taken
-	SubsetMem &mem;
+struct ResultCsc {               // a CSC of three such arrays, given back with this object unless handed over
+	ResultMem &mem;
 	svt_dev_csc c;
-	explicit SubsetCsc(SubsetMem &m) : mem(m) { memset(&c, 0, sizeof(c)); }
-	SubsetCsc(const SubsetCsc &) = delete;
-	~SubsetCsc() { drop(); }
+	explicit ResultCsc(ResultMem &m) : mem(m) { memset(&c, 0, sizeof(c)); }
+	ResultCsc(const ResultCsc &) = delete;
+	~ResultCsc() { drop(); }
 	void drop()
 	{
 		mem.put(c.col_ptr); mem.put(c.row_idx); mem.put(c.val);
 		c.col_ptr = NULL; c.row_idx = NULL; c.val = NULL;
 	}
-	int shape(const svt_dev_csc *like, int64_t nrow, int64_t ncol)
+	int shape(int Rtype, int na_background, int64_t nrow, int64_t ncol)
 	{
 		drop();
-		c.Rtype = like->Rtype; c.na_background = like->na_background;
+		c.Rtype = Rtype; c.na_background = na_background;
 		c.nrow = nrow; c.ncol = ncol; c.nnz = 0;
 		c.col_ptr = (int64_t *) mem.get(((size_t) ncol + 1) * 8);
 		return c.col_ptr ? 0 : -1;
@@ -1360,91 +1391,126 @@ struct SubsetCsc {               // a CSC of three such arrays, given back with 
 		c.val = mem.get(n * elt_size(c.Rtype));
 		return c.row_idx && c.val ? 0 : -1;
 	}
+	void hand_over(const ResultDest &to)
+	{
+		*to.nnz = c.nnz;
+		*to.col_ptr = c.col_ptr; *to.row_idx = c.row_idx; *to.val = c.val;
+		c.col_ptr = NULL; c.row_idx = NULL; c.val = NULL;   // taken
+	}
 };
-struct SubsetWs {
-	SubsetMem &mem;
+struct ResultWs {
+	ResultMem &mem;
 	void *p = NULL;
 	size_t n = 0;
-	explicit SubsetWs(SubsetMem &m) : mem(m) {}
-	SubsetWs(const SubsetWs &) = delete;
-	~SubsetWs() { mem.put(p); }
+	explicit ResultWs(ResultMem &m) : mem(m) {}
+	ResultWs(const ResultWs &) = delete;
+	~ResultWs() { mem.put(p); }
 	int get(size_t bytes) { p = mem.get(bytes); n = bytes; return p ? 0 : -1; }
 };
 
-static int subset_gather_into(SubsetMem &mem, const svt_dev_csc *A, const int32_t *cols, int64_t n, SubsetCsc &out, void *s)
+// The driver, into an operand that stays with the composition: count(col_ptr, &nnz, ws, ws_bytes), then
+// fill(R.c, ws, ws_bytes); a status of `count` other than 0 ends the call and is returned as it is.
+template <class Count, class Fill>
+static int compose_into(ResultCsc &R, int Rtype, int na_background, int64_t nrow, int64_t ncol, size_t ws_bytes, Count count, Fill fill)
 {
-	SubsetWs ws(mem);
+	ResultWs ws(R.mem);
 	int64_t nnz = 0;
-	if (out.shape(A, A->nrow, n) || ws.get(subset_cols_ws_bytes(n)) ||
-	    dev_subset_cols_count_impl(A, cols, n, out.c.col_ptr, &nnz, ws.p, ws.n, s) || out.entries(nnz))
+	if (R.shape(Rtype, na_background, nrow, ncol) || ws.get(ws_bytes))
 		return -1;
-	return dev_subset_cols_fill_impl(A, cols, n, out.c.col_ptr, out.c.row_idx, out.c.val, s);
+	if (const int rc = count(R.c.col_ptr, &nnz, ws.p, ws.n))
+		return rc;
+	if (R.entries(nnz))
+		return -1;
+	return fill(R.c, ws.p, ws.n);
+}
+// The driver, for the result that goes to the caller
+template <class Count, class Fill>
+static int compose_result(const char *who, const ResultDest &to, int Rtype, int na_background, int64_t nrow, int64_t ncol,
+			  size_t ws_bytes, Count count, Fill fill)
+{
+	ResultMem mem(who, to);
+	ResultCsc R(mem);
+	if (compose_into(R, Rtype, na_background, nrow, ncol, ws_bytes, count, fill))
+		return -1;
+	R.hand_over(to);
+	return 0;
 }
 
-static int subset_transpose_into(SubsetMem &mem, const svt_dev_csc *A, SubsetCsc &out, void *s)
+// The composition x[rows, cols], stated once: columns first (cheap, and it shrinks the operand), then the rows by the
+// filter when the subscript is strictly increasing, else t() -> column gather with the row subscript -> t().
+static int subset_gather_into(const svt_dev_csc *A, const int32_t *cols, int64_t n, ResultCsc &out, void *s)
 {
-	SubsetWs ws(mem);
-	if (out.shape(A, A->ncol, A->nrow) || out.entries(A->nnz) ||
+	return compose_into(out, A->Rtype, A->na_background, A->nrow, n, subset_cols_ws_bytes(n),
+		[&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t ws_bytes) {
+			return dev_subset_cols_count_impl(A, cols, n, col_ptr, nnz, ws, ws_bytes, s);
+		},
+		[&](const svt_dev_csc &R, const void *, size_t) {
+			return dev_subset_cols_fill_impl(A, cols, n, R.col_ptr, R.row_idx, R.val, s);
+		});
+}
+
+static int subset_transpose_into(const svt_dev_csc *A, ResultCsc &out, void *s)
+{
+	ResultWs ws(out.mem);
+	if (out.shape(A->Rtype, A->na_background, A->ncol, A->nrow) || out.entries(A->nnz) ||
 	    ws.get(transpose_ws_bytes_box(A->nrow, A->nnz, box_nnz_get())))
 		return -1;
 	return dev_transpose_impl(A, out.c.col_ptr, out.c.row_idx, out.c.val, ws.p, ws.n, s);
 }
 
 // 0 done, -1 error, 1 the subscript is in range but not strictly increasing (nothing of `out` is of use)
-static int subset_filter_into(SubsetMem &mem, const svt_dev_csc *A, const int32_t *rows, int64_t n, SubsetCsc &out, void *s)
+static int subset_filter_into(const svt_dev_csc *A, const int32_t *rows, int64_t n, ResultCsc &out, void *s)
 {
-	SubsetWs ws(mem);
-	int64_t nnz = 0;
-	if (out.shape(A, n, A->ncol) || ws.get(subset_rows_ws_bytes(A->nrow, A->ncol, A->nnz)))
-		return -1;
-	if (dev_subset_rows_count_impl(A, rows, n, out.c.col_ptr, &nnz, ws.p, ws.n, s)) {
-		if (!g_unsupported) return -1;
-		svt_clear_unsupported();
-		return 1;
-	}
-	if (out.entries(nnz))
-		return -1;
-	return dev_subset_rows_fill_impl(A, out.c.row_idx, out.c.val, ws.p, ws.n, s);
+	return compose_into(out, A->Rtype, A->na_background, n, A->ncol, subset_rows_ws_bytes(A->nrow, A->ncol, A->nnz),
+		[&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t ws_bytes) {
+			if (dev_subset_rows_count_impl(A, rows, n, col_ptr, nnz, ws, ws_bytes, s) == 0) return 0;
+			if (!g_unsupported) return -1;
+			svt_clear_unsupported();
+			return 1;
+		},
+		[&](const svt_dev_csc &R, const void *ws, size_t ws_bytes) {
+			return dev_subset_rows_fill_impl(A, R.row_idx, R.val, ws, ws_bytes, s);
+		});
 }
 
 // rows in any order, with repeats (all in range: the filter's count call has looked): a column gather on t(A)
-static int subset_rows_general_into(SubsetMem &mem, const svt_dev_csc *A, const int32_t *rows, int64_t n, SubsetCsc &out, void *s)
+static int subset_rows_general_into(const svt_dev_csc *A, const int32_t *rows, int64_t n, ResultCsc &out, void *s)
 {
 	g_subset_route[SUBSET_GENERAL]++;
 	if (A->nnz == 0) {
-		if (out.shape(A, n, A->ncol) || out.entries(0))
+		if (out.shape(A->Rtype, A->na_background, n, A->ncol) || out.entries(0))
 			return -1;
 		HIP_TRY(hipMemsetAsync(out.c.col_ptr, 0, ((size_t) A->ncol + 1) * 8, (hipStream_t) s));
 		return 0;
 	}
-	SubsetCsc T(mem), G(mem);
-	if (subset_transpose_into(mem, A, T, s) || subset_gather_into(mem, &T.c, rows, n, G, s))
+	ResultCsc T(out.mem), G(out.mem);
+	if (subset_transpose_into(A, T, s) || subset_gather_into(&T.c, rows, n, G, s))
 		return -1;
 	T.drop();
-	return subset_transpose_into(mem, &G.c, out, s);
+	return subset_transpose_into(&G.c, out, s);
 }
 
 static int dev_subset_impl(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, const int32_t *cols, int64_t ncols_sel,
-			   svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz,
-			   int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+			   const ResultDest &to, void *stream)
 {
-	if (alloc == NULL || release == NULL)
-		return svt_set_error("svt_dev_subset: an allocator is needed");
-	SubsetMem mem = { alloc, release, ctx };
-	SubsetCsc B(mem), R(mem);
+	const char *who = "svt_dev_subset";
+	if (need_allocator(who, to.alloc, to.release))
+		return -1;
+	ResultMem mem(who, to);
+	ResultCsc B(mem), R(mem);
 	const svt_dev_csc *cur = A;
 	if (ncols_sel >= 0) {
-		if (subset_gather_into(mem, A, cols, ncols_sel, B, stream))
+		if (subset_gather_into(A, cols, ncols_sel, B, stream))
 			return -1;
 		cur = &B.c;
 	}
 	if (nrows_sel >= 0) {
-		const int rc = subset_filter_into(mem, cur, rows, nrows_sel, R, stream);
-		if (rc < 0 || (rc > 0 && subset_rows_general_into(mem, cur, rows, nrows_sel, R, stream)))
+		const int rc = subset_filter_into(cur, rows, nrows_sel, R, stream);
+		if (rc < 0 || (rc > 0 && subset_rows_general_into(cur, rows, nrows_sel, R, stream)))
 			return -1;
 	} else if (cur == A) {                              // x[, ]: a copy
 		hipStream_t s = (hipStream_t) stream;
-		if (R.shape(A, A->nrow, A->ncol) || R.entries(A->nnz))
+		if (R.shape(A->Rtype, A->na_background, A->nrow, A->ncol) || R.entries(A->nnz))
 			return -1;
 		HIP_TRY(hipMemcpyAsync(R.c.col_ptr, A->col_ptr, ((size_t) A->ncol + 1) * 8, hipMemcpyDeviceToDevice, s));
 		if (A->nnz > 0) {
@@ -1454,9 +1520,7 @@ static int dev_subset_impl(const svt_dev_csc *A, const int32_t *rows, int64_t nr
 	} else {
 		std::swap(R.c, B.c);
 	}
-	*out_nnz = R.c.nnz;
-	*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
-	R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
+	R.hand_over(to);
 	return 0;
 }
 extern "C" int svt_dev_subset(const svt_dev_csc *A, const int32_t *rows, int64_t nrows_sel, const int32_t *cols,
@@ -1464,8 +1528,8 @@ extern "C" int svt_dev_subset(const svt_dev_csc *A, const int32_t *rows, int64_t
 			      int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
 {
 	return abi_status([&] {
-		return dev_subset_impl(A, rows, nrows_sel, cols, ncols_sel, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx,
-				       out_val, stream);
+		return dev_subset_impl(A, rows, nrows_sel, cols, ncols_sel, { alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val },
+				       stream);
 	});
 }
 
@@ -1680,8 +1744,7 @@ struct ArithCall {
 		if (y != NULL ? launch_arith_merge_count(merge_args(), out_col_ptr, ws, st)
 			      : launch_arith_map_count(map_args(), out_col_ptr, ws, st))
 			return -1;
-		int flag = 0;
-		return subset_read_head(ws, st, &flag, out_nnz);
+		return WsHead::total_of(ws, st, out_nnz);
 	}
 	int fill(int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream)
 	{
@@ -1691,31 +1754,38 @@ struct ArithCall {
 		return y != NULL ? launch_arith_merge_fill(merge_args(), out_row_idx, out_val, ovflow, ws, st)
 				 : launch_arith_map_fill(map_args(), out_row_idx, out_val, ovflow, ws, st);
 	}
-	// count -> allocate -> fill over the caller's allocator
-	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype_p, int64_t *out_nnz,
-		    int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, int *ovflow, void *stream)
+	int compose(const ResultDest &to, int *out_Rtype_p, int *ovflow, void *stream)
 	{
-		if (alloc == NULL || release == NULL)
-			return svt_set_error("%s: an allocator is needed", who);
-		if (check(need()))
+		if (need_allocator(who, to.alloc, to.release) || check(need()))
 			return -1;
-		SubsetMem mem = { alloc, release, ctx };
-		SubsetCsc R(mem);
-		SubsetWs ws(mem);
-		int64_t nnz = 0;
-		if (R.shape(x, x->nrow, x->ncol) || ws.get(need()))
-			return -1;
-		R.c.Rtype = out_Rtype;
-		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, stream) || R.entries(nnz) ||
-		    fill(R.c.row_idx, R.c.val, ovflow, ws.p, ws.n, stream))
+		if (compose_result(who, to, out_Rtype, x->na_background, x->nrow, x->ncol, need(),
+				   [&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) { return count(col_ptr, nnz, ws, n, stream); },
+				   [&](const svt_dev_csc &R, const void *ws, size_t n) { return fill(R.row_idx, R.val, ovflow, ws, n, stream); }))
 			return -1;
 		*out_Rtype_p = out_Rtype;
-		*out_nnz = nnz;
-		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
-		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
 		return 0;
 	}
 };
+
+// The typed outputs of an entry point brought to the form compose() takes -- V int32_t: Compare, Logic and is*(), whose
+// result is logical and which have no 'out_Rtype'; V void: pmin / pmax -- with the status the caller gets
+template <class V, class Compose>
+static int typed_compose(const char *who, int *out_Rtype, V **out_val, Compose compose)
+{
+	return abi_status([&] {
+		const bool lgl = std::is_same<V, int32_t>::value;
+		if (out_val == NULL || (!lgl && out_Rtype == NULL))
+			return svt_set_error(lgl ? "%s: 'out_val' is needed" : "%s: 'out_Rtype' and 'out_val' are needed", who);
+		int rt = 0;
+		void *val = NULL;
+		const int rc = compose(&rt, &val);
+		if (rc == 0) {
+			*out_val = (V *) val;
+			if (!lgl) *out_Rtype = rt;
+		}
+		return rc;
+	});
+}
 
 extern "C" int svt_dev_arith_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr,
 					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
@@ -1737,7 +1807,7 @@ extern "C" int svt_dev_arith_merge(const svt_dev_csc *x, const svt_dev_csc *y, i
 {
 	ArithCall c = { "svt_dev_arith_merge", SVT_ARITH_MERGE, op, x, y, 0.0, 0 };
 	return abi_status([&] {
-		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, ovflow, stream);
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, out_Rtype, ovflow, stream);
 	});
 }
 extern "C" int svt_dev_arith_map_count(const svt_dev_csc *x, int kind, int op, double s, int s_Rtype, int64_t *out_col_ptr,
@@ -1760,7 +1830,7 @@ extern "C" int svt_dev_arith_map(const svt_dev_csc *x, int kind, int op, double 
 {
 	ArithCall c = { "svt_dev_arith_map", kind == SVT_ARITH_MERGE ? -1 : kind, op, x, NULL, s, s_Rtype };
 	return abi_status([&] {
-		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, ovflow, stream);
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, out_Rtype, ovflow, stream);
 	});
 }
 
@@ -1772,17 +1842,13 @@ static ArithCall compare_call(const char *who, int rule, int kind, int op, const
 	c.rule = rule;
 	return c;
 }
-static int compare_compose(ArithCall c, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz,
-			   int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val, void *stream)
+// typed_compose() around the composition of such a call: 'out_Rtype' NULL for Compare, Logic and is*(), given for pmin / pmax
+template <class V>
+static int compare_compose(ArithCall c, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz,
+			   int64_t **out_col_ptr, int32_t **out_row_idx, V **out_val, void *stream)
 {
-	return abi_status([&] {
-		int rt = 0;
-		void *val = NULL;
-		if (out_val == NULL)
-			return svt_set_error("%s: 'out_val' is needed", c.who);
-		const int rc = c.compose(alloc, release, ctx, &rt, out_nnz, out_col_ptr, out_row_idx, &val, NULL, stream);
-		if (rc == 0) *out_val = (int32_t *) val;
-		return rc;
+	return typed_compose(c.who, out_Rtype, out_val, [&](int *rt, void **val) {
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, val }, rt, NULL, stream);
 	});
 }
 
@@ -1804,7 +1870,7 @@ extern "C" int svt_dev_compare_merge(const svt_dev_csc *x, const svt_dev_csc *y,
 				     int32_t **out_row_idx, int32_t **out_val, void *stream)
 {
 	ArithCall c = compare_call("svt_dev_compare_merge", ARI_RULE_COMPARE, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
-	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	return compare_compose(c, alloc, release, ctx, NULL, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 extern "C" int svt_dev_compare_map_count(const svt_dev_csc *x, int op, double s, int s_Rtype, int64_t *out_col_ptr,
 					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
@@ -1824,7 +1890,7 @@ extern "C" int svt_dev_compare_map(const svt_dev_csc *x, int op, double s, int s
 				   int32_t **out_row_idx, int32_t **out_val, void *stream)
 {
 	ArithCall c = compare_call("svt_dev_compare_map", ARI_RULE_COMPARE, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
-	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	return compare_compose(c, alloc, release, ctx, NULL, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 extern "C" int svt_dev_logic_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr,
 					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
@@ -1844,22 +1910,13 @@ extern "C" int svt_dev_logic_merge(const svt_dev_csc *x, const svt_dev_csc *y, i
 				   int32_t **out_row_idx, int32_t **out_val, void *stream)
 {
 	ArithCall c = compare_call("svt_dev_logic_merge", ARI_RULE_LOGIC, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
-	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	return compare_compose(c, alloc, release, ctx, NULL, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 
 // ---- pmin / pmax and is.na / is.nan / is.infinite: the same call object under two more rules; no overflow word ----
 extern "C" int svt_dev_pminmax_out_Rtype(int x_Rtype, int y_Rtype)
 {
 	return svt_rule_assign_out_Rtype(x_Rtype, y_Rtype);
-}
-static int pminmax_compose(ArithCall c, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz,
-			   int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
-{
-	return abi_status([&] {
-		if (out_Rtype == NULL || out_val == NULL)
-			return svt_set_error("%s: 'out_Rtype' and 'out_val' are needed", c.who);
-		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, stream);
-	});
 }
 extern "C" int svt_dev_pminmax_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int op, int64_t *out_col_ptr,
 					   int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
@@ -1879,7 +1936,7 @@ extern "C" int svt_dev_pminmax_merge(const svt_dev_csc *x, const svt_dev_csc *y,
 				     int32_t **out_row_idx, void **out_val, void *stream)
 {
 	ArithCall c = compare_call("svt_dev_pminmax_merge", ARI_RULE_PMINMAX, SVT_ARITH_MERGE, op, x, y, 0.0, 0);
-	return pminmax_compose(c, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	return compare_compose(c, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 extern "C" int svt_dev_pminmax_map_count(const svt_dev_csc *x, int op, double s, int s_Rtype, int64_t *out_col_ptr,
 					 int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
@@ -1899,7 +1956,7 @@ extern "C" int svt_dev_pminmax_map(const svt_dev_csc *x, int op, double s, int s
 				   int32_t **out_row_idx, void **out_val, void *stream)
 {
 	ArithCall c = compare_call("svt_dev_pminmax_map", ARI_RULE_PMINMAX, SVT_ARITH_SCALAR, op, x, NULL, s, s_Rtype);
-	return pminmax_compose(c, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	return compare_compose(c, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 extern "C" int svt_dev_isfun_map_count(const svt_dev_csc *x, int op, int64_t *out_col_ptr, int64_t *out_nnz, void *ws,
 				       size_t ws_bytes, void *stream)
@@ -1918,7 +1975,7 @@ extern "C" int svt_dev_isfun_map(const svt_dev_csc *x, int op, svt_dev_alloc_fn 
 				 int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, int32_t **out_val, void *stream)
 {
 	ArithCall c = compare_call("svt_dev_isfun_map", ARI_RULE_ISFUN, SVT_ARITH_SCALAR, op, x, NULL, 0.0, 0);
-	return compare_compose(c, alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+	return compare_compose(c, alloc, release, ctx, NULL, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
 }
 
 // ---- sweep: x op stats[k], Arith or Compare with one element of a device vector per row or per leaf ----
@@ -1996,14 +2053,14 @@ struct SweepCall {
 		hipStream_t st = (hipStream_t) stream;
 		if (launch_arith_sweep_count(args(), out_col_ptr, ws, st))
 			return -1;
-		int64_t head[3] = { 0, 0, 0 };                      // [1] the result's nonzeros, [2] the refused element
-		HIP_TRY(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		if (head[2] != -1) {
-			if (bad_index != NULL) *bad_index = head[2];
-			return svt_set_error("%s: element %lld of the vector does not keep the result sparse", who, (long long) head[2]);
+		WsHead head;                                        // (the third word: the refused element)
+		if (head.read(ws, st, 3))
+			return -1;
+		if (head.third != -1) {
+			if (bad_index != NULL) *bad_index = head.third;
+			return svt_set_error("%s: element %lld of the vector does not keep the result sparse", who, (long long) head.third);
 		}
-		*out_nnz = head[1];
+		*out_nnz = head.total;
 		return 0;
 	}
 	int fill(int32_t *out_row_idx, void *out_val, int *ovflow, const void *ws, size_t ws_bytes, void *stream)
@@ -2012,28 +2069,16 @@ struct SweepCall {
 			return rc;
 		return launch_arith_sweep_fill(args(), out_row_idx, out_val, ovflow, ws, (hipStream_t) stream);
 	}
-	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype_p, int64_t *out_nnz,
-		    int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, int *ovflow, int64_t *bad_index, void *stream)
+	int compose(const ResultDest &to, int *out_Rtype_p, int *ovflow, int64_t *bad_index, void *stream)
 	{
 		if (bad_index != NULL) *bad_index = -1;
-		if (alloc == NULL || release == NULL)
-			return svt_set_error("%s: an allocator is needed", who);
-		if (const int rc = x == NULL ? check(0) : check(need()))
-			return rc;
-		SubsetMem mem = { alloc, release, ctx };
-		SubsetCsc R(mem);
-		SubsetWs ws(mem);
-		int64_t nnz = 0;
-		if (R.shape(x, x->nrow, x->ncol) || ws.get(need()))
+		if (need_allocator(who, to.alloc, to.release) || (x == NULL ? check(0) : check(need())))
 			return -1;
-		R.c.Rtype = out_Rtype;
-		if (count(R.c.col_ptr, &nnz, bad_index, ws.p, ws.n, stream) || R.entries(nnz) ||
-		    fill(R.c.row_idx, R.c.val, ovflow, ws.p, ws.n, stream))
+		if (compose_result(who, to, out_Rtype, x->na_background, x->nrow, x->ncol, need(),
+				   [&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) { return count(col_ptr, nnz, bad_index, ws, n, stream); },
+				   [&](const svt_dev_csc &R, const void *ws, size_t n) { return fill(R.row_idx, R.val, ovflow, ws, n, stream); }))
 			return -1;
 		*out_Rtype_p = out_Rtype;
-		*out_nnz = nnz;
-		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
-		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
 		return 0;
 	}
 };
@@ -2064,7 +2109,7 @@ extern "C" int svt_dev_arith_sweep(const svt_dev_csc *x, int op, const void *sta
 {
 	SweepCall c = { "svt_dev_arith_sweep", ARI_RULE_ARITH, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
 	return abi_status([&] {
-		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, ovflow, bad_index, stream);
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, out_Rtype, ovflow, bad_index, stream);
 	});
 }
 extern "C" int svt_dev_compare_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
@@ -2088,14 +2133,8 @@ extern "C" int svt_dev_compare_sweep(const svt_dev_csc *x, int op, const void *s
 				     int64_t *bad_index, void *stream)
 {
 	SweepCall c = { "svt_dev_compare_sweep", ARI_RULE_COMPARE, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
-	return abi_status([&] {
-		int rt = 0;
-		void *val = NULL;
-		if (out_val == NULL)
-			return svt_set_error("%s: 'out_val' is needed", c.who);
-		const int rc = c.compose(alloc, release, ctx, &rt, out_nnz, out_col_ptr, out_row_idx, &val, NULL, bad_index, stream);
-		if (rc == 0) *out_val = (int32_t *) val;
-		return rc;
+	return typed_compose(c.who, NULL, out_val, [&](int *rt, void **val) {
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, val }, rt, NULL, bad_index, stream);
 	});
 }
 extern "C" int svt_dev_pminmax_sweep_count(const svt_dev_csc *x, int op, const void *stats, int stats_Rtype, int64_t stats_len,
@@ -2119,10 +2158,8 @@ extern "C" int svt_dev_pminmax_sweep(const svt_dev_csc *x, int op, const void *s
 				     void **out_val, int64_t *bad_index, void *stream)
 {
 	SweepCall c = { "svt_dev_pminmax_sweep", ARI_RULE_PMINMAX, op, x, stats, stats_Rtype, stats_len, with_rows, stride, len };
-	return abi_status([&] {
-		if (out_Rtype == NULL || out_val == NULL)
-			return svt_set_error("%s: 'out_Rtype' and 'out_val' are needed", c.who);
-		return c.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, bad_index, stream);
+	return typed_compose(c.who, out_Rtype, out_val, [&](int *rt, void **val) {
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, val }, rt, NULL, bad_index, stream);
 	});
 }
 
@@ -2249,13 +2286,12 @@ struct AbindCall {
 		}
 		if (launch_abind_count(a, out_col_ptr, ws, st))
 			return -1;
-		int flag = 0;
-		int64_t total = 0;
-		if (subset_read_head(ws, st, &flag, &total))        // (the table of objects has been copied by now)
+		WsHead head;
+		if (head.read(ws, st))                              // (the table of objects has been copied by now)
 			return -1;
-		if (flag)
+		if (head.flag)
 			return svt_set_error("%s: the column pointers of an object descend or pass its nonzeros", who);
-		*out_nnz = total;
+		*out_nnz = head.total;
 		return 0;
 	}
 	int fill(int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream)
@@ -2264,29 +2300,26 @@ struct AbindCall {
 			return svt_set_error("%s: workspace too small", who);
 		return launch_abind_fill(a, out_row_idx, out_val, ws, (hipStream_t) stream);
 	}
-	// count -> allocate -> fill over the caller's allocator
-	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
-		    int32_t **out_row_idx, void **out_val, void *stream)
+	int compose(const ResultDest &to, void *stream)
 	{
-		if (alloc == NULL || release == NULL)
-			return svt_set_error("%s: an allocator is needed", who);
-		SubsetMem mem = { alloc, release, ctx };
-		SubsetCsc R(mem);
-		SubsetWs ws(mem);
-		int64_t nnz = 0;
-		svt_dev_csc like;
-		memset(&like, 0, sizeof(like));
-		like.Rtype = a.ans_Rtype; like.na_background = na_background;
-		if (R.shape(&like, out_nrow, a.out_nleaves) || ws.get(need()))
+		if (need_allocator(who, to.alloc, to.release))
 			return -1;
-		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, stream) || R.entries(nnz) || fill(R.c.row_idx, R.c.val, ws.p, ws.n, stream))
-			return -1;
-		*out_nnz = nnz;
-		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
-		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
-		return 0;
+		return compose_result(who, to, a.ans_Rtype, na_background, out_nrow, a.out_nleaves, need(),
+			[&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) { return count(col_ptr, nnz, ws, n, stream); },
+			[&](const svt_dev_csc &R, const void *ws, size_t n) { return fill(R.row_idx, R.val, ws, n, stream); });
 	}
 };
+
+// x as it is in the type `rt`, the one-object case of abind: the result of a subassignment that selects nothing
+static int compose_coerced(const char *who, const svt_dev_csc *x, int rt, const ResultDest &to, int *out_Rtype, void *stream)
+{
+	AbindCall c = { who };
+	const svt_dev_csc *objs[1] = { x };
+	if (c.plan(objs, 1, 0, NULL, rt) || c.compose(to, stream))
+		return -1;
+	*out_Rtype = rt;
+	return 0;
+}
 
 extern "C" int svt_dev_abind_count(const svt_dev_csc *const *objs, int nobj, int64_t inner, const int64_t *ext, int ans_Rtype,
 				   int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
@@ -2315,7 +2348,7 @@ extern "C" int svt_dev_abind(const svt_dev_csc *const *objs, int nobj, int64_t i
 	return abi_status([&] {
 		AbindCall c = { "svt_dev_abind" };
 		if (c.plan(objs, nobj, inner, ext, ans_Rtype) ||
-		    c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream))
+		    c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, stream))
 			return -1;
 		*out_nrow = c.out_nrow;
 		*out_nleaves = c.a.out_nleaves;
@@ -2382,8 +2415,7 @@ struct FromDenseCall {
 		}
 		if (launch_from_dense_count(a, out_col_ptr, ws, st))
 			return -1;
-		int flag = 0;
-		return subset_read_head(ws, st, &flag, out_nnz);
+		return WsHead::total_of(ws, st, out_nnz);
 	}
 	int fill(int32_t *out_row_idx, void *out_val, const void *ws, size_t ws_bytes, void *stream)
 	{
@@ -2391,27 +2423,13 @@ struct FromDenseCall {
 			return svt_set_error("%s: workspace too small", who);
 		return launch_from_dense_fill(a, out_row_idx, out_val, ws, (hipStream_t) stream);
 	}
-	// count -> allocate -> fill over the caller's allocator
-	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
-		    int32_t **out_row_idx, void **out_val, void *stream)
+	int compose(const ResultDest &to, void *stream)
 	{
-		if (alloc == NULL || release == NULL)
-			return svt_set_error("%s: an allocator is needed", who);
-		SubsetMem mem = { alloc, release, ctx };
-		SubsetCsc R(mem);
-		SubsetWs ws(mem);
-		int64_t nnz = 0;
-		svt_dev_csc like;
-		memset(&like, 0, sizeof(like));
-		like.Rtype = a.ans_Rtype; like.na_background = a.na_background;
-		if (R.shape(&like, a.nrow, a.nleaves) || ws.get(need()))
+		if (need_allocator(who, to.alloc, to.release))
 			return -1;
-		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, stream) || R.entries(nnz) || fill(R.c.row_idx, R.c.val, ws.p, ws.n, stream))
-			return -1;
-		*out_nnz = nnz;
-		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = R.c.val;
-		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
-		return 0;
+		return compose_result(who, to, a.ans_Rtype, a.na_background, a.nrow, a.nleaves, need(),
+			[&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) { return count(col_ptr, nnz, ws, n, stream); },
+			[&](const svt_dev_csc &R, const void *ws, size_t n) { return fill(R.row_idx, R.val, ws, n, stream); });
 	}
 };
 
@@ -2442,7 +2460,7 @@ extern "C" int svt_dev_from_dense(const void *x, int x_Rtype, int64_t nrow, int6
 	return abi_status([&] {
 		FromDenseCall c = { "svt_dev_from_dense" };
 		if (c.plan(x, x_Rtype, nrow, nleaves, ans_Rtype, na_background)) return -1;
-		return c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, stream);
 	});
 }
 
@@ -2512,6 +2530,30 @@ extern "C" size_t svt_dev_subassign_place_ws_bytes(int64_t nrow, int64_t ncol)
 	return subassign_ws_bytes(nrow, ncol);
 }
 
+// The merge that writes the placed operand y over x, under the two cover tables or (no tables) under the rule of the cells
+static ArithCall assign_call(const char *who, const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
+			     const unsigned char *cover_leaf, int rule = ARI_RULE_ASSIGN)
+{
+	ArithCall c = { who, SVT_ARITH_MERGE, 0, x, y, 0.0, 0 };
+	c.rule = rule;
+	c.cover_row = cover_row; c.cover_leaf = cover_leaf;
+	return c;
+}
+static ArithCall assign_cells_call(const char *who, const svt_dev_csc *x, const svt_dev_csc *y)
+{
+	return assign_call(who, x, y, NULL, NULL, ARI_RULE_ASSIGN_CELLS);
+}
+// what a composed subassignment refuses about x and the value's type before it places anything; *rt <- the wider type
+static int assign_out_Rtype(const char *who, const svt_dev_csc *x, int v_Rtype, int *rt)
+{
+	*rt = svt_rule_assign_out_Rtype(x->Rtype, v_Rtype);
+	if (*rt == 0)
+		return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
+	if (x->na_background)
+		return svt_set_unsupported("%s: NaArray operands are not supported here", who);
+	return 0;
+}
+
 // One placement, of either form (v != NULL: the SVT form): every check that needs no GPU, then count / fill.
 struct SubassignCall {
 	const char *who;
@@ -2560,15 +2602,14 @@ struct SubassignCall {
 		hipStream_t st = (hipStream_t) stream;
 		if (launch_subassign_count(a, y_col_ptr, cover_row, cover_leaf, ws, st))
 			return -1;
-		int flag = 0;
-		int64_t total = 0;
-		if (subset_read_head(ws, st, &flag, &total))
+		WsHead head;
+		if (head.read(ws, st))
 			return -1;
-		if (flag & 1)
+		if (head.flag & 1)
 			return svt_set_error("subscript contains out-of-bound indices or NAs");
-		if (flag)
+		if (head.flag)
 			return svt_set_unsupported("%s: the row subscript is not strictly increasing, or a leaf is repeated", who);
-		*y_nnz = total;
+		*y_nnz = head.total;
 		return 0;
 	}
 	int fill(const int64_t *y_col_ptr, int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes, void *stream)
@@ -2578,43 +2619,30 @@ struct SubassignCall {
 		return launch_subassign_fill(a, y_col_ptr, y_nnz, y_row_idx, y_val, ws, (hipStream_t) stream);
 	}
 	// place -> merge over the caller's allocator: the whole of x[rows, leaves] <- value
-	int compose(const svt_dev_csc *x, svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int *out_Rtype, int64_t *out_nnz,
-		    int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+	int compose(const svt_dev_csc *x, const ResultDest &to, int *out_Rtype, void *stream)
 	{
-		if (alloc == NULL || release == NULL)
-			return svt_set_error("%s: an allocator is needed", who);
-		const int rt = svt_rule_assign_out_Rtype(x->Rtype, a.v_Rtype);
-		if (rt == 0)
-			return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
-		if (x->na_background)
-			return svt_set_unsupported("%s: NaArray operands are not supported here", who);
-		if (a.nrows_sel == 0 || a.nleaves_sel == 0) {       // nothing selected: x, coerced (the one-object case of abind)
-			AbindCall c = { who };
-			const svt_dev_csc *objs[1] = { x };
-			if (c.plan(objs, 1, 0, NULL, rt) || c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream))
-				return -1;
-			*out_Rtype = rt;
-			return 0;
-		}
-		SubsetMem mem = { alloc, release, ctx };
-		SubsetCsc Y(mem);
-		SubsetWs ws(mem), cover(mem);
-		svt_dev_csc like;
-		memset(&like, 0, sizeof(like));
-		like.Rtype = a.v_Rtype;
+		int rt = 0;
+		if (need_allocator(who, to.alloc, to.release) || assign_out_Rtype(who, x, a.v_Rtype, &rt))
+			return -1;
+		if (a.nrows_sel == 0 || a.nleaves_sel == 0)         // nothing selected
+			return compose_coerced(who, x, rt, to, out_Rtype, stream);
+		ResultMem mem(who, to);
+		ResultCsc Y(mem);
+		ResultWs cover(mem);                                // the two tables, the merge reads them: allocated third, kept to the end
 		const size_t row_bytes = ((size_t) x->nrow + 255) / 256 * 256;
-		if (Y.shape(&like, x->nrow, x->ncol) || ws.get(need()) || cover.get(row_bytes + (size_t) x->ncol))
+		unsigned char *cover_row = NULL, *cover_leaf = NULL;
+		if (compose_into(Y, a.v_Rtype, 0, x->nrow, x->ncol, need(),
+				 [&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) {
+					 if (cover.get(row_bytes + (size_t) x->ncol)) return -1;
+					 if (a.nrows_sel >= 0) cover_row = (unsigned char *) cover.p;
+					 if (a.nleaves_sel >= 0) cover_leaf = (unsigned char *) cover.p + row_bytes;
+					 return count(col_ptr, cover_row, cover_leaf, nnz, ws, n, stream);
+				 },
+				 [&](const svt_dev_csc &R, const void *ws, size_t n) {
+					 return fill(R.col_ptr, R.nnz, R.row_idx, R.val, ws, n, stream);
+				 }))
 			return -1;
-		unsigned char *cover_row = a.nrows_sel < 0 ? NULL : (unsigned char *) cover.p;
-		unsigned char *cover_leaf = a.nleaves_sel < 0 ? NULL : (unsigned char *) cover.p + row_bytes;
-		int64_t y_nnz = 0;
-		if (count(Y.c.col_ptr, cover_row, cover_leaf, &y_nnz, ws.p, ws.n, stream) || Y.entries(y_nnz) ||
-		    fill(Y.c.col_ptr, y_nnz, Y.c.row_idx, Y.c.val, ws.p, ws.n, stream))
-			return -1;
-		ArithCall m = { who, SVT_ARITH_MERGE, 0, x, &Y.c, 0.0, 0 };
-		m.rule = ARI_RULE_ASSIGN;
-		m.cover_row = cover_row; m.cover_leaf = cover_leaf;
-		return m.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, stream);
+		return assign_call(who, x, &Y.c, cover_row, cover_leaf).compose(to, out_Rtype, NULL, stream);
 	}
 };
 
@@ -2663,14 +2691,6 @@ extern "C" int svt_dev_subassign_place_svt_fill(int64_t nrow, int64_t ncol, cons
 	});
 }
 
-static ArithCall assign_call(const char *who, const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
-			     const unsigned char *cover_leaf)
-{
-	ArithCall c = { who, SVT_ARITH_MERGE, 0, x, y, 0.0, 0 };
-	c.rule = ARI_RULE_ASSIGN;
-	c.cover_row = cover_row; c.cover_leaf = cover_leaf;
-	return c;
-}
 extern "C" int svt_dev_assign_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, const unsigned char *cover_row,
 					  const unsigned char *cover_leaf, int64_t *out_col_ptr, int64_t *out_nnz, void *ws,
 					  size_t ws_bytes, void *stream)
@@ -2696,7 +2716,7 @@ extern "C" int svt_dev_subassign_vector(const svt_dev_csc *x, const int32_t *row
 		SubassignCall c = { "svt_dev_subassign_vector" };
 		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
 		if (c.plan(x->nrow, x->ncol, rows, nrows_sel, leaves, nleaves_sel, vals, nvals, v_Rtype, NULL, false)) return -1;
-		return c.compose(x, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+		return c.compose(x, { alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, out_Rtype, stream);
 	});
 }
 extern "C" int svt_dev_subassign_svt(const svt_dev_csc *x, const int32_t *rows, int64_t nrows_sel, const int32_t *leaves,
@@ -2708,7 +2728,7 @@ extern "C" int svt_dev_subassign_svt(const svt_dev_csc *x, const int32_t *rows, 
 		SubassignCall c = { "svt_dev_subassign_svt" };
 		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
 		if (c.plan(x->nrow, x->ncol, rows, nrows_sel, leaves, nleaves_sel, NULL, 0, 0, v, true)) return -1;
-		return c.compose(x, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+		return c.compose(x, { alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, out_Rtype, stream);
 	});
 }
 
@@ -2810,21 +2830,17 @@ struct LindexCall {
 		hipStream_t st = (hipStream_t) stream;
 		if (launch_lindex_check(a, ws, st))
 			return -1;
-		int64_t head[3] = { 0, 0, 0 };                      // [flag][the entries of Y][unsorted, the route]
-		HIP_TRY(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		if (head[0] & 0xFFFFFFFFLL)
+		WsHead head;                                        // (the third word: unsorted, the route)
+		if (head.read(ws, st, 3))
+			return -1;
+		if (head.flag)
 			return svt_set_error("%s", bad_index_message());
-		const int unsorted = (head[2] & 0xFFFFFFFFLL) != 0;
+		const int unsorted = (head.third & 0xFFFFFFFFLL) != 0;
 		g_lindex_route[unsorted ? LINDEX_UNSORTED : LINDEX_SORTED]++;
 		if (launch_lindex_place(a, unsorted, y_col_ptr, ws, st))
 			return -1;
 		*y_nnz = a.K;                                       // the sorted route: every index is an entry
-		if (unsorted) {
-			int flag = 0;
-			return subset_read_head(ws, st, &flag, y_nnz);
-		}
-		return 0;
+		return unsorted ? WsHead::total_of(ws, st, y_nnz) : 0;
 	}
 	int fill(const void *vals, int64_t nvals, int v_Rtype, int64_t y_nnz, int32_t *y_row_idx, void *y_val, const void *ws, size_t ws_bytes,
 		 void *stream)
@@ -2836,41 +2852,25 @@ struct LindexCall {
 		return launch_lindex_fill(a, vals, nvals, v_Rtype, y_nnz, y_row_idx, y_val, ws, (hipStream_t) stream);
 	}
 	// place -> merge over the caller's allocator: the whole of x[index] <- vals
-	int compose(const svt_dev_csc *x, const void *vals, int64_t nvals, int v_Rtype, svt_dev_alloc_fn alloc, svt_dev_free_fn release,
-		    void *ctx, int *out_Rtype, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx, void **out_val, void *stream)
+	int compose(const svt_dev_csc *x, const void *vals, int64_t nvals, int v_Rtype, const ResultDest &to, int *out_Rtype, void *stream)
 	{
-		if (alloc == NULL || release == NULL)
-			return svt_set_error("%s: an allocator is needed", who);
-		if (const int rc = check_values(vals, nvals, v_Rtype, need()))
-			return rc;
-		const int rt = svt_rule_assign_out_Rtype(x->Rtype, v_Rtype);
-		if (rt == 0)
-			return svt_set_error("%s: operands must be of type \"logical\", \"integer\" or \"double\"", who);
-		if (x->na_background)
-			return svt_set_unsupported("%s: NaArray operands are not supported here", who);
-		if (a.K == 0) {                                     // nothing assigned: x, coerced (the one-object case of abind)
-			AbindCall c = { who };
-			const svt_dev_csc *objs[1] = { x };
-			if (c.plan(objs, 1, 0, NULL, rt) || c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, stream))
-				return -1;
-			*out_Rtype = rt;
-			return 0;
-		}
-		SubsetMem mem = { alloc, release, ctx };
-		SubsetCsc Y(mem);
-		SubsetWs ws(mem);
-		svt_dev_csc like;
-		memset(&like, 0, sizeof(like));
-		like.Rtype = v_Rtype;
-		if (Y.shape(&like, x->nrow, x->ncol) || ws.get(need()))
+		int rt = 0;
+		if (need_allocator(who, to.alloc, to.release) || check_values(vals, nvals, v_Rtype, need()) ||
+		    assign_out_Rtype(who, x, v_Rtype, &rt))
 			return -1;
-		int64_t y_nnz = 0;
-		if (count(vals, nvals, v_Rtype, Y.c.col_ptr, &y_nnz, ws.p, ws.n, stream) || Y.entries(y_nnz) ||
-		    fill(vals, nvals, v_Rtype, y_nnz, Y.c.row_idx, Y.c.val, ws.p, ws.n, stream))
+		if (a.K == 0)                                       // nothing assigned
+			return compose_coerced(who, x, rt, to, out_Rtype, stream);
+		ResultMem mem(who, to);
+		ResultCsc Y(mem);
+		if (compose_into(Y, v_Rtype, 0, x->nrow, x->ncol, need(),
+				 [&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) {
+					 return count(vals, nvals, v_Rtype, col_ptr, nnz, ws, n, stream);
+				 },
+				 [&](const svt_dev_csc &R, const void *ws, size_t n) {
+					 return fill(vals, nvals, v_Rtype, R.nnz, R.row_idx, R.val, ws, n, stream);
+				 }))
 			return -1;
-		ArithCall m = { who, SVT_ARITH_MERGE, 0, x, &Y.c, 0.0, 0 };
-		m.rule = ARI_RULE_ASSIGN_CELLS;
-		return m.compose(alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, NULL, stream);
+		return assign_cells_call(who, x, &Y.c).compose(to, out_Rtype, NULL, stream);
 	}
 };
 
@@ -2917,12 +2917,6 @@ extern "C" int svt_dev_subassign_place_lindex_fill(int64_t nrow, int64_t ncol, c
 	});
 }
 
-static ArithCall assign_cells_call(const char *who, const svt_dev_csc *x, const svt_dev_csc *y)
-{
-	ArithCall c = { who, SVT_ARITH_MERGE, 0, x, y, 0.0, 0 };
-	c.rule = ARI_RULE_ASSIGN_CELLS;
-	return c;
-}
 extern "C" int svt_dev_assign_cells_merge_count(const svt_dev_csc *x, const svt_dev_csc *y, int64_t *out_col_ptr, int64_t *out_nnz,
 						void *ws, size_t ws_bytes, void *stream)
 {
@@ -2945,7 +2939,7 @@ extern "C" int svt_dev_subassign_lindex(const svt_dev_csc *x, const int64_t *lin
 		LindexCall c = { "svt_dev_subassign_lindex" };
 		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
 		if (c.plan(x->nrow, x->ncol, lindex, K, 0, NULL)) return -1;
-		return c.compose(x, vals, nvals, v_Rtype, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+		return c.compose(x, vals, nvals, v_Rtype, { alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, out_Rtype, stream);
 	});
 }
 extern "C" int svt_dev_subassign_mindex(const svt_dev_csc *x, const int32_t *mindex, int64_t K, int ndim, const int64_t *dim,
@@ -2958,7 +2952,7 @@ extern "C" int svt_dev_subassign_mindex(const svt_dev_csc *x, const int32_t *min
 		if (x == NULL) return svt_set_error("%s: an operand is needed", c.who);
 		if (ndim < 1) return svt_set_error("%s: an M-index takes between 1 and 8 dimensions", c.who);
 		if (c.plan(x->nrow, x->ncol, mindex, K, ndim, dim)) return -1;
-		return c.compose(x, vals, nvals, v_Rtype, alloc, release, ctx, out_Rtype, out_nnz, out_col_ptr, out_row_idx, out_val, stream);
+		return c.compose(x, vals, nvals, v_Rtype, { alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, out_Rtype, stream);
 	});
 }
 
@@ -3091,8 +3085,7 @@ struct SpgemmCall {
 		hipStream_t st = (hipStream_t) stream;
 		if (launch_spgemm_count(args(), A->nnz, B->nnz, out_col_ptr, not_finite, ws, st))
 			return -1;
-		int flag = 0;
-		return subset_read_head(ws, st, &flag, out_nnz);
+		return WsHead::total_of(ws, st, out_nnz);
 	}
 	int fill(int32_t *out_row_idx, double *out_val, const void *ws, size_t ws_bytes, void *stream) const
 	{
@@ -3100,30 +3093,17 @@ struct SpgemmCall {
 			return rc;
 		return launch_spgemm_fill(args(), out_row_idx, out_val, ws, (hipStream_t) stream);
 	}
-	// count -> allocate -> fill over the caller's allocator
-	int compose(svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
-		    int32_t **out_row_idx, double **out_val, int *not_finite, void *stream) const
+	int compose(const ResultDest &to, int *not_finite, void *stream) const
 	{
-		if (alloc == NULL || release == NULL)
-			return svt_set_error("%s: an allocator is needed", who);
+		if (need_allocator(who, to.alloc, to.release))
+			return -1;
 		if (A == NULL || B == NULL)
 			return svt_set_error("%s: two operands are needed", who);
 		if (check(need()))
 			return -1;
-		SubsetMem mem = { alloc, release, ctx };
-		SubsetCsc R(mem);
-		SubsetWs ws(mem);
-		int64_t nnz = 0;
-		if (R.shape(A, A->nrow, B->ncol) || ws.get(need()))
-			return -1;
-		R.c.Rtype = SVT_REALSXP; R.c.na_background = 0;
-		if (count(R.c.col_ptr, &nnz, ws.p, ws.n, not_finite, stream) || R.entries(nnz) ||
-		    fill(R.c.row_idx, (double *) R.c.val, ws.p, ws.n, stream))
-			return -1;
-		*out_nnz = nnz;
-		*out_col_ptr = R.c.col_ptr; *out_row_idx = R.c.row_idx; *out_val = (double *) R.c.val;
-		R.c.col_ptr = NULL; R.c.row_idx = NULL; R.c.val = NULL;   // taken
-		return 0;
+		return compose_result(who, to, SVT_REALSXP, 0, A->nrow, B->ncol, need(),
+			[&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) { return count(col_ptr, nnz, ws, n, not_finite, stream); },
+			[&](const svt_dev_csc &R, const void *ws, size_t n) { return fill(R.row_idx, (double *) R.val, ws, n, stream); });
 	}
 };
 
@@ -3145,7 +3125,12 @@ extern "C" int svt_dev_spgemm(const svt_dev_csc *A, const svt_dev_csc *B, svt_de
 			      int *not_finite, void *stream)
 {
 	const SpgemmCall c = { "svt_dev_spgemm", A, B };
-	return abi_status([&] { return c.compose(alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val, not_finite, stream); });
+	return abi_status([&] {
+		void *val = NULL;                                   // (the result is double: 'out_val' is typed)
+		const int rc = c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, &val }, not_finite, stream);
+		if (rc == 0) *out_val = (double *) val;
+		return rc;
+	});
 }
 
 // crossprod(X, Y) of two sparse operands on t(X) and Y (kernels_gram.hip)
@@ -4263,12 +4248,46 @@ static int subset_index0(const int *idx, int64_t n, int extent, std::vector<int3
 	return 0;
 }
 
-static void *subset_hip_alloc(size_t n, void *)
+static void *result_hip_alloc(size_t n, void *)
 {
 	void *p = NULL;
 	return hipMalloc(&p, n) == hipSuccess ? p : NULL;
 }
-static void subset_hip_free(void *p, void *) { (void) hipFree(p); }
+static void result_hip_free(void *p, void *) { (void) hipFree(p); }
+
+// The tail of every `begin` that leaves a result on the device, stated once: the handle that owns the result is made with
+// the type and extents given, `compose(to, &Rtype)` runs on the default stream over hipMalloc / hipFree, the stream is
+// synchronised; a failure without a message gets the default text, and every failure releases what there is.  Then the
+// result record is made, the flag word is read where there is one (`flag`: the overflow of Arith and sweep, the
+// not_finite of the product) and the outputs are published ('out_Rtype' and 'raised' may be NULL).
+template <class Res, class Compose>
+static int result_begin(const char *who, int Rtype, int na_background, int64_t nrow, int64_t ncol, Compose compose, DevFlag *flag,
+			Res **res, int *out_Rtype, int64_t *out_nnz, int *raised)
+{
+	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
+	if (h == NULL) return svt_set_error("out of memory");
+	h->Rtype = Rtype; h->owned = 1; h->na_background = na_background;
+	h->nrow = nrow; h->ncol = ncol;
+	if (compose(ResultDest{ result_hip_alloc, result_hip_free, NULL, &h->nnz, &h->col_ptr, &h->row_idx, &h->val }, &h->Rtype) ||
+	    hipStreamSynchronize(0) != hipSuccess) {
+		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
+		svt_release(h);
+		return -1;
+	}
+	int w = 0;
+	Res *r = (Res *) calloc(1, sizeof(*r));
+	if ((flag != NULL && flag->read(&w)) || r == NULL) {
+		svt_release(h);
+		free(r);
+		return r == NULL ? svt_set_error("out of memory") : -1;
+	}
+	r->h = h;
+	*res = r;
+	if (out_Rtype != NULL) *out_Rtype = h->Rtype;
+	*out_nnz = h->nnz;
+	if (raised != NULL) *raised = w;
+	return 0;
+}
 
 static int subset_SVT_begin_impl(const svt_view *x, const int *rows, int64_t nrows_sel, const int *cols, int64_t ncols_sel,
 				 svt_subset_result **res, int64_t *out_nnz)
@@ -4289,24 +4308,13 @@ static int subset_SVT_begin_impl(const svt_view *x, const int *rows, int64_t nro
 	DevBuf dr, dc;
 	if ((rows != NULL && dr.upload(r0.data(), r0.size() * 4)) || (cols != NULL && dc.upload(c0.data(), c0.size() * 4)))
 		return -1;
-	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
-	if (h == NULL) return svt_set_error("out of memory");
-	h->Rtype = A.h->Rtype; h->owned = 1; h->na_background = A.h->na_background;
-	h->nrow = rows != NULL ? nrows_sel : A.h->nrow;
-	h->ncol = cols != NULL ? ncols_sel : A.h->ncol;
-	if (dev_subset_impl(A.h, dr.as<int32_t>(), rows != NULL ? nrows_sel : -1, dc.as<int32_t>(), cols != NULL ? ncols_sel : -1,
-			    subset_hip_alloc, subset_hip_free, NULL, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, NULL) ||
-	    hipStreamSynchronize(0) != hipSuccess) {
-		if (svt_last_error()[0] == '\0') svt_set_error("device error while subsetting");
-		svt_release(h);
-		return -1;
-	}
-	svt_subset_result *r = (svt_subset_result *) calloc(1, sizeof(*r));
-	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
-	r->h = h;
-	*res = r;
-	*out_nnz = h->nnz;
-	return 0;
+	return result_begin("svt_subset_SVT_begin", A.h->Rtype, A.h->na_background, rows != NULL ? nrows_sel : A.h->nrow,
+			    cols != NULL ? ncols_sel : A.h->ncol,
+			    [&](const ResultDest &to, int *) {
+				    return dev_subset_impl(A.h, dr.as<int32_t>(), rows != NULL ? nrows_sel : -1, dc.as<int32_t>(),
+							   cols != NULL ? ncols_sel : -1, to, NULL);
+			    },
+			    NULL, res, NULL, out_nnz, NULL);
 }
 extern "C" int svt_subset_SVT_begin(const svt_view *x, const int *rows, int64_t nrows_sel, const int *cols, int64_t ncols_sel,
 				    svt_subset_result **res, int64_t *out_nnz)
@@ -4372,32 +4380,11 @@ static int arith_begin_impl(const char *who, int kind, int op, const svt_view *x
 	}
 	DevFlag ov;
 	if (ov.init()) return -1;
-	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
-	if (h == NULL) return svt_set_error("out of memory");
-	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
 	ArithCall c = { who, kind, op, A.h, B ? B->h : NULL, s, s_Rtype };
 	c.rule = rule;
-	int rt = 0;
-	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, ov.ptr(), NULL) ||
-	    hipStreamSynchronize(0) != hipSuccess) {
-		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
-		svt_release(h);
-		return -1;
-	}
-	h->Rtype = rt;
-	int raised = 0;
-	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
-	if (ov.read(&raised) || r == NULL) {
-		svt_release(h);
-		free(r);
-		return r == NULL ? svt_set_error("out of memory") : -1;
-	}
-	r->h = h;
-	*res = r;
-	*out_Rtype = rt;
-	*out_nnz = h->nnz;
-	if (ovflow != NULL) *ovflow = raised;
-	return 0;
+	return result_begin(who, 0, 0, A.h->nrow, A.h->ncol,
+			    [&](const ResultDest &to, int *rt) { return c.compose(to, rt, ov.ptr(), NULL); }, &ov, res, out_Rtype, out_nnz,
+			    ovflow);
 }
 extern "C" int svt_Arith_SVT_SVT_begin(const svt_view *x, const svt_view *y, int op, svt_arith_result **res, int *out_Rtype,
 				       int64_t *out_nnz, int *ovflow)
@@ -4521,32 +4508,10 @@ static int sweep_begin_impl(const char *who, int rule, const svt_view *x, int op
 	DevFlag ov;
 	if (dv.upload(stats, (size_t) stats_len * elt_size(stats_Rtype)) || ov.init())
 		return -1;
-	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
-	if (h == NULL) return svt_set_error("out of memory");
-	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
 	SweepCall c = { who, rule, op, A.h, dv.p, stats_Rtype, stats_len, with_rows, stride, len };
-	int rt = 0;
-	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, ov.ptr(), bad_index,
-		      NULL) ||
-	    hipStreamSynchronize(0) != hipSuccess) {
-		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
-		svt_release(h);
-		return -1;
-	}
-	h->Rtype = rt;
-	int raised = 0;
-	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
-	if (ov.read(&raised) || r == NULL) {
-		svt_release(h);
-		free(r);
-		return r == NULL ? svt_set_error("out of memory") : -1;
-	}
-	r->h = h;
-	*res = r;
-	*out_Rtype = rt;
-	*out_nnz = h->nnz;
-	if (ovflow != NULL) *ovflow = raised;
-	return 0;
+	return result_begin(who, 0, 0, A.h->nrow, A.h->ncol,
+			    [&](const ResultDest &to, int *rt) { return c.compose(to, rt, ov.ptr(), bad_index, NULL); }, &ov, res, out_Rtype,
+			    out_nnz, ovflow);
 }
 extern "C" int svt_Arith_SVT_vector_begin(const svt_view *x, int op, const void *stats, int64_t stats_len, int stats_Rtype,
 					  const int *margin, int nmargin, int64_t *bad_index, svt_arith_result **res, int *out_Rtype,
@@ -4654,27 +4619,14 @@ static int subassign_begin_impl(const char *who, const svt_view *x, const int *c
 	    (!leaves.empty() && dl.upload(leaves.data(), leaves.size() * 4)) ||
 	    (!svt_form && dv.upload(vals, (size_t) nvals * elt_size(v_Rtype))))
 		return -1;
-	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
-	if (h == NULL) return svt_set_error("out of memory");
-	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
 	SubassignCall c = { who };
-	int rt = 0;
-	if (c.plan(A.h->nrow, A.h->ncol, dr.as<int32_t>(), whole_rows ? -1 : len[0], dl.as<int32_t>(), nleaves_sel, dv.as<char>(), nvals,
-		   v_Rtype, svt_form ? V->h : NULL, svt_form) ||
-	    c.compose(A.h, subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, NULL) ||
-	    hipStreamSynchronize(0) != hipSuccess) {
-		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
-		svt_release(h);
-		return -1;
-	}
-	h->Rtype = rt;
-	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
-	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
-	r->h = h;
-	*res = r;
-	*out_Rtype = rt;
-	*out_nnz = h->nnz;
-	return 0;
+	return result_begin(who, 0, 0, A.h->nrow, A.h->ncol,
+			    [&](const ResultDest &to, int *rt) {
+				    return c.plan(A.h->nrow, A.h->ncol, dr.as<int32_t>(), whole_rows ? -1 : len[0], dl.as<int32_t>(), nleaves_sel,
+						  dv.as<char>(), nvals, v_Rtype, svt_form ? V->h : NULL, svt_form) ||
+					   c.compose(A.h, to, rt, NULL);
+			    },
+			    NULL, res, out_Rtype, out_nnz, NULL);
 }
 extern "C" int svt_subassign_SVT_vector_begin(const svt_view *x, const int *const *index, const int64_t *index_len, const void *vals,
 					      int64_t nvals, int v_Rtype, svt_arith_result **res, int *out_Rtype, int64_t *out_nnz)
@@ -4804,27 +4756,12 @@ static int subassign_by_cells(const char *who, const svt_view *x, const std::vec
 	DevBuf di, dv;
 	if ((K > 0 && di.upload(cells.data(), (size_t) K * 8)) || dv.upload(vals, (size_t) nvals * elt_size(v_Rtype)))
 		return -1;
-	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
-	if (h == NULL) return svt_set_error("out of memory");
-	h->owned = 1; h->nrow = A.h->nrow; h->ncol = A.h->ncol;
 	LindexCall c = { who };
-	int rt = 0;
-	if (c.plan(A.h->nrow, A.h->ncol, di.p, K, 0, NULL) ||
-	    c.compose(A.h, dv.p, nvals, v_Rtype, subset_hip_alloc, subset_hip_free, NULL, &rt, &h->nnz, &h->col_ptr, &h->row_idx, &h->val,
-		      NULL) ||
-	    hipStreamSynchronize(0) != hipSuccess) {
-		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
-		svt_release(h);
-		return -1;
-	}
-	h->Rtype = rt;
-	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
-	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
-	r->h = h;
-	*res = r;
-	*out_Rtype = rt;
-	*out_nnz = h->nnz;
-	return 0;
+	return result_begin(who, 0, 0, A.h->nrow, A.h->ncol,
+			    [&](const ResultDest &to, int *rt) {
+				    return c.plan(A.h->nrow, A.h->ncol, di.p, K, 0, NULL) || c.compose(A.h, dv.p, nvals, v_Rtype, to, rt, NULL);
+			    },
+			    NULL, res, out_Rtype, out_nnz, NULL);
 }
 // the checks both forms share, before the index is looked at
 static int subassign_by_index_head(const char *who, const svt_view *x, const void *vals, int64_t nvals, int v_Rtype,
@@ -4916,22 +4853,8 @@ static int abind_SVT_begin_impl(const svt_view *const *objs, int nobj, int along
 	AbindCall c = { who };
 	if (c.plan(handles.data(), nobj, inner, along == 1 ? NULL : ext.data(), ans_Rtype))
 		return -1;
-	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
-	if (h == NULL) return svt_set_error("out of memory");
-	h->owned = 1; h->Rtype = ans_Rtype; h->na_background = c.na_background;
-	h->nrow = c.out_nrow; h->ncol = c.a.out_nleaves;
-	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &h->nnz, &h->col_ptr, &h->row_idx, &h->val, NULL) ||
-	    hipStreamSynchronize(0) != hipSuccess) {
-		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
-		svt_release(h);
-		return -1;
-	}
-	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
-	if (r == NULL) { svt_release(h); return svt_set_error("out of memory"); }
-	r->h = h;
-	*res = r;
-	*out_nnz = h->nnz;
-	return 0;
+	return result_begin(who, ans_Rtype, c.na_background, c.out_nrow, c.a.out_nleaves,
+			    [&](const ResultDest &to, int *) { return c.compose(to, NULL); }, NULL, res, NULL, out_nnz, NULL);
 }
 extern "C" int svt_abind_SVT_begin(const svt_view *const *objs, int nobj, int along, int ans_Rtype, svt_arith_result **res,
 				   int64_t *out_nnz)
@@ -5098,31 +5021,9 @@ static int matmul_SVT_SVT_sparse_begin_impl(const svt_view *x, const svt_view *y
 	if (A == NULL || B == NULL) return -1;
 	DevFlag nf;
 	if (nf.init()) return -1;
-	svt_dev_csc *h = (svt_dev_csc *) calloc(1, sizeof(*h));
-	if (h == NULL) return svt_set_error("out of memory");
-	h->owned = 1; h->Rtype = SVT_REALSXP; h->nrow = A->nrow; h->ncol = B->ncol;
 	const SpgemmCall c = { who, A, B };
-	double *val = NULL;
-	if (c.compose(subset_hip_alloc, subset_hip_free, NULL, &h->nnz, &h->col_ptr, &h->row_idx, &val, nf.ptr(), NULL) ||
-	    hipStreamSynchronize(0) != hipSuccess) {
-		if (svt_last_error()[0] == '\0') svt_set_error("%s: device error", who);
-		h->val = val;
-		svt_release(h);
-		return -1;
-	}
-	h->val = val;
-	int raised = 0;
-	svt_arith_result *r = (svt_arith_result *) calloc(1, sizeof(*r));
-	if (nf.read(&raised) || r == NULL) {
-		svt_release(h);
-		free(r);
-		return r == NULL ? svt_set_error("out of memory") : -1;
-	}
-	r->h = h;
-	*res = r;
-	*out_nnz = h->nnz;
-	*not_finite = raised;
-	return 0;
+	return result_begin(who, SVT_REALSXP, 0, A->nrow, B->ncol,
+			    [&](const ResultDest &to, int *) { return c.compose(to, nf.ptr(), NULL); }, &nf, res, NULL, out_nnz, not_finite);
 }
 extern "C" int svt_matmul_SVT_SVT_sparse_begin(const svt_view *x, const svt_view *y, int tr_x, int tr_y, svt_arith_result **res,
 					       int64_t *out_nnz, int *not_finite)

@@ -89,14 +89,9 @@ class DeviceCSC:
     def _sparsify(cls, a, dim, x_Rtype, ans_Rtype, na_background):
         """svt_dev_from_dense on the memory of ``a`` read as the column-major array of extents ``dim``"""
         nrow, nleaves = dim[0], int(np.prod(dim[1:], dtype=np.int64))
-        mem = _TorchBlocks(a.device)
-        nnz = c_int64(0)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(_lib().svt_dev_from_dense(a.data_ptr(), x_Rtype, nrow, nleaves, ans_Rtype, int(bool(na_background)),
-                                         mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz),
-                                         *[ctypes.byref(o) for o in out], _stream()))
-        dtype = torch.float64 if ans_Rtype == REALSXP else torch.int32
-        return cls(nrow, *mem.csc(out, nleaves, int(nnz.value), dtype), logical=ans_Rtype == LGLSXP)
+        return _composed(lambda *r: _lib().svt_dev_from_dense(a.data_ptr(), x_Rtype, nrow, nleaves, ans_Rtype,
+                                                              int(bool(na_background)), *r),
+                         a.device, nrow, nleaves, ans_Rtype)
 
     def _dim(self, dim):
         dim = (self.nrow, self.ncol) if dim is None else tuple(int(d) for d in dim)
@@ -195,16 +190,10 @@ class DeviceCSC:
         it.  Every array the composition needs is a torch allocation on the current stream."""
         dev = self.val.device
         sub = [None if v is None else _subscript(v, dev) for v in (rows, cols)]
-        mem = _TorchBlocks(dev)
-        nnz = c_int64(0)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(_lib().svt_dev_subset(self.handle, *[a for v in sub for a in ((None, -1) if v is None else
-                                                                               (v.data_ptr(), v.numel()))],
-                                     mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz),
-                                     *[ctypes.byref(o) for o in out], _stream()))
+        idx = [a for v in sub for a in ((None, -1) if v is None else (v.data_ptr(), v.numel()))]
         nrow = self.nrow if sub[0] is None else sub[0].numel()
         ncol = self.ncol if sub[1] is None else sub[1].numel()
-        return DeviceCSC(nrow, *mem.csc(out, ncol, int(nnz.value), self.val.dtype), logical=self.Rtype == LGLSXP)
+        return _composed(lambda *a: _lib().svt_dev_subset(self.handle, *idx, *a), dev, nrow, ncol, self.Rtype)
 
     def subassign(self, rows, leaves, value, logical: bool = False) -> "DeviceCSC":
         """``x[rows, leaves] <- value`` on the device (include/svt_hip.h, svt_dev_subassign_vector / _svt): ``rows`` /
@@ -223,13 +212,7 @@ class DeviceCSC:
             vals, v_Rtype = _assign_values(value, dev, logical)
             call = lambda *a: _lib().svt_dev_subassign_vector(self.handle, *idx, vals.data_ptr(), vals.numel(),  # noqa: E731
                                                               v_Rtype, *a)
-        mem = _TorchBlocks(dev)
-        rt, nnz = ctypes.c_int(0), c_int64(0)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt), ctypes.byref(nnz), *[ctypes.byref(o) for o in out],
-                    _stream()))
-        dtype = torch.float64 if rt.value == REALSXP else torch.int32
-        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype), logical=rt.value == LGLSXP)
+        return self._result(call)
 
     def _cell_index(self, index, dim, matrix):
         """The arguments (pointer, K[, ndim, dim]) of an L-index (int64[K], 0-based, LINDEX_NA for NA) or an M-index
@@ -291,13 +274,7 @@ class DeviceCSC:
         keep, args = self._cell_index(index, dim, matrix)
         vals, v_Rtype = _assign_values(value, self.val.device, logical)
         fn = _lib().svt_dev_subassign_mindex if matrix else _lib().svt_dev_subassign_lindex
-        mem = _TorchBlocks(self.val.device)
-        rt, nnz = ctypes.c_int(0), c_int64(0)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(fn(self.handle, *args, vals.data_ptr(), vals.numel(), v_Rtype, mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt),
-                  ctypes.byref(nnz), *[ctypes.byref(o) for o in out], _stream()))
-        dtype = torch.float64 if rt.value == REALSXP else torch.int32
-        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype), logical=rt.value == LGLSXP)
+        return self._result(lambda *a: fn(self.handle, *args, vals.data_ptr(), vals.numel(), v_Rtype, *a))
 
     def subassign_lindex(self, L, value, logical: bool = False) -> "DeviceCSC":
         """``x[L] <- value`` by a linear index on the device (svt_dev_subassign_lindex): ``L`` as in subset_lindex, no
@@ -313,21 +290,10 @@ class DeviceCSC:
         subassign_lindex."""
         return self._subassign_cells(M, value, dim, logical, True)
 
-    def _arith_result(self, call):
-        """The new DeviceCSC that ``call(alloc, release, ctx, out_Rtype, nnz, col_ptr, row_idx, val, ovflow, stream)`` --
-        one of the two compositions svt_dev_arith_merge / svt_dev_arith_map -- leaves in torch allocations.  Its
-        ``ovflow`` attribute is the device word of the overflow flag (int32 tensor; nonzero once the fill has run: "NAs
-        produced by integer overflow"), left on the device so that the call stays asynchronous after its count."""
-        mem = _TorchBlocks(self.val.device)
-        ovflow = torch.zeros(1, dtype=torch.int32, device=self.val.device)
-        rt, nnz = ctypes.c_int(0), c_int64(0)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt), ctypes.byref(nnz), *[ctypes.byref(o) for o in out],
-                    ovflow.data_ptr(), _stream()))
-        dtype = torch.float64 if rt.value == REALSXP else torch.int32
-        R = DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype))
-        R.ovflow = ovflow
-        return R
+    def _result(self, call, rtype=None, ovflow=False) -> "DeviceCSC":
+        """_composed() for a result of the operand's extents: ``rtype`` LGLSXP for Compare, Logic and is*(), None where
+        the library reports the type; ``ovflow`` for Arith, Math and the Arith sweep."""
+        return _composed(call, self.val.device, self.nrow, self.ncol, rtype, ovflow)
 
     def arith(self, op: str, other):
         """``self op other`` on the device (include/svt_hip.h, svt_dev_arith_merge / svt_dev_arith_map): ``other`` a
@@ -338,14 +304,15 @@ class DeviceCSC:
         if op not in ARITH_OPCODES:
             raise SparseArrayError(f"unknown Arith operation {op!r}")
         if isinstance(other, DeviceCSC):
-            return self._arith_result(lambda *a: _lib().svt_dev_arith_merge(self.handle, other.handle, ARITH_OPCODES[op], *a))
+            return self._result(lambda *a: _lib().svt_dev_arith_merge(self.handle, other.handle, ARITH_OPCODES[op], *a),
+                                ovflow=True)
         s_Rtype = INTSXP if isinstance(other, (int, np.integer)) and not isinstance(other, (bool, np.bool_)) else REALSXP
-        return self._arith_result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_SCALAR, ARITH_OPCODES[op],
-                                                                      float(other), s_Rtype, *a))
+        return self._result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_SCALAR, ARITH_OPCODES[op], float(other),
+                                                                s_Rtype, *a), ovflow=True)
 
     def neg(self) -> "DeviceCSC":
         """``-self`` on the device; the type is kept."""
-        return self._arith_result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_NEG, 0, 0.0, 0, *a))
+        return self._result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_NEG, 0, 0.0, 0, *a), ovflow=True)
 
     def math(self, op: str) -> "DeviceCSC":
         """One of abs sign sqrt floor ceiling trunc log1p expm1 on a double operand; the other zero-preserving members
@@ -353,17 +320,8 @@ class DeviceCSC:
         from .api import MATH_OPCODES
         if op not in MATH_OPCODES:
             raise SparseArrayError(f"unknown Math operation {op!r}")
-        return self._arith_result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_MATH, MATH_OPCODES[op], 0.0, 0, *a))
-
-    def _logical_result(self, call):
-        """The new logical DeviceCSC that ``call(alloc, release, ctx, nnz, col_ptr, row_idx, val, stream)`` -- one of
-        svt_dev_compare_merge / svt_dev_compare_map / svt_dev_logic_merge -- leaves in torch allocations; the call
-        stays asynchronous after its count."""
-        mem = _TorchBlocks(self.val.device)
-        nnz = c_int64(0)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz), *[ctypes.byref(o) for o in out], _stream()))
-        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), torch.int32), logical=True)
+        return self._result(lambda *a: _lib().svt_dev_arith_map(self.handle, ARITH_MATH, MATH_OPCODES[op], 0.0, 0, *a),
+                            ovflow=True)
 
     def compare(self, op: str, other) -> "DeviceCSC":
         """``self op other`` on the device (include/svt_hip.h, svt_dev_compare_merge / svt_dev_compare_map): ``other`` a
@@ -374,33 +332,22 @@ class DeviceCSC:
         if op not in COMPARE_OPCODES:
             raise SparseArrayError(f"unknown Compare operation {op!r}")
         if isinstance(other, DeviceCSC):
-            return self._logical_result(lambda *a: _lib().svt_dev_compare_merge(self.handle, other.handle, COMPARE_OPCODES[op], *a))
+            return self._result(lambda *a: _lib().svt_dev_compare_merge(self.handle, other.handle, COMPARE_OPCODES[op], *a),
+                                LGLSXP)
         s_Rtype = (LGLSXP if isinstance(other, (bool, np.bool_)) else
                    INTSXP if isinstance(other, (int, np.integer)) else REALSXP)
-        return self._logical_result(lambda *a: _lib().svt_dev_compare_map(self.handle, COMPARE_OPCODES[op], float(other),
-                                                                          s_Rtype, *a))
-
-    def _typed_result(self, call):
-        """The new DeviceCSC that ``call(alloc, release, ctx, out_Rtype, nnz, col_ptr, row_idx, val, stream)`` -- one of
-        svt_dev_pminmax_merge / svt_dev_pminmax_map -- leaves in torch allocations, logical, integer or double as the
-        library says; the call stays asynchronous after its count."""
-        mem = _TorchBlocks(self.val.device)
-        rt, nnz = ctypes.c_int(0), c_int64(0)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(call(mem.alloc_fn, mem.free_fn, None, ctypes.byref(rt), ctypes.byref(nnz), *[ctypes.byref(o) for o in out],
-                    _stream()))
-        dtype = torch.float64 if rt.value == REALSXP else torch.int32
-        return DeviceCSC(self.nrow, *mem.csc(out, self.ncol, int(nnz.value), dtype), logical=rt.value == LGLSXP)
+        return self._result(lambda *a: _lib().svt_dev_compare_map(self.handle, COMPARE_OPCODES[op], float(other), s_Rtype, *a),
+                            LGLSXP)
 
     def _pminmax(self, name: str, other, na_rm) -> "DeviceCSC":
         from .api import PMINMAX_NA_RM, PMINMAX_OPCODES
         op = PMINMAX_OPCODES[name] | (PMINMAX_NA_RM if na_rm else 0)
         if isinstance(other, DeviceCSC):
-            return self._typed_result(lambda *a: _lib().svt_dev_pminmax_merge(self.handle, other.handle, op, *a))
+            return self._result(lambda *a: _lib().svt_dev_pminmax_merge(self.handle, other.handle, op, *a))
         s_Rtype = (LGLSXP if isinstance(other, (bool, np.bool_)) else
                    INTSXP if isinstance(other, (int, np.integer)) else REALSXP)
         try:
-            return self._typed_result(lambda *a: _lib().svt_dev_pminmax_map(self.handle, op, float(other), s_Rtype, *a))
+            return self._result(lambda *a: _lib().svt_dev_pminmax_map(self.handle, op, float(other), s_Rtype, *a))
         except SparseArrayError as e:
             if "result wouldn't be sparse" not in str(e):
                 raise
@@ -419,7 +366,7 @@ class DeviceCSC:
 
     def _isfun(self, name: str) -> "DeviceCSC":
         from .api import ISFUN_OPCODES
-        return self._logical_result(lambda *a: _lib().svt_dev_isfun_map(self.handle, ISFUN_OPCODES[name], *a))
+        return self._result(lambda *a: _lib().svt_dev_isfun_map(self.handle, ISFUN_OPCODES[name], *a), LGLSXP)
 
     def is_na(self) -> "DeviceCSC":
         """``is.na(self)`` on the device (svt_dev_isfun_map): a logical DeviceCSC that stores 1 where an entry is NA or
@@ -467,14 +414,14 @@ class DeviceCSC:
         geometry = (vals.data_ptr(), s_Rtype, vals.numel(), with_rows, stride, length)
         try:
             if pminmax:
-                return self._typed_result(lambda *a: _lib().svt_dev_pminmax_sweep(
+                return self._result(lambda *a: _lib().svt_dev_pminmax_sweep(
                     self.handle, PMINMAX_OPCODES[op] | (PMINMAX_NA_RM if na_rm else 0), *geometry, *a[:-1],
                     ctypes.byref(bad), a[-1]))
             if compare:
-                return self._logical_result(lambda *a: _lib().svt_dev_compare_sweep(
-                    self.handle, COMPARE_OPCODES[op], *geometry, *a[:-1], ctypes.byref(bad), a[-1]))
-            return self._arith_result(lambda *a: _lib().svt_dev_arith_sweep(
-                self.handle, ARITH_OPCODES[op], *geometry, *a[:-1], ctypes.byref(bad), a[-1]))
+                return self._result(lambda *a: _lib().svt_dev_compare_sweep(
+                    self.handle, COMPARE_OPCODES[op], *geometry, *a[:-1], ctypes.byref(bad), a[-1]), LGLSXP)
+            return self._result(lambda *a: _lib().svt_dev_arith_sweep(
+                self.handle, ARITH_OPCODES[op], *geometry, *a[:-1], ctypes.byref(bad), a[-1]), ovflow=True)
         except SparseArrayError as e:
             if bad.value < 0:
                 raise
@@ -489,7 +436,7 @@ class DeviceCSC:
             raise SparseArrayError(f"unknown Logic operation {op!r}")
         if not isinstance(other, DeviceCSC):
             raise SparseArrayError("logic() takes two DeviceCSC operands")
-        return self._logical_result(lambda *a: _lib().svt_dev_logic_merge(self.handle, other.handle, LOGIC_OPCODES[op], *a))
+        return self._result(lambda *a: _lib().svt_dev_logic_merge(self.handle, other.handle, LOGIC_OPCODES[op], *a), LGLSXP)
 
     def matmul_sparse(self, other: "DeviceCSC"):
         """``self %*% other`` with a resident sparse result: (DeviceCSC of type double, not_finite), see
@@ -530,6 +477,48 @@ class _TorchBlocks:
         live, self.live = self.live, {}
         return (live[out[0].value].view(torch.int64)[:ncol + 1], live[out[1].value].view(torch.int32)[:nnz],
                 live[out[2].value].view(dtype)[:nnz])
+
+
+def _composed(call, device, nrow, ncol=None, rtype=None, ovflow=False) -> DeviceCSC:
+    """The new DeviceCSC that a composition of the library -- count, allocate, fill over the caller's allocator
+    (include/svt_hip.h, svt_dev_subset) -- leaves in torch allocations on the current stream.  ``call`` is given the
+    arguments from ``alloc`` on, in the header's order: alloc, release, ctx, [out_nrow, out_nleaves: ``ncol`` None, the
+    library reports the extents (abind),] [out_Rtype: ``rtype`` None, the library reports the type,] out_nnz,
+    out_col_ptr, out_row_idx, out_val, [the overflow word: ``ovflow``,] stream.  With ``ovflow`` the result's ``ovflow``
+    attribute is that device word (int32 tensor; nonzero once the fill has run: "NAs produced by integer overflow"),
+    left on the device so that the call stays asynchronous after its count."""
+    mem = _TorchBlocks(device)
+    dims = [] if ncol is not None else [c_int64(0), c_int64(0)]
+    rt = [] if rtype is not None else [ctypes.c_int(0)]
+    nnz, out = c_int64(0), [c_void_p(0), c_void_p(0), c_void_p(0)]
+    word = [torch.zeros(1, dtype=torch.int32, device=device)] if ovflow else []
+    _check(call(mem.alloc_fn, mem.free_fn, None, *[ctypes.byref(c) for c in dims + rt + [nnz] + out],
+                *[w.data_ptr() for w in word], _stream()))
+    if dims:
+        nrow, ncol = int(dims[0].value), int(dims[1].value)
+    if rt:
+        rtype = rt[0].value
+    dtype = torch.float64 if rtype == REALSXP else torch.int32
+    R = DeviceCSC(nrow, *mem.csc(out, ncol, int(nnz.value), dtype), logical=rtype == LGLSXP)
+    if word:
+        R.ovflow = word[0]
+    return R
+
+
+def _two_calls(device, nrow, ncol, dtype, logical, count, fill, need=0, ws=None, col_ptr=None) -> DeviceCSC:
+    """The two-call form of the same protocol, every array a tensor made here: the workspace (``ws``, or ``need`` bytes)
+    and col_ptr (``col_ptr``, or int64[ncol + 1]), ``count(col_ptr, out_nnz, ws, ws_bytes, stream)``, row_idx and val for
+    the nonzeros it found, ``fill(col_ptr, nnz, row_idx, val, ws, ws_bytes, stream)``."""
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda
+    cp = torch.empty(ncol + 1, dtype=torch.int64, device=device) if col_ptr is None else col_ptr
+    nnz = c_int64(0)
+    _check(count(cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(), _stream()))
+    ri = torch.empty(nnz.value, dtype=torch.int32, device=device)
+    vv = torch.empty(nnz.value, dtype=dtype, device=device)
+    _check(fill(cp.data_ptr(), nnz.value, ri.data_ptr(), vv.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return DeviceCSC(nrow, cp, ri, vv, logical=logical)
 
 
 def _subscript(v, device) -> torch.Tensor:
@@ -579,13 +568,9 @@ def subassign_place(nrow, ncol, rows, leaves, value, logical=False, ws=None, tab
     dev = value.val.device if isinstance(value, DeviceCSC) else torch.device("cuda")
     sub = [None if v is None else _subscript(v, dev) for v in (rows, leaves)]
     idx = [a for v in sub for a in ((None, -1) if v is None else (v.data_ptr(), v.numel()))]
-    if ws is None:
-        ws = torch.empty(lib.svt_dev_subassign_place_ws_bytes(nrow, ncol), dtype=torch.uint8, device=dev)
     if tables is None:
         tables = [None if s is None else torch.empty(n, dtype=torch.uint8, device=dev) for s, n in zip(sub, (nrow, ncol))]
-    cp = torch.empty(ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
     tab = [None if t is None else t.data_ptr() for t in tables]
-    nnz = c_int64(0)
     if isinstance(value, DeviceCSC):
         what, dtype, is_lgl = (value.handle,), value.val.dtype, value.Rtype == LGLSXP
         count, fill = lib.svt_dev_subassign_place_svt_count, lib.svt_dev_subassign_place_svt_fill
@@ -593,31 +578,27 @@ def subassign_place(nrow, ncol, rows, leaves, value, logical=False, ws=None, tab
         vals, v_Rtype = _assign_values(value, dev, logical)
         what, dtype, is_lgl = (vals.data_ptr(), vals.numel(), v_Rtype), vals.dtype, v_Rtype == LGLSXP
         count, fill = lib.svt_dev_subassign_place_vector_count, lib.svt_dev_subassign_place_vector_fill
-    _check(count(nrow, ncol, *idx, *what, cp.data_ptr(), *tab, ctypes.byref(nnz), ws.data_ptr(), ws.numel(), _stream()))
-    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
-    vv = torch.empty(nnz.value, dtype=dtype, device=dev)
-    _check(fill(nrow, ncol, *idx, *what, cp.data_ptr(), nnz.value, ri.data_ptr(), vv.data_ptr(), ws.data_ptr(), ws.numel(),
-                _stream()))
-    return DeviceCSC(nrow, cp, ri, vv, logical=is_lgl), tables[0], tables[1]
+    Y = _two_calls(dev, nrow, ncol, dtype, is_lgl,
+                   lambda cp, nnz, *w: count(nrow, ncol, *idx, *what, cp, *tab, nnz, *w),
+                   lambda cp, *a: fill(nrow, ncol, *idx, *what, cp, *a),
+                   lib.svt_dev_subassign_place_ws_bytes(nrow, ncol), ws, col_ptr)
+    return Y, tables[0], tables[1]
 
 
 def assign_merge(x: DeviceCSC, y: DeviceCSC, cover_row=None, cover_leaf=None, ws=None, col_ptr=None) -> DeviceCSC:
     """The assign merge alone (svt_dev_assign_merge_count, then _fill): x with the placed operand ``y`` written over
     it under the two cover tables (uint8 tensors; None: the whole axis)."""
-    lib, dev = _lib(), x.val.device
-    if ws is None:
-        ws = torch.empty(lib.svt_dev_arith_merge_ws_bytes(x.ncol, x.nnz, y.nnz), dtype=torch.uint8, device=dev)
-    cp = torch.empty(x.ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
     tab = [None if t is None else t.data_ptr() for t in (cover_row, cover_leaf)]
-    nnz = c_int64(0)
-    _check(lib.svt_dev_assign_merge_count(x.handle, y.handle, *tab, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
-                                          _stream()))
-    double = REALSXP in (x.Rtype, y.Rtype)
-    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
-    vv = torch.empty(nnz.value, dtype=torch.float64 if double else torch.int32, device=dev)
-    _check(lib.svt_dev_assign_merge_fill(x.handle, y.handle, *tab, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
-                                         ws.numel(), _stream()))
-    return DeviceCSC(x.nrow, cp, ri, vv, logical=x.Rtype == LGLSXP and y.Rtype == LGLSXP)
+    return _merge_two_calls(x, y, _lib().svt_dev_assign_merge_count, _lib().svt_dev_assign_merge_fill, tab, ws, col_ptr)
+
+
+def _merge_two_calls(x, y, count, fill, tab, ws, col_ptr) -> DeviceCSC:
+    """_two_calls() for a merge of the placed operand ``y`` over ``x``: the result has the wider type of the two"""
+    return _two_calls(x.val.device, x.nrow, x.ncol, torch.float64 if REALSXP in (x.Rtype, y.Rtype) else torch.int32,
+                      x.Rtype == LGLSXP and y.Rtype == LGLSXP,
+                      lambda *a: count(x.handle, y.handle, *tab, *a),
+                      lambda cp, nnz, *a: fill(x.handle, y.handle, *tab, cp, *a),
+                      _lib().svt_dev_arith_merge_ws_bytes(x.ncol, x.nnz, y.nnz), ws, col_ptr)
 
 
 # the NA of an L-index (include/svt_hip.h, svt_dev_subset_lindex)
@@ -645,35 +626,18 @@ def lindex_place(x: DeviceCSC, index, value, dim=None, matrix=False, logical=Fal
     keep, args = x._cell_index(index, dim, matrix)
     args = args if matrix else args + (0, None)
     vals, v_Rtype = _assign_values(value, dev, logical)
-    if ws is None:
-        ws = torch.empty(lib.svt_dev_subassign_place_lindex_ws_bytes(args[1], x.ncol), dtype=torch.uint8, device=dev)
-    cp = torch.empty(x.ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
-    what = (x.nrow, x.ncol, *args, vals.data_ptr(), vals.numel(), v_Rtype, cp.data_ptr())
-    nnz = c_int64(0)
-    _check(lib.svt_dev_subassign_place_lindex_count(*what, ctypes.byref(nnz), ws.data_ptr(), ws.numel(), _stream()))
-    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
-    vv = torch.empty(nnz.value, dtype=vals.dtype, device=dev)
-    _check(lib.svt_dev_subassign_place_lindex_fill(*what, nnz.value, ri.data_ptr(), vv.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   _stream()))
-    return DeviceCSC(x.nrow, cp, ri, vv, logical=v_Rtype == LGLSXP)
+    what = (x.nrow, x.ncol, *args, vals.data_ptr(), vals.numel(), v_Rtype)
+    return _two_calls(dev, x.nrow, x.ncol, vals.dtype, v_Rtype == LGLSXP,
+                      lambda *a: lib.svt_dev_subassign_place_lindex_count(*what, *a),
+                      lambda *a: lib.svt_dev_subassign_place_lindex_fill(*what, *a),
+                      lib.svt_dev_subassign_place_lindex_ws_bytes(args[1], x.ncol), ws, col_ptr)
 
 
 def assign_cells_merge(x: DeviceCSC, y: DeviceCSC, ws=None, col_ptr=None) -> DeviceCSC:
     """The merge under the rule of the subassignment by cells alone (svt_dev_assign_cells_merge_count, then _fill): x
     with the placed operand ``y`` written over it, a zero of ``y`` deleting."""
-    lib, dev = _lib(), x.val.device
-    if ws is None:
-        ws = torch.empty(lib.svt_dev_arith_merge_ws_bytes(x.ncol, x.nnz, y.nnz), dtype=torch.uint8, device=dev)
-    cp = torch.empty(x.ncol + 1, dtype=torch.int64, device=dev) if col_ptr is None else col_ptr
-    nnz = c_int64(0)
-    _check(lib.svt_dev_assign_cells_merge_count(x.handle, y.handle, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
-                                                _stream()))
-    double = REALSXP in (x.Rtype, y.Rtype)
-    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
-    vv = torch.empty(nnz.value, dtype=torch.float64 if double else torch.int32, device=dev)
-    _check(lib.svt_dev_assign_cells_merge_fill(x.handle, y.handle, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), _stream()))
-    return DeviceCSC(x.nrow, cp, ri, vv, logical=x.Rtype == LGLSXP and y.Rtype == LGLSXP)
+    lib = _lib()
+    return _merge_two_calls(x, y, lib.svt_dev_assign_cells_merge_count, lib.svt_dev_assign_cells_merge_fill, (), ws, col_ptr)
 
 
 # kinds of svt_dev_arith_map / svt_dev_arith_out_Rtype (include/svt_hip.h)
@@ -721,23 +685,15 @@ def _subset_two_calls(A: DeviceCSC, idx, ws, rows: bool) -> DeviceCSC:
     lib, dev = _lib(), A.val.device
     idx = _subscript(idx, dev)
     n = idx.numel()
-    if ws is None:
-        nb = lib.svt_dev_subset_rows_ws_bytes(A.nrow, A.ncol, A.nnz) if rows else lib.svt_dev_subset_cols_ws_bytes(n)
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda
-    cp = torch.empty((A.ncol if rows else n) + 1, dtype=torch.int64, device=dev)
-    nnz = c_int64(0)
-    count = lib.svt_dev_subset_rows_count if rows else lib.svt_dev_subset_cols_count
-    _check(count(A.handle, idx.data_ptr(), n, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(), _stream()))
-    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
-    vv = torch.empty(nnz.value, dtype=A.val.dtype, device=dev)
     if rows:
-        _check(lib.svt_dev_subset_rows_fill(A.handle, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), _stream()))
-    else:
-        _check(lib.svt_dev_subset_cols_fill(A.handle, idx.data_ptr(), n, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(),
-                                            _stream()))
-    return DeviceCSC(n if rows else A.nrow, cp, ri, vv, logical=A.Rtype == LGLSXP)
+        return _two_calls(dev, n, A.ncol, A.val.dtype, A.Rtype == LGLSXP,
+                          lambda *a: lib.svt_dev_subset_rows_count(A.handle, idx.data_ptr(), n, *a),
+                          lambda cp, nnz, *a: lib.svt_dev_subset_rows_fill(A.handle, cp, *a),
+                          lib.svt_dev_subset_rows_ws_bytes(A.nrow, A.ncol, A.nnz), ws)
+    return _two_calls(dev, A.nrow, n, A.val.dtype, A.Rtype == LGLSXP,
+                      lambda *a: lib.svt_dev_subset_cols_count(A.handle, idx.data_ptr(), n, *a),
+                      lambda cp, nnz, ri, vv, *w: lib.svt_dev_subset_cols_fill(A.handle, idx.data_ptr(), n, cp, ri, vv, w[-1]),
+                      lib.svt_dev_subset_cols_ws_bytes(n), ws)
 
 
 def subset_cols(A: DeviceCSC, cols, ws=None) -> DeviceCSC:
@@ -805,14 +761,8 @@ def abind(objects, along=1, dim=None):
     (logical only when every object is logical) and the values widen on the device.  Returns (DeviceCSC, its dim); every
     array is a torch allocation on the current stream."""
     objects, handles, inner, ext, ans_Rtype, new_dim = _abind_operands(objects, int(along), dim)
-    mem = _TorchBlocks(objects[0].val.device)
-    nrow, nleaves, nnz = c_int64(0), c_int64(0), c_int64(0)
-    out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-    _check(_lib().svt_dev_abind(handles, len(objects), inner, ext, ans_Rtype, mem.alloc_fn, mem.free_fn, None,
-                                ctypes.byref(nrow), ctypes.byref(nleaves), ctypes.byref(nnz),
-                                *[ctypes.byref(o) for o in out], _stream()))
-    dtype = torch.float64 if ans_Rtype == REALSXP else torch.int32
-    R = DeviceCSC(int(nrow.value), *mem.csc(out, int(nleaves.value), int(nnz.value), dtype), logical=ans_Rtype == LGLSXP)
+    R = _composed(lambda *a: _lib().svt_dev_abind(handles, len(objects), inner, ext, ans_Rtype, *a), objects[0].val.device,
+                  None, None, ans_Rtype)
     return R, new_dim
 
 
@@ -1135,22 +1085,12 @@ def matmul_csc_csc_sparse(A: DeviceCSC, B: DeviceCSC, ws=None):
         raise SparseArrayError("matmul_csc_csc_sparse() takes two DeviceCSC operands")
     lib, dev = _lib(), A.val.device
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    nnz = c_int64(0)
     if ws is None:
-        mem = _TorchBlocks(dev)
-        out = [c_void_p(0), c_void_p(0), c_void_p(0)]
-        _check(lib.svt_dev_spgemm(A.handle, B.handle, mem.alloc_fn, mem.free_fn, None, ctypes.byref(nnz),
-                                  *[ctypes.byref(o) for o in out], flag.data_ptr(), _stream()))
-        return DeviceCSC(A.nrow, *mem.csc(out, B.ncol, int(nnz.value), torch.float64)), flag
-    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda
-    cp = torch.empty(B.ncol + 1, dtype=torch.int64, device=dev)
-    _check(lib.svt_dev_spgemm_count(A.handle, B.handle, cp.data_ptr(), ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
-                                    flag.data_ptr(), _stream()))
-    ri = torch.empty(nnz.value, dtype=torch.int32, device=dev)
-    vv = torch.empty(nnz.value, dtype=torch.float64, device=dev)
-    _check(lib.svt_dev_spgemm_fill(A.handle, B.handle, cp.data_ptr(), ri.data_ptr(), vv.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   _stream()))
-    return DeviceCSC(A.nrow, cp, ri, vv), flag
+        return _composed(lambda *a: lib.svt_dev_spgemm(A.handle, B.handle, *a[:-1], flag.data_ptr(), a[-1]), dev, A.nrow, B.ncol,
+                         REALSXP), flag
+    return _two_calls(dev, A.nrow, B.ncol, torch.float64, False,
+                      lambda *a: lib.svt_dev_spgemm_count(A.handle, B.handle, *a[:-1], flag.data_ptr(), a[-1]),
+                      lambda cp, nnz, *a: lib.svt_dev_spgemm_fill(A.handle, B.handle, cp, *a), ws=ws), flag
 
 
 def crossprod_csc_csc_sparse(X: DeviceCSC, Y: DeviceCSC = None):
