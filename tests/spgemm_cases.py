@@ -221,6 +221,10 @@ RANDOM_SHAPES = 20
 
 @functools.lru_cache(maxsize=None)
 def device_cases(P):
+    """The cases around the panel height P.  Their extents: at most 30 pairs in a column of B, leaves of A below 600
+    entries, ``nnz(A) // ncol(A)`` below 1000, integers below 1000 in magnitude, at most 3 P + 50 rows.  The branches of
+    the kernels past those extents (a second batch of 64 pairs, runs of 64 and more, split leaves, the second trip of
+    the value scan, operands past 1023 panels, integers near 2^31) are run by the cases of tests/spgemm_branch_cases.py."""
     cases = {}
     for nrow, tag in ((P - 1, "P-1"), (P, "P"), (P + 1, "P+1"), (2 * P + 3, "2P+3")):
         cases[f"nrow_{tag}"] = _boundary(P, nrow, 100 + nrow % 7)

@@ -1,8 +1,10 @@
 """The sparse x sparse products with a sparse result on the GPU (kernels_spgemm.hip; include/svt_hip.h, svt_dev_spgemm_*
 and svt_matmul_SVT_SVT_sparse_begin): the cases of tests/spgemm_cases.py, built around the panel height the library
 answers, through the count and fill calls with the test's own buffers, through the composition and through the host
-entry points.  The expectation and the way values are compared are stated in tests/spgemm_cases.py.  No operand holds
-more than a few panels of rows."""
+entry points.  The expectation and the way values are compared are stated in tests/spgemm_cases.py.  No operand here
+holds more than a few panels of rows, 30 entries in a column of B or 600 in a leaf of A: the branches past those extents
+(metadata batches, long runs, split leaves, the scan's second trip, very tall operands, integers near 2^31) are run by
+tests/test_zzzzzzzzzz_spgemm_branches_hip.py on the cases of tests/spgemm_branch_cases.py."""
 import ctypes
 
 import numpy as np
@@ -96,15 +98,14 @@ def _same_bits(a, b):
     return all(np.array_equal(x, y) for x, y in zip(a[:2], b[:2])) and np.array_equal(ac.sc.bits(a[2]), ac.sc.bits(b[2]))
 
 
-@pytest.mark.parametrize("name", gc.DEVICE_NAMES)
-def test_case_through_count_and_fill_and_the_compositions(panel, name):
+def through_the_whole_route(opA, opB, want, name):
     """count's out_col_ptr, nnz and flag, then the filled arrays, every guard word intact, on a workspace of 0xA5; the
     same arrays from svt_dev_spgemm (DeviceCSC.matmul_sparse), from a second run, and from a workspace poisoned
-    differently"""
+    differently.  ``opA``, ``opB``: operands with ``.csc`` and ``.shape``; ``want``: an expectation with ``.csc``,
+    ``.csc_cls`` and ``.not_finite``.  Returns the Raw run and the composition's arrays.  (Shared with
+    tests/test_zzzzzzzzzz_spgemm_branches_hip.py.)"""
     from sparsearray_amd.device import matmul_csc_csc_sparse
-    c = gc.device_cases(panel)[name]
-    want = c.want
-    A, B = _device(c.A), _device(c.B)
+    A, B = _device(opA), _device(opB)
     r = Raw(A, B)
     assert r.count() == 0
     assert r.nnz.value == want.csc[1].size and np.array_equal(r.cp.body(), want.csc[0]), f"{name}: count"
@@ -115,7 +116,7 @@ def test_case_through_count_and_fill_and_the_compositions(panel, name):
     gc.expected_mask_check(r.arrays(), want, name)
     R, flag = A.matmul_sparse(B)
     got = _arrays(R)
-    assert R.nrow == c.A.shape[0] and R.ncol == c.B.shape[1] and R.val.dtype == torch.float64
+    assert R.nrow == opA.shape[0] and R.ncol == opB.shape[1] and R.val.dtype == torch.float64
     assert int(flag.item()) == int(want.not_finite)
     gc.expected_mask_check(got, want, f"{name}, composition")
     assert _same_bits(got, r.arrays()), f"{name}: the composition and the two calls differ"
@@ -126,6 +127,14 @@ def test_case_through_count_and_fill_and_the_compositions(panel, name):
     # the form with the caller's workspace
     ws = torch.full((r.nb,), 0x5A, dtype=torch.uint8, device="cuda")
     assert _same_bits(_arrays(matmul_csc_csc_sparse(A, B, ws=ws)[0]), got)
+    return r, got
+
+
+@pytest.mark.parametrize("name", gc.DEVICE_NAMES)
+def test_case_through_count_and_fill_and_the_compositions(panel, name):
+    """every case of spgemm_cases.device_cases through ``through_the_whole_route``"""
+    c = gc.device_cases(panel)[name]
+    r, got = through_the_whole_route(c.A, c.B, c.want, name)
     if name == "100000_empty_columns":
         empty = ~c.B.stored.any(axis=0)
         assert np.all(np.diff(got[0])[empty] == 0) and empty.sum() == 99_998
