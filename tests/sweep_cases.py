@@ -8,9 +8,10 @@ is broadcast along the margin with numpy (``index_of``: np.unravel_index of ever
 margin coordinates) and the operator is applied element-wise by the rules of tests/arith_cases.py (``_int_arith``, the
 double rules) and tests/compare_cases.py (``compare_values``).  A position is stored in the result exactly when it is
 stored in the operand and the result there is not ``== 0``.  Values are compared as bits and the stored mask exactly,
-under the classes of arith_cases (EXACT, NAN_SIGN, ANY_NAN).  ``^`` is not expected here: its yardstick is the
-correctly rounded power, and the sweep calls the very device function of the scalar map, against which it is compared
-bit for bit instead.
+under the classes of arith_cases (EXACT, NAN_SIGN, ANY_NAN).  The hand-built cases do not expect ``^`` here: its
+yardstick is the correctly rounded power, and the sweep calls the very device function of the scalar map, against which
+they compare it bit for bit instead.  ``element_results`` states it all the same, in the class ULPS, for the seeded
+random cases of tests/random_cases.py.
 
 Every vector built here holds a DISTINCT value at every index, so an element read from a wrong index changes bits.
 """
@@ -54,8 +55,8 @@ def stats_length(dim, margin):
 
 
 def element_results(op, val, s, s_type):
-    """x op s element-wise on 1-D arrays: (values, cls, kept, type of the result, overflow flag)"""
-    assert op != "^"
+    """x op s element-wise on 1-D arrays: (values, cls, kept, type of the result, overflow flag); ``^`` gives the
+    correctly rounded power in the class ULPS of arith_cases (the seeded random cases hold it to MAX_ULPS["^"])"""
     x_type = "double" if val.dtype == np.float64 else "integer"
     if op in cc.COMPARE_OPS:
         v, cls, t, over = cc.compare_values(op, val, s), np.zeros(val.shape, np.int8), "logical", False

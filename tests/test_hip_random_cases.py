@@ -2,7 +2,11 @@
 at the device level, eight seeds each, one seed one test.  Whatever a seed draws is compared -- nothing is filtered,
 skipped or retried -- against the generator's dense expectation: bits for subset, arith_cases.compare for Arith (ulps
 for log1p, expm1 and ^ with the measured MAX_ULPS of tests/test_hip_arith.py), tolerance 0 for medians, quantiles, MADs
-and ranks.  tests/test_random_cases_cpu.py validates generators and expectations without a GPU."""
+and ranks.  tests/test_random_cases_cpu.py validates generators and expectations without a GPU.
+
+tests/random_cases.py draws nine families; the five later ones -- Compare / Logic, sweep(), pmin / pmax and is*(),
+subassignment by N-index, the L-index and M-index -- run in tests/test_zzzzzzzzzzz_random_cases_hip.py, which stands
+last in the suite's order."""
 import numpy as np
 import pytest
 

@@ -3,7 +3,11 @@ offers the operation (subset, medians, quantiles, MADs, ranks) -- generator and 
 an independent implementation -- and, for Arith / Math, which the oracle session does not offer, the structural claims of
 the generator: pairs straddle a tile boundary, the weakest comparison class stays rare, every result type occurs.
 
-The 40 000-row operands of the order statistics are run here as well (two columns each: a second or two in all)."""
+The 40 000-row operands of the order statistics are run here as well (two columns each: a second or two in all).
+
+tests/random_cases.py draws nine families; the five later ones -- Compare / Logic, sweep(), pmin / pmax and is*(),
+subassignment by N-index, the L-index and M-index -- have their twin in tests/test_zzzzzzzzzzz_random_cases_cpu.py, which
+stands last in the suite's order."""
 import numpy as np
 import pytest
 
