@@ -1370,6 +1370,65 @@ int svt_dev_from_dense(const void *x, int x_Rtype, int64_t nrow, int64_t nleaves
 int svt_dev_to_dense(const svt_dev_csc *A, int na_background, int out_Rtype, void *out, int *bad, void *stream);
 int svt_dev_nzwhich(const svt_dev_csc *A, int ndim, const int64_t *dim, int arr_ind, void *out, void *stream);
 
+/* Random count arrays: poissonSparseArray(dim, lambda) and simple_rpois(n, lambda) (C_poissonSparseArray and
+   C_simple_rpois, src/randomSparseArray.c; kernels_coerce.hip).  Every cell of the array is drawn from Poisson(lambda)
+   and the nonzeros are kept, as an integer operand.  On the device this is the compaction of svt_dev_from_dense_* with a
+   generated cell in place of a loaded one: the same masks, tile bases, publish pass and workspace; the array of the
+   cells never exists.  The rules are stated once, in sparsearray_amd/csrc/svt_random_rules.h.
+
+     generator  Philox4x32-10 (Salmon et al., SC 2011).  cell = leaf * nrow + row, in 64 bits, counted in the WHOLE
+            array; block = cell >> 1; counter = (lo32(block), hi32(block), 0, 0); key = (lo32(seed), hi32(seed)).  The
+            even cell of a block takes the output words (w0, w1), the odd cell (w2, w3); x = w_hi << 32 | w_lo and
+            u = (x >> 11) * 2^-53, in [0, 1).  Counter words 2 and 3 are reserved.
+     value  find_interval of the reference: the first k with u < ticks[k], or the number of ticks when there is none.
+     ticks  compute_cumsum_dpois of the reference, on the host in long double: at most 32 doubles, the cumulated
+            probabilities, ascending.  Their NUMBER is the reference's for every lambda (its stopping rule on its own
+            arithmetic, a double exp() and double quotients lambda / n: 18 ticks at lambda = 1, 31 at 4); their VALUES
+            come from the same sum with both in long double, the true CDF rounded once, where the reference's own are
+            up to 2 ulp off.  svt_poisson_ticks writes them to ticks32 (32 doubles; may be NULL) and returns their number:
+            0 when every cell is 0 (lambda == 0, or exp(-lambda) rounds to 1); -1 when lambda is negative, NaN or
+            infinite or when 32 ticks are not enough ("'lambda' too big?": every lambda of 4.5 and above, none up to 4).
+            Needs no GPU.  The kernels get the table by value and call no exp.
+     seed   `seed` carries the 64 bits of an unsigned seed (0 .. 2^64 - 1; a seed of 2^63 and above arrives as the
+            negative int64_t of the same bits).  It stands in for R's global RNG state; R's streams are not reproduced.
+
+   A cell is a pure function of (seed, cell), so the array does not depend on the tiling or the grid, two runs give the
+   same bits, and `first_leaf` makes a call produce the leaves [first_leaf, first_leaf + nleaves) of a larger array of
+   nrow rows: the windows of an array bound with svt_dev_abind ARE the array.
+
+   The contract is that of svt_dev_from_dense_*.  svt_dev_poisson_count writes out_col_ptr int64[nleaves + 1] and
+   *out_nnz and synchronises `stream` once; svt_dev_poisson_fill is asynchronous, takes the same operands, reads the
+   workspace as the count call left it and writes out_row_idx int32[*out_nnz] and out_val int32[*out_nnz] (the value is
+   made again only where the mask has a bit).  Every position is a 64-bit prefix sum and none is decided by an atomic.
+   Status < 0, answered on the host before anything is launched or written: nrow, first_leaf or nleaves < 0, nrow >
+   2^31 - 1, (first_leaf + nleaves) * nrow past int64, a workspace below svt_dev_poisson_ws_bytes(nrow * nleaves), a
+   lambda for which svt_poisson_ticks answers -1.  Allowed, and never a launch over an empty range: nrow == 0 and
+   nleaves == 0, as for svt_dev_from_dense_count.  svt_dev_poisson is the composition over the allocator of
+   svt_dev_subset().  svt_dev_rpois writes out[i] = the value of cell first + i, i < n, int32: the dense form, asynchronous,
+   no workspace; < 0 for n < 0 ("'n' cannot be negative"), first < 0, first + n past int64, a bad lambda.
+
+   Host level.  svt_poissonSparseArray_begin runs svt_dev_poisson with first_leaf = 0 on the first device of the list
+   (not sharded) and leaves the result on the device: *out_nnz is its nonzero count, its type is integer.  The existing
+   svt_Arith_SVT_end copies it out and releases it.  svt_simple_rpois writes out[n] on the host.
+
+   Not offered: randomSparseArray() (exactly floor(n * density) positions without replacement is a selection over all
+   cells), a lambda per row or per column, a lambda above what 32 ticks resolve, sharding over the device list, an entry
+   in the R glue. */
+int svt_poisson_ticks(double lambda, double *ticks32);
+size_t svt_dev_poisson_ws_bytes(int64_t ncells);
+int svt_dev_poisson_count(double lambda, int64_t seed, int64_t nrow, int64_t first_leaf, int64_t nleaves, int64_t *out_col_ptr,
+			  int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream);
+int svt_dev_poisson_fill(double lambda, int64_t seed, int64_t nrow, int64_t first_leaf, int64_t nleaves,
+			 const int64_t *out_col_ptr, int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes,
+			 void *stream);
+int svt_dev_poisson(double lambda, int64_t seed, int64_t nrow, int64_t first_leaf, int64_t nleaves, svt_dev_alloc_fn alloc,
+		    svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr, int32_t **out_row_idx,
+		    void **out_val, void *stream);
+int svt_dev_rpois(double lambda, int64_t seed, int64_t first, int64_t n, int32_t *out, void *stream);
+int svt_poissonSparseArray_begin(int64_t nrow, int64_t nleaves, double lambda, int64_t seed, svt_arith_result **res,
+				 int64_t *out_nnz);
+int svt_simple_rpois(int64_t n, double lambda, int64_t seed, int32_t *out);
+
 /* Subassignment x[i, j, ...] <- value by an N-index (.subassign_SVT_by_Nindex, R/SparseArray-subassignment.R:114-170;
    C_subassign_SVT_with_short_Rvector, src/SparseArray_subassignment.c:1005-1230): the result is a new operand in the
    device layout with x's extents.  Its type is the wider of x's and the value's, logical < integer < double; a value

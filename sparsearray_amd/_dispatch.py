@@ -597,6 +597,31 @@ class CAbiDispatcher:
         _, buf = self._index_buffer(M.reshape(-1, order="F"), np.int32)
         return self._assigned("subassign_SVT_by_Mindex_begin", x, (buf, int(M.shape[0])) + self._assigned_value(value))
 
+    # poissonSparseArray() / simple_rpois() (src/randomSparseArray.c; include/svt_hip.h; HIP library only): begin leaves
+    # the array on the device, Arith_SVT_end copies it out; ``seed`` in [0, 2^64) goes over as the int64 of its bits ----
+    @staticmethod
+    def _seed_bits(seed: int) -> int:
+        return seed - 2 ** 64 if seed >= 2 ** 63 else seed
+
+    def C_poissonSparseArray(self, dim, lambda_: float, seed: int):
+        """The "integer" SVT_SparseArray of ``dim`` (a tuple of ints), no dimnames."""
+        nleaves = int(np.prod(dim[1:], dtype=object)) if len(dim) > 1 else 1
+        res, nnz = c_void_p(0), ctypes.c_int64(0)
+        if nleaves >= 2 ** 63:
+            raise SparseArrayError("the array has more than 2^63 - 1 leaves")
+        self._run("poissonSparseArray_begin", int(dim[0]), nleaves, float(lambda_), self._seed_bits(seed), byref(res), byref(nnz))
+        n = int(nnz.value)
+        cp = np.zeros(nleaves + 1, dtype=np.int64)
+        ri = np.zeros(max(n, 1), dtype=np.int32)
+        vv = np.zeros(max(n, 1), dtype=np.int32)
+        self._run("Arith_SVT_end", res, cp, ri, vv)
+        return SVT_SparseArray.from_csc(tuple(dim), "integer", cp, ri[:n], vv[:n])
+
+    def C_simple_rpois(self, n: int, lambda_: float, seed: int):
+        out = np.zeros(max(int(n), 1), dtype=np.int32)
+        self._run("simple_rpois", int(n), float(lambda_), self._seed_bits(seed), out)
+        return out[:int(n)]
+
     def C_rowsum_dgCMatrix(self, x, group, ngroup, na_rm):
         """``x`` = ((nrow, ncol), p, i, x) -- the dgCMatrix slots."""
         return self._dgc("rowsum_dgCMatrix", x, group, ngroup, na_rm,

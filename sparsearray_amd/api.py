@@ -15,6 +15,7 @@ as ``src/R_init_SparseArray.c:94,121-134``:
     C_Compare_SVT1_v2     C_Compare_SVT1_SVT2   C_Logic_SVT1_SVT2      (HIP library only)
     C_abind_SVT_SparseArray_objects                                      (HIP library only)
     C_subassign_SVT_with_short_Rvector  C_subassign_SVT_with_SVT         (HIP library only)
+    C_poissonSparseArray  C_simple_rpois (with a seed in place of R's RNG state) (HIP library only)
 
 and the entry points the HIP library adds to them (include/svt_hip.h):
 
@@ -103,6 +104,52 @@ def _check_not_NaArray(what: str, x):
 def _check_flag(name: str, value):
     if not isinstance(value, (bool, np.bool_)):
         raise SparseArrayError(f"'{name}' must be TRUE or FALSE")
+
+
+def _is_single_number(v) -> bool:
+    # isSingleNumber(): one numeric value that is not NA (a logical is not numeric)
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and not np.isnan(v)
+
+
+def normarg_dim(dim) -> tuple:
+    """``dim`` as a tuple of ints: a non-empty vector of non-negative integers up to 2^31 - 1.  "'dim' must be an integer
+    vector" is the reference's message (S4Arrays:::normarg_dim); the other two are this package's words."""
+    a = np.asarray(dim)
+    if a.ndim > 1 or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise SparseArrayError("'dim' must be an integer vector")
+    a = a.reshape(-1)
+    if a.size == 0:
+        raise SparseArrayError("'dim' must have at least one element")
+    if np.issubdtype(a.dtype, np.floating):
+        if np.isnan(a).any():
+            raise SparseArrayError("'dim' must contain non-negative integers <= 2^31 - 1, no NAs")
+        if (a != np.floor(a)).any():
+            raise SparseArrayError("'dim' must be an integer vector")
+    if (a < 0).any() or (a > 2 ** 31 - 1).any():
+        raise SparseArrayError("'dim' must contain non-negative integers <= 2^31 - 1, no NAs")
+    return tuple(int(d) for d in a)
+
+
+def poisson_lambda(lambda_, density) -> float:
+    """The lambda of poissonSparseArray(lambda=, density=) (R/randomSparseArray.R:67-76); None: not given."""
+    if lambda_ is not None and density is not None:
+        raise SparseArrayError("only one of 'lambda' and 'density' can be specified")
+    if lambda_ is not None:
+        if not _is_single_number(lambda_) or lambda_ < 0:
+            raise SparseArrayError("'lambda' must be a non-negative number")
+        return float(lambda_)
+    if density is not None:
+        if not _is_single_number(density) or density < 0 or density >= 1:
+            raise SparseArrayError("'density' must be a number >= 0 and < 1")
+        return -float(np.log(1.0 - float(density)))
+    return -float(np.log(0.95))
+
+
+def seed_word(seed) -> int:
+    """``seed`` checked: an integer in [0, 2^64) (this package's words; the reference has R's global RNG state)."""
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise SparseArrayError("'seed' must be an integer >= 0 and < 2^64")
+    return int(seed)
 
 
 def _check_crossprod_input_type(type_: str):
@@ -1659,6 +1706,46 @@ class Session:
 
     def colVars_dgCMatrix(self, x, na_rm=False):
         return self._dgc_colstat("C_colVars_dgCMatrix", x, na_rm)
+
+    # ------------------------------------------------------------------
+    # poissonSparseArray(), poissonSparseMatrix(), simple_rpois()  (R/randomSparseArray.R:55-81,150-162)
+    # ------------------------------------------------------------------
+    def poissonSparseArray(self, dim, lambda_=None, density=None, dimnames=None, seed=0):
+        """``poissonSparseArray(dim, lambda=-log(0.95), density=NA, dimnames=NULL)``: every cell drawn from
+        Poisson(lambda), the nonzeros kept, type "integer".  ``lambda_`` / ``density`` None: not given.  ``seed``, an
+        integer in [0, 2^64), stands in for R's global RNG state: the array is a function of (dim, lambda, seed)
+        (include/svt_hip.h); R's own streams are not reproduced."""
+        dim = normarg_dim(dim)
+        lam = poisson_lambda(lambda_, density)
+        seed = seed_word(seed)
+        if dimnames is not None:
+            dimnames = list(dimnames)
+            if len(dimnames) != len(dim) or any(n is not None and len(n) != d for n, d in zip(dimnames, dim)):
+                raise SparseArrayError("'dimnames' must be NULL or a list with one element per dimension, each NULL or of the "
+                                       "length of its dimension")
+        self._optional_entry("C_poissonSparseArray", "poissonSparseArray_begin")
+        ans = self.SparseArray_Call("C_poissonSparseArray", dim, lam, seed)
+        ans.dimnames = dimnames
+        return ans
+
+    def poissonSparseMatrix(self, nrow=1, ncol=1, lambda_=None, density=None, dimnames=None, seed=0):
+        if not (_is_single_number(nrow) and _is_single_number(ncol)):
+            raise SparseArrayError("'nrow' and 'ncol' must be single integers")
+        return self.poissonSparseArray((nrow, ncol), lambda_=lambda_, density=density, dimnames=dimnames, seed=seed)
+
+    def simple_rpois(self, n, lambda_, seed=0):
+        """``simple_rpois(n, lambda)``: the int32 vector of n draws, cell i of the stream of ``seed``."""
+        if not _is_single_number(n) or int(n) != n:
+            raise SparseArrayError("'n' must be a single integer")
+        if n < 0:
+            raise SparseArrayError("'n' cannot be negative")
+        if not _is_single_number(lambda_):
+            raise SparseArrayError("'lambda' must be a single numeric value")
+        if lambda_ < 0:
+            raise SparseArrayError("'lambda' cannot be negative")
+        seed = seed_word(seed)
+        self._optional_entry("C_simple_rpois", "simple_rpois")
+        return self.SparseArray_Call("C_simple_rpois", int(n), float(lambda_), seed)
 
 
 # ---------------------------------------------------------------------------

@@ -21,12 +21,22 @@
 // its first leaf.  The leaf of an entry: sub_last_le over the col_ptr of the leaves the tile touches, which are checked
 // first (ascending, inside [0, nnz]); a row outside [0, nrow) or a cell outside the tile is never used as an address.
 //
+// The compaction takes its cells from a SOURCE: value(c), the cell c of the call, and keep(v), whether it is stored.
+// DenseSource loads the cell from the array.  PoissonSource generates it (poissonSparseArray(), svt_random_rules.h): the
+// value of cell `first + c` of the whole array under the seed, so the count pass marks what the generator makes and the
+// fill pass makes the value again only where the bit is set -- no array of the cells ever exists.  A Philox block serves
+// the two cells 2b and 2b + 1.  poisson_mark_pairs_kernel, taken when `first` is even, computes every block once: a lane
+// makes the block of two neighbouring cells and the two ballots (even cells, odd cells) are dealt back into the mask words
+// of 64 consecutive cells by two more ballots.  With `first` odd the pairs straddle the tiles and the mark kernel of the
+// source computes a block per cell (profiles/poisson_timing.txt has both times).
+//
 // nzwhich: the tiles of svt_tile.h over the entries, like the copy of abind -- the leaves a tile touches by two binary
 // searches, one lane per leaf boundary inside the tile, the max-scan.
 #include <string.h>
 
 #include "svt_common.h"
 #include "svt_coerce_rules.h"
+#include "svt_random_rules.h"
 #include "svt_scan.h"
 #include "svt_tile.h"
 
@@ -65,10 +75,36 @@ __device__ inline int coerce_rank(const coerce_word *wb, const int *cpre, int o)
 // dense -> sparse
 // ---------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(SVT_TILE_NT) void from_dense_mark_kernel(const T *__restrict__ x, int64_t ncells, int64_t ntiles,
-									  int na_bg, coerce_word *__restrict__ bits,
-									  int64_t *__restrict__ cnt)
+struct DenseSource {
+	typedef T value_type;
+	const T *__restrict__ x;
+	int na_bg;
+	__device__ T value(int64_t c) const { return x[c]; }
+	__device__ bool keep(T v) const { return svt_rule_keep(v, na_bg != 0); }
+};
+struct PoissonSource {
+	typedef int32_t value_type;
+	svt_poisson_table table;
+	uint64_t seed, first;                   // cell c of the call is cell first + c of the array
+	__device__ int32_t value(int64_t c) const { return svt_rule_poisson_cell(seed, first + (uint64_t) c, table); }
+	__device__ bool keep(int32_t v) const { return v != 0; }
+};
+
+// a tile's count from those of its four wavefronts; ends with a barrier (wsum is written again by the next tile)
+__device__ inline void coerce_tile_count(int mine, int *wsum, int64_t *cnt, int64_t t)
 {
+	const int tid = threadIdx.x;
+	if ((tid & 63) == 0) wsum[tid >> 6] = mine;
+	__syncthreads();
+	if (tid == 0) cnt[t] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+	__syncthreads();
+}
+
+template <typename Source>
+__global__ __launch_bounds__(SVT_TILE_NT) void from_dense_mark_kernel(const Source src, int64_t ncells, int64_t ntiles,
+									  coerce_word *__restrict__ bits, int64_t *__restrict__ cnt)
+{
+	typedef typename Source::value_type T;
 	__shared__ int wsum[SVT_TILE_NT / SVT_WAVE];
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 	for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -77,20 +113,52 @@ __global__ __launch_bounds__(SVT_TILE_NT) void from_dense_mark_kernel(const T *_
 #pragma unroll
 		for (int it = 0; it < SVT_TILE_ITEMS; it++) {
 			const int64_t c = ts + it * SVT_TILE_NT + tid;
-			v[it] = c < ncells ? x[c] : (T) 0;
+			v[it] = c < ncells ? src.value(c) : (T) 0;
 		}
 		int mine = 0;
 #pragma unroll
 		for (int it = 0; it < SVT_TILE_ITEMS; it++) {
 			const int64_t c = ts + it * SVT_TILE_NT + tid;
-			const coerce_word m = __ballot(c < ncells && svt_rule_keep(v[it], na_bg != 0));
+			const coerce_word m = __ballot(c < ncells && src.keep(v[it]));
 			if (lane == 0) bits[(t << 6) + it * (SVT_TILE_NT / SVT_WAVE) + w] = m;
 			mine += __popcll(m);
 		}
-		if (lane == 0) wsum[w] = mine;
-		__syncthreads();
-		if (tid == 0) cnt[t] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-		__syncthreads();
+		coerce_tile_count(mine, wsum, cnt, t);
+	}
+	if (blockIdx.x == 0 && tid == 0) cnt[ntiles] = 0;       // the scan's total
+}
+
+// The mark pass of the Poisson source for an even `first`: trip j of wavefront w takes the 128 cells of the chunks 2k and
+// 2k + 1, k = j * 4 + w; lane l makes the block of the cells 128 k + 2 l and + 1.  The count pass asks value != 0 alone.
+__global__ __launch_bounds__(SVT_TILE_NT) void poisson_mark_pairs_kernel(const PoissonSource src, int64_t ncells, int64_t ntiles,
+									 coerce_word *__restrict__ bits, int64_t *__restrict__ cnt)
+{
+	__shared__ int wsum[SVT_TILE_NT / SVT_WAVE];
+	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const int half = lane >> 1, odd = lane & 1;
+	for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+		const int64_t ts = t << SVT_TILE_SHIFT;
+		int mine = 0;
+#pragma unroll 2
+		for (int j = 0; j < SVT_TILE_ITEMS / 2; j++) {
+			const int k = j * (SVT_TILE_NT / SVT_WAVE) + w;
+			const int64_t c = ts + k * (2 * SVT_WAVE) + 2 * lane;           // even, like src.first
+			bool k0 = false, k1 = false;
+			if (c < ncells) {
+				const svt_philox_words b = svt_rule_cell_block(src.seed, (src.first + (uint64_t) c) >> 1);
+				k0 = svt_rule_poisson_nonzero(svt_rule_block_uniform(b, 0), src.table);
+				k1 = c + 1 < ncells && svt_rule_poisson_nonzero(svt_rule_block_uniform(b, 1), src.table);
+			}
+			const coerce_word be = __ballot(k0), bo = __ballot(k1);
+			const coerce_word mix = odd ? bo : be;                          // cell 2 h + odd of the 128 is bit h of it
+			const coerce_word m0 = __ballot((mix >> half) & 1ULL), m1 = __ballot((mix >> (32 + half)) & 1ULL);
+			if (lane == 0) {
+				bits[(t << 6) + 2 * k] = m0;
+				bits[(t << 6) + 2 * k + 1] = m1;
+			}
+			mine += __popcll(m0) + __popcll(m1);
+		}
+		coerce_tile_count(mine, wsum, cnt, t);
 	}
 	if (blockIdx.x == 0 && tid == 0) cnt[ntiles] = 0;       // the scan's total
 }
@@ -124,8 +192,8 @@ __global__ __launch_bounds__(SVT_TILE_NT) void from_dense_publish_kernel(int64_t
 	}
 }
 
-template <typename TI, typename TO>
-__global__ __launch_bounds__(SVT_TILE_NT) void from_dense_fill_kernel(const TI *__restrict__ x, int64_t nrow, int64_t ntiles,
+template <typename Source, typename TO>
+__global__ __launch_bounds__(SVT_TILE_NT) void from_dense_fill_kernel(const Source src, int64_t nrow, int64_t ntiles,
 									  const coerce_word *__restrict__ bits,
 									  const int64_t *__restrict__ base,
 									  int32_t *__restrict__ out_row_idx, TO *__restrict__ out_val)
@@ -151,7 +219,7 @@ __global__ __launch_bounds__(SVT_TILE_NT) void from_dense_fill_kernel(const TI *
 			const uint32_t v = r0 + (uint32_t) o;       // < nrow + SVT_TILE <= 2^31 + 4095
 			out_row_idx[rank] = (int32_t) (one_wrap ? (v >= nr ? v - nr : v) : v % nr);
 			TO ov;
-			svt_rule_coerce(x[ts + o], &ov);
+			svt_rule_coerce(src.value(ts + o), &ov);
 			out_val[rank] = ov;
 		}
 		__syncthreads();
@@ -350,45 +418,103 @@ size_t from_dense_ws_bytes(int64_t ncells)
 	return coerce_ws(ncells).total;
 }
 
-int launch_from_dense_count(const FromDenseArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s)
+// The count pass of either source behind `mark(grid, block, bits, cnt)`, which launches the source's mark kernel: the
+// masks and the tile counts, the scan of the counts into the tile bases, out_col_ptr and the head from the masks.
+template <class Mark>
+static int coerce_count(int64_t nrow, int64_t nleaves, int64_t ncells, int64_t *out_col_ptr, void *ws, hipStream_t s, Mark mark)
 {
-	const CoerceWs L = coerce_ws(a.ncells);
+	const CoerceWs L = coerce_ws(ncells);
 	char *w = (char *) ws;
 	int64_t *base = (int64_t *) (w + L.base);
 	coerce_word *bits = (coerce_word *) (w + L.bits);
 	const dim3 grid(coerce_grid(L.ntiles, COERCE_GRID)), block(SVT_TILE_NT);
-	if (a.x_Rtype == SVT_REALSXP)
-		hipLaunchKernelGGL(from_dense_mark_kernel<double>, grid, block, 0, s, (const double *) a.x, a.ncells, L.ntiles,
-				   a.na_background, bits, base);
-	else
-		hipLaunchKernelGGL(from_dense_mark_kernel<int32_t>, grid, block, 0, s, (const int32_t *) a.x, a.ncells, L.ntiles,
-				   a.na_background, bits, base);
+	mark(grid, block, L.ntiles, bits, base);
 	if (launch_exclusive_scan_i64(base, L.ntiles + 1, w + L.scan, s))
 		return -1;
-	hipLaunchKernelGGL(from_dense_publish_kernel, grid, block, 0, s, a.nrow, a.nleaves, a.ncells, L.ntiles,
+	hipLaunchKernelGGL(from_dense_publish_kernel, grid, block, 0, s, nrow, nleaves, ncells, L.ntiles,
 			   (const coerce_word *) bits, (const int64_t *) base, out_col_ptr, (int64_t *) w);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
+template <typename Source, typename TO>
+static int coerce_fill(const Source &src, int64_t nrow, int64_t ncells, int32_t *out_row_idx, TO *out_val, const void *ws,
+		       hipStream_t s)
+{
+	if (ncells <= 0)
+		return 0;
+	const CoerceWs L = coerce_ws(ncells);
+	const char *w = (const char *) ws;
+	const dim3 grid(coerce_grid(L.ntiles, COERCE_GRID)), block(SVT_TILE_NT);
+	hipLaunchKernelGGL((from_dense_fill_kernel<Source, TO>), grid, block, 0, s, src, nrow, L.ntiles,
+			   (const coerce_word *) (w + L.bits), (const int64_t *) (w + L.base), out_row_idx, out_val);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int launch_from_dense_count(const FromDenseArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s)
+{
+	return coerce_count(a.nrow, a.nleaves, a.ncells, out_col_ptr, ws, s,
+		[&](dim3 grid, dim3 block, int64_t ntiles, coerce_word *bits, int64_t *cnt) {
+			if (a.x_Rtype == SVT_REALSXP)
+				hipLaunchKernelGGL(from_dense_mark_kernel<DenseSource<double>>, grid, block, 0, s,
+						   DenseSource<double>{ (const double *) a.x, a.na_background }, a.ncells, ntiles, bits, cnt);
+			else
+				hipLaunchKernelGGL(from_dense_mark_kernel<DenseSource<int32_t>>, grid, block, 0, s,
+						   DenseSource<int32_t>{ (const int32_t *) a.x, a.na_background }, a.ncells, ntiles, bits, cnt);
+		});
+}
 
 int launch_from_dense_fill(const FromDenseArgs &a, int32_t *out_row_idx, void *out_val, const void *ws, hipStream_t s)
 {
-	if (a.ncells <= 0)
-		return 0;
-	const CoerceWs L = coerce_ws(a.ncells);
-	const char *w = (const char *) ws;
-	const int64_t *base = (const int64_t *) (w + L.base);
-	const coerce_word *bits = (const coerce_word *) (w + L.bits);
-	const dim3 grid(coerce_grid(L.ntiles, COERCE_GRID)), block(SVT_TILE_NT);
 	if (a.x_Rtype == SVT_REALSXP)
-		hipLaunchKernelGGL((from_dense_fill_kernel<double, double>), grid, block, 0, s, (const double *) a.x, a.nrow, L.ntiles,
-				   bits, base, out_row_idx, (double *) out_val);
-	else if (a.ans_Rtype == SVT_REALSXP)
-		hipLaunchKernelGGL((from_dense_fill_kernel<int32_t, double>), grid, block, 0, s, (const int32_t *) a.x, a.nrow, L.ntiles,
-				   bits, base, out_row_idx, (double *) out_val);
-	else
-		hipLaunchKernelGGL((from_dense_fill_kernel<int32_t, int32_t>), grid, block, 0, s, (const int32_t *) a.x, a.nrow,
-				   L.ntiles, bits, base, out_row_idx, (int32_t *) out_val);
+		return coerce_fill(DenseSource<double>{ (const double *) a.x, a.na_background }, a.nrow, a.ncells, out_row_idx,
+				   (double *) out_val, ws, s);
+	const DenseSource<int32_t> src = { (const int32_t *) a.x, a.na_background };
+	if (a.ans_Rtype == SVT_REALSXP)
+		return coerce_fill(src, a.nrow, a.ncells, out_row_idx, (double *) out_val, ws, s);
+	return coerce_fill(src, a.nrow, a.ncells, out_row_idx, (int32_t *) out_val, ws, s);
+}
+
+// ---------------------------------------------------------------------------
+// generated cells: poissonSparseArray() through the same passes, simple_rpois() by a plain kernel
+// ---------------------------------------------------------------------------
+#define RPOIS_GRID 2048
+
+__global__ __launch_bounds__(SVT_TILE_NT) void rpois_kernel(const PoissonSource src, int64_t n, int32_t *__restrict__ out)
+{
+	for (int64_t i = (int64_t) blockIdx.x * SVT_TILE_NT + threadIdx.x; i < n; i += (int64_t) gridDim.x * SVT_TILE_NT)
+		out[i] = src.value(i);
+}
+
+static PoissonSource poisson_source(const PoissonArgs &a)
+{
+	return PoissonSource{ a.table, a.seed, (uint64_t) a.first_leaf * (uint64_t) a.nrow };
+}
+
+int launch_poisson_count(const PoissonArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s)
+{
+	const PoissonSource src = poisson_source(a);
+	return coerce_count(a.nrow, a.nleaves, a.ncells, out_col_ptr, ws, s,
+		[&](dim3 grid, dim3 block, int64_t ntiles, coerce_word *bits, int64_t *cnt) {
+			if ((src.first & 1) == 0)
+				hipLaunchKernelGGL(poisson_mark_pairs_kernel, grid, block, 0, s, src, a.ncells, ntiles, bits, cnt);
+			else
+				hipLaunchKernelGGL(from_dense_mark_kernel<PoissonSource>, grid, block, 0, s, src, a.ncells, ntiles, bits, cnt);
+		});
+}
+
+int launch_poisson_fill(const PoissonArgs &a, int32_t *out_row_idx, int32_t *out_val, const void *ws, hipStream_t s)
+{
+	return coerce_fill(poisson_source(a), a.nrow, a.ncells, out_row_idx, out_val, ws, s);
+}
+
+int launch_rpois(const svt_poisson_table &table, uint64_t seed, int64_t first, int64_t n, int32_t *out, hipStream_t s)
+{
+	if (n <= 0)
+		return 0;
+	const int64_t nb = (n + SVT_TILE_NT - 1) / SVT_TILE_NT;
+	hipLaunchKernelGGL(rpois_kernel, dim3((unsigned) (nb < RPOIS_GRID ? nb : RPOIS_GRID)), dim3(SVT_TILE_NT), 0, s,
+			   PoissonSource{ table, seed, (uint64_t) first }, n, out);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/svt_hip.h"
+#include "svt_random_rules.h"
 
 #define SVT_WAVE 64
 #define NA_INT (-2147483647 - 1)
@@ -447,6 +448,17 @@ int coerce_tile(void);
 size_t from_dense_ws_bytes(int64_t ncells);
 int launch_from_dense_count(const FromDenseArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
 int launch_from_dense_fill(const FromDenseArgs &a, int32_t *out_row_idx, void *out_val, const void *ws, hipStream_t s);
+// The same two launchers over generated cells (poissonSparseArray(); svt_random_rules.h): the leaves [first_leaf,
+// first_leaf + nleaves) of an integer array of nrow rows, ncells = nrow * nleaves > 0, the workspace that of
+// from_dense_ws_bytes(ncells).  launch_rpois: out[i] = the value of cell first + i, n > 0.
+struct PoissonArgs {
+	svt_poisson_table table;
+	uint64_t seed;
+	int64_t nrow, first_leaf, nleaves, ncells;
+};
+int launch_poisson_count(const PoissonArgs &a, int64_t *out_col_ptr, void *ws, hipStream_t s);
+int launch_poisson_fill(const PoissonArgs &a, int32_t *out_row_idx, int32_t *out_val, const void *ws, hipStream_t s);
+int launch_rpois(const svt_poisson_table &table, uint64_t seed, int64_t first, int64_t n, int32_t *out, hipStream_t s);
 int launch_to_dense(const int64_t *col_ptr, const int32_t *row_idx, const void *val, int Rtype, int64_t nrow, int64_t ncol,
 		    int64_t nnz, int na_background, int out_Rtype, void *out, int *bad, hipStream_t s);
 int launch_nzwhich(const int64_t *col_ptr, const int32_t *row_idx, int64_t nrow, int64_t ncol, int64_t nnz, int ndim,

@@ -2464,6 +2464,127 @@ extern "C" int svt_dev_from_dense(const void *x, int x_Rtype, int64_t nrow, int6
 	});
 }
 
+// ---- poissonSparseArray() and simple_rpois() (C_poissonSparseArray, C_simple_rpois, src/randomSparseArray.c): the
+// compaction of dense -> sparse over generated cells (kernels_coerce.hip, svt_random_rules.h) ----
+extern "C" int svt_poisson_ticks(double lambda, double *ticks32)
+{
+	double local[SVT_POISSON_MAX_TICKS];
+	return svt_rule_poisson_ticks(lambda, ticks32 != NULL ? ticks32 : local);
+}
+extern "C" size_t svt_dev_poisson_ws_bytes(int64_t ncells)
+{
+	return from_dense_ws_bytes(ncells);
+}
+static int poisson_table(const char *who, double lambda, svt_poisson_table *t)
+{
+	memset(t, 0, sizeof(*t));
+	if (!(lambda >= 0.0))
+		return svt_set_error("%s: 'lambda' must be a non-negative number", who);
+	t->n = svt_rule_poisson_ticks(lambda, t->ticks);
+	if (t->n < 0)
+		return svt_set_error("'lambda' too big?");
+	return 0;
+}
+
+// One call of the generator: every check that needs no GPU, then count / fill / their composition.
+struct PoissonCall {
+	const char *who;
+	PoissonArgs a;
+
+	int plan(double lambda, int64_t seed, int64_t nrow, int64_t first_leaf, int64_t nleaves)
+	{
+		memset(&a, 0, sizeof(a));
+		if (poisson_table(who, lambda, &a.table))
+			return -1;
+		if (nrow < 0 || nleaves < 0 || first_leaf < 0)
+			return svt_set_error("%s: negative extent", who);
+		if (nrow > 0x7FFFFFFFLL)
+			return svt_set_error("%s: more than 2^31 - 1 rows", who);
+		if (first_leaf > INT64_MAX - nleaves || (nrow > 0 && first_leaf + nleaves > INT64_MAX / nrow))
+			return svt_set_error("%s: (first_leaf + nleaves) * nrow overflows 64 bits", who);
+		a.seed = (uint64_t) seed;
+		a.nrow = nrow; a.first_leaf = first_leaf; a.nleaves = nleaves; a.ncells = nrow * nleaves;
+		return 0;
+	}
+	size_t need() const { return from_dense_ws_bytes(a.ncells); }
+
+	int count(int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		hipStream_t st = (hipStream_t) stream;
+		if (a.ncells == 0) {                                // no rows or no leaves: nothing to count, every pointer is 0
+			HIP_TRY(hipMemsetAsync(out_col_ptr, 0, ((size_t) a.nleaves + 1) * 8, st));
+			*out_nnz = 0;
+			return 0;
+		}
+		if (launch_poisson_count(a, out_col_ptr, ws, st))
+			return -1;
+		return WsHead::total_of(ws, st, out_nnz);
+	}
+	int fill(int32_t *out_row_idx, int32_t *out_val, const void *ws, size_t ws_bytes, void *stream)
+	{
+		if (ws_bytes < need())
+			return svt_set_error("%s: workspace too small", who);
+		return launch_poisson_fill(a, out_row_idx, out_val, ws, (hipStream_t) stream);
+	}
+	int compose(const ResultDest &to, void *stream)
+	{
+		if (need_allocator(who, to.alloc, to.release))
+			return -1;
+		return compose_result(who, to, SVT_INTSXP, 0, a.nrow, a.nleaves, need(),
+			[&](int64_t *col_ptr, int64_t *nnz, void *ws, size_t n) { return count(col_ptr, nnz, ws, n, stream); },
+			[&](const svt_dev_csc &R, const void *ws, size_t n) { return fill(R.row_idx, (int32_t *) R.val, ws, n, stream); });
+	}
+};
+
+extern "C" int svt_dev_poisson_count(double lambda, int64_t seed, int64_t nrow, int64_t first_leaf, int64_t nleaves,
+				     int64_t *out_col_ptr, int64_t *out_nnz, void *ws, size_t ws_bytes, void *stream)
+{
+	return abi_status([&] {
+		PoissonCall c = { "svt_dev_poisson_count" };
+		if (c.plan(lambda, seed, nrow, first_leaf, nleaves)) return -1;
+		return c.count(out_col_ptr, out_nnz, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_poisson_fill(double lambda, int64_t seed, int64_t nrow, int64_t first_leaf, int64_t nleaves,
+				    const int64_t *out_col_ptr, int32_t *out_row_idx, int32_t *out_val, const void *ws,
+				    size_t ws_bytes, void *stream)
+{
+	(void) out_col_ptr;                                 // (the tile bases in `ws` place the entries)
+	return abi_status([&] {
+		PoissonCall c = { "svt_dev_poisson_fill" };
+		if (c.plan(lambda, seed, nrow, first_leaf, nleaves)) return -1;
+		return c.fill(out_row_idx, out_val, ws, ws_bytes, stream);
+	});
+}
+extern "C" int svt_dev_poisson(double lambda, int64_t seed, int64_t nrow, int64_t first_leaf, int64_t nleaves,
+			       svt_dev_alloc_fn alloc, svt_dev_free_fn release, void *ctx, int64_t *out_nnz, int64_t **out_col_ptr,
+			       int32_t **out_row_idx, void **out_val, void *stream)
+{
+	return abi_status([&] {
+		PoissonCall c = { "svt_dev_poisson" };
+		if (c.plan(lambda, seed, nrow, first_leaf, nleaves)) return -1;
+		return c.compose({ alloc, release, ctx, out_nnz, out_col_ptr, out_row_idx, out_val }, stream);
+	});
+}
+extern "C" int svt_dev_rpois(double lambda, int64_t seed, int64_t first, int64_t n, int32_t *out, void *stream)
+{
+	const char *who = "svt_dev_rpois";
+	return abi_status([&] {
+		svt_poisson_table t;
+		if (poisson_table(who, lambda, &t))
+			return -1;
+		if (n < 0)
+			return svt_set_error("'n' cannot be negative");
+		if (first < 0 || first > INT64_MAX - n)
+			return svt_set_error("%s: 'first' is negative or first + n overflows 64 bits", who);
+		if (n > 0 && out == NULL)
+			return svt_set_error("%s: 'out' is NULL", who);
+		return launch_rpois(t, (uint64_t) seed, first, n, out, (hipStream_t) stream);
+	});
+}
+
 extern "C" int svt_dev_to_dense(const svt_dev_csc *A, int na_background, int out_Rtype, void *out, int *bad, void *stream)
 {
 	const char *who = "svt_dev_to_dense";
@@ -4861,6 +4982,43 @@ extern "C" int svt_abind_SVT_begin(const svt_view *const *objs, int nobj, int al
 {
 	return abi_status([&] { return abind_SVT_begin_impl(objs, nobj, along, ans_Rtype, res, out_nnz); });
 }
+// poissonSparseArray() and simple_rpois() for a host caller: nothing goes up; PoissonCall::compose() runs on the first
+// device and the result stays there until svt_Arith_SVT_end, the vector of simple_rpois comes down at once.
+extern "C" int svt_poissonSparseArray_begin(int64_t nrow, int64_t nleaves, double lambda, int64_t seed, svt_arith_result **res,
+					    int64_t *out_nnz)
+{
+	const char *who = "svt_poissonSparseArray_begin";
+	return abi_status([&] {
+		if (res == NULL || out_nnz == NULL)
+			return svt_set_error("%s: 'res' and 'out_nnz' are needed", who);
+		*res = NULL;
+		PoissonCall c = { who };
+		if (c.plan(lambda, seed, nrow, 0, nleaves) || ensure_init())
+			return -1;
+		return result_begin(who, SVT_INTSXP, 0, nrow, nleaves, [&](const ResultDest &to, int *) { return c.compose(to, NULL); },
+				    NULL, res, NULL, out_nnz, NULL);
+	});
+}
+extern "C" int svt_simple_rpois(int64_t n, double lambda, int64_t seed, int32_t *out)
+{
+	const char *who = "svt_simple_rpois";
+	return abi_status([&] {
+		svt_poisson_table t;
+		if (n < 0)
+			return svt_set_error("'n' cannot be negative");
+		if (poisson_table(who, lambda, &t))
+			return -1;
+		if (n == 0)
+			return 0;
+		if (out == NULL)
+			return svt_set_error("%s: 'out' is NULL", who);
+		DevBuf d;
+		if (ensure_init() || d.alloc((size_t) n * 4) || launch_rpois(t, (uint64_t) seed, 0, n, (int32_t *) d.p, NULL))
+			return -1;
+		return staged_download(out, d.p, (size_t) n * 4);
+	});
+}
+
 extern "C" int svt_Arith_SVT_end(svt_arith_result *res, int64_t *out_col_ptr, int32_t *out_row_idx, void *out_val)
 {
 	return abi_status([&] {

@@ -14,7 +14,7 @@ import torch
 
 from . import _hip
 from ._abi import ALLOC_FN, FREE_FN
-from .api import OPCODES, SparseArrayError, SparseArrayUnsupported
+from .api import OPCODES, SparseArrayError, SparseArrayUnsupported, normarg_dim, poisson_lambda, seed_word
 from .svt import INTSXP, LGLSXP, REALSXP
 
 
@@ -718,6 +718,53 @@ def coerce_tile() -> int:
     """Cells (dense <-> sparse) or entries (nzwhich) per workgroup tile of the coercion kernels (svt_dev_coerce_tile).
     Needs no GPU."""
     return int(_hip.load_library().svt_dev_coerce_tile())
+
+
+def _seed_bits(seed) -> int:
+    """``seed`` in [0, 2^64) as the int64 of the same bits, which is how the C ABI takes it"""
+    seed = seed_word(seed)
+    return seed - 2 ** 64 if seed >= 2 ** 63 else seed
+
+
+def poisson_ticks(lambda_: float):
+    """The table of cumulated Poisson probabilities behind poisson() and rpois() (svt_poisson_ticks): a float64 array of at
+    most 32 ticks, empty when every cell is 0; "'lambda' too big?" when 32 are not enough.  Needs no GPU."""
+    buf = (ctypes.c_double * 32)()
+    n = _hip.load_library().svt_poisson_ticks(float(lambda_), buf)
+    if n < 0:
+        raise SparseArrayError("'lambda' too big?" if lambda_ >= 0 else "'lambda' must be a non-negative number")
+    return np.array(buf[:n], dtype=np.float64)
+
+
+def poisson(dim, lambda_=None, density=None, seed=0, first_leaf=0, nleaves=None, device="cuda") -> DeviceCSC:
+    """poissonSparseArray(dim, lambda, density) made on the device (include/svt_hip.h, svt_dev_poisson): the integer
+    operand with nrow = dim[0] whose leaves are the prod(dim[1:]) leaves of the array, every cell drawn from
+    Poisson(lambda) and the nonzeros kept.  A cell is a function of (seed, its flat index in the whole array), so
+    ``first_leaf`` / ``nleaves`` give the window of leaves [first_leaf, first_leaf + nleaves) of the same array (default:
+    from first_leaf to the end): the windows, bound by cbind(), are the array.  ``seed``: an integer in [0, 2^64).  Every
+    array is a torch allocation on the current stream."""
+    dim = normarg_dim(dim)
+    lam = poisson_lambda(lambda_, density)
+    bits = _seed_bits(seed)
+    total = int(np.prod(dim[1:], dtype=object)) if len(dim) > 1 else 1
+    first_leaf = int(first_leaf)
+    nleaves = total - first_leaf if nleaves is None else int(nleaves)
+    if first_leaf < 0 or nleaves < 0 or first_leaf + nleaves > total:
+        raise SparseArrayError("the window of leaves is not inside the array")
+    return _composed(lambda *r: _lib().svt_dev_poisson(lam, bits, dim[0], first_leaf, nleaves, *r), torch.device(device), dim[0],
+                     nleaves, INTSXP)
+
+
+def rpois(n, lambda_, seed=0, first=0, device="cuda") -> torch.Tensor:
+    """simple_rpois(n, lambda) on the device (svt_dev_rpois): the int32 tensor of the cells [first, first + n) of the
+    stream of ``seed`` -- the dense form of poisson(): rpois(nrow * ncol) read column-major is the array."""
+    n = int(n)
+    if n < 0:
+        raise SparseArrayError("'n' cannot be negative")
+    lam = poisson_lambda(lambda_, None)
+    out = torch.empty(n, dtype=torch.int32, device=device)
+    _check(_lib().svt_dev_rpois(lam, _seed_bits(seed), int(first), n, out.data_ptr(), _stream()))
+    return out
 
 
 def abind_tile() -> int:
